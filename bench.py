@@ -1,6 +1,6 @@
 """bench.py -- animated frames/sec of the FDM diffusion-sampling hot path on N MI355X (one node).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dtype bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dtype bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A bench "step" = one full sampling call over this rank's batch of clips (cfg2: B = 4 clips x L = 200
@@ -10,22 +10,30 @@ value = (N * B * L * K) / elapsed = latent frames fully denoised per wall-second
 Weak scaling: every rank owns B clips (clip-level batch sharding); the only
 collective is the all-gather of the finished latents, inside the timed region.
 
-Default invocation (the line the driver records) carries three more things besides the headline leg (--dtype, default bf16 =
+A plain run (no --full) does only what the headline figure needs: set up, warm up, time the K steps, write the outputs of the
+last timed step (--dump-outputs DIR) and print the line.  --full adds, besides the headline leg (--dtype, default bf16 =
 BASELINE.json configs[1]):
   "f16_mode"       the same workload on single-plane fp16 operands (round 6): bf16's speed, ~8x closer to the reference
   "contract_mode"  the same workload timed in f16x3 -- the mode that meets north_star's 1e-4 tolerance on the 16-bit matrix
                    cores -- with its own HIP-event roofline and its own parity figure;
   "parity"         max-abs of the headline mode's plan against tests/golden/chains_vocaset.npz (outputs of the reference itself:
                    DDPM t = 9..0 and 999..990 with injected noise, DDIM 50), with the tolerance that mode states;
-  "rccl_ranks"     dist.get_world_size() when launched under torch.distributed.run (1 otherwise).
+  "cpu_baseline"   (below), the counter-derived roofline fields and "roofline_hbm" (from the committed profiles), the per-stage
+                   split and the sequential-loop comparison of the style-loop and shipped configurations, and the N > 1 shard check.
+"rccl_ranks" is dist.get_world_size() when launched under torch.distributed.run (1 otherwise).
 --config cfg1x8 is the reference sampler's style loop (samples/sample_diffusion_vocaset.py:71-83: 1 clip x 100 frames x 8 style
-one-hots, DDIM 100) as ONE condition-batched call, reported beside the sequential loop of eight B = 1 calls.
+one-hots, DDIM 100) as ONE condition-batched call, reported (--full) beside the sequential loop of eight B = 1 calls.
 
 --config shipped_vocaset | shipped_mead | shipped_biwi is what the reference's OWN callers issue for one test clip, end to end
 inside the timed call (samples/sample_diffusion_vocaset.py:71-88: 10 s of audio -> HuBERT-large -> every one of the 8 style
 one-hots, DDIM 100 -> quant -> decode; sample_diffusion_mead.py:67-86: HuBERT -> 1000-step DDPM -> EVQ quant -> decode;
-sample_diffusion_biwi.py:60-78: wav2vec2-base -> DDIM 50 -> quant -> decode to 23370 vertices), with a per-stage split
+sample_diffusion_biwi.py:60-78: wav2vec2-base -> DDIM 50 -> quant -> decode to 23370 vertices); --full adds a per-stage split
 ("stages_ms") and, for VOCASET, the reference's sequential loop of eight B = 1 pipelines beside the condition-batched call.
+
+--dump-outputs DIR: after the timed steps, what the last timed call returned to its caller (gathered over the ranks) is saved as
+DIR/latents.npy (the sampled latents) or DIR/vertices.npy (the end-to-end configurations' decoded meshes) in float32.  An output
+above 64 MB is saved as a fixed seeded sample of its elements, DIR/<name>.npy, with their flat indices in DIR/<name>_index.npy
+(float64).  Weights, inputs and noise are seeded, so two builds run with the same arguments can be compared output for output.
 
 roofline_hbm: the HBM-class kernels of the step (SURVEY.md section 8d "report both per kernel class"): the LayerNorm launches and the
 scheduler-fused latent decoder's epilogue traffic, algorithmic bytes / profiled duration (the committed rocprofv3 summary of this
@@ -198,6 +206,28 @@ def parity_vs_reference(plan, dev):
     return worst
 
 
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, name, out):
+    """Save the caller-visible output of the last timed call as out_dir/<name>.npy (float32, float64 kept).  Above the byte budget a
+    fixed seeded sample of the flat elements is saved instead, with their flat indices in out_dir/<name>_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = out.detach()
+    if out.dtype != torch.float64:
+        out = out.float()
+    flat = out.reshape(-1)
+    if flat.numel() * flat.element_size() <= DUMP_LIMIT - 4096:
+        np.save(os.path.join(out_dir, name + ".npy"), out.cpu().numpy())
+        return
+    n = (DUMP_LIMIT // 2) // (flat.element_size() + 8)              # values + float64 indices within half the budget
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), size=n, dtype=np.int64))      # sorted, fixed by the seed
+    vals = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, name + ".npy"), vals)
+    np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -207,8 +237,14 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f16x3", "f16"],
                     help="arithmetic mode: bf16 (throughput; BASELINE configs[1]), f32 (exact fp32 MFMA) and f16x3 (split-fp16 "
                          "operands, three 16-bit MFMA passes) meet the 1e-4 contract")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the contract-mode leg and the parity legs (sweeps, profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the contract-mode (f16x3) and f16 legs, parity against the reference's "
+                         "chains, the CPU baseline, counter-derived roofline fields, the per-stage split and sequential-loop comparisons, "
+                         "the N > 1 shard check")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed call returned as DIR/<name>.npy (float32; a seeded sample above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the contract-mode leg and the parity legs (sweeps, profiles)")
     ap.add_argument("--contract-steps", type=int, default=5, help="timed sampling calls of the contract-mode (f16x3) leg")
     ap.add_argument("--profile-steps", type=int, default=0, help="profiling only: shorten the diffusion chain to this many steps")
     ap.add_argument("--chain-steps", type=int, default=0, help="tests only: shorten the diffusion chain to this many steps, every stage of the call kept "
@@ -221,6 +257,9 @@ def main():
                     help="fdm_plan_set on every denoiser plan of the run before its tables are built, e.g. ksplit.out=2, fuse_ln3=1 (A/B measurements)")
     ap.add_argument("--dump", default="", help="tests only: rank 0 saves the gathered output of the last call to this .npy file")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = a.full and not a.profile_steps          # the measurements and checks beside the headline figure
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -387,7 +426,7 @@ def main():
                             "achieved": round(ach, 2), "peak": PEAK[dtype_name], "unit": "TFLOP/s",
                             "frac": round(ach / PEAK[dtype_name], 4), "traffic": None,
                             "flops_per_launch": fl, "avg_launch_ms": round(step_ms, 5)}}
-        if shipped and not a.profile_steps:
+        if extras and shipped:
             # per-stage split of the call (HIP events between the stages, three extra calls outside the timed region)
             acc = [0.0] * 5
             for _ in range(3):
@@ -403,7 +442,7 @@ def main():
             ach = fl / (step_ms * 1e-3) / 1e12
             leg["roofline"].update({"achieved": round(ach, 2), "frac": round(ach / PEAK[dtype_name], 4), "avg_launch_ms": round(step_ms, 5)})
             leg["diffusion_steps_per_s"] = round(n_live / (acc[2] * 1e-3), 1)
-        if shipped and S > 1 and not a.profile_steps:
+        if extras and shipped and S > 1:
             # the reference's loop as written (samples/sample_diffusion_vocaset.py:71-88): per style one-hot, one B = 1 pipeline --
             # audio encoder, tables, DDIM chain, quant, decode -- with the same audio
             st1 = [style[i:i + 1] for i in range(B * S)]
@@ -427,7 +466,7 @@ def main():
                                       "bit_identical_to_batched": bool(torch.equal(out_s, out))}
             leg["speedup_vs_sequential_loop"] = round(el_s / el, 3)
             prep()
-        elif S > 1 and not a.profile_steps:
+        elif extras and S > 1:
             # the reference's own loop: one B = 1 sampling call per style, same audio (tables rebuilt per call, as a caller that
             # loops ddim_sample does); same plan, same tiles policy, same timing harness
             st1 = [style[i:i + 1] for i in range(B * S)]
@@ -449,7 +488,7 @@ def main():
                                       "what": f"{S} sequential B = 1 calls per clip (samples/sample_diffusion_vocaset.py:71-83)",
                                       "bit_identical_to_batched": bool(torch.equal(out_s, out))}
             leg["speedup_vs_sequential_loop"] = round(el_s / el, 3)
-        if world > 1 and rank == 0 and not e2e and S == 1 and not a.profile_steps:
+        if extras and world > 1 and rank == 0 and not e2e and S == 1:
             # N > 1 self-check, outside the timed region: rank 0 recomputes the LAST rank's clips (same global clip indices, so the
             # same Philox streams) and compares them with what the collective delivered -- cross-rank determinism and the gather
             # order, verified on the hardware the line was measured on
@@ -465,17 +504,19 @@ def main():
             leg["parity_max_abs"] = parity_vs_reference(plan, dev)
         return leg, plan, out
 
-    head, plan, out = run_leg(a.dtype, a.steps, a.warmup, not a.headline_only and not a.profile_steps)
+    head, plan, out = run_leg(a.dtype, a.steps, a.warmup, extras and not a.headline_only)
     if a.dump and rank == 0:
         import numpy as np
         np.save(a.dump, out.float().cpu().numpy())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, "vertices" if e2e and not a.profile_steps else "latents", out)
     contract = None
-    if not a.headline_only and not a.profile_steps and a.dtype not in ("f32", "f16x3"):
+    if extras and not a.headline_only and a.dtype not in ("f32", "f16x3"):
         del plan
         contract, _, _ = run_leg("f16x3", a.contract_steps, a.warmup, True)
         contract["roofline"]["kernel"] = "denoiser step graph in the contract mode (split-fp16 operands, three 16-bit MFMA passes per product)"
     f16leg = None
-    if not a.headline_only and not a.profile_steps and a.dtype == "bf16" and world == 1:
+    if extras and not a.headline_only and a.dtype == "bf16" and world == 1:
         # the throughput mode's closer twin (round 6): single-plane fp16 operands -- bf16's bytes and MFMA rate, 11 significand bits --
         # timed and checked against the same reference chains, so the line shows what the headline's 8 bits cost beside what they buy
         f16leg, _, _ = run_leg("f16", a.contract_steps, a.warmup, True)
@@ -534,7 +575,8 @@ def main():
                     return
                 except (OSError, ValueError, KeyError):
                     continue
-        counters(head)
+        if a.full:
+            counters(head)
         res = {
             "metric": "animated frames/sec (1000-step DDPM, VOCASET FDM) at 1/2/4/8 MI355X",
             "value": head["value"], "unit": "frames/s",
@@ -579,7 +621,7 @@ def main():
                                "roofline_frac": f16leg["roofline"]["frac"], "gemm_tiles": f16leg["gemm_tiles"],
                                "parity_max_abs": f16leg.get("parity_max_abs"), "tolerance": PARITY_TOL["f16"], "within_1e-4_contract": False,
                                "what": "the same workload on single-plane fp16 operands (FDM_F16: the split kind's hi plane alone)"}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             # the bounded CPU sample is defined for the denoiser-only configs; cfg4/cfg5 reuse cfg2's shape class
             res["cpu_baseline"] = cpu_baseline(a.config if a.config in ("cfg1", "cfg2", "cfg3") else ("cfg1" if (a.config == "cfg1x8" or shipped) else "cfg2"))
         print(json.dumps(res), flush=True)

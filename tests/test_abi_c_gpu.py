@@ -80,7 +80,7 @@ def test_two_rank_bench_on_one_gpu_matches_single_process(tmp_path):
     port = s.getsockname()[1]
     s.close()
     bench = os.path.join(ROOT, "bench.py")
-    common = [sys.executable, bench, "--config", "cfg1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dtype", "f32"]
+    common = [sys.executable, bench, "--config", "cfg1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--dtype", "f32"]
     one = str(tmp_path / "one.npy")
     r = subprocess.run(common + ["--gpus", "1", "--batch", "2", "--dump", one], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -156,7 +156,7 @@ def test_bench_shipped_configs_print_a_complete_line(config):
     import json
     import sys
     bench = os.path.join(ROOT, "bench.py")
-    r = subprocess.run([sys.executable, bench, "--config", config, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--headline-only",
+    r = subprocess.run([sys.executable, bench, "--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--headline-only",
                         "--dtype", "f16x3"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -168,3 +168,37 @@ def test_bench_shipped_configs_print_a_complete_line(config):
     assert config in d["config"]["workload"] and d["value"] > 0 and 0 < d["roofline"]["frac"] < 1
     if config == "shipped_vocaset":
         assert d["sequential_loop"]["bit_identical_to_batched"] is True and d["speedup_vs_sequential_loop"] > 1.0
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps calls and prints the headline line without the --full legs;
+    --dump-outputs saves what the last timed call returned, bit-identical between two runs with the same arguments.  An output above
+    64 MB (cfg5's vertices at 4 clips: 120 MB) is saved as a seeded sample with its flat indices: those elements of the whole output."""
+    import json
+    import sys
+    import numpy as np
+    bench = os.path.join(ROOT, "bench.py")
+    common = [sys.executable, bench, "--config", "cfg1", "--chain-steps", "4", "--steps", "2", "--warmup", "1", "--dtype", "bf16", "--gpus", "1"]
+    for d in ("a", "b"):
+        r = subprocess.run(common + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "bf16" and rec["unit"] == "frames/s"
+        assert rec["higher_is_better"] is True and rec["value"] > 0 and rec["ms_per_step"] > 0
+        assert not {"parity", "contract_mode", "f16_mode", "cpu_baseline", "sequential_loop", "stages_ms", "roofline_hbm"} & set(rec)
+        assert sorted(os.listdir(tmp_path / d)) == ["latents.npy"]
+    a, b = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "b" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == b.shape and a.shape[0] == 1 and np.isfinite(a).all() and np.array_equal(a, b)
+    whole, d5 = str(tmp_path / "whole.npy"), tmp_path / "cfg5"
+    r = subprocess.run([sys.executable, bench, "--config", "cfg5", "--chain-steps", "2", "--batch", "4", "--steps", "1", "--warmup", "0",
+                        "--gpus", "1", "--dump", whole, "--dump-outputs", str(d5)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert sorted(os.listdir(d5)) == ["vertices.npy", "vertices_index.npy"]
+    assert sum(os.path.getsize(d5 / f) for f in os.listdir(d5)) <= 64 << 20
+    vals, idx = np.load(d5 / "vertices.npy"), np.load(d5 / "vertices_index.npy")
+    full = np.load(whole)
+    assert full.shape == (4, 498, 15069) and vals.dtype == np.float32 and idx.dtype == np.float64
+    assert vals.shape == idx.shape and len(idx) > 1_000_000 and np.all(np.diff(idx) > 0) and idx[-1] < full.size
+    assert np.array_equal(vals, full.reshape(-1)[idx.astype(np.int64)])

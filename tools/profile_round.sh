@@ -15,11 +15,11 @@ unset FDM_TILE_OVERRIDE FDM_TUNE
 cd "$GRAFT_REPO_ROOT"
 # the committed counter summaries must exist BEFORE the bench lines that quote them are taken
 for t in cfg2_bf16 cfg2_f16x3; do mkdir -p profiles/${R}_pmc_$t; cp gpurun_out/pmc_${R}_$t/summary.json gpurun_out/pmc_${R}_$t/summary.md profiles/${R}_pmc_$t/ 2>/dev/null; mkdir -p gpurun_out/profiles_${R}_pmc_$t; cp gpurun_out/pmc_${R}_$t/summary.* gpurun_out/profiles_${R}_pmc_$t/; done
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json; echo
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json; echo
 bash tools/bench_all.sh 2>&1 | tail -25
 for c in shipped_vocaset shipped_mead shipped_biwi cfg1x8; do
   for dt in bf16 f16x3; do
-    timeout 900 python bench.py --config $c --dtype $dt --headline-only --steps 3 --warmup 1 --no-cpu-baseline > $O/${c}_$dt.json 2> $O/${c}_$dt.err
+    timeout 900 python bench.py --config $c --dtype $dt --full --headline-only --steps 3 --warmup 1 --no-cpu-baseline > $O/${c}_$dt.json 2> $O/${c}_$dt.err
     python3 -c "import json; d=json.load(open('$O/${c}_$dt.json')); print('$c', d['dtype'], d['value'], d['ms_per_step'], d.get('stages_ms'), d.get('speedup_vs_sequential_loop'))" || tail -3 $O/${c}_$dt.err
   done
 done

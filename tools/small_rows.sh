@@ -13,7 +13,7 @@ for c in cfg1 shipped_mead shipped_biwi; do for m in bf16 f16x3; do
       single) o="";;
       single_fuse) o="--plan-set fuse_ln3=1";;
     esac
-    timeout 300 python bench.py --config $c --dtype $m --headline-only --no-cpu-baseline --steps 5 $o > $out/${c}_${m}_${v}_$rep.json 2> $out/${c}_${m}_${v}_$rep.err
+    timeout 300 python bench.py --config $c --dtype $m --full --headline-only --no-cpu-baseline --steps 5 $o > $out/${c}_${m}_${v}_$rep.json 2> $out/${c}_${m}_${v}_$rep.err
   done
 done; done
 done
