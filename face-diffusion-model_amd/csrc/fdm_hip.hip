@@ -12,6 +12,7 @@
 
 #include "../../include/fdm_hip.h"
 #include "elementwise.hpp"
+#include "window.hpp"
 #include "kernels.hpp"
 
 namespace fdm {
@@ -240,6 +241,21 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
   fdm_sched_args c = *a;
   return submit([c](hipStream_t s) { return fdm::sched_launch(c, s); }, stream, "sched");
 }
+
+}  // extern "C"
+
+// windowed sampling's blend + scheduler pass (window.hpp): not a public operator -- the plan layer records it into the step program
+// of a windowed plan (fdm_sample_windows)
+int fdm::window_sched_op(const fdm_sched_args& a, const fdm::WinArgs& w, void* stream) {
+  if (!a.x || !w.off || !w.ent || !w.xw || (!w.init && (!a.x0 || !a.x_out))) return fail(FDM_ERR_ARG, "window_sched: null operand");
+  if (a.n <= 0 || a.n % 4 || w.d % 4 || w.L_total < 1 || w.W < 1 || w.n_win < 1 || a.n % ((long long)w.L_total * w.d))
+    return fail(FDM_ERR_SHAPE, "window_sched: n=%lld is not a whole number of long clips of %d x %d", a.n, w.L_total, w.d);
+  fdm_sched_args c = a;
+  fdm::WinArgs ww = w;
+  return submit([c, ww](hipStream_t s) { return fdm::window_launch(c, ww, s); }, stream, "window_sched");
+}
+
+extern "C" {
 
 int fdm_op_cast(const float* src, void* dst, long long n, int dtype, void* stream) {
   if (!src || !dst || n <= 0) return fail(FDM_ERR_ARG, "cast: bad argument");

@@ -18,6 +18,21 @@ hipError_t attn_launch_f16(const fdm_attn_args& a, hipStream_t s);
 hipError_t pack_kv_launch_f32(const void* K, long long ldk, const void* V, long long ldv, void* Kp, void* Vp, int B, int H, int L, int Lpad, int hd, hipStream_t s);
 hipError_t pack_kv_launch_bf16(const void* K, long long ldk, const void* V, long long ldv, void* Kp, void* Vp, int B, int H, int L, int Lpad, int hd, hipStream_t s);
 
+// windowed sampling (window.hpp, plan.hip): frame f of a long clip is covered by the windows ent[off[f] .. off[f + 1]) in ascending
+// window order, each with its start frame and normalised blend weight; one table serves every long clip of the batch
+struct WinEnt { int w; int start; float wt; int pad; };
+struct WinArgs {
+  const int* off; const WinEnt* ent;
+  float* xw;          // the plan's fp32 x, window layout [B * n_win, W * d] (x0 / x0u / x_out_t of the sched args use the same rows)
+  int L_total;        // latent frames of a long clip
+  int n_win;          // windows per long clip (plan clip b * n_win + w)
+  int W;              // frames per window (= the plan's L)
+  int d;              // elements per latent frame (G * c)
+  int init;           // 1: no update -- copy the long buffer (x_T) into the window rows only
+};
+// fdm_hip.hip: records / launches window_sched_kernel like any fdm_op_* (p in long layout, see window.hpp)
+int window_sched_op(const fdm_sched_args& p, const WinArgs& w, void* stream);
+
 inline hipError_t gemm_launch(const fdm_gemm_args& a, hipStream_t s) {
   switch (a.dtype) {
     case FDM_BF16: return gemm_launch_bf16(a, s);

@@ -84,9 +84,61 @@ void alibi_slopes(int n, std::vector<double>& out) {       // get_slopes, models
   for (int i = 0; i < n - c; ++i) out.push_back(more[2 * i]);
 }
 
+// Windowed sampling layout (include/fdm_hip.h, fdm_window_layout_host): n windows of W' = min(W, L) frames over L latent frames,
+// neighbours overlapping by >= O frames.  L <= W: one window; otherwise n = ceil((L - O) / (W - O)), s_w = floor(w (L - W) / (n - 1)).
+int window_layout(int L, int W, int O, std::vector<int>& starts) {
+  if (W < 1 || O < 0 || O >= W) return fail(FDM_ERR_ARG, "window_layout: window %d, overlap %d (need 1 <= window, 0 <= overlap < window)", W, O);
+  if (L < 1) return fail(FDM_ERR_SHAPE, "window_layout: L_total = %d latent frames", L);
+  starts.clear();
+  if (L <= W) { starts.push_back(0); return 1; }
+  const int n = (int)(((long long)L - O + (W - O) - 1) / (W - O));
+  for (int w = 0; w < n; ++w) starts.push_back((int)((long long)w * (L - W) / (n - 1)));
+  return n;
+}
+// normalised blend weights [n, W'] of that layout: omega_w(f) = min(1, (f - s_w + 0.5) / O, (s_w + W' - f - 0.5) / O), no taper at
+// the long clip's first / last frame, O = 0 -> 1; w_hat = omega / (sum of omega over the windows covering f), in double, rounded once
+void window_weights(int L, int W, int O, const std::vector<int>& starts, std::vector<float>& out) {
+  const int n = (int)starts.size(), Wf = std::min(W, L);
+  std::vector<double> om((size_t)n * Wf), sum(L, 0.0);
+  for (int w = 0; w < n; ++w)
+    for (int i = 0; i < Wf; ++i) {
+      const int f = starts[w] + i;
+      double o = 1.0;
+      if (O > 0) {
+        if (starts[w] > 0) o = std::min(o, (i + 0.5) / O);
+        if (starts[w] + Wf < L) o = std::min(o, (Wf - i - 0.5) / O);
+      }
+      om[(size_t)w * Wf + i] = o;
+      sum[f] += o;
+    }
+  out.resize((size_t)n * Wf);
+  for (int w = 0; w < n; ++w)
+    for (int i = 0; i < Wf; ++i) out[(size_t)w * Wf + i] = (float)(om[(size_t)w * Wf + i] / sum[starts[w] + i]);
+}
+
 }  // namespace
 
 extern "C" {
+
+int fdm_window_layout_host(int L_total, int window, int overlap, int* starts, int cap) {
+  std::vector<int> st;
+  const int n = window_layout(L_total, window, overlap, st);
+  if (n < 0) return n;
+  if (starts && cap >= n) std::copy(st.begin(), st.end(), starts);
+  return n;
+}
+
+int fdm_window_weights_host(int L_total, int window, int overlap, float* w) {
+  std::vector<int> st;
+  const int n = window_layout(L_total, window, overlap, st);
+  if (n < 0) return n;
+  if (w) {
+    std::vector<float> wt;
+    window_weights(L_total, window, overlap, st, wt);
+    std::copy(wt.begin(), wt.end(), w);
+  }
+  return n;
+}
 
 int fdm_schedule_host(int T, float* out) {
   if (T <= 0 || !out) return fail(FDM_ERR_ARG, "schedule_host: bad argument");
@@ -245,6 +297,13 @@ struct fdm_plan {
   int lockstep = 0;                          // fdm_plan_set "lockstep": the lockstep k loop in every GEMM of the step (A/B against the loader-wave form; same bits)
   int tune_lazy = 0;                         // 1: fdm_sample_graph may tune in-call once a shape has run 2000 steps (opt-in)
   long long last_graph_launches = 0, launches_per_step = 0;
+  // ---- windowed sampling (fdm_audio_prepare_windows): win_B long clips of win_total latent frames run as the plan's B = win_B * win_n
+  // clips ("windows") of L = win_len frames; win_n == 0 = plain mode.  Plan-lifetime buffers, grown on demand (growing drops programs).
+  int win_n = 0, win_len = 0, win_total = 0, win_overlap = 0, win_B = 0;
+  float* xlong = nullptr; size_t xlong_cap = 0;             // x_t in long layout [win_B, win_total * d]
+  int* win_off = nullptr; size_t win_off_cap = 0;           // CSR of the covering windows per frame (fdm::WinArgs)
+  fdm::WinEnt* win_ent = nullptr; size_t win_ent_cap = 0;
+  float* win_stage = nullptr; size_t win_stage_cap = 0;     // gathered window audio rows + repeated one-hots (read by the prepare)
 };
 
 namespace {
@@ -686,10 +745,21 @@ std::string tiles_sig(const fdm_plan* P) {
   return s;
 }
 
+fdm::WinArgs win_args(const fdm_plan* P, int init) {
+  fdm::WinArgs w;
+  w.off = P->win_off; w.ent = P->win_ent; w.xw = P->x;
+  w.L_total = P->win_total; w.n_win = P->win_n; w.W = P->win_len; w.d = P->m.d; w.init = init;
+  return w;
+}
+
 int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
   char key[512];
   snprintf(key, sizeof(key), "%s#%s|%d|%p|%a|%p|%d", shape_key(P).c_str(), tiles_sig(P).c_str(), sp.kind, (const void*)sp.noise, (double)sp.cfg_scale,
            (const void*)sp.san, sp.reps);
+  if (P->win_n) {            // a windowed plan's programs end in the blend pass over its long layout (plain keys unchanged)
+    const size_t kl = strlen(key);
+    snprintf(key + kl, sizeof(key) - kl, "|win%d,%d,%d,%d,%d", P->win_B, P->win_total, P->win_n, P->win_len, P->win_overlap);
+  }
   auto it = P->progs.find(key);
   if (it != P->progs.end()) {            // hit: most recently used goes to the back, and the caller's handle stays valid for this call
     auto pos = std::find(P->prog_order.begin(), P->prog_order.end(), std::string(key));
@@ -730,6 +800,15 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       sc.noise = sp.noise; sc.noise_stride = n; sc.seed_dev = P->seedbuf;
     } else if (sp.kind == 2) {
       sc.mode = 1; sc.sra = P->sra; sc.srm1 = P->srm1; sc.sqrt_an = sp.san; sc.c_n = sp.cn;
+    }
+    if (sp.kind != 0 && P->win_n) {
+      // windowed plan: the chain unfused, then one pass over the long layout -- blend the windows' x0 (after their CFG mix), update
+      // each long-clip element once (noise keyed by the long clip), write back to the long buffer and every window holding the frame
+      const long long nl = (long long)P->win_B * P->win_total * d;
+      sc.x = P->xlong; sc.x_out = P->xlong; sc.n = nl; sc.n_per_clip = (long long)P->win_total * d; sc.noise_stride = nl;
+      rc = record_chain(P, nullptr, stream);
+      if (rc == FDM_OK) rc = fdm::window_sched_op(sc, win_args(P, 0), stream);
+      continue;
     }
     if (sp.kind != 0 && fuse_sched) {
       // non-CFG samplers: the update runs in the latent decoder GEMM's epilogue (bit-identical, one launch less)
@@ -787,6 +866,17 @@ int load_x(fdm_plan* P, const float* x, void* stream) {
     return fdm_op_sched_step(&sc, stream);
   }
   return FDM_OK;
+}
+
+// windowed plan: x_T in long layout -> the long buffer, then the window rows (+ their operand copy) through the window pass's store path
+int load_x_long(fdm_plan* P, const float* x, void* stream) {
+  const long long n = (long long)P->win_B * P->win_total * P->m.d;
+  HIPCK(hipMemcpyAsync(P->xlong, x, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  fdm_sched_args sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.mode = 2; sc.x = P->xlong; sc.n = n;
+  if (P->dtype != FDM_F32) { sc.x_out_t = P->xt.p; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo; }
+  return fdm::window_sched_op(sc, win_args(P, 1), stream);
 }
 
 int check_ready(const fdm_plan* P) {
@@ -1141,6 +1231,7 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   const fdm_model_desc& m = P->m;
   if (B0 < 1 || N < 1 || fw < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: bad feature shape [%d, %d, %d]", B0, N, fw);
   if (S < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: S=%d conditions per clip", S);
+  P->win_n = 0;                              // plain mode (fdm_audio_prepare_windows sets the window mode after this call)
   if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
   if (L < 1 || L > N / m.pair || L > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare: latent frames L=%d outside [1, min(%d, %d)] (models/fdm_vocaset.py:44,64-66)", L, N / m.pair, m.max_len);
   if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
@@ -1216,6 +1307,77 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   return FDM_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// a plan-lifetime device buffer of at least `bytes` (windowed sampling): growing drains the stream and drops the recorded programs
+int grow(fdm_plan* P, void** buf, size_t* cap, size_t bytes, void* stream) {
+  if (*buf && *cap >= bytes) return FDM_OK;
+  FCK(drop_programs(P, stream));
+  if (*buf) {
+    HIPCK(hipStreamSynchronize((hipStream_t)stream));
+    auto it = std::find(P->allocs.begin(), P->allocs.end(), *buf);
+    if (it != P->allocs.end()) P->allocs.erase(it);
+    (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+  }
+  FCK(dalloc(P, buf, bytes, false));
+  *cap = bytes;
+  return FDM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L_total,
+                              int window, int overlap, int cfg, void* stream) {
+  if (!P || !hub || !style) return fail(FDM_ERR_ARG, "audio_prepare_windows: null argument");
+  const fdm_model_desc& m = P->m;
+  P->win_n = 0;
+  if (B < 1 || N < 1 || fw < 1) return fail(FDM_ERR_SHAPE, "audio_prepare_windows: bad feature shape [%d, %d, %d]", B, N, fw);
+  if (window < 1 || window > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare_windows: window %d outside [1, max_len %d]", window, m.max_len);
+  if (overlap < 0 || overlap >= window) return fail(FDM_ERR_ARG, "audio_prepare_windows: overlap %d outside [0, window %d)", overlap, window);
+  if (L_total < 1 || L_total > N / m.pair) return fail(FDM_ERR_SHAPE, "audio_prepare_windows: L_total=%d outside [1, %d] (N / pair)", L_total, N / m.pair);
+  if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare_windows: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
+  if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare_windows: this model needs an emotion one-hot");
+  std::vector<int> starts;
+  const int n = window_layout(L_total, window, overlap, starts);
+  if (n < 0) return n;
+  const int W = std::min(window, L_total), Bw = B * n, d = m.d;
+  const size_t rows = (size_t)W * m.pair;                       // encoder frames per window
+  const size_t n_hub = (size_t)Bw * rows * fw, n_sty = (size_t)Bw * m.n_style, n_emo = m.n_emo ? (size_t)Bw * m.n_emo : 0;
+  hipStream_t s = (hipStream_t)stream;
+  FCK(grow(P, (void**)&P->win_stage, &P->win_stage_cap, (n_hub + n_sty + n_emo) * 4, stream));
+  FCK(grow(P, (void**)&P->xlong, &P->xlong_cap, (size_t)B * L_total * d * 4, stream));
+  // window w of long clip b = plan clip b * n + w: audio rows [s_w pair, (s_w + W) pair) of the clip, the clip's one-hots
+  float *hw = P->win_stage, *sw = hw + n_hub, *ew = sw + n_sty;
+  for (int b = 0; b < B; ++b)
+    for (int w = 0; w < n; ++w) {
+      const size_t k = (size_t)b * n + w;
+      HIPCK(hipMemcpyAsync(hw + k * rows * fw, hub + ((size_t)b * N + (size_t)starts[w] * m.pair) * fw, rows * fw * 4, hipMemcpyDefault, s));
+      HIPCK(hipMemcpyAsync(sw + k * m.n_style, style + (size_t)b * m.n_style, (size_t)m.n_style * 4, hipMemcpyDefault, s));
+      if (m.n_emo) HIPCK(hipMemcpyAsync(ew + k * m.n_emo, emo + (size_t)b * m.n_emo, (size_t)m.n_emo * 4, hipMemcpyDefault, s));
+    }
+  // covering windows per frame (ascending window order) with their normalised weights
+  std::vector<float> wt;
+  window_weights(L_total, window, overlap, starts, wt);
+  std::vector<int> off(1, 0);
+  std::vector<fdm::WinEnt> ent;
+  for (int f = 0; f < L_total; ++f) {
+    for (int w = 0; w < n; ++w)
+      if (starts[w] <= f && f < starts[w] + W) ent.push_back(fdm::WinEnt{w, starts[w], wt[(size_t)w * W + (f - starts[w])], 0});
+    off.push_back((int)ent.size());
+  }
+  FCK(grow(P, (void**)&P->win_off, &P->win_off_cap, off.size() * sizeof(int), stream));
+  FCK(grow(P, (void**)&P->win_ent, &P->win_ent_cap, ent.size() * sizeof(fdm::WinEnt), stream));
+  HIPCK(hipMemcpyAsync(P->win_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(P->win_ent, ent.data(), ent.size() * sizeof(fdm::WinEnt), hipMemcpyHostToDevice, s));
+  HIPCK(hipStreamSynchronize(s));            // (off / ent are host vectors of this call)
+  FCK(fdm_audio_prepare_conds(P, hw, Bw, (int)rows, fw, 1, sw, m.n_emo ? ew : nullptr, W, cfg, stream));
+  P->win_n = n; P->win_len = W; P->win_total = L_total; P->win_overlap = overlap; P->win_B = B;
+  return FDM_OK;
+}
+
 int fdm_denoise_step(fdm_plan* P, const float* x_t, int t, float cfg_scale, float* x0_hat, float* x0_uncond, void* stream) {
   FCK(check_ready(P));
   P->pinned.clear();
@@ -1232,8 +1394,11 @@ int fdm_denoise_step(fdm_plan* P, const float* x_t, int t, float cfg_scale, floa
   return FDM_OK;
 }
 
-int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
-  FCK(check_ready(P));
+}  // extern "C"
+
+namespace {
+// fdm_sample_graph (plain plan, x in plan layout) and fdm_sample_windows (windowed plan, x_T / out / noise / record in long layout)
+int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   P->pinned.clear();
   if (!a || !a->x_T || !a->out) return fail(FDM_ERR_ARG, "sample_graph: null argument");
   hipStream_t s = (hipStream_t)stream;
@@ -1270,7 +1435,9 @@ int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
     return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM)", a->kind);
   }
   const int n_steps = (int)ts.size();
-  const size_t nb = (size_t)P->M * P->m.d * 4;
+  const size_t nx = P->win_n ? (size_t)P->win_B * P->win_total * P->m.d : (size_t)P->M * P->m.d;     // elements of x in the caller's layout
+  const size_t nb = nx * 4;
+  float* xc = P->win_n ? P->xlong : P->x;
   P->last_graph_launches = 0;
   if (n_steps == 0) {        // e.g. ddim_steps = 1: only the dead pair
     if (a->out != a->x_T) HIPCK(hipMemcpyAsync(a->out, a->x_T, nb, hipMemcpyDeviceToDevice, s));
@@ -1278,7 +1445,7 @@ int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   }
   if (P->tune_lazy) tune_soft(P, stream);
   P->steps_seen[shape_key(P)] += n_steps;
-  FCK(load_x(P, a->x_T, stream));
+  FCK(P->win_n ? load_x_long(P, a->x_T, stream) : load_x(P, a->x_T, stream));
   FCK(set_steps(P, ts.data(), n_steps, stream));
   fdm_prog* p1 = nullptr;
   FCK(get_program(P, sp, stream, &p1));
@@ -1286,7 +1453,7 @@ int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
     for (int i = 0; i < n_steps; ++i) {
       if (a->eager) { FCK(fdm_prog_run(p1, stream)); }
       else { FCK(fdm_prog_instantiate(p1, stream)); FCK(fdm_prog_replay(p1, 1, stream)); ++P->last_graph_launches; }
-      if (a->record) HIPCK(hipMemcpyAsync(a->record + (size_t)i * P->M * P->m.d, P->x, nb, hipMemcpyDeviceToDevice, s));
+      if (a->record) HIPCK(hipMemcpyAsync(a->record + (size_t)i * nx, xc, nb, hipMemcpyDeviceToDevice, s));
     }
   } else {
     int K = a->graph_steps > 0 ? a->graph_steps : 10;
@@ -1307,8 +1474,23 @@ int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
       P->last_graph_launches += left;
     }
   }
-  HIPCK(hipMemcpyAsync(a->out, P->x, nb, hipMemcpyDeviceToDevice, s));
+  HIPCK(hipMemcpyAsync(a->out, xc, nb, hipMemcpyDeviceToDevice, s));
   return FDM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  FCK(check_ready(P));
+  if (P->win_n) return fail(FDM_ERR_STATE, "sample_graph: the plan was prepared for windowed sampling (fdm_sample_windows)");
+  return sample_impl(P, a, stream);
+}
+
+int fdm_sample_windows(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  FCK(check_ready(P));
+  if (!P->win_n) return fail(FDM_ERR_STATE, "sample_windows: call fdm_audio_prepare_windows first");
+  return sample_impl(P, a, stream);
 }
 
 int fdm_plan_tune(fdm_plan* P, void* stream) {
@@ -1328,6 +1510,9 @@ int fdm_plan_get(fdm_plan* P, const char* key, long long* out) {
   else if (k == "tuned") *out = P->tile_cache.count(shape_key(P)) ? 1 : 0;
   else if (k == "needs_tune") { const std::string sk = shape_key(P); *out = (!P->tile_cache.count(sk) && P->tune_enabled && P->steps_seen.count(sk) && P->steps_seen[sk] >= 2000 && !P->tune_failed_shapes.count(sk)) ? 1 : 0; }
   else if (k == "tune_failed") *out = P->tune_failed;
+  else if (k == "windows") *out = P->win_n;
+  else if (k == "window_len") *out = P->win_n ? P->win_len : P->L;
+  else if (k == "L_total") *out = P->win_n ? P->win_total : P->L;
   else if (k.rfind("tile.", 0) == 0) { auto it = P->tiles.find(k.substr(5)); *out = it == P->tiles.end() ? 0 : it->second; }
   else return fail(FDM_ERR_ARG, "plan_get: unknown key '%s'", key);
   return FDM_OK;

@@ -1,0 +1,70 @@
+// Windowed sampling of clips longer than the denoiser's max_len (fdm_audio_prepare_windows / fdm_sample_windows): one pass over
+// the LONG layout [B, L_total * d] per diffusion step that blends the overlapping windows' x0 predictions, applies the scheduler
+// update once per long-clip element (sched_update4: the same bits and the same Philox stream as sched_kernel) and writes the
+// result back to the long buffer and to every window row that holds the frame (fp32 x + the operand-kind copy of the next step).
+#pragma once
+#include "common.hpp"
+#include "sched.hpp"
+#include "../../include/fdm_hip.h"
+#include "kernels.hpp"
+
+namespace fdm {
+
+// p: the scheduler arguments in LONG layout (x = x_out = the long buffer, n = B * L_total * d, n_per_clip = L_total * d, noise
+// [steps, B, L_total * d]); p.x0 / p.x0u / p.x_out_t are the plan's window-layout buffers.  Vector loads and stores only.
+__global__ __launch_bounds__(256) void window_sched_kernel(const fdm_sched_args p, const WinArgs w) {
+  const SchedCoef c = sched_coef_load(p);
+  const long long nq = p.n / 4, per_clip = (long long)w.L_total * w.d, wrows = (long long)w.W * w.d;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
+    const long long e = 4 * i;
+    const int b = (int)(e / per_clip);
+    const long long r = e - (long long)b * per_clip;
+    const int f = (int)(r / w.d);
+    const long long col = r - (long long)f * w.d;
+    const int j0 = w.off[f], j1 = w.off[f + 1];
+    const long long base = (long long)b * w.n_win * wrows + (long long)f * w.d + col;     // + window * wrows - start * d
+    f32x4 o;
+    if (w.init) {
+      o = *(const f32x4*)(p.x + e);
+    } else {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = j0; j < j1; ++j) {
+        const WinEnt en = w.ent[j];
+        const long long q = base + (long long)en.w * wrows - (long long)en.start * w.d;
+        f32x4 x0 = *(const f32x4*)(p.x0 + q);
+        if (p.x0u) {      // CFG mix per window, before the blend (utiles/classifierfree.py:20-21; sched_kernel's expression)
+          const f32x4 u = *(const f32x4*)(p.x0u + q);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) x0[k] = __fadd_rn(u[k], __fmul_rn(p.cfg_scale, __fsub_rn(x0[k], u[k])));
+        }
+        // ascending window order, the first term starts the sum (one window: weight 1, x0 passes through bit for bit, -0 included)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = j == j0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
+      }
+      const f32x4 x = *(const f32x4*)(p.x + e);
+      o = sched_update4(p, c, acc, x, e);
+      *(f32x4*)(p.x_out + e) = o;
+    }
+    for (int j = j0; j < j1; ++j) {
+      const WinEnt en = w.ent[j];
+      const long long q = base + (long long)en.w * wrows - (long long)en.start * w.d;
+      *(f32x4*)(w.xw + q) = o;
+      if (p.x_out_t) {
+        if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + q, 0, o);
+        else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + q, p.x_out_t_lo_off, o);
+        else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + q, 0, o);
+      }
+    }
+  }
+}
+
+static hipError_t window_launch(const fdm_sched_args& a, const WinArgs& w, hipStream_t s) {
+  const long long nq = a.n / 4;
+  int blocks = (int)((nq + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(window_sched_kernel, dim3(blocks), dim3(256), 0, s, a, w);
+  return hipGetLastError();
+}
+
+}  // namespace fdm

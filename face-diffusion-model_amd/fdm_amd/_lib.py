@@ -123,6 +123,10 @@ SYMBOLS = {
     "fdm_audio_prepare_conds": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
     "fdm_denoise_step": (ci, [vp, vp, ci, cf, vp, vp, vp]),
     "fdm_sample_graph": (ci, [vp, C.POINTER(SampleArgs), vp]),
+    "fdm_window_layout_host": (ci, [ci, ci, ci, vp, ci]),
+    "fdm_window_weights_host": (ci, [ci, ci, ci, vp]),
+    "fdm_audio_prepare_windows": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+    "fdm_sample_windows": (ci, [vp, C.POINTER(SampleArgs), vp]),
     "fdm_plan_tune": (ci, [vp, vp]),
     "fdm_plan_get": (ci, [vp, C.c_char_p, C.POINTER(ll)]),
     "fdm_plan_set": (ci, [vp, C.c_char_p, ll]),

@@ -38,6 +38,26 @@ def model_desc(p):
                      1 if p.pe == "periodic" else 0, p.period, int(p.latent_mish), int(p.style_mish), p.max_len)
 
 
+def window_starts(L_total, window, overlap=60):
+    """Window starts of the windowed-sampling layout (fdm_window_layout_host; include/fdm_hip.h states the rule)."""
+    n = lib().fdm_window_layout_host(int(L_total), int(window), int(overlap), None, 0)
+    if n < 0:
+        check(n)
+    buf = (C.c_int * n)()
+    check(0 if lib().fdm_window_layout_host(int(L_total), int(window), int(overlap), buf, n) == n else -1)
+    return list(buf)
+
+
+def window_weights(L_total, window, overlap=60):
+    """Normalised blend weights [n, min(window, L_total)] of that layout (fdm_window_weights_host), a float32 CPU tensor."""
+    n = lib().fdm_window_weights_host(int(L_total), int(window), int(overlap), None)
+    if n < 0:
+        check(n)
+    w = torch.empty(n, min(int(window), int(L_total)), dtype=torch.float32)
+    check(0 if lib().fdm_window_weights_host(int(L_total), int(window), int(overlap), C.c_void_p(w.data_ptr())) == n else -1)
+    return w
+
+
 class DenoiserPlan:
     def __init__(self, preset, weights, dtype=F32, device="cuda:0"):
         self.p = presets.get(preset)
@@ -182,6 +202,77 @@ class DenoiserPlan:
         out = self._sample(a, x_T)
         if rec is not None:
             record.extend(rec[i] for i in range(n_live))
+        return out
+
+    # ------------------------------------------------------------------------------------------
+    def prepare_windows(self, hub, style, emo=None, L_total=None, window=None, overlap=60, cfg=False):
+        """Clips longer than max_len (fdm_audio_prepare_windows): hub [B, N, fw] features of B whole long clips, style [B, n_style],
+        emo [B, n_emo]; L_total latent frames (default N // pair, no cap) as windows of `window` (default max_len) frames overlapping
+        by >= `overlap`.  The plan's batch becomes B * n windows; sample_windows takes and returns latents in the long layout
+        [B, L_total*G, c].  Returns the window starts (window_starts())."""
+        p, dv = self.p, self.device
+        hub = _dev(hub, dv)
+        B, N, fw = hub.shape
+        L_total = N // p.pair if L_total is None else int(L_total)
+        window = p.max_len if window is None else int(window)
+        starts = window_starts(L_total, window, overlap)
+        if style.dim() == 1:
+            style = style.unsqueeze(0).expand(B, -1)
+        style = _dev(style, dv)
+        if p.n_emo:
+            if emo is None:
+                raise FdmError("this preset needs an emotion one-hot")
+            emo = _dev(emo.unsqueeze(0).expand(B, -1) if emo.dim() == 1 else emo, dv)
+        if style.shape[0] != B or (p.n_emo and emo.shape[0] != B):
+            raise FdmError(f"one style / emotion row per long clip expected ({B})")
+        with torch.cuda.device(dv):
+            check(lib().fdm_audio_prepare_windows(self.h, hub.data_ptr(), B, N, fw, style.data_ptr(),
+                                                  emo.data_ptr() if p.n_emo else None, L_total, window, int(overlap),
+                                                  int(bool(cfg)), _stream()))
+        self._inputs = (hub, style, emo)
+        W = min(window, L_total)
+        self.B, self.L, self.M, self.cfg, self.S = B * len(starts), W, B * len(starts) * W, bool(cfg), 1
+        self.B_long, self.L_total, self.starts = B, L_total, starts
+        return starts
+
+    def sample_windows(self, x_T, kind="ddpm", t_list=None, steps=None, noise=None, seed=0, clip0=0, cfg_scale=2.5, record=None,
+                       use_graph=True, graph_steps=0):
+        """fdm_sample_windows: x_T [B, L_total*G, c] -> [B, L_total*G, c].  kind "ddpm" over t_list (noise [len(t_list), B,
+        L_total*G, c] injected, or Philox keyed by (seed, clip0 + long clip, step)) or "ddim" with `steps`.  record (a list) receives
+        the long latent after every step."""
+        if not self.get("windows"):
+            raise FdmError("call prepare_windows() first")
+        shape = (self.B_long, self.L_total * self.p.G, self.p.c)
+        if tuple(x_T.shape) != shape:
+            raise FdmError(f"latent shape {tuple(x_T.shape)} != {shape}")
+        x = _dev(x_T, self.device)
+        a = SampleArgs()
+        a.cfg_scale, a.eager, a.graph_steps = float(cfg_scale), int(not use_graph), int(graph_steps)
+        if kind == "ddpm":
+            ts = (C.c_int * len(t_list))(*[int(t) for t in t_list])
+            a.kind, a.t_list, a.n_steps, a.seed, a.clip0 = 0, C.cast(ts, C.c_void_p), len(t_list), int(seed), int(clip0)
+            n_rec = len(t_list)
+            if noise is not None:
+                nz = _dev(noise, self.device)
+                if nz.numel() != len(t_list) * x.numel():
+                    raise FdmError("noise must be [len(t_list), B, L_total*G, c]")
+                self._keep = (self._keep + [nz])[-8:]
+                a.noise = nz.data_ptr()
+        elif kind == "ddim":
+            a.kind, a.ddim_steps = 1, int(steps)
+            n_rec = sum(1 for pr in schedule.ddim_time_pairs(int(steps)) if pr[1] >= 0)
+        else:
+            raise FdmError(f"kind {kind!r} (ddpm | ddim)")
+        rec = None
+        if record is not None:
+            rec = torch.empty(max(n_rec, 1), *shape, device=self.device)
+            a.record = rec.data_ptr()
+        out = torch.empty_like(x)
+        a.x_T, a.out = x.data_ptr(), out.data_ptr()
+        with torch.cuda.device(self.device):
+            check(lib().fdm_sample_windows(self.h, C.byref(a), _stream()))
+        if rec is not None:
+            record.extend(rec[i] for i in range(n_rec))
         return out
 
     # ------------------------------------------------------------------------------------------

@@ -203,6 +203,54 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     return verts, lats
 
 
+@torch.no_grad()
+def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
+                 window=None, overlap=60, device="cuda:0"):
+    """audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
+    encoder frames // pair (no 600-frame cap: animate() keeps the reference's crop).
+
+    The audio encoder runs once over each whole waveform; sampling runs on windows of `window` (default max_len) latent frames
+    overlapping by >= `overlap`, blended in x0 space at every diffusion step (include/fdm_hip.h, fdm_audio_prepare_windows /
+    fdm_sample_windows); the quantiser and the decoder then run on the whole clip.  One condition per clip (id_one_hot [B, n_style],
+    emotion_one_hot [B, n_emo]; defaults as animate()).  x_T is drawn per long clip from a CPU generator seeded with `seed` (as
+    animate() draws it) and the DDPM noise is Philox keyed by (seed, long clip, step), so with L_total <= window the result is
+    bit-identical to animate()'s.  DDIM (eta = 0) when ddim_steps, on every preset; classifier-free guidance when `diffusion`
+    wraps a ClassifierFreeSampleModel."""
+    cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
+    model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
+    scale = float(diffusion.denoise_fn.level) if cfg else 2.5
+    p = model.preset
+    audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
+    if audio.dim() == 1:
+        audio = audio.unsqueeze(0)
+    B = audio.shape[0]
+    style = (torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32))
+    style = style.reshape(-1, p.n_style).expand(B, -1) if style.reshape(-1, p.n_style).shape[0] == 1 else style.reshape(-1, p.n_style)
+    emo = None
+    if p.n_emo:
+        emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32)
+        emo = emo.reshape(-1, p.n_emo)
+        emo = (emo.expand(B, -1) if emo.shape[0] == 1 else emo).to(device)
+    style = style.to(device)
+    hub = model.audio_features(audio)
+    L_total = hub.shape[1] // p.pair
+    plan = model.plan(hub.device)
+    model._prep_key = None            # the plan leaves the state FDM.prepare() cached
+    plan.prepare_windows(hub, style, emo, L_total=L_total, window=window, overlap=overlap, cfg=cfg)
+    shape = (B, L_total * p.G, p.c)
+    x_T = torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
+    if ddim_steps:
+        latent = plan.sample_windows(x_T, "ddim", steps=ddim_steps, cfg_scale=scale)
+    else:
+        ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
+        latent = plan.sample_windows(x_T, "ddpm", t_list=ts, seed=seed, cfg_scale=scale)
+    quanted = autoencoder.quant(latent, emo, stats=False)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
+    out = autoencoder.decode(quanted)
+    if template is not None:
+        out = out + torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
+    return out, latent
+
+
 def demo_main(preset, argv=None):
     """CLI of demo/demo_{vocaset,biwi,3d_mead}.py:109-121: same flags, output = np.save(<audio_path>/<stem>.npy, [1, L, V3])."""
     import argparse
@@ -220,6 +268,9 @@ def demo_main(preset, argv=None):
     ap.add_argument("--audio_path", type=str, default=f"{p.name}/result")
     ap.add_argument("--ddim_steps", type=int, default=0, help="build-added: DDIM steps (0 = full DDPM chain)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--long_audio", type=str, default="truncate", choices=["truncate", "window"],
+                    help="build-added: audio past max_len latent frames: truncate (the reference's crop) or window (animate it all)")
+    ap.add_argument("--window_overlap", type=int, default=60, help="build-added: frames shared by neighbouring windows (--long_audio window)")
     a = ap.parse_args(argv)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
                                  cfg_level=None)
@@ -230,7 +281,11 @@ def demo_main(preset, argv=None):
     emo = None
     if p.n_emo:
         emo = torch.eye(p.n_emo)[EMOTIONS.index(a.emotion)].unsqueeze(0)
-    out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device)
+    if a.long_audio == "window":
+        out, _ = animate_long(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed,
+                              overlap=a.window_overlap, device=a.device)
+    else:
+        out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device)
     os.makedirs(a.audio_path, exist_ok=True)
     dst = os.path.join(a.audio_path, os.path.basename(a.audio_file)[:-4])
     np.save(dst, out.detach().cpu().numpy())

@@ -427,6 +427,38 @@ typedef struct fdm_sample_args {
   int graph_steps;                /* diffusion steps per graph launch; 0 = default */
 } fdm_sample_args;
 int fdm_sample_graph(fdm_plan* p, const fdm_sample_args* a, void* stream);
+/* Clips longer than max_len (windowed sampling).  A long clip of L_total latent frames (no cap) is sampled as n windows of exactly
+ * W' = min(W, L_total) frames (1 <= W <= max_len), neighbours overlapping by >= O frames (0 <= O < W):
+ *   layout   L_total <= W: one window of L_total frames; otherwise n = ceil((L_total - O) / (W - O)), s_w = floor(w (L_total - W) / (n - 1)).
+ *            Every frame is covered; with 2 * stride < W three or more windows cover a frame (the blend takes any number).
+ *   inputs   window w is an ordinary clip of the plan: audio rows [s_w pair, (s_w + W') pair) of the long encoder output, the long
+ *            clip's style / emotion, window-local positions 0 .. W'-1 (ALiBi is relative: nothing else changes).
+ *   blend    every diffusion step, in x0 space: omega_w(f) = min(1, (f - s_w + 0.5) / O, (s_w + W' - f - 0.5) / O) (no taper at the long
+ *            clip's first and last frames; O = 0 -> 1), w_hat = omega / sum(omega), x0(f) = sum_w w_hat_w(f) x0_w(f - s_w) in ascending
+ *            window order (fp32, _rn operations; CFG: each window's cond / uncond mix first).  The scheduler update (DDPM posterior sample
+ *            / DDIM eta = 0) then runs ONCE per long-clip element and its result is written back to every window holding the frame, so
+ *            overlapping rows are bitwise equal across windows at every step.  (The denoiser is causal: a window's FIRST frames lack
+ *            context, hence the taper; the taper at the right edge keeps the weights continuous through the overlap.)
+ *   noise    keyed by the long clip: Philox (seed, clip0 + long clip, element index inside the long clip, step); injected noise is
+ *            [n_steps, B, L_total*G, c].  A one-window plan is bit-identical to fdm_sample_graph on the same clip.
+ *   layout of x_T / out / noise / record: LONG, [B, L_total*G, c]; after the last step the long buffer is the stitched latent (the
+ *            VQ quantiser / decoder then run on the whole L_total: the decoder is not causal).
+ * fdm_window_layout_host: returns n and writes the starts when cap >= n (starts may be NULL: returns the needed cap);
+ * fdm_window_weights_host: returns n and writes w_hat [n, W'] (w may be NULL).  FDM_ERR_ARG: W < 1, O < 0 or O >= W; FDM_ERR_SHAPE: L_total < 1. */
+int fdm_window_layout_host(int L_total, int window, int overlap, int* starts, int cap);
+int fdm_window_weights_host(int L_total, int window, int overlap, float* w);
+/* hub [B, N, fw] features of B long clips (the audio encoder runs once over each whole waveform), style [B, n_style], emo [B, n_emo]
+ * or NULL, device fp32; L_total <= N / pair.  The plan's batch becomes B * n windows of W' frames in (long clip, window) order (the
+ * window audio rows are gathered on the device; workspaces are reserved as fdm_audio_prepare does).  FDM_ERR_SHAPE: window > max_len,
+ * L_total > N / pair; FDM_ERR_ARG: overlap >= window.  fdm_plan_get: "windows" (n; 0 = plain plan), "window_len" (W'), "L_total".
+ * Any fdm_audio_prepare* call returns the plan to plain mode; fdm_sample_graph on a windowed plan fails with FDM_ERR_STATE;
+ * fdm_denoise_step stays per window (plan layout [B * n, W'*G, c], no blend). */
+int fdm_audio_prepare_windows(fdm_plan* p, const float* hub, int B, int N, int fw, const float* style, const float* emo,
+                              int L_total, int window, int overlap, int cfg, void* stream);
+/* The sampler of a windowed plan: fdm_sample_args as for fdm_sample_graph (DDPM / DDIM, eager, graph_steps, cfg_scale, seed, clip0),
+ * with x_T / out / noise / record in LONG layout.  Step program: the denoiser chain with its scheduler update unfused, then the blend
+ * + update pass (one launch more per step than a plain plan without guidance). */
+int fdm_sample_windows(fdm_plan* p, const fdm_sample_args* a, void* stream);
 /* Plan-time tuning of the GEMM output tiles at the prepared shape (times candidates per call site; changes speed only, every
  * tile accumulates k in the same order).  This call is the ONLY place the library tunes by itself: request paths
  * (fdm_audio_prepare*, fdm_sample_graph) never do -- fdm_plan_get(p, "needs_tune") turns 1 once the prepared shape has served
