@@ -138,7 +138,7 @@ static hipError_t ln_launch_t(const fdm_ln_args& a, hipStream_t s) {
 }
 
 __global__ __launch_bounds__(256) void sched_kernel(const fdm_sched_args p) {
-  const SchedCoef c = sched_coef_load(p);
+  const SchedCoef c = p.mode == 3 ? sched_coef_load<true>(p) : sched_coef_load<false>(p);
   const int k = c.k;
   if (p.arrive && p.advance && threadIdx.x == 0) {
     // every block reads *step first, then takes a ticket; the block holding the last ticket knows all
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void sched_kernel(const fdm_sched_args p) {
       o = x0;
     } else {
       const f32x4 x = *(const f32x4*)(p.x + 4 * i);
-      o = sched_update4(p, c, x0, x, 4 * i);
+      o = p.mode == 3 ? sched_update4<true>(p, c, x0, x, 4 * i) : sched_update4<false>(p, c, x0, x, 4 * i);
     }
     *(f32x4*)(p.x_out + 4 * i) = o;
     if (p.x_out_t) {

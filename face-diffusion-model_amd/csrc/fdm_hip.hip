@@ -133,7 +133,7 @@ int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
   if (a->tile < 0 || (a->tile & FDM_TILE_ID_MASK) > FDM_TILE_MAX) return fail(FDM_ERR_ARG, "gemm: unknown tile %d", a->tile);
   if (a->sched_fuse) {
     const fdm_sched_args& sc = a->sched;
-    if (sc.mode != 0 && sc.mode != 1) return fail(FDM_ERR_ARG, "gemm: fused scheduler supports mode 0 (DDPM) and 1 (DDIM)");
+    if (sc.mode != 0 && sc.mode != 1 && sc.mode != 3) return fail(FDM_ERR_ARG, "gemm: fused scheduler supports mode 0 (DDPM), 1 (DDIM) and 3 (table-driven)");
     if (!a->resid || !a->out_f32 || a->N % 64 || a->ldo_f32 != a->N || a->ldr != a->N || a->resid_row_mod || a->batch > 1 ||
         !aligned16(a->resid) || !aligned16(a->out_f32) || (a->out_t && (a->ldo_t != a->N || !aligned16(a->out_t))))
       return fail(FDM_ERR_SHAPE, "gemm: fused scheduler needs resid = x_t and out_f32 = x_{t-1} as dense [M, N] arrays, N %% 64 == 0");
@@ -142,6 +142,9 @@ int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
     if (sc.mode == 0 && (!sc.c1 || !sc.c2 || !sc.sigma)) return fail(FDM_ERR_ARG, "gemm: fused DDPM needs c1, c2, sigma");
     if (sc.mode == 1 && (!sc.sra || !sc.srm1 || !sc.sqrt_an || !sc.c_n)) return fail(FDM_ERR_ARG, "gemm: fused DDIM needs sra, srm1, sqrt_an, c_n");
     if (sc.mode == 0 && !sc.noise && sc.n_per_clip <= 0) return fail(FDM_ERR_ARG, "gemm: fused DDPM with Philox noise needs n_per_clip");
+    if (sc.mode == 3 && (!sc.lm_a || !sc.lm_b || !sc.lm_c || !sc.lm_s || !sc.x0_hist || !aligned16(sc.x0_hist)))
+      return fail(FDM_ERR_ARG, "gemm: fused table-driven sampler needs lm_a, lm_b, lm_c, lm_s and a 16-byte aligned x0_hist [M, N]");
+    if (sc.mode == 3 && !sc.noise && sc.n_per_clip <= 0) return fail(FDM_ERR_ARG, "gemm: fused table-driven sampler with Philox noise needs n_per_clip");
   }
   if (a->ksplit < 0 || a->ksplit > 4) return fail(FDM_ERR_ARG, "gemm: ksplit %d outside 0..4", a->ksplit);
   if (a->ksplit > 1) {
@@ -234,7 +237,9 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
   if (a->n <= 0 || a->n % 4) return fail(FDM_ERR_SHAPE, "sched: n=%lld must be a positive multiple of 4", a->n);
   if (a->mode == 0 && (!a->x || !a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "sched: DDPM tables missing");
   if (a->mode == 1 && (!a->x || !a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "sched: DDIM tables missing");
-  if (a->mode < 0 || a->mode > 2) return fail(FDM_ERR_ARG, "sched: bad mode %d", a->mode);
+  if (a->mode == 3 && (!a->x || !a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist)) return fail(FDM_ERR_ARG, "sched: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist");
+  if (a->mode < 0 || a->mode > 3) return fail(FDM_ERR_ARG, "sched: bad mode %d", a->mode);
+  if (a->mode == 3 && !a->noise && (a->n_per_clip <= 0 || a->n_per_clip % 4)) return fail(FDM_ERR_SHAPE, "sched: n_per_clip must be a positive multiple of 4");
   if (a->mode == 0 && !a->noise && (a->n_per_clip <= 0 || a->n_per_clip % 4)) return fail(FDM_ERR_SHAPE, "sched: n_per_clip must be a positive multiple of 4");
   if (a->x_out_t && (a->out_dtype < FDM_F32 || a->out_dtype > FDM_F16)) return fail(FDM_ERR_ARG, "sched: bad out_dtype %d", a->out_dtype);
   if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "sched: split x_out_t needs x_out_t_lo_off");
@@ -248,6 +253,7 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
 // of a windowed plan (fdm_sample_windows)
 int fdm::window_sched_op(const fdm_sched_args& a, const fdm::WinArgs& w, void* stream) {
   if (!a.x || !w.off || !w.ent || !w.xw || (!w.init && (!a.x0 || !a.x_out))) return fail(FDM_ERR_ARG, "window_sched: null operand");
+  if (!w.init && a.mode == 3 && (!a.lm_a || !a.lm_b || !a.lm_c || !a.lm_s || !a.x0_hist)) return fail(FDM_ERR_ARG, "window_sched: table-driven sampler needs its tables and x0_hist");
   if (a.n <= 0 || a.n % 4 || w.d % 4 || w.L_total < 1 || w.W < 1 || w.n_win < 1 || a.n % ((long long)w.L_total * w.d))
     return fail(FDM_ERR_SHAPE, "window_sched: n=%lld is not a whole number of long clips of %d x %d", a.n, w.L_total, w.d);
   fdm_sched_args c = a;

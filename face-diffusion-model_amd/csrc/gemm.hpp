@@ -75,11 +75,11 @@ __device__ __forceinline__ void gemm_load_rowstats(const fdm_gemm_args& p, int m
 // cover them too.
 template <int MI, int NI> struct EpiPre { f32x4 csv[NI], bv[NI], gmv[NI], btv[NI], rv[MI][NI]; SchedCoef sc; };
 
-template <typename T, int BM, int BN, int WM, int WN, bool SCHED = false>
+template <typename T, int BM, int BN, int WM, int WN, int SCHED = 0>      // SCHED: 0 none, 1 DDPM / DDIM, 2 table-driven (GEMM_LM)
 __device__ __forceinline__ void gemm_epi_preload(const fdm_gemm_args& p, int m0, int n0, int z, int wm, int wn, int g, int r16,
                                                  bool ln_capable, EpiPre<BM / WM / 16, BN / WN / 16>& e) {
   constexpr int MI = BM / WM / 16, NI = BN / WN / 16;
-  if constexpr (SCHED) e.sc = sched_coef_load(p.sched);     // k -> t -> table entries: three dependent loads, hidden by the k loop
+  if constexpr (SCHED != 0) e.sc = sched_coef_load<SCHED == 2>(p.sched);     // k -> t -> table entries: three dependent loads, hidden by the k loop
   const int M = p.M, N = p.N;
   const bool use_ln = ln_capable && p.ln_stat_in;
   const float* bias = p.bias ? p.bias + (size_t)z * p.bias_batch_stride : nullptr;
@@ -131,7 +131,9 @@ __host__ __device__ inline bool gemm_act_is_heavy(int act) { return act == ACT_M
 // instruction fetch -- is not compiled in.
 // SPEC further says what the launch can need: GEMM_KV = packed K / V outputs, GEMM_FOLD = the LayerNorm-folding producer /
 // consumer forms; a lean kernel without either is bias + activation + residual + stores (a few hundred instructions).
-constexpr int GEMM_LEAN = 1, GEMM_KV = 2, GEMM_FOLD = 4, GEMM_KSPLIT = 8, GEMM_B2 = 16;
+constexpr int GEMM_LEAN = 1, GEMM_KV = 2, GEMM_FOLD = 4, GEMM_KSPLIT = 8, GEMM_B2 = 16, GEMM_LM = 32;
+// GEMM_LM (with SCHED): the fused scheduler update is the table-driven linear multistep form (fdm_sched_args.mode 3: it reads and
+// rewrites x0_hist); a specialisation of its own, so the DDPM / DDIM kernels keep their registers (profiles/sampler_tables/resources.txt).
 // GEMM_KSPLIT (with GEMM_LEAN): blockIdx.z is a K slice, not a batch index -- slice s runs k-tiles [s nk / S, (s + 1) nk / S) and
 // stores its fp32 partial tile to plane s of out_f32; slice 0 alone adds bias and residual (fdm_gemm_args.ksplit).  The
 // epilogue sees the slice's view of the arguments:
@@ -236,7 +238,7 @@ __device__ __forceinline__ void gemm_epilogue(const fdm_gemm_args& p, f32x4 (&ac
         }
         if constexpr (SCHED) {
           // fused scheduler: v = x0_hat, rv = x_t (same element), flat element index of the chain's x buffer
-          v = sched_update4(p.sched, e.sc, v, rv[mi][ni], (long long)m * N + (ncol + ni * 16));
+          v = sched_update4<(SPEC & GEMM_LM) != 0>(p.sched, e.sc, v, rv[mi][ni], (long long)m * N + (ncol + ni * 16));
         } else {
           if (p.resid) v += pre_rln ? (rv[mi][ni] - mu) * rs * gmv[ni] + btv[ni] : rv[mi][ni];
         }
@@ -595,7 +597,7 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_glds_kernel(const vo
   }
   EpiPre<MI, NI> epre;
   constexpr bool FOLDC = !(SPEC & GEMM_LEAN) || (SPEC & GEMM_FOLD);
-  gemm_epi_preload<T, BM, BN, WM, WN, SCHED>(pe, m0, n0, z, wm, wn, g, r16, FOLDC, epre);
+  gemm_epi_preload<T, BM, BN, WM, WN, (SCHED ? ((SPEC & GEMM_LM) ? 2 : 1) : 0)>(pe, m0, n0, z, wm, wn, g, r16, FOLDC, epre);
   if constexpr (FOLDC) gemm_load_rowstats<BM>(p, m0, rowstat);   // visible to every wave after the first barrier of the k loop
 
   // fragment (plane pl, k-step s) of tile row `row` in the stage at `base`: one ds_read_b128 through the XOR swizzle
@@ -952,12 +954,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const fdm_gemm_args p) {
       f32x4 (&acch)[MI / 2][NI] = *reinterpret_cast<f32x4 (*)[MI / 2][NI]>(&acc[hh * (MI / 2)]);
       const int m0h = m0 + wm * (BM / WM) - wm * (BM / 2 / WM) + hh * (BM / 2 / WM);
       EpiPre<MI / 2, NI> epre;
-      gemm_epi_preload<T, BM / 2, BN, WM, WN, SCHED>(p, m0h, n0, z, wm, wn, g, r16, false, epre);
+      gemm_epi_preload<T, BM / 2, BN, WM, WN, (SCHED ? ((SPEC & GEMM_LM) ? 2 : 1) : 0)>(p, m0h, n0, z, wm, wn, g, r16, false, epre);
       gemm_epilogue<T, BM / 2, BN, WM, WN, HEAVY, SCHED, SPEC>(p, acch, epre, m0h, n0, z, wm, wn, g, r16, nullptr, nullptr);
     }
   } else {
     EpiPre<MI, NI> epre;
-    gemm_epi_preload<T, BM, BN, WM, WN, SCHED>(p, m0, n0, z, wm, wn, g, r16, FOLDC, epre);
+    gemm_epi_preload<T, BM, BN, WM, WN, (SCHED ? ((SPEC & GEMM_LM) ? 2 : 1) : 0)>(p, m0, n0, z, wm, wn, g, r16, FOLDC, epre);
     gemm_epilogue<T, BM, BN, WM, WN, HEAVY, SCHED, SPEC>(p, acc, epre, m0, n0, z, wm, wn, g, r16, rowstat, smem);
   }
 #ifdef FDM_PP_PHASES
@@ -1207,15 +1209,18 @@ static bool gemm_sched_fuse_heuristic_pp(const fdm_gemm_args& a, int elem_bytes)
 }
 
 // the scheduler-fused latent decoder on the 64x64 tile (lean kernels only), loader-wave form for the 16-bit kinds
-template <typename T>
+template <typename T, int LM = 0>
 static hipError_t gemm_sched_fuse_launch(const fdm_gemm_args& a, hipStream_t s) {
+  if constexpr (LM == 0) {
+    if (a.sched.mode == 3) return gemm_sched_fuse_launch<T, GEMM_LM>(a, s);      // the table-driven form: its own kernels
+  }
   if constexpr (!std::is_same<T, float>::value) {
     if (!(a.tile & FDM_TILE_LOCKSTEP) && !gemm_lockstep_env())
-      return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD, 4>(a, s)
-                          : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN, 4>(a, s);
+      return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD | LM, 4>(a, s)
+                          : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | LM, 4>(a, s);
   }
-  return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD>(a, s)
-                      : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN>(a, s);
+  return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD | LM>(a, s)
+                      : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | LM>(a, s);
 }
 
 // K-sliced launches (fdm_gemm_args.ksplit): the 64-column tiles, ring depth by tile id.  With S slices per output tile the grid
@@ -1237,7 +1242,8 @@ static hipError_t gemm_dispatch(const fdm_gemm_args& a, hipStream_t s) {
     const int tile_id = a.tile & FDM_TILE_ID_MASK;
     const bool pp = tile_id == FDM_TILE_256x128_PP || (tile_id == 0 && gemm_tile_override() == 0 && gemm_sched_fuse_heuristic_pp(a, (int)sizeof(typename Opnd<T>::E)));
     if (pp && !a.ln_stat_in && a.N % 128 == 0)
-      return gemm_pp_launch_h<T, 256, 128, 4, 2, 3, false, true, GEMM_LEAN>(a, s);
+      return a.sched.mode == 3 ? gemm_pp_launch_h<T, 256, 128, 4, 2, 3, false, true, GEMM_LEAN | GEMM_LM>(a, s)
+                               : gemm_pp_launch_h<T, 256, 128, 4, 2, 3, false, true, GEMM_LEAN>(a, s);
     return gemm_sched_fuse_launch<T>(a, s);
   }
   const int tile_id = a.tile & FDM_TILE_ID_MASK;

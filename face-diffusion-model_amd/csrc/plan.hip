@@ -193,6 +193,60 @@ int fdm_ddim_schedule_host(int steps, int T, int* t, int* t_next, float* sqrt_an
   return n;
 }
 
+// alphas_cumprod of the cosine schedule in fp64 (the expression order of fdm_schedule_host, before its fp32 cast)
+static void alphas_cumprod_f64(int T, std::vector<double>& acp) {
+  const double s = 0.008;
+  std::vector<double> ac(T + 1);
+  for (int i = 0; i <= T; ++i) {
+    const double c = std::cos((((double)i / T) + s) / (1 + s) * M_PI * 0.5);
+    ac[i] = c * c;
+  }
+  const double a0 = ac[0];
+  for (int i = 0; i <= T; ++i) ac[i] = ac[i] / a0;
+  acp.resize(T);
+  double run = 1.0;
+  for (int i = 0; i < T; ++i) {
+    double b = 1 - (ac[i + 1] / ac[i]);
+    b = b < 0 ? 0 : (b > 0.9999 ? 0.9999 : b);
+    run = (i == 0) ? 1.0 - b : run * (1.0 - b);
+    acp[i] = run;
+  }
+}
+
+int fdm_sampler_tables_host(int kind, int steps, int T, double eta, int* t, float* a, float* b, float* c, float* s) {
+  if (kind != FDM_SAMPLER_DPMPP_2M && kind != FDM_SAMPLER_DDIM) return fail(FDM_ERR_ARG, "sampler_tables_host: unknown kind %d", kind);
+  if (T < 1 || steps < 1 || steps > T) return fail(FDM_ERR_ARG, "sampler_tables_host: steps = %d outside [1, T = %d]", steps, T);
+  if (!(eta >= 0.0 && eta <= 1.0)) return fail(FDM_ERR_ARG, "sampler_tables_host: eta = %g outside [0, 1]", eta);
+  if (kind == FDM_SAMPLER_DPMPP_2M && eta != 0.0) return fail(FDM_ERR_ARG, "sampler_tables_host: DPM-Solver++ 2M is deterministic (eta must be 0)");
+  if (!t || !a || !b || !c || !s) return fail(FDM_ERR_ARG, "sampler_tables_host: null output");
+  // the grid of fdm_ddim_schedule_host, every pair executed: the last one, (t_last, -1), goes to data (alpha_bar(-1) := 1)
+  std::vector<int> times(steps + 1);
+  const double start = -1.0, stop = (double)T - 1.0, step = (stop - start) / steps;
+  for (int i = 0; i <= steps; ++i) times[i] = (int)(i == steps ? stop : (double)i * step + start);
+  std::vector<double> acp;
+  alphas_cumprod_f64(T, acp);
+  double h_prev = 0.0;
+  for (int k = 0; k < steps; ++k) {
+    const int tc = times[steps - k], tn = times[steps - k - 1];
+    t[k] = tc;
+    if (tn < 0) { a[k] = 0.f; b[k] = 1.f; c[k] = 0.f; s[k] = 0.f; continue; }
+    const double ab = acp[tc], abn = acp[tn];
+    if (kind == FDM_SAMPLER_DDIM) {
+      const double sg = eta * std::sqrt((1.0 - abn) / (1.0 - ab)) * std::sqrt(1.0 - ab / abn);
+      const double av = std::sqrt(1.0 - abn - sg * sg) / std::sqrt(1.0 - ab);
+      a[k] = (float)av; b[k] = (float)(std::sqrt(abn) - av * std::sqrt(ab)); c[k] = 0.f; s[k] = (float)sg;
+      continue;
+    }
+    const double lam = 0.5 * std::log(ab / (1.0 - ab)), lam_n = 0.5 * std::log(abn / (1.0 - abn));
+    const double h = lam_n - lam, phi = std::sqrt(abn) * (1.0 - std::exp(-h));
+    a[k] = (float)(std::sqrt(1.0 - abn) / std::sqrt(1.0 - ab)); s[k] = 0.f;
+    if (k == 0) { b[k] = (float)phi; c[k] = 0.f; }
+    else { const double r = h_prev / h; b[k] = (float)(phi * (1.0 + 1.0 / (2.0 * r))); c[k] = (float)(-phi / (2.0 * r)); }
+    h_prev = h;
+  }
+  return FDM_OK;
+}
+
 int fdm_alibi_slopes_host(int n_head, float* out) {
   if (n_head <= 0 || !out) return fail(FDM_ERR_ARG, "alibi_slopes_host: bad argument");
   std::vector<double> v;
@@ -275,6 +329,10 @@ struct fdm_plan {
   int* step = nullptr;                       // [device step counter, t of the current step]
   unsigned long long* seedbuf = nullptr;     // {Philox seed, global index of clip 0}: read by the scheduler at run time
   int* tseq = nullptr; int tseq_cap = 0;
+  // table-driven sampler (fdm_sample_args kind 2): device tables [4][lm_cap] (a | b | c | s, uploaded per call) and the fp32 history
+  // of the previous step's x0 prediction -- plan layout, sized with the workspaces (a windowed plan keeps its own in long layout)
+  float* lm_tab = nullptr; int lm_cap = 0;
+  float* x0_hist = nullptr;
   std::map<int, std::pair<int, float*>> ddim;   // ddim_steps -> (live pairs, device [san | cn])
   std::map<int, std::vector<int>> ddim_t;
   // ---- programs and tiles
@@ -301,6 +359,7 @@ struct fdm_plan {
   // clips ("windows") of L = win_len frames; win_n == 0 = plain mode.  Plan-lifetime buffers, grown on demand (growing drops programs).
   int win_n = 0, win_len = 0, win_total = 0, win_overlap = 0, win_B = 0;
   float* xlong = nullptr; size_t xlong_cap = 0;             // x_t in long layout [win_B, win_total * d]
+  float* hist_long = nullptr; size_t hist_long_cap = 0;     // x0_hist of the table-driven sampler in long layout (the blended x0)
   int* win_off = nullptr; size_t win_off_cap = 0;           // CSR of the covering windows per frame (fdm::WinArgs)
   fdm::WinEnt* win_ent = nullptr; size_t win_ent_cap = 0;
   float* win_stage = nullptr; size_t win_stage_cap = 0;     // gathered window audio rows + repeated one-hots (read by the prepare)
@@ -578,6 +637,7 @@ int reserve(fdm_plan* P, int B, int L, int cfg) {
   FCK(dalloc_t(P, &P->h, R * d, true)); FCK(dalloc_t(P, &P->h2, R * d, true)); P->x1_planes = std::max(1, std::max(P->ksplit_out, P->ksplit_ffn2));      // (x1: one fp32 plane per K slice of the plan's setting; plan_set grows it)
   FCK(dalloc_t(P, &P->x1, R * d * P->x1_planes, true));
   FCK(dalloc_t(P, &P->x0, R * d, true)); FCK(dalloc_t(P, &P->x, M * d, true));
+  FCK(dalloc_t(P, &P->x0_hist, M * d, true));      // fp32 in every arithmetic mode
   if (P->dtype != FDM_F32) {
     FCK(dalloc_mat(P, &P->xt, M, d, true)); FCK(dalloc_mat(P, &P->ht, R, d, true)); FCK(dalloc_mat(P, &P->h2t, R, d, true));
   } else {        // fp32 operands alias the fp32 residual-stream buffers
@@ -607,6 +667,7 @@ int reserve(fdm_plan* P, int B, int L, int cfg) {
   FCK(dalloc_t(P, &P->step, (size_t)4, true));
   FCK(dalloc_t(P, &P->seedbuf, (size_t)2, true));
   if (!P->tseq) { P->tseq_cap = 1024; FCK(dalloc_t(P, &P->tseq, (size_t)P->tseq_cap, false)); }
+  if (!P->lm_tab) { P->lm_cap = 1024; FCK(dalloc_t(P, &P->lm_tab, (size_t)4 * P->lm_cap, false)); }
   P->capB = B; P->capL = L; P->capRep = repc;
   return FDM_OK;
 }
@@ -727,7 +788,7 @@ int record_chain(fdm_plan* P, const fdm_sched_args* sched, void* stream) {
 }
 
 struct ProgSpec {
-  int kind;                  // 0 pass (denoiser only, + CFG mix), 1 DDPM, 2 DDIM
+  int kind;                  // 0 pass (denoiser only, + CFG mix), 1 DDPM, 2 DDIM, 3 table-driven linear multistep (san = the device tables)
   const float* noise = nullptr; float cfg_scale = 0.f;
   const float* san = nullptr; const float* cn = nullptr;
   int reps = 1;              // diffusion steps recorded back to back (one graph launch runs them all)
@@ -800,6 +861,11 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       sc.noise = sp.noise; sc.noise_stride = n; sc.seed_dev = P->seedbuf;
     } else if (sp.kind == 2) {
       sc.mode = 1; sc.sra = P->sra; sc.srm1 = P->srm1; sc.sqrt_an = sp.san; sc.c_n = sp.cn;
+    } else if (sp.kind == 3) {
+      sc.mode = 3; sc.n_per_clip = (long long)P->L * d;
+      sc.lm_a = P->lm_tab; sc.lm_b = P->lm_tab + P->lm_cap; sc.lm_c = P->lm_tab + 2 * (size_t)P->lm_cap; sc.lm_s = P->lm_tab + 3 * (size_t)P->lm_cap;
+      sc.x0_hist = P->win_n ? P->hist_long : P->x0_hist;
+      sc.noise = sp.noise; sc.noise_stride = n; sc.seed_dev = P->seedbuf;
     }
     if (sp.kind != 0 && P->win_n) {
       // windowed plan: the chain unfused, then one pass over the long layout -- blend the windows' x0 (after their CFG mix), update
@@ -1349,6 +1415,7 @@ int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int f
   hipStream_t s = (hipStream_t)stream;
   FCK(grow(P, (void**)&P->win_stage, &P->win_stage_cap, (n_hub + n_sty + n_emo) * 4, stream));
   FCK(grow(P, (void**)&P->xlong, &P->xlong_cap, (size_t)B * L_total * d * 4, stream));
+  FCK(grow(P, (void**)&P->hist_long, &P->hist_long_cap, (size_t)B * L_total * d * 4, stream));
   // window w of long clip b = plan clip b * n + w: audio rows [s_w pair, (s_w + W) pair) of the clip, the clip's one-hots
   float *hw = P->win_stage, *sw = hw + n_hub, *ew = sw + n_sty;
   for (int b = 0; b < B; ++b)
@@ -1397,6 +1464,13 @@ int fdm_denoise_step(fdm_plan* P, const float* x_t, int t, float cfg_scale, floa
 }  // extern "C"
 
 namespace {
+// the table-driven sampler's own arguments: checkable without a plan or a device
+int check_tables_args(const fdm_sample_args* a) {
+  if (a && a->kind == 2 && (!a->lm_tables || !a->t_list || a->n_steps < 1))
+    return fail(FDM_ERR_ARG, "sample_graph: the table-driven sampler needs lm_tables [4][n_steps], t_list and n_steps >= 1");
+  return FDM_OK;
+}
+
 // fdm_sample_graph (plain plan, x in plan layout) and fdm_sample_windows (windowed plan, x_T / out / noise / record in long layout)
 int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   P->pinned.clear();
@@ -1431,8 +1505,29 @@ int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
     }
     ts = P->ddim_t[a->ddim_steps];
     sp.kind = 2; sp.san = P->ddim[a->ddim_steps].second; sp.cn = sp.san + a->ddim_steps;
+  } else if (a->kind == 2) {
+    FCK(check_tables_args(a));
+    for (int i = 0; i < a->n_steps; ++i) {
+      if (a->t_list[i] < 0 || a->t_list[i] >= 1000) return fail(FDM_ERR_ARG, "sample_graph: timestep %d outside [0, 1000)", a->t_list[i]);
+      ts.push_back(a->t_list[i]);
+    }
+    if (a->n_steps > P->lm_cap) {      // a longer table than any before: a new buffer (recorded programs point at the old one)
+      FCK(drop_programs(P, stream));
+      auto old = std::find(P->allocs.begin(), P->allocs.end(), (void*)P->lm_tab);
+      if (old != P->allocs.end()) { P->allocs.erase(old); (void)hipFree(P->lm_tab); }
+      P->lm_tab = nullptr; P->lm_cap = a->n_steps;
+      FCK(dalloc_t(P, &P->lm_tab, (size_t)4 * P->lm_cap, false));
+    }
+    for (int j = 0; j < 4; ++j)        // set_steps() below drains the copies (the tables are caller memory)
+      HIPCK(hipMemcpyAsync(P->lm_tab + (size_t)j * P->lm_cap, a->lm_tables + (size_t)j * a->n_steps, (size_t)a->n_steps * 4, hipMemcpyHostToDevice, s));
+    const unsigned long long sd[2] = {a->seed, (unsigned long long)(unsigned)a->clip0};
+    HIPCK(hipMemcpyAsync(P->seedbuf, sd, 16, hipMemcpyHostToDevice, s));
+    // a call never sees the history of the one before it (the shipped tables have c[0] = 0 and do not read it at step 0)
+    if (P->win_n) HIPCK(hipMemsetAsync(P->hist_long, 0, (size_t)P->win_B * P->win_total * P->m.d * 4, s));
+    else HIPCK(hipMemsetAsync(P->x0_hist, 0, (size_t)P->M * P->m.d * 4, s));
+    sp.kind = 3; sp.noise = a->noise; sp.san = P->lm_tab;
   } else {
-    return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM)", a->kind);
+    return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", a->kind);
   }
   const int n_steps = (int)ts.size();
   const size_t nx = P->win_n ? (size_t)P->win_B * P->win_total * P->m.d : (size_t)P->M * P->m.d;     // elements of x in the caller's layout
@@ -1482,12 +1577,14 @@ int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
 extern "C" {
 
 int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  FCK(check_tables_args(a));
   FCK(check_ready(P));
   if (P->win_n) return fail(FDM_ERR_STATE, "sample_graph: the plan was prepared for windowed sampling (fdm_sample_windows)");
   return sample_impl(P, a, stream);
 }
 
 int fdm_sample_windows(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  FCK(check_tables_args(a));
   FCK(check_ready(P));
   if (!P->win_n) return fail(FDM_ERR_STATE, "sample_windows: call fdm_audio_prepare_windows first");
   return sample_impl(P, a, stream);

@@ -1,5 +1,6 @@
-// Device functions of the diffusion scheduler update (DDPM posterior sample / DDIM eta = 0) and its Philox noise,
-// shared by sched_kernel (elementwise.hpp) and the GEMM epilogue's fused form (gemm.hpp) so both produce the same bits.
+// Device functions of the diffusion scheduler update (DDPM posterior sample / DDIM eta = 0 / table-driven linear multistep) and its
+// Philox noise, shared by sched_kernel (elementwise.hpp), the GEMM epilogue's fused form (gemm.hpp) and window_sched_kernel
+// (window.hpp) so all three produce the same bits.
 #pragma once
 #include "common.hpp"
 #include "../../include/fdm_hip.h"
@@ -46,6 +47,10 @@ __device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigne
 // flat element e of the x buffer.  Shared by sched_kernel and by the GEMM epilogue's fused form (fdm_gemm_args.sched_fuse),
 // so both produce the same bits.
 struct SchedCoef { int k, t; float c1, c2, sg, sra, srm1, san, cn; unsigned long long seed; int clip0; };
+// LM = the table-driven linear multistep form (fdm_sched_args.mode 3) is compiled in; without it the DDPM / DDIM forms keep the
+// code (and the registers: no x0_hist pointer, no extra table loads) they had before mode 3 existed.  sched_kernel and
+// window_sched_kernel branch on the mode at run time; the GEMM epilogue's fused form is a template specialisation (GEMM_LM).
+template <bool LM = false>
 __device__ __forceinline__ SchedCoef sched_coef_load(const fdm_sched_args& p) {
   SchedCoef c;
   c.k = p.step ? *(volatile const int*)p.step : 0;
@@ -54,24 +59,47 @@ __device__ __forceinline__ SchedCoef sched_coef_load(const fdm_sched_args& p) {
   c.srm1 = 1.f;
   c.seed = p.seed_dev ? p.seed_dev[0] : p.seed;
   c.clip0 = p.seed_dev ? (int)p.seed_dev[1] : p.clip0;
-  if (p.mode == 0) { c.c1 = p.c1[c.t]; c.c2 = p.c2[c.t]; c.sg = p.sigma[c.t]; }
-  if (p.mode == 1) { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = p.sqrt_an[c.k]; c.cn = p.c_n[c.k]; }
+  if constexpr (LM) {
+    // x' = a x + b x0 + c x0_prev + s z, tables indexed by step k.  The four scalars ride in the DDPM / DDIM slots
+    // (c1 = b, c2 = a, sg = s, cn = c), so the coefficient block keeps its size.
+    c.c1 = p.lm_b[c.k]; c.c2 = p.lm_a[c.k]; c.sg = p.lm_s[c.k]; c.cn = p.lm_c[c.k];
+  } else {
+    if (p.mode == 0) { c.c1 = p.c1[c.t]; c.c2 = p.c2[c.t]; c.sg = p.sigma[c.t]; }
+    if (p.mode == 1) { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = p.sqrt_an[c.k]; c.cn = p.c_n[c.k]; }
+  }
   return c;
 }
+// z of 4 consecutive elements for step k: injected noise, or Philox keyed (seed, clip0 + clip, element, k)
+__device__ __forceinline__ f32x4 sched_noise4(const fdm_sched_args& p, const SchedCoef& c, long long e) {
+  if (p.noise) return *(const f32x4*)(p.noise + (size_t)c.k * (p.noise_stride > 0 ? p.noise_stride : p.n) + e);
+  const int clip = (int)(e / p.n_per_clip);
+  return philox_normal4(c.seed, (unsigned)((e - (long long)clip * p.n_per_clip) >> 2), (unsigned)c.k, (unsigned)(c.clip0 + clip));
+}
+template <bool LM = false>
 __device__ __forceinline__ f32x4 sched_update4(const fdm_sched_args& p, const SchedCoef& c, f32x4 x0, f32x4 x, long long e) {
   f32x4 o;
+  if constexpr (LM) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(__fmul_rn(c.c1, x0[j]), __fmul_rn(c.c2, x[j]));      // b x0 + a x
+    // the previous step's x0 prediction: each lane reads, then rewrites, its own four elements of x0_hist (no hazard)
+    if (c.cn != 0.f) {
+      const f32x4 h = *(const f32x4*)(p.x0_hist + e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(o[j], __fmul_rn(c.cn, h[j]));
+    }
+    *(f32x4*)(p.x0_hist + e) = x0;
+    if (c.sg != 0.f) {
+      const f32x4 z = sched_noise4(p, c, e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(o[j], __fmul_rn(c.sg, z[j]));
+    }
+    return o;
+  }
   if (p.mode == 0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(__fmul_rn(c.c1, x0[j]), __fmul_rn(c.c2, x[j]));
     if (c.t > 0) {
-      f32x4 z;
-      if (p.noise) {
-        z = *(const f32x4*)(p.noise + (size_t)c.k * (p.noise_stride > 0 ? p.noise_stride : p.n) + e);
-      } else {
-        const int clip = (int)(e / p.n_per_clip);
-        z = philox_normal4(c.seed, (unsigned)((e - (long long)clip * p.n_per_clip) >> 2), (unsigned)c.k,
-                           (unsigned)(c.clip0 + clip));
-      }
+      const f32x4 z = sched_noise4(p, c, e);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = __fadd_rn(o[j], __fmul_rn(c.sg, z[j]));
     }

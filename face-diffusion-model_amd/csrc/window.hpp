@@ -11,9 +11,10 @@
 namespace fdm {
 
 // p: the scheduler arguments in LONG layout (x = x_out = the long buffer, n = B * L_total * d, n_per_clip = L_total * d, noise
-// [steps, B, L_total * d]); p.x0 / p.x0u / p.x_out_t are the plan's window-layout buffers.  Vector loads and stores only.
+// [steps, B, L_total * d], x0_hist of the table-driven mode [B, L_total * d]: it keeps the BLENDED x0); p.x0 / p.x0u / p.x_out_t
+// are the plan's window-layout buffers.  Vector loads and stores only.
 __global__ __launch_bounds__(256) void window_sched_kernel(const fdm_sched_args p, const WinArgs w) {
-  const SchedCoef c = sched_coef_load(p);
+  const SchedCoef c = p.mode == 3 ? sched_coef_load<true>(p) : sched_coef_load<false>(p);
   const long long nq = p.n / 4, per_clip = (long long)w.L_total * w.d, wrows = (long long)w.W * w.d;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
     const long long e = 4 * i;
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(256) void window_sched_kernel(const fdm_sched_args 
         for (int k = 0; k < 4; ++k) acc[k] = j == j0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
       }
       const f32x4 x = *(const f32x4*)(p.x + e);
-      o = sched_update4(p, c, acc, x, e);
+      o = p.mode == 3 ? sched_update4<true>(p, c, acc, x, e) : sched_update4<false>(p, c, acc, x, e);
       *(f32x4*)(p.x_out + e) = o;
     }
     for (int j = j0; j < j1; ++j) {

@@ -48,7 +48,8 @@ def synthetic_loader(p, clips, seconds, seed=0, names=None):
 
 
 @torch.no_grad()
-def sample_step(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps, emotion=4, all_styles=False, batched=True, dataset=None):
+def sample_step(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps, emotion=4, all_styles=False, batched=True, dataset=None,
+                fast=None):
     """The reference loops the style one-hots of a clip through one B = 1 sampling call each, with the same audio
     (samples/sample_diffusion_vocaset.py:71-83).  Here all styles of a clip are ONE call (condition-batched step program:
     the audio encoder and audio tables run once per clip); batched=False keeps the sequential loop (same files, bit-identical
@@ -59,13 +60,14 @@ def sample_step(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps,
         styles = list(range(one_hot_all.shape[1])) if all_styles else [0]
         emo = torch.eye(p.n_emo)[emotion:emotion + 1] if p.n_emo else None
         steps = None if p.n_emo else ddim_steps
+        fast = fast or {}          # build-added: sampler / sampler_steps / eta of pipeline.animate
         if batched and len(styles) > 1:
             ids = one_hot_all[0, styles, :]                              # [S, n_style]: one call for the whole style loop
-            outs, _ = pipeline.animate(diffusion, autoencoder, audio, template, ids, emo, ddim_steps=steps, device=dev)
+            outs, _ = pipeline.animate(diffusion, autoencoder, audio, template, ids, emo, ddim_steps=steps, device=dev, **fast)
             outs = [outs[i:i + 1] for i in range(len(styles))]
         else:
             outs = [pipeline.animate(diffusion, autoencoder, audio, template, one_hot_all[:, it, :], emo, ddim_steps=steps,
-                                     device=dev)[0] for it in styles]    # samples/sample_diffusion_vocaset.py:71
+                                     device=dev, **fast)[0] for it in styles]    # samples/sample_diffusion_vocaset.py:71
         for it, out in zip(styles, outs):
             dst = os.path.join(save_folder, save_name(dataset, file_name, it))
             np.save(dst, out.detach().cpu().numpy())
@@ -73,7 +75,7 @@ def sample_step(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps,
 
 
 @torch.no_grad()
-def sample_batched(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps, emotion=4, max_batch=8, dataset=None):
+def sample_batched(loader, dev, diffusion, autoencoder, save_folder, p, ddim_steps, emotion=4, max_batch=8, dataset=None, fast=None):
     """The same files as sample_step (style 0 of every clip), but clips of the loader -- whatever their durations -- go through
     ONE sampling call per `max_batch` clips (pipeline.animate_many: exact, the denoiser's attention is causal) instead of the
     reference's one B = 1 call per clip (samples/sample_diffusion_vocaset.py:51: batch size 1)."""
@@ -84,7 +86,7 @@ def sample_batched(loader, dev, diffusion, autoencoder, save_folder, p, ddim_ste
     ids = [oh[:, 0, :] for _, _, oh, _ in items]
     emo = [torch.eye(p.n_emo)[emotion:emotion + 1]] * len(items) if p.n_emo else None
     verts, _ = pipeline.animate_many(diffusion, autoencoder, audios, tmpl, ids, emo, ddim_steps=None if p.n_emo else ddim_steps,
-                                     device=dev, max_batch=max_batch)
+                                     device=dev, max_batch=max_batch, **(fast or {}))
     for (_, _, _, file_name), out in zip(items, verts):
         dst = os.path.join(save_folder, save_name(dataset or p.name, file_name, 0))
         np.save(dst, out.detach().cpu().numpy())
@@ -107,7 +109,12 @@ def main(dataset=None, argv=None):
     ap.add_argument("--all_styles", action="store_true", help="every style one-hot of each clip (the reference's VOCASET loop), as one batched call")
     ap.add_argument("--sequential", action="store_true", help="with --all_styles: one B = 1 call per style, as the reference does")
     ap.add_argument("--batch", type=int, default=1, help="clips per sampling call (clips of different durations batch exactly)")
+    ap.add_argument("--sampler", default=None, choices=["dpmpp2m", "ddim_eta"],
+                    help="build-added: table-driven multistep sampler (DPM-Solver++ 2M | DDIM with --eta) instead of the shipped one")
+    ap.add_argument("--sampler_steps", type=int, default=20, help="steps of --sampler")
+    ap.add_argument("--eta", type=float, default=0.0, help="eta of --sampler ddim_eta, in [0, 1]")
     a = ap.parse_args(argv)
+    fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
     named = dataset is not None
     dataset = dataset or a.dataset
     p = presets.get(dataset)
@@ -117,10 +124,10 @@ def main(dataset=None, argv=None):
     single = a.batch <= 1 and (not all_styles or a.sequential)
     diffusion, ae = pipeline.build_models(dataset, None, a.device, a.stage1_model_path, a.stage2_model_path, single_clip=single)
     if a.batch > 1 and not all_styles:
-        sample_batched(synthetic_loader(p, a.clips, a.seconds), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset)
+        sample_batched(synthetic_loader(p, a.clips, a.seconds), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset, fast=fast)
     else:
         sample_step(synthetic_loader(p, a.clips, a.seconds), a.device, diffusion, ae, a.out, p, steps,
-                    all_styles=all_styles, batched=not a.sequential, dataset=dataset)
+                    all_styles=all_styles, batched=not a.sequential, dataset=dataset, fast=fast)
 
 
 if __name__ == "__main__":

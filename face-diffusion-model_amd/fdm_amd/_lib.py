@@ -9,6 +9,8 @@ LIB_PATH = os.environ.get("FDM_LIB_PATH") or os.path.join(_HERE, "libfdm_hip.so"
 
 F32, BF16, F16X3, F16 = 0, 1, 2, 3      # include/fdm_hip.h FDM_*: operand kinds (F16X3 is a split plane pair; F16 its hi plane alone: denoiser only)
 DTYPE_NAMES = {"f32": F32, "bf16": BF16, "f16x3": F16X3, "f16": F16}
+SAMPLER_DPMPP_2M, SAMPLER_DDIM = 0, 1    # fdm_sampler_tables_host kinds
+SAMPLER_NAMES = {"dpmpp2m": SAMPLER_DPMPP_2M, "ddim_eta": SAMPLER_DDIM}
 ACT_NONE, ACT_RELU, ACT_MISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_LEAKY02 = range(6)
 
 vp, ll, ci, cf = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -20,7 +22,8 @@ class SchedArgs(C.Structure):
                 ("c1", vp), ("c2", vp), ("sigma", vp), ("sra", vp), ("srm1", vp),
                 ("sqrt_an", vp), ("c_n", vp), ("noise", vp), ("noise_stride", ll), ("x_out_t", vp), ("out_dtype", ci), ("arrive", vp),
                 ("seed", C.c_ulonglong), ("clip0", ci),
-                ("mode", ci), ("x_out_t_lo_off", ll), ("seed_dev", vp)]
+                ("mode", ci), ("x_out_t_lo_off", ll), ("seed_dev", vp),
+                ("lm_a", vp), ("lm_b", vp), ("lm_c", vp), ("lm_s", vp), ("x0_hist", vp)]
 
 
 class GemmArgs(C.Structure):
@@ -52,7 +55,8 @@ class ModelDesc(C.Structure):
 
 class SampleArgs(C.Structure):
     _fields_ = [("kind", ci), ("x_T", vp), ("out", vp), ("t_list", vp), ("n_steps", ci), ("ddim_steps", ci), ("noise", vp),
-                ("seed", C.c_ulonglong), ("clip0", ci), ("cfg_scale", cf), ("eager", ci), ("record", vp), ("graph_steps", ci)]
+                ("seed", C.c_ulonglong), ("clip0", ci), ("cfg_scale", cf), ("eager", ci), ("record", vp), ("graph_steps", ci),
+                ("lm_tables", vp)]
 
 
 class VqDesc(C.Structure):
@@ -144,6 +148,7 @@ SYMBOLS = {
     "fdm_vq_destroy": (ci, [vp]),
     "fdm_schedule_host": (ci, [ci, vp]),
     "fdm_ddim_schedule_host": (ci, [ci, ci, vp, vp, vp, vp]),
+    "fdm_sampler_tables_host": (ci, [ci, ci, ci, C.c_double, vp, vp, vp, vp, vp]),
     "fdm_alibi_slopes_host": (ci, [ci, vp]),
     "fdm_pe_table_host": (ci, [ci, ci, ci, ci, vp]),
 }

@@ -204,6 +204,39 @@ class DenoiserPlan:
             record.extend(rec[i] for i in range(n_live))
         return out
 
+    def _tables_args(self, a, t_list, tables):
+        """kind 2 of fdm_sample_args: host timesteps + host [4, n_steps] tables (the library uploads both during the call)."""
+        tab = torch.as_tensor(tables, dtype=torch.float32).detach().cpu().contiguous()
+        if tab.dim() != 2 or tab.shape[0] != 4 or tab.shape[1] != len(t_list):
+            raise FdmError(f"tables must be [4, len(t_list) = {len(t_list)}] (a, b, c, s), got {tuple(tab.shape)}")
+        ts = (C.c_int * len(t_list))(*[int(t) for t in t_list])
+        a.kind, a.t_list, a.n_steps, a.lm_tables = 2, C.cast(ts, C.c_void_p), len(t_list), tab.data_ptr()
+        return ts, tab
+
+    def sample_tables(self, x_T, t_list, tables, noise=None, seed=0, clip0=0, cfg_scale=2.5, use_graph=True, record=None, graph_steps=0):
+        """Table-driven linear multistep sampler (fdm_sample_graph kind 2): step k runs the denoiser at t_list[k] and sets
+        x <- a[k] x + b[k] x0 + c[k] x0_prev + s[k] z with tables = [a, b, c, s] ([4, len(t_list)], host), x0_prev the previous
+        step's (guidance-mixed) prediction kept by the plan.  schedule.sampler_tables builds t_list and the tables of
+        DPM-Solver++ 2M and of DDIM with eta.  noise / seed / clip0 / record / use_graph / graph_steps as sample_ddpm."""
+        a = SampleArgs()
+        held = self._tables_args(a, t_list, tables)
+        a.seed, a.clip0, a.cfg_scale, a.eager, a.graph_steps = int(seed), int(clip0), float(cfg_scale), int(not use_graph), int(graph_steps)
+        if noise is not None:
+            nz = _dev(noise, self.device)
+            if nz.numel() != len(t_list) * self.M * self.p.d:
+                raise FdmError("noise must be [len(t_list), B, L*G, c]")
+            self._keep = (self._keep + [nz])[-8:]
+            a.noise = nz.data_ptr()
+        rec = None
+        if record is not None:
+            rec = torch.empty(len(t_list), *x_T.shape, device=self.device)
+            a.record = rec.data_ptr()
+        out = self._sample(a, x_T)
+        del held
+        if rec is not None:
+            record.extend(rec[i] for i in range(len(t_list)))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def prepare_windows(self, hub, style, emo=None, L_total=None, window=None, overlap=60, cfg=False):
         """Clips longer than max_len (fdm_audio_prepare_windows): hub [B, N, fw] features of B whole long clips, style [B, n_style],
@@ -236,10 +269,11 @@ class DenoiserPlan:
         return starts
 
     def sample_windows(self, x_T, kind="ddpm", t_list=None, steps=None, noise=None, seed=0, clip0=0, cfg_scale=2.5, record=None,
-                       use_graph=True, graph_steps=0):
+                       use_graph=True, graph_steps=0, tables=None):
         """fdm_sample_windows: x_T [B, L_total*G, c] -> [B, L_total*G, c].  kind "ddpm" over t_list (noise [len(t_list), B,
-        L_total*G, c] injected, or Philox keyed by (seed, clip0 + long clip, step)) or "ddim" with `steps`.  record (a list) receives
-        the long latent after every step."""
+        L_total*G, c] injected, or Philox keyed by (seed, clip0 + long clip, step)), "ddim" with `steps`, or "tables" over t_list
+        with `tables` [4, len(t_list)] (sample_tables; noise / seed as "ddpm").  record (a list) receives the long latent after
+        every step."""
         if not self.get("windows"):
             raise FdmError("call prepare_windows() first")
         shape = (self.B_long, self.L_total * self.p.G, self.p.c)
@@ -248,9 +282,13 @@ class DenoiserPlan:
         x = _dev(x_T, self.device)
         a = SampleArgs()
         a.cfg_scale, a.eager, a.graph_steps = float(cfg_scale), int(not use_graph), int(graph_steps)
-        if kind == "ddpm":
-            ts = (C.c_int * len(t_list))(*[int(t) for t in t_list])
-            a.kind, a.t_list, a.n_steps, a.seed, a.clip0 = 0, C.cast(ts, C.c_void_p), len(t_list), int(seed), int(clip0)
+        if kind in ("ddpm", "tables"):
+            if kind == "tables":
+                held = self._tables_args(a, t_list, tables)
+                a.seed, a.clip0 = int(seed), int(clip0)
+            else:
+                ts = (C.c_int * len(t_list))(*[int(t) for t in t_list])
+                a.kind, a.t_list, a.n_steps, a.seed, a.clip0 = 0, C.cast(ts, C.c_void_p), len(t_list), int(seed), int(clip0)
             n_rec = len(t_list)
             if noise is not None:
                 nz = _dev(noise, self.device)
@@ -262,7 +300,7 @@ class DenoiserPlan:
             a.kind, a.ddim_steps = 1, int(steps)
             n_rec = sum(1 for pr in schedule.ddim_time_pairs(int(steps)) if pr[1] >= 0)
         else:
-            raise FdmError(f"kind {kind!r} (ddpm | ddim)")
+            raise FdmError(f"kind {kind!r} (ddpm | ddim | tables)")
         rec = None
         if record is not None:
             rec = torch.empty(max(n_rec, 1), *shape, device=self.device)

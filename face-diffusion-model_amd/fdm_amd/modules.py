@@ -553,6 +553,21 @@ class GaussianDiffusion(nn.Module):
         x_T = torch.randn(shape, device=plan.device) if x_T is None else x_T.to(plan.device)
         return plan.sample_ddim(x_T.float().contiguous(), steps, cfg_scale=scale)
 
+    @torch.no_grad()
+    def fast_sample(self, audio, latent_motion_shape, *cond, steps=20, sampler="dpmpp2m", eta=0.0, x_T=None, seed=None,
+                    guidance_scale=None, clip0=0):
+        """Build-added: few-step sampling with a table-driven multistep solver (DenoiserPlan.sample_tables).  sampler "dpmpp2m"
+        (DPM-Solver++ 2M: second order, one denoiser call per step) or "ddim_eta" (DDIM with eta in [0, 1]; eta > 0 draws
+        Philox noise keyed by (seed, clip0 + row block, step)).  `steps` pairs of the reference's DDIM grid, all executed: the
+        last one goes to data.  cond / x_T / seed / clip0 / guidance_scale as sample().  What 20 steps do to perceptual quality
+        on trained checkpoints is unmeasured."""
+        plan, scale = self._plan(audio, latent_motion_shape, cond, guidance_scale)
+        t_list, tables = schedule.sampler_tables(sampler, steps, eta, self.num_timesteps)
+        shape = (plan.B,) + tuple(latent_motion_shape[1:])
+        x_T = torch.randn(shape, device=plan.device) if x_T is None else x_T.to(plan.device)
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+        return plan.sample_tables(x_T.float().contiguous(), t_list, tables, seed=seed, clip0=int(clip0), cfg_scale=scale)
+
     def forward(self, x, audio, *cond):
         """Forward-only loss (:757-761); there is no backward pass on this path (training is out of scope).  Like the reference,
         one timestep per clip: t = randint(0, T, (b,)) (:759).  The step program shares t across its rows, so clips with

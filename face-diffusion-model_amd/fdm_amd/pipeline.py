@@ -81,8 +81,11 @@ def _clip_x_T(shape, S, seed):
 
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
-            ddim_steps=None, seed=0, device="cuda:0"):
+            ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    sampler "dpmpp2m" | "ddim_eta" (with eta=): `sampler_steps` steps of the table-driven multistep sampler
+    (GaussianDiffusion.fast_sample) from the same per-clip x_T, on every preset; None = the paths below, unchanged.
 
     id_one_hot [B*S, n_style] (and emotion_one_hot [B*S, n_emo]) with S > 1 animates every clip under S conditions in ONE
     sampling call -- the reference sampler's style loop (samples/sample_diffusion_vocaset.py:71-83) batched: the audio
@@ -117,10 +120,17 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
             emotion_one_hot = emotion_one_hot.expand(rows, -1)
         if id_one_hot.shape[0] == 1 and rows > 1:
             id_one_hot = id_one_hot.expand(rows, -1)
-        latent = diffusion.sample(audio, shape, emotion_one_hot, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed))
+        if sampler:
+            latent = diffusion.fast_sample(audio, shape, emotion_one_hot, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta,
+                                           seed=seed, x_T=_clip_x_T(shape, S, seed))
+        else:
+            latent = diffusion.sample(audio, shape, emotion_one_hot, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed))
         quanted, _, _ = autoencoder.quant(latent, emotion_one_hot, stats=False)
     else:
-        if ddim_steps:
+        if sampler:
+            latent = diffusion.fast_sample(audio, shape, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta, seed=seed,
+                                           x_T=_clip_x_T(shape, S, seed))
+        elif ddim_steps:
             g = torch.Generator(device="cpu").manual_seed(seed)
             x_T = torch.randn(shape, generator=g).repeat_interleave(S, dim=0)
             latent = diffusion.ddim_sample(audio, shape, id_one_hot, ddim_steps, x_T=x_T)
@@ -136,7 +146,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
-                 seed=0, device="cuda:0", max_batch=8, bucket=16):
+                 seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
 
     The reference's samplers take the clips of a loader one at a time (bs = 1: samples/sample_diffusion_vocaset.py:51,71-83),
@@ -149,7 +159,8 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     in the caller's order.  DDIM (noise-free): clips are grouped by length (least padding).  DDPM: groups follow the caller's
     order and clip b draws the noise stream of index b (Philox key clip0 + position), so results do not depend on max_batch.
     A group's length is rounded up to a multiple of `bucket` frames (free: the padding is exact), so a long-running caller
-    cycles through a handful of shapes whose recorded step programs and tuned tiles the plan keeps."""
+    cycles through a handful of shapes whose recorded step programs and tuned tiles the plan keeps.  sampler / sampler_steps / eta:
+    as animate() (groups follow the caller's order, noise keyed as for DDPM)."""
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
     n = len(audios)
@@ -162,7 +173,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             return default
         x = torch.as_tensor(x[b] if isinstance(x, (list, tuple)) else x, dtype=torch.float32).reshape(-1, width)
         return x[b:b + 1] if x.shape[0] == n else x[:1]
-    ddim = bool(ddim_steps) and not p.n_emo
+    ddim = bool(ddim_steps) and not p.n_emo and not sampler
     order = sorted(range(n), key=lambda b: Ls[b]) if ddim else list(range(n))
     verts, lats = [None] * n, [None] * n
     prev = (model._hub_key, model._hub)
@@ -185,6 +196,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             shape = (len(grp), Lmax * p.G, p.c)
             if p.n_emo:
                 emos = torch.cat([row(emotion_one_hots, b, p.n_emo, torch.eye(p.n_emo)[4:5]) for b in grp]).to(device)
+            if sampler:
+                lat = diffusion.fast_sample(dummy, shape, *((emos, ids) if p.n_emo else (ids,)), steps=sampler_steps, sampler=sampler,
+                                            eta=eta, seed=seed, x_T=x_T, clip0=g0)
+            elif p.n_emo:
                 lat = diffusion.sample(dummy, shape, emos, ids, seed=seed, x_T=x_T, clip0=g0)
             elif ddim_steps:
                 lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T)
@@ -205,7 +220,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
-                 window=None, overlap=60, device="cuda:0"):
+                 window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0):
     """audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
     encoder frames // pair (no 600-frame cap: animate() keeps the reference's crop).
 
@@ -215,7 +230,8 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     emotion_one_hot [B, n_emo]; defaults as animate()).  x_T is drawn per long clip from a CPU generator seeded with `seed` (as
     animate() draws it) and the DDPM noise is Philox keyed by (seed, long clip, step), so with L_total <= window the result is
     bit-identical to animate()'s.  DDIM (eta = 0) when ddim_steps, on every preset; classifier-free guidance when `diffusion`
-    wraps a ClassifierFreeSampleModel."""
+    wraps a ClassifierFreeSampleModel.  sampler / sampler_steps / eta: as animate() (the history of the multistep solver is the
+    blended x0 in the long layout)."""
     cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
     model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
     scale = float(diffusion.denoise_fn.level) if cfg else 2.5
@@ -239,7 +255,11 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     plan.prepare_windows(hub, style, emo, L_total=L_total, window=window, overlap=overlap, cfg=cfg)
     shape = (B, L_total * p.G, p.c)
     x_T = torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
-    if ddim_steps:
+    if sampler:
+        from . import schedule
+        t_list, tables = schedule.sampler_tables(sampler, sampler_steps, eta, diffusion.num_timesteps)
+        latent = plan.sample_windows(x_T, "tables", t_list=t_list, tables=tables, seed=seed, cfg_scale=scale)
+    elif ddim_steps:
         latent = plan.sample_windows(x_T, "ddim", steps=ddim_steps, cfg_scale=scale)
     else:
         ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
@@ -267,6 +287,10 @@ def demo_main(preset, argv=None):
     ap.add_argument("--stage2_model_path", type=str, default=f"{p.name}/{p.name}_stage2.mpt")
     ap.add_argument("--audio_path", type=str, default=f"{p.name}/result")
     ap.add_argument("--ddim_steps", type=int, default=0, help="build-added: DDIM steps (0 = full DDPM chain)")
+    ap.add_argument("--sampler", type=str, default=None, choices=["dpmpp2m", "ddim_eta"],
+                    help="build-added: table-driven multistep sampler (DPM-Solver++ 2M | DDIM with --eta) instead of DDPM / DDIM")
+    ap.add_argument("--sampler_steps", type=int, default=20, help="build-added: steps of --sampler")
+    ap.add_argument("--eta", type=float, default=0.0, help="build-added: eta of --sampler ddim_eta, in [0, 1]")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--long_audio", type=str, default="truncate", choices=["truncate", "window"],
                     help="build-added: audio past max_len latent frames: truncate (the reference's crop) or window (animate it all)")
@@ -281,11 +305,12 @@ def demo_main(preset, argv=None):
     emo = None
     if p.n_emo:
         emo = torch.eye(p.n_emo)[EMOTIONS.index(a.emotion)].unsqueeze(0)
+    fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
     if a.long_audio == "window":
         out, _ = animate_long(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed,
-                              overlap=a.window_overlap, device=a.device)
+                              overlap=a.window_overlap, device=a.device, **fast)
     else:
-        out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device)
+        out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device, **fast)
     os.makedirs(a.audio_path, exist_ok=True)
     dst = os.path.join(a.audio_path, os.path.basename(a.audio_file)[:-4])
     np.save(dst, out.detach().cpu().numpy())

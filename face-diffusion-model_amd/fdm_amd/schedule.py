@@ -59,6 +59,23 @@ def ddim_tables(buf, pairs):
     return torch.sqrt(an), c
 
 
+def sampler_tables(kind, steps, eta=0.0, T=1000):
+    """Timesteps and coefficient tables of the table-driven sampler (fdm_sampler_tables_host; include/fdm_hip.h states the
+    formulas): kind "dpmpp2m" (DPM-Solver++ 2M) or "ddim_eta" (DDIM with eta in [0, 1]).  Returns (t_list, tables): `steps`
+    ints and a float32 CPU tensor [4, steps] of a, b, c, s for DenoiserPlan.sample_tables -- every pair of the reference's
+    DDIM grid is executed and the last one goes to data."""
+    import ctypes as C
+    from ._lib import SAMPLER_NAMES, check, lib
+    if kind not in SAMPLER_NAMES:
+        raise ValueError(f"sampler {kind!r} ({' | '.join(SAMPLER_NAMES)})")
+    n = max(int(steps), 1)
+    t = (C.c_int * n)()
+    tab = torch.zeros(4, n, dtype=torch.float32)
+    ptr = [C.c_void_p(tab[i].data_ptr()) for i in range(4)]
+    check(lib().fdm_sampler_tables_host(SAMPLER_NAMES[kind], int(steps), int(T), float(eta), C.cast(t, C.c_void_p), *ptr))
+    return list(t), tab
+
+
 def alibi_slopes(n):
     """get_slopes, models/fdm_vocaset.py:96-106."""
     def p2(n):

@@ -80,7 +80,13 @@ int fdm_device_ok(void);
  * x0 = x0u + cfg_scale*(x0 - x0u) before the update.
  * DDPM: x' = c1[t]*x0 + c2[t]*x + sigma[t]*z, z = 0 when t == 0.  z comes from `noise`
  * (+ k*n elements) if non-NULL, else Philox4x32-10/Box-Muller keyed by (seed, clip0 + clip, k).
- * DDIM (eta = 0): eps = (sra[t]*x - x0)/srm1[t]; x' = x0*sqrt_an[k] + c_n[k]*eps.           */
+ * DDIM (eta = 0): eps = (sra[t]*x - x0)/srm1[t]; x' = x0*sqrt_an[k] + c_n[k]*eps.
+ * Table-driven linear multistep (mode 3): x' = lm_a[k]*x + lm_b[k]*x0 + lm_c[k]*x0_hist + lm_s[k]*z, then x0_hist = x0 (under
+ * the CFG mix: the mixed x0).  Evaluated in _rn operations without contraction, in this order: o = b*x0 + a*x; if c[k] != 0:
+ * o += c*x0_hist[e]; if s[k] != 0: o += s*z, z exactly as for DDPM (`noise`, or Philox keyed (seed, clip0 + clip, element, k)).
+ * The four tables are device fp32 arrays indexed by the STEP k (not by t); x0_hist is n fp32 elements, read only when
+ * c[k] != 0 and rewritten every step.  fdm_sampler_tables_host builds the tables of DPM-Solver++ 2M and of DDIM with eta; a
+ * caller may bring its own.                                                                     */
 typedef struct fdm_sched_args {
   const float* x0; const float* x0u; float cfg_scale;
   const float* x; float* x_out;
@@ -94,10 +100,12 @@ typedef struct fdm_sched_args {
   unsigned int* arrive;                                      /* device word (zeroed once): lets the LAST block to read *step
                                                                 advance it inside this kernel (no separate launch) */
   unsigned long long seed; int clip0;
-  int mode;                                                  /* 0 DDPM, 1 DDIM, 2 CFG mix only (x_out = mix) */
+  int mode;                                                  /* 0 DDPM, 1 DDIM, 2 CFG mix only (x_out = mix), 3 table-driven linear multistep */
   long long x_out_t_lo_off;                                  /* split out_dtype: elements between the hi and lo planes of x_out_t */
   const unsigned long long* seed_dev;                        /* optional device words {seed, clip0}: override `seed` / `clip0`, so a
                                                                 captured graph serves every seed / shard (no re-capture per call) */
+  const float* lm_a; const float* lm_b; const float* lm_c; const float* lm_s;   /* mode 3: device tables indexed by step k */
+  float* x0_hist;                                            /* mode 3: fp32 [n], the previous step's x0 prediction (read, then rewritten) */
 } fdm_sched_args;
 int fdm_op_sched_step(const fdm_sched_args* a, void* stream);
 
@@ -147,7 +155,7 @@ typedef struct fdm_gemm_args {
   /* output tile per workgroup: 0 = library heuristic, else FDM_TILE_*.  Results do not depend on it (every tile
    * accumulates k in the same order): callers time the candidates once per shape at plan build and pass the winner. */
   int tile;
-  /* sched_fuse != 0: the epilogue applies fdm_op_sched_step's DDPM / DDIM update (sched.mode 0 / 1, no CFG mix) to the
+  /* sched_fuse != 0: the epilogue applies fdm_op_sched_step's DDPM / DDIM / table-driven update (sched.mode 0 / 1 / 3, no CFG mix) to the
    * tile it just computed, v = x0_hat: `resid` is read as the current latent x_t (NOT added), and x_{t-1} goes to
    * out_f32 (may alias resid) and, if given, out_t (the next step's operand copy).  The latent-decoder GEMM of a
    * non-CFG sampler uses this: one launch less per diffusion step, bit-identical to the separate kernel.  Needs
@@ -415,7 +423,8 @@ int fdm_denoise_step(fdm_plan* p, const float* x_t, int t, float cfg_scale, floa
  * 649-667): the step program (denoiser + fused scheduler update) replayed n_steps times as a hipGraph, the timestep read
  * from a device-side counter; graph_steps (default 10) diffusion steps are captured per graph launch. */
 typedef struct fdm_sample_args {
-  int kind;                       /* 0 = DDPM over t_list, 1 = DDIM (eta = 0) with `ddim_steps` (the dead last pair is skipped) */
+  int kind;                       /* 0 = DDPM over t_list, 1 = DDIM (eta = 0) with `ddim_steps` (the dead last pair is skipped),
+                                     2 = table-driven linear multistep sampler over t_list with `lm_tables` (below) */
   const float* x_T; float* out;   /* [B, L*G, c] device fp32 (may alias) */
   const int* t_list; int n_steps; /* DDPM: host array of timesteps, descending */
   int ddim_steps;
@@ -425,6 +434,13 @@ typedef struct fdm_sample_args {
   int eager;                      /* != 0: launch the recorded ops directly instead of replaying the graph (bit-identical) */
   float* record;                  /* optional [n_steps, B, L*G, c]: the latent after every step */
   int graph_steps;                /* diffusion steps per graph launch; 0 = default */
+  /* kind 2: HOST memory [4][n_steps] fp32 in the order a, b, c, s -- step k computes x' = a[k] x + b[k] x0 + c[k] x0_prev + s[k] z
+   * (fdm_sched_args mode 3) with the denoiser run at t_list[k] (t_list need not be contiguous).  The plan uploads the tables
+   * per call and owns the fp32 history buffer x0_prev (zeroed at the start of every call; LONG layout on a windowed plan).
+   * noise, seed, clip0, cfg_scale, eager, record and graph_steps behave as for DDPM; the step program has DDPM's launch count
+   * and its own cache key (the DDPM / DDIM programs of the plan are untouched).  fdm_sampler_tables_host builds t_list and
+   * the tables of DPM-Solver++ 2M and of DDIM with eta.  FDM_ERR_ARG: lm_tables NULL, t_list NULL, n_steps < 1. */
+  const float* lm_tables;
 } fdm_sample_args;
 int fdm_sample_graph(fdm_plan* p, const fdm_sample_args* a, void* stream);
 /* Clips longer than max_len (windowed sampling).  A long clip of L_total latent frames (no cap) is sampled as n windows of exactly
@@ -455,7 +471,7 @@ int fdm_window_weights_host(int L_total, int window, int overlap, float* w);
  * fdm_denoise_step stays per window (plan layout [B * n, W'*G, c], no blend). */
 int fdm_audio_prepare_windows(fdm_plan* p, const float* hub, int B, int N, int fw, const float* style, const float* emo,
                               int L_total, int window, int overlap, int cfg, void* stream);
-/* The sampler of a windowed plan: fdm_sample_args as for fdm_sample_graph (DDPM / DDIM, eager, graph_steps, cfg_scale, seed, clip0),
+/* The sampler of a windowed plan: fdm_sample_args as for fdm_sample_graph (DDPM / DDIM / table-driven kind 2, eager, graph_steps, cfg_scale, seed, clip0),
  * with x_T / out / noise / record in LONG layout.  Step program: the denoiser chain with its scheduler update unfused, then the blend
  * + update pass (one launch more per step than a plain plan without guidance). */
 int fdm_sample_windows(fdm_plan* p, const fdm_sample_args* a, void* stream);
@@ -532,6 +548,22 @@ int fdm_vq_destroy(fdm_vq* v);
  * the positional tables (:150-184). */
 int fdm_schedule_host(int T, float* out12);
 int fdm_ddim_schedule_host(int steps, int T, int* t, int* t_next, float* sqrt_an, float* c_n);
+/* Tables of the table-driven sampler (fdm_sample_args kind 2 / fdm_sched_args mode 3): `steps` entries of t, a, b, c, s each, fp64
+ * math on the cosine schedule of fdm_schedule_host, fp32 cast.  Schedule overrides given to a plan ("sched.*") do not apply here.
+ * Grid: the reference's own, reversed(linspace(-1, T-1, steps+1).astype(int32)), and ALL `steps` pairs are executed: for the last
+ * pair (t_last, -1) alpha_bar(-1) := 1, i.e. a = 0, b = 1, c = 0, s = 0 -- the sampler ends in data (its output is the last x0
+ * prediction), unlike the reference's DDIM, which skips that pair and returns a latent still at t_last.
+ * With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln(alpha / sigma), h_k = lambda(t_next) - lambda(t),
+ * phi_k = alpha_next (1 - exp(-h_k)):
+ *   FDM_SAMPLER_DPMPP_2M (DPM-Solver++ 2M, Lu et al. 2022; eta must be 0): a = sigma_next / sigma, s = 0; first step and final pair:
+ *     b = phi, c = 0; otherwise with r = h_{k-1} / h_k: b = phi (1 + 1 / (2 r)), c = -phi / (2 r).
+ *   FDM_SAMPLER_DDIM (Song et al. 2020, eta in [0, 1]): sigma_k = eta sqrt((1 - abar_n) / (1 - abar)) sqrt(1 - abar / abar_n),
+ *     a = sqrt(1 - abar_n - sigma_k^2) / sqrt(1 - abar), b = sqrt(abar_n) - a sqrt(abar), c = 0, s = sigma_k.
+ * FDM_ERR_ARG: steps < 1, steps > T, eta outside [0, 1] (or != 0 for 2M), unknown kind, a NULL output.  What 20 such steps do to
+ * perceptual quality on trained checkpoints is unmeasured here. */
+#define FDM_SAMPLER_DPMPP_2M 0
+#define FDM_SAMPLER_DDIM 1
+int fdm_sampler_tables_host(int kind, int steps, int T, double eta, int* t, float* a, float* b, float* c, float* s);
 int fdm_alibi_slopes_host(int n_head, float* out);
 int fdm_pe_table_host(int d, int periodic, int period, int rows, float* out);
 
