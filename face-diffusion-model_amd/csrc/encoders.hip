@@ -10,23 +10,12 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/fdm_hip.h"
 #include "common.hpp"
-#include "kernels.hpp"
+#include "host.hpp"
 
 namespace {
-using fdm::fail;
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(FDM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-#define FCK(x) do { int r_ = (x); if (r_ != FDM_OK) return r_; } while (0)
-
-int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
+using namespace fdm;
 
 // ---- one-time repack kernels -----------------------------------------------------------------------------------------
 // Conv1d weight [out, in, k] -> [out, k, in]: a strided Conv1d over a channels-last signal is then a GEMM whose A rows overlap
@@ -84,23 +73,6 @@ __global__ void argmax_rows_kernel(const float* x, int* out, int B, int n) {
 }
 
 // ---- shared bookkeeping -----------------------------------------------------------------------------------------------
-struct Wt { float* p = nullptr; long long n = 0; };
-struct Mat { void* p = nullptr; long long lo = 0; };      // operand-kind matrix; lo = elements between the hi and lo planes (split kind)
-
-struct Arena {
-  std::vector<void*> allocs;
-  int alloc(void** out, size_t bytes, bool zero = false) {
-    void* p = nullptr;
-    HIPCK(hipMalloc(&p, bytes ? bytes : 16));
-    if (zero) HIPCK(hipMemset(p, 0, bytes ? bytes : 16));
-    allocs.push_back(p);
-    *out = p;
-    return FDM_OK;
-  }
-  template <typename T> int alloc_t(T** out, size_t n, bool zero = false) { return alloc((void**)out, n * sizeof(T), zero); }
-  void release() { for (void* p : allocs) (void)hipFree(p); allocs.clear(); }
-};
-
 struct Store {       // fp32 weights by reference state-dict name (plan-owned copies)
   std::map<std::string, Wt> w;
   Arena mem;
@@ -111,31 +83,11 @@ struct Store {       // fp32 weights by reference state-dict name (plan-owned co
     return FDM_OK;
   }
   const Wt* find(const std::string& name) const { auto it = w.find(name); return it == w.end() ? nullptr : &it->second; }
-  int need(const std::string& name, long long n, const float** out) const {
-    const Wt* t = find(name);
-    if (!t) return fail(FDM_ERR_STATE, "missing weight %s", name.c_str());
-    if (t->n != n) return fail(FDM_ERR_SHAPE, "weight %s has %lld elements, expected %lld", name.c_str(), t->n, n);
-    *out = t->p;
-    return FDM_OK;
-  }
+  int need(const std::string& name, long long n, const float** out) const { return need_weight(w, "", name, n, out); }
 };
 
-size_t esize(int dtype) { return dtype == FDM_BF16 ? 2 : 4; }      // (FDM_F16X3: two 2-byte planes = 4)
+size_t esize(int dtype) { return kind(dtype).full(); }      // bytes per matrix element (a split kind's two 2-byte planes = 4)
 
-int to_operand(Arena& mem, int dtype, const float* src, long long n, Mat* out, void* stream) {
-  if (dtype == FDM_F32) { out->p = (void*)src; return FDM_OK; }
-  FCK(mem.alloc(&out->p, (size_t)n * esize(dtype)));
-  out->lo = dtype == FDM_F16X3 ? n : 0;          // fdm_op_cast writes the lo plane n elements after the hi plane
-  return fdm_op_cast(src, out->p, n, dtype, stream);
-}
-
-fdm_gemm_args gemm_args(int dtype, const void* A, const void* W, int M, int N, int K) {
-  fdm_gemm_args a;
-  memset(&a, 0, sizeof(a));
-  a.A = A; a.lda = K; a.W = W; a.ldw = K; a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = dtype;
-  a.ldr = N; a.ldo_f32 = N; a.ldo_t = N; a.ln_eps = 1e-5f;
-  return a;
-}
 // (split dtype: y_t is a plane pair of M * d elements each, lo plane right behind the hi plane)
 int layernorm(const float* x, const float* gamma, const float* beta, int M, int d, int act, float* y32, void* yt, int dtype, void* stream) {
   fdm_ln_args a;
@@ -360,7 +312,7 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   FCK(enc_commit(E, stream));
   FCK(enc_reserve(E, B, n));
   const int D = E->D, dt = E->front_dtype(), dtl = E->dtype, H = E->H, FFN = E->FFN, HD = 64;
-  const size_t es = esize(dt), esl = esize(dtl);
+  const size_t esl = esize(dtl);
   const bool split = dtl == FDM_F16X3;
   // --- conv feature extractor (channels-last) ---
   // split front (FDM_F16X3): every activation matrix [rows, C] is a plane pair, lo plane rows * C elements behind the hi plane
@@ -378,7 +330,7 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   int Tin = T[0];
   for (int i = 1; i < 7; ++i) {
     const int k = CONV_K[i], sd = CONV_S[i], To = T[i];
-    fdm_gemm_args g = gemm_args(dt, xt, E->conv_w[i].p, To, CD, k * CD);
+    fdm_gemm_args g = dense_gemm(dt, xt, E->conv_w[i].p, To, CD, k * CD);
     g.lda = (long long)sd * CD; g.bias = E->conv_b[i]; g.batch = B; g.a_batch_stride = (long long)Tin * CD; g.out_batch_stride = (long long)To * CD;
     g.a_lo_off = lo_of((long long)B * Tin, CD); g.w_lo_off = E->conv_w[i].lo;
     void* nx = (xt == E->xa) ? E->xb : E->xa;
@@ -399,7 +351,7 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   if (interp) { FCK(fdm_op_linear_interp(E->g6, E->gi, B, T6, N, CD, stream)); g6 = E->gi; T6 = N; }
   FCK(layernorm(g6, E->fp_lng, E->fp_lnb, B * T6, CD, FDM_ACT_NONE, nullptr, E->ft, dt, stream));
   const int M = B * N;
-  fdm_gemm_args g = gemm_args(dt, E->ft, E->fp_w.p, N, D, CD);
+  fdm_gemm_args g = dense_gemm(dt, E->ft, E->fp_w.p, N, D, CD);
   g.bias = E->fp_b; g.out_f32 = E->h; g.batch = B; g.a_batch_stride = (long long)T6 * CD; g.out_batch_stride = (long long)N * D;
   g.a_lo_off = lo_of((long long)B * T6, CD); g.w_lo_off = E->fp_w.lo;
   void* ht = dt != FDM_F32 ? E->ht : (void*)E->h;
@@ -408,15 +360,13 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   // --- positional conv embedding: h += GELU(grouped conv(h)), k = 128, groups = 16, pad 64, last output dropped ---
   const int dg = D / POS_G;
   const long long xg_plane = (long long)POS_G * B * (N + POS_K) * dg;      // elements of one [groups, B, N + K, dg] plane
-  const size_t ee = fsplit ? 2 : es;                                     // bytes per element of a plane
   FCK(fdm_op_group_pad(ht, E->xg, B, N, D, POS_G, POS_K / 2, dt, stream));
   if (fsplit) FCK(fdm_op_group_pad((const char*)ht + (size_t)M * D * 2, (char*)E->xg + (size_t)xg_plane * 2, B, N, D, POS_G, POS_K / 2, dt, stream));
   {
     // ONE launch for all clips (round 5; one launch per clip before): z = (clip, group), the weights of a group shared by the clips
     // and by the row tiles, workgroups dealt so that every XCD works on two groups only -- its L2 streams 1 / 8 of the 16.8 MB
     // weight once (fdm_gemm_args.batch2).  Per clip the launch fetched 133 MB for 18 MB of operands (profiles/r4_pmc_hubert_bf16_B4).
-    (void)ee;
-    fdm_gemm_args pg = gemm_args(dt, E->xg, E->pc_w.p, N, dg, POS_K * dg);
+    fdm_gemm_args pg = dense_gemm(dt, E->xg, E->pc_w.p, N, dg, POS_K * dg);
     pg.lda = dg; pg.batch = POS_G; pg.a_batch_stride = (long long)B * (N + POS_K) * dg; pg.w_batch_stride = (long long)dg * POS_K * dg;
     pg.batch2 = B; pg.a_batch_stride2 = (long long)(N + POS_K) * dg; pg.out_batch_stride2 = (long long)N * D;
     pg.a_lo_off = fsplit ? xg_plane : 0; pg.w_lo_off = E->pc_w.lo;
@@ -426,7 +376,6 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   }
   float* h = E->h2;
   float* hb = E->hb;
-  float* hx = E->h;         // free fp32 buffer (the pre-posconv h)
   // --- encoder layers ---
   const int Lpad = kv_pad(N);
   HIPCK(hipMemsetAsync(E->kp, 0, (size_t)B * Lpad * D * esl, (hipStream_t)stream));       // pad keys must be finite; the layout depends on N
@@ -434,17 +383,11 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   // split kind: every operand of the layer loop is a plane pair; lo planes sit one whole matrix after the hi planes
   const long long lo_md = split ? (long long)M * D : 0, lo_mf = split ? (long long)M * FFN : 0, lo_kv = split ? (long long)B * Lpad * D : 0;
   auto lgemm = [&](const void* A, long long a_lo, const Mat& W, int n_out, int k_in) {
-    fdm_gemm_args a = gemm_args(dtl, A, W.p, M, n_out, k_in);
+    fdm_gemm_args a = dense_gemm(dtl, A, W.p, M, n_out, k_in);
     a.a_lo_off = a_lo; a.w_lo_off = W.lo;
     return a;
   };
-  auto lnorm = [&](const float* x, const float* gam, const float* bet, float* y32, void* yt) {
-    fdm_ln_args a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.M = M; a.d = D; a.gamma = gam; a.beta = bet; a.eps = 1e-5f; a.act = FDM_ACT_NONE; a.y_f32 = y32; a.y_t = yt; a.dtype = dtl;
-    a.y_t_lo_off = yt ? lo_md : 0;
-    return fdm_op_layernorm(&a, stream);
-  };
+  auto lnorm = [&](const float* x, const float* gam, const float* bet, float* y32, void* yt) { return layernorm(x, gam, bet, M, D, FDM_ACT_NONE, y32, yt, dtl, stream); };
   auto qkv = [&](const void* a_in, const Layer& ly) {
     fdm_gemm_args a = lgemm(a_in, lo_md, ly.wqkv, 3 * D, D);
     a.bias = ly.bqkv; a.out_t = E->q; a.ldo_t = D; a.out_t_lo_off = lo_md; a.out_kp = E->kp; a.kp_col0 = D; a.out_vp = E->vp; a.vp_col0 = 2 * D;
@@ -498,7 +441,6 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
     }
     HIPCK(hipMemcpyAsync(out, hb, (size_t)M * D * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   }
-  (void)hx;
   if (n_frames) *n_frames = N;
   return FDM_OK;
 }
@@ -661,15 +603,10 @@ int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B,
   // split kind: every operand of the loop is a plane pair, the lo plane one whole matrix after the hi plane
   const bool split = dt == FDM_F16X3;
   const long long lo_md = split ? (long long)M * d : 0, lo_mf = split ? (long long)M * VQ_FFN : 0, lo_kv = split ? (long long)B * Lpad * d : 0;
-  auto lnorm = [&](const float* x, const float* gam, const float* bet) {
-    fdm_ln_args a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.M = M; a.d = d; a.gamma = gam; a.beta = bet; a.eps = 1e-5f; a.act = FDM_ACT_NONE; a.y_t = V->a; a.y_t_lo_off = lo_md; a.dtype = dt;
-    return fdm_op_layernorm(&a, stream);
-  };
+  auto lnorm = [&](const float* x, const float* gam, const float* bet) { return layernorm(x, gam, bet, M, d, FDM_ACT_NONE, nullptr, V->a, dt, stream); };
   for (const Layer& ly : layers) {
     FCK(lnorm(h, ly.ln1g, ly.ln1b));
-    fdm_gemm_args g = gemm_args(dt, V->a, ly.wqkv.p, M, 3 * d, d);
+    fdm_gemm_args g = dense_gemm(dt, V->a, ly.wqkv.p, M, 3 * d, d);
     g.a_lo_off = lo_md; g.w_lo_off = ly.wqkv.lo; g.out_t_lo_off = lo_md; g.kv_lo_off = lo_kv;
     g.out_t = V->q; g.ldo_t = d; g.out_kp = V->kp; g.kp_col0 = d; g.out_vp = V->vp; g.vp_col0 = 2 * d; g.kv_L = L; g.kv_Lpad = Lpad; g.kv_hd = hd;
     FCK(fdm_op_gemm(&g, stream));
@@ -679,16 +616,16 @@ int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B,
     at.dtype = dt; at.scale = 1.0f / std::sqrt((float)d); at.causal = 0; at.period = 1;      // scale = hidden^-0.5 (base_models.py:144)
     at.q_lo_off = lo_md; at.kv_lo_off = lo_kv; at.o_lo_off = lo_md;
     FCK(fdm_op_attention(&at, stream));
-    g = gemm_args(dt, V->ctx, ly.wo.p, M, d, d);
+    g = dense_gemm(dt, V->ctx, ly.wo.p, M, d, d);
     g.a_lo_off = lo_md; g.w_lo_off = ly.wo.lo;
     g.bias = ly.bo; g.resid = h; g.out_f32 = V->hb;
     FCK(fdm_op_gemm(&g, stream));
     FCK(lnorm(V->hb, ly.ln2g, ly.ln2b));
-    g = gemm_args(dt, V->a, ly.w1.p, M, VQ_FFN, d);
+    g = dense_gemm(dt, V->a, ly.w1.p, M, VQ_FFN, d);
     g.a_lo_off = lo_md; g.w_lo_off = ly.w1.lo; g.out_t_lo_off = lo_mf;
     g.bias = ly.b1; g.act = FDM_ACT_GELU_TANH; g.out_t = V->u;
     FCK(fdm_op_gemm(&g, stream));
-    g = gemm_args(dt, V->u, ly.w2.p, M, d, VQ_FFN);
+    g = dense_gemm(dt, V->u, ly.w2.p, M, d, VQ_FFN);
     g.a_lo_off = lo_mf; g.w_lo_off = ly.w2.lo;
     g.bias = ly.b2; g.resid = V->hb; g.out_f32 = h;
     FCK(fdm_op_gemm(&g, stream));
@@ -700,11 +637,11 @@ int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B,
 int vq_conv_norm_embed(fdm_vq* V, const void* xt, const Mat& conv_w, const float* conv_b, const Mat& emb_w, const float* emb_b, int B, int L, void* stream) {
   const int d = VQ_HIDDEN, dt = V->front_dtype(), M = B * L;
   FCK(fdm_op_pad_rows(xt, V->xp, B, L, d, 2, dt, 0, stream));
-  fdm_gemm_args g = gemm_args(dt, V->xp, conv_w.p, L, d, 5 * d);
+  fdm_gemm_args g = dense_gemm(dt, V->xp, conv_w.p, L, d, 5 * d);
   g.lda = d; g.bias = conv_b; g.out_f32 = V->c32; g.batch = B; g.a_batch_stride = (long long)(L + 4) * d; g.out_batch_stride = (long long)L * d;
   FCK(fdm_op_gemm(&g, stream));
   FCK(fdm_op_leaky_instnorm(V->c32, nullptr, V->nt, B, L, d, 1e-5f, dt, stream));
-  g = gemm_args(dt, V->nt, emb_w.p, M, d, d);
+  g = dense_gemm(dt, V->nt, emb_w.p, M, d, d);
   g.bias = emb_b; g.resid = V->pe0; g.ldr = d; g.resid_row_mod = 1; g.out_f32 = V->h;
   return fdm_op_gemm(&g, stream);
 }
@@ -794,7 +731,7 @@ int fdm_vq_decode(fdm_vq* V, const float* zq_bcl, int B, int R, float* out, void
   const void* xt = nullptr;
   FCK(vq_operand(V, V->x32, V->xt, (long long)M * W, &xt, stream));
   if (q.pre) {
-    fdm_gemm_args g = gemm_args(dt, xt, V->pre_w.p, M, d, W);
+    fdm_gemm_args g = dense_gemm(dt, xt, V->pre_w.p, M, d, W);
     g.bias = V->pre_b;
     if (dt == FDM_F32) g.out_f32 = (float*)V->y; else g.out_t = V->y;
     FCK(fdm_op_gemm(&g, stream));
@@ -804,7 +741,7 @@ int fdm_vq_decode(fdm_vq* V, const float* zq_bcl, int B, int R, float* out, void
   FCK(vq_transformer(V, V->h, V->dec_layers, B, L, stream));
   const void* ht = nullptr;
   FCK(vq_operand(V, V->h, V->a, (long long)M * d, &ht, stream));
-  fdm_gemm_args g = gemm_args(dt, ht, V->out_w.p, M, q.V3, d);
+  fdm_gemm_args g = dense_gemm(dt, ht, V->out_w.p, M, q.V3, d);
   g.bias = V->out_b; g.out_f32 = out;
   return fdm_op_gemm(&g, stream);
 }
@@ -822,7 +759,7 @@ int fdm_vq_encode(fdm_vq* V, const float* x, const float* emo_one_hot, int B, in
   hipLaunchKernelGGL(pad_cols_kernel, dim3(grid_for((long long)M * V->Kp)), dim3(256), 0, (hipStream_t)stream, x, V->xpad32, (long long)M, q.V3, V->Kp);
   const void* xp = nullptr;
   FCK(vq_operand(V, V->xpad32, V->xpt, (long long)M * V->Kp, &xp, stream));
-  fdm_gemm_args g = gemm_args(dt, xp, V->e_map_w.p, M, d, V->Kp);
+  fdm_gemm_args g = dense_gemm(dt, xp, V->e_map_w.p, M, d, V->Kp);
   g.bias = V->e_map_b; g.act = FDM_ACT_LEAKY02; g.out_f32 = V->h2;
   FCK(fdm_op_gemm(&g, stream));
   const float* h = V->h2;
@@ -837,7 +774,7 @@ int fdm_vq_encode(fdm_vq* V, const float* x, const float* emo_one_hot, int B, in
   FCK(vq_transformer(V, V->h, V->enc_layers, B, L, stream));
   if (q.pre) {
     FCK(vq_operand(V, V->h, V->a, (long long)M * d, &ht, stream));
-    g = gemm_args(dt, ht, V->e_post_w.p, M, q.G * q.c, d);
+    g = dense_gemm(dt, ht, V->e_post_w.p, M, q.G * q.c, d);
     g.bias = V->e_post_b; g.out_f32 = latent;
     return fdm_op_gemm(&g, stream);
   }

@@ -2,22 +2,17 @@
 // the boundary, no allocation or synchronisation inside fdm_op_* (so a caller may capture them).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <functional>
-#include <string>
-#include <vector>
 
-#include "../../include/fdm_hip.h"
 #include "elementwise.hpp"
 #include "window.hpp"
-#include "kernels.hpp"
+#include "host.hpp"
 
 namespace fdm {
 thread_local std::string g_err;
-// records the message returned by fdm_last_error() on this thread and hands back `code` (shared with plan.hip)
+// records the message returned by fdm_last_error() on this thread and hands back `code` (kernels.hpp: shared by every host unit)
 int fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -30,8 +25,7 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace fdm
 
 namespace {
-using fdm::fail;
-using fdm::g_err;
+using namespace fdm;
 
 int hip_fail(hipError_t e, const char* what) {
   return fail(FDM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -63,13 +57,6 @@ int submit(Op op, void* stream, const char* what) {
 }
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-int grid_for(long long n) {
-  long long b = (n + 255) / 256;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 }  // namespace
 
@@ -105,9 +92,9 @@ static bool gemm_act_heavy_host(int act) { return act == FDM_ACT_MISH || act == 
 int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
   if (!a || !a->A || !a->W) return fail(FDM_ERR_ARG, "gemm: null operand");
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return fail(FDM_ERR_SHAPE, "gemm: M,N,K must be positive (%d,%d,%d)", a->M, a->N, a->K);
-  if (a->dtype < FDM_F32 || a->dtype > FDM_F16) return fail(FDM_ERR_ARG, "gemm: bad dtype %d", a->dtype);
-  const bool split = a->dtype == FDM_F16X3;
-  const int bk = a->dtype == FDM_F32 ? 32 : 64, epc = a->dtype == FDM_F32 ? 4 : 8;
+  if (!kind_ok(a->dtype)) return fail(FDM_ERR_ARG, "gemm: bad dtype %d", a->dtype);
+  const bool split = kind(a->dtype).planes == 2;
+  const int bk = kind(a->dtype).bk, epc = kind(a->dtype).epc;
   if (split && (a->a_lo_off <= 0 || a->w_lo_off <= 0 || a->a_lo_off % epc || a->w_lo_off % epc))
     return fail(FDM_ERR_ARG, "gemm: split operands need positive a_lo_off / w_lo_off (multiples of 8 elements)");
   if (split && a->out_t && a->out_t_lo_off <= 0) return fail(FDM_ERR_ARG, "gemm: split out_t needs out_t_lo_off");
@@ -183,14 +170,14 @@ int fdm_op_attention(const fdm_attn_args* a, void* stream) {
   if (a->hd != 64 && a->hd != 128 && a->hd != 256) return fail(FDM_ERR_SHAPE, "attention: head_dim %d unsupported (64, 128, 256)", a->hd);
   if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(FDM_ERR_SHAPE, "attention: B,H,L must be positive");
   if (a->Lpad < a->L || a->Lpad % 32) return fail(FDM_ERR_SHAPE, "attention: Lpad=%d must be a multiple of 32 >= L", a->Lpad);
-  if (a->dtype < FDM_F32 || a->dtype > FDM_F16) return fail(FDM_ERR_ARG, "attention: bad dtype %d (FDM_F32, FDM_BF16, FDM_F16X3, FDM_F16)", a->dtype);
+  if (!kind_ok(a->dtype)) return fail(FDM_ERR_ARG, "attention: bad dtype %d (FDM_F32, FDM_BF16, FDM_F16X3, FDM_F16)", a->dtype);
   if (a->o_split && (a->dtype != FDM_F32 || a->o_split != FDM_F16X3 || a->o_lo_off <= 0))
     return fail(FDM_ERR_ARG, "attention: o_split needs dtype FDM_F32, a split kind and o_lo_off");
   if (a->dtype == FDM_F16X3 && (a->q_lo_off <= 0 || a->kv_lo_off <= 0 || a->o_lo_off <= 0 || a->q_lo_off % 8 || a->kv_lo_off % 8 || a->o_lo_off % 4))
     return fail(FDM_ERR_ARG, "attention: split operands need q_lo_off, kv_lo_off and o_lo_off");
   if (a->q_lo_off > 0x7fffffffLL || a->kv_lo_off > 0x7fffffffLL || a->ldq > 0x7fffffffLL)
     return fail(FDM_ERR_SHAPE, "attention: q_lo_off, kv_lo_off and ldq are passed to the kernel as 32-bit element counts");
-  const int epc = a->dtype == FDM_F32 ? 4 : 8;
+  const int epc = kind(a->dtype).epc;
   if (a->ldq % epc || a->ldo % 4 || !aligned16(a->Q) || !aligned16(a->Kp) || !aligned16(a->Vp) || !aligned16(a->O))
     return fail(FDM_ERR_ARG, "attention: operands need 16-byte aligned rows");
   if (a->slopes && a->period <= 0) return fail(FDM_ERR_ARG, "attention: period must be positive");
@@ -214,7 +201,7 @@ int fdm_op_layernorm(const fdm_ln_args* a, void* stream) {
   if (a->d != 256 && a->d != 512 && a->d != 768 && a->d != 1024) return fail(FDM_ERR_SHAPE, "layernorm: d=%d unsupported (256, 512, 768, 1024)", a->d);
   if (a->M <= 0) return fail(FDM_ERR_SHAPE, "layernorm: M must be positive");
   if (!a->y_f32 && !a->y_t) return fail(FDM_ERR_ARG, "layernorm: no output");
-  if (a->dtype < FDM_F32 || a->dtype > FDM_F16) return fail(FDM_ERR_ARG, "layernorm: bad dtype %d", a->dtype);
+  if (!kind_ok(a->dtype)) return fail(FDM_ERR_ARG, "layernorm: bad dtype %d", a->dtype);
   if (a->y_t && a->dtype == FDM_F16X3 && (a->y_t_lo_off <= 0 || a->y_t_lo_off % 4)) return fail(FDM_ERR_ARG, "layernorm: split y_t needs y_t_lo_off");
   if (a->add_mat_group < 0 || a->add_mat_wrap < 0 ||
       (a->add_mat_group > 0 && (a->add_mat_L <= 0 || a->add_mat_group % a->add_mat_L || (a->add_mat_wrap > 0 && a->add_mat_wrap % a->add_mat_group))))
@@ -241,7 +228,7 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
   if (a->mode < 0 || a->mode > 3) return fail(FDM_ERR_ARG, "sched: bad mode %d", a->mode);
   if (a->mode == 3 && !a->noise && (a->n_per_clip <= 0 || a->n_per_clip % 4)) return fail(FDM_ERR_SHAPE, "sched: n_per_clip must be a positive multiple of 4");
   if (a->mode == 0 && !a->noise && (a->n_per_clip <= 0 || a->n_per_clip % 4)) return fail(FDM_ERR_SHAPE, "sched: n_per_clip must be a positive multiple of 4");
-  if (a->x_out_t && (a->out_dtype < FDM_F32 || a->out_dtype > FDM_F16)) return fail(FDM_ERR_ARG, "sched: bad out_dtype %d", a->out_dtype);
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "sched: bad out_dtype %d", a->out_dtype);
   if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "sched: split x_out_t needs x_out_t_lo_off");
   fdm_sched_args c = *a;
   return submit([c](hipStream_t s) { return fdm::sched_launch(c, s); }, stream, "sched");
@@ -265,7 +252,7 @@ extern "C" {
 
 int fdm_op_cast(const float* src, void* dst, long long n, int dtype, void* stream) {
   if (!src || !dst || n <= 0) return fail(FDM_ERR_ARG, "cast: bad argument");
-  if (dtype < FDM_F32 || dtype > FDM_F16) return fail(FDM_ERR_ARG, "cast: bad dtype %d", dtype);
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "cast: bad dtype %d", dtype);
   return submit([=](hipStream_t s) {
     const dim3 g(grid_for(n)), b(256);
     if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::cast_kernel<fdm::bf16>), g, b, 0, s, src, (fdm::bf16*)dst, n);
@@ -305,9 +292,11 @@ int fdm_op_small_linear(const float* x, const float* W, const float* bias, float
 
 int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream) {
   if (!in || !out || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "pad_rows: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "pad_rows: bad dtype %d", dtype);
   const long long n = (long long)B * (L + 2 * pad) * d;
+  const bool two_byte = kind(dtype).bytes == 2;      // a pure move: every 2-byte kind (one plane of a split operand included) moves as bf16 bit patterns
   return submit([=](hipStream_t s) {
-    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::pad_rows_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, L, d, pad, zero);
+    if (two_byte) hipLaunchKernelGGL((fdm::pad_rows_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, L, d, pad, zero);
     else hipLaunchKernelGGL((fdm::pad_rows_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, L, d, pad, zero);
     return hipGetLastError();
   }, stream, "pad_rows");
@@ -315,9 +304,11 @@ int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int
 
 int fdm_op_group_pad(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, void* stream) {
   if (!in || !out || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "group_pad: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "group_pad: bad dtype %d", dtype);
   const long long n = (long long)B * (T + 2 * pad) * d;
+  const bool two_byte = kind(dtype).bytes == 2;      // (one plane of a split operand moves like any 2-byte matrix: the caller passes each plane)
   return submit([=](hipStream_t s) {
-    if (dtype == FDM_BF16 || dtype == FDM_F16X3)      // (one plane of a split operand moves like any 2-byte matrix: the caller passes each plane)
+    if (two_byte)
       hipLaunchKernelGGL((fdm::group_pad_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, T, d, groups, pad);
     else hipLaunchKernelGGL((fdm::group_pad_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, T, d, groups, pad);
     return hipGetLastError();
@@ -348,6 +339,8 @@ int fdm_op_conv0_ln_gelu(const float* wav, const float* w, const float* bias, co
 
 int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, void* stream) {
   if (!x || (!y_f32 && !y_t) || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "leaky_instnorm: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "leaky_instnorm: bad dtype %d", dtype);
+  if (y_t && dtype != FDM_F32 && dtype != FDM_BF16) return fail(FDM_ERR_ARG, "leaky_instnorm: y_t dtype %d (fp32 or bf16 output)", dtype);
   return submit([=](hipStream_t s) {
     dim3 grid((d + 63) / 64, B);
     if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::leaky_instnorm_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, y_f32, (fdm::bf16*)y_t, L, d, eps);
@@ -359,6 +352,8 @@ int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L,
 int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
                           float eps, int act, int dtype, void* scratch, long long scratch_bytes, void* stream) {
   if (!x || (!y_f32 && !y_t) || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "time_groupnorm: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "time_groupnorm: bad dtype %d", dtype);
+  if (y_t && dtype == FDM_F16) return fail(FDM_ERR_ARG, "time_groupnorm: y_t dtype %d (fp32, bf16 or FDM_F16X3 output)", dtype);
   if (y_t && dtype == FDM_F16X3 && y_t_lo_off <= 0) return fail(FDM_ERR_ARG, "time_groupnorm: split y_t needs y_t_lo_off");
   // long clips with a scratch buffer: statistics and normalisation over time chunks (two launches, hundreds of workgroups)
   const int nch = T >= 4096 ? std::min(64, (T + 1023) / 1024) : 1;

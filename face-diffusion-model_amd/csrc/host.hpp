@@ -1,0 +1,91 @@
+// Host-side helpers shared by the C layers of libfdm_hip.so (fdm_hip.hip, plan.hip, tune.hip, host_tables.hip, encoders.hip):
+// error macros, the operand-kind table, device-memory arenas and the operand / GEMM-argument constructors.  No device code;
+// the kernel units (gemm_*.hip, attn_*.hip) do not include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "kernels.hpp"
+
+#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fdm::fail(FDM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+#define FCK(x) do { int r_ = (x); if (r_ != FDM_OK) return r_; } while (0)
+
+namespace fdm {
+
+// blocks of 256 threads for a grid-stride loop over n elements
+inline int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
+
+// ---- operand kinds (FDM_F32 | FDM_BF16 | FDM_F16X3 | FDM_F16): the one place that knows their geometry
+struct Kind {
+  int bytes;       // per element of one plane
+  int planes;      // 2 = split kind (hi plane, lo plane lo_off elements behind it)
+  int bk;          // k-tile of the GEMM kernels (K must be a multiple)
+  int epc;         // elements per 16 bytes (row strides and offsets must be multiples)
+  size_t full() const { return (size_t)bytes * planes; }      // bytes per matrix element over all planes
+};
+inline bool kind_ok(int dtype) { return dtype >= FDM_F32 && dtype <= FDM_F16; }
+inline const Kind& kind(int dtype) {      // (callers check kind_ok first; an unknown code reads as FDM_F32)
+  static const Kind table[4] = {{4, 1, 32, 4}, {2, 1, 64, 8}, {2, 2, 64, 8}, {2, 1, 64, 8}};
+  return table[kind_ok(dtype) ? dtype : FDM_F32];
+}
+
+struct Wt { float* p = nullptr; long long n = 0; };       // fp32 weight / buffer by reference state-dict name
+struct Mat { void* p = nullptr; long long lo = 0; };      // operand-kind matrix: pointer + hi->lo plane distance (elements; 0 = one plane)
+
+// device allocations with one lifetime
+struct Arena {
+  std::vector<void*> allocs;
+  int alloc(void** out, size_t bytes, bool zero = false) {
+    void* p = nullptr;
+    HIPCK(hipMalloc(&p, bytes ? bytes : 16));
+    if (zero) HIPCK(hipMemset(p, 0, bytes ? bytes : 16));
+    allocs.push_back(p);
+    *out = p;
+    return FDM_OK;
+  }
+  template <typename T> int alloc_t(T** out, size_t n, bool zero = false) { return alloc((void**)out, n * sizeof(T), zero); }
+  void free_one(void* p) {      // (the caller has drained whatever may still read p)
+    auto it = std::find(allocs.begin(), allocs.end(), p);
+    if (it == allocs.end()) return;
+    allocs.erase(it);
+    (void)hipFree(p);
+  }
+  void release() { for (void* p : allocs) (void)hipFree(p); allocs.clear(); }
+};
+
+inline int need_weight(const std::map<std::string, Wt>& w, const char* who, const std::string& name, long long n, const float** out) {
+  auto it = w.find(name);
+  if (it == w.end()) return fail(FDM_ERR_STATE, "%smissing weight %s", who, name.c_str());
+  if (it->second.n != n) return fail(FDM_ERR_SHAPE, "%sweight %s has %lld elements, expected %lld", who, name.c_str(), it->second.n, n);
+  *out = it->second.p;
+  return FDM_OK;
+}
+
+// GEMM args with the defaults the op layer's callers use (dense row-major operands, one batch)
+inline fdm_gemm_args dense_gemm(int dtype, const void* A, const void* W, int M, int N, int K) {
+  fdm_gemm_args a;
+  memset(&a, 0, sizeof(a));
+  a.A = A; a.lda = K; a.W = W; a.ldw = K; a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = dtype;
+  a.ldr = N; a.ldo_f32 = N; a.ldo_t = N; a.ln_eps = 1e-5f;
+  return a;
+}
+
+// operand-kind copy of n fp32 elements, allocated from `mem` (FDM_F32: the fp32 array itself; split kinds: fdm_op_cast writes the
+// lo plane n elements after the hi plane)
+inline int to_operand(Arena& mem, int dtype, const float* src, long long n, Mat* out, void* stream) {
+  out->lo = kind(dtype).planes == 2 ? n : 0;
+  if (dtype == FDM_F32) { out->p = (void*)src; return FDM_OK; }
+  FCK(mem.alloc(&out->p, (size_t)n * kind(dtype).full()));
+  return fdm_op_cast(src, out->p, n, dtype, stream);
+}
+
+// host tables that the plan layer also uses directly (host_tables.hip; include/fdm_hip.h states the rules)
+int window_layout(int L, int W, int O, std::vector<int>& starts);
+void window_weights(int L, int W, int O, const std::vector<int>& starts, std::vector<float>& out);
+
+}  // namespace fdm

@@ -1,5 +1,5 @@
 // Launchers of the heavy kernel families, one translation unit per operand kind (gemm_*.hip, attn_*.hip) so that the
-// library builds in parallel; fdm_hip.hip (the C ABI + the bandwidth kernels) calls them through these declarations.
+// library builds in parallel; fdm_hip.hip (the C ABI + the bandwidth kernels) calls them through these declarations (host-only helpers: host.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/fdm_hip.h"
@@ -18,7 +18,7 @@ hipError_t attn_launch_f16(const fdm_attn_args& a, hipStream_t s);
 hipError_t pack_kv_launch_f32(const void* K, long long ldk, const void* V, long long ldv, void* Kp, void* Vp, int B, int H, int L, int Lpad, int hd, hipStream_t s);
 hipError_t pack_kv_launch_bf16(const void* K, long long ldk, const void* V, long long ldv, void* Kp, void* Vp, int B, int H, int L, int Lpad, int hd, hipStream_t s);
 
-// windowed sampling (window.hpp, plan.hip): frame f of a long clip is covered by the windows ent[off[f] .. off[f + 1]) in ascending
+// windowed sampling (window.hpp; tables built by fdm_audio_prepare_windows, plan.hip): frame f of a long clip is covered by the windows ent[off[f] .. off[f + 1]) in ascending
 // window order, each with its start frame and normalised blend weight; one table serves every long clip of the batch
 struct WinEnt { int w; int start; float wt; int pad; };
 struct WinArgs {

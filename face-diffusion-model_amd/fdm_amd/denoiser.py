@@ -1,5 +1,6 @@
 """Denoiser + scheduler plan: a thin binding of the library's plan layer (include/fdm_hip.h: fdm_plan_create,
-fdm_plan_set_weights, fdm_audio_prepare, fdm_denoise_step, fdm_sample_graph; implementation csrc/plan.hip).
+fdm_plan_set_weights, fdm_audio_prepare, fdm_denoise_step, fdm_sample_graph; implementation csrc/plan.hip, with the tile
+tuner in csrc/tune.hip and the host tables -- schedules, sampler tables, window layout -- in csrc/host_tables.hip).
 
 The per-step FDM forward (models/fdm_vocaset.py:54-91, models/fdm_vqvae_mead.py:65-104) and the sampling loops
 (diffusion_BIWI_encoder_decoder.py:649-710, diffusion_mead_encoder_decoder.py:649-667) live in C++ / HIP:

@@ -177,6 +177,42 @@ def test_program_recording_and_split_validation_without_device():
     assert l.fdm_plan_get(None, b"rows", C.byref(C.c_longlong())) == -1
 
 
+def test_operand_kind_of_the_move_and_norm_ops_is_validated():
+    """fdm_op_pad_rows / fdm_op_group_pad / fdm_op_leaky_instnorm / fdm_op_time_groupnorm look at `dtype`: an unknown code is an
+    argument error, the two moves take every kind (routed by element size), the two norms take the kinds they have a y_t kernel
+    for -- and do not care when only y_f32 is written.  Accepted calls are recorded, nothing is launched."""
+    from fdm_amd import _lib
+    l = _lib.lib()
+    F32, BF16, F16X3, F16 = _lib.F32, _lib.BF16, _lib.F16X3, _lib.F16
+    pad_rows = lambda dt: l.fdm_op_pad_rows(16, 16, 2, 5, 8, 3, dt, 0, None)
+    group_pad = lambda dt: l.fdm_op_group_pad(16, 16, 2, 5, 8, 2, 3, dt, None)
+    instnorm = lambda dt, y32, yt: l.fdm_op_leaky_instnorm(16, y32, yt, 2, 5, 8, 1e-5, dt, None)
+    groupnorm = lambda dt, y32, yt: l.fdm_op_time_groupnorm(16, 16, 16, y32, yt, 80 if yt else 0, 2, 5, 8, 1e-5, 0, dt, None, 0, None)
+    h = C.c_void_p()
+    assert l.fdm_prog_create(C.byref(h)) == 0 and l.fdm_prog_begin(h) == 0
+    for op in (pad_rows, group_pad, lambda dt: instnorm(dt, 16, None), lambda dt: groupnorm(dt, 16, None),
+               lambda dt: instnorm(dt, None, 16), lambda dt: groupnorm(dt, None, 16)):
+        assert op(7) == -1 and b"dtype" in l.fdm_last_error()
+        assert op(-1) == -1 and b"dtype" in l.fdm_last_error()
+    assert l.fdm_prog_num_ops(h) == 0
+    n = 0
+    for dt in (F32, BF16, F16X3, F16):
+        assert pad_rows(dt) == 0 and group_pad(dt) == 0
+        assert instnorm(dt, 16, None) == 0 and groupnorm(dt, 16, None) == 0          # y_f32 only: dtype names no output
+        n += 4
+    for dt in (F32, BF16):
+        assert instnorm(dt, None, 16) == 0
+        n += 1
+    for dt in (F32, BF16, F16X3):
+        assert groupnorm(dt, None, 16) == 0
+        n += 1
+    assert instnorm(F16X3, None, 16) == -1 and b"dtype" in l.fdm_last_error()         # no split-output kernel
+    assert instnorm(F16, None, 16) == -1 and b"dtype" in l.fdm_last_error()
+    assert groupnorm(F16, None, 16) == -1 and b"dtype" in l.fdm_last_error()
+    assert instnorm(F16, 16, 16) == -1 and groupnorm(F16, 16, 16) == -1               # y_t given: its kind counts
+    assert l.fdm_prog_end(h) == 0 and l.fdm_prog_num_ops(h) == n == 21 and l.fdm_prog_destroy(h) == 0
+
+
 def test_plan_layer_argument_validation_without_device():
     """The plan layer reports bad arguments before touching a device (null handles, bad geometry / kinds / dtypes)."""
     from fdm_amd import _lib

@@ -634,6 +634,29 @@ def test_small_ops():
     torch.cuda.synchronize()
 
 
+def test_pad_rows_and_group_pad_move_fp16_by_element_size():
+    """ops.pad_rows / ops.group_pad on a torch.float16 tensor (operand kind FDM_F16): pure moves, so the output bits equal those of
+    the same call on the tensor's bit pattern viewed as bfloat16, and nothing is written outside the output (a 2-byte tensor
+    handed to the 4-byte kernel would read and write twice the buffer).  [2, 5, 8], pad 3, 2 groups: the smallest shape where
+    row, pad and group indexing all matter (odd L and pad keep the row and pad counts apart)."""
+    GUARD, SENT = 64, -7.0
+    x16 = torch.randn(2, 5, 8, generator=torch.Generator().manual_seed(5)).to(torch.float16).to(DEV)
+    n_out = 2 * (5 + 2 * 3) * 8
+
+    def run(x, op):
+        buf = torch.full((GUARD + n_out + GUARD,), SENT, dtype=x.dtype, device=DEV)
+        op(x, buf[GUARD:GUARD + n_out])
+        torch.cuda.synchronize()
+        assert bool((buf[:GUARD] == SENT).all()) and bool((buf[GUARD + n_out:] == SENT).all()), "wrote outside the output"
+        return buf[GUARD:GUARD + n_out].view(torch.int16).cpu()
+
+    moves = [lambda x, o: ops.pad_rows(x, o, 2, 5, 8, 3, zero=False), lambda x, o: ops.pad_rows(x, o, 2, 5, 8, 3, zero=True),
+             lambda x, o: ops.group_pad(x, o, 2, 5, 8, 2, 3)]
+    for op in moves:
+        got, want = run(x16, op), run(x16.view(torch.bfloat16), op)
+        assert torch.equal(got, want)       # (an op that moved nothing would leave two different sentinel bit patterns behind)
+
+
 def test_program_record_graph_replay():
     """Record two ops, run eagerly, then replay as a hipGraph with a device-side step counter."""
     n = 4096
