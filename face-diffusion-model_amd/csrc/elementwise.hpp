@@ -16,7 +16,9 @@ namespace fdm {
 // 800 rows against 5.4 us here; HEAVY = the activation may be a transcendental one -- GELU after HuBERT's conv LayerNorm --
 // and is templated out of the step's instances: the inlined libm forms were 90 % of that kernel's code.)
 // ------------------------------------------------------------------------------------------------
-template <typename T, int NV, bool HEAVY>
+// CLIP = the table row is chosen per clip (fdm_ln_args.clip_step: the slot program, whose clips sit at different diffusion steps); a
+// specialisation, so the instances of the plain programs keep the single step word and their registers.
+template <typename T, int NV, bool HEAVY, bool CLIP = false>
 __global__ __launch_bounds__(64 * NV) void ln_row_kernel(const float* p_x, const float* p_add_mat, const float* p_add_tab, const int* p_tab_step,
                                                          const int* p_tab_index, int p_add_mat_group, int p_add_mat_wrap, int p_add_mat_L,
                                                          const fdm_ln_args p) {
@@ -54,7 +56,13 @@ __global__ __launch_bounds__(64 * NV) void ln_row_kernel(const float* p_x, const
   const f32x4 g2 = *(const f32x4*)(gp2 + col), b2 = *(const f32x4*)(bp2 + col);
   f32x4 et = zero;
   if (p_add_tab) {
-    const int k = p_tab_step ? *p_tab_step : 0;
+    int k;
+    if constexpr (CLIP) {              // (uniform: scalar arithmetic) the step word of the row's clip
+      const int m = p.clip_wrap > 0 ? row % p.clip_wrap : row;
+      k = p.clip_step[(size_t)(m / p.clip_rows) * p.clip_step_stride];
+    } else {
+      k = p_tab_step ? *p_tab_step : 0;
+    }
     const int idx = p_tab_index ? p_tab_index[k] : k;
     et = *(const f32x4*)(p_add_tab + (size_t)idx * d + col);
   }
@@ -123,6 +131,20 @@ __global__ __launch_bounds__(64 * NV) void ln_row_kernel(const float* p_x, const
 template <typename T, bool HEAVY>
 static hipError_t ln_launch_h(const fdm_ln_args& a, hipStream_t s) {
   dim3 grid(a.M);
+  if constexpr (!HEAVY) {
+    if (a.clip_step) {
+      switch (a.d) {
+        case 256: hipLaunchKernelGGL((ln_row_kernel<T, 1, false, true>), grid, dim3(64), 0, s, LN_PRELOAD_ARGS, a); break;
+        case 512: hipLaunchKernelGGL((ln_row_kernel<T, 2, false, true>), grid, dim3(128), 0, s, LN_PRELOAD_ARGS, a); break;
+        case 768: hipLaunchKernelGGL((ln_row_kernel<T, 3, false, true>), grid, dim3(192), 0, s, LN_PRELOAD_ARGS, a); break;
+        case 1024: hipLaunchKernelGGL((ln_row_kernel<T, 4, false, true>), grid, dim3(256), 0, s, LN_PRELOAD_ARGS, a); break;
+        default: return hipErrorInvalidValue;
+      }
+      return hipGetLastError();
+    }
+  } else if (a.clip_step) {
+    return hipErrorInvalidValue;       // (fdm_op_layernorm refuses it)
+  }
   switch (a.d) {
     case 256: hipLaunchKernelGGL((ln_row_kernel<T, 1, HEAVY>), grid, dim3(64), 0, s, LN_PRELOAD_ARGS, a); break;
     case 512: hipLaunchKernelGGL((ln_row_kernel<T, 2, HEAVY>), grid, dim3(128), 0, s, LN_PRELOAD_ARGS, a); break;

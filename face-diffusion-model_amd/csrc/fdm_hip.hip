@@ -8,6 +8,7 @@
 
 #include "elementwise.hpp"
 #include "window.hpp"
+#include "slots.hpp"
 #include "host.hpp"
 
 namespace fdm {
@@ -208,6 +209,9 @@ int fdm_op_layernorm(const fdm_ln_args* a, void* stream) {
     return fail(FDM_ERR_SHAPE, "layernorm: shared add_mat needs add_mat_L | add_mat_group | add_mat_wrap (got %d, %d, %d)", a->add_mat_L, a->add_mat_group, a->add_mat_wrap);
   if (a->x_planes < 0 || a->x_planes > 4 || (a->x_planes > 1 && (a->x_plane_stride < (long long)a->M * a->d || a->x_plane_stride % 4)))
     return fail(FDM_ERR_ARG, "layernorm: x_planes %d (0..4) needs x_plane_stride >= M * d, a multiple of 4", a->x_planes);
+  if (a->clip_step && (a->clip_rows <= 0 || a->clip_step_stride <= 0 || a->clip_wrap < 0 || (a->clip_wrap > 0 && a->clip_wrap % a->clip_rows)))
+    return fail(FDM_ERR_SHAPE, "layernorm: clip_step needs clip_rows > 0, clip_step_stride > 0 and clip_rows | clip_wrap (got %d, %d, %d)", a->clip_rows, a->clip_step_stride, a->clip_wrap);
+  if (a->clip_step && a->act != FDM_ACT_NONE && a->act != FDM_ACT_RELU) return fail(FDM_ERR_ARG, "layernorm: clip_step runs with FDM_ACT_NONE / FDM_ACT_RELU only");
   fdm_ln_args c = *a;
   return submit([c](hipStream_t s) {
     switch (c.dtype) {
@@ -234,7 +238,42 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
   return submit([c](hipStream_t s) { return fdm::sched_launch(c, s); }, stream, "sched");
 }
 
+int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, void* stream) {
+  if (!a || !a->x0 || !a->x || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_sched: null operand");
+  if (a->noise) return fail(FDM_ERR_ARG, "slot_sched: injected noise is not supported (Philox keyed per slot)");
+  if (a->mode != 0 && a->mode != 1 && a->mode != 3) return fail(FDM_ERR_ARG, "slot_sched: mode %d (0 DDPM, 1 DDIM, 3 table-driven)", a->mode);
+  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_sched: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
+  if (a->mode == 0 && (!a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "slot_sched: DDPM tables missing");
+  if (a->mode == 1 && (!a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "slot_sched: DDIM tables missing");
+  if (a->mode == 3 && (!a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist)) return fail(FDM_ERR_ARG, "slot_sched: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist");
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_sched: bad out_dtype %d", a->out_dtype);
+  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_sched: split x_out_t needs x_out_t_lo_off");
+  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state))
+    return fail(FDM_ERR_ARG, "slot_sched: operands and the state words must be 16-byte aligned");
+  fdm_sched_args c = *a;
+  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
+  return submit([c, state, keys](hipStream_t s) { return fdm::slot_sched_launch(c, state, keys, s); }, stream, "slot_sched");
+}
+
 }  // extern "C"
+
+// the two small launches of the slot program that are not public operators (slots.hpp): recorded like any fdm_op_*
+int fdm::slot_advance_op(int* state, const int* tseq, int n_steps, int n_slots, void* stream) {
+  if (!state || !tseq || n_steps < 1 || n_slots < 1) return fail(FDM_ERR_ARG, "slot_advance: bad argument");
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::slot_advance_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state, tseq, n_steps, n_slots);
+    return hipGetLastError();
+  }, stream, "slot_advance");
+}
+int fdm::slot_set_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id, void* stream) {
+  if (!state || !keys || slot < 0) return fail(FDM_ERR_ARG, "slot_set: bad argument");
+  const fdm::SlotState v{k, t, live, run};
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::slot_set_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state + slot, v, keys + 2 * (size_t)slot, seed, (unsigned long long)(unsigned)clip_id);
+    return hipGetLastError();
+  }, stream, "slot_set");
+}
 
 // windowed sampling's blend + scheduler pass (window.hpp): not a public operator -- the plan layer records it into the step program
 // of a windowed plan (fdm_sample_windows)

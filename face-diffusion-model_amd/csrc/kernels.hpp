@@ -33,6 +33,10 @@ struct WinArgs {
 // fdm_hip.hip: records / launches window_sched_kernel like any fdm_op_* (p in long layout, see window.hpp)
 int window_sched_op(const fdm_sched_args& p, const WinArgs& w, void* stream);
 
+// in-flight batching (slots.hpp): advance every slot's {k, t, live, run} word once per step; set one slot's word and noise key
+int slot_advance_op(int* state, const int* tseq, int n_steps, int n_slots, void* stream);
+int slot_set_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id, void* stream);
+
 inline hipError_t gemm_launch(const fdm_gemm_args& a, hipStream_t s) {
   switch (a.dtype) {
     case FDM_BF16: return gemm_launch_bf16(a, s);

@@ -343,7 +343,7 @@ int fdm::record_chain(fdm_plan* P, const fdm_sched_args* sched, void* stream) {
     g.resid = P->E0; g.out_f32 = P->h;
     if (both) set_out_t(g, P->ht);
     g.batch = P->rep; g.out_batch_stride = (long long)M * d;
-    g.incr_counter = step; g.incr_table = P->tseq;
+    if (!P->slots) { g.incr_counter = step; g.incr_table = P->tseq; }      // (slot mode: the advance launch moved every slot's own word)
     FCK(plan_gemm(P, "enc", g, stream));
   }
   const int BB = P->B * P->rep;
@@ -389,6 +389,9 @@ int fdm::record_chain(fdm_plan* P, const fdm_sched_args* sched, void* stream) {
     memset(&ln, 0, sizeof(ln));
     ln.x = P->x1; ln.M = R; ln.d = d; ln.add_mat = P->C1[l]; ln.add_tab = P->TT[l]; ln.tab_step = tcur; ln.eps = eps;
     if (P->S > 1) { ln.add_mat_L = L; ln.add_mat_group = P->S * L; ln.add_mat_wrap = M; }     // C1_l holds one block per audio clip
+    if (P->slots) {      // every slot gathers TT_l by the t word of its own state (both CFG halves share it)
+      ln.tab_step = nullptr; ln.clip_step = P->slot_state + 1; ln.clip_step_stride = 4; ln.clip_rows = L; ln.clip_wrap = M;
+    }
     if (!f) set_ksplit(ln, P->ksplit_out, (long long)R * d);
     FCK(need(P, lname(l, "norm1.weight"), d, &ln.gamma)); FCK(need(P, lname(l, "norm1.bias"), d, &ln.beta));
     FCK(need(P, lname(l, "norm2.weight"), d, &ln.gamma2)); FCK(need(P, lname(l, "norm2.bias"), d, &ln.beta2));
@@ -444,6 +447,7 @@ struct ProgSpec {
   const float* noise = nullptr; float cfg_scale = 0.f;
   const float* san = nullptr; const float* cn = nullptr;
   int reps = 1;              // diffusion steps recorded back to back (one graph launch runs them all)
+  int slot_steps = 0;        // > 0: the slot program of a chain of that many steps (advance launch, chain, slot scheduler pass)
 };
 
 // Recorded programs are kept per (shape, tile set, program kind): a serving loop that alternates between shapes (clips of
@@ -473,6 +477,10 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
     const size_t kl = strlen(key);
     snprintf(key + kl, sizeof(key) - kl, "|win%d,%d,%d,%d,%d", P->win_B, P->win_total, P->win_n, P->win_len, P->win_overlap);
   }
+  if (P->slots) {            // slot mode: the chain gathers per slot and nothing advances P->step (plain keys unchanged)
+    const size_t kl = strlen(key);
+    snprintf(key + kl, sizeof(key) - kl, "|slot%d,%d,%p", sp.slot_steps, P->slots, (const void*)sp.cn);
+  }
   auto it = P->progs.find(key);
   if (it != P->progs.end()) {            // hit: most recently used goes to the back, and the caller's handle stays valid for this call
     auto pos = std::find(P->prog_order.begin(), P->prog_order.end(), std::string(key));
@@ -501,7 +509,7 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
   fdm_prog* prog = nullptr;
   FCK(fdm_prog_create(&prog));
   int rc = fdm_prog_begin(prog);
-  const bool fuse_sched = !P->cfg && sp.kind != 0;
+  const bool fuse_sched = !P->cfg && sp.kind != 0 && !sp.slot_steps;
   for (int rep = 0; rc == FDM_OK && rep < sp.reps; ++rep) {
     fdm_sched_args sc;
     memset(&sc, 0, sizeof(sc));
@@ -518,6 +526,15 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       sc.lm_a = P->lm_tab; sc.lm_b = P->lm_tab + P->lm_cap; sc.lm_c = P->lm_tab + 2 * (size_t)P->lm_cap; sc.lm_s = P->lm_tab + 3 * (size_t)P->lm_cap;
       sc.x0_hist = P->win_n ? P->hist_long : P->x0_hist;
       sc.noise = sp.noise; sc.noise_stride = n; sc.seed_dev = P->seedbuf;
+    }
+    if (sp.slot_steps) {
+      // slot program: advance every slot's word, the chain with per-slot table rows and its scheduler update unfused, then the
+      // pass that updates the live slots only -- two launches more than the plain program without guidance
+      sc.n_per_clip = (long long)P->L * d; sc.noise = nullptr; sc.seed_dev = nullptr; sc.step = nullptr; sc.tseq = nullptr;
+      rc = fdm::slot_advance_op(P->slot_state, P->tseq, sp.slot_steps, P->slots, stream);
+      if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
+      if (rc == FDM_OK) rc = fdm_op_slot_sched(&sc, P->slot_state, P->slot_keys, P->slots, stream);
+      continue;
     }
     if (sp.kind != 0 && P->win_n) {
       // windowed plan: the chain unfused, then one pass over the long layout -- blend the windows' x0 (after their CFG mix), update
@@ -632,14 +649,10 @@ int take_steps(const fdm_sample_args* a, std::vector<int>& ts) {
   return FDM_OK;
 }
 
-// fdm_sample_graph (plain plan, x in plan layout) and fdm_sample_windows (windowed plan, x_T / out / noise / record in long layout)
-int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
-  P->pinned.clear();
-  if (!a || !a->x_T || !a->out) return fail(FDM_ERR_ARG, "sample_graph: null argument");
+// the sampler of a call: its timestep list, its program kind and its device tables (DDIM: cached per step count; table-driven:
+// uploaded per call, history zeroed).  Shared by fdm_sample_graph / fdm_sample_windows and fdm_slots_open.
+int sampler_setup(fdm_plan* P, const fdm_sample_args* a, void* stream, std::vector<int>& ts, ProgSpec& sp) {
   hipStream_t s = (hipStream_t)stream;
-  std::vector<int> ts;
-  ProgSpec sp;
-  sp.cfg_scale = a->cfg_scale;
   if (a->kind == 0) {
     if (!a->t_list || a->n_steps <= 0) return fail(FDM_ERR_ARG, "sample_graph: DDPM needs t_list / n_steps");
     FCK(take_steps(a, ts));
@@ -679,6 +692,18 @@ int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   } else {
     return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", a->kind);
   }
+  return FDM_OK;
+}
+
+// fdm_sample_graph (plain plan, x in plan layout) and fdm_sample_windows (windowed plan, x_T / out / noise / record in long layout)
+int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  P->pinned.clear();
+  if (!a || !a->x_T || !a->out) return fail(FDM_ERR_ARG, "sample_graph: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> ts;
+  ProgSpec sp;
+  sp.cfg_scale = a->cfg_scale;
+  FCK(sampler_setup(P, a, stream, ts, sp));
   // {Philox seed, global index of clip 0} of the samplers that draw noise in-kernel (set_steps() below drains the copy)
   const unsigned long long sd[2] = {a->seed, (unsigned long long)(unsigned)a->clip0};
   if (a->kind != 1) HIPCK(hipMemcpyAsync(P->seedbuf, sd, 16, hipMemcpyHostToDevice, s));
@@ -723,6 +748,53 @@ int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
     }
   }
   HIPCK(hipMemcpyAsync(a->out, xc, nb, hipMemcpyDeviceToDevice, s));
+  return FDM_OK;
+}
+// The per-clip GEMMs of the prepare, shared by fdm_audio_prepare_conds (all clips at once) and fdm_slot_admit (one slot's rows).
+// Every GEMM is row-independent and accumulates k in one order, so a clip's rows do not depend on how many rows ride the launch.
+// clip_audio_in: t1[row0 .. row0 + rows) = Mish(audio_extract.0(hub rows of one clip)).
+int clip_audio_in(fdm_plan* P, const float* hub_clip, int row0, int rows, void* stream) {
+  const fdm_model_desc& m = P->m;
+  const float *w0 = nullptr, *b0 = nullptr;
+  FCK(need(P, "audio_extract.0.weight", (long long)m.d * m.audio_in, &w0)); FCK(need(P, "audio_extract.0.bias", m.d, &b0));
+  fdm_gemm_args g = dense_gemm(FDM_F32, hub_clip, w0, rows, m.d, m.audio_in);
+  g.bias = b0; g.act = FDM_ACT_MISH; g.out_f32 = P->t1 + (size_t)row0 * m.d;
+  return fdm_op_gemm(&g, stream);
+}
+// clip_tables: AF = audio_extract.2(t1) and C1_l = Wo_l (Wv_l AF + bv_l) + bo_l for the rows [row0, row0 + rows) (t1's rows are
+// reused as scratch); uncond_off > 0: every C1_l row block is copied that many elements on (the uncond half of a CFG plan).
+int clip_tables(fdm_plan* P, int row0, int rows, size_t uncond_off, void* stream) {
+  const fdm_model_desc& m = P->m;
+  const int d = m.d;
+  const size_t o = (size_t)row0 * d;
+  const float *w2 = nullptr, *b2 = nullptr;
+  FCK(need(P, "audio_extract.2.weight", (long long)d * d, &w2)); FCK(need(P, "audio_extract.2.bias", d, &b2));
+  fdm_gemm_args g = dense_gemm(FDM_F32, P->t1 + o, w2, rows, d, d);
+  g.bias = b2; g.out_f32 = P->AF + o;
+  FCK(fdm_op_gemm(&g, stream));
+  for (int l = 0; l < m.n_layers; ++l) {
+    g = dense_gemm(FDM_F32, P->AF + o, P->Wv[l], rows, d, d);
+    g.bias = P->bv[l]; g.out_f32 = P->t1 + o;
+    FCK(fdm_op_gemm(&g, stream));
+    g = dense_gemm(FDM_F32, P->t1 + o, P->Wo[l], rows, d, d);
+    g.bias = P->bo[l]; g.out_f32 = P->C1[l] + o;
+    FCK(fdm_op_gemm(&g, stream));
+    if (uncond_off) HIPCK(hipMemcpyAsync(P->C1[l] + o + uncond_off, P->C1[l] + o, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  return FDM_OK;
+}
+
+// zero n elements (per plane) of an operand-kind matrix starting at element `at`
+int zero_mat(const fdm_plan* P, const Mat& mt, size_t at, size_t n, void* stream) {
+  const size_t eb = kind(P->dtype).bytes;
+  HIPCK(hipMemsetAsync((char*)mt.p + at * eb, 0, n * eb, (hipStream_t)stream));
+  if (mt.lo) HIPCK(hipMemsetAsync((char*)mt.p + ((size_t)mt.lo + at) * eb, 0, n * eb, (hipStream_t)stream));
+  return FDM_OK;
+}
+
+int check_slots(const fdm_plan* P, const char* who) {
+  if (!P) return fail(FDM_ERR_ARG, "%s: null plan", who);
+  if (!P->slots || !P->prepared) return fail(FDM_ERR_STATE, "%s: the plan is not in slot mode (fdm_slots_open)", who);
   return FDM_OK;
 }
 }  // namespace
@@ -802,6 +874,7 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   if (B0 < 1 || N < 1 || fw < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: bad feature shape [%d, %d, %d]", B0, N, fw);
   if (S < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: S=%d conditions per clip", S);
   P->win_n = 0;                              // plain mode (fdm_audio_prepare_windows sets the window mode after this call)
+  P->slots = 0;                              // ... and out of slot mode (slot programs keep their own cache keys)
   if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
   if (L < 1 || L > N / m.pair || L > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare: latent frames L=%d outside [1, min(%d, %d)] (models/fdm_vocaset.py:44,64-66)", L, N / m.pair, m.max_len);
   if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
@@ -812,35 +885,18 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   // before (serving) finds them and their instantiated graphs again (get_program keys them by shape and tile set)
   hipStream_t s = (hipStream_t)stream;
   const int d = m.d, M0 = B0 * L, M = B * L, rep = cfg ? 2 : 1;
+  (void)d;
   P->B = B; P->S = S; P->L = L; P->M = M; P->rep = rep; P->R = M * rep; P->cfg = cfg ? 1 : 0; P->Lpad = (L + 31) / 32 * 32;
   // pad keys of the packed K / V buffers must be finite: the layout depends on (L, Lpad), so clear them per shape
   HIPCK(hipMemsetAsync(P->kp, 0, P->kv_bytes, s));
   HIPCK(hipMemsetAsync(P->vp, 0, P->kv_bytes, s));
-  const float *w0 = nullptr, *b0 = nullptr, *w2 = nullptr, *b2 = nullptr;
-  FCK(need(P, "audio_extract.0.weight", (long long)d * m.audio_in, &w0)); FCK(need(P, "audio_extract.0.bias", d, &b0));
-  FCK(need(P, "audio_extract.2.weight", (long long)d * d, &w2)); FCK(need(P, "audio_extract.2.bias", d, &b2));
   // audio rows: `pair` consecutive encoder frames per latent frame (models/fdm_vqvae_mead.py:73), cropped to L (:64-66);
   // the rows of a clip are contiguous in hub, so each clip's GEMM reads them in place (fp32: once per clip, parity)
-  for (int b = 0; b < B0; ++b) {
-    fdm_gemm_args g = dense_gemm(FDM_F32, hub + (size_t)b * N * fw, w0, L, d, m.audio_in);
-    g.bias = b0; g.act = FDM_ACT_MISH; g.out_f32 = P->t1 + (size_t)b * L * d;
-    FCK(fdm_op_gemm(&g, stream));
-  }
-  fdm_gemm_args g = dense_gemm(FDM_F32, P->t1, w2, M0, d, d);
-  g.bias = b2; g.out_f32 = P->AF;
-  FCK(fdm_op_gemm(&g, stream));
+  for (int b = 0; b < B0; ++b) FCK(clip_audio_in(P, hub + (size_t)b * N * fw, b * L, L, stream));
   // folded cross-attention tables C1_l = Wo_l (Wv_l AF + bv_l) + bo_l.  S = 1: layout [rep][M, d] (the uncond half is a copy);
   // S > 1: ONE block of [B0 * L, d] per layer, every condition (and both CFG halves) of a clip reads its clip's rows through
   // the LayerNorm kernel's row map (fdm_ln_args.add_mat_group) -- no table work per condition
-  for (int l = 0; l < m.n_layers; ++l) {
-    g = dense_gemm(FDM_F32, P->AF, P->Wv[l], M0, d, d);
-    g.bias = P->bv[l]; g.out_f32 = P->t1;
-    FCK(fdm_op_gemm(&g, stream));
-    g = dense_gemm(FDM_F32, P->t1, P->Wo[l], M0, d, d);
-    g.bias = P->bo[l]; g.out_f32 = P->C1[l];
-    FCK(fdm_op_gemm(&g, stream));
-    if (rep == 2 && S == 1) HIPCK(hipMemcpyAsync(P->C1[l] + (size_t)M * d, P->C1[l], (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
-  }
+  FCK(clip_tables(P, 0, M0, (rep == 2 && S == 1) ? (size_t)M * d : 0, stream));
   // conditioning addend E0 = PE[l] + style[b] (+ emotion[b]) (:75-84), one row block per (clip, condition)
   const float *sw = nullptr, *sbias = nullptr;
   FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
@@ -917,6 +973,7 @@ int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int f
 
 int fdm_denoise_step(fdm_plan* P, const float* x_t, int t, float cfg_scale, float* x0_hat, float* x0_uncond, void* stream) {
   FCK(check_ready(P));
+  if (P->slots) return fail(FDM_ERR_STATE, "denoise_step: the plan is in slot mode (fdm_slots_run)");
   P->pinned.clear();
   if (!x_t || !x0_hat || t < 0 || t >= 1000) return fail(FDM_ERR_ARG, "denoise_step: bad argument (t = %d)", t);
   FCK(load_x(P, x_t, stream));
@@ -935,14 +992,183 @@ int fdm_sample_graph(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   FCK(check_tables_args(a));
   FCK(check_ready(P));
   if (P->win_n) return fail(FDM_ERR_STATE, "sample_graph: the plan was prepared for windowed sampling (fdm_sample_windows)");
+  if (P->slots) return fail(FDM_ERR_STATE, "sample_graph: the plan is in slot mode (fdm_slots_run)");
   return sample_impl(P, a, stream);
 }
 
 int fdm_sample_windows(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   FCK(check_tables_args(a));
   FCK(check_ready(P));
+  if (P->slots) return fail(FDM_ERR_STATE, "sample_windows: the plan is in slot mode (fdm_slots_run)");
   if (!P->win_n) return fail(FDM_ERR_STATE, "sample_windows: call fdm_audio_prepare_windows first");
   return sample_impl(P, a, stream);
+}
+
+// ---- in-flight batching (include/fdm_hip.h, "Slots") -------------------------------------------------------------------
+int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a, void* stream) {
+  if (!a) return fail(FDM_ERR_ARG, "slots_open: null sampler");
+  if (a->noise || a->record) return fail(FDM_ERR_ARG, "slots_open: injected noise and record are not supported in slot mode");
+  if (!P) return fail(FDM_ERR_ARG, "slots_open: null plan");
+  FCK(check_tables_args(a));
+  if (B < 1 || L < 1 || L > P->m.max_len) return fail(FDM_ERR_SHAPE, "slots_open: B=%d, L=%d outside [1, .] x [1, %d]", B, L, P->m.max_len);
+  const fdm_model_desc& m = P->m;
+  hipStream_t s = (hipStream_t)stream;
+  P->pinned.clear();
+  P->win_n = 0; P->slots = 0;
+  FCK(commit(P, stream));
+  FCK(reserve(P, B, L, cfg));
+  FCK(grow(P, (void**)&P->slot_state, &P->slot_state_cap, (size_t)B * 16, stream));
+  FCK(grow(P, (void**)&P->slot_keys, &P->slot_keys_cap, (size_t)B * 16, stream));
+  const int d = m.d, M = B * L, rep = cfg ? 2 : 1;
+  P->B = B; P->S = 1; P->L = L; P->M = M; P->rep = rep; P->R = M * rep; P->cfg = cfg ? 1 : 0; P->Lpad = (L + 31) / 32 * 32;
+  // every slot idle and holding zeros: tables, latent (+ operand copy), history, packed K / V pad keys, state words and keys
+  HIPCK(hipMemsetAsync(P->kp, 0, P->kv_bytes, s));
+  HIPCK(hipMemsetAsync(P->vp, 0, P->kv_bytes, s));
+  const size_t nm = (size_t)M * d, nr = (size_t)P->R * d;
+  HIPCK(hipMemsetAsync(P->AF, 0, nm * 4, s));
+  HIPCK(hipMemsetAsync(P->E0, 0, nr * 4, s));
+  for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l], 0, nr * 4, s));
+  HIPCK(hipMemsetAsync(P->x, 0, nm * 4, s));
+  HIPCK(hipMemsetAsync(P->x0_hist, 0, nm * 4, s));
+  if (P->dtype != FDM_F32) FCK(zero_mat(P, P->xt, 0, nm, stream));
+  HIPCK(hipMemsetAsync(P->slot_state, 0, (size_t)B * 16, s));
+  HIPCK(hipMemsetAsync(P->slot_keys, 0, (size_t)B * 16, s));
+  // the shared sampler: timestep list and tables on the device (drains the stream once, as a sampling call does)
+  std::vector<int> ts;
+  ProgSpec sp;
+  FCK(sampler_setup(P, a, stream, ts, sp));
+  if (ts.empty()) return fail(FDM_ERR_ARG, "slots_open: the sampler has no live step (ddim_steps = %d)", a->ddim_steps);
+  FCK(set_steps(P, ts.data(), (int)ts.size(), stream));
+  P->slot_kind = sp.kind; P->slot_nsteps = (int)ts.size(); P->slot_t0 = ts[0];
+  P->slot_san = sp.san; P->slot_cn = sp.cn;
+  P->slot_cfg_scale = a->cfg_scale; P->slot_graph_steps = a->graph_steps; P->slot_eager = a->eager;
+  P->slot_host.assign(B, fdm_plan::SlotHost());
+  P->slots = B;
+  P->prepared = true;
+  select_tiles(P);
+  return FDM_OK;
+}
+
+int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                   const float* x_T, unsigned long long seed, int clip_id, void* stream) {
+  if (!P || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit: null argument");
+  FCK(check_slots(P, "slot_admit"));
+  const fdm_model_desc& m = P->m;
+  if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_admit: slot %d outside [0, %d)", slot, P->slots);
+  if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "slot_admit: this model needs an emotion one-hot");
+  if (N < 1 || fw < 1 || m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "slot_admit: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
+  if (L_clip < 1 || L_clip > P->L || L_clip > N / m.pair) return fail(FDM_ERR_SHAPE, "slot_admit: L_clip=%d outside [1, min(%d, %d)]", L_clip, P->L, N / m.pair);
+  fdm_plan::SlotHost& h = P->slot_host[slot];
+  if (h.status != 0) return fail(FDM_ERR_STATE, "slot_admit: slot %d is %s", slot, h.status == 1 ? "running" : "finished and not read");
+  hipStream_t s = (hipStream_t)stream;
+  const int d = m.d, L = P->L, M = P->M, row0 = slot * L, pad = L - L_clip;
+  const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
+  // this slot's rows of AF, C1_l (both CFG halves) and E0: the per-clip GEMMs of fdm_audio_prepare_conds on L_clip rows
+  FCK(clip_audio_in(P, hub, row0, L_clip, stream));
+  FCK(clip_tables(P, row0, L_clip, P->rep == 2 ? (size_t)M * d : 0, stream));
+  const float *sw = nullptr, *sbias = nullptr, *ew = nullptr, *eb = nullptr;
+  FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
+  float *sty = P->sty + (size_t)slot * d, *em = P->em + (size_t)slot * d, *emu = P->emu + (size_t)slot * d;
+  FCK(fdm_op_small_linear(style, sw, sbias, sty, 1, m.n_style, d, m.style_mish ? FDM_ACT_MISH : FDM_ACT_NONE, stream));
+  if (m.n_emo) {
+    FCK(need(P, "emotion_embedd.weight", (long long)d * m.n_emo, &ew)); FCK(need(P, "emotion_embedd.bias", d, &eb));
+    FCK(fdm_op_small_linear(emo, ew, eb, em, 1, m.n_emo, d, FDM_ACT_NONE, stream));
+    if (P->cfg) FCK(fdm_op_small_linear(P->zeros, ew, eb, emu, 1, m.n_emo, d, FDM_ACT_NONE, stream));
+  }
+  for (int r = 0; r < P->rep; ++r) {
+    const float* e = m.n_emo ? (r == 1 ? emu : em) : nullptr;
+    const size_t ro = (size_t)r * M * d + o;
+    FCK(fdm_op_add_rows(P->pe, 1, L_clip, sty, L_clip, 1, e, L_clip, 1, P->E0 + ro, L_clip, d, stream));
+    if (pad) {      // rows L_clip .. L of the slot: zero addends (the denoiser is causal: they never reach the clip's own frames)
+      HIPCK(hipMemsetAsync(P->E0 + ro + nclip, 0, npad * 4, s));
+      for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l] + ro + nclip, 0, npad * 4, s));
+    }
+  }
+  // x_T (+ zero tail) and its operand copy into the slot's rows; the history starts at zero
+  HIPCK(hipMemcpyAsync(P->x + o, x_T, nclip * 4, hipMemcpyDeviceToDevice, s));
+  if (pad) HIPCK(hipMemsetAsync(P->x + o + nclip, 0, npad * 4, s));
+  HIPCK(hipMemsetAsync(P->x0_hist + o, 0, (size_t)L * d * 4, s));
+  if (P->dtype != FDM_F32) {      // (the scheduler's mix-only mode writes an operand copy at any plane distance, as load_x does)
+    fdm_sched_args sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.mode = 2; sc.x0 = P->x + o; sc.x_out = P->x + o; sc.n = (long long)L * d;
+    sc.x_out_t = (char*)P->xt.p + o * kind(P->dtype).bytes; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo;
+    FCK(fdm_op_sched_step(&sc, stream));
+  }
+  // {k = -1, running}: the next step's advance launch makes it step 0 of this slot's chain
+  FCK(fdm::slot_set_op(P->slot_state, slot, -1, P->slot_t0, 0, 1, P->slot_keys, seed, clip_id, stream));
+  h.status = 1; h.done = 0; h.L = L_clip;
+  return FDM_OK;
+}
+
+int fdm_slots_run(fdm_plan* P, int n_steps, void* stream) {
+  FCK(check_slots(P, "slots_run"));
+  if (n_steps < 0) return fail(FDM_ERR_ARG, "slots_run: n_steps = %d", n_steps);
+  P->pinned.clear();
+  P->last_graph_launches = 0;
+  ProgSpec sp;
+  sp.kind = P->slot_kind; sp.cfg_scale = P->slot_cfg_scale; sp.san = P->slot_san; sp.cn = P->slot_cn; sp.slot_steps = P->slot_nsteps;
+  fdm_prog* p1 = nullptr;
+  FCK(get_program(P, sp, stream, &p1));
+  if (n_steps == 0) return FDM_OK;
+  P->steps_seen[shape_key(P)] += n_steps;
+  if (P->slot_eager) {
+    for (int i = 0; i < n_steps; ++i) FCK(fdm_prog_run(p1, stream));
+  } else {
+    int K = P->slot_graph_steps > 0 ? P->slot_graph_steps : 10;
+    if (K > n_steps) K = n_steps;
+    int left = n_steps;
+    if (K > 1) {
+      ProgSpec spk = sp; spk.reps = K;
+      fdm_prog* pk = nullptr;
+      FCK(get_program(P, spk, stream, &pk));
+      FCK(fdm_prog_instantiate(pk, stream));
+      FCK(fdm_prog_replay(pk, left / K, stream));
+      P->last_graph_launches += left / K;
+      left %= K;
+    }
+    if (left) {
+      FCK(fdm_prog_instantiate(p1, stream));
+      FCK(fdm_prog_replay(p1, left, stream));
+      P->last_graph_launches += left;
+    }
+  }
+  // the host mirror: a running slot does min(n_steps, what its chain has left) steps and freezes when the chain ends
+  for (auto& h : P->slot_host)
+    if (h.status == 1) {
+      h.done = std::min(P->slot_nsteps, h.done + n_steps);
+      if (h.done == P->slot_nsteps) h.status = 2;
+    }
+  return FDM_OK;
+}
+
+int fdm_slot_state(fdm_plan* P, int slot, int* steps_done, int* steps_total, int* status) {
+  FCK(check_slots(P, "slot_state"));
+  if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_state: slot %d outside [0, %d)", slot, P->slots);
+  const fdm_plan::SlotHost& h = P->slot_host[slot];
+  if (steps_done) *steps_done = h.done;
+  if (steps_total) *steps_total = P->slot_nsteps;
+  if (status) *status = h.status;
+  return FDM_OK;
+}
+
+int fdm_slot_read(fdm_plan* P, int slot, float* out, void* stream) {
+  FCK(check_slots(P, "slot_read"));
+  if (!out) return fail(FDM_ERR_ARG, "slot_read: null output");
+  if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_read: slot %d outside [0, %d)", slot, P->slots);
+  fdm_plan::SlotHost& h = P->slot_host[slot];
+  if (h.status != 2) return fail(FDM_ERR_STATE, "slot_read: slot %d is %s, not finished", slot, h.status == 1 ? "running" : "idle");
+  HIPCK(hipMemcpyAsync(out, P->x + (size_t)slot * P->L * P->m.d, (size_t)h.L * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  h = fdm_plan::SlotHost();
+  return FDM_OK;
+}
+
+int fdm_slot_peek(fdm_plan* P, int slot, float* out, void* stream) {
+  FCK(check_slots(P, "slot_peek"));
+  if (!out) return fail(FDM_ERR_ARG, "slot_peek: null output");
+  if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_peek: slot %d outside [0, %d)", slot, P->slots);
+  HIPCK(hipMemcpyAsync(out, P->x + (size_t)slot * P->L * P->m.d, (size_t)P->L * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return FDM_OK;
 }
 
 int fdm_plan_tune(fdm_plan* P, void* stream) {
@@ -963,6 +1189,7 @@ int fdm_plan_get(fdm_plan* P, const char* key, long long* out) {
   else if (k == "needs_tune") *out = needs_tune(P, shape_key(P)) ? 1 : 0;
   else if (k == "tune_failed") *out = P->tune_failed;
   else if (k == "windows") *out = P->win_n;
+  else if (k == "slots") *out = P->slots;
   else if (k == "window_len") *out = P->win_n ? P->win_len : P->L;
   else if (k == "L_total") *out = P->win_n ? P->win_total : P->L;
   else if (k.rfind("tile.", 0) == 0) { auto it = P->tiles.find(k.substr(5)); *out = it == P->tiles.end() ? 0 : it->second; }

@@ -72,6 +72,18 @@ struct fdm_plan {
   int* win_off = nullptr; size_t win_off_cap = 0;           // CSR of the covering windows per frame (fdm::WinArgs)
   fdm::WinEnt* win_ent = nullptr; size_t win_ent_cap = 0;
   float* win_stage = nullptr; size_t win_stage_cap = 0;     // gathered window audio rows + repeated one-hots (read by the prepare)
+  // ---- in-flight batching (fdm_slots_open): the plan's B clips are `slots` SLOTS of L frames, each at its own diffusion step of one
+  // shared sampler; slots == 0 = not in slot mode.  Device: one {k, t, live, run} word and one {seed, clip id} key per slot
+  // (plan-lifetime, grown on demand).  Host: a mirror of every slot's status and step count, so no call reads the device words.
+  int slots = 0;
+  int* slot_state = nullptr; size_t slot_state_cap = 0;
+  unsigned long long* slot_keys = nullptr; size_t slot_keys_cap = 0;
+  struct SlotHost { int status = 0, done = 0, L = 0; };     // status: 0 idle, 1 running, 2 finished (not read yet)
+  std::vector<SlotHost> slot_host;
+  int slot_kind = 0, slot_nsteps = 0, slot_t0 = 0;          // program kind (1 DDPM, 2 DDIM, 3 table-driven), steps per chain, tseq[0]
+  int slot_graph_steps = 0, slot_eager = 0;
+  float slot_cfg_scale = 0.f;
+  const float *slot_san = nullptr, *slot_cn = nullptr;      // DDIM per-step tables of the session
 };
 
 namespace fdm {

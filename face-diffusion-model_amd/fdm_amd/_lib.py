@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("FDM_LIB_PATH") or os.path.join(_HERE, "libfdm_hip.so"
 F32, BF16, F16X3, F16 = 0, 1, 2, 3      # include/fdm_hip.h FDM_*: operand kinds (F16X3 is a split plane pair; F16 its hi plane alone: denoiser only)
 DTYPE_NAMES = {"f32": F32, "bf16": BF16, "f16x3": F16X3, "f16": F16}
 SAMPLER_DPMPP_2M, SAMPLER_DDIM = 0, 1    # fdm_sampler_tables_host kinds
+SLOT_IDLE, SLOT_RUNNING, SLOT_FINISHED = 0, 1, 2     # fdm_slot_state status
 SAMPLER_NAMES = {"dpmpp2m": SAMPLER_DPMPP_2M, "ddim_eta": SAMPLER_DDIM}
 ACT_NONE, ACT_RELU, ACT_MISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_LEAKY02 = range(6)
 
@@ -73,7 +74,8 @@ class LnArgs(C.Structure):
     _fields_ = [("x", vp), ("M", ci), ("d", ci), ("add_mat", vp), ("add_tab", vp),
                 ("tab_index", vp), ("tab_step", vp), ("gamma", vp), ("beta", vp), ("eps", cf),
                 ("act", ci), ("y_f32", vp), ("y_t", vp), ("dtype", ci), ("gamma2", vp), ("beta2", vp), ("y_t_lo_off", ll),
-                ("add_mat_L", ci), ("add_mat_group", ci), ("add_mat_wrap", ci), ("x_planes", ci), ("x_plane_stride", ll)]
+                ("add_mat_L", ci), ("add_mat_group", ci), ("add_mat_wrap", ci), ("x_planes", ci), ("x_plane_stride", ll),
+                ("clip_step", vp), ("clip_step_stride", ci), ("clip_rows", ci), ("clip_wrap", ci)]
 
 
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
@@ -92,6 +94,7 @@ SYMBOLS = {
     "fdm_op_pack_kv": (ci, [vp, ll, vp, ll, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "fdm_op_layernorm": (ci, [C.POINTER(LnArgs), vp]),
     "fdm_op_sched_step": (ci, [C.POINTER(SchedArgs), vp]),
+    "fdm_op_slot_sched": (ci, [C.POINTER(SchedArgs), vp, vp, ci, vp]),
     "fdm_op_cast": (ci, [vp, vp, ll, ci, vp]),
     "fdm_op_vertex_err": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
     "fdm_op_motion_std": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
@@ -131,6 +134,12 @@ SYMBOLS = {
     "fdm_window_weights_host": (ci, [ci, ci, ci, vp]),
     "fdm_audio_prepare_windows": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
     "fdm_sample_windows": (ci, [vp, C.POINTER(SampleArgs), vp]),
+    "fdm_slots_open": (ci, [vp, ci, ci, ci, C.POINTER(SampleArgs), vp]),
+    "fdm_slot_admit": (ci, [vp, ci, vp, ci, ci, vp, vp, ci, vp, C.c_ulonglong, ci, vp]),
+    "fdm_slots_run": (ci, [vp, ci, vp]),
+    "fdm_slot_state": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+    "fdm_slot_read": (ci, [vp, ci, vp, vp]),
+    "fdm_slot_peek": (ci, [vp, ci, vp, vp]),
     "fdm_plan_tune": (ci, [vp, vp]),
     "fdm_plan_get": (ci, [vp, C.c_char_p, C.POINTER(ll)]),
     "fdm_plan_set": (ci, [vp, C.c_char_p, ll]),

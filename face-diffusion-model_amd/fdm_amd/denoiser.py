@@ -315,6 +315,75 @@ class DenoiserPlan:
         return out
 
     # ------------------------------------------------------------------------------------------
+    def open_slots(self, slots, L, kind="ddim", steps=None, t_list=None, tables=None, cfg=False, cfg_scale=2.5, use_graph=True, graph_steps=0):
+        """In-flight batching (fdm_slots_open): `slots` slots of up to L latent frames, each a clip at its own step of ONE shared
+        sampler -- kind "ddim" with `steps`, "ddpm" over t_list, or "tables" over t_list with `tables` [4, len(t_list)]
+        (sample_tables).  Every slot starts idle; admit() / run() / slot_state() / read_slot() drive them.  Returns the number of
+        steps of a chain."""
+        a = SampleArgs()
+        a.cfg_scale, a.eager, a.graph_steps = float(cfg_scale), int(not use_graph), int(graph_steps)
+        held = None
+        if kind == "ddim":
+            a.kind, a.ddim_steps = 1, int(steps)
+        elif kind == "ddpm":
+            held = (C.c_int * len(t_list))(*[int(t) for t in t_list])
+            a.kind, a.t_list, a.n_steps = 0, C.cast(held, C.c_void_p), len(t_list)
+        elif kind == "tables":
+            held = self._tables_args(a, t_list, tables)
+        else:
+            raise FdmError(f"kind {kind!r} (ddpm | ddim | tables)")
+        with torch.cuda.device(self.device):
+            check(lib().fdm_slots_open(self.h, int(slots), int(L), int(bool(cfg)), C.byref(a), _stream()))
+        del held
+        self._slot_inputs = {}
+        self.B, self.L, self.M, self.cfg, self.S = int(slots), int(L), int(slots) * int(L), bool(cfg), 1
+        return self.slot_state(0)[1]
+
+    def admit(self, slot, hub, style, emo=None, x_T=None, L=None, seed=0, clip_id=0):
+        """fdm_slot_admit: one clip into an idle slot, between steps.  hub [N, fw] (or [1, N, fw]) audio-encoder features, style
+        [n_style], emo [n_emo], x_T [L_clip*G, c] (or [1, ...]); L = latent frames of the clip (default N // pair).  Its latent will
+        equal the solo sample_* call on a (1, L_clip) plan with the same x_T, seed and clip0 = clip_id."""
+        p, dv = self.p, self.device
+        hub = _dev(hub, dv).reshape(-1, hub.shape[-1])
+        N, fw = hub.shape
+        L = N // p.pair if L is None else int(L)
+        style = _dev(style, dv).reshape(-1)
+        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
+        x = _dev(x_T, dv).reshape(-1)
+        if x.numel() != L * p.d:
+            raise FdmError(f"x_T has {x.numel()} elements, expected L_clip*G*c = {L * p.d}")
+        with torch.cuda.device(dv):
+            check(lib().fdm_slot_admit(self.h, int(slot), hub.data_ptr(), N, fw, style.data_ptr(), emo.data_ptr() if emo is not None else None,
+                                       L, x.data_ptr(), int(seed), int(clip_id), _stream()))
+        self._slot_inputs[int(slot)] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the slot is admitted again
+        return L
+
+    def run(self, n_steps):
+        """fdm_slots_run: n_steps diffusion steps for every running slot (a chain that ends part-way freezes there)."""
+        with torch.cuda.device(self.device):
+            check(lib().fdm_slots_run(self.h, int(n_steps), _stream()))
+
+    def slot_state(self, slot):
+        """(steps_done, steps_total, status) of a slot from the host mirror; status _lib.SLOT_IDLE / SLOT_RUNNING / SLOT_FINISHED."""
+        d, t, st = C.c_int(), C.c_int(), C.c_int()
+        check(lib().fdm_slot_state(self.h, int(slot), C.byref(d), C.byref(t), C.byref(st)))
+        return d.value, t.value, st.value
+
+    def read_slot(self, slot, L):
+        """fdm_slot_read: the finished slot's latent [1, L*G, c] (L = the clip's frames, as admitted); the slot is idle afterwards."""
+        out = torch.empty(1, int(L) * self.p.G, self.p.c, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().fdm_slot_read(self.h, int(slot), out.data_ptr(), _stream()))
+        return out
+
+    def peek_slot(self, slot):
+        """fdm_slot_peek: all L rows of a slot's latent [1, L*G, c], whatever its status (inspection; changes nothing)."""
+        out = torch.empty(1, self.L * self.p.G, self.p.c, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().fdm_slot_peek(self.h, int(slot), out.data_ptr(), _stream()))
+        return out
+
+    # ------------------------------------------------------------------------------------------
     def tune(self):
         """Tune the GEMM tiles for the prepared shape now (plan-time work).  Nothing else tunes: get("needs_tune") says when a
         shape has run 2000 steps untuned; only a caller that set "tune_lazy" lets a sampling call tune (once per shape)."""

@@ -152,13 +152,18 @@ def attention(Q, Kp, Vp, O, *, B, H, L, hd, ldq, ldo, Lpad, scale, causal=False,
 
 
 def layernorm(x, gamma, beta, M, d, *, add_mat=None, add_tab=None, tab_index=None, tab_step=None, eps=1e-5,
-              act=ACT_NONE, y_f32=None, y_t=None, dtype=F32, gamma2=None, beta2=None, x_planes=0, x_plane_stride=0):
+              act=ACT_NONE, y_f32=None, y_t=None, dtype=F32, gamma2=None, beta2=None, x_planes=0, x_plane_stride=0,
+              clip_step=None, clip_step_stride=1, clip_rows=0, clip_wrap=0):
+    """clip_step (device int32 words, clip_step_stride ints apart): the add_tab row is chosen per clip of clip_rows rows
+    (fdm_ln_args.clip_step: the slot program's form) instead of by the single word tab_step."""
     a = LnArgs()
     a.x, a.M, a.d, a.add_mat, a.add_tab = _p(x), M, d, _p(add_mat), _p(add_tab)
     a.tab_index, a.tab_step, a.gamma, a.beta, a.eps = _p(tab_index), _p(tab_step), _p(gamma), _p(beta), eps
     a.act, a.y_f32, a.y_t, a.dtype = act, _p(y_f32), _p(y_t), dtype
     a.gamma2, a.beta2, a.y_t_lo_off = _p(gamma2), _p(beta2), _lo(y_t)
     a.x_planes, a.x_plane_stride = x_planes, x_plane_stride
+    if clip_step is not None:
+        a.clip_step, a.clip_step_stride, a.clip_rows, a.clip_wrap = _p(clip_step), clip_step_stride, clip_rows, clip_wrap
     check(lib().fdm_op_layernorm(C.byref(a), stream()))
 
 
@@ -181,6 +186,13 @@ def sched_args(mode, x0, x, x_out, n, *, x0u=None, cfg_scale=0.0, n_per_clip=0, 
 def sched_step(mode, x0, x, x_out, n, **kw):
     a = sched_args(mode, x0, x, x_out, n, **kw)
     check(lib().fdm_op_sched_step(C.byref(a), stream()))
+
+
+def slot_sched(mode, x0, x, x_out, n, state, keys, n_slots, **kw):
+    """fdm_op_slot_sched: state int32 [n_slots, 4] = {k, t, live, run}, keys int64 [n_slots, 2] = {seed, clip id} (device);
+    the other arguments as sched_step (n_per_clip = n // n_slots is required)."""
+    a = sched_args(mode, x0, x, x_out, n, **kw)
+    check(lib().fdm_op_slot_sched(C.byref(a), _p(state), _p(keys), n_slots, stream()))
 
 
 def cast(src, dst):

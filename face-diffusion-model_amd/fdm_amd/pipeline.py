@@ -271,6 +271,117 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     return out, latent
 
 
+class SlotServer:
+    """In-flight batching for a long-running caller whose requests arrive one by one: `slots` clips share ONE step program, each
+    at its own diffusion step (DenoiserPlan.open_slots; include/fdm_hip.h, "Slots").  A request joins the running batch at the next
+    step boundary and leaves when its own chain ends; its result equals animate() on that audio alone with the same arguments
+    (torch.equal on latent and vertices: DDIM, DDPM -- clip id 0, as the solo call keys its noise -- and sampler=).
+
+    One sampler per server, chosen as animate() chooses it: sampler= ("dpmpp2m" | "ddim_eta" with eta=, sampler_steps), else
+    ddim_steps (presets without an emotion input), else the DDPM chain.  Guidance when `diffusion` wraps a
+    ClassifierFreeSampleModel.  max_frames: latent frames a slot holds (default the model's max_len); a longer clip is refused.
+    The server owns the model's plan while it runs: an animate*() call on the same model returns the plan to plain mode and the
+    next submit() / step() raises."""
+
+    def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
+                 device="cuda:0"):
+        from . import schedule
+        self.diffusion, self.ae, self.device = diffusion, autoencoder, device
+        self.cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
+        self.model = diffusion.denoise_fn.model if self.cfg else diffusion.denoise_fn
+        p = self.p = self.model.preset
+        self.n_slots = int(slots)
+        self.L = min(int(max_frames), p.max_len) if max_frames else p.max_len
+        self.plan = self.model.plan(device)
+        self.model._prep_key = None           # the plan leaves the state FDM.prepare() cached
+        kw = dict(cfg=self.cfg, cfg_scale=float(diffusion.denoise_fn.level) if self.cfg else 2.5)
+        if sampler:
+            t_list, tables = schedule.sampler_tables(sampler, sampler_steps, eta, diffusion.num_timesteps)
+            self.chain = self.plan.open_slots(self.n_slots, self.L, "tables", t_list=t_list, tables=tables, **kw)
+        elif ddim_steps and not p.n_emo:
+            self.chain = self.plan.open_slots(self.n_slots, self.L, "ddim", steps=ddim_steps, **kw)
+        else:
+            ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
+            self.chain = self.plan.open_slots(self.n_slots, self.L, "ddpm", t_list=ts, **kw)
+        self._next, self._queue, self._slot, self._done = 0, [], [None] * self.n_slots, []
+
+    def _check(self):
+        from ._lib import FdmError
+        if self.plan.get("slots") != self.n_slots:
+            raise FdmError("SlotServer: the model's plan left slot mode (another sampling call used it)")
+
+    @torch.no_grad()
+    def submit(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0):
+        """One processor-normalised waveform [n] -> a handle.  Runs the audio encoder at the clip's own length, draws x_T as
+        animate() does and admits the clip, or queues it until a slot is free."""
+        self._check()
+        p, dev = self.p, self.device
+        wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
+        hub = self.model.audio_encoder(wav).last_hidden_state
+        L = min(hub.shape[1] // p.pair, p.max_len)
+        if L < 1 or L > self.L:
+            raise ValueError(f"clip of {L} latent frames, slots hold [1, {self.L}]")
+        ids = torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32).reshape(-1, p.n_style)[:1]
+        emo = None
+        if p.n_emo:
+            emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
+            emo = emo.to(dev)
+        x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
+        h = self._next
+        self._next += 1
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template))
+        self._fill()
+        return h
+
+    def _fill(self):
+        for s in range(self.n_slots):
+            if self._slot[s] is None and self._queue:
+                r = self._queue.pop(0)
+                self.plan.admit(s, r["hub"], r["ids"], r["emo"], r["x_T"], L=r["L"], seed=r["seed"], clip_id=0)
+                r.pop("hub"), r.pop("x_T")
+                self._slot[s] = r
+
+    @torch.no_grad()
+    def step(self, n=10):
+        """n diffusion steps for every running clip; clips whose chain ended are read, quantised and decoded at their own length
+        (as animate_many does) and their slots go to the queue.  Returns the number of clips finished by this call."""
+        from ._lib import SLOT_FINISHED
+        self._check()
+        self._fill()
+        self.plan.run(n)
+        fin = 0
+        for s in range(self.n_slots):
+            r = self._slot[s]
+            if r is None or self.plan.slot_state(s)[2] != SLOT_FINISHED:
+                continue
+            lat = self.plan.read_slot(s, r["L"])
+            q = self.ae.quant(lat, r["emo"], stats=False)[0] if self.p.n_emo else self.ae.quant(lat, stats=False)[0]
+            out = self.ae.decode(q)
+            if r["template"] is not None:
+                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
+            self._done.append((r["handle"], out, lat))
+            self._slot[s] = None
+            fin += 1
+        self._fill()
+        return fin
+
+    @property
+    def pending(self):
+        """Requests queued or in a slot."""
+        return len(self._queue) + sum(r is not None for r in self._slot)
+
+    def results(self):
+        """[(handle, vertices [1, L, V3], latent [1, L*G, c])] of the clips finished since the last call."""
+        out, self._done = self._done, []
+        return out
+
+    def drain(self, n=10):
+        """step(n) until nothing is queued or running; returns results()."""
+        while self.pending:
+            self.step(n)
+        return self.results()
+
+
 def demo_main(preset, argv=None):
     """CLI of demo/demo_{vocaset,biwi,3d_mead}.py:109-121: same flags, output = np.save(<audio_path>/<stem>.npy, [1, L, V3])."""
     import argparse

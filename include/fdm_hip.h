@@ -108,6 +108,13 @@ typedef struct fdm_sched_args {
   float* x0_hist;                                            /* mode 3: fp32 [n], the previous step's x0 prediction (read, then rewritten) */
 } fdm_sched_args;
 int fdm_op_sched_step(const fdm_sched_args* a, void* stream);
+/* The scheduler pass of the slot program (fdm_slots_open): the clips of x are n_slots SLOTS of n_per_clip elements, each at its own step.
+ * state: one 16-byte word {int k, t, live, run} per slot; keys: {seed, clip id} (two 64-bit words) per slot.  A slot with live == 0
+ * is skipped whole: nothing of its x_out, x_out_t or x0_hist rows is stored.  A live slot gets the optional CFG mix, then the update
+ * of mode 0 / 1 / 3 at ITS (k, t) with fdm_op_sched_step's expressions -- the bits of that call on the slot's slice with step k,
+ * seed = the slot's seed and clip0 = the slot's clip id (Philox keyed (seed, clip id, element inside the clip, k)).  n must be
+ * n_slots * n_per_clip; a->step / tseq / advance / arrive / seed / clip0 / seed_dev are not read; a->noise must be NULL. */
+int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * C[M,N] = epilogue(A[M,K] * W[N,K]^T): every nn.Linear / Conv1d-as-GEMM on the path
@@ -282,6 +289,11 @@ typedef struct fdm_ln_args {
   /* x given as x_planes (2..4) partial planes, x_plane_stride elements apart (a split-K GEMM's outputs, fdm_gemm_args.ksplit):
    * the row is ((x[0] + x[1]) + x[2]) + ..., summed in plane order before anything else; 0 / 1 = one plane */
   int x_planes; long long x_plane_stride;
+  /* per-clip table row (the slot program, fdm_slots_open): clip_step != NULL -> the add_tab row of row m is
+   * add_tab[tab_index ? tab_index[k_c] : k_c] with k_c = clip_step[clip * clip_step_stride], clip = (m % clip_wrap) / clip_rows
+   * (clip_wrap = rows per cond / uncond half, 0 = no wrap; both halves of a clip share its word); tab_step is then not read.
+   * Light activations only (NONE / RELU).  NULL = the single step word above. */
+  const int* clip_step; int clip_step_stride, clip_rows, clip_wrap;
 } fdm_ln_args;
 int fdm_op_layernorm(const fdm_ln_args* a, void* stream);
 
@@ -475,6 +487,46 @@ int fdm_audio_prepare_windows(fdm_plan* p, const float* hub, int B, int N, int f
  * with x_T / out / noise / record in LONG layout.  Step program: the denoiser chain with its scheduler update unfused, then the blend
  * + update pass (one launch more per step than a plain plan without guidance). */
 int fdm_sample_windows(fdm_plan* p, const fdm_sample_args* a, void* stream);
+/* Slots (in-flight batching).  A plan in slot mode holds B SLOTS of up to L latent frames; every slot is a clip at ITS OWN step of one
+ * shared sampler, so a clip joins a running batch at any step boundary and leaves when its own chain ends -- and its latent is, bit
+ * for bit, what fdm_sample_graph returns for it on a (1, L_clip) plan with the same weights, x_T, seed and clip0 = clip_id.
+ *   state    per slot on the device {k, t, live, run} and {seed, clip id}; zeroed = idle.  The host keeps a mirror of every slot's
+ *            status and step count: no call below reads device memory.
+ *   step     ONE recorded program for any mix of idle, running and finished slots, replayed as a hipGraph: a one-workgroup launch
+ *            advances every slot's word (running with k + 1 < n_steps: k += 1, t = tseq[k], live; otherwise live = 0, t kept in
+ *            range), the denoiser chain follows with every LayerNorm launch gathering TT_l by the row's clip (fdm_ln_args.clip_step) and
+ *            its scheduler update unfused, then fdm_op_slot_sched updates the live slots only.  Two launches more per step than the
+ *            plain program without guidance (fdm_plan_get "launches_per_step").
+ *   exact    every kernel of the chain is row- or clip-independent, self-attention is causal (a clip padded at its end computes its
+ *            own frames' bits), every GEMM tile accumulates k in one order, the unfused scheduler kernel gives the bits of the fused
+ *            epilogue, and noise is keyed by (seed, clip id, element inside the clip, step of the clip).
+ * fdm_slots_open: commits, reserves (B, L, cfg), sets the plan's shape, zeroes the clip tables, x and the state (every slot idle,
+ *   holding zeros) and takes the shared sampler from `sampler`: kind, t_list / n_steps, ddim_steps, lm_tables, cfg_scale,
+ *   graph_steps, eager (x_T, out, seed, clip0 are ignored; noise or record given: FDM_ERR_ARG).  Drains the stream once.  While in
+ *   slot mode fdm_sample_graph, fdm_sample_windows and fdm_denoise_step fail with FDM_ERR_STATE; any fdm_audio_prepare* call returns
+ *   the plan to plain mode.  fdm_plan_get "slots" = B (0 = not in slot mode).
+ * fdm_slot_admit: hub [N, fw] features of ONE clip, style [n_style], emo [n_emo] or NULL, x_T [L_clip*G, c], device fp32.  Builds the
+ *   slot's rows of AF, C1_l (both CFG halves) and E0 with the per-clip GEMMs of fdm_audio_prepare_conds, zero-pads rows L_clip..L,
+ *   loads x_T (+ operand copy), zeroes the slot's history rows and sets {k = -1, running}, seed and clip id.  (The padding rows start
+ *   at zero and are then updated with the slot like any row: finite, never read out, and -- the denoiser being causal -- without effect
+ *   on the clip's own frames.)  Stream-ordered, between
+ *   steps, while other slots are mid-chain.  FDM_ERR_STATE: the slot is running or finished and not read; FDM_ERR_SHAPE: L_clip outside
+ *   [1, min(L, N / pair)]; FDM_ERR_ARG: slot outside [0, B).
+ * fdm_slots_run: n_steps diffusion steps for every running slot; a slot whose chain ends part-way freezes there (finished).
+ * fdm_slot_state: host only; status 0 idle, 1 running, 2 finished.  Any output may be NULL.
+ * fdm_slot_read: copies the slot's L_clip rows to out [L_clip*G, c] (device fp32, stream-ordered) and marks the slot idle;
+ *   FDM_ERR_STATE unless the slot is finished. */
+#define FDM_SLOT_IDLE 0
+#define FDM_SLOT_RUNNING 1
+#define FDM_SLOT_FINISHED 2
+int fdm_slots_open(fdm_plan* p, int B, int L, int cfg, const fdm_sample_args* sampler, void* stream);
+int fdm_slot_admit(fdm_plan* p, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                   const float* x_T, unsigned long long seed, int clip_id, void* stream);
+int fdm_slots_run(fdm_plan* p, int n_steps, void* stream);
+int fdm_slot_state(fdm_plan* p, int slot, int* steps_done, int* steps_total, int* status);
+int fdm_slot_read(fdm_plan* p, int slot, float* out, void* stream);
+/* inspection: all L rows of a slot's latent, [L*G, c], whatever its status (an idle slot never admitted holds zeros); changes nothing */
+int fdm_slot_peek(fdm_plan* p, int slot, float* out, void* stream);
 /* Plan-time tuning of the GEMM output tiles at the prepared shape (times candidates per call site; changes speed only, every
  * tile accumulates k in the same order).  This call is the ONLY place the library tunes by itself: request paths
  * (fdm_audio_prepare*, fdm_sample_graph) never do -- fdm_plan_get(p, "needs_tune") turns 1 once the prepared shape has served
@@ -489,7 +541,7 @@ int fdm_sample_windows(fdm_plan* p, const fdm_sample_args* a, void* stream);
  * FDM_GEMM_LOCKSTEP=1 = FDM_TILE_LOCKSTEP for every fdm_op_gemm of the process (A/B of the once-per-clip stages; the step has fdm_plan_set "lockstep"). */
 int fdm_plan_tune(fdm_plan* p, void* stream);
 /* Introspection / experiments: integer properties by name -- "launches_per_step", "graph_launches" (host graph launches of
- * the last fdm_sample_graph), "rows", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
+ * the last fdm_sample_graph / fdm_slots_run), "rows", "slots", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
  * enc, dec, ...). */
 int fdm_plan_get(fdm_plan* p, const char* key, long long* out);
 /* "tile.<call site>" (drops recorded programs), "tune" (0 = off), "tune_lazy" (1 = in-call tuning allowed), "untune" (forget every
