@@ -247,7 +247,12 @@ typedef struct fdm_attn_args {
   int dtype;
   float scale;
   int causal;
-  const float* slopes;   /* [H] device floats or NULL */
+  /* slopes ([H] device floats or NULL) and causal are independent.  With slopes the score of (query i, key j) gets
+   * -slopes[h] * floor((i - j) / period), floor towards -inf, for EVERY visible key: with causal = 0 the keys j > i are visible and
+   * take the same formula, i.e. a bias >= 0 that grows with j - i (the first key after i already gets +slopes[h]).  causal = 1 hides
+   * j > i whether or not there are slopes.  Any period >= 1 is taken, also one longer than L.  Pad keys (l >= L) are never seen,
+   * whatever finite values they hold.  (tests/test_attention_edges_gpu.py) */
+  const float* slopes;
   int period;
   /* o_split = FDM_F16X3 (with dtype FDM_F32): O is written as a split plane pair (the next GEMM's input),
    * lo plane o_lo_off elements after the hi plane; 0 = O has the dtype of Q */

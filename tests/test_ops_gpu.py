@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from attn_cases import pack_host  # noqa: E402
 from fdm_amd import ops  # noqa: E402
 from fdm_amd._lib import (ACT_GELU_ERF, ACT_GELU_TANH, ACT_LEAKY02, ACT_MISH, ACT_NONE, ACT_RELU, BF16, F16, F16X3, F32)  # noqa: E402
 
@@ -310,7 +311,8 @@ def test_every_tile_on_random_ragged_shapes(dtype):
 
 
 def test_split_producers_write_plane_pairs():
-    """LayerNorm, scheduler and fp32 attention write GEMM inputs as plane pairs in the split modes."""
+    """LayerNorm and the scheduler write GEMM inputs as plane pairs in the split modes (fp32 attention does too, through
+    fdm_attn_args.o_split: tests/test_attention_edges_gpu.py, test_fp32_attention_writes_split_output)."""
     g = torch.Generator().manual_seed(3)
     M, d = 37, 1024
     x = torch.randn(M, d, generator=g)
@@ -380,28 +382,9 @@ def alibi(H, L, period, slopes):
 
 
 def pack_ref(k, v, Lpad, dtype):
-    """Host restatement of the fragment-packed K / V layouts (include/fdm_hip.h, fdm_attn_args).
-    k, v: [B, H, L, hd] -> two [B*H, Lpad*hd] tensors (pad keys zero)."""
-    B, H, L, hd = k.shape
-    epc = 8 if dtype in (BF16, F16) else 4
-    kt_keys = 4 * epc
-    nsub, nks = kt_keys // 16, hd // (4 * epc)
-    l = torch.arange(L).view(L, 1)
-    e = torch.arange(hd).view(1, hd)
-    kt, w = l // kt_keys, l % kt_keys
-    if nsub == 2:
-        sub, r = (w >> 2) & 1, ((w >> 3) << 2) | (w & 3)
-    else:
-        sub, r = torch.zeros_like(w), w
-    ch = e // epc
-    koff = (((((kt * nsub + sub) * nks + (ch >> 2)) * 4 + (ch & 3)) * 16 + r) * epc + e % epc).reshape(-1)
-    voff = ((((kt * (hd // 16) + (e >> 4)) * 4 + w // epc) * 16 + (e & 15)) * epc + w % epc).reshape(-1)
-    assert koff.unique().numel() == L * hd and voff.unique().numel() == L * hd
-    kp = torch.zeros(B * H, Lpad * hd, dtype=k.dtype)
-    vp = torch.zeros(B * H, Lpad * hd, dtype=v.dtype)
-    kp[:, koff] = k.reshape(B * H, L * hd)
-    vp[:, voff] = v.reshape(B * H, L * hd)
-    return kp, vp
+    """Host restatement of the fragment-packed K / V layouts (include/fdm_hip.h, fdm_attn_args), pad keys zero: it lives in
+    tests/attn_cases.py (pack_host), which also fills the pads with a chosen value and packs split kinds plane by plane."""
+    return pack_host(k, v, Lpad, dtype)
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16])
