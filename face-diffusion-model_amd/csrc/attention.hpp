@@ -46,7 +46,15 @@ template <typename T> __device__ __forceinline__ float fexp(float x) {
 // in halves (round 3's first form: four round trips, 463 registers) was 3.7 us slower per launch (cfg4 f16x3 0.826 -> 0.795 ms).
 template <typename T, int HD> constexpr bool attn_streamed() { return Opnd<T>::NP == 2 && HD == 256; }
 
-template <typename T, int HD, int QS>
+// RAG (fdm_attn_args.lens, non-causal only): clip b has its own length Lc = lens[b] <= L inside the padded [B, L] problem.  Everything
+// that looks across keys -- the tile count, the dealing of the tiles to the four waves, the end-of-sequence mask -- is computed from
+// Lc exactly as a launch with L = Lc computes it from L, so a query's online-softmax order, and with it its bits, are those of the
+// clip's own launch; only the addressing (row stride of Q and O, K / V block stride) follows the padded L.  A query's arithmetic
+// does not depend on QS (the sub-tiles share fragments, nothing else), so the padded launch may run QS = 2 where the solo one
+// runs QS = 1.  Rows at or beyond Lc store zeros; key tiles wholly beyond Lc are never fetched.
+// (RAG is a template parameter of the one kernel, not a shared device body called from two kernels: that form changed the register
+//  allocation of the uniform instantiations; this one leaves their VGPR / SGPR / LDS figures as they were, profiles/ragged/resources.txt.)
+template <typename T, int HD, int QS, bool RAG = false>
 __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_kernel(const void* pQ, const void* pKp, const void* pVp, int p_q_lo_off, int p_kv_lo_off, int pL, int pB, int pH, int p_ldq,
                                                                                      int pLpad, const fdm_attn_args p) {
   // (the leading arguments repeat fields of p: kernel-argument preload, 13 SGPRs -- the Q / K fragment loads go out without waiting for
@@ -78,6 +86,8 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
   if (bh >= pB * pH) return;
   const int b = bh / pH, h = bh - b * pH;
   const int q0 = (nqt - 1 - (rem >> 3)) * BQ;
+  int Lc = L;                              // this clip's own length
+  if constexpr (RAG) Lc = min(max(p.lens[b], 0), L);
   // (+4 floats per row: the merge writes below put 8 lanes on 8 consecutive rows at one column; without the pad they share
   //  a bank group -- SQ_LDS_BANK_CONFLICT was 79 % of this kernel's LDS cycles)
   __shared__ __attribute__((aligned(16))) float part_o[4][BQ][HD + 4];
@@ -96,7 +106,7 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
     qi[u] = q0 + 16 * u + r16;
-    const int qrow = min(qi[u], L - 1);
+    const int qrow = RAG ? max(min(qi[u], Lc - 1), 0) : min(qi[u], L - 1);
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
@@ -117,8 +127,8 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
   const float inv_period = 1.f / (float)p.period;
   const bool fastbias = !p.slopes || p.period >= 8;
   const int goff = (NSUB == 2 ? 8 : 4) * g;
-  const int kend = p.causal ? min(q0 + BQ, L) : L;     // keys [0, kend) can be visible to this workgroup
-  const int ntiles = (kend + KT - 1) / KT;
+  const int kend = p.causal ? min(q0 + BQ, L) : Lc;     // keys [0, kend) can be visible to this workgroup
+  const int ntiles = (RAG && q0 >= Lc) ? 0 : (kend + KT - 1) / KT;      // (a query tile wholly in the padding only stores zeros)
 
   // Measured (twice: with the accumulators in AGPRs and again after they moved to VGPRs, 6.4 vs 6.1 us at L = 200):
   // software prefetch of the next tile's fragments (register double buffers, copy or ping-pong) is SLOWER here: the extra VGPRs cost residency, and residency is what hides the L2 round trips of these
@@ -182,7 +192,7 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
         b1 = b0 - slope;
       }
       // only tiles that straddle the causal diagonal or the end of the sequence need the mask
-      const bool edge = (kbase + KT > L) || (p.causal && kbase + KT - 1 > q0 + 16 * u);
+      const bool edge = (kbase + KT > Lc) || (p.causal && kbase + KT - 1 > q0 + 16 * u);
       float mx = -INFINITY;
       if (fastbias) {
 #pragma unroll
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
           }
       }
       if (edge) {
-        const int jmax = min(p.causal ? D : (1 << 30), L - 1 - kbase - goff);     // largest visible j of this lane
+        const int jmax = min(p.causal ? D : (1 << 30), Lc - 1 - kbase - goff);     // largest visible j of this lane
 #pragma unroll
         for (int s = 0; s < NSUB; ++s)
 #pragma unroll
@@ -313,6 +323,7 @@ __global__ __launch_bounds__(256, (attn_streamed<T, HD>() ? 1 : 2)) void attn_ke
 #pragma unroll
         for (int w = 0; w < 4; ++w) v += *(const f32x4*)&part_o[w][q][e0 + j] * sw[w];
         v *= inv;
+        if constexpr (RAG) { if (qq >= Lc) v = f32x4{0.f, 0.f, 0.f, 0.f}; }
         if constexpr (std::is_same<T, float>::value) {
           // fp32 attention feeding a split-operand GEMM: O is written as the plane pair
           if (p.o_split == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.O + oo + j, p.o_lo_off, v);
@@ -335,16 +346,21 @@ static void attn_launch_t(const fdm_attn_args& a, hipStream_t s) {
   if constexpr (HD <= 128 && Opnd<T>::NP == 1) {
     if (a.L >= qs2) {
       dim3 grid((a.L + 31) / 32 * groups);
+      if (a.lens) { hipLaunchKernelGGL((attn_kernel<T, HD, 2, true>), grid, dim3(256), 0, s, ATTN_PRELOAD_ARGS, a); return; }
       hipLaunchKernelGGL((attn_kernel<T, HD, 2>), grid, dim3(256), 0, s, ATTN_PRELOAD_ARGS, a);
       return;
     }
   }
   dim3 grid((a.L + 15) / 16 * groups);
+  if constexpr (HD <= 128) {        // per-clip lengths: head dims 64 / 128 (fdm_op_attention refuses 256)
+    if (a.lens) { hipLaunchKernelGGL((attn_kernel<T, HD, 1, true>), grid, dim3(256), 0, s, ATTN_PRELOAD_ARGS, a); return; }
+  }
   hipLaunchKernelGGL((attn_kernel<T, HD, 1>), grid, dim3(256), 0, s, ATTN_PRELOAD_ARGS, a);
 }
 
 template <typename T>
 static hipError_t attn_launch_dtype(const fdm_attn_args& a, hipStream_t s) {
+  if (a.lens && a.hd != 64 && a.hd != 128) return hipErrorInvalidValue;      // per-clip lengths exist for head dims 64 / 128 only
   if constexpr (Opnd<T>::NP == 2) {       // split kind: head_dim 64 / 128 hold a key tile's fragments, 256 streams them (one wave per SIMD)
     if (a.hd == 256) attn_launch_t<T, 256>(a, s);
     else if (a.hd == 128) attn_launch_t<T, 128>(a, s);

@@ -264,6 +264,33 @@ __global__ void pad_rows_kernel(const T* in, T* out, int B, int L, int d, int pa
   }
 }
 
+// The replicate form for clips of unequal length inside one padded [B, L, d] batch: clip b is lens[b] frames long, so its end
+// padding -- and every row beyond -- copies ITS last frame, lens[b] - 1; rows of `in` at or beyond lens[b] are never read.
+template <typename T>
+__global__ void pad_rows_lens_kernel(const T* in, T* out, int B, int L, int d, int pad, const int* lens) {
+  const long long n = (long long)B * (L + 2 * pad) * d;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int col = (int)(i % d);
+    const long long r = i / d;
+    const int k = (int)(r % (L + 2 * pad));
+    const int b = (int)(r / (L + 2 * pad));
+    const int Lb = min(max(lens[b], 1), L);
+    int src = k - pad;
+    src = src < 0 ? 0 : (src >= Lb ? Lb - 1 : src);
+    out[i] = in[((size_t)b * L + src) * d + col];
+  }
+}
+
+// x[b, l, :] = 0 for l >= lens[b]: the rows of a padded batch that belong to no clip
+__global__ void zero_pad_rows_kernel(float* x, int B, int L, int d, const int* lens) {
+  const long long n = (long long)B * L * d;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / d;
+    const int l = (int)(r % L), b = (int)(r / L);
+    if (l >= lens[b]) x[i] = 0.f;
+  }
+}
+
 // [B, T, d] -> [groups, B, T + 2*pad, d/groups], zero padded in time
 template <typename T>
 __global__ void group_pad_kernel(const T* in, T* out, int B, int Tn, int d, int groups, int pad) {
@@ -280,6 +307,42 @@ __global__ void group_pad_kernel(const T* in, T* out, int B, int Tn, int d, int 
     T v = from_f32<T>(0.f);
     if (src >= 0 && src < Tn) v = in[((size_t)b * Tn + src) * d + gi * dg + col];
     out[i] = v;
+  }
+}
+
+// The same for clips of unequal length inside one padded [B, Tn, d] batch: frames at or beyond lens[b] are written as zeros, so a
+// convolution over a clip's last frames sees the zero padding its own launch sees
+template <typename T>
+__global__ void group_pad_lens_kernel(const T* in, T* out, int B, int Tn, int d, int groups, int pad, const int* lens) {
+  const int dg = d / groups;
+  const long long n = (long long)groups * B * (Tn + 2 * pad) * dg;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int col = (int)(i % dg);
+    long long r = i / dg;
+    const int k = (int)(r % (Tn + 2 * pad));
+    r /= (Tn + 2 * pad);
+    const int b = (int)(r % B);
+    const int gi = (int)(r / B);
+    const int src = k - pad;
+    T v = from_f32<T>(0.f);
+    if (src >= 0 && src < min(lens[b], Tn)) v = in[((size_t)b * Tn + src) * d + gi * dg + col];
+    out[i] = v;
+  }
+}
+
+// Host ints -> device ints through the kernel arguments (up to 64 per launch): the values travel with the launch itself, so the
+// caller's array is not read after the call returns and nothing has to be pinned or kept alive (fdm_op_set_ints).
+struct IntPack { int v[64]; };
+__global__ void set_ints_kernel(int* dst, IntPack p, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = p.v[threadIdx.x];
+}
+
+// out[b, i] = wav[b, i] for i < lens[b], 0 beyond: the waveforms of a padded batch with their padding cleared, whatever it held
+__global__ void mask_samples_kernel(const float* wav, float* out, int B, int n, const int* lens) {
+  const long long tot = (long long)B * n;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / n), k = (int)(i - (long long)b * n);
+    out[i] = k < lens[b] ? wav[i] : 0.f;
   }
 }
 
@@ -423,6 +486,43 @@ __global__ __launch_bounds__(1024) void leaky_instnorm_kernel(const float* x, fl
   }
 }
 
+// The same over clips of unequal length inside one padded [B, L, d] batch: clip b's statistics run over its first Lb = lens[b]
+// frames with the time-lanes striding and folding exactly as the kernel above does for L = Lb (the bits of the clip's own
+// launch); frames at or beyond Lb are written as zeros.
+template <typename T>
+__global__ __launch_bounds__(1024) void leaky_instnorm_lens_kernel(const float* x, float* y_f32, T* y_t, int L, int d, float eps, const int* lens) {
+  __shared__ float red[16][64];
+  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
+  const bool ok = ch < d;
+  const int Lb = min(max(lens[b], 1), L);
+  const float* xp = x + (size_t)b * L * d + (ok ? ch : 0);
+  float s = 0.f;
+  if (ok) for (int l = tl; l < Lb; l += 16) s += act_apply(xp[(size_t)l * d], ACT_LEAKY02);
+  red[tl][cl] = s;
+  __syncthreads();
+  float mean = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) mean += red[i][cl];
+  mean /= Lb;
+  __syncthreads();
+  float q = 0.f;
+  if (ok) for (int l = tl; l < Lb; l += 16) { const float c = act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean; q += c * c; }
+  red[tl][cl] = q;
+  __syncthreads();
+  float var = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) var += red[i][cl];
+  const float rstd = 1.f / sqrtf(var / Lb + eps);
+  if (!ok) return;
+  for (int l = tl; l < L; l += 16) {
+    const float v = l < Lb ? (act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean) * rstd : 0.f;
+    const size_t o = ((size_t)b * L + l) * d + ch;
+    if (y_f32) y_f32[o] = v;
+    if (y_t) y_t[o] = from_f32<T>(v);
+  }
+}
+
 // GroupNorm(num_groups = C) of wav2vec2's first conv layer: per (clip, channel) statistics over time
 // (biased variance), affine, then activation.  Workgroup = 16 time-lanes x 64 channels; the time-lanes
 // stride over t and combine through LDS; three passes (mean, centred variance, normalise).
@@ -510,6 +610,115 @@ __global__ __launch_bounds__(1024) void time_norm_apply_kernel(const float* x, c
     const size_t o = ((size_t)b * Tn + t) * C + ch;
     if (y_f32) y_f32[o] = v;
     if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
+  }
+}
+
+// The three kernels above for clips of unequal length inside one padded [B, Tn, C] batch (lens[b] frames each).  A clip takes the
+// form its own launch takes -- the three-pass kernel below 4096 frames, the fp64 chunk pair from there on, with the chunk count and
+// width computed from ITS length -- so its statistics fold in the solo order; all three kernels are launched, and a workgroup whose
+// clip belongs to the other form leaves at once.  Frames at or beyond lens[b] are written as zeros.
+__device__ __forceinline__ int time_chunks_of(int Tb, int* chunk) {
+  const int nch = min(64, (Tb + 1023) / 1024);
+  *chunk = ((Tb + nch - 1) / nch + 15) / 16 * 16;
+  return nch;
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void time_groupnorm_lens_kernel(const float* x, const float* gamma, const float* beta, float* y_f32,
+                                                                   typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
+  __shared__ float red[16][64];
+  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
+  const int Tb = min(max(lens[b], 1), Tn);
+  if (Tb >= 4096) return;       // (uniform over the workgroup) the chunk pair's clip
+  const bool ok = ch < C;
+  const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
+  float s = 0.f;
+  if (ok) for (int t = tl; t < Tb; t += 16) s += xp[(size_t)t * C];
+  red[tl][cl] = s;
+  __syncthreads();
+  float mean = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) mean += red[i][cl];
+  mean /= Tb;
+  __syncthreads();
+  float q = 0.f;
+  if (ok) for (int t = tl; t < Tb; t += 16) { const float c = xp[(size_t)t * C] - mean; q += c * c; }
+  red[tl][cl] = q;
+  __syncthreads();
+  float var = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) var += red[i][cl];
+  const float rstd = 1.f / sqrtf(var / Tb + eps);
+  if (!ok) return;
+  const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
+  for (int t = tl; t < Tn; t += 16) {
+    float v = 0.f;
+    if (t < Tb) v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
+    const size_t o = ((size_t)b * Tn + t) * C + ch;
+    if (y_f32) y_f32[o] = v;
+    if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
+  }
+}
+// (part: [B, gridDim.y, C, 2] doubles; a clip uses its first time_chunks_of(lens[b]) chunk slots)
+__global__ __launch_bounds__(1024) void time_stats_lens_kernel(const float* x, double* part, int Tn, int C, const int* lens) {
+  __shared__ double rs[16][64], rq[16][64];
+  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nmax = gridDim.y;
+  const int Tb = min(max(lens[b], 1), Tn);
+  if (Tb < 4096) return;
+  int chunk;
+  const int nch = time_chunks_of(Tb, &chunk);
+  if (c >= nch) return;
+  const bool ok = ch < C;
+  const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
+  const int t1 = min(Tb, (c + 1) * chunk);
+  double s = 0.0, q = 0.0;
+  if (ok) for (int t = c * chunk + tl; t < t1; t += 16) { const double v = (double)xp[(size_t)t * C]; s += v; q += v * v; }
+  rs[tl][cl] = s; rq[tl][cl] = q;
+  __syncthreads();
+  if (tl == 0 && ok) {
+    double ss = 0.0, qq = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { ss += rs[i][cl]; qq += rq[i][cl]; }
+    double* o = part + (((size_t)b * nmax + c) * C + ch) * 2;
+    o[0] = ss; o[1] = qq;
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void time_norm_apply_lens_kernel(const float* x, const double* part, const float* gamma, const float* beta,
+                                                                    float* y_f32, typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
+  __shared__ float st[64][2];
+  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nmax = gridDim.y;
+  const int Tb = min(max(lens[b], 1), Tn);
+  if (Tb < 4096) return;
+  int chunk;
+  const int nch = time_chunks_of(Tb, &chunk);
+  const bool ok = ch < C;
+  if (tl == 0) {
+    double ss = 0.0, qq = 0.0;
+    if (ok) for (int i = 0; i < nch; ++i) { const double* o = part + (((size_t)b * nmax + i) * C + ch) * 2; ss += o[0]; qq += o[1]; }
+    const double mean = ss / Tb, var = fmax(qq / Tb - mean * mean, 0.0);
+    st[cl][0] = (float)mean; st[cl][1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+  __syncthreads();
+  if (!ok) return;
+  const float mean = st[cl][0], rstd = st[cl][1];
+  const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
+  const float* xp = x + (size_t)b * Tn * C + ch;
+  if (c < nch) {
+    const int t1 = min(Tb, (c + 1) * chunk);
+    for (int t = c * chunk + tl; t < t1; t += 16) {
+      const float v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
+      const size_t o = ((size_t)b * Tn + t) * C + ch;
+      if (y_f32) y_f32[o] = v;
+      if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
+    }
+  }
+  for (int t = Tb + c * 16 + tl; t < Tn; t += nmax * 16) {       // the clip's pad frames, shared out among its workgroups
+    const size_t o = ((size_t)b * Tn + t) * C + ch;
+    if (y_f32) y_f32[o] = 0.f;
+    if (y_t) store_opnd1<T>(y_t + o, lo_off, 0.f);
   }
 }
 

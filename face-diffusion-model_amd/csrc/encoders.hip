@@ -133,6 +133,8 @@ struct fdm_audio_encoder {
   // workspace (capacity: capB clips x capN samples)
   int capB = 0, capN = 0;
   float *x32 = nullptr, *y32 = nullptr, *g6 = nullptr, *gi = nullptr, *h = nullptr, *h2 = nullptr, *hb = nullptr, *x1 = nullptr;
+  float* wavm = nullptr;       // ragged call: the waveforms with their padding cleared [capB, capN]
+  int* lens = nullptr;         // ragged call: per-clip samples, conv-0 frames and output frames [3, capB]
   void *xa = nullptr, *xb = nullptr, *ft = nullptr, *ht = nullptr, *xg = nullptr, *xt = nullptr, *q = nullptr, *kp = nullptr, *vp = nullptr, *ctx = nullptr, *u = nullptr;
 };
 
@@ -248,6 +250,7 @@ int enc_reserve(fdm_audio_encoder* E, int B, int n) {
   FCK(E->ws.alloc(&E->xg, (size_t)POS_G * B * (N + POS_K) * (D / POS_G) * es));
   FCK(E->ws.alloc(&E->u, M * E->FFN * esl));
   FCK(E->ws.alloc(&E->kp, (size_t)B * kv_pad((int)N) * D * esl, true)); FCK(E->ws.alloc(&E->vp, (size_t)B * kv_pad((int)N) * D * esl, true));
+  FCK(E->ws.alloc_t(&E->wavm, (size_t)B * n)); FCK(E->ws.alloc_t(&E->lens, (size_t)3 * B));
   E->capB = B; E->capN = n;
   return FDM_OK;
 }
@@ -292,16 +295,28 @@ int fdm_hubert_set_weights(fdm_audio_encoder* E, const char* name, const float* 
   return E->st.set(name, ptr, n, stream);
 }
 
-int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int frame_num, int interp_in_fps, int interp_out_fps,
-                       float* out, int* n_frames, void* stream) {
-  if (!E || !wav || !out) return fail(FDM_ERR_ARG, "hubert_forward: null argument");
-  if (B < 1 || n < 400) return fail(FDM_ERR_SHAPE, "hubert_forward: audio too short (%d samples)", n);
-  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "hubert_forward: no gfx950 device visible (there is no CPU fallback)");
+// n_samples: per-clip sample counts (host, validated by the caller) of a batch padded to n samples, or nullptr.  With them every
+// stage that looks across time knows each clip's length: the waveform padding is cleared (so every pad frame of the conv stack is a
+// finite function of nothing), the time GroupNorm, the positional conv's padding and attention take per-clip frame counts, and the
+// output's pad rows are zeroed; the conv stack itself and everything per row run on the padded rows (a valid frame of a strided
+// conv reads valid frames only).
+static int hubert_forward_impl(fdm_audio_encoder* E, const float* wav, const int* n_samples, int B, int n, int frame_num, int interp_in_fps, int interp_out_fps,
+                               float* out, int* n_frames, void* stream) {
   int T[7];
   conv_lengths(n, T);
-  if (T[6] < 2) return fail(FDM_ERR_SHAPE, "hubert_forward: audio too short (%d samples)", n);
   const bool interp = interp_in_fps > 0 && interp_out_fps > 0;
   int N = T[6] - (T[6] % 2);                                        // drop the last frame if odd (models/hubert.py:95-96)
+  std::vector<int> hl;                                              // [samples | conv-0 frames | output frames] per clip
+  if (n_samples) {
+    hl.resize((size_t)3 * B);
+    N = 0;
+    for (int b = 0; b < B; ++b) {
+      int Tb[7];
+      conv_lengths(n_samples[b], Tb);
+      hl[b] = n_samples[b]; hl[B + b] = Tb[0]; hl[2 * B + b] = Tb[6] - (Tb[6] % 2);
+      N = hl[2 * B + b] > N ? hl[2 * B + b] : N;
+    }
+  }
   if (frame_num > 0 && !interp && N > frame_num * 2) N = frame_num * 2;     // :97-98
   int T6 = T[6];
   if (interp) {
@@ -311,6 +326,13 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   }
   FCK(enc_commit(E, stream));
   FCK(enc_reserve(E, B, n));
+  const int *lens_n = nullptr, *lens_t0 = nullptr, *lens_N = nullptr;
+  if (n_samples) {
+    FCK(fdm_op_set_ints(E->lens, hl.data(), 3 * B, stream));
+    lens_n = E->lens; lens_t0 = E->lens + B; lens_N = E->lens + 2 * B;
+    FCK(fdm_op_mask_samples(wav, E->wavm, B, n, lens_n, stream));
+    wav = E->wavm;
+  }
   const int D = E->D, dt = E->front_dtype(), dtl = E->dtype, H = E->H, FFN = E->FFN, HD = 64;
   const size_t esl = esize(dtl);
   const bool split = dtl == FDM_F16X3;
@@ -324,7 +346,9 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   } else {                         // wav2vec2-base: GroupNorm over time needs the whole clip's conv output first
     FCK(fdm_op_conv0(wav, E->conv0_w, E->conv_b[0], E->x32, B, n, T[0], stream));
     // (chunk statistics go through y32: the conv stack's fp32 scratch, free until layer 1's GEMM writes it)
-    FCK(fdm_op_time_groupnorm(E->x32, E->conv_g[0], E->conv_beta[0], nullptr, xt, lo_of((long long)B * T[0], CD), B, T[0], CD, 1e-5f, FDM_ACT_GELU_ERF, dt,
+    if (lens_t0) FCK(fdm_op_time_groupnorm_lens(E->x32, E->conv_g[0], E->conv_beta[0], nullptr, xt, lo_of((long long)B * T[0], CD), B, T[0], CD, 1e-5f, FDM_ACT_GELU_ERF, dt,
+                                                E->y32, (long long)B * T[1] * CD * 4, lens_t0, stream));
+    else FCK(fdm_op_time_groupnorm(E->x32, E->conv_g[0], E->conv_beta[0], nullptr, xt, lo_of((long long)B * T[0], CD), B, T[0], CD, 1e-5f, FDM_ACT_GELU_ERF, dt,
                               E->y32, (long long)B * T[1] * CD * 4, stream));
   }
   int Tin = T[0];
@@ -360,8 +384,13 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
   // --- positional conv embedding: h += GELU(grouped conv(h)), k = 128, groups = 16, pad 64, last output dropped ---
   const int dg = D / POS_G;
   const long long xg_plane = (long long)POS_G * B * (N + POS_K) * dg;      // elements of one [groups, B, N + K, dg] plane
-  FCK(fdm_op_group_pad(ht, E->xg, B, N, D, POS_G, POS_K / 2, dt, stream));
-  if (fsplit) FCK(fdm_op_group_pad((const char*)ht + (size_t)M * D * 2, (char*)E->xg + (size_t)xg_plane * 2, B, N, D, POS_G, POS_K / 2, dt, stream));
+  if (lens_N) {
+    FCK(fdm_op_group_pad_lens(ht, E->xg, B, N, D, POS_G, POS_K / 2, dt, lens_N, stream));
+    if (fsplit) FCK(fdm_op_group_pad_lens((const char*)ht + (size_t)M * D * 2, (char*)E->xg + (size_t)xg_plane * 2, B, N, D, POS_G, POS_K / 2, dt, lens_N, stream));
+  } else {
+    FCK(fdm_op_group_pad(ht, E->xg, B, N, D, POS_G, POS_K / 2, dt, stream));
+    if (fsplit) FCK(fdm_op_group_pad((const char*)ht + (size_t)M * D * 2, (char*)E->xg + (size_t)xg_plane * 2, B, N, D, POS_G, POS_K / 2, dt, stream));
+  }
   {
     // ONE launch for all clips (round 5; one launch per clip before): z = (clip, group), the weights of a group shared by the clips
     // and by the row tiles, workgroups dealt so that every XCD works on two groups only -- its L2 streams 1 / 8 of the 16.8 MB
@@ -399,7 +428,7 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
     memset(&a, 0, sizeof(a));
     a.Q = E->q; a.ldq = D; a.Kp = E->kp; a.Vp = E->vp; a.Lpad = Lpad; a.O = E->ctx; a.ldo = D; a.B = B; a.H = H; a.L = N; a.hd = HD;
     a.dtype = dtl; a.scale = 0.125f; a.causal = 0; a.period = 1;
-    a.q_lo_off = lo_md; a.kv_lo_off = lo_kv; a.o_lo_off = lo_md;
+    a.q_lo_off = lo_md; a.kv_lo_off = lo_kv; a.o_lo_off = lo_md; a.lens = lens_N;
     return fdm_op_attention(&a, stream);
   };
   if (E->stable_ln) {       // pre-LN layers, final LayerNorm (HubertEncoderStableLayerNorm)
@@ -441,8 +470,37 @@ int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int
     }
     HIPCK(hipMemcpyAsync(out, hb, (size_t)M * D * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   }
-  if (n_frames) *n_frames = N;
+  if (lens_N) {
+    FCK(fdm_op_zero_pad_rows(out, B, N, D, lens_N, stream));
+    for (int b = 0; b < B; ++b) n_frames[b] = hl[2 * B + b];
+  } else if (n_frames) {
+    *n_frames = N;
+  }
   return FDM_OK;
+}
+
+int fdm_hubert_forward(fdm_audio_encoder* E, const float* wav, int B, int n, int frame_num, int interp_in_fps, int interp_out_fps,
+                       float* out, int* n_frames, void* stream) {
+  if (!E || !wav || !out) return fail(FDM_ERR_ARG, "hubert_forward: null argument");
+  if (B < 1 || n < 400) return fail(FDM_ERR_SHAPE, "hubert_forward: audio too short (%d samples)", n);
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "hubert_forward: no gfx950 device visible (there is no CPU fallback)");
+  int T[7];
+  conv_lengths(n, T);
+  if (T[6] < 2) return fail(FDM_ERR_SHAPE, "hubert_forward: audio too short (%d samples)", n);
+  return hubert_forward_impl(E, wav, nullptr, B, n, frame_num, interp_in_fps, interp_out_fps, out, n_frames, stream);
+}
+
+int fdm_hubert_forward_ragged(fdm_audio_encoder* E, const float* wav, const int* n_samples, int B, int n_max, float* out, int* n_frames, void* stream) {
+  if (!E || !wav || !n_samples || !out || !n_frames) return fail(FDM_ERR_ARG, "hubert_forward_ragged: null argument");
+  if (B < 1) return fail(FDM_ERR_SHAPE, "hubert_forward_ragged: B = %d", B);
+  for (int b = 0; b < B; ++b) {
+    if (n_samples[b] > n_max) return fail(FDM_ERR_SHAPE, "hubert_forward_ragged: clip %d has %d samples, the batch is %d wide", b, n_samples[b], n_max);
+    int T[7];
+    if (n_samples[b] >= 400) conv_lengths(n_samples[b], T);
+    if (n_samples[b] < 400 || T[6] < 2) return fail(FDM_ERR_SHAPE, "hubert_forward_ragged: clip %d: audio too short (%d samples)", b, n_samples[b]);
+  }
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "hubert_forward_ragged: no gfx950 device visible (there is no CPU fallback)");
+  return hubert_forward_impl(E, wav, n_samples, B, n_max, 0, 0, 0, out, n_frames, stream);
 }
 
 }  // extern "C"
@@ -472,6 +530,7 @@ struct fdm_vq {
   float *x32 = nullptr, *c32 = nullptr, *h = nullptr, *hb = nullptr, *h2 = nullptr, *em = nullptr, *xpad32 = nullptr;
   void *xt = nullptr, *y = nullptr, *xp = nullptr, *nt = nullptr, *q = nullptr, *kp = nullptr, *vp = nullptr, *ctx = nullptr, *u = nullptr, *a = nullptr, *xpt = nullptr;
   int* book = nullptr;
+  int* lens = nullptr;       // per-clip frame counts of the last fdm_vq_decode_ragged [capB]
   double* stat_partial = nullptr; int* stat_hist = nullptr;      // fdm_vq_quant_stats scratch
 };
 
@@ -587,15 +646,16 @@ int vq_reserve(fdm_vq* V, int B, int L) {
   FCK(V->ws.alloc_t(&V->h, M * d)); FCK(V->ws.alloc_t(&V->hb, M * d)); FCK(V->ws.alloc_t(&V->h2, M * d)); FCK(V->ws.alloc_t(&V->em, (size_t)B * d));
   FCK(V->ws.alloc(&V->q, M * d * es)); FCK(V->ws.alloc(&V->ctx, M * d * es)); FCK(V->ws.alloc(&V->a, M * d * es)); FCK(V->ws.alloc(&V->u, M * VQ_FFN * es));
   FCK(V->ws.alloc(&V->kp, (size_t)B * kv_pad(L) * d * es, true)); FCK(V->ws.alloc(&V->vp, (size_t)B * kv_pad(L) * d * es, true));
-  FCK(V->ws.alloc_t(&V->book, (size_t)B));
+  FCK(V->ws.alloc_t(&V->book, (size_t)B)); FCK(V->ws.alloc_t(&V->lens, (size_t)B));
   FCK(V->ws.alloc_t(&V->stat_partial, (size_t)1024)); FCK(V->ws.alloc_t(&V->stat_hist, (size_t)V->d.K));
   if (V->has_encoder) { FCK(V->ws.alloc_t(&V->xpad32, M * V->Kp)); FCK(V->ws.alloc(&V->xpt, M * V->Kp * es)); }
   V->capB = B; V->capL = L;
   return FDM_OK;
 }
 
-// 6 pre-LN blocks on the fp32 residual stream h [B*L, 1024] (updated in place)
-int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B, int L, void* stream) {
+// 6 pre-LN blocks on the fp32 residual stream h [B*L, 1024] (updated in place); lens: per-clip frame counts of a padded batch
+// (device ints) or nullptr -- attention is the only stage of a block that looks across time
+int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B, int L, void* stream, const int* lens = nullptr) {
   const int d = VQ_HIDDEN, dt = V->dtype, M = B * L, hd = d / VQ_HEADS, Lpad = kv_pad(L);
   const size_t es = esize(dt);
   HIPCK(hipMemsetAsync(V->kp, 0, (size_t)B * Lpad * d * es, (hipStream_t)stream));
@@ -614,7 +674,7 @@ int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B,
     memset(&at, 0, sizeof(at));
     at.Q = V->q; at.ldq = d; at.Kp = V->kp; at.Vp = V->vp; at.Lpad = Lpad; at.O = V->ctx; at.ldo = d; at.B = B; at.H = VQ_HEADS; at.L = L; at.hd = hd;
     at.dtype = dt; at.scale = 1.0f / std::sqrt((float)d); at.causal = 0; at.period = 1;      // scale = hidden^-0.5 (base_models.py:144)
-    at.q_lo_off = lo_md; at.kv_lo_off = lo_kv; at.o_lo_off = lo_md;
+    at.q_lo_off = lo_md; at.kv_lo_off = lo_kv; at.o_lo_off = lo_md; at.lens = lens;
     FCK(fdm_op_attention(&at, stream));
     g = dense_gemm(dt, V->ctx, ly.wo.p, M, d, d);
     g.a_lo_off = lo_md; g.w_lo_off = ly.wo.lo;
@@ -634,13 +694,17 @@ int vq_transformer(fdm_vq* V, float* h, const std::vector<Layer>& layers, int B,
 }
 
 // Conv1d(k = 5, replicate) -> LeakyReLU -> InstanceNorm1d -> Linear + pe[0]; xt [B*L, 1024] operand kind -> V->h fp32
-int vq_conv_norm_embed(fdm_vq* V, const void* xt, const Mat& conv_w, const float* conv_b, const Mat& emb_w, const float* emb_b, int B, int L, void* stream) {
+// (lens: the replicate padding copies each clip's own last frame and the instance statistics run over its own frames)
+int vq_conv_norm_embed(fdm_vq* V, const void* xt, const Mat& conv_w, const float* conv_b, const Mat& emb_w, const float* emb_b, int B, int L, void* stream,
+                       const int* lens = nullptr) {
   const int d = VQ_HIDDEN, dt = V->front_dtype(), M = B * L;
-  FCK(fdm_op_pad_rows(xt, V->xp, B, L, d, 2, dt, 0, stream));
+  if (lens) FCK(fdm_op_pad_rows_lens(xt, V->xp, B, L, d, 2, dt, lens, stream));
+  else FCK(fdm_op_pad_rows(xt, V->xp, B, L, d, 2, dt, 0, stream));
   fdm_gemm_args g = dense_gemm(dt, V->xp, conv_w.p, L, d, 5 * d);
   g.lda = d; g.bias = conv_b; g.out_f32 = V->c32; g.batch = B; g.a_batch_stride = (long long)(L + 4) * d; g.out_batch_stride = (long long)L * d;
   FCK(fdm_op_gemm(&g, stream));
-  FCK(fdm_op_leaky_instnorm(V->c32, nullptr, V->nt, B, L, d, 1e-5f, dt, stream));
+  if (lens) FCK(fdm_op_leaky_instnorm_lens(V->c32, nullptr, V->nt, B, L, d, 1e-5f, dt, lens, stream));
+  else FCK(fdm_op_leaky_instnorm(V->c32, nullptr, V->nt, B, L, d, 1e-5f, dt, stream));
   g = dense_gemm(dt, V->nt, emb_w.p, M, d, d);
   g.bias = emb_b; g.resid = V->pe0; g.ldr = d; g.resid_row_mod = 1; g.out_f32 = V->h;
   return fdm_op_gemm(&g, stream);
@@ -716,15 +780,14 @@ int fdm_vq_quant_stats(fdm_vq* V, const float* z, const float* emo_one_hot, cons
   return fdm_op_vq_stats(z, V->codebook, book, idx, B, R, V->d.c, V->d.K, beta, min_encodings, V->stat_partial, V->stat_hist, out2, stream);
 }
 
-int fdm_vq_decode(fdm_vq* V, const float* zq_bcl, int B, int R, float* out, void* stream) {
-  if (!V || !zq_bcl || !out) return fail(FDM_ERR_ARG, "vq_decode: null argument");
+// frames: per-clip frame counts (host, validated by the caller) of a batch padded to L = R / G frames, or nullptr
+static int vq_decode_impl(fdm_vq* V, const float* zq_bcl, const int* frames, int B, int R, float* out, void* stream) {
   const fdm_vq_desc& q = V->d;
-  if (B < 1 || R < 1 || R % q.G) return fail(FDM_ERR_SHAPE, "vq_decode: bad quantised latent shape [%d, %d, %d]", B, q.c, R);
   const int L = R / q.G;
-  if (L < 2) return fail(FDM_ERR_SHAPE, "vq_decode: needs at least 2 frames (InstanceNorm1d over one element is undefined in the reference)");
-  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vq_decode: no gfx950 device visible (there is no CPU fallback)");
   FCK(vq_commit(V, stream));
   FCK(vq_reserve(V, B, L));
+  const int* lens = nullptr;
+  if (frames) { FCK(fdm_op_set_ints(V->lens, frames, B, stream)); lens = V->lens; }
   const int d = VQ_HIDDEN, dt = V->front_dtype(), M = B * L, W = q.G * q.c;
   // [B, c, L*G] -> [B, L*G, c] == [B*L, G*c] (layout only; models/vq_vae_vocaset.py:37-40)
   hipLaunchKernelGGL(bcr_to_brc_kernel, dim3(grid_for((long long)B * q.c * R)), dim3(256), 0, (hipStream_t)stream, zq_bcl, V->x32, B, q.c, R);
@@ -737,13 +800,36 @@ int fdm_vq_decode(fdm_vq* V, const float* zq_bcl, int B, int R, float* out, void
     FCK(fdm_op_gemm(&g, stream));
     xt = V->y;
   }
-  FCK(vq_conv_norm_embed(V, xt, V->conv_w, V->conv_b, V->emb_w, V->emb_b, B, L, stream));
-  FCK(vq_transformer(V, V->h, V->dec_layers, B, L, stream));
+  FCK(vq_conv_norm_embed(V, xt, V->conv_w, V->conv_b, V->emb_w, V->emb_b, B, L, stream, lens));
+  FCK(vq_transformer(V, V->h, V->dec_layers, B, L, stream, lens));
   const void* ht = nullptr;
   FCK(vq_operand(V, V->h, V->a, (long long)M * d, &ht, stream));
   fdm_gemm_args g = dense_gemm(dt, ht, V->out_w.p, M, q.V3, d);
   g.bias = V->out_b; g.out_f32 = out;
-  return fdm_op_gemm(&g, stream);
+  FCK(fdm_op_gemm(&g, stream));
+  if (lens) FCK(fdm_op_zero_pad_rows(out, B, L, q.V3, lens, stream));
+  return FDM_OK;
+}
+
+int fdm_vq_decode(fdm_vq* V, const float* zq_bcl, int B, int R, float* out, void* stream) {
+  if (!V || !zq_bcl || !out) return fail(FDM_ERR_ARG, "vq_decode: null argument");
+  const fdm_vq_desc& q = V->d;
+  if (B < 1 || R < 1 || R % q.G) return fail(FDM_ERR_SHAPE, "vq_decode: bad quantised latent shape [%d, %d, %d]", B, q.c, R);
+  if (R / q.G < 2) return fail(FDM_ERR_SHAPE, "vq_decode: needs at least 2 frames (InstanceNorm1d over one element is undefined in the reference)");
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vq_decode: no gfx950 device visible (there is no CPU fallback)");
+  return vq_decode_impl(V, zq_bcl, nullptr, B, R, out, stream);
+}
+
+int fdm_vq_decode_ragged(fdm_vq* V, const float* zq_bcl, const int* frames, int B, int R_max, float* out, void* stream) {
+  if (!V || !zq_bcl || !frames || !out) return fail(FDM_ERR_ARG, "vq_decode_ragged: null argument");
+  const fdm_vq_desc& q = V->d;
+  if (B < 1 || R_max < 1 || R_max % q.G) return fail(FDM_ERR_SHAPE, "vq_decode_ragged: bad quantised latent shape [%d, %d, %d]", B, q.c, R_max);
+  for (int b = 0; b < B; ++b)
+    if (frames[b] < 2 || frames[b] > R_max / q.G)
+      return fail(FDM_ERR_SHAPE, "vq_decode_ragged: clip %d has %d frames (2 .. %d = R_max / G; InstanceNorm1d over one element is undefined in the reference)",
+                  b, frames[b], R_max / q.G);
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vq_decode_ragged: no gfx950 device visible (there is no CPU fallback)");
+  return vq_decode_impl(V, zq_bcl, frames, B, R_max, out, stream);
 }
 
 int fdm_vq_encode(fdm_vq* V, const float* x, const float* emo_one_hot, int B, int L, float* latent, void* stream) {

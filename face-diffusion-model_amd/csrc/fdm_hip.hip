@@ -182,6 +182,8 @@ int fdm_op_attention(const fdm_attn_args* a, void* stream) {
   if (a->ldq % epc || a->ldo % 4 || !aligned16(a->Q) || !aligned16(a->Kp) || !aligned16(a->Vp) || !aligned16(a->O))
     return fail(FDM_ERR_ARG, "attention: operands need 16-byte aligned rows");
   if (a->slopes && a->period <= 0) return fail(FDM_ERR_ARG, "attention: period must be positive");
+  if (a->lens && (a->causal || (a->hd != 64 && a->hd != 128)))
+    return fail(FDM_ERR_ARG, "attention: per-clip lengths need causal = 0 and head_dim 64 or 128");
   fdm_attn_args c = *a;
   return submit([c](hipStream_t s) { return fdm::attn_launch(c, s); }, stream, "attention");
 }
@@ -341,6 +343,26 @@ int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int
   }, stream, "pad_rows");
 }
 
+int fdm_op_pad_rows_lens(const void* in, void* out, int B, int L, int d, int pad, int dtype, const int* lens, void* stream) {
+  if (!in || !out || !lens || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "pad_rows_lens: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "pad_rows_lens: bad dtype %d", dtype);
+  const bool two_byte = kind(dtype).bytes == 2;
+  return submit([=](hipStream_t s) {
+    const long long n = (long long)B * (L + 2 * pad) * d;
+    if (two_byte) hipLaunchKernelGGL((fdm::pad_rows_lens_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, L, d, pad, lens);
+    else hipLaunchKernelGGL((fdm::pad_rows_lens_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, L, d, pad, lens);
+    return hipGetLastError();
+  }, stream, "pad_rows_lens");
+}
+
+int fdm_op_zero_pad_rows(float* x, int B, int L, int d, const int* lens, void* stream) {
+  if (!x || !lens || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "zero_pad_rows: bad argument");
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::zero_pad_rows_kernel, dim3(grid_for((long long)B * L * d)), dim3(256), 0, s, x, B, L, d, lens);
+    return hipGetLastError();
+  }, stream, "zero_pad_rows");
+}
+
 int fdm_op_group_pad(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, void* stream) {
   if (!in || !out || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "group_pad: bad argument");
   if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "group_pad: bad dtype %d", dtype);
@@ -352,6 +374,43 @@ int fdm_op_group_pad(const void* in, void* out, int B, int T, int d, int groups,
     else hipLaunchKernelGGL((fdm::group_pad_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, T, d, groups, pad);
     return hipGetLastError();
   }, stream, "group_pad");
+}
+
+int fdm_op_group_pad_lens(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, const int* lens, void* stream) {
+  if (!in || !out || !lens || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "group_pad_lens: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "group_pad_lens: bad dtype %d", dtype);
+  const long long n = (long long)B * (T + 2 * pad) * d;
+  const bool two_byte = kind(dtype).bytes == 2;
+  return submit([=](hipStream_t s) {
+    if (two_byte)
+      hipLaunchKernelGGL((fdm::group_pad_lens_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, T, d, groups, pad, lens);
+    else hipLaunchKernelGGL((fdm::group_pad_lens_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, T, d, groups, pad, lens);
+    return hipGetLastError();
+  }, stream, "group_pad_lens");
+}
+
+int fdm_op_mask_samples(const float* wav, float* out, int B, int n, const int* lens, void* stream) {
+  if (!wav || !out || !lens || B <= 0 || n <= 0) return fail(FDM_ERR_ARG, "mask_samples: bad argument");
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::mask_samples_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, s, wav, out, B, n, lens);
+    return hipGetLastError();
+  }, stream, "mask_samples");
+}
+
+int fdm_op_set_ints(int* dst, const int* src, int n, void* stream) {
+  if (!dst || !src || n <= 0) return fail(FDM_ERR_ARG, "set_ints: bad argument");
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    fdm::IntPack p;
+    const int m = n - i0 < 64 ? n - i0 : 64;
+    for (int i = 0; i < 64; ++i) p.v[i] = i < m ? src[i0 + i] : 0;
+    int* d = dst + i0;
+    const int r = submit([=](hipStream_t s) {
+      hipLaunchKernelGGL(fdm::set_ints_kernel, dim3(1), dim3(64), 0, s, d, p, m);
+      return hipGetLastError();
+    }, stream, "set_ints");
+    if (r != FDM_OK) return r;
+  }
+  return FDM_OK;
 }
 
 int fdm_op_conv0(const float* wav, const float* w, const float* bias, float* out, int B, int n, int T0, void* stream) {
@@ -388,6 +447,18 @@ int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L,
   }, stream, "leaky_instnorm");
 }
 
+int fdm_op_leaky_instnorm_lens(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, const int* lens, void* stream) {
+  if (!x || (!y_f32 && !y_t) || !lens || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: bad dtype %d", dtype);
+  if (y_t && dtype != FDM_F32 && dtype != FDM_BF16) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: y_t dtype %d (fp32 or bf16 output)", dtype);
+  return submit([=](hipStream_t s) {
+    dim3 grid((d + 63) / 64, B);
+    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::leaky_instnorm_lens_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, y_f32, (fdm::bf16*)y_t, L, d, eps, lens);
+    else hipLaunchKernelGGL((fdm::leaky_instnorm_lens_kernel<float>), grid, dim3(1024), 0, s, x, y_f32, (float*)y_t, L, d, eps, lens);
+    return hipGetLastError();
+  }, stream, "leaky_instnorm_lens");
+}
+
 int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
                           float eps, int act, int dtype, void* scratch, long long scratch_bytes, void* stream) {
   if (!x || (!y_f32 && !y_t) || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "time_groupnorm: bad argument");
@@ -417,6 +488,34 @@ int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta,
     else hipLaunchKernelGGL((fdm::time_groupnorm_kernel<float>), grid, dim3(1024), 0, s, x, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act);
     return hipGetLastError();
   }, stream, "time_groupnorm");
+}
+
+int fdm_op_time_groupnorm_lens(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
+                               float eps, int act, int dtype, void* scratch, long long scratch_bytes, const int* lens, void* stream) {
+  if (!x || (!y_f32 && !y_t) || !lens || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "time_groupnorm_lens: bad argument");
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "time_groupnorm_lens: bad dtype %d", dtype);
+  if (y_t && dtype == FDM_F16) return fail(FDM_ERR_ARG, "time_groupnorm_lens: y_t dtype %d (fp32, bf16 or FDM_F16X3 output)", dtype);
+  if (y_t && dtype == FDM_F16X3 && y_t_lo_off <= 0) return fail(FDM_ERR_ARG, "time_groupnorm_lens: split y_t needs y_t_lo_off");
+  // a clip of >= 4096 frames takes the chunked form, as fdm_op_time_groupnorm does when it is given scratch: here the scratch is required
+  const int nch = T >= 4096 ? std::min(64, (T + 1023) / 1024) : 0;
+  const long long need = (long long)B * nch * C * 2 * (long long)sizeof(double);
+  if (nch && (!scratch || scratch_bytes < need || ((uintptr_t)scratch % 8) != 0))
+    return fail(FDM_ERR_ARG, "time_groupnorm_lens: T = %d needs %lld bytes of 8-byte aligned scratch", T, need);
+  const long long lo = y_t_lo_off;
+  double* part = (double*)scratch;
+  return submit([=](hipStream_t s) {
+    const dim3 g1((C + 63) / 64, B), g2((C + 63) / 64, nch ? nch : 1, B);
+    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<fdm::bf16>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, eps, act, lens);
+    else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<fdm::f16x3_t>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, eps, act, lens);
+    else hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<float>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act, lens);
+    if (nch) {
+      hipLaunchKernelGGL(fdm::time_stats_lens_kernel, g2, dim3(1024), 0, s, x, part, T, C, lens);
+      if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<fdm::bf16>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, eps, act, lens);
+      else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<fdm::f16x3_t>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, eps, act, lens);
+      else hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<float>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act, lens);
+    }
+    return hipGetLastError();
+  }, stream, "time_groupnorm_lens");
 }
 
 int fdm_op_mean_diff(const float* a, const float* b, float* partial, float* out, long long n, int l1, void* stream) {

@@ -67,7 +67,8 @@ class VqDesc(C.Structure):
 class AttnArgs(C.Structure):
     _fields_ = [("Q", vp), ("ldq", ll), ("Kp", vp), ("Vp", vp), ("Lpad", ci),
                 ("O", vp), ("ldo", ll), ("B", ci), ("H", ci), ("L", ci), ("hd", ci), ("dtype", ci),
-                ("scale", cf), ("causal", ci), ("slopes", vp), ("period", ci), ("o_split", ci), ("o_lo_off", ll), ("q_lo_off", ll), ("kv_lo_off", ll)]
+                ("scale", cf), ("causal", ci), ("slopes", vp), ("period", ci), ("o_split", ci), ("o_lo_off", ll), ("q_lo_off", ll), ("kv_lo_off", ll),
+                ("lens", vp)]
 
 
 class LnArgs(C.Structure):
@@ -103,13 +104,20 @@ SYMBOLS = {
     "fdm_op_add_rows": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, ll, ci, vp]),
     "fdm_op_small_linear": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "fdm_op_pad_rows": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "fdm_op_pad_rows_lens": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp]),
+    "fdm_op_zero_pad_rows": (ci, [vp, ci, ci, ci, vp, vp]),
     "fdm_op_group_pad": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "fdm_op_set_ints": (ci, [vp, vp, ci, vp]),
+    "fdm_op_mask_samples": (ci, [vp, vp, ci, ci, vp, vp]),
+    "fdm_op_group_pad_lens": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "fdm_op_conv0": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "fdm_op_conv0_ln_gelu": (ci, [vp, vp, vp, vp, vp, vp, ll, ci, ci, ci, cf, ci, vp]),
     "fdm_op_leaky_instnorm": (ci, [vp, vp, vp, ci, ci, ci, cf, ci, vp]),
+    "fdm_op_leaky_instnorm_lens": (ci, [vp, vp, vp, ci, ci, ci, cf, ci, vp, vp]),
     "fdm_op_adain": (ci, [vp, vp, vp, ci, ci, ci, cf, vp]),
     "fdm_op_mean_diff": (ci, [vp, vp, vp, vp, ll, ci, vp]),
     "fdm_op_time_groupnorm": (ci, [vp, vp, vp, vp, vp, ll, ci, ci, ci, cf, ci, ci, vp, ll, vp]),
+    "fdm_op_time_groupnorm_lens": (ci, [vp, vp, vp, vp, vp, ll, ci, ci, ci, cf, ci, ci, vp, ll, vp, vp]),
     "fdm_op_vq_quant": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "fdm_op_vq_stats": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
     "fdm_prog_create": (ci, [C.POINTER(vp)]),
@@ -147,12 +155,14 @@ SYMBOLS = {
     "fdm_hubert_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_hubert_forward": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, C.POINTER(ci), vp]),
     "fdm_hubert_frames": (ci, [ci]),
+    "fdm_hubert_forward_ragged": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "fdm_hubert_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "fdm_vq_quant_stats": (ci, [vp, vp, vp, vp, ci, ci, cf, vp, vp, vp]),
     "fdm_vq_decode": (ci, [vp, vp, ci, ci, vp, vp]),
+    "fdm_vq_decode_ragged": (ci, [vp, vp, vp, ci, ci, vp, vp]),
     "fdm_vq_encode": (ci, [vp, vp, vp, ci, ci, vp, vp]),
     "fdm_vq_destroy": (ci, [vp]),
     "fdm_schedule_host": (ci, [ci, vp]),

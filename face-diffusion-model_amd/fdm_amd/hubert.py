@@ -140,3 +140,34 @@ class HubertPlan:
             raise FdmError(f"fdm_hubert_forward produced {nf.value} frames, expected {N}")
         self._wav = wav          # read asynchronously on this stream
         return out
+
+    def forward_ragged(self, wavs):
+        """Clips of unequal length in ONE call: wavs = list of 1-D processor-normalised waveforms -> (out [B, N_max, D] fp32, lens),
+        lens[b] = num_frames(len(wavs[b])).  Rows [0, lens[b]) of clip b are bit for bit forward() of that clip alone; rows beyond
+        are zeros (fdm_hubert_forward_ragged)."""
+        ws = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in wavs]
+        ns = [int(w.numel()) for w in ws]
+        wav = torch.zeros(len(ws), max(ns), device=self.device)
+        for b, w in enumerate(ws):
+            wav[b, :ns[b]] = w.to(self.device)
+        return self.forward_padded(wav, ns)
+
+    def forward_padded(self, wav, n_samples):
+        """forward_ragged on an already padded batch: wav [B, n_max] (what it holds at or beyond n_samples[b] never matters)."""
+        import ctypes as C
+        from ._lib import check, lib
+        dv = self.device
+        wav = wav.detach().to(device=dv, dtype=torch.float32).contiguous()
+        B, n_max = wav.shape
+        ns = [int(n) for n in n_samples]
+        if len(ns) != B:
+            raise FdmError(f"{len(ns)} lengths for {B} clips")
+        lens = [num_frames(n) if n >= 400 else 0 for n in ns]      # the per-clip even crop (== fdm_hubert_frames)
+        out = torch.empty(B, max(max(lens), 1), self.cfg.D, device=dv)
+        nsa, nf = (C.c_int * B)(*ns), (C.c_int * B)()
+        with torch.cuda.device(dv):
+            check(lib().fdm_hubert_forward_ragged(self.h, wav.data_ptr(), nsa, B, n_max, out.data_ptr(), nf, torch.cuda.current_stream().cuda_stream))
+        if list(nf) != lens:
+            raise FdmError(f"fdm_hubert_forward_ragged produced {list(nf)} frames, expected {lens}")
+        self._wav = wav
+        return out, lens

@@ -221,6 +221,12 @@ class HubertModel(ParamTree):
         out = self._get_plan(input_values.device).forward(input_values, frame_num=frame_num, interp_fps=interp_fps)
         return SimpleNamespace(last_hidden_state=out, hidden_states=None, attentions=None)
 
+    def encode_many(self, wavs, device="cuda:0"):
+        """Clips of unequal length in ONE encoder call: list of 1-D waveforms -> list of last_hidden_state [1, N_b, D], each bit for
+        bit forward() of that clip alone (HubertPlan.forward_ragged)."""
+        out, lens = self._get_plan(device).forward_ragged(wavs)
+        return [out[b:b + 1, :n].contiguous() for b, n in enumerate(lens)]
+
 
 class Wav2Vec2Model(HubertModel):
     """wav2vec2-base (12 layers, d = 768) with the reference's forward override (models/wav2vec.py:69-143):
@@ -650,3 +656,11 @@ class VQAutoEncoder(ParamTree):
         if not quant.is_cuda:
             raise FdmError("VQAutoEncoder.decode runs on the HIP path only")
         return self.plan(quant.device).decode(quant)
+
+    def decode_many(self, quant, frames):
+        """Clips of unequal length in ONE decode: quant [B, c, L_max*G] (clip b's codes in its first frames[b]*G positions),
+        frames: B ints -> [B, L_max, V3]; rows [0, frames[b]) of clip b are bit for bit decode() of that clip alone, rows beyond
+        are zeros (VQPlan.decode_ragged)."""
+        if not quant.is_cuda:
+            raise FdmError("VQAutoEncoder.decode_many runs on the HIP path only")
+        return self.plan(quant.device).decode_ragged(quant, frames)

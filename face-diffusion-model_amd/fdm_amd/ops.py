@@ -139,7 +139,8 @@ def pack_kv(K, V, Kp, Vp, *, B, H, L, Lpad, hd, ldk, ldv):
     check(lib().fdm_op_pack_kv(_p(K), ldk, _p(V), ldv, _p(Kp), _p(Vp), B, H, L, Lpad, hd, code_of(K), stream()))
 
 
-def attention(Q, Kp, Vp, O, *, B, H, L, hd, ldq, ldo, Lpad, scale, causal=False, slopes=None, period=1):
+def attention(Q, Kp, Vp, O, *, B, H, L, hd, ldq, ldo, Lpad, scale, causal=False, slopes=None, period=1, lens=None):
+    """lens: device int32 [B], per-clip lengths inside the padded [B, L] problem (fdm_attn_args.lens; non-causal, head dim 64 / 128)."""
     a = AttnArgs()
     a.Q, a.ldq, a.Kp, a.Vp, a.Lpad = _p(Q), ldq, _p(Kp), _p(Vp), Lpad
     a.O, a.ldo, a.B, a.H, a.L, a.hd, a.dtype = _p(O), ldo, B, H, L, hd, code_of(Q)
@@ -147,7 +148,7 @@ def attention(Q, Kp, Vp, O, *, B, H, L, hd, ldq, ldo, Lpad, scale, causal=False,
         a.q_lo_off, a.kv_lo_off, a.o_lo_off = Q.lo_off, Kp.lo_off, O.lo_off
     elif isinstance(O, Split):     # fp32 attention writing the next GEMM's split operand
         a.o_split, a.o_lo_off = O.code, O.lo_off
-    a.scale, a.causal, a.slopes, a.period = scale, int(causal), _p(slopes), period
+    a.scale, a.causal, a.slopes, a.period, a.lens = scale, int(causal), _p(slopes), period, _p(lens)
     check(lib().fdm_op_attention(C.byref(a), stream()))
 
 
@@ -227,6 +228,15 @@ def pad_rows(inp, out, B, L, d, pad, zero=False):
     check(lib().fdm_op_pad_rows(_p(inp), _p(out), B, L, d, pad, code_of(inp), int(zero), stream()))
 
 
+def pad_rows_lens(inp, out, B, L, d, pad, lens):
+    """Replicate padding of clips of unequal length (lens: device int32 [B]) inside one padded [B, L, d] batch."""
+    check(lib().fdm_op_pad_rows_lens(_p(inp), _p(out), B, L, d, pad, code_of(inp), _p(lens), stream()))
+
+
+def zero_pad_rows(x, B, L, d, lens):
+    check(lib().fdm_op_zero_pad_rows(_p(x), B, L, d, _p(lens), stream()))
+
+
 def group_pad(inp, out, B, T, d, groups, pad):
     check(lib().fdm_op_group_pad(_p(inp), _p(out), B, T, d, groups, pad, code_of(inp), stream()))
 
@@ -242,6 +252,10 @@ def conv0_ln_gelu(wav, w, bias, gamma, beta, out, B, n, T0, eps=1e-5):
 
 def leaky_instnorm(x, B, L, d, *, y_f32=None, y_t=None, eps=1e-5, dtype=F32):
     check(lib().fdm_op_leaky_instnorm(_p(x), _p(y_f32), _p(y_t), B, L, d, eps, dtype, stream()))
+
+
+def leaky_instnorm_lens(x, B, L, d, lens, *, y_f32=None, y_t=None, eps=1e-5, dtype=F32):
+    check(lib().fdm_op_leaky_instnorm_lens(_p(x), _p(y_f32), _p(y_t), B, L, d, eps, dtype, _p(lens), stream()))
 
 
 def time_groupnorm(x, gamma, beta, B, T, C, *, y_f32=None, y_t=None, eps=1e-5, act=ACT_NONE, dtype=F32, scratch=None):

@@ -146,7 +146,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
-                 seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0):
+                 seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
 
     The reference's samplers take the clips of a loader one at a time (bs = 1: samples/sample_diffusion_vocaset.py:51,71-83),
@@ -160,12 +160,19 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     order and clip b draws the noise stream of index b (Philox key clip0 + position), so results do not depend on max_batch.
     A group's length is rounded up to a multiple of `bucket` frames (free: the padding is exact), so a long-running caller
     cycles through a handful of shapes whose recorded step programs and tuned tiles the plan keeps.  sampler / sampler_steps / eta:
-    as animate() (groups follow the caller's order, noise keyed as for DDPM)."""
+    as animate() (groups follow the caller's order, noise keyed as for DDPM).
+    batch_stages: the two stages that are not causal run batched too -- ONE audio-encoder call over all clips of the call
+    (encode_many) and, per group, ONE padded quant and ONE decode (VQAutoEncoder.decode_many); every kernel that looks across time
+    carries the clips' own lengths, and the returned lists are torch.equal to the per-clip path's.  Off by default: its gain is
+    unmeasured (profiles/ragged/README.md)."""
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
     n = len(audios)
     wavs = [torch.as_tensor(a, dtype=torch.float32, device=device).reshape(1, -1) for a in audios]
-    hubs = [model.audio_encoder(w).last_hidden_state for w in wavs]                 # [1, N_b, fw] each, own length
+    if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
+        hubs = model.audio_encoder.encode_many([w[0] for w in wavs], device)
+    else:
+        hubs = [model.audio_encoder(w).last_hidden_state for w in wavs]             # [1, N_b, fw] each, own length
     Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
 
     def row(x, b, width, default):
@@ -205,10 +212,18 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                 lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T)
             else:
                 lat = diffusion.sample(dummy, shape, ids, seed=seed, x_T=x_T, clip0=g0)
+            outs = None
+            if batch_stages:        # one padded quant (per row) and one decode that knows each clip's length
+                lat_g = lat[:, :max(Ls[b] for b in grp) * p.G].contiguous()        # (not the bucket's rows: they belong to no clip)
+                qs = autoencoder.quant(lat_g, emos, stats=False)[0] if p.n_emo else autoencoder.quant(lat_g, stats=False)[0]
+                outs = autoencoder.decode_many(qs, [Ls[b] for b in grp])
             for i, b in enumerate(grp):
                 lb = lat[i:i + 1, :Ls[b] * p.G].contiguous()
-                q = autoencoder.quant(lb, emos[i:i + 1], stats=False)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
-                out = autoencoder.decode(q)
+                if outs is not None:
+                    out = outs[i:i + 1, :Ls[b]].contiguous()
+                else:
+                    q = autoencoder.quant(lb, emos[i:i + 1], stats=False)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
+                    out = autoencoder.decode(q)
                 if templates is not None:
                     tp = templates[b] if isinstance(templates, (list, tuple)) else templates
                     out = out + torch.as_tensor(tp, dtype=torch.float32, device=device).reshape(1, 1, -1)
@@ -281,12 +296,15 @@ class SlotServer:
     ddim_steps (presets without an emotion input), else the DDPM chain.  Guidance when `diffusion` wraps a
     ClassifierFreeSampleModel.  max_frames: latent frames a slot holds (default the model's max_len); a longer clip is refused.
     The server owns the model's plan while it runs: an animate*() call on the same model returns the plan to plain mode and the
-    next submit() / step() raises."""
+    next submit() / step() raises.  batch_stages: the clips that finish in one step() call are quantised in one padded call and
+    decoded in one call over their unequal lengths (VQAutoEncoder.decode_many) -- the same results, bit for bit."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
-                 device="cuda:0"):
+                 device="cuda:0", batch_stages=False):
         from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
+        self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
+        self.batched_decodes = []                   # clips per batched decode, in call order
         self.cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
         self.model = diffusion.denoise_fn.model if self.cfg else diffusion.denoise_fn
         p = self.p = self.model.preset
@@ -333,6 +351,36 @@ class SlotServer:
         self._fill()
         return h
 
+    @torch.no_grad()
+    def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0):
+        """Several requests at once: ONE audio-encoder call over the waveforms' unequal lengths (encode_many), then each request is
+        admitted or queued exactly as submit() does it, in the given order.  templates / id_one_hots / emotion_one_hots / seeds:
+        one per request (lists) or one for all.  Returns the handles; results equal submit() in a loop bit for bit."""
+        self._check()
+        p, dev = self.p, self.device
+        n = len(audios)
+        per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
+        hubs = self.model.audio_encoder.encode_many([torch.as_tensor(a, dtype=torch.float32).reshape(-1) for a in audios], dev)
+        Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
+        for L in Ls:
+            if L < 1 or L > self.L:
+                raise ValueError(f"clip of {L} latent frames, slots hold [1, {self.L}]")
+        handles = []
+        for b in range(n):
+            ido, emo_in, seed = per(id_one_hots, b), per(emotion_one_hots, b), int(per(seeds, b))
+            ids = torch.eye(p.n_style)[:1] if ido is None else torch.as_tensor(ido, dtype=torch.float32).reshape(-1, p.n_style)[:1]
+            emo = None
+            if p.n_emo:
+                emo = torch.eye(p.n_emo)[4:5] if emo_in is None else torch.as_tensor(emo_in, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
+                emo = emo.to(dev)
+            x_T = torch.randn((1, Ls[b] * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
+            h = self._next
+            self._next += 1
+            self._queue.append(dict(handle=h, hub=hubs[b], L=Ls[b], ids=ids.to(dev), emo=emo, x_T=x_T, seed=seed, template=per(templates, b)))
+            handles.append(h)
+        self._fill()
+        return handles
+
     def _fill(self):
         for s in range(self.n_slots):
             if self._slot[s] is None and self._queue:
@@ -349,6 +397,10 @@ class SlotServer:
         self._check()
         self._fill()
         self.plan.run(n)
+        if self.batch_stages:
+            fin = self._finish_batched()
+            self._fill()
+            return fin
         fin = 0
         for s in range(self.n_slots):
             r = self._slot[s]
@@ -364,6 +416,29 @@ class SlotServer:
             fin += 1
         self._fill()
         return fin
+
+    def _finish_batched(self):
+        """batch_stages: the clips whose chains ended in this call through ONE padded quant and ONE decode over their unequal lengths."""
+        from ._lib import SLOT_FINISHED
+        p = self.p
+        done = [s for s in range(self.n_slots) if self._slot[s] is not None and self.plan.slot_state(s)[2] == SLOT_FINISHED]
+        if not done:
+            return 0
+        reqs = [self._slot[s] for s in done]
+        lats = [self.plan.read_slot(s, r["L"]) for s, r in zip(done, reqs)]
+        pad = torch.zeros(len(done), max(r["L"] for r in reqs) * p.G, p.c, device=lats[0].device)
+        for i, lat in enumerate(lats):
+            pad[i, :lat.shape[1]] = lat[0]
+        qs = self.ae.quant(pad, torch.cat([r["emo"] for r in reqs]), stats=False)[0] if p.n_emo else self.ae.quant(pad, stats=False)[0]
+        outs = self.ae.decode_many(qs, [r["L"] for r in reqs])
+        self.batched_decodes.append(len(done))
+        for i, (s, r) in enumerate(zip(done, reqs)):
+            out = outs[i:i + 1, :r["L"]].contiguous()
+            if r["template"] is not None:
+                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
+            self._done.append((r["handle"], out, lats[i]))
+            self._slot[s] = None
+        return len(done)
 
     @property
     def pending(self):

@@ -135,3 +135,23 @@ class VQPlan:
             check(lib().fdm_vq_decode(self.h, zq.data_ptr(), B, R, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
         self._in = (zq,)
         return out
+
+    def decode_ragged(self, zq, frames):
+        """Clips of unequal length in one call: zq [B, c, L_max*G] (clip b's latent in its first frames[b]*G positions; what the rest
+        holds never matters), frames: B ints, 2 <= frames[b] <= L_max -> [B, L_max, V3] fp32.  Rows [0, frames[b]) of clip b are bit
+        for bit decode() of that clip alone; rows beyond are zeros (fdm_vq_decode_ragged)."""
+        import ctypes as C
+        from ._lib import check, lib
+        p, dv = self.p, self.device
+        B, c, R = zq.shape
+        frames = [int(f) for f in frames]
+        if c != p.c or R % p.G or len(frames) != B:
+            raise FdmError(f"bad quantised latent shape {tuple(zq.shape)} for {len(frames)} clips")
+        L = R // p.G
+        zq = zq.detach().to(device=dv, dtype=torch.float32).contiguous()
+        out = torch.empty(B, L, p.V3, device=dv)
+        fr = (C.c_int * B)(*frames)
+        with torch.cuda.device(dv):
+            check(lib().fdm_vq_decode_ragged(self.h, zq.data_ptr(), fr, B, R, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        self._in = (zq,)
+        return out

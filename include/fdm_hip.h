@@ -261,6 +261,12 @@ typedef struct fdm_attn_args {
    * 16-bit MFMA passes with the probabilities split in registers: fp32-class results.  q_lo_off / kv_lo_off / o_lo_off =
    * elements between the hi and lo planes of Q / Kp and Vp / O. */
   long long q_lo_off, kv_lo_off;
+  /* per-clip lengths ([B] device ints, 1 <= lens[b] <= L) or NULL = every clip is L long.  Clip b sees keys [0, lens[b]) and its key
+   * tiles are counted, dealt to the waves and masked from lens[b] exactly as a launch with L = lens[b] does it: rows [0, lens[b]) of
+   * clip b are bit for bit what that launch returns for the clip alone.  Rows at or beyond lens[b] are written as zeros; K / V
+   * entries of key tiles wholly beyond lens[b] are never read (they may hold anything), those of the straddling tile must be
+   * finite as pad keys are.  Non-causal only (causal = 0), head_dim 64 / 128.  (tests/test_ragged_gpu.py) */
+  const int* lens;
 } fdm_attn_args;
 int fdm_op_attention(const fdm_attn_args* a, void* stream);
 /* row-major K, V (row b*L + l, column h*hd + e, row strides ldk / ldv) -> the packed layouts above */
@@ -319,6 +325,19 @@ int fdm_op_small_linear(const float* x, const float* W, const float* bias, float
                         int act, void* stream);
 /* out[b, k, :] = in[b, clamp(k - pad, 0, L-1), :] for k in [0, L + 2*pad): replicate padding, channels-last */
 int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream);
+/* the replicate form with per-clip lengths ([B] device ints, 1 <= lens[b] <= L): out[b, k, :] = in[b, clamp(k - pad, 0, lens[b]-1), :],
+ * so a clip's end padding copies its own last frame and rows of `in` at or beyond lens[b] are never read */
+int fdm_op_pad_rows_lens(const void* in, void* out, int B, int L, int d, int pad, int dtype, const int* lens, void* stream);
+/* x[b, l, :] = 0 for l >= lens[b] (x [B, L, d] fp32, lens [B] device ints): the pad rows of a batch of clips of unequal length */
+int fdm_op_zero_pad_rows(float* x, int B, int L, int d, const int* lens, void* stream);
+/* dst[i] = src[i], src a HOST array of n ints: the values travel inside kernel arguments (64 per launch), in stream order, so src is
+ * not read after the call returns and need not be pinned -- how the per-clip lengths of the *_ragged calls reach the device */
+int fdm_op_set_ints(int* dst, const int* src, int n, void* stream);
+/* out[b, i] = wav[b, i] for i < lens[b], 0 beyond (wav, out [B, n] fp32; lens [B] device ints): a padded batch of waveforms with
+ * its padding cleared, whatever it held */
+int fdm_op_mask_samples(const float* wav, float* out, int B, int n, const int* lens, void* stream);
+/* fdm_op_group_pad with per-clip lengths ([B] device ints): frames at or beyond lens[b] are written as zeros */
+int fdm_op_group_pad_lens(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, const int* lens, void* stream);
 /* HuBERT / wav2vec2 conv layer 0: wav [B, n] -> out [B, T0, 512], Conv1d(1, 512, k=10, s=5) (+ bias if non-NULL) */
 int fdm_op_conv0(const float* wav, const float* w, const float* bias, float* out, int B, int n, int T0, void* stream);
 /* the same layer with the LayerNorm(512, eps) + GELU(erf) that follows it in HuBERT-large (feat_extract_norm = 'layer') applied
@@ -327,6 +346,9 @@ int fdm_op_conv0_ln_gelu(const float* wav, const float* w, const float* bias, co
                          long long out_lo_off, int B, int n, int T0, float eps, int dtype, void* stream);     /* dtype FDM_F16X3: a plane pair, lo plane out_lo_off elements on */
 /* per-(clip, channel) InstanceNorm1d over L after LeakyReLU(0.2): models/vq_vae_vocaset.py:204-209 */
 int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, void* stream);
+/* the same with per-clip lengths ([B] device ints, 1 <= lens[b] <= L): clip b's statistics run over its first lens[b] frames in the
+ * order of a call with L = lens[b]; frames at or beyond lens[b] are written as zeros */
+int fdm_op_leaky_instnorm_lens(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, const int* lens, void* stream);
 /* GroupNorm(num_groups = C, affine) over time + activation, channels-last x [B, T, C]: first conv layer of
  * wav2vec2-base (transformers Wav2Vec2GroupNormConvLayer; BIWI audio encoder, models/wav2vec.py:69-143) */
 /* scratch (optional, 8-byte aligned, >= B * min(64, ceil(T / 1024)) * C * 16 bytes): with it, clips of T >= 4096 frames are
@@ -334,6 +356,11 @@ int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L,
  * it one launch of C / 64 workgroups per clip does the three passes (fine for short clips; the operator never allocates) */
 int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
                           float eps, int act, int dtype, void* scratch, long long scratch_bytes, void* stream);
+/* the same with per-clip lengths ([B] device ints, 1 <= lens[b] <= T): clip b is normalised over its first lens[b] frames in the form
+ * and order of a call with T = lens[b] and scratch (three passes below 4096 frames, fp64 chunks of ITS length from there on);
+ * frames at or beyond lens[b] are written as zeros.  scratch is required when T >= 4096 (FDM_ERR_ARG otherwise). */
+int fdm_op_time_groupnorm_lens(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
+                               float eps, int act, int dtype, void* scratch, long long scratch_bytes, const int* lens, void* stream);
 /* out[0] = mean(|a - b|^p), p = 2 (l1 = 0) or 1: the forward value of p_losses' F.mse_loss / F.l1_loss
  * (diffusion_BIWI_encoder_decoder.py:744-749); partial: >= 1024 floats of scratch; deterministic order */
 int fdm_op_mean_diff(const float* a, const float* b, float* partial, float* out, long long n, int l1, void* stream);
@@ -573,6 +600,13 @@ int fdm_hubert_set_weights(fdm_audio_encoder* e, const char* name, const float* 
 int fdm_hubert_forward(fdm_audio_encoder* e, const float* wav, int B, int n_samples, int frame_num, int interp_in_fps, int interp_out_fps,
                        float* out, int* n_frames, void* stream);
 int fdm_hubert_frames(int n_samples);
+/* B clips of unequal length in one call, padded to the longest: wav [B, n_max], n_samples [B] HOST ints (copied to the device in
+ * stream order, not read after the call returns) -> out [B, N_max, D] with N[b] = fdm_hubert_frames(n_samples[b]) (the even crop per
+ * clip), N_max = max N[b]; n_frames [B] host ints receives N[b].  Rows [0, N[b]) of clip b are bit for bit what fdm_hubert_forward
+ * returns for that clip alone (B = 1, n = n_samples[b], no frame_num, no interpolation), for both kinds and every dtype; rows at or
+ * beyond N[b] are zeros; what wav holds at or beyond n_samples[b] never matters (it may be NaN).  Every check is made before the
+ * first launch: FDM_ERR_ARG (null pointer), FDM_ERR_SHAPE (B < 1, a clip shorter than fdm_hubert_forward accepts, n_samples[b] > n_max). */
+int fdm_hubert_forward_ragged(fdm_audio_encoder* e, const float* wav, const int* n_samples, int B, int n_max, float* out, int* n_frames, void* stream);
 int fdm_hubert_destroy(fdm_audio_encoder* e);
 
 /* ------------------------------------------------------------------------------------------
@@ -596,6 +630,12 @@ int fdm_vq_quant(fdm_vq* v, const float* z, const float* emo_one_hot, int B, int
 int fdm_vq_quant_stats(fdm_vq* v, const float* z, const float* emo_one_hot, const long long* idx, int B, int R, float beta,
                        float* min_encodings, float* out2, void* stream);
 int fdm_vq_decode(fdm_vq* v, const float* zq_bcl, int B, int R, float* out, void* stream);
+/* B clips of unequal length in one call, padded to the longest: z_q [B, c, R_max], frames [B] HOST ints (2 <= frames[b] <= R_max / G;
+ * copied into the object's workspace in stream order, not read after the call returns) -> out [B, L_max, V3], L_max = R_max / G.
+ * Rows [0, frames[b]) of clip b are bit for bit what fdm_vq_decode returns for that clip alone (B = 1, R = frames[b] * G), in
+ * every dtype; rows at or beyond frames[b] are zeros.  What the caller's latent holds beyond frames[b] * G never matters (it may
+ * be NaN).  Every check is made before the first launch: FDM_ERR_ARG (null pointer), FDM_ERR_SHAPE (R_max, frames[b]). */
+int fdm_vq_decode_ragged(fdm_vq* v, const float* zq_bcl, const int* frames, int B, int R_max, float* out, void* stream);
 int fdm_vq_encode(fdm_vq* v, const float* x, const float* emo_one_hot, int B, int L, float* latent, void* stream);
 int fdm_vq_destroy(fdm_vq* v);
 
