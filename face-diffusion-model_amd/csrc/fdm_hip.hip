@@ -77,6 +77,7 @@ int fdm_abi_struct_size(const char* name) {
   if (n == "fdm_model_desc") return (int)sizeof(fdm_model_desc);
   if (n == "fdm_sample_args") return (int)sizeof(fdm_sample_args);
   if (n == "fdm_vq_desc") return (int)sizeof(fdm_vq_desc);
+  if (n == "fdm_slot_group_args") return (int)sizeof(fdm_slot_group_args);
   return fdm::fail(FDM_ERR_ARG, "abi_struct_size: unknown struct '%s'", name);
 }
 
@@ -256,6 +257,37 @@ int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned 
   fdm_sched_args c = *a;
   c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
   return submit([c, state, keys](hipStream_t s) { return fdm::slot_sched_launch(c, state, keys, s); }, stream, "slot_sched");
+}
+
+int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                            const fdm_slot_group_args* g, void* stream) {
+  if (!a || !g || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_group_sched: null operand");
+  if (!g->member || !g->frames || !g->entries || !g->groups || !g->x_long) return fail(FDM_ERR_ARG, "slot_group_sched: null table or arena");
+  if (!g->init && (!a->x0 || !a->x)) return fail(FDM_ERR_ARG, "slot_group_sched: null operand");
+  if (g->init && g->plain) return fail(FDM_ERR_ARG, "slot_group_sched: init loads the arena into the window rows only (plain must be 0)");
+  if (a->noise) return fail(FDM_ERR_ARG, "slot_group_sched: injected noise is not supported (Philox keyed per slot / group)");
+  if (!g->init && a->mode != 0 && a->mode != 1 && a->mode != 3) return fail(FDM_ERR_ARG, "slot_group_sched: mode %d (0 DDPM, 1 DDIM, 3 table-driven)", a->mode);
+  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
+  if (g->L < 1 || g->d < 4 || g->d % 4 || (long long)g->L * g->d != a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched: L=%d x d=%d (a multiple of 4) must be n_per_clip=%lld", g->L, g->d, a->n_per_clip);
+  if (g->arena_frames < 1 || g->n_groups < 1 || g->n_entries < 1 || g->frame0 < 0 || g->frame1 < g->frame0 || g->frame1 > g->arena_frames)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched: arena frames [%d, %d) outside [0, %d), or no groups / entries", g->frame0, g->frame1, g->arena_frames);
+  if (!g->init) {
+    if (a->mode == 0 && (!a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "slot_group_sched: DDPM tables missing");
+    if (a->mode == 1 && (!a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "slot_group_sched: DDIM tables missing");
+    if (a->mode == 3 && (!a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist || !g->hist_long))
+      return fail(FDM_ERR_ARG, "slot_group_sched: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist and hist_long");
+  }
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_group_sched: bad out_dtype %d", a->out_dtype);
+  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_group_sched: split x_out_t needs x_out_t_lo_off");
+  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state) ||
+      !aligned16(g->frames) || !aligned16(g->entries) || !aligned16(g->groups) || !aligned16(g->x_long) || !aligned16(g->hist_long))
+    return fail(FDM_ERR_ARG, "slot_group_sched: operands, table rows and the state words must be 16-byte aligned");
+  fdm_sched_args c = *a;
+  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
+  const fdm_slot_group_args gg = *g;
+  return submit([c, state, keys, gg, n_slots](hipStream_t s) { return fdm::slot_group_sched_launch(c, state, keys, gg, n_slots, s); }, stream, "slot_group_sched");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Host tables of libfdm_hip.so (include/fdm_hip.h, fdm_*_host and fdm_model_preset): everything the plan layer derives from
 // numbers alone -- diffusion schedules, sampler coefficient tables, ALiBi slopes, the positional table, the windowed-sampling
-// layout and blend weights, the model presets.  No device, no plan: callable (and tested) on a machine without a GPU.
+// layout and blend weights, the table of a slot group, the model presets.  No device, no plan: callable (and tested) on a machine without a GPU.
 #include <cmath>
 
 #include "host.hpp"
@@ -105,6 +105,31 @@ int fdm_window_weights_host(int L_total, int window, int overlap, float* w) {
     std::copy(wt.begin(), wt.end(), w);
   }
   return n;
+}
+
+// Tables of one group of a slot plan (include/fdm_hip.h, fdm_slot_admit_long): the windowed layout with window = the slot capacity,
+// each window held by a slot of the caller's list.  The weights are window_weights()'s values themselves.
+int fdm_slot_group_table_host(int L_total, int L, int overlap, const int* slots, int n, int* off, int* ent_slot, int* ent_start,
+                              float* ent_wt, int cap) {
+  if (!slots) return fail(FDM_ERR_ARG, "slot_group_table_host: null slot list");
+  std::vector<int> st;
+  const int nw = fdm::window_layout(L_total, L, overlap, st);
+  if (nw < 0) return nw;
+  if (L_total <= L) return fail(FDM_ERR_SHAPE, "slot_group_table_host: L_total = %d fits one slot of %d frames (no group needed)", L_total, L);
+  if (n != nw) return fail(FDM_ERR_SHAPE, "slot_group_table_host: %d slots for %d windows", n, nw);
+  const long long total = (long long)nw * L;
+  if (total > 0x7fffffffLL) return fail(FDM_ERR_SHAPE, "slot_group_table_host: %d windows of %d frames", nw, L);
+  if (cap < total || !off || !ent_slot || !ent_start || !ent_wt) return (int)total;
+  std::vector<float> wt;
+  fdm::window_weights(L_total, L, overlap, st, wt);
+  int k = 0;
+  off[0] = 0;
+  for (int f = 0; f < L_total; ++f) {
+    for (int w = 0; w < nw; ++w)
+      if (st[w] <= f && f < st[w] + L) { ent_slot[k] = slots[w]; ent_start[k] = st[w]; ent_wt[k] = wt[(size_t)w * L + (f - st[w])]; ++k; }
+    off[f + 1] = k;
+  }
+  return k;
 }
 
 int fdm_schedule_host(int T, float* out) {

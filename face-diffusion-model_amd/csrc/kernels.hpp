@@ -37,6 +37,13 @@ int window_sched_op(const fdm_sched_args& p, const WinArgs& w, void* stream);
 int slot_advance_op(int* state, const int* tseq, int n_steps, int n_slots, void* stream);
 int slot_set_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id, void* stream);
 
+// long requests in slot mode (slots.hpp; tables built by fdm_slot_group_table_host, uploaded by fdm_slot_admit_long): the device rows
+// fdm_slot_group_args points at.  One LongFrame per frame of the long arena, one LongEnt per (window, frame of the window), one
+// LongGroup per group descriptor.
+struct LongFrame { int group; int e0; int e1; int pad; };      // group < 0: the arena frame is free; its covering entries are ent[e0 .. e1)
+struct LongEnt { int slot; int start; float wt; int pad; };    // member slot holding the window, the window's first frame, blend weight
+struct LongGroup { int leader; int L_total; int first; int pad; };      // leader slot, frames of the long clip, its first arena frame
+
 inline hipError_t gemm_launch(const fdm_gemm_args& a, hipStream_t s) {
   switch (a.dtype) {
     case FDM_BF16: return gemm_launch_bf16(a, s);

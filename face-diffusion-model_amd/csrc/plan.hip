@@ -469,6 +469,17 @@ fdm::WinArgs win_args(const fdm_plan* P, int init) {
   return w;
 }
 
+// the group tables and the arena of a slot plan with long capacity, visiting arena frames [f0, f1)
+fdm_slot_group_args long_args(const fdm_plan* P, int f0, int f1, int plain, int init) {
+  fdm_slot_group_args g;
+  memset(&g, 0, sizeof(g));
+  g.member = P->slot_member; g.frames = (const int*)P->long_frame; g.entries = P->long_ent; g.groups = (const int*)P->long_group;
+  g.x_long = P->long_x; g.hist_long = P->long_hist;
+  g.arena_frames = P->long_frames; g.n_entries = P->long_entries; g.n_groups = P->long_groups;
+  g.L = P->L; g.d = P->m.d; g.frame0 = f0; g.frame1 = f1; g.plain = plain; g.init = init;
+  return g;
+}
+
 int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
   char key[512];
   snprintf(key, sizeof(key), "%s#%s|%d|%p|%a|%p|%d", shape_key(P).c_str(), tiles_sig(P).c_str(), sp.kind, (const void*)sp.noise, (double)sp.cfg_scale,
@@ -480,6 +491,10 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
   if (P->slots) {            // slot mode: the chain gathers per slot and nothing advances P->step (plain keys unchanged)
     const size_t kl = strlen(key);
     snprintf(key + kl, sizeof(key) - kl, "|slot%d,%d,%p", sp.slot_steps, P->slots, (const void*)sp.cn);
+    if (P->long_frames) {    // ... and with long capacity the scheduler pass also walks the arena (keys without capacity unchanged)
+      const size_t k2 = strlen(key);
+      snprintf(key + k2, sizeof(key) - k2, "|long%d,%d", P->long_frames, P->long_groups);
+    }
   }
   auto it = P->progs.find(key);
   if (it != P->progs.end()) {            // hit: most recently used goes to the back, and the caller's handle stays valid for this call
@@ -533,7 +548,12 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       sc.n_per_clip = (long long)P->L * d; sc.noise = nullptr; sc.seed_dev = nullptr; sc.step = nullptr; sc.tseq = nullptr;
       rc = fdm::slot_advance_op(P->slot_state, P->tseq, sp.slot_steps, P->slots, stream);
       if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
-      if (rc == FDM_OK) rc = fdm_op_slot_sched(&sc, P->slot_state, P->slot_keys, P->slots, stream);
+      if (rc == FDM_OK) {
+        // long capacity: the same launch also updates the groups over the long arena (fdm_op_slot_group_sched); without it the
+        // program is the plain slot program
+        if (P->long_frames) { const fdm_slot_group_args lg = long_args(P, 0, P->long_frames, 1, 0); rc = fdm_op_slot_group_sched(&sc, P->slot_state, P->slot_keys, P->slots, &lg, stream); }
+        else rc = fdm_op_slot_sched(&sc, P->slot_state, P->slot_keys, P->slots, stream);
+      }
       continue;
     }
     if (sp.kind != 0 && P->win_n) {
@@ -792,6 +812,37 @@ int zero_mat(const fdm_plan* P, const Mat& mt, size_t at, size_t n, void* stream
   return FDM_OK;
 }
 
+// One slot's rows of AF, C1_l (both CFG halves) and E0 for a clip (or a window of a long clip) of L_clip frames whose audio rows start
+// at hub_clip: the per-clip GEMMs of fdm_audio_prepare_conds on L_clip rows, zero addends in the rows L_clip .. L.  Shared by
+// fdm_slot_admit and fdm_slot_admit_long.
+int slot_rows(fdm_plan* P, int slot, const float* hub_clip, const float* style, const float* emo, int L_clip, void* stream) {
+  const fdm_model_desc& m = P->m;
+  hipStream_t s = (hipStream_t)stream;
+  const int d = m.d, L = P->L, M = P->M, row0 = slot * L, pad = L - L_clip;
+  const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
+  FCK(clip_audio_in(P, hub_clip, row0, L_clip, stream));
+  FCK(clip_tables(P, row0, L_clip, P->rep == 2 ? (size_t)M * d : 0, stream));
+  const float *sw = nullptr, *sbias = nullptr, *ew = nullptr, *eb = nullptr;
+  FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
+  float *sty = P->sty + (size_t)slot * d, *em = P->em + (size_t)slot * d, *emu = P->emu + (size_t)slot * d;
+  FCK(fdm_op_small_linear(style, sw, sbias, sty, 1, m.n_style, d, m.style_mish ? FDM_ACT_MISH : FDM_ACT_NONE, stream));
+  if (m.n_emo) {
+    FCK(need(P, "emotion_embedd.weight", (long long)d * m.n_emo, &ew)); FCK(need(P, "emotion_embedd.bias", d, &eb));
+    FCK(fdm_op_small_linear(emo, ew, eb, em, 1, m.n_emo, d, FDM_ACT_NONE, stream));
+    if (P->cfg) FCK(fdm_op_small_linear(P->zeros, ew, eb, emu, 1, m.n_emo, d, FDM_ACT_NONE, stream));
+  }
+  for (int r = 0; r < P->rep; ++r) {
+    const float* e = m.n_emo ? (r == 1 ? emu : em) : nullptr;
+    const size_t ro = (size_t)r * M * d + o;
+    FCK(fdm_op_add_rows(P->pe, 1, L_clip, sty, L_clip, 1, e, L_clip, 1, P->E0 + ro, L_clip, d, stream));
+    if (pad) {      // rows L_clip .. L of the slot: zero addends (the denoiser is causal: they never reach the clip's own frames)
+      HIPCK(hipMemsetAsync(P->E0 + ro + nclip, 0, npad * 4, s));
+      for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l] + ro + nclip, 0, npad * 4, s));
+    }
+  }
+  return FDM_OK;
+}
+
 int check_slots(const fdm_plan* P, const char* who) {
   if (!P) return fail(FDM_ERR_ARG, "%s: null plan", who);
   if (!P->slots || !P->prepared) return fail(FDM_ERR_STATE, "%s: the plan is not in slot mode (fdm_slots_open)", who);
@@ -875,6 +926,7 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   if (S < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: S=%d conditions per clip", S);
   P->win_n = 0;                              // plain mode (fdm_audio_prepare_windows sets the window mode after this call)
   P->slots = 0;                              // ... and out of slot mode (slot programs keep their own cache keys)
+  P->long_frames = P->long_groups = P->long_entries = 0;
   if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
   if (L < 1 || L > N / m.pair || L > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare: latent frames L=%d outside [1, min(%d, %d)] (models/fdm_vocaset.py:44,64-66)", L, N / m.pair, m.max_len);
   if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
@@ -1015,10 +1067,31 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   hipStream_t s = (hipStream_t)stream;
   P->pinned.clear();
   P->win_n = 0; P->slots = 0;
+  P->long_frames = P->long_groups = P->long_entries = 0;
   FCK(commit(P, stream));
   FCK(reserve(P, B, L, cfg));
   FCK(grow(P, (void**)&P->slot_state, &P->slot_state_cap, (size_t)B * 16, stream));
   FCK(grow(P, (void**)&P->slot_keys, &P->slot_keys_cap, (size_t)B * 16, stream));
+  // long capacity asked for before this call: the arena (latent + history), one table row per arena frame, B * L entries (every slot
+  // holds at most one window) and the group descriptors -- all reserved here, nothing per admit
+  const int LF = (P->want_long_frames > 0 && P->want_long_groups > 0) ? P->want_long_frames : 0, LG = LF ? P->want_long_groups : 0;
+  P->long_frames = 0; P->long_groups = 0; P->long_entries = 0;
+  P->group_host.clear();
+  if (LF) {
+    const size_t na = (size_t)LF * m.d;
+    FCK(grow(P, (void**)&P->long_x, &P->long_x_cap, na * 4, stream));
+    FCK(grow(P, (void**)&P->long_hist, &P->long_hist_cap, na * 4, stream));
+    FCK(grow(P, (void**)&P->long_frame, &P->long_frame_cap, (size_t)LF * sizeof(fdm::LongFrame), stream));
+    FCK(grow(P, (void**)&P->long_ent, &P->long_ent_cap, (size_t)B * L * sizeof(fdm::LongEnt), stream));
+    FCK(grow(P, (void**)&P->long_group, &P->long_group_cap, (size_t)LG * sizeof(fdm::LongGroup), stream));
+    FCK(grow(P, (void**)&P->slot_member, &P->slot_member_cap, (size_t)B * 4, stream));
+    HIPCK(hipMemsetAsync(P->long_x, 0, na * 4, s));
+    HIPCK(hipMemsetAsync(P->long_hist, 0, na * 4, s));
+    HIPCK(hipMemsetAsync(P->long_frame, 0xff, (size_t)LF * sizeof(fdm::LongFrame), s));      // group = -1: every arena frame free
+    HIPCK(hipMemsetAsync(P->long_ent, 0, (size_t)B * L * sizeof(fdm::LongEnt), s));
+    HIPCK(hipMemsetAsync(P->long_group, 0, (size_t)LG * sizeof(fdm::LongGroup), s));
+    HIPCK(hipMemsetAsync(P->slot_member, 0xff, (size_t)B * 4, s));                            // -1: every slot plain
+  }
   const int d = m.d, M = B * L, rep = cfg ? 2 : 1;
   P->B = B; P->S = 1; P->L = L; P->M = M; P->rep = rep; P->R = M * rep; P->cfg = cfg ? 1 : 0; P->Lpad = (L + 31) / 32 * 32;
   // every slot idle and holding zeros: tables, latent (+ operand copy), history, packed K / V pad keys, state words and keys
@@ -1044,6 +1117,7 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   P->slot_cfg_scale = a->cfg_scale; P->slot_graph_steps = a->graph_steps; P->slot_eager = a->eager;
   P->slot_host.assign(B, fdm_plan::SlotHost());
   P->slots = B;
+  if (LF) { P->long_frames = LF; P->long_groups = LG; P->long_entries = B * L; P->group_host.assign(LG, fdm_plan::GroupHost()); }
   P->prepared = true;
   select_tiles(P);
   return FDM_OK;
@@ -1061,29 +1135,9 @@ int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const
   fdm_plan::SlotHost& h = P->slot_host[slot];
   if (h.status != 0) return fail(FDM_ERR_STATE, "slot_admit: slot %d is %s", slot, h.status == 1 ? "running" : "finished and not read");
   hipStream_t s = (hipStream_t)stream;
-  const int d = m.d, L = P->L, M = P->M, row0 = slot * L, pad = L - L_clip;
+  const int d = m.d, L = P->L, row0 = slot * L, pad = L - L_clip;
   const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
-  // this slot's rows of AF, C1_l (both CFG halves) and E0: the per-clip GEMMs of fdm_audio_prepare_conds on L_clip rows
-  FCK(clip_audio_in(P, hub, row0, L_clip, stream));
-  FCK(clip_tables(P, row0, L_clip, P->rep == 2 ? (size_t)M * d : 0, stream));
-  const float *sw = nullptr, *sbias = nullptr, *ew = nullptr, *eb = nullptr;
-  FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
-  float *sty = P->sty + (size_t)slot * d, *em = P->em + (size_t)slot * d, *emu = P->emu + (size_t)slot * d;
-  FCK(fdm_op_small_linear(style, sw, sbias, sty, 1, m.n_style, d, m.style_mish ? FDM_ACT_MISH : FDM_ACT_NONE, stream));
-  if (m.n_emo) {
-    FCK(need(P, "emotion_embedd.weight", (long long)d * m.n_emo, &ew)); FCK(need(P, "emotion_embedd.bias", d, &eb));
-    FCK(fdm_op_small_linear(emo, ew, eb, em, 1, m.n_emo, d, FDM_ACT_NONE, stream));
-    if (P->cfg) FCK(fdm_op_small_linear(P->zeros, ew, eb, emu, 1, m.n_emo, d, FDM_ACT_NONE, stream));
-  }
-  for (int r = 0; r < P->rep; ++r) {
-    const float* e = m.n_emo ? (r == 1 ? emu : em) : nullptr;
-    const size_t ro = (size_t)r * M * d + o;
-    FCK(fdm_op_add_rows(P->pe, 1, L_clip, sty, L_clip, 1, e, L_clip, 1, P->E0 + ro, L_clip, d, stream));
-    if (pad) {      // rows L_clip .. L of the slot: zero addends (the denoiser is causal: they never reach the clip's own frames)
-      HIPCK(hipMemsetAsync(P->E0 + ro + nclip, 0, npad * 4, s));
-      for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l] + ro + nclip, 0, npad * 4, s));
-    }
-  }
+  FCK(slot_rows(P, slot, hub, style, emo, L_clip, stream));
   // x_T (+ zero tail) and its operand copy into the slot's rows; the history starts at zero
   HIPCK(hipMemcpyAsync(P->x + o, x_T, nclip * 4, hipMemcpyDeviceToDevice, s));
   if (pad) HIPCK(hipMemsetAsync(P->x + o + nclip, 0, npad * 4, s));
@@ -1157,6 +1211,7 @@ int fdm_slot_read(fdm_plan* P, int slot, float* out, void* stream) {
   if (!out) return fail(FDM_ERR_ARG, "slot_read: null output");
   if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_read: slot %d outside [0, %d)", slot, P->slots);
   fdm_plan::SlotHost& h = P->slot_host[slot];
+  if (h.group >= 0) return fail(FDM_ERR_STATE, "slot_read: slot %d holds a window of a long request (fdm_slot_read_long on its leader)", slot);
   if (h.status != 2) return fail(FDM_ERR_STATE, "slot_read: slot %d is %s, not finished", slot, h.status == 1 ? "running" : "idle");
   HIPCK(hipMemcpyAsync(out, P->x + (size_t)slot * P->L * P->m.d, (size_t)h.L * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   h = fdm_plan::SlotHost();
@@ -1168,6 +1223,128 @@ int fdm_slot_peek(fdm_plan* P, int slot, float* out, void* stream) {
   if (!out) return fail(FDM_ERR_ARG, "slot_peek: null output");
   if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_peek: slot %d outside [0, %d)", slot, P->slots);
   HIPCK(hipMemcpyAsync(out, P->x + (size_t)slot * P->L * P->m.d, (size_t)P->L * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return FDM_OK;
+}
+
+// ---- long requests in slot mode (include/fdm_hip.h, "Long requests in slot mode") -----------------------------------------
+int fdm_slot_admit_long(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                        int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, void* stream) {
+  if (!P || !slots || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit_long: null argument");
+  FCK(check_slots(P, "slot_admit_long"));
+  const fdm_model_desc& m = P->m;
+  const int d = m.d, L = P->L;
+  if (!P->long_frames) return fail(FDM_ERR_ARG, "slot_admit_long: the session has no long capacity (fdm_plan_set slot_long_frames / slot_long_groups before fdm_slots_open)");
+  if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "slot_admit_long: this model needs an emotion one-hot");
+  if (N < 1 || fw < 1 || m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "slot_admit_long: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
+  if (overlap < 0 || overlap >= L) return fail(FDM_ERR_ARG, "slot_admit_long: overlap %d outside [0, slot capacity %d)", overlap, L);
+  if (L_total <= L) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d fits one slot of %d frames (fdm_slot_admit)", L_total, L);
+  if (L_total > N / m.pair) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d outside (%d, %d] (N / pair)", L_total, L, N / m.pair);
+  if (L_total > P->long_frames) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d exceeds the arena of %d long frames", L_total, P->long_frames);
+  std::vector<int> starts;
+  const int nw = window_layout(L_total, L, overlap, starts);
+  if (nw < 0) return nw;
+  if (n != nw) return fail(FDM_ERR_SHAPE, "slot_admit_long: %d slots for the %d windows of L_total=%d, window %d, overlap %d", n, nw, L_total, L, overlap);
+  if (n > P->slots) return fail(FDM_ERR_SHAPE, "slot_admit_long: %d windows, the plan has %d slots", n, P->slots);
+  for (int w = 0; w < n; ++w) {
+    if (slots[w] < 0 || slots[w] >= P->slots) return fail(FDM_ERR_ARG, "slot_admit_long: slot %d outside [0, %d)", slots[w], P->slots);
+    for (int v = 0; v < w; ++v)
+      if (slots[v] == slots[w]) return fail(FDM_ERR_ARG, "slot_admit_long: slot %d is listed twice", slots[w]);
+  }
+  for (int w = 0; w < n; ++w) {
+    const int st = P->slot_host[slots[w]].status;
+    if (st != 0) return fail(FDM_ERR_STATE, "slot_admit_long: slot %d is %s", slots[w], st == 1 ? "running" : "finished and not read");
+  }
+  // a free descriptor, a contiguous arena range and a contiguous entry range, by first fit over what the live groups hold
+  int gi = -1;
+  for (int i = 0; i < P->long_groups && gi < 0; ++i)
+    if (!P->group_host[i].used) gi = i;
+  if (gi < 0) return fail(FDM_ERR_STATE, "slot_admit_long: all %d group descriptors are in use", P->long_groups);
+  auto first_fit = [&](bool arena, int need, int cap) {
+    std::vector<std::pair<int, int>> used;
+    for (const auto& g : P->group_host)
+      if (g.used) used.push_back(arena ? std::make_pair(g.first, g.L_total) : std::make_pair(g.e0, g.ne));
+    std::sort(used.begin(), used.end());
+    int at = 0;
+    for (const auto& u : used) {
+      if (u.first - at >= need) return at;
+      at = u.first + u.second;
+    }
+    return cap - at >= need ? at : -1;
+  };
+  const int ne = n * L;
+  const int a0 = first_fit(true, L_total, P->long_frames), e0 = first_fit(false, ne, P->long_entries);
+  if (a0 < 0) return fail(FDM_ERR_STATE, "slot_admit_long: no free arena range of %d frames (arena %d)", L_total, P->long_frames);
+  if (e0 < 0) return fail(FDM_ERR_STATE, "slot_admit_long: no free entry range of %d entries", ne);
+  std::vector<int> off((size_t)L_total + 1), es(ne), est(ne);
+  std::vector<float> ew(ne);
+  const int got = fdm_slot_group_table_host(L_total, L, overlap, slots, n, off.data(), es.data(), est.data(), ew.data(), ne);
+  if (got != ne) return got < 0 ? got : fail(FDM_ERR_STATE, "slot_admit_long: the group table has %d entries, expected %d", got, ne);
+  std::vector<fdm::LongFrame> frames(L_total);
+  std::vector<fdm::LongEnt> ents(ne);
+  for (int f = 0; f < L_total; ++f) frames[f] = fdm::LongFrame{gi, e0 + off[f], e0 + off[f + 1], 0};
+  for (int j = 0; j < ne; ++j) ents[j] = fdm::LongEnt{es[j], est[j], ew[j], 0};
+  const fdm::LongGroup desc{slots[0], L_total, a0, 0};
+  std::vector<int> member(n, gi);
+  // ---- nothing above touched the plan; from here on the device work, in stream order between steps
+  hipStream_t s = (hipStream_t)stream;
+  HIPCK(hipMemcpyAsync(P->long_frame + a0, frames.data(), frames.size() * sizeof(fdm::LongFrame), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(P->long_ent + e0, ents.data(), ents.size() * sizeof(fdm::LongEnt), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(P->long_group + gi, &desc, sizeof(desc), hipMemcpyHostToDevice, s));
+  for (int w = 0; w < n; ++w) HIPCK(hipMemcpyAsync(P->slot_member + slots[w], &member[w], 4, hipMemcpyHostToDevice, s));
+  HIPCK(hipStreamSynchronize(s));            // (the tables are host vectors of this call)
+  // every member's rows of AF, C1_l and E0: window w is an ordinary clip of L frames on the audio rows [s_w pair, (s_w + L) pair)
+  for (int w = 0; w < n; ++w) FCK(slot_rows(P, slots[w], hub + (size_t)starts[w] * m.pair * fw, style, emo, L, stream));
+  // x_T into the arena, the group's history to zero, then the window rows (+ operand copies) through the pass's init form
+  const size_t ao = (size_t)a0 * d, nl = (size_t)L_total * d;
+  HIPCK(hipMemcpyAsync(P->long_x + ao, x_T, nl * 4, hipMemcpyDeviceToDevice, s));
+  HIPCK(hipMemsetAsync(P->long_hist + ao, 0, nl * 4, s));
+  fdm_sched_args sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.mode = 2; sc.x_out = P->x; sc.n = (long long)P->M * d; sc.n_per_clip = (long long)L * d;
+  if (P->dtype != FDM_F32) { sc.x_out_t = P->xt.p; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo; }
+  const fdm_slot_group_args lg = long_args(P, a0, a0 + L_total, 0, 1);
+  FCK(fdm_op_slot_group_sched(&sc, P->slot_state, P->slot_keys, P->slots, &lg, stream));
+  // every member {k = -1, running} with the group's key: the next step's advance launch makes it step 0 of the group's chain
+  for (int w = 0; w < n; ++w) {
+    FCK(fdm::slot_set_op(P->slot_state, slots[w], -1, P->slot_t0, 0, 1, P->slot_keys, seed, clip_id, stream));
+    fdm_plan::SlotHost& h = P->slot_host[slots[w]];
+    h.status = 1; h.done = 0; h.L = L; h.group = gi;
+  }
+  fdm_plan::GroupHost& gh = P->group_host[gi];
+  gh.used = true; gh.L_total = L_total; gh.first = a0; gh.e0 = e0; gh.ne = ne; gh.slots.assign(slots, slots + n);
+  return FDM_OK;
+}
+
+int fdm_slot_group(fdm_plan* P, int slot, int* leader, int* n, int* L_total) {
+  FCK(check_slots(P, "slot_group"));
+  if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_group: slot %d outside [0, %d)", slot, P->slots);
+  const int gi = P->slot_host[slot].group;
+  const fdm_plan::GroupHost* g = gi >= 0 ? &P->group_host[gi] : nullptr;
+  if (leader) *leader = g ? g->slots[0] : -1;
+  if (n) *n = g ? (int)g->slots.size() : 0;
+  if (L_total) *L_total = g ? g->L_total : 0;
+  return FDM_OK;
+}
+
+int fdm_slot_read_long(fdm_plan* P, int leader, float* out, void* stream) {
+  FCK(check_slots(P, "slot_read_long"));
+  if (!out) return fail(FDM_ERR_ARG, "slot_read_long: null output");
+  if (leader < 0 || leader >= P->slots) return fail(FDM_ERR_ARG, "slot_read_long: slot %d outside [0, %d)", leader, P->slots);
+  const int gi = P->slot_host[leader].group;
+  if (gi < 0 || P->group_host[gi].slots[0] != leader) return fail(FDM_ERR_STATE, "slot_read_long: slot %d does not lead a long request", leader);
+  fdm_plan::GroupHost& g = P->group_host[gi];
+  for (int sl : g.slots)
+    if (P->slot_host[sl].status != 2) return fail(FDM_ERR_STATE, "slot_read_long: the group of slot %d is running, not finished", leader);
+  hipStream_t s = (hipStream_t)stream;
+  const int d = P->m.d;
+  HIPCK(hipMemcpyAsync(out, P->long_x + (size_t)g.first * d, (size_t)g.L_total * d * 4, hipMemcpyDeviceToDevice, s));
+  // the arena frames go back to free and the members to plain, so that a later clip in the leader's slot never wakes this group
+  HIPCK(hipMemsetAsync(P->long_frame + g.first, 0xff, (size_t)g.L_total * sizeof(fdm::LongFrame), s));
+  for (int sl : g.slots) {
+    HIPCK(hipMemsetAsync(P->slot_member + sl, 0xff, 4, s));
+    P->slot_host[sl] = fdm_plan::SlotHost();
+  }
+  g = fdm_plan::GroupHost();
   return FDM_OK;
 }
 
@@ -1190,6 +1367,8 @@ int fdm_plan_get(fdm_plan* P, const char* key, long long* out) {
   else if (k == "tune_failed") *out = P->tune_failed;
   else if (k == "windows") *out = P->win_n;
   else if (k == "slots") *out = P->slots;
+  else if (k == "slot_long_frames") *out = P->want_long_frames;
+  else if (k == "slot_long_groups") *out = P->want_long_groups;
   else if (k == "window_len") *out = P->win_n ? P->win_len : P->L;
   else if (k == "L_total") *out = P->win_n ? P->win_total : P->L;
   else if (k.rfind("tile.", 0) == 0) { auto it = P->tiles.find(k.substr(5)); *out = it == P->tiles.end() ? 0 : it->second; }
@@ -1202,6 +1381,11 @@ int fdm_plan_set(fdm_plan* P, const char* key, long long value) {
   const std::string k(key);
   if (k == "tune") { P->tune_enabled = value != 0; return FDM_OK; }
   if (k == "tune_lazy") { P->tune_lazy = value != 0; return FDM_OK; }
+  if (k == "slot_long_frames" || k == "slot_long_groups") {      // long capacity of the NEXT fdm_slots_open (both > 0 to have any)
+    if (value < 0 || value > 0x3fffffffLL) return fail(FDM_ERR_ARG, "plan_set: %s = %lld", key, value);
+    (k == "slot_long_frames" ? P->want_long_frames : P->want_long_groups) = (int)value;
+    return FDM_OK;
+  }
   if (k == "fuse_ln3") {      // takes effect at the next commit (the folded weights are commit-time tables)
     if ((value != 0) != (P->want_fuse_ln3 != 0)) { P->want_fuse_ln3 = value != 0; P->committed = false; P->prepared = false; return drop_programs(P, nullptr); }
     return FDM_OK;

@@ -78,12 +78,26 @@ struct fdm_plan {
   int slots = 0;
   int* slot_state = nullptr; size_t slot_state_cap = 0;
   unsigned long long* slot_keys = nullptr; size_t slot_keys_cap = 0;
-  struct SlotHost { int status = 0, done = 0, L = 0; };     // status: 0 idle, 1 running, 2 finished (not read yet)
+  struct SlotHost { int status = 0, done = 0, L = 0, group = -1; };     // status: 0 idle, 1 running, 2 finished (not read yet); group: its long request, -1 = a plain clip
   std::vector<SlotHost> slot_host;
   int slot_kind = 0, slot_nsteps = 0, slot_t0 = 0;          // program kind (1 DDPM, 2 DDIM, 3 table-driven), steps per chain, tseq[0]
   int slot_graph_steps = 0, slot_eager = 0;
   float slot_cfg_scale = 0.f;
   const float *slot_san = nullptr, *slot_cn = nullptr;      // DDIM per-step tables of the session
+  // ---- long requests in slot mode (fdm_slot_admit_long): a recording longer than a slot occupies a GROUP of slots, one window each,
+  // and a range of the long ARENA (its latent and blended-x0 history in long layout).  Capacity is asked for before fdm_slots_open
+  // (fdm_plan_set "slot_long_frames" / "slot_long_groups") and reserved there; long_frames == 0 = a session without long capacity,
+  // whose program is the plain slot program.  Device tables as fdm_slot_group_args describes them; the host mirrors every group.
+  int want_long_frames = 0, want_long_groups = 0;
+  int long_frames = 0, long_groups = 0, long_entries = 0;
+  float* long_x = nullptr; size_t long_x_cap = 0;
+  float* long_hist = nullptr; size_t long_hist_cap = 0;
+  fdm::LongFrame* long_frame = nullptr; size_t long_frame_cap = 0;
+  fdm::LongEnt* long_ent = nullptr; size_t long_ent_cap = 0;
+  fdm::LongGroup* long_group = nullptr; size_t long_group_cap = 0;
+  int* slot_member = nullptr; size_t slot_member_cap = 0;
+  struct GroupHost { bool used = false; int L_total = 0, first = 0, e0 = 0, ne = 0; std::vector<int> slots; };      // slots[0] = the leader
+  std::vector<GroupHost> group_host;
 };
 
 namespace fdm {

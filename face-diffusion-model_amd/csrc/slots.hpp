@@ -2,10 +2,14 @@
 // steps inside one step program.  Per-slot device state, advanced once per diffusion step before anything reads it, and the
 // scheduler pass that updates every live slot with its own (k, t, seed, clip id) -- sched_update4 / sched_noise4 of sched.hpp, so a
 // slot's bits are those of sched_kernel on the clip alone.  Vector loads and stores only; state words are written in plain C++.
+// Long requests (fdm_slot_admit_long): a recording longer than a slot occupies a GROUP of slots, one window each; with long capacity
+// the scheduler pass is slot_group_sched_kernel, which does the plain slots' update and, over the long arena, window_sched_kernel's
+// blend + update per group at the group's own (k, t).
 #pragma once
 #include "common.hpp"
 #include "sched.hpp"
 #include "../../include/fdm_hip.h"
+#include "kernels.hpp"
 
 namespace fdm {
 
@@ -35,6 +39,42 @@ __global__ void slot_set_kernel(SlotState* st, SlotState v, unsigned long long* 
   if (threadIdx.x == 0) { *st = v; key[0] = seed; key[1] = clip_id; }
 }
 
+// The per-step scalars of a slot at ITS (k, t), noise keyed (seed, clip0 + clip of the element)
+__device__ __forceinline__ SchedCoef slot_coef(const fdm_sched_args& p, const SlotState& s, unsigned long long seed, int clip0) {
+  SchedCoef c;
+  c.k = s.k; c.t = s.t;
+  c.c1 = c.c2 = c.sg = c.sra = c.san = c.cn = 0.f;
+  c.srm1 = 1.f;
+  c.seed = seed;
+  c.clip0 = clip0;
+  if (p.mode == 3) { c.c1 = p.lm_b[c.k]; c.c2 = p.lm_a[c.k]; c.sg = p.lm_s[c.k]; c.cn = p.lm_c[c.k]; }
+  else if (p.mode == 0) { c.c1 = p.c1[c.t]; c.c2 = p.c2[c.t]; c.sg = p.sigma[c.t]; }
+  else { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = p.sqrt_an[c.k]; c.cn = p.c_n[c.k]; }
+  return c;
+}
+// the operand-kind copy of four updated elements at flat element q of x_out_t
+__device__ __forceinline__ void slot_store_t(const fdm_sched_args& p, long long q, f32x4 o) {
+  if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + q, 0, o);
+  else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + q, p.x_out_t_lo_off, o);
+  else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + q, 0, o);
+  else *(f32x4*)((float*)p.x_out_t + q) = o;
+}
+// One plain slot's four elements starting at flat element e (the slot is live): CFG mix, update at the slot's (k, t), stores.
+__device__ __forceinline__ void slot_update_quad(const fdm_sched_args& p, const SlotState& s, const unsigned long long* keys, int clip, long long e) {
+  // sched_noise4 keys by clip0 + (e / n_per_clip) = the slot's clip id
+  const SchedCoef c = slot_coef(p, s, keys[2 * clip], (int)keys[2 * clip + 1] - clip);
+  f32x4 x0 = *(const f32x4*)(p.x0 + e);
+  if (p.x0u) {
+    const f32x4 u = *(const f32x4*)(p.x0u + e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x0[j] = __fadd_rn(u[j], __fmul_rn(p.cfg_scale, __fsub_rn(x0[j], u[j])));
+  }
+  const f32x4 x = *(const f32x4*)(p.x + e);
+  const f32x4 o = p.mode == 3 ? sched_update4<true>(p, c, x0, x, e) : sched_update4<false>(p, c, x0, x, e);
+  *(f32x4*)(p.x_out + e) = o;
+  if (p.x_out_t) slot_store_t(p, e, o);
+}
+
 // The scheduler pass of the slot program.  p: x0 (+ x0u, cfg_scale), x, x_out, x_out_t, n = n_slots * n_per_clip, mode 0 / 1 / 3 with
 // its tables and x0_hist; p.step / tseq / seed / clip0 / seed_dev / arrive / noise are not read.  A slot that is not live is
 // skipped whole: nothing of it is stored.
@@ -45,29 +85,84 @@ __global__ __launch_bounds__(256) void slot_sched_kernel(const fdm_sched_args p,
     const int clip = (int)(e / p.n_per_clip);
     const SlotState s = st[clip];
     if (!s.live) continue;
-    SchedCoef c;
-    c.k = s.k; c.t = s.t;
-    c.c1 = c.c2 = c.sg = c.sra = c.san = c.cn = 0.f;
-    c.srm1 = 1.f;
-    c.seed = keys[2 * clip];
-    c.clip0 = (int)keys[2 * clip + 1] - clip;      // sched_noise4 keys by clip0 + (e / n_per_clip) = the slot's clip id
-    if (p.mode == 3) { c.c1 = p.lm_b[c.k]; c.c2 = p.lm_a[c.k]; c.sg = p.lm_s[c.k]; c.cn = p.lm_c[c.k]; }
-    else if (p.mode == 0) { c.c1 = p.c1[c.t]; c.c2 = p.c2[c.t]; c.sg = p.sigma[c.t]; }
-    else { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = p.sqrt_an[c.k]; c.cn = p.c_n[c.k]; }
-    f32x4 x0 = *(const f32x4*)(p.x0 + e);
-    if (p.x0u) {
-      const f32x4 u = *(const f32x4*)(p.x0u + e);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x0[j] = __fadd_rn(u[j], __fmul_rn(p.cfg_scale, __fsub_rn(x0[j], u[j])));
+    slot_update_quad(p, s, keys, clip, e);
+  }
+}
+
+// The scheduler pass of a slot plan with long capacity (fdm_slot_admit_long): ONE launch over the plain slots and the long arena.
+//   plain slots   quads [0, p.n / 4) when g.plain: slot_sched_kernel's update, except that a slot that belongs to a group
+//                 (g.member[slot] >= 0) is skipped -- its rows are written from the arena below
+//   long arena    one quad per four elements of the arena frames [g.frame0, g.frame1).  A frame's group gives the leader slot,
+//                 whose state word supplies (k, t, live) and whose key words supply (seed, clip id); the covering windows' x0 (CFG
+//                 mix per window first) are blended in ascending window order, the first term starting the sum, as
+//                 window_sched_kernel does; the update runs once per long-clip element with the element's index INSIDE ITS OWN long
+//                 clip as noise counter and history index (groups have different L_total: sched_update4 gets a per-group view of p);
+//                 the result goes to the arena and to every window row holding the frame (p.x_out + operand copy).
+//                 g.init: no update -- the arena (x_T) is copied into the window rows, whatever the leader's word says.
+// Every table row is checked against the sizes in g before it is used as an index; a row outside them stores nothing.
+__global__ __launch_bounds__(256) void slot_group_sched_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys,
+                                                               const fdm_slot_group_args g, int n_slots) {
+  const long long nq_plain = g.plain ? p.n / 4 : 0;
+  const long long nq = nq_plain + (long long)(g.frame1 - g.frame0) * g.d / 4;
+  const LongFrame* frames = (const LongFrame*)g.frames;
+  const LongEnt* ents = (const LongEnt*)g.entries;
+  const LongGroup* groups = (const LongGroup*)g.groups;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
+    if (i < nq_plain) {
+      const long long e = 4 * i;
+      const int clip = (int)(e / p.n_per_clip);
+      const SlotState s = st[clip];
+      if (!s.live || g.member[clip] >= 0) continue;
+      slot_update_quad(p, s, keys, clip, e);
+      continue;
     }
-    const f32x4 x = *(const f32x4*)(p.x + e);
-    const f32x4 o = p.mode == 3 ? sched_update4<true>(p, c, x0, x, e) : sched_update4<false>(p, c, x0, x, e);
-    *(f32x4*)(p.x_out + e) = o;
-    if (p.x_out_t) {
-      if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + e, 0, o);
-      else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + e, p.x_out_t_lo_off, o);
-      else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + e, 0, o);
-      else *(f32x4*)((float*)p.x_out_t + e) = o;
+    const long long ea = (long long)g.frame0 * g.d + 4 * (i - nq_plain);      // element of the arena
+    const int f = (int)(ea / g.d), col = (int)(ea - (long long)f * g.d);
+    const LongFrame fr = frames[f];
+    if (fr.group < 0 || fr.group >= g.n_groups || fr.e0 < 0 || fr.e1 > g.n_entries) continue;
+    const LongGroup gr = groups[fr.group];
+    const int fl = f - gr.first;                                              // frame inside the long clip
+    if (gr.leader < 0 || gr.leader >= n_slots || fl < 0 || fl >= gr.L_total) continue;
+    const SlotState s = st[gr.leader];
+    if (!g.init && !s.live) continue;
+    f32x4 o;
+    if (g.init) {
+      o = *(const f32x4*)(g.x_long + ea);
+    } else {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = fr.e0; j < fr.e1; ++j) {
+        const LongEnt en = ents[j];
+        const int r = fl - en.start;
+        if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
+        const long long q = ((long long)en.slot * g.L + r) * g.d + col;
+        f32x4 x0 = *(const f32x4*)(p.x0 + q);
+        if (p.x0u) {      // CFG mix per window, before the blend (window_sched_kernel's expression)
+          const f32x4 u = *(const f32x4*)(p.x0u + q);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) x0[k] = __fadd_rn(u[k], __fmul_rn(p.cfg_scale, __fsub_rn(x0[k], u[k])));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = j == fr.e0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
+      }
+      // the group's view of the arguments: one clip of L_total frames whose history starts at its first arena frame; the element
+      // index inside the long clip keys the noise (clip0 = the group's clip id) and indexes the history
+      fdm_sched_args pl = p;
+      pl.n_per_clip = (long long)gr.L_total * g.d;
+      pl.x0_hist = g.hist_long ? g.hist_long + (long long)gr.first * g.d : nullptr;
+      pl.noise = nullptr;
+      const SchedCoef c = slot_coef(p, s, keys[2 * gr.leader], (int)keys[2 * gr.leader + 1]);
+      const long long el = (long long)fl * g.d + col;
+      const f32x4 x = *(const f32x4*)(g.x_long + ea);
+      o = p.mode == 3 ? sched_update4<true>(pl, c, acc, x, el) : sched_update4<false>(pl, c, acc, x, el);
+      *(f32x4*)(g.x_long + ea) = o;
+    }
+    for (int j = fr.e0; j < fr.e1; ++j) {
+      const LongEnt en = ents[j];
+      const int r = fl - en.start;
+      if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
+      const long long q = ((long long)en.slot * g.L + r) * g.d + col;
+      *(f32x4*)(p.x_out + q) = o;
+      if (p.x_out_t) slot_store_t(p, q, o);
     }
   }
 }
@@ -78,6 +173,16 @@ static hipError_t slot_sched_launch(const fdm_sched_args& a, const int* state, c
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(slot_sched_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys);
+  return hipGetLastError();
+}
+
+static hipError_t slot_group_sched_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, const fdm_slot_group_args& g,
+                                          int n_slots, hipStream_t s) {
+  const long long nq = (g.plain ? a.n / 4 : 0) + (long long)(g.frame1 - g.frame0) * g.d / 4;
+  int blocks = (int)((nq + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(slot_group_sched_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys, g, n_slots);
   return hipGetLastError();
 }
 

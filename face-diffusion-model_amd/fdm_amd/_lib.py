@@ -79,9 +79,15 @@ class LnArgs(C.Structure):
                 ("clip_step", vp), ("clip_step_stride", ci), ("clip_rows", ci), ("clip_wrap", ci)]
 
 
+class SlotGroupArgs(C.Structure):
+    _fields_ = [("member", vp), ("frames", vp), ("entries", vp), ("groups", vp), ("x_long", vp), ("hist_long", vp),
+                ("arena_frames", ci), ("n_entries", ci), ("n_groups", ci), ("L", ci), ("d", ci), ("frame0", ci), ("frame1", ci),
+                ("plain", ci), ("init", ci)]
+
+
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
-           "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc}
+           "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -96,6 +102,7 @@ SYMBOLS = {
     "fdm_op_layernorm": (ci, [C.POINTER(LnArgs), vp]),
     "fdm_op_sched_step": (ci, [C.POINTER(SchedArgs), vp]),
     "fdm_op_slot_sched": (ci, [C.POINTER(SchedArgs), vp, vp, ci, vp]),
+    "fdm_op_slot_group_sched": (ci, [C.POINTER(SchedArgs), vp, vp, ci, C.POINTER(SlotGroupArgs), vp]),
     "fdm_op_cast": (ci, [vp, vp, ll, ci, vp]),
     "fdm_op_vertex_err": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
     "fdm_op_motion_std": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
@@ -148,6 +155,10 @@ SYMBOLS = {
     "fdm_slot_state": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
     "fdm_slot_read": (ci, [vp, ci, vp, vp]),
     "fdm_slot_peek": (ci, [vp, ci, vp, vp]),
+    "fdm_slot_admit_long": (ci, [vp, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, C.c_ulonglong, ci, vp]),
+    "fdm_slot_group": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+    "fdm_slot_read_long": (ci, [vp, ci, vp, vp]),
+    "fdm_slot_group_table_host": (ci, [ci, ci, ci, vp, ci, vp, vp, vp, vp, ci]),
     "fdm_plan_tune": (ci, [vp, vp]),
     "fdm_plan_get": (ci, [vp, C.c_char_p, C.POINTER(ll)]),
     "fdm_plan_set": (ci, [vp, C.c_char_p, ll]),
@@ -210,4 +221,6 @@ def lib():
 
 def check(code):
     if code != 0:
-        raise FdmError(f"libfdm_hip error {code}: {lib().fdm_last_error().decode()}")
+        err = FdmError(f"libfdm_hip error {code}: {lib().fdm_last_error().decode()}")
+        err.code = code              # FDM_ERR_*: a caller that waits on FDM_ERR_STATE (SlotServer) reads it here
+        raise err

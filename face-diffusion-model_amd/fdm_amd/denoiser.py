@@ -315,11 +315,13 @@ class DenoiserPlan:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def open_slots(self, slots, L, kind="ddim", steps=None, t_list=None, tables=None, cfg=False, cfg_scale=2.5, use_graph=True, graph_steps=0):
+    def open_slots(self, slots, L, kind="ddim", steps=None, t_list=None, tables=None, cfg=False, cfg_scale=2.5, use_graph=True, graph_steps=0,
+                   long_frames=0, long_groups=0):
         """In-flight batching (fdm_slots_open): `slots` slots of up to L latent frames, each a clip at its own step of ONE shared
         sampler -- kind "ddim" with `steps`, "ddpm" over t_list, or "tables" over t_list with `tables` [4, len(t_list)]
         (sample_tables).  Every slot starts idle; admit() / run() / slot_state() / read_slot() drive them.  Returns the number of
-        steps of a chain."""
+        steps of a chain.  long_frames / long_groups > 0 reserve capacity for long requests (admit_long): an arena of long_frames
+        latent frames and long_groups group descriptors; 0 = the plain slot program."""
         a = SampleArgs()
         a.cfg_scale, a.eager, a.graph_steps = float(cfg_scale), int(not use_graph), int(graph_steps)
         held = None
@@ -332,6 +334,8 @@ class DenoiserPlan:
             held = self._tables_args(a, t_list, tables)
         else:
             raise FdmError(f"kind {kind!r} (ddpm | ddim | tables)")
+        self.set("slot_long_frames", int(long_frames))
+        self.set("slot_long_groups", int(long_groups))
         with torch.cuda.device(self.device):
             check(lib().fdm_slots_open(self.h, int(slots), int(L), int(bool(cfg)), C.byref(a), _stream()))
         del held
@@ -357,6 +361,42 @@ class DenoiserPlan:
                                        L, x.data_ptr(), int(seed), int(clip_id), _stream()))
         self._slot_inputs[int(slot)] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the slot is admitted again
         return L
+
+    def admit_long(self, slots, hub, style, emo=None, x_T=None, L_total=None, overlap=60, seed=0, clip_id=0):
+        """fdm_slot_admit_long: a recording of L_total > L latent frames into the idle slots `slots`, one window each (slots[0] leads
+        the group); len(slots) must be the window count of window_starts(L_total, L, overlap).  hub [N, fw] (or [1, N, fw]) features
+        of the whole recording, x_T [L_total*G, c] (or [1, ...]).  Its latent will equal sample_windows on a B = 1 windowed plan
+        (window = L, the same overlap, x_T, seed, clip0 = clip_id).  Drains the stream once.  Returns L_total."""
+        p, dv = self.p, self.device
+        hub = _dev(hub, dv).reshape(-1, hub.shape[-1])
+        N, fw = hub.shape
+        L_total = N // p.pair if L_total is None else int(L_total)
+        style = _dev(style, dv).reshape(-1)
+        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
+        x = _dev(x_T, dv).reshape(-1)
+        if x.numel() != L_total * p.d:
+            raise FdmError(f"x_T has {x.numel()} elements, expected L_total*G*c = {L_total * p.d}")
+        ids = (C.c_int * len(slots))(*[int(s) for s in slots])
+        with torch.cuda.device(dv):
+            check(lib().fdm_slot_admit_long(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, style.data_ptr(),
+                                            emo.data_ptr() if emo is not None else None, L_total, int(overlap), x.data_ptr(),
+                                            int(seed), int(clip_id), _stream()))
+        self._slot_inputs[int(slots[0])] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the leader's slot is admitted again
+        return L_total
+
+    def slot_group(self, slot):
+        """fdm_slot_group: (leader, members, L_total) of the long request a slot belongs to; (-1, 0, 0) for a plain or idle slot."""
+        a, n, lt = C.c_int(), C.c_int(), C.c_int()
+        check(lib().fdm_slot_group(self.h, int(slot), C.byref(a), C.byref(n), C.byref(lt)))
+        return a.value, n.value, lt.value
+
+    def read_long(self, leader):
+        """fdm_slot_read_long: the finished group's latent [1, L_total*G, c]; its slots, arena range and descriptor are free afterwards."""
+        L_total = self.slot_group(leader)[2]
+        out = torch.empty(1, max(L_total, 1) * self.p.G, self.p.c, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().fdm_slot_read_long(self.h, int(leader), out.data_ptr(), _stream()))
+        return out
 
     def run(self, n_steps):
         """fdm_slots_run: n_steps diffusion steps for every running slot (a chain that ends part-way freezes there)."""

@@ -196,6 +196,19 @@ def slot_sched(mode, x0, x, x_out, n, state, keys, n_slots, **kw):
     check(lib().fdm_op_slot_sched(C.byref(a), _p(state), _p(keys), n_slots, stream()))
 
 
+def slot_group_sched(mode, x0, x, x_out, n, state, keys, n_slots, *, member, frames, entries, groups, x_long, hist_long=None, L, d,
+                     frame0=0, frame1=None, plain=1, init=0, **kw):
+    """fdm_op_slot_group_sched: slot_sched over the plain slots plus the group update over the long arena in one launch.  Device
+    tables: member int32 [n_slots], frames int32 [arena_frames, 4], entries [n_entries, 4] 32-bit words {slot, start, weight
+    bits, 0}, groups int32 [n_groups, 4]; x_long / hist_long fp32 [arena_frames * d]."""
+    a = sched_args(mode, x0, x, x_out, n, **kw)
+    g = _lib.SlotGroupArgs()
+    g.member, g.frames, g.entries, g.groups, g.x_long, g.hist_long = _p(member), _p(frames), _p(entries), _p(groups), _p(x_long), _p(hist_long)
+    g.arena_frames, g.n_entries, g.n_groups, g.L, g.d = frames.shape[0], entries.shape[0], groups.shape[0], L, d
+    g.frame0, g.frame1, g.plain, g.init = frame0, frames.shape[0] if frame1 is None else frame1, plain, init
+    check(lib().fdm_op_slot_group_sched(C.byref(a), _p(state), _p(keys), n_slots, C.byref(g), stream()))
+
+
 def cast(src, dst):
     check(lib().fdm_op_cast(_p(src), _p(dst), src.numel(), code_of(dst), stream()))
 

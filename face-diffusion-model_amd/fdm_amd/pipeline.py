@@ -297,10 +297,17 @@ class SlotServer:
     ClassifierFreeSampleModel.  max_frames: latent frames a slot holds (default the model's max_len); a longer clip is refused.
     The server owns the model's plan while it runs: an animate*() call on the same model returns the plan to plain mode and the
     next submit() / step() raises.  batch_stages: the clips that finish in one step() call are quantised in one padded call and
-    decoded in one call over their unequal lengths (VQAutoEncoder.decode_many) -- the same results, bit for bit."""
+    decoded in one call over their unequal lengths (VQAutoEncoder.decode_many) -- the same results, bit for bit.
+
+    Long recordings (submit_long): long_frames > 0 reserves an arena of that many latent frames and long_groups group descriptors
+    (DenoiserPlan.open_slots); a recording longer than a slot then rides the same step program as a GROUP of slots, one window of
+    max_frames frames per slot overlapping by >= `overlap`, blended every step as animate_long blends them.  Its result equals
+    animate_long(..., window=max_frames, overlap=overlap) with the server's sampler and the same seed (torch.equal).  The queue is
+    strictly first in, first out: a long request that does not fit yet waits at the head and nothing behind it is admitted, so it
+    cannot starve.  long_frames = 0 (default): the plain slot program, and submit_long refuses what needs a group."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
-                 device="cuda:0", batch_stages=False):
+                 device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60):
         from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
@@ -313,6 +320,11 @@ class SlotServer:
         self.plan = self.model.plan(device)
         self.model._prep_key = None           # the plan leaves the state FDM.prepare() cached
         kw = dict(cfg=self.cfg, cfg_scale=float(diffusion.denoise_fn.level) if self.cfg else 2.5)
+        self.long_frames, self.overlap = int(long_frames), int(overlap)
+        if self.long_frames:
+            if not 0 <= self.overlap < self.L:
+                raise ValueError(f"overlap {self.overlap} outside [0, max_frames {self.L})")
+            kw.update(long_frames=self.long_frames, long_groups=int(long_groups))
         if sampler:
             t_list, tables = schedule.sampler_tables(sampler, sampler_steps, eta, diffusion.num_timesteps)
             self.chain = self.plan.open_slots(self.n_slots, self.L, "tables", t_list=t_list, tables=tables, **kw)
@@ -382,12 +394,66 @@ class SlotServer:
         return handles
 
     def _fill(self):
-        for s in range(self.n_slots):
-            if self._slot[s] is None and self._queue:
-                r = self._queue.pop(0)
-                self.plan.admit(s, r["hub"], r["ids"], r["emo"], r["x_T"], L=r["L"], seed=r["seed"], clip_id=0)
-                r.pop("hub"), r.pop("x_T")
+        """Admit from the head of the queue while the head fits: a plain request needs one idle slot (the lowest), a long one needs
+        its window count in idle slots, an arena range and a descriptor (FDM_ERR_STATE from admit_long = not yet).  Nothing passes a
+        request that waits."""
+        from ._lib import FdmError
+        while self._queue:
+            r = self._queue[0]
+            free = [s for s in range(self.n_slots) if self._slot[s] is None]
+            if r.get("windows"):
+                if len(free) < r["windows"]:
+                    return
+                try:
+                    self.plan.admit_long(free[:r["windows"]], r["hub"], r["ids"], r["emo"], r["x_T"], L_total=r["L"], overlap=self.overlap,
+                                         seed=r["seed"], clip_id=0)
+                except FdmError as e:
+                    if getattr(e, "code", None) == -4:       # arena or descriptors busy: the plan is untouched, wait for a group to leave
+                        return
+                    raise
+                r["slots"] = free[:r["windows"]]
+            else:
+                if not free:
+                    return
+                self.plan.admit(free[0], r["hub"], r["ids"], r["emo"], r["x_T"], L=r["L"], seed=r["seed"], clip_id=0)
+                r["slots"] = free[:1]
+            self._queue.pop(0)
+            r.pop("hub"), r.pop("x_T")
+            for s in r["slots"]:
                 self._slot[s] = r
+
+    @torch.no_grad()
+    def submit_long(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0):
+        """One processor-normalised waveform [n] of ANY length -> a handle.  The audio encoder runs over the whole waveform and
+        L_total = frames // pair is kept whole (submit() crops to a slot).  L_total <= max_frames is an ordinary request; a longer
+        one becomes a group of slots (class docstring) with x_T drawn as animate_long draws it.  ValueError if the request can
+        never fit: more windows than slots, or L_total > long_frames."""
+        from .denoiser import window_starts
+        self._check()
+        p, dev = self.p, self.device
+        wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
+        hub = self.model.audio_encoder(wav).last_hidden_state
+        L = hub.shape[1] // p.pair
+        if L < 1:
+            raise ValueError(f"clip of {L} latent frames")
+        windows = 0
+        if L > self.L:
+            if L > self.long_frames:
+                raise ValueError(f"recording of {L} latent frames, the server's long arena holds {self.long_frames} (long_frames=)")
+            windows = len(window_starts(L, self.L, self.overlap))
+            if windows > self.n_slots:
+                raise ValueError(f"recording of {L} latent frames needs {windows} windows of {self.L}, the server has {self.n_slots} slots")
+        ids = torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32).reshape(-1, p.n_style)[:1]
+        emo = None
+        if p.n_emo:
+            emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
+            emo = emo.to(dev)
+        x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
+        h = self._next
+        self._next += 1
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, windows=windows))
+        self._fill()
+        return h
 
     @torch.no_grad()
     def step(self, n=10):
@@ -398,10 +464,10 @@ class SlotServer:
         self._fill()
         self.plan.run(n)
         if self.batch_stages:
-            fin = self._finish_batched()
+            fin = self._finish_long() + self._finish_batched()
             self._fill()
             return fin
-        fin = 0
+        fin = self._finish_long()
         for s in range(self.n_slots):
             r = self._slot[s]
             if r is None or self.plan.slot_state(s)[2] != SLOT_FINISHED:
@@ -415,6 +481,26 @@ class SlotServer:
             self._slot[s] = None
             fin += 1
         self._fill()
+        return fin
+
+    def _finish_long(self):
+        """The groups whose chains ended: read the long latent, quantise and decode the whole L_total (the decoder is not causal), as
+        animate_long does; every member slot goes back to the queue.  A long result has its own decode call, batch_stages or not."""
+        from ._lib import SLOT_FINISHED
+        fin = 0
+        for s in range(self.n_slots):
+            r = self._slot[s]
+            if r is None or not r.get("windows") or r["slots"][0] != s or self.plan.slot_state(s)[2] != SLOT_FINISHED:
+                continue
+            lat = self.plan.read_long(s)
+            q = self.ae.quant(lat, r["emo"], stats=False)[0] if self.p.n_emo else self.ae.quant(lat, stats=False)[0]
+            out = self.ae.decode(q)
+            if r["template"] is not None:
+                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
+            self._done.append((r["handle"], out, lat))
+            for m in r["slots"]:
+                self._slot[m] = None
+            fin += 1
         return fin
 
     def _finish_batched(self):
@@ -443,7 +529,7 @@ class SlotServer:
     @property
     def pending(self):
         """Requests queued or in a slot."""
-        return len(self._queue) + sum(r is not None for r in self._slot)
+        return len(self._queue) + len({r["handle"] for r in self._slot if r is not None})
 
     def results(self):
         """[(handle, vertices [1, L, V3], latent [1, L*G, c])] of the clips finished since the last call."""

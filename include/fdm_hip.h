@@ -115,6 +115,33 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream);
  * seed = the slot's seed and clip0 = the slot's clip id (Philox keyed (seed, clip id, element inside the clip, k)).  n must be
  * n_slots * n_per_clip; a->step / tseq / advance / arrive / seed / clip0 / seed_dev are not read; a->noise must be NULL. */
 int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, void* stream);
+/* The scheduler pass of a slot plan with long capacity (fdm_slot_admit_long): fdm_op_slot_sched over the plain slots and the group update
+ * over the long arena, in ONE launch.  a / state / keys / n_slots as for fdm_op_slot_sched (a->x / x_out / x_out_t / x0 / x0u are the slot
+ * rows, [n_slots, L * d]; a->x0_hist the plain slots' history); g points at device tables:
+ *   member   [n_slots] ints: the group a slot belongs to, -1 = a plain slot.  A member slot is skipped by the plain part.
+ *   frames   [arena_frames] rows {int group, int e0, int e1, int 0}: the group of an arena frame (-1 = free: skipped) and its covering
+ *            entries [e0, e1), in ascending window order
+ *   entries  [n_entries] rows {int slot, int window start, float weight, int 0} (fdm_slot_group_table_host)
+ *   groups   [n_groups] rows {int leader slot, int L_total, int first arena frame, int 0}
+ *   x_long / hist_long   the arena, fp32 [arena_frames * d]: the long clips' latents and (mode 3) their blended-x0 histories
+ * Arena frames [frame0, frame1) are visited.  A frame of a group whose LEADER's word is live gets: the CFG mix per covering window, the
+ * blend x0 = sum_w weight_w x0_w in ascending window order (the first term starts the sum), ONE update with fdm_op_sched_step's
+ * expressions at the leader's (k, t), noise Philox (leader's seed, leader's clip id, element index inside the long clip, k), history
+ * (mode 3) = the blended x0 at hist_long + first * d + element; the result is stored to x_long and to every window row holding the
+ * frame (a->x_out, plus a->x_out_t).  These are the bits of window_sched_kernel (fdm_sample_windows) on that clip alone, B = 1.  A group
+ * whose leader is not live is skipped whole.  init != 0: no update and no look at the state -- x_long is copied into the window rows
+ * (+ operand copy): how fdm_slot_admit_long loads x_T.  plain == 0: the plain slots are not visited.  Every table row is checked against
+ * n_slots / n_groups / n_entries / L / L_total before it is used as an index (a bad row stores nothing).  d % 4 == 0. */
+typedef struct fdm_slot_group_args {
+  const int* member; const int* frames; const void* entries; const int* groups;
+  float* x_long; float* hist_long;
+  int arena_frames, n_entries, n_groups;
+  int L, d;                        /* frames per slot, elements per frame (n_per_clip == L * d) */
+  int frame0, frame1;
+  int plain, init;
+} fdm_slot_group_args;
+int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                            const fdm_slot_group_args* g, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * C[M,N] = epilogue(A[M,K] * W[N,K]^T): every nn.Linear / Conv1d-as-GEMM on the path
@@ -559,6 +586,52 @@ int fdm_slot_state(fdm_plan* p, int slot, int* steps_done, int* steps_total, int
 int fdm_slot_read(fdm_plan* p, int slot, float* out, void* stream);
 /* inspection: all L rows of a slot's latent, [L*G, c], whatever its status (an idle slot never admitted holds zeros); changes nothing */
 int fdm_slot_peek(fdm_plan* p, int slot, float* out, void* stream);
+/* Long requests in slot mode: a recording of L_total > L latent frames (L = the slot capacity) rides the slot program as a GROUP.
+ *   rule     the request is n = fdm_window_layout_host(L_total, L, O) windows of exactly L frames, admitted into n idle slots at once:
+ *            any slots, in any order, window w into slots[w]; slots[0] is the group's LEADER.  Every member carries the same state word
+ *            and advances with the advance launch like any slot.  The denoiser chain treats a member as an ordinary slot holding its
+ *            window's audio rows [s_w pair, (s_w + L) pair), the clip's style / emotion and window-local positions.  The scheduler pass
+ *            (fdm_op_slot_group_sched) treats the group as fdm_sample_windows treats a windowed plan: CFG mix per window; the covering
+ *            windows' x0 blended in ascending window order with fdm_window_weights_host's weights, the first term starting the sum; one
+ *            update per long-clip element with fdm_op_sched_step's expressions at the leader's (k, t); noise Philox (seed, clip_id,
+ *            element index inside the long clip, k); the table-driven sampler's history is the blended x0 in long layout; the result
+ *            goes to the long buffer and to every window row holding the frame (fp32 + operand copy).  A group that is not live is
+ *            skipped whole.
+ *   exact    the group's latent is bit for bit what fdm_sample_windows returns for the clip alone on a B = 1 windowed plan (same weights,
+ *            window = L, the same overlap, x_T, seed, clip0 = clip_id), in every arithmetic mode, for DDPM / DDIM / the table-driven
+ *            sampler, with and without guidance, whatever the other slots hold and whenever the group was admitted.  Plain slots beside
+ *            it keep their guarantee; overlapping rows of member slots are bitwise equal at every step.
+ *   capacity fdm_plan_set(p, "slot_long_frames", F) and (p, "slot_long_groups", G) BEFORE fdm_slots_open (both default 0 = no long
+ *            capacity: the recorded program and its launch count are exactly those of a plan without this feature).  fdm_slots_open then
+ *            reserves an arena of F long frames (latent, history, per-frame table), B * L entries and G group descriptors; nothing is
+ *            allocated per admit.  fdm_plan_get reads both keys back (a build without the feature does not know them).  With capacity the
+ *            step has the same launch count: the group update rides the slot scheduler pass.
+ * fdm_slot_admit_long: hub [N, fw] features of the WHOLE recording, style / emo as fdm_slot_admit, x_T [L_total*G, c] device fp32.  n must
+ *   equal the layout's window count, every listed slot must be idle and distinct, L_total > L (a shorter clip is one window: use
+ *   fdm_slot_admit) and L_total <= N / pair; a contiguous arena range, an entry range and a descriptor are taken by first fit.  Builds
+ *   each member's rows with fdm_slot_admit's per-clip GEMMs, copies x_T into the arena and scatters it into the window rows (+ operand
+ *   copies), zeroes the group's history, uploads the group's tables and sets every member's word to {k = -1, running} with the group's
+ *   key.  The tables are host memory of this call: the call DRAINS THE STREAM ONCE after uploading them, as fdm_audio_prepare_windows
+ *   does (no pinned staging buffer).  FDM_ERR_STATE: a listed slot is busy, or no arena range / entry range / descriptor is free -- the
+ *   caller's cue to wait; FDM_ERR_SHAPE: L_total <= L, L_total > N / pair, n != the window count, n > B, bad feature width;
+ *   FDM_ERR_ARG: null pointer, slot outside [0, B), a slot listed twice, overlap outside [0, L), no long capacity reserved.  Every
+ *   check is made before the first launch: a failed call leaves the plan untouched.
+ * fdm_slot_state reports the group's progress for every member.  fdm_slot_group (host only): leader = -1, n = 0, L_total = 0 for a plain
+ *   or idle slot, else the group's leader, member count and L_total (any output may be NULL).  fdm_slot_read_long: copies the long buffer
+ *   to out [L_total*G, c], frees the arena range, the entries and the descriptor and marks every member idle; FDM_ERR_STATE unless `leader`
+ *   leads a finished group.  fdm_slot_read on a member fails with FDM_ERR_STATE; fdm_slot_peek stays per slot (a member's window rows). */
+int fdm_slot_admit_long(fdm_plan* p, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                        int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, void* stream);
+int fdm_slot_group(fdm_plan* p, int slot, int* leader, int* n, int* L_total);
+int fdm_slot_read_long(fdm_plan* p, int leader, float* out, void* stream);
+/* The tables of one group (host, no device): for a long clip of L_total > L frames as n = fdm_window_layout_host(L_total, L, overlap)
+ * windows held by slots[0 .. n), off [L_total + 1] receives the per-frame offsets into the entries (off[0] = 0, monotone) and
+ * ent_slot / ent_start / ent_wt [n * L] the entries: for frame f the covering windows in ascending window order, each with its slot
+ * (slots[w]), its start s_w and its normalised weight -- bit for bit fdm_window_weights_host's.  Returns the number of entries (n * L);
+ * nothing is written unless cap >= it (outputs may be NULL to ask for the count).  FDM_ERR_ARG: bad overlap, slots NULL;
+ * FDM_ERR_SHAPE: L_total <= L, n != the window count.  fdm_slot_admit_long builds its tables with this function. */
+int fdm_slot_group_table_host(int L_total, int L, int overlap, const int* slots, int n, int* off, int* ent_slot, int* ent_start,
+                              float* ent_wt, int cap);
 /* Plan-time tuning of the GEMM output tiles at the prepared shape (times candidates per call site; changes speed only, every
  * tile accumulates k in the same order).  This call is the ONLY place the library tunes by itself: request paths
  * (fdm_audio_prepare*, fdm_sample_graph) never do -- fdm_plan_get(p, "needs_tune") turns 1 once the prepared shape has served
@@ -573,10 +646,11 @@ int fdm_slot_peek(fdm_plan* p, int slot, float* out, void* stream);
  * FDM_GEMM_LOCKSTEP=1 = FDM_TILE_LOCKSTEP for every fdm_op_gemm of the process (A/B of the once-per-clip stages; the step has fdm_plan_set "lockstep"). */
 int fdm_plan_tune(fdm_plan* p, void* stream);
 /* Introspection / experiments: integer properties by name -- "launches_per_step", "graph_launches" (host graph launches of
- * the last fdm_sample_graph / fdm_slots_run), "rows", "slots", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
+ * the last fdm_sample_graph / fdm_slots_run), "rows", "slots", "slot_long_frames", "slot_long_groups", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
  * enc, dec, ...). */
 int fdm_plan_get(fdm_plan* p, const char* key, long long* out);
-/* "tile.<call site>" (drops recorded programs), "tune" (0 = off), "tune_lazy" (1 = in-call tuning allowed), "untune" (forget every
+/* "slot_long_frames" / "slot_long_groups" (long capacity of the NEXT fdm_slots_open, see fdm_slot_admit_long),
+ * "tile.<call site>" (drops recorded programs), "tune" (0 = off), "tune_lazy" (1 = in-call tuning allowed), "untune" (forget every
  * tuned set), "fuse_ln3" (1 = fold norm3 into the GEMMs around it: 8 launches fewer per step, no longer faster; takes effect at
  * the next commit) */
 int fdm_plan_set(fdm_plan* p, const char* key, long long value);
