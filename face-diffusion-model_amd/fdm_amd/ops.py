@@ -154,8 +154,10 @@ def attention(Q, Kp, Vp, O, *, B, H, L, hd, ldq, ldo, Lpad, scale, causal=False,
 
 def layernorm(x, gamma, beta, M, d, *, add_mat=None, add_tab=None, tab_index=None, tab_step=None, eps=1e-5,
               act=ACT_NONE, y_f32=None, y_t=None, dtype=F32, gamma2=None, beta2=None, x_planes=0, x_plane_stride=0,
-              clip_step=None, clip_step_stride=1, clip_rows=0, clip_wrap=0):
-    """clip_step (device int32 words, clip_step_stride ints apart): the add_tab row is chosen per clip of clip_rows rows
+              clip_step=None, clip_step_stride=1, clip_rows=0, clip_wrap=0, add_mat_group=0, add_mat_wrap=0, add_mat_L=0):
+    """add_mat_group > 0: rows share add_mat rows (fdm_ln_args.add_mat_group: row m reads (m' / group) * add_mat_L + m' % add_mat_L,
+    m' = m % add_mat_wrap when add_mat_wrap > 0).
+    clip_step (device int32 words, clip_step_stride ints apart): the add_tab row is chosen per clip of clip_rows rows
     (fdm_ln_args.clip_step: the slot program's form) instead of by the single word tab_step."""
     a = LnArgs()
     a.x, a.M, a.d, a.add_mat, a.add_tab = _p(x), M, d, _p(add_mat), _p(add_tab)
@@ -163,6 +165,7 @@ def layernorm(x, gamma, beta, M, d, *, add_mat=None, add_tab=None, tab_index=Non
     a.act, a.y_f32, a.y_t, a.dtype = act, _p(y_f32), _p(y_t), dtype
     a.gamma2, a.beta2, a.y_t_lo_off = _p(gamma2), _p(beta2), _lo(y_t)
     a.x_planes, a.x_plane_stride = x_planes, x_plane_stride
+    a.add_mat_group, a.add_mat_wrap, a.add_mat_L = add_mat_group, add_mat_wrap, add_mat_L
     if clip_step is not None:
         a.clip_step, a.clip_step_stride, a.clip_rows, a.clip_wrap = _p(clip_step), clip_step_stride, clip_rows, clip_wrap
     check(lib().fdm_op_layernorm(C.byref(a), stream()))
