@@ -78,6 +78,7 @@ int fdm_abi_struct_size(const char* name) {
   if (n == "fdm_sample_args") return (int)sizeof(fdm_sample_args);
   if (n == "fdm_vq_desc") return (int)sizeof(fdm_vq_desc);
   if (n == "fdm_slot_group_args") return (int)sizeof(fdm_slot_group_args);
+  if (n == "fdm_slot_bank_args") return (int)sizeof(fdm_slot_bank_args);
   return fdm::fail(FDM_ERR_ARG, "abi_struct_size: unknown struct '%s'", name);
 }
 
@@ -290,6 +291,60 @@ int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const uns
   return submit([c, state, keys, gg, n_slots](hipStream_t s) { return fdm::slot_group_sched_launch(c, state, keys, gg, n_slots, s); }, stream, "slot_group_sched");
 }
 
+// what the two bank operators share: the bank's own pointers and sizes (the kernel checks every row against them)
+static int check_bank(const fdm_slot_bank_args* b, const char* who) {
+  if (!b || !b->req || !b->desc || !b->t) return fail(FDM_ERR_ARG, "%s: null bank table", who);
+  if (b->n_samplers < 1 || b->n_t < 1 || b->n_coef < 0 || (b->n_coef > 0 && !b->coef)) return fail(FDM_ERR_SHAPE, "%s: bank sizes (%d samplers, %d timesteps, %d coefficients)", who, b->n_samplers, b->n_t, b->n_coef);
+  if (!aligned16(b->req) || !aligned16(b->desc)) return fail(FDM_ERR_ARG, "%s: request rows and descriptors must be 16-byte aligned", who);
+  return FDM_OK;
+}
+
+int fdm_op_slot_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                           const fdm_slot_bank_args* b, void* stream) {
+  if (!a || !a->x0 || !a->x || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_sched_bank: null operand");
+  FCK(check_bank(b, "slot_sched_bank"));
+  if (a->noise) return fail(FDM_ERR_ARG, "slot_sched_bank: injected noise is not supported (Philox keyed per slot)");
+  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_sched_bank: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_sched_bank: bad out_dtype %d", a->out_dtype);
+  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_sched_bank: split x_out_t needs x_out_t_lo_off");
+  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state))
+    return fail(FDM_ERR_ARG, "slot_sched_bank: operands and the state words must be 16-byte aligned");
+  fdm_sched_args c = *a;
+  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
+  c.sqrt_an = c.c_n = nullptr; c.lm_a = c.lm_b = c.lm_c = c.lm_s = nullptr;      // (the bank holds every step-indexed table)
+  const fdm_slot_bank_args bb = *b;
+  return submit([c, state, keys, bb](hipStream_t s) { return fdm::slot_sched_bank_launch(c, state, keys, bb, s); }, stream, "slot_sched_bank");
+}
+
+int fdm_op_slot_group_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                                 const fdm_slot_group_args* g, const fdm_slot_bank_args* b, void* stream) {
+  if (!a || !g || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null operand");
+  FCK(check_bank(b, "slot_group_sched_bank"));
+  if (!g->member || !g->frames || !g->entries || !g->groups || !g->x_long) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null table or arena");
+  if (!g->init && (!a->x0 || !a->x)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null operand");
+  if (g->init && g->plain) return fail(FDM_ERR_ARG, "slot_group_sched_bank: init loads the arena into the window rows only (plain must be 0)");
+  if (a->noise) return fail(FDM_ERR_ARG, "slot_group_sched_bank: injected noise is not supported (Philox keyed per slot / group)");
+  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
+  if (g->L < 1 || g->d < 4 || g->d % 4 || (long long)g->L * g->d != a->n_per_clip)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: L=%d x d=%d (a multiple of 4) must be n_per_clip=%lld", g->L, g->d, a->n_per_clip);
+  if (g->arena_frames < 1 || g->n_groups < 1 || g->n_entries < 1 || g->frame0 < 0 || g->frame1 < g->frame0 || g->frame1 > g->arena_frames)
+    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: arena frames [%d, %d) outside [0, %d), or no groups / entries", g->frame0, g->frame1, g->arena_frames);
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: bad out_dtype %d", a->out_dtype);
+  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: split x_out_t needs x_out_t_lo_off");
+  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state) ||
+      !aligned16(g->frames) || !aligned16(g->entries) || !aligned16(g->groups) || !aligned16(g->x_long) || !aligned16(g->hist_long))
+    return fail(FDM_ERR_ARG, "slot_group_sched_bank: operands, table rows and the state words must be 16-byte aligned");
+  fdm_sched_args c = *a;
+  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
+  c.sqrt_an = c.c_n = nullptr; c.lm_a = c.lm_b = c.lm_c = c.lm_s = nullptr;
+  const fdm_slot_group_args gg = *g;
+  const fdm_slot_bank_args bb = *b;
+  return submit([c, state, keys, gg, n_slots, bb](hipStream_t s) { return fdm::slot_group_sched_bank_launch(c, state, keys, gg, n_slots, bb, s); }, stream,
+                "slot_group_sched_bank");
+}
+
 }  // extern "C"
 
 // the two small launches of the slot program that are not public operators (slots.hpp): recorded like any fdm_op_*
@@ -307,6 +362,35 @@ int fdm::slot_set_op(int* state, int slot, int k, int t, int live, int run, unsi
     hipLaunchKernelGGL(fdm::slot_set_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state + slot, v, keys + 2 * (size_t)slot, seed, (unsigned long long)(unsigned)clip_id);
     return hipGetLastError();
   }, stream, "slot_set");
+}
+
+// ... and their forms on a plan with a sampler bank
+int fdm::slot_advance_bank_op(int* state, const fdm_slot_bank_args& b, int n_slots, void* stream) {
+  if (!state || !b.req || !b.desc || !b.t || b.n_samplers < 1 || b.n_t < 1 || n_slots < 1) return fail(FDM_ERR_ARG, "slot_advance_bank: bad argument");
+  const fdm_slot_bank_args bb = b;
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::slot_advance_bank_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state, (const fdm::SlotReq*)bb.req, (const fdm::BankDesc*)bb.desc,
+                       bb.t, bb.n_samplers, bb.n_t, n_slots);
+    return hipGetLastError();
+  }, stream, "slot_advance_bank");
+}
+int fdm::slot_set_bank_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id,
+                          void* req, int sampler, float cfg_scale, void* stream) {
+  if (!state || !keys || !req || slot < 0 || sampler < 0) return fail(FDM_ERR_ARG, "slot_set_bank: bad argument");
+  const fdm::SlotState v{k, t, live, run};
+  const fdm::SlotReq r{sampler, cfg_scale, 0, 0};
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::slot_set_bank_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state + slot, v, keys + 2 * (size_t)slot, seed,
+                       (unsigned long long)(unsigned)clip_id, (fdm::SlotReq*)req + slot, r);
+    return hipGetLastError();
+  }, stream, "slot_set_bank");
+}
+int fdm::slot_park_op(int* state, int slot, void* stream) {
+  if (!state || slot < 0) return fail(FDM_ERR_ARG, "slot_park: bad argument");
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::slot_park_kernel, dim3(1), dim3(64), 0, s, (fdm::SlotState*)state + slot);
+    return hipGetLastError();
+  }, stream, "slot_park");
 }
 
 // windowed sampling's blend + scheduler pass (window.hpp): not a public operator -- the plan layer records it into the step program

@@ -36,6 +36,12 @@ int window_sched_op(const fdm_sched_args& p, const WinArgs& w, void* stream);
 // in-flight batching (slots.hpp): advance every slot's {k, t, live, run} word once per step; set one slot's word and noise key
 int slot_advance_op(int* state, const int* tseq, int n_steps, int n_slots, void* stream);
 int slot_set_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id, void* stream);
+// ... on a plan with a sampler bank (fdm_slot_bank_args): the advance launch reads every slot's own sampler; an admit also writes the
+// slot's request row {sampler, cfg_scale}; a read parks the slot's word
+int slot_advance_bank_op(int* state, const fdm_slot_bank_args& b, int n_slots, void* stream);
+int slot_set_bank_op(int* state, int slot, int k, int t, int live, int run, unsigned long long* keys, unsigned long long seed, int clip_id,
+                     void* req, int sampler, float cfg_scale, void* stream);
+int slot_park_op(int* state, int slot, void* stream);
 
 // long requests in slot mode (slots.hpp; tables built by fdm_slot_group_table_host, uploaded by fdm_slot_admit_long): the device rows
 // fdm_slot_group_args points at.  One LongFrame per frame of the long arena, one LongEnt per (window, frame of the window), one

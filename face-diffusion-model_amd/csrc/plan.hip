@@ -448,6 +448,7 @@ struct ProgSpec {
   const float* san = nullptr; const float* cn = nullptr;
   int reps = 1;              // diffusion steps recorded back to back (one graph launch runs them all)
   int slot_steps = 0;        // > 0: the slot program of a chain of that many steps (advance launch, chain, slot scheduler pass)
+  int bank = 0;              // slot program with a sampler bank: the bank forms of the advance launch and of the scheduler pass
 };
 
 // Recorded programs are kept per (shape, tile set, program kind): a serving loop that alternates between shapes (clips of
@@ -480,6 +481,15 @@ fdm_slot_group_args long_args(const fdm_plan* P, int f0, int f1, int plain, int 
   return g;
 }
 
+// the sampler bank of a slot plan with bank capacity (fdm_slot_bank_args; sizes = what fdm_slots_open reserved)
+fdm_slot_bank_args bank_args(const fdm_plan* P) {
+  fdm_slot_bank_args b;
+  memset(&b, 0, sizeof(b));
+  b.req = P->slot_req; b.desc = P->bank_desc; b.t = P->bank_t; b.coef = P->bank_c;
+  b.n_samplers = P->bank_rows; b.n_t = P->bank_t_cap; b.n_coef = P->bank_c_cap;
+  return b;
+}
+
 int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
   char key[512];
   snprintf(key, sizeof(key), "%s#%s|%d|%p|%a|%p|%d", shape_key(P).c_str(), tiles_sig(P).c_str(), sp.kind, (const void*)sp.noise, (double)sp.cfg_scale,
@@ -494,6 +504,10 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
     if (P->long_frames) {    // ... and with long capacity the scheduler pass also walks the arena (keys without capacity unchanged)
       const size_t k2 = strlen(key);
       snprintf(key + k2, sizeof(key) - k2, "|long%d,%d", P->long_frames, P->long_groups);
+    }
+    if (sp.bank) {           // ... and with a sampler bank both ends of the step read it (keys without a bank unchanged)
+      const size_t k3 = strlen(key);
+      snprintf(key + k3, sizeof(key) - k3, "|bank%d,%d,%d", P->bank_rows, P->bank_t_cap, P->bank_c_cap);
     }
   }
   auto it = P->progs.find(key);
@@ -546,6 +560,20 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       // slot program: advance every slot's word, the chain with per-slot table rows and its scheduler update unfused, then the
       // pass that updates the live slots only -- two launches more than the plain program without guidance
       sc.n_per_clip = (long long)P->L * d; sc.noise = nullptr; sc.seed_dev = nullptr; sc.step = nullptr; sc.tseq = nullptr;
+      if (sp.bank) {
+        // sampler bank: the same three parts, both ends reading every slot's own sampler; sc carries the t-indexed tables of every
+        // mode and the plain slots' history (mode, scale and the step-indexed tables come from the bank)
+        const fdm_slot_bank_args bk = bank_args(P);
+        sc.mode = 0; sc.cfg_scale = 0.f;
+        sc.c1 = P->c1; sc.c2 = P->c2; sc.sigma = P->sigma; sc.sra = P->sra; sc.srm1 = P->srm1; sc.x0_hist = P->x0_hist;
+        rc = fdm::slot_advance_bank_op(P->slot_state, bk, P->slots, stream);
+        if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
+        if (rc == FDM_OK) {
+          if (P->long_frames) { const fdm_slot_group_args lg = long_args(P, 0, P->long_frames, 1, 0); rc = fdm_op_slot_group_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &lg, &bk, stream); }
+          else rc = fdm_op_slot_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &bk, stream);
+        }
+        continue;
+      }
       rc = fdm::slot_advance_op(P->slot_state, P->tseq, sp.slot_steps, P->slots, stream);
       if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
       if (rc == FDM_OK) {
@@ -711,6 +739,37 @@ int sampler_setup(fdm_plan* P, const fdm_sample_args* a, void* stream, std::vect
     sp.kind = 3; sp.noise = a->noise; sp.san = P->lm_tab;
   } else {
     return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", a->kind);
+  }
+  return FDM_OK;
+}
+
+// A sampler definition as the bank stores it (slots.hpp): the scheduler mode, the timestep list and the step-indexed coefficients
+// in bank layout -- the values sampler_setup puts on the device for the same arguments, so a slot's bits match the solo path.
+struct SamplerDef { int kind = 0, mode = 0; std::vector<int> ts; std::vector<float> coef; };
+int sampler_def(const fdm_sample_args* a, const char* who, SamplerDef& o) {
+  o.kind = a->kind;
+  if (a->kind == 0) {
+    if (!a->t_list || a->n_steps <= 0) return fail(FDM_ERR_ARG, "%s: DDPM needs t_list / n_steps", who);
+    FCK(take_steps(a, o.ts));
+    o.mode = 0;
+  } else if (a->kind == 1) {
+    if (a->ddim_steps <= 0) return fail(FDM_ERR_ARG, "%s: DDIM needs ddim_steps", who);
+    std::vector<int> t(a->ddim_steps), tn(a->ddim_steps);
+    std::vector<float> tab(2 * (size_t)a->ddim_steps);
+    const int n = fdm_ddim_schedule_host(a->ddim_steps, 1000, t.data(), tn.data(), tab.data(), tab.data() + a->ddim_steps);
+    if (n < 0) return n;
+    if (n == 0) return fail(FDM_ERR_ARG, "%s: the sampler has no live step (ddim_steps = %d)", who, a->ddim_steps);
+    o.mode = 1;
+    o.ts.assign(t.begin(), t.begin() + n);                                   // (the dead last pair is skipped)
+    o.coef.assign(tab.begin(), tab.begin() + n);                             // sqrt_an[n] | c_n[n]
+    o.coef.insert(o.coef.end(), tab.begin() + a->ddim_steps, tab.begin() + a->ddim_steps + n);
+  } else if (a->kind == 2) {
+    FCK(check_tables_args(a));
+    FCK(take_steps(a, o.ts));
+    o.mode = 3;
+    o.coef.assign(a->lm_tables, a->lm_tables + 4 * (size_t)a->n_steps);      // a | b | c | s, each n_steps
+  } else {
+    return fail(FDM_ERR_ARG, "%s: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", who, a->kind);
   }
   return FDM_OK;
 }
@@ -927,6 +986,7 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   P->win_n = 0;                              // plain mode (fdm_audio_prepare_windows sets the window mode after this call)
   P->slots = 0;                              // ... and out of slot mode (slot programs keep their own cache keys)
   P->long_frames = P->long_groups = P->long_entries = 0;
+  P->bank_rows = P->bank_t_cap = P->bank_c_cap = 0;
   if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
   if (L < 1 || L > N / m.pair || L > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare: latent frames L=%d outside [1, min(%d, %d)] (models/fdm_vocaset.py:44,64-66)", L, N / m.pair, m.max_len);
   if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
@@ -1068,6 +1128,7 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   P->pinned.clear();
   P->win_n = 0; P->slots = 0;
   P->long_frames = P->long_groups = P->long_entries = 0;
+  P->bank_rows = P->bank_t_cap = P->bank_c_cap = 0;
   FCK(commit(P, stream));
   FCK(reserve(P, B, L, cfg));
   FCK(grow(P, (void**)&P->slot_state, &P->slot_state_cap, (size_t)B * 16, stream));
@@ -1092,6 +1153,24 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
     HIPCK(hipMemsetAsync(P->long_group, 0, (size_t)LG * sizeof(fdm::LongGroup), s));
     HIPCK(hipMemsetAsync(P->slot_member, 0xff, (size_t)B * 4, s));                            // -1: every slot plain
   }
+  // bank capacity asked for before this call: request rows, 1 + S descriptors, sampler 0's steps + N timesteps, four coefficients per
+  // step -- all reserved here, nothing per fdm_slot_sampler_add
+  const bool want_bank = P->want_samplers > 0 && P->want_sampler_steps > 0;
+  SamplerDef def0;
+  P->bank_rows = 0; P->bank_t_cap = 0; P->bank_c_cap = 0;
+  P->sampler_host.clear();
+  if (want_bank) {
+    FCK(sampler_def(a, "slots_open", def0));
+    const int rows = 1 + P->want_samplers, nt = (int)def0.ts.size() + P->want_sampler_steps;
+    FCK(grow(P, &P->slot_req, &P->slot_req_cap, (size_t)B * 16, stream));
+    FCK(grow(P, (void**)&P->bank_desc, &P->bank_desc_cap, (size_t)rows * 16, stream));
+    FCK(grow(P, (void**)&P->bank_t, &P->bank_t_bytes, (size_t)nt * 4, stream));
+    FCK(grow(P, (void**)&P->bank_c, &P->bank_c_bytes, (size_t)nt * 16, stream));
+    HIPCK(hipMemsetAsync(P->slot_req, 0, (size_t)B * 16, s));
+    HIPCK(hipMemsetAsync(P->bank_desc, 0, (size_t)rows * 16, s));             // n_steps = 0: every descriptor free
+    HIPCK(hipMemsetAsync(P->bank_t, 0, (size_t)nt * 4, s));
+    HIPCK(hipMemsetAsync(P->bank_c, 0, (size_t)nt * 16, s));
+  }
   const int d = m.d, M = B * L, rep = cfg ? 2 : 1;
   P->B = B; P->S = 1; P->L = L; P->M = M; P->rep = rep; P->R = M * rep; P->cfg = cfg ? 1 : 0; P->Lpad = (L + 31) / 32 * 32;
   // every slot idle and holding zeros: tables, latent (+ operand copy), history, packed K / V pad keys, state words and keys
@@ -1111,6 +1190,12 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   ProgSpec sp;
   FCK(sampler_setup(P, a, stream, ts, sp));
   if (ts.empty()) return fail(FDM_ERR_ARG, "slots_open: the sampler has no live step (ddim_steps = %d)", a->ddim_steps);
+  if (want_bank) {           // sampler 0 at the start of the bank (set_steps below drains the copies: def0 is host memory)
+    const int desc0[4] = {def0.mode, (int)def0.ts.size(), 0, 0};
+    HIPCK(hipMemcpyAsync(P->bank_desc, desc0, 16, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(P->bank_t, def0.ts.data(), def0.ts.size() * 4, hipMemcpyHostToDevice, s));
+    if (!def0.coef.empty()) HIPCK(hipMemcpyAsync(P->bank_c, def0.coef.data(), def0.coef.size() * 4, hipMemcpyHostToDevice, s));
+  }
   FCK(set_steps(P, ts.data(), (int)ts.size(), stream));
   P->slot_kind = sp.kind; P->slot_nsteps = (int)ts.size(); P->slot_t0 = ts[0];
   P->slot_san = sp.san; P->slot_cn = sp.cn;
@@ -1118,13 +1203,43 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   P->slot_host.assign(B, fdm_plan::SlotHost());
   P->slots = B;
   if (LF) { P->long_frames = LF; P->long_groups = LG; P->long_entries = B * L; P->group_host.assign(LG, fdm_plan::GroupHost()); }
+  if (want_bank) {
+    P->bank_rows = 1 + P->want_samplers; P->bank_t_cap = (int)def0.ts.size() + P->want_sampler_steps; P->bank_c_cap = 4 * P->bank_t_cap;
+    P->sampler_host.assign(P->bank_rows, fdm_plan::SamplerHost());
+    fdm_plan::SamplerHost& s0 = P->sampler_host[0];
+    s0.used = true; s0.kind = def0.kind; s0.mode = def0.mode; s0.n_steps = (int)def0.ts.size(); s0.t0 = def0.ts[0]; s0.n_c = (int)def0.coef.size();
+  }
   P->prepared = true;
   select_tiles(P);
   return FDM_OK;
 }
 
+// the sampler and guidance scale of a request, checked (fdm_slot_admit_as / fdm_slot_admit_long_as): steps and first timestep of its chain
+static int request_sampler(const fdm_plan* P, const char* who, int sampler, float cfg_scale, int* n_steps, int* t0) {
+  if (!P->bank_rows) {
+    if (sampler != 0) return fail(FDM_ERR_ARG, "%s: sampler %d, the session has no sampler bank (fdm_plan_set slot_samplers / slot_sampler_steps before fdm_slots_open)", who, sampler);
+    if (P->cfg && cfg_scale != P->slot_cfg_scale) return fail(FDM_ERR_ARG, "%s: a cfg_scale per request needs a sampler bank (the session's is %g)", who, (double)P->slot_cfg_scale);
+    *n_steps = P->slot_nsteps; *t0 = P->slot_t0;
+    return FDM_OK;
+  }
+  if (sampler < 0 || sampler >= P->bank_rows || !P->sampler_host[sampler].used) return fail(FDM_ERR_ARG, "%s: unknown sampler %d", who, sampler);
+  *n_steps = P->sampler_host[sampler].n_steps; *t0 = P->sampler_host[sampler].t0;
+  return FDM_OK;
+}
+// one slot's word and key (and, with a bank, its request row): {k = -1, running} at the first timestep of its sampler
+static int slot_start(fdm_plan* P, int slot, int t0, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
+  if (P->bank_rows) return fdm::slot_set_bank_op(P->slot_state, slot, -1, t0, 0, 1, P->slot_keys, seed, clip_id, P->slot_req, sampler, cfg_scale, stream);
+  return fdm::slot_set_op(P->slot_state, slot, -1, t0, 0, 1, P->slot_keys, seed, clip_id, stream);
+}
+
 int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
                    const float* x_T, unsigned long long seed, int clip_id, void* stream) {
+  if (!P) return fail(FDM_ERR_ARG, "slot_admit: null argument");
+  return fdm_slot_admit_as(P, slot, hub, N, fw, style, emo, L_clip, x_T, seed, clip_id, 0, P->slot_cfg_scale, stream);
+}
+
+int fdm_slot_admit_as(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                      const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
   if (!P || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit: null argument");
   FCK(check_slots(P, "slot_admit"));
   const fdm_model_desc& m = P->m;
@@ -1134,6 +1249,8 @@ int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const
   if (L_clip < 1 || L_clip > P->L || L_clip > N / m.pair) return fail(FDM_ERR_SHAPE, "slot_admit: L_clip=%d outside [1, min(%d, %d)]", L_clip, P->L, N / m.pair);
   fdm_plan::SlotHost& h = P->slot_host[slot];
   if (h.status != 0) return fail(FDM_ERR_STATE, "slot_admit: slot %d is %s", slot, h.status == 1 ? "running" : "finished and not read");
+  int total = 0, t0 = 0;
+  FCK(request_sampler(P, "slot_admit", sampler, cfg_scale, &total, &t0));
   hipStream_t s = (hipStream_t)stream;
   const int d = m.d, L = P->L, row0 = slot * L, pad = L - L_clip;
   const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
@@ -1150,8 +1267,8 @@ int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const
     FCK(fdm_op_sched_step(&sc, stream));
   }
   // {k = -1, running}: the next step's advance launch makes it step 0 of this slot's chain
-  FCK(fdm::slot_set_op(P->slot_state, slot, -1, P->slot_t0, 0, 1, P->slot_keys, seed, clip_id, stream));
-  h.status = 1; h.done = 0; h.L = L_clip;
+  FCK(slot_start(P, slot, t0, seed, clip_id, sampler, cfg_scale, stream));
+  h.status = 1; h.done = 0; h.L = L_clip; h.sampler = sampler; h.total = total;
   return FDM_OK;
 }
 
@@ -1162,6 +1279,10 @@ int fdm_slots_run(fdm_plan* P, int n_steps, void* stream) {
   P->last_graph_launches = 0;
   ProgSpec sp;
   sp.kind = P->slot_kind; sp.cfg_scale = P->slot_cfg_scale; sp.san = P->slot_san; sp.cn = P->slot_cn; sp.slot_steps = P->slot_nsteps;
+  if (P->bank_rows) {        // the bank program serves every sampler and scale: none of them is part of its key
+    sp = ProgSpec();
+    sp.kind = 4; sp.slot_steps = 1; sp.bank = 1;
+  }
   fdm_prog* p1 = nullptr;
   FCK(get_program(P, sp, stream, &p1));
   if (n_steps == 0) return FDM_OK;
@@ -1187,11 +1308,11 @@ int fdm_slots_run(fdm_plan* P, int n_steps, void* stream) {
       P->last_graph_launches += left;
     }
   }
-  // the host mirror: a running slot does min(n_steps, what its chain has left) steps and freezes when the chain ends
+  // the host mirror: a running slot does min(n_steps, what ITS chain has left) steps and freezes when the chain ends
   for (auto& h : P->slot_host)
     if (h.status == 1) {
-      h.done = std::min(P->slot_nsteps, h.done + n_steps);
-      if (h.done == P->slot_nsteps) h.status = 2;
+      h.done = std::min(h.total, h.done + n_steps);
+      if (h.done == h.total) h.status = 2;
     }
   return FDM_OK;
 }
@@ -1201,7 +1322,7 @@ int fdm_slot_state(fdm_plan* P, int slot, int* steps_done, int* steps_total, int
   if (slot < 0 || slot >= P->slots) return fail(FDM_ERR_ARG, "slot_state: slot %d outside [0, %d)", slot, P->slots);
   const fdm_plan::SlotHost& h = P->slot_host[slot];
   if (steps_done) *steps_done = h.done;
-  if (steps_total) *steps_total = P->slot_nsteps;
+  if (steps_total) *steps_total = h.status ? h.total : P->slot_nsteps;      // (an idle slot: sampler 0's)
   if (status) *status = h.status;
   return FDM_OK;
 }
@@ -1214,6 +1335,7 @@ int fdm_slot_read(fdm_plan* P, int slot, float* out, void* stream) {
   if (h.group >= 0) return fail(FDM_ERR_STATE, "slot_read: slot %d holds a window of a long request (fdm_slot_read_long on its leader)", slot);
   if (h.status != 2) return fail(FDM_ERR_STATE, "slot_read: slot %d is %s, not finished", slot, h.status == 1 ? "running" : "idle");
   HIPCK(hipMemcpyAsync(out, P->x + (size_t)slot * P->L * P->m.d, (size_t)h.L * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (P->bank_rows) FCK(fdm::slot_park_op(P->slot_state, slot, stream));      // (its sampler may be dropped and the descriptor reused)
   h = fdm_plan::SlotHost();
   return FDM_OK;
 }
@@ -1229,6 +1351,13 @@ int fdm_slot_peek(fdm_plan* P, int slot, float* out, void* stream) {
 // ---- long requests in slot mode (include/fdm_hip.h, "Long requests in slot mode") -----------------------------------------
 int fdm_slot_admit_long(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
                         int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, void* stream) {
+  if (!P) return fail(FDM_ERR_ARG, "slot_admit_long: null argument");
+  return fdm_slot_admit_long_as(P, slots, n, hub, N, fw, style, emo, L_total, overlap, x_T, seed, clip_id, 0, P->slot_cfg_scale, stream);
+}
+
+int fdm_slot_admit_long_as(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                           int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale,
+                           void* stream) {
   if (!P || !slots || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit_long: null argument");
   FCK(check_slots(P, "slot_admit_long"));
   const fdm_model_desc& m = P->m;
@@ -1240,6 +1369,8 @@ int fdm_slot_admit_long(fdm_plan* P, const int* slots, int n, const float* hub, 
   if (L_total <= L) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d fits one slot of %d frames (fdm_slot_admit)", L_total, L);
   if (L_total > N / m.pair) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d outside (%d, %d] (N / pair)", L_total, L, N / m.pair);
   if (L_total > P->long_frames) return fail(FDM_ERR_SHAPE, "slot_admit_long: L_total=%d exceeds the arena of %d long frames", L_total, P->long_frames);
+  int total = 0, t0 = 0;
+  FCK(request_sampler(P, "slot_admit_long", sampler, cfg_scale, &total, &t0));
   std::vector<int> starts;
   const int nw = window_layout(L_total, L, overlap, starts);
   if (nw < 0) return nw;
@@ -1304,11 +1435,11 @@ int fdm_slot_admit_long(fdm_plan* P, const int* slots, int n, const float* hub, 
   if (P->dtype != FDM_F32) { sc.x_out_t = P->xt.p; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo; }
   const fdm_slot_group_args lg = long_args(P, a0, a0 + L_total, 0, 1);
   FCK(fdm_op_slot_group_sched(&sc, P->slot_state, P->slot_keys, P->slots, &lg, stream));
-  // every member {k = -1, running} with the group's key: the next step's advance launch makes it step 0 of the group's chain
+  // every member {k = -1, running} with the group's key (and request): the next step's advance launch makes it step 0 of the group's chain
   for (int w = 0; w < n; ++w) {
-    FCK(fdm::slot_set_op(P->slot_state, slots[w], -1, P->slot_t0, 0, 1, P->slot_keys, seed, clip_id, stream));
+    FCK(slot_start(P, slots[w], t0, seed, clip_id, sampler, cfg_scale, stream));
     fdm_plan::SlotHost& h = P->slot_host[slots[w]];
-    h.status = 1; h.done = 0; h.L = L; h.group = gi;
+    h.status = 1; h.done = 0; h.L = L; h.group = gi; h.sampler = sampler; h.total = total;
   }
   fdm_plan::GroupHost& gh = P->group_host[gi];
   gh.used = true; gh.L_total = L_total; gh.first = a0; gh.e0 = e0; gh.ne = ne; gh.slots.assign(slots, slots + n);
@@ -1342,9 +1473,79 @@ int fdm_slot_read_long(fdm_plan* P, int leader, float* out, void* stream) {
   HIPCK(hipMemsetAsync(P->long_frame + g.first, 0xff, (size_t)g.L_total * sizeof(fdm::LongFrame), s));
   for (int sl : g.slots) {
     HIPCK(hipMemsetAsync(P->slot_member + sl, 0xff, 4, s));
+    if (P->bank_rows) FCK(fdm::slot_park_op(P->slot_state, sl, stream));
     P->slot_host[sl] = fdm_plan::SlotHost();
   }
   g = fdm_plan::GroupHost();
+  return FDM_OK;
+}
+
+// ---- samplers per request in slot mode (include/fdm_hip.h, "Samplers per request in slot mode") ---------------------------
+int fdm_slot_sampler_add(fdm_plan* P, const fdm_sample_args* a, void* stream) {
+  if (!a) return fail(FDM_ERR_ARG, "slot_sampler_add: null sampler");
+  if (a->noise || a->record) return fail(FDM_ERR_ARG, "slot_sampler_add: injected noise and record are not supported in slot mode");
+  if (!P) return fail(FDM_ERR_ARG, "slot_sampler_add: null plan");
+  FCK(check_slots(P, "slot_sampler_add"));
+  SamplerDef def;
+  FCK(sampler_def(a, "slot_sampler_add", def));
+  if (!P->bank_rows) return fail(FDM_ERR_STATE, "slot_sampler_add: the session has no sampler bank (fdm_plan_set slot_samplers / slot_sampler_steps before fdm_slots_open)");
+  int id = -1;
+  for (int i = 1; i < P->bank_rows && id < 0; ++i)
+    if (!P->sampler_host[i].used) id = i;
+  if (id < 0) return fail(FDM_ERR_STATE, "slot_sampler_add: all %d bank rows are in use", P->bank_rows - 1);
+  // a timestep range and a coefficient range, by first fit over what the live samplers hold
+  auto first_fit = [&](bool coef, int need, int cap) {
+    std::vector<std::pair<int, int>> used;
+    for (const auto& h : P->sampler_host)
+      if (h.used && (coef ? h.n_c : h.n_steps) > 0) used.push_back(coef ? std::make_pair(h.c_off, h.n_c) : std::make_pair(h.t_off, h.n_steps));
+    std::sort(used.begin(), used.end());
+    int at = 0;
+    for (const auto& u : used) {
+      if (u.first - at >= need) return at;
+      at = u.first + u.second;
+    }
+    return cap - at >= need ? at : -1;
+  };
+  const int nt = (int)def.ts.size(), nc = (int)def.coef.size();
+  const int t_off = first_fit(false, nt, P->bank_t_cap), c_off = nc ? first_fit(true, nc, P->bank_c_cap) : 0;
+  if (t_off < 0) return fail(FDM_ERR_STATE, "slot_sampler_add: no free range of %d timesteps (bank %d)", nt, P->bank_t_cap);
+  if (c_off < 0) return fail(FDM_ERR_STATE, "slot_sampler_add: no free range of %d coefficients (bank %d)", nc, P->bank_c_cap);
+  // ---- nothing above touched the plan.  The ranges are free: no running slot names them, so the upload is legal mid-chain
+  hipStream_t s = (hipStream_t)stream;
+  const int desc[4] = {def.mode, nt, t_off, c_off};
+  HIPCK(hipMemcpyAsync(P->bank_t + t_off, def.ts.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+  if (nc) HIPCK(hipMemcpyAsync(P->bank_c + c_off, def.coef.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(P->bank_desc + 4 * (size_t)id, desc, 16, hipMemcpyHostToDevice, s));
+  HIPCK(hipStreamSynchronize(s));            // (the tables are host memory of this call)
+  fdm_plan::SamplerHost& h = P->sampler_host[id];
+  h.used = true; h.kind = def.kind; h.mode = def.mode; h.n_steps = nt; h.t0 = def.ts[0]; h.t_off = t_off; h.c_off = c_off; h.n_c = nc;
+  return id;
+}
+
+int fdm_slot_sampler_drop(fdm_plan* P, int id) {
+  if (!P) return fail(FDM_ERR_ARG, "slot_sampler_drop: null plan");
+  FCK(check_slots(P, "slot_sampler_drop"));
+  if (id < 1 || id >= P->bank_rows || !P->sampler_host[id].used) return fail(FDM_ERR_ARG, "slot_sampler_drop: %s", id == 0 ? "sampler 0 belongs to the session" : "unknown sampler");
+  for (size_t i = 0; i < P->slot_host.size(); ++i)
+    if (P->slot_host[i].status != 0 && P->slot_host[i].sampler == id)
+      return fail(FDM_ERR_STATE, "slot_sampler_drop: slot %d (%s) names sampler %d", (int)i, P->slot_host[i].status == 1 ? "running" : "finished and not read", id);
+  // host only: every slot that named it has been read (its word is parked), and a descriptor nobody names is never loaded
+  P->sampler_host[id] = fdm_plan::SamplerHost();
+  return FDM_OK;
+}
+
+int fdm_slot_sampler_info(fdm_plan* P, int id, int* kind, int* n_steps) {
+  if (!P) return fail(FDM_ERR_ARG, "slot_sampler_info: null plan");
+  FCK(check_slots(P, "slot_sampler_info"));
+  if (!P->bank_rows) {
+    if (id != 0) return fail(FDM_ERR_ARG, "slot_sampler_info: unknown sampler %d", id);
+    if (kind) *kind = P->slot_kind - 1;      // (program kind 1 / 2 / 3 = fdm_sample_args.kind 0 / 1 / 2)
+    if (n_steps) *n_steps = P->slot_nsteps;
+    return FDM_OK;
+  }
+  if (id < 0 || id >= P->bank_rows || !P->sampler_host[id].used) return fail(FDM_ERR_ARG, "slot_sampler_info: unknown sampler %d", id);
+  if (kind) *kind = P->sampler_host[id].kind;
+  if (n_steps) *n_steps = P->sampler_host[id].n_steps;
   return FDM_OK;
 }
 
@@ -1369,6 +1570,8 @@ int fdm_plan_get(fdm_plan* P, const char* key, long long* out) {
   else if (k == "slots") *out = P->slots;
   else if (k == "slot_long_frames") *out = P->want_long_frames;
   else if (k == "slot_long_groups") *out = P->want_long_groups;
+  else if (k == "slot_samplers") *out = P->want_samplers;
+  else if (k == "slot_sampler_steps") *out = P->want_sampler_steps;
   else if (k == "window_len") *out = P->win_n ? P->win_len : P->L;
   else if (k == "L_total") *out = P->win_n ? P->win_total : P->L;
   else if (k.rfind("tile.", 0) == 0) { auto it = P->tiles.find(k.substr(5)); *out = it == P->tiles.end() ? 0 : it->second; }
@@ -1384,6 +1587,11 @@ int fdm_plan_set(fdm_plan* P, const char* key, long long value) {
   if (k == "slot_long_frames" || k == "slot_long_groups") {      // long capacity of the NEXT fdm_slots_open (both > 0 to have any)
     if (value < 0 || value > 0x3fffffffLL) return fail(FDM_ERR_ARG, "plan_set: %s = %lld", key, value);
     (k == "slot_long_frames" ? P->want_long_frames : P->want_long_groups) = (int)value;
+    return FDM_OK;
+  }
+  if (k == "slot_samplers" || k == "slot_sampler_steps") {      // bank capacity of the NEXT fdm_slots_open (both > 0 to have any)
+    if (value < 0 || value > 0xfffffLL) return fail(FDM_ERR_ARG, "plan_set: %s = %lld", key, value);
+    (k == "slot_samplers" ? P->want_samplers : P->want_sampler_steps) = (int)value;
     return FDM_OK;
   }
   if (k == "fuse_ln3") {      // takes effect at the next commit (the folded weights are commit-time tables)

@@ -73,12 +73,12 @@ struct fdm_plan {
   fdm::WinEnt* win_ent = nullptr; size_t win_ent_cap = 0;
   float* win_stage = nullptr; size_t win_stage_cap = 0;     // gathered window audio rows + repeated one-hots (read by the prepare)
   // ---- in-flight batching (fdm_slots_open): the plan's B clips are `slots` SLOTS of L frames, each at its own diffusion step of one
-  // shared sampler; slots == 0 = not in slot mode.  Device: one {k, t, live, run} word and one {seed, clip id} key per slot
+  // shared sampler (or, with a sampler bank, of its own: below); slots == 0 = not in slot mode.  Device: one {k, t, live, run} word and one {seed, clip id} key per slot
   // (plan-lifetime, grown on demand).  Host: a mirror of every slot's status and step count, so no call reads the device words.
   int slots = 0;
   int* slot_state = nullptr; size_t slot_state_cap = 0;
   unsigned long long* slot_keys = nullptr; size_t slot_keys_cap = 0;
-  struct SlotHost { int status = 0, done = 0, L = 0, group = -1; };     // status: 0 idle, 1 running, 2 finished (not read yet); group: its long request, -1 = a plain clip
+  struct SlotHost { int status = 0, done = 0, L = 0, group = -1, sampler = 0, total = 0; };     // status: 0 idle, 1 running, 2 finished (not read yet); group: its long request, -1 = a plain clip; sampler / total: its request's bank row and chain length
   std::vector<SlotHost> slot_host;
   int slot_kind = 0, slot_nsteps = 0, slot_t0 = 0;          // program kind (1 DDPM, 2 DDIM, 3 table-driven), steps per chain, tseq[0]
   int slot_graph_steps = 0, slot_eager = 0;
@@ -98,6 +98,18 @@ struct fdm_plan {
   int* slot_member = nullptr; size_t slot_member_cap = 0;
   struct GroupHost { bool used = false; int L_total = 0, first = 0, e0 = 0, ne = 0; std::vector<int> slots; };      // slots[0] = the leader
   std::vector<GroupHost> group_host;
+  // ---- samplers per request in slot mode (fdm_slot_sampler_add / fdm_slot_admit_as): a BANK of sampler definitions, sampler 0 = the one
+  // given to fdm_slots_open.  Capacity is asked for before fdm_slots_open (fdm_plan_set "slot_samplers" / "slot_sampler_steps") and
+  // reserved there; bank_rows == 0 = a session without a bank, whose program is the plain slot program.  Device tables as
+  // fdm_slot_bank_args describes them (layout: slots.hpp); the host mirrors every descriptor.
+  int want_samplers = 0, want_sampler_steps = 0;
+  int bank_rows = 0, bank_t_cap = 0, bank_c_cap = 0;          // descriptors (1 + capacity), timesteps, coefficients of this session
+  void* slot_req = nullptr; size_t slot_req_cap = 0;
+  int* bank_desc = nullptr; size_t bank_desc_cap = 0;
+  int* bank_t = nullptr; size_t bank_t_bytes = 0;
+  float* bank_c = nullptr; size_t bank_c_bytes = 0;
+  struct SamplerHost { bool used = false; int kind = 0, mode = 0, n_steps = 0, t0 = 0, t_off = 0, c_off = 0, n_c = 0; };      // kind as fdm_sample_args.kind
+  std::vector<SamplerHost> sampler_host;
 };
 
 namespace fdm {

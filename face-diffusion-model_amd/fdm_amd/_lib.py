@@ -85,9 +85,14 @@ class SlotGroupArgs(C.Structure):
                 ("plain", ci), ("init", ci)]
 
 
+class SlotBankArgs(C.Structure):
+    _fields_ = [("req", vp), ("desc", vp), ("t", vp), ("coef", vp), ("n_samplers", ci), ("n_t", ci), ("n_coef", ci), ("reserved", ci)]
+
+
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
-           "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs}
+           "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs,
+           "fdm_slot_bank_args": SlotBankArgs}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -103,6 +108,8 @@ SYMBOLS = {
     "fdm_op_sched_step": (ci, [C.POINTER(SchedArgs), vp]),
     "fdm_op_slot_sched": (ci, [C.POINTER(SchedArgs), vp, vp, ci, vp]),
     "fdm_op_slot_group_sched": (ci, [C.POINTER(SchedArgs), vp, vp, ci, C.POINTER(SlotGroupArgs), vp]),
+    "fdm_op_slot_sched_bank": (ci, [C.POINTER(SchedArgs), vp, vp, ci, C.POINTER(SlotBankArgs), vp]),
+    "fdm_op_slot_group_sched_bank": (ci, [C.POINTER(SchedArgs), vp, vp, ci, C.POINTER(SlotGroupArgs), C.POINTER(SlotBankArgs), vp]),
     "fdm_op_cast": (ci, [vp, vp, ll, ci, vp]),
     "fdm_op_vertex_err": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
     "fdm_op_motion_std": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
@@ -159,6 +166,11 @@ SYMBOLS = {
     "fdm_slot_group": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
     "fdm_slot_read_long": (ci, [vp, ci, vp, vp]),
     "fdm_slot_group_table_host": (ci, [ci, ci, ci, vp, ci, vp, vp, vp, vp, ci]),
+    "fdm_slot_sampler_add": (ci, [vp, C.POINTER(SampleArgs), vp]),
+    "fdm_slot_sampler_drop": (ci, [vp, ci]),
+    "fdm_slot_sampler_info": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
+    "fdm_slot_admit_as": (ci, [vp, ci, vp, ci, ci, vp, vp, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
+    "fdm_slot_admit_long_as": (ci, [vp, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
     "fdm_plan_tune": (ci, [vp, vp]),
     "fdm_plan_get": (ci, [vp, C.c_char_p, C.POINTER(ll)]),
     "fdm_plan_set": (ci, [vp, C.c_char_p, ll]),

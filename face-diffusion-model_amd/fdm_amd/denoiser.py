@@ -315,38 +315,69 @@ class DenoiserPlan:
         return out
 
     # ------------------------------------------------------------------------------------------
+    def _sampler_args(self, a, kind, steps=None, t_list=None, tables=None):
+        """kind / steps / t_list / tables of a sampler definition into fdm_sample_args; returns what must stay alive during the call."""
+        if kind == "ddim":
+            a.kind, a.ddim_steps = 1, int(steps)
+            return None
+        if kind == "ddpm":
+            held = (C.c_int * len(t_list))(*[int(t) for t in t_list])
+            a.kind, a.t_list, a.n_steps = 0, C.cast(held, C.c_void_p), len(t_list)
+            return held
+        if kind == "tables":
+            return self._tables_args(a, t_list, tables)
+        raise FdmError(f"kind {kind!r} (ddpm | ddim | tables)")
+
     def open_slots(self, slots, L, kind="ddim", steps=None, t_list=None, tables=None, cfg=False, cfg_scale=2.5, use_graph=True, graph_steps=0,
-                   long_frames=0, long_groups=0):
+                   long_frames=0, long_groups=0, samplers=0, sampler_steps=0):
         """In-flight batching (fdm_slots_open): `slots` slots of up to L latent frames, each a clip at its own step of ONE shared
         sampler -- kind "ddim" with `steps`, "ddpm" over t_list, or "tables" over t_list with `tables` [4, len(t_list)]
         (sample_tables).  Every slot starts idle; admit() / run() / slot_state() / read_slot() drive them.  Returns the number of
         steps of a chain.  long_frames / long_groups > 0 reserve capacity for long requests (admit_long): an arena of long_frames
-        latent frames and long_groups group descriptors; 0 = the plain slot program."""
+        latent frames and long_groups group descriptors; 0 = the plain slot program.
+        samplers / sampler_steps > 0 reserve a sampler BANK: `samplers` definitions beyond this one (sampler 0), holding
+        `sampler_steps` steps in all (add_sampler); every admit then names its sampler and, with cfg, its own cfg_scale."""
         a = SampleArgs()
         a.cfg_scale, a.eager, a.graph_steps = float(cfg_scale), int(not use_graph), int(graph_steps)
-        held = None
-        if kind == "ddim":
-            a.kind, a.ddim_steps = 1, int(steps)
-        elif kind == "ddpm":
-            held = (C.c_int * len(t_list))(*[int(t) for t in t_list])
-            a.kind, a.t_list, a.n_steps = 0, C.cast(held, C.c_void_p), len(t_list)
-        elif kind == "tables":
-            held = self._tables_args(a, t_list, tables)
-        else:
-            raise FdmError(f"kind {kind!r} (ddpm | ddim | tables)")
+        held = self._sampler_args(a, kind, steps, t_list, tables)
         self.set("slot_long_frames", int(long_frames))
         self.set("slot_long_groups", int(long_groups))
+        self.set("slot_samplers", int(samplers))
+        self.set("slot_sampler_steps", int(sampler_steps))
         with torch.cuda.device(self.device):
             check(lib().fdm_slots_open(self.h, int(slots), int(L), int(bool(cfg)), C.byref(a), _stream()))
         del held
-        self._slot_inputs = {}
+        self._slot_inputs, self._slot_scale = {}, float(cfg_scale)
         self.B, self.L, self.M, self.cfg, self.S = int(slots), int(L), int(slots) * int(L), bool(cfg), 1
         return self.slot_state(0)[1]
 
-    def admit(self, slot, hub, style, emo=None, x_T=None, L=None, seed=0, clip_id=0):
+    def add_sampler(self, kind, steps=None, t_list=None, tables=None):
+        """fdm_slot_sampler_add: one more sampler definition into the bank, between steps (kind / steps / t_list / tables as
+        open_slots).  Returns its id >= 1; FdmError with code -4 when the bank has no room (the plan is untouched).  Drains the stream once."""
+        a = SampleArgs()
+        held = self._sampler_args(a, kind, steps, t_list, tables)
+        with torch.cuda.device(self.device):
+            rc = lib().fdm_slot_sampler_add(self.h, C.byref(a), _stream())
+        del held
+        if rc < 0:
+            check(rc)
+        return rc
+
+    def drop_sampler(self, id):
+        """fdm_slot_sampler_drop: frees a bank row; FdmError -4 while a running or unread slot names it, -1 for id 0 / unknown."""
+        check(lib().fdm_slot_sampler_drop(self.h, int(id)))
+
+    def sampler_info(self, id):
+        """fdm_slot_sampler_info: (kind 0 DDPM / 1 DDIM / 2 table-driven, steps of a chain) of a bank row (host only)."""
+        k, n = C.c_int(), C.c_int()
+        check(lib().fdm_slot_sampler_info(self.h, int(id), C.byref(k), C.byref(n)))
+        return k.value, n.value
+
+    def admit(self, slot, hub, style, emo=None, x_T=None, L=None, seed=0, clip_id=0, sampler=0, cfg_scale=None):
         """fdm_slot_admit: one clip into an idle slot, between steps.  hub [N, fw] (or [1, N, fw]) audio-encoder features, style
         [n_style], emo [n_emo], x_T [L_clip*G, c] (or [1, ...]); L = latent frames of the clip (default N // pair).  Its latent will
-        equal the solo sample_* call on a (1, L_clip) plan with the same x_T, seed and clip0 = clip_id."""
+        equal the solo sample_* call on a (1, L_clip) plan with the same x_T, seed and clip0 = clip_id -- with the sampler the
+        request names (a bank id; 0 = the session's) and its cfg_scale (None = the session's)."""
         p, dv = self.p, self.device
         hub = _dev(hub, dv).reshape(-1, hub.shape[-1])
         N, fw = hub.shape
@@ -357,12 +388,17 @@ class DenoiserPlan:
         if x.numel() != L * p.d:
             raise FdmError(f"x_T has {x.numel()} elements, expected L_clip*G*c = {L * p.d}")
         with torch.cuda.device(dv):
-            check(lib().fdm_slot_admit(self.h, int(slot), hub.data_ptr(), N, fw, style.data_ptr(), emo.data_ptr() if emo is not None else None,
-                                       L, x.data_ptr(), int(seed), int(clip_id), _stream()))
+            if sampler == 0 and cfg_scale is None:
+                check(lib().fdm_slot_admit(self.h, int(slot), hub.data_ptr(), N, fw, style.data_ptr(), emo.data_ptr() if emo is not None else None,
+                                           L, x.data_ptr(), int(seed), int(clip_id), _stream()))
+            else:
+                scale = self._slot_scale if cfg_scale is None else float(cfg_scale)
+                check(lib().fdm_slot_admit_as(self.h, int(slot), hub.data_ptr(), N, fw, style.data_ptr(), emo.data_ptr() if emo is not None else None,
+                                              L, x.data_ptr(), int(seed), int(clip_id), int(sampler), scale, _stream()))
         self._slot_inputs[int(slot)] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the slot is admitted again
         return L
 
-    def admit_long(self, slots, hub, style, emo=None, x_T=None, L_total=None, overlap=60, seed=0, clip_id=0):
+    def admit_long(self, slots, hub, style, emo=None, x_T=None, L_total=None, overlap=60, seed=0, clip_id=0, sampler=0, cfg_scale=None):
         """fdm_slot_admit_long: a recording of L_total > L latent frames into the idle slots `slots`, one window each (slots[0] leads
         the group); len(slots) must be the window count of window_starts(L_total, L, overlap).  hub [N, fw] (or [1, N, fw]) features
         of the whole recording, x_T [L_total*G, c] (or [1, ...]).  Its latent will equal sample_windows on a B = 1 windowed plan
@@ -378,9 +414,15 @@ class DenoiserPlan:
             raise FdmError(f"x_T has {x.numel()} elements, expected L_total*G*c = {L_total * p.d}")
         ids = (C.c_int * len(slots))(*[int(s) for s in slots])
         with torch.cuda.device(dv):
-            check(lib().fdm_slot_admit_long(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, style.data_ptr(),
-                                            emo.data_ptr() if emo is not None else None, L_total, int(overlap), x.data_ptr(),
-                                            int(seed), int(clip_id), _stream()))
+            if sampler == 0 and cfg_scale is None:
+                check(lib().fdm_slot_admit_long(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, style.data_ptr(),
+                                                emo.data_ptr() if emo is not None else None, L_total, int(overlap), x.data_ptr(),
+                                                int(seed), int(clip_id), _stream()))
+            else:      # the request's own sampler (a bank id) and cfg_scale (None = the session's)
+                scale = self._slot_scale if cfg_scale is None else float(cfg_scale)
+                check(lib().fdm_slot_admit_long_as(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, style.data_ptr(),
+                                                   emo.data_ptr() if emo is not None else None, L_total, int(overlap), x.data_ptr(),
+                                                   int(seed), int(clip_id), int(sampler), scale, _stream()))
         self._slot_inputs[int(slots[0])] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the leader's slot is admitted again
         return L_total
 

@@ -212,6 +212,35 @@ def slot_group_sched(mode, x0, x, x_out, n, state, keys, n_slots, *, member, fra
     check(lib().fdm_op_slot_group_sched(C.byref(a), _p(state), _p(keys), n_slots, C.byref(g), stream()))
 
 
+def bank_args(req, desc, t, coef):
+    """fdm_slot_bank_args: req int32 [n_slots, 4] = {sampler, cfg_scale bits, 0, 0}, desc int32 [n_samplers, 4] = {mode, n_steps, t_off,
+    c_off}, t int32 [n_t], coef fp32 [n_coef] (device; the layout is in include/fdm_hip.h)."""
+    b = _lib.SlotBankArgs()
+    b.req, b.desc, b.t, b.coef = _p(req), _p(desc), _p(t), _p(coef)
+    b.n_samplers, b.n_t, b.n_coef = desc.shape[0], t.numel(), coef.numel()
+    return b
+
+
+def slot_sched_bank(x0, x, x_out, n, state, keys, n_slots, *, req, desc, t, coef, **kw):
+    """fdm_op_slot_sched_bank: slot_sched with every slot's mode, step tables and cfg_scale read from its request row and the bank
+    (bank_args); kw carries the t-indexed tables (c1 / c2 / sigma, sra / srm1), x0u, x_out_t, x0_hist, n_per_clip."""
+    a = sched_args(0, x0, x, x_out, n, **kw)
+    b = bank_args(req, desc, t, coef)
+    check(lib().fdm_op_slot_sched_bank(C.byref(a), _p(state), _p(keys), n_slots, C.byref(b), stream()))
+
+
+def slot_group_sched_bank(x0, x, x_out, n, state, keys, n_slots, *, req, desc, t, coef, member, frames, entries, groups, x_long, hist_long=None,
+                          L, d, frame0=0, frame1=None, plain=1, init=0, **kw):
+    """fdm_op_slot_group_sched_bank: slot_group_sched with the bank (a group reads its leader's request row)."""
+    a = sched_args(0, x0, x, x_out, n, **kw)
+    g = _lib.SlotGroupArgs()
+    g.member, g.frames, g.entries, g.groups, g.x_long, g.hist_long = _p(member), _p(frames), _p(entries), _p(groups), _p(x_long), _p(hist_long)
+    g.arena_frames, g.n_entries, g.n_groups, g.L, g.d = frames.shape[0], entries.shape[0], groups.shape[0], L, d
+    g.frame0, g.frame1, g.plain, g.init = frame0, frames.shape[0] if frame1 is None else frame1, plain, init
+    b = bank_args(req, desc, t, coef)
+    check(lib().fdm_op_slot_group_sched_bank(C.byref(a), _p(state), _p(keys), n_slots, C.byref(g), C.byref(b), stream()))
+
+
 def cast(src, dst):
     check(lib().fdm_op_cast(_p(src), _p(dst), src.numel(), code_of(dst), stream()))
 

@@ -292,7 +292,7 @@ class SlotServer:
     step boundary and leaves when its own chain ends; its result equals animate() on that audio alone with the same arguments
     (torch.equal on latent and vertices: DDIM, DDPM -- clip id 0, as the solo call keys its noise -- and sampler=).
 
-    One sampler per server, chosen as animate() chooses it: sampler= ("dpmpp2m" | "ddim_eta" with eta=, sampler_steps), else
+    One sampler per server (more with a sampler bank, below), chosen as animate() chooses it: sampler= ("dpmpp2m" | "ddim_eta" with eta=, sampler_steps), else
     ddim_steps (presets without an emotion input), else the DDPM chain.  Guidance when `diffusion` wraps a
     ClassifierFreeSampleModel.  max_frames: latent frames a slot holds (default the model's max_len); a longer clip is refused.
     The server owns the model's plan while it runs: an animate*() call on the same model returns the plan to plain mode and the
@@ -304,10 +304,18 @@ class SlotServer:
     max_frames frames per slot overlapping by >= `overlap`, blended every step as animate_long blends them.  Its result equals
     animate_long(..., window=max_frames, overlap=overlap) with the server's sampler and the same seed (torch.equal).  The queue is
     strictly first in, first out: a long request that does not fit yet waits at the head and nothing behind it is admitted, so it
-    cannot starve.  long_frames = 0 (default): the plain slot program, and submit_long refuses what needs a group."""
+    cannot starve.  long_frames = 0 (default): the plain slot program, and submit_long refuses what needs a group.
+
+    Samplers per request: samplers > 0 reserves a sampler bank of that many definitions beyond the server's own, holding
+    bank_steps steps in all (DenoiserPlan.open_slots; the name sampler_steps= is taken: it is the step count of sampler=).  submit / submit_many / submit_long then take ddim_steps= / sampler= /
+    sampler_steps= / eta= per request, resolved exactly as animate() resolves them (a request that names none gets the server's
+    sampler), and cfg_scale= under guidance (None = the model's level).  The server keeps a {definition: bank id} map; when the
+    bank is full it drops the least recently used sampler no slot holds, and if none can go the request waits at the head of the
+    queue like a long request that does not fit.  Every result equals animate() / animate_long() with the same arguments and seed.
+    samplers = 0 (default): the single-sampler slot program; a request that names another sampler is refused (ValueError)."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
-                 device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60):
+                 device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0):
         from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
@@ -325,15 +333,79 @@ class SlotServer:
             if not 0 <= self.overlap < self.L:
                 raise ValueError(f"overlap {self.overlap} outside [0, max_frames {self.L})")
             kw.update(long_frames=self.long_frames, long_groups=int(long_groups))
-        if sampler:
-            t_list, tables = schedule.sampler_tables(sampler, sampler_steps, eta, diffusion.num_timesteps)
-            self.chain = self.plan.open_slots(self.n_slots, self.L, "tables", t_list=t_list, tables=tables, **kw)
-        elif ddim_steps and not p.n_emo:
-            self.chain = self.plan.open_slots(self.n_slots, self.L, "ddim", steps=ddim_steps, **kw)
-        else:
-            ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
-            self.chain = self.plan.open_slots(self.n_slots, self.L, "ddpm", t_list=ts, **kw)
+        self.bank_samplers, self.bank_steps = int(samplers), int(bank_steps)
+        if self.bank_samplers and self.bank_steps:
+            kw.update(samplers=self.bank_samplers, sampler_steps=self.bank_steps)
+        self.scale = kw["cfg_scale"]
+        self.default = self._definition(ddim_steps, sampler, sampler_steps, eta)
+        self.chain = self.plan.open_slots(self.n_slots, self.L, **self._definition_args(self.default), **kw)
+        self._defs, self._lru = {self.default: 0}, []        # definition -> bank id; ids beyond 0, least recently used first
         self._next, self._queue, self._slot, self._done = 0, [], [None] * self.n_slots, []
+
+    def _definition(self, ddim_steps, sampler, sampler_steps, eta):
+        """A sampler definition (hashable), chosen as animate() chooses it."""
+        if sampler:
+            return ("tables", str(sampler), int(sampler_steps), float(eta))
+        if ddim_steps and not self.p.n_emo:
+            return ("ddim", int(ddim_steps))
+        return ("ddpm",)
+
+    def _definition_args(self, key):
+        """open_slots / add_sampler arguments of a definition."""
+        from . import schedule
+        if key[0] == "tables":
+            t_list, tables = schedule.sampler_tables(key[1], key[2], key[3], self.diffusion.num_timesteps)
+            return dict(kind="tables", t_list=t_list, tables=tables)
+        if key[0] == "ddim":
+            return dict(kind="ddim", steps=key[1])
+        ts = list(range(self.diffusion.num_timesteps - 1, -1, -1)) if self.diffusion.full_chain else list(range(999, 499, -1))
+        return dict(kind="ddpm", t_list=ts)
+
+    def _request(self, ddim_steps, sampler, sampler_steps, eta, cfg_scale):
+        """(definition, cfg_scale) of a request; (None, None) = it names nothing: the server's sampler and scale, admitted as before.
+        ValueError for what can never fit: another sampler or scale without a bank, or more steps than the bank holds."""
+        if ddim_steps is None and sampler is None and cfg_scale is None:
+            return None, None
+        key = self.default if (ddim_steps is None and sampler is None) else \
+            self._definition(ddim_steps, sampler, 20 if sampler_steps is None else sampler_steps, 0.0 if eta is None else eta)
+        scale = None if (cfg_scale is None or not self.cfg) else float(cfg_scale)
+        if key == self.default and (scale is None or scale == self.scale):
+            return None, None
+        if not (self.bank_samplers and self.bank_steps):
+            raise ValueError(f"request with sampler {key} / cfg_scale {cfg_scale}: this server was opened without a sampler bank (samplers=, bank_steps=)")
+        if key not in self._defs:
+            a = self._definition_args(key)
+            from . import schedule
+            n = sum(1 for pr in schedule.ddim_time_pairs(a["steps"]) if pr[1] >= 0) if a["kind"] == "ddim" else len(a["t_list"])
+            if n < 1 or n > self.bank_steps:
+                raise ValueError(f"sampler {key} has {n} steps, the server's bank holds [1, {self.bank_steps}] (bank_steps=)")
+        return key, scale
+
+    def _sampler_id(self, key):
+        """The bank id of a definition, added on first use.  A full bank drops its least recently used sampler that no slot holds;
+        None = nothing can be dropped yet: the request waits."""
+        from ._lib import FdmError
+        if key in self._defs:
+            sid = self._defs[key]
+        else:
+            while True:
+                try:
+                    sid = self.plan.add_sampler(**self._definition_args(key))
+                    break
+                except FdmError as e:
+                    if getattr(e, "code", None) != -4:
+                        raise
+                held = {r["sid"] for r in self._slot if r is not None}
+                victim = next((i for i in self._lru if i not in held), None)
+                if victim is None:
+                    return None
+                self.plan.drop_sampler(victim)
+                self._lru.remove(victim)
+                self._defs = {k: v for k, v in self._defs.items() if v != victim}
+            self._defs[key] = sid
+        if sid:
+            self._lru = [i for i in self._lru if i != sid] + [sid]
+        return sid
 
     def _check(self):
         from ._lib import FdmError
@@ -341,10 +413,13 @@ class SlotServer:
             raise FdmError("SlotServer: the model's plan left slot mode (another sampling call used it)")
 
     @torch.no_grad()
-    def submit(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0):
+    def submit(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
+               sampler_steps=None, eta=None, cfg_scale=None):
         """One processor-normalised waveform [n] -> a handle.  Runs the audio encoder at the clip's own length, draws x_T as
-        animate() does and admits the clip, or queues it until a slot is free."""
+        animate() does and admits the clip, or queues it until a slot is free.  ddim_steps / sampler / sampler_steps / eta /
+        cfg_scale: the request's own sampler and guidance scale (class docstring); none given = the server's."""
         self._check()
+        key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
         p, dev = self.p, self.device
         wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
         hub = self.model.audio_encoder(wav).last_hidden_state
@@ -359,19 +434,22 @@ class SlotServer:
         x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
         h = self._next
         self._next += 1
-        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template))
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, sampler=key, scale=scale))
         self._fill()
         return h
 
     @torch.no_grad()
-    def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0):
+    def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0, ddim_steps=None, sampler=None,
+                    sampler_steps=None, eta=None, cfg_scale=None):
         """Several requests at once: ONE audio-encoder call over the waveforms' unequal lengths (encode_many), then each request is
         admitted or queued exactly as submit() does it, in the given order.  templates / id_one_hots / emotion_one_hots / seeds:
-        one per request (lists) or one for all.  Returns the handles; results equal submit() in a loop bit for bit."""
+        one per request (lists) or one for all, and so are ddim_steps / sampler / sampler_steps / eta / cfg_scale (submit()).
+        Returns the handles; results equal submit() in a loop bit for bit."""
         self._check()
         p, dev = self.p, self.device
         n = len(audios)
         per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
+        reqs = [self._request(per(ddim_steps, b), per(sampler, b), per(sampler_steps, b), per(eta, b), per(cfg_scale, b)) for b in range(n)]
         hubs = self.model.audio_encoder.encode_many([torch.as_tensor(a, dtype=torch.float32).reshape(-1) for a in audios], dev)
         Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
         for L in Ls:
@@ -388,34 +466,39 @@ class SlotServer:
             x_T = torch.randn((1, Ls[b] * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
             h = self._next
             self._next += 1
-            self._queue.append(dict(handle=h, hub=hubs[b], L=Ls[b], ids=ids.to(dev), emo=emo, x_T=x_T, seed=seed, template=per(templates, b)))
+            self._queue.append(dict(handle=h, hub=hubs[b], L=Ls[b], ids=ids.to(dev), emo=emo, x_T=x_T, seed=seed, template=per(templates, b),
+                                    sampler=reqs[b][0], scale=reqs[b][1]))
             handles.append(h)
         self._fill()
         return handles
 
     def _fill(self):
         """Admit from the head of the queue while the head fits: a plain request needs one idle slot (the lowest), a long one needs
-        its window count in idle slots, an arena range and a descriptor (FDM_ERR_STATE from admit_long = not yet).  Nothing passes a
-        request that waits."""
+        its window count in idle slots, an arena range and a descriptor (FDM_ERR_STATE from admit_long = not yet); a request with
+        its own sampler also needs that sampler in the bank (_sampler_id).  Nothing passes a request that waits."""
         from ._lib import FdmError
         while self._queue:
             r = self._queue[0]
             free = [s for s in range(self.n_slots) if self._slot[s] is None]
-            if r.get("windows"):
-                if len(free) < r["windows"]:
+            if len(free) < max(r.get("windows", 0), 1):
+                return
+            own, r["sid"] = {}, 0          # a request that names nothing is admitted exactly as before
+            if r.get("sampler") is not None or r.get("scale") is not None:
+                r["sid"] = self._sampler_id(r["sampler"])
+                if r["sid"] is None:       # the bank is full of samplers in use: wait for a slot to leave
                     return
+                own = dict(sampler=r["sid"], cfg_scale=r["scale"])
+            if r.get("windows"):
                 try:
                     self.plan.admit_long(free[:r["windows"]], r["hub"], r["ids"], r["emo"], r["x_T"], L_total=r["L"], overlap=self.overlap,
-                                         seed=r["seed"], clip_id=0)
+                                         seed=r["seed"], clip_id=0, **own)
                 except FdmError as e:
                     if getattr(e, "code", None) == -4:       # arena or descriptors busy: the plan is untouched, wait for a group to leave
                         return
                     raise
                 r["slots"] = free[:r["windows"]]
             else:
-                if not free:
-                    return
-                self.plan.admit(free[0], r["hub"], r["ids"], r["emo"], r["x_T"], L=r["L"], seed=r["seed"], clip_id=0)
+                self.plan.admit(free[0], r["hub"], r["ids"], r["emo"], r["x_T"], L=r["L"], seed=r["seed"], clip_id=0, **own)
                 r["slots"] = free[:1]
             self._queue.pop(0)
             r.pop("hub"), r.pop("x_T")
@@ -423,13 +506,16 @@ class SlotServer:
                 self._slot[s] = r
 
     @torch.no_grad()
-    def submit_long(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0):
+    def submit_long(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
+                    sampler_steps=None, eta=None, cfg_scale=None):
         """One processor-normalised waveform [n] of ANY length -> a handle.  The audio encoder runs over the whole waveform and
         L_total = frames // pair is kept whole (submit() crops to a slot).  L_total <= max_frames is an ordinary request; a longer
         one becomes a group of slots (class docstring) with x_T drawn as animate_long draws it.  ValueError if the request can
-        never fit: more windows than slots, or L_total > long_frames."""
+        never fit: more windows than slots, or L_total > long_frames.  ddim_steps / sampler / sampler_steps / eta / cfg_scale as
+        submit(): the result equals animate_long() with them."""
         from .denoiser import window_starts
         self._check()
+        key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
         p, dev = self.p, self.device
         wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
         hub = self.model.audio_encoder(wav).last_hidden_state
@@ -451,7 +537,8 @@ class SlotServer:
         x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
         h = self._next
         self._next += 1
-        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, windows=windows))
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, windows=windows,
+                                sampler=key, scale=scale))
         self._fill()
         return h
 

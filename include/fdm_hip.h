@@ -142,6 +142,28 @@ typedef struct fdm_slot_group_args {
 } fdm_slot_group_args;
 int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
                             const fdm_slot_group_args* g, void* stream);
+/* The two passes above with a SAMPLER BANK (fdm_slot_sampler_add): every slot names its own sampler and guidance scale.  b points at
+ * device tables:
+ *   req     [n_slots] 16-byte rows {int sampler, float cfg_scale, int 0, int 0}: the request a slot runs
+ *   desc    [n_samplers] 16-byte rows {int mode (0 DDPM / 1 DDIM / 3 table-driven), int n_steps, int t_off, int c_off}; n_steps = 0: free
+ *   t       [n_t] ints: the timesteps of sampler i are t[t_off .. t_off + n_steps) (read by the advance launch of the slot program)
+ *   coef    [n_coef] fp32, indexed by the STEP k from c_off:  mode 1: sqrt_an[n_steps] | c_n[n_steps];  mode 3: a[n_steps] | b[n_steps] |
+ *           c[n_steps] | s[n_steps];  mode 0: nothing -- its tables (a->c1 / c2 / sigma) are indexed by t and shared, as are a->sra / srm1
+ * a->mode, a->cfg_scale, a->sqrt_an / c_n and a->lm_* are NOT read.  A live slot gets fdm_op_slot_sched's update with mode, step tables
+ * and cfg_scale of ITS request: the bits of fdm_op_sched_step on the slot's slice with that mode, those tables, step k, seed, clip id
+ * and scale.  A group (fdm_op_slot_group_sched_bank) reads its LEADER's request row.  Mode 3 uses the slot's x0_hist rows (a group's
+ * hist_long range) as before; modes 0 and 1 never touch them.  Every field of a request row and of a descriptor is checked against
+ * n_samplers / n_t / n_coef (and k against n_steps, t against [0, 1000), the mode's shared tables against NULL) before it becomes an
+ * index: a slot with a bad row stores nothing.  req and desc must be 16-byte aligned. */
+typedef struct fdm_slot_bank_args {
+  const void* req; const int* desc; const int* t; const float* coef;
+  int n_samplers, n_t, n_coef;
+  int reserved;
+} fdm_slot_bank_args;
+int fdm_op_slot_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                           const fdm_slot_bank_args* b, void* stream);
+int fdm_op_slot_group_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                                 const fdm_slot_group_args* g, const fdm_slot_bank_args* b, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * C[M,N] = epilogue(A[M,K] * W[N,K]^T): every nn.Linear / Conv1d-as-GEMM on the path
@@ -632,6 +654,41 @@ int fdm_slot_read_long(fdm_plan* p, int leader, float* out, void* stream);
  * FDM_ERR_SHAPE: L_total <= L, n != the window count.  fdm_slot_admit_long builds its tables with this function. */
 int fdm_slot_group_table_host(int L_total, int L, int overlap, const int* slots, int n, int* off, int* ent_slot, int* ent_start,
                               float* ent_wt, int cap);
+/* Samplers per request in slot mode: a plan in slot mode owns a BANK of sampler definitions, and every admitted request names one
+ * (and, on a guidance plan, its own cfg_scale) -- a 10-step preview, a 100-step DDIM final and a DDPM chain share one step program.
+ *   rule     sampler 0 is the one given to fdm_slots_open; further samplers are added (and dropped) between steps with the calls below.
+ *            The guarantee of "Slots" and "Long requests" holds PER REQUEST: a slot's latent is bit for bit fdm_sample_graph on a
+ *            (1, L_clip) plan with that request's sampler and scale (same x_T, seed, clip0 = clip_id), a group's latent bit for bit
+ *            fdm_sample_windows with them -- in every arithmetic mode, whatever the other slots run.  Why: the denoiser chain reads only
+ *            the slot's t word; the sampler is read by the advance launch (n_steps, timestep list) and by the scheduler pass (mode,
+ *            step tables, scale), and both take them from the slot's own request row (fdm_slot_bank_args).
+ *   capacity fdm_plan_set(p, "slot_samplers", S) = bank rows beyond sampler 0, (p, "slot_sampler_steps", N) = total steps those rows
+ *            may hold, both BEFORE fdm_slots_open and both default 0 = no bank: the recorded program, its kernels, its launch count and
+ *            its cache key are exactly those of a plan without this feature.  With both > 0 fdm_slots_open reserves the request rows,
+ *            1 + S descriptors, n_steps(sampler 0) + N timesteps and four coefficients per step, and the step program records the bank
+ *            forms of the advance launch and of the scheduler pass: the same launch count, its own cache key.  fdm_plan_get reads both
+ *            keys back (a build without the feature does not know them).
+ * fdm_slot_sampler_add: reads only kind, t_list / n_steps, ddim_steps and lm_tables of `sampler` (noise or record given: FDM_ERR_ARG);
+ *   builds the tables as a sampling call does (kind 1: fdm_ddim_schedule_host, the dead last pair skipped), takes a descriptor, a
+ *   timestep range and a coefficient range by first fit, uploads them and DRAINS THE STREAM ONCE (the tables are host memory of the
+ *   call).  Legal between any two fdm_slots_run calls while slots are mid-chain.  Returns the sampler's id >= 1, or FDM_ERR_STATE when
+ *   nothing fits (no bank, no free descriptor or range: the plan is untouched), FDM_ERR_ARG for a bad definition.
+ * fdm_slot_sampler_drop: frees the descriptor and its ranges.  FDM_ERR_STATE while a running or finished-and-unread slot names the
+ *   sampler; FDM_ERR_ARG for id 0 or an unknown id.
+ * fdm_slot_sampler_info (host only): kind (0 / 1 / 2 as fdm_sample_args.kind) and steps of a chain; outputs untouched on error.
+ * fdm_slot_admit_as / fdm_slot_admit_long_as: fdm_slot_admit / fdm_slot_admit_long plus the request's sampler and cfg_scale (ignored on a
+ *   plan opened without guidance).  The slot's t word starts at the first timestep of ITS sampler.  An unknown sampler: FDM_ERR_ARG,
+ *   nothing changed; without a bank only sampler 0 with the open's scale is accepted.  fdm_slot_admit / fdm_slot_admit_long are
+ *   unchanged: on any plan they mean sampler 0 with the open's cfg_scale.  fdm_slots_run advances every slot to min(its own total,
+ *   done + n) and fdm_slot_state reports the slot's own steps_total (an idle slot: sampler 0's). */
+int fdm_slot_sampler_add(fdm_plan* p, const fdm_sample_args* sampler, void* stream);
+int fdm_slot_sampler_drop(fdm_plan* p, int id);
+int fdm_slot_sampler_info(fdm_plan* p, int id, int* kind, int* n_steps);
+int fdm_slot_admit_as(fdm_plan* p, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                      const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream);
+int fdm_slot_admit_long_as(fdm_plan* p, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                           int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale,
+                           void* stream);
 /* Plan-time tuning of the GEMM output tiles at the prepared shape (times candidates per call site; changes speed only, every
  * tile accumulates k in the same order).  This call is the ONLY place the library tunes by itself: request paths
  * (fdm_audio_prepare*, fdm_sample_graph) never do -- fdm_plan_get(p, "needs_tune") turns 1 once the prepared shape has served
@@ -646,10 +703,11 @@ int fdm_slot_group_table_host(int L_total, int L, int overlap, const int* slots,
  * FDM_GEMM_LOCKSTEP=1 = FDM_TILE_LOCKSTEP for every fdm_op_gemm of the process (A/B of the once-per-clip stages; the step has fdm_plan_set "lockstep"). */
 int fdm_plan_tune(fdm_plan* p, void* stream);
 /* Introspection / experiments: integer properties by name -- "launches_per_step", "graph_launches" (host graph launches of
- * the last fdm_sample_graph / fdm_slots_run), "rows", "slots", "slot_long_frames", "slot_long_groups", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
+ * the last fdm_sample_graph / fdm_slots_run), "rows", "slots", "slot_long_frames", "slot_long_groups", "slot_samplers", "slot_sampler_steps", "tuned", "needs_tune", "tune_failed", "fuse_ln3", "tile.<call site>" (qkv, out, ffn1, ffn2,
  * enc, dec, ...). */
 int fdm_plan_get(fdm_plan* p, const char* key, long long* out);
 /* "slot_long_frames" / "slot_long_groups" (long capacity of the NEXT fdm_slots_open, see fdm_slot_admit_long),
+ * "slot_samplers" / "slot_sampler_steps" (bank capacity of the NEXT fdm_slots_open, see fdm_slot_sampler_add),
  * "tile.<call site>" (drops recorded programs), "tune" (0 = off), "tune_lazy" (1 = in-call tuning allowed), "untune" (forget every
  * tuned set), "fuse_ln3" (1 = fold norm3 into the GEMMs around it: 8 launches fewer per step, no longer faster; takes effect at
  * the next commit) */
