@@ -19,8 +19,9 @@ The epilogue forms kept exact: bias add, ReLU, LeakyReLU(0.2) (one fp32 product 
 both sides; leaky cases carry no residual, so no second rounding and no fused multiply-add can differ), residual add, the
 operand-kind copy (round to nearest even: torch's CPU casts; the split kind as store_opnd4 does it: hi = half(x),
 lo = half((x - hi) * 2048)), packed K / V (attn_cases.pack_host of the exact values), stat_out (integer sums and sums of
-squares below 2^24) and ksplit planes.  Mish, the GELUs, the LayerNorm folds and the fused scheduler are not exact arithmetic
-and stay with the tests they have."""
+squares below 2^24) and ksplit planes.  Mish and the GELUs are not exact arithmetic: tests/epilogue_cases.py bounds them per
+element on these operands, and the LayerNorm folds on exact rows of their own.  The fused scheduler is compared bit for bit
+with GEMM + fdm_op_sched_step in tests/test_ops_gpu.py (modes 0, 1 and 3)."""
 import functools
 import zlib
 from collections import namedtuple
@@ -78,7 +79,7 @@ class Case(namedtuple("Case", "name M N ku K bias resid act out lda ldo ldr rmod
     S: ksplit.  kv: (B, H, L, hd) of a QKV projection with packed K / V.  stat: stat_out.  wden: one W entry in wden is
     non-zero.  lo: "rand" | "zero" (split kind's lo planes).  values: "random" | "unique" (A holds position-dependent values
     and every W row one 1: each output is a copy of one A element) | "round" (outputs of thousands: the operand-kind copy has
-    to round)."""
+    to round) | "rowcol" / "row" (acc[m, n] = I_m + J_n / = I_m: the known pre-activation values of tests/epilogue_cases.py)."""
 
     @property
     def id(self):
@@ -186,6 +187,22 @@ def problem(kind, case):
         W[0, p.w_idx] = (mask * s.view(1, K)).expand(G, N, K)
         A[1, p.a_idx] = _randint(gen, -2, 2, (C, G, M, K))
         W[1, p.w_idx] = _randint(gen, -2, 2, (G, N, K))
+    elif case.values in ("rowcol", "row"):
+        # acc[m, n] = I_m + J_n (tests/epilogue_cases.py): the first half of K carries I_m against one 1 per W row (at another k
+        # per row), the second half ones against W in {-1, 0, 1} whose row sum is J_n ("row": +1 -1 pairs, J_n = 0, products live)
+        assert case.lo == "zero" and K % 4 == 0
+        h = K // 2
+        i_m = (torch.arange(M) % 49 - 24).float()
+        if case.values == "row":
+            i_m = torch.where(torch.arange(M) % 3 == 0, torch.zeros(M), i_m)
+        A[0, p.a_idx] = torch.cat([i_m.view(M, 1).expand(M, h), torch.ones(M, K - h)], 1).expand(C, G, M, K)
+        wv = torch.zeros(G, N, K)
+        wv[:, torch.arange(N), (5 * torch.arange(N)) % h] = 1.0
+        if case.values == "row":
+            wv[:, :, h:] = torch.tensor([1.0, -1.0]).repeat((K - h) // 2)
+        else:
+            wv[:, :, h:] = _randint(gen, -1, 1, (G, N, K - h))
+        W[0, p.w_idx] = wv
     else:
         A[0, p.a_idx] = _randint(gen, -2, 2, (C, G, M, K))
         wv = _randint(gen, -1, 1, (G, N, K))

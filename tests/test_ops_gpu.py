@@ -784,6 +784,42 @@ def test_gemm_fused_scheduler_equals_gemm_then_sched_step(dtype, mode):
         assert torch.equal(xf, ref) and torch.equal(xf_t, ref_t), (mode, k)
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_gemm_fused_table_scheduler_equals_gemm_then_sched_step(dtype):
+    """The same equality for the table-driven form (fdm_sched_args.mode 3, the GEMM_LM kernels): x_out, its operand copy and the
+    rewritten x0_hist, at step 0 (c[0] = 0: no history read), a middle step (history and Philox noise) and the last step (s = 0),
+    on the heuristic's tile and on FDM_TILE_256x128_PP.  A small shape the fused form takes: N = 128, one whole column tile of
+    either kernel (the fused form has the lean epilogue only: it needs whole column tiles and skips the rows past M = 80)."""
+    from fdm_amd._lib import TILE_256x128_PP
+    g = torch.Generator().manual_seed(31)
+    td = ops.tdtype(dtype)
+    B, L, d, K = 2, 40, 128, 64
+    M = B * L
+    A = torch.randn(M, K, generator=g).to(td).to(DEV)
+    W = (torch.randn(d, K, generator=g) / math.sqrt(K)).to(td).to(DEV)
+    bias = torch.randn(d, generator=g).to(DEV)
+    x = torch.randn(M, d, generator=g).to(DEV)
+    hist0 = torch.randn(M, d, generator=g).to(DEV)
+    lm_a, lm_b = (torch.rand(3, generator=g) + 0.1).to(DEV), (torch.rand(3, generator=g) + 0.1).to(DEV)
+    lm_c, lm_s = torch.tensor([0.0, 0.3, -0.2], device=DEV), torch.tensor([0.5, 0.4, 0.0], device=DEV)
+    tseq = torch.tensor([999, 500, 0], dtype=torch.int32, device=DEV)
+    x0 = torch.zeros(M, d, device=DEV)
+    ops.gemm(A, W, M, d, K, bias=bias, out_f32=x0)
+    for k in range(3):
+        step = torch.tensor([k, 0], dtype=torch.int32, device=DEV)
+        kw = dict(n_per_clip=L * d, tseq=tseq, step=step, seed=99, clip0=4, lm_a=lm_a, lm_b=lm_b, lm_c=lm_c, lm_s=lm_s)
+        ref, ref_t, ref_h = torch.zeros(M, d, device=DEV), torch.zeros(M, d, device=DEV, dtype=td), hist0.clone()
+        ops.sched_step(3, x0, x, ref, M * d, x_out_t=ref_t, x0_hist=ref_h, **kw)
+        torch.cuda.synchronize()
+        assert torch.equal(ref_h, x0) and not torch.equal(ref, x0), k          # (the history is rewritten; the update is not the identity)
+        for tile in (0, TILE_256x128_PP):
+            xf, xf_t, xf_h = x.clone(), torch.zeros(M, d, device=DEV, dtype=td), hist0.clone()
+            ops.gemm(A, W, M, d, K, bias=bias, resid=xf, out_f32=xf, out_t=xf_t, tile=tile,
+                     sched=ops.sched_args(3, None, None, None, M * d, x0_hist=xf_h, **kw))
+            torch.cuda.synchronize()
+            assert torch.equal(xf, ref) and torch.equal(xf_t, ref_t) and torch.equal(xf_h, ref_h), (k, tile)
+
+
 def test_specialised_and_general_gemm_kernels_agree_bitwise():
     """The GEMM dispatch picks kernels specialised by what a launch can need (lean / packed-KV / LayerNorm-fold epilogues) when
     the host-side predicate says every tile is interior; FDM_TILE_GENERAL or-ed into fdm_gemm_args.tile forces the general
