@@ -356,6 +356,63 @@ __global__ void small_linear_kernel(const float* x, const float* W, const float*
   out[i] = act_apply(acc + (bias ? bias[j] : 0.f), act);
 }
 
+// Condition tracks: the conditioning addend of the denoiser from PER-FRAME style / emotion rows, one launch for every row of one or
+// more clips.  Row r = clip * L + l of `out`:
+//   l <  L_clip:  out[r] = pe[l] + act(W_s style[clip, l] + b_s) (+ W_e emo[clip, l] + b_e); with uncond_off > 0 the uncond half
+//                 out[r + uncond_off / d] = pe[l] + (the same style term) + (W_e 0 + b_e) goes out in the same launch
+//   l >= L_clip:  zeros (both halves): the rows of a slot that belong to no frame
+// Bit rule: every element is what small_linear_kernel followed by add_rows_kernel gives for the row's vectors -- the same fmaf chain
+// over k from a zero accumulator, `acc + bias`, the activation, then (pe + style term) + emotion term, every add rounded on its own.
+// One workgroup per row; the row's vectors go through ONE vector load per element into LDS (never through the scalar data cache:
+// they are the caller's memory), tracks are [clips, L_track, K] and the rows L_clip .. L_track of a clip are never read.
+constexpr int COND_ROWS_MAX_K = 128;
+struct CondRowsArgs {
+  const float* pe; const float* style; const float* emo;
+  const float* sw; const float* sb; const float* ew; const float* eb;
+  float* out; long long uncond_off;
+  int rows, L, L_clip, L_track, d, n_style, n_emo, act;
+};
+__global__ __launch_bounds__(256) void cond_rows_kernel(const CondRowsArgs p) {
+  __shared__ float xs[COND_ROWS_MAX_K], xe[COND_ROWS_MAX_K];
+  const int row = blockIdx.x;
+  if (row >= p.rows) return;
+  const int clip = row / p.L, l = row - clip * p.L;
+  float* o = p.out + (size_t)row * p.d;
+  if (l >= p.L_clip) {
+    for (int j = threadIdx.x; j < p.d; j += 256) {
+      o[j] = 0.f;
+      if (p.uncond_off) o[p.uncond_off + j] = 0.f;
+    }
+    return;
+  }
+  const size_t tr = (size_t)clip * p.L_track + l;
+  const int t = threadIdx.x;
+  if (t < p.n_style) xs[t] = p.style[tr * p.n_style + t];
+  if (p.emo && t < p.n_emo) xe[t] = p.emo[tr * p.n_emo + t];
+  __syncthreads();
+  const float* per = p.pe + (size_t)l * p.d;
+  for (int j = t; j < p.d; j += 256) {
+    float acc = 0.f;
+    for (int k = 0; k < p.n_style; ++k) acc = fmaf(p.sw[(size_t)j * p.n_style + k], xs[k], acc);
+    const float sty = act_apply(__fadd_rn(acc, p.sb ? p.sb[j] : 0.f), p.act);
+    const float v = __fadd_rn(per[j], sty);
+    if (p.emo) {
+      float ae = 0.f, au = 0.f;
+      for (int k = 0; k < p.n_emo; ++k) {
+        const float w = p.ew[(size_t)j * p.n_emo + k];
+        ae = fmaf(w, xe[k], ae);
+        if (p.uncond_off) au = fmaf(w, 0.f, au);      // the null condition is a zero vector through the same chain (NaN / inf weights included)
+      }
+      const float b = p.eb ? p.eb[j] : 0.f;
+      o[j] = __fadd_rn(v, __fadd_rn(ae, b));
+      if (p.uncond_off) o[p.uncond_off + j] = __fadd_rn(v, __fadd_rn(au, b));
+    } else {
+      o[j] = v;
+      if (p.uncond_off) o[p.uncond_off + j] = v;
+    }
+  }
+}
+
 // HuBERT feature-extractor layer 0: Conv1d(1, 512, k=10, stride=5) + bias, channels-last output
 __global__ __launch_bounds__(256) void conv0_kernel(const float* wav, const float* w, const float* bias, float* out,
                                                     int n, int T0) {
@@ -773,8 +830,11 @@ __global__ __launch_bounds__(256) void adain_kernel(const float* content, const 
 // d_k = (sum_i z_i^2 + sum_i e_ki^2) - 2 * dot, every sum a sequential fmaf chain over i (the
 // documented order shared with oracle/fdm_oracle_c.c); first-min argmin; z_q = z + (e - z).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void vq_quant_kernel(const float* z, const float* codebook, const int* book, int B, int R, int c,
-                                                       int K, float* zq_bcl, long long* idx) {
+// ROWBOOK = false: book[b], one codebook slice per clip (or book == NULL: slice 0).  ROWBOOK = true (condition tracks): book has one
+// entry per ROW, [B * R] -- a frame's G rows carry the slice of the frame's own emotion; an entry outside [0, n_books) reads slice 0.
+template <bool ROWBOOK>
+__device__ __forceinline__ void vq_quant_body(const float* z, const float* codebook, const int* book, int n_books, int B, int R, int c,
+                                              int K, float* zq_bcl, long long* idx) {
   __shared__ float zs[4][128];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long row = (long long)blockIdx.x * 4 + wave;
@@ -783,7 +843,10 @@ __global__ __launch_bounds__(256) void vq_quant_kernel(const float* z, const flo
   const float* zr = z + (size_t)row * c;
   for (int i = lane; i < c; i += 64) zs[wave][i] = zr[i];
   __builtin_amdgcn_wave_barrier();
-  const float* E = codebook + (size_t)(book ? book[b] : 0) * K * c;
+  int bsel;
+  if constexpr (ROWBOOK) { bsel = book[row]; if (bsel < 0 || bsel >= n_books) bsel = 0; }
+  else bsel = book ? book[b] : 0;
+  const float* E = codebook + (size_t)bsel * K * c;
   float z2 = 0.f;
   for (int i = 0; i < c; ++i) z2 = __fmaf_rn(zs[wave][i], zs[wave][i], z2);
   float best = INFINITY;
@@ -813,6 +876,14 @@ __global__ __launch_bounds__(256) void vq_quant_kernel(const float* z, const flo
     zq_bcl[((size_t)b * c + i) * R + r] = __fadd_rn(zv, __fsub_rn(e[i], zv));
   }
 }
+__global__ __launch_bounds__(256) void vq_quant_kernel(const float* z, const float* codebook, const int* book, int B, int R, int c,
+                                                       int K, float* zq_bcl, long long* idx) {
+  vq_quant_body<false>(z, codebook, book, 1, B, R, c, K, zq_bcl, idx);
+}
+__global__ __launch_bounds__(256) void vq_quant_rowbook_kernel(const float* z, const float* codebook, const int* book, int n_books, int B,
+                                                               int R, int c, int K, float* zq_bcl, long long* idx) {
+  vq_quant_body<true>(z, codebook, book, n_books, B, R, c, K, zq_bcl, idx);
+}
 
 // ------------------------------------------------------------------------------------------------
 // The rest of VectorQuantizer.forward's return tuple (models/lib/quantizer.py:46-61, models/vq_vae_emotion.py:232-249):
@@ -822,8 +893,9 @@ __global__ __launch_bounds__(256) void vq_quant_kernel(const float* z, const flo
 //   accumulated per wave in double; code histogram through integer atomics (exact in any order).  Pass 2: one workgroup sums the
 //   per-workgroup partials in index order and evaluates the two scalars.  Deterministic; not on the sampling path's clock.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void vq_stats_partial_kernel(const float* z, const float* codebook, const int* book, const long long* idx,
-                                                               int B, int R, int c, int K, float* min_enc, double* partial, int* hist) {
+template <bool ROWBOOK>
+__device__ __forceinline__ void vq_stats_partial_body(const float* z, const float* codebook, const int* book, int n_books, const long long* idx,
+                                                      int B, int R, int c, int K, float* min_enc, double* partial, int* hist) {
   __shared__ double wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long rows = (long long)B * R;
@@ -831,7 +903,10 @@ __global__ __launch_bounds__(256) void vq_stats_partial_kernel(const float* z, c
   for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += (long long)gridDim.x * 4) {
     const int b = (int)(row / R);
     const int k = (int)idx[row];
-    const float* e = codebook + ((size_t)(book ? book[b] : 0) * K + k) * c;
+    int bsel;
+    if constexpr (ROWBOOK) { bsel = book[row]; if (bsel < 0 || bsel >= n_books) bsel = 0; }
+    else bsel = book ? book[b] : 0;
+    const float* e = codebook + ((size_t)bsel * K + k) * c;
     const float* zr = z + (size_t)row * c;
     float d2 = 0.f;
     for (int i = lane; i < c; i += 64) { const float d = __fsub_rn(e[i], zr[i]); d2 = __fmaf_rn(d, d, d2); }
@@ -843,6 +918,26 @@ __global__ __launch_bounds__(256) void vq_stats_partial_kernel(const float* z, c
   if (lane == 0) wsum[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+__global__ __launch_bounds__(256) void vq_stats_partial_kernel(const float* z, const float* codebook, const int* book, const long long* idx,
+                                                               int B, int R, int c, int K, float* min_enc, double* partial, int* hist) {
+  vq_stats_partial_body<false>(z, codebook, book, 1, idx, B, R, c, K, min_enc, partial, hist);
+}
+__global__ __launch_bounds__(256) void vq_stats_partial_rowbook_kernel(const float* z, const float* codebook, const int* book, int n_books,
+                                                                       const long long* idx, int B, int R, int c, int K, float* min_enc,
+                                                                       double* partial, int* hist) {
+  vq_stats_partial_body<true>(z, codebook, book, n_books, idx, B, R, c, K, min_enc, partial, hist);
+}
+// book[row * rep .. row * rep + rep) = argmax(x[row, :]) (the first maximum, as torch.argmax -- except that a NaN never wins a
+// comparison here, where torch.argmax returns the NaN's index; the per-clip argmax_rows_kernel has the same rule): the codebook of every frame of an emotion
+// track, written once per latent vector of the frame (rep = G: the EVQ grouping maps frames to rows as it maps clips to rows)
+__global__ void argmax_rows_rep_kernel(const float* x, int* out, long long rows, int n, int rep) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  int best = 0;
+  float bv = x[(size_t)r * n];
+  for (int i = 1; i < n; ++i) { const float v = x[(size_t)r * n + i]; if (v > bv) { bv = v; best = i; } }
+  for (int g = 0; g < rep; ++g) out[r * rep + g] = best;
 }
 __global__ __launch_bounds__(256) void vq_stats_final_kernel(const double* partial, int nparts, const int* hist, int K, long long rows, int c,
                                                              float beta, float* out) {

@@ -530,6 +530,7 @@ struct fdm_vq {
   float *x32 = nullptr, *c32 = nullptr, *h = nullptr, *hb = nullptr, *h2 = nullptr, *em = nullptr, *xpad32 = nullptr;
   void *xt = nullptr, *y = nullptr, *xp = nullptr, *nt = nullptr, *q = nullptr, *kp = nullptr, *vp = nullptr, *ctx = nullptr, *u = nullptr, *a = nullptr, *xpt = nullptr;
   int* book = nullptr;
+  int* book_rows = nullptr; size_t book_rows_cap = 0;            // fdm_vq_quant_tracks: one codebook slice per latent vector, grown on demand (V->mem)
   int* lens = nullptr;       // per-clip frame counts of the last fdm_vq_decode_ragged [capB]
   double* stat_partial = nullptr; int* stat_hist = nullptr;      // fdm_vq_quant_stats scratch
 };
@@ -778,6 +779,48 @@ int fdm_vq_quant_stats(fdm_vq* V, const float* z, const float* emo_one_hot, cons
     book = V->book;
   }
   return fdm_op_vq_stats(z, V->codebook, book, idx, B, R, V->d.c, V->d.K, beta, min_encodings, V->stat_partial, V->stat_hist, out2, stream);
+}
+
+// Condition tracks: every frame is quantised in the codebook of ITS emotion.  emo [B, L, n_books] with L = R / G; the book of a frame
+// is argmax(emo[b, l, :]), the first maximum, written once per latent vector of the frame.  A model without EVQ: the per-clip call.
+// (the callers have checked R % G == 0)
+static int vq_row_books(fdm_vq* V, const float* emo, int B, int R, const int** book, void* stream) {
+  FCK(vq_commit(V, stream));
+  FCK(vq_reserve(V, B, 2));                  // (the statistics scratch, as the per-clip quant)
+  const size_t n = (size_t)B * R;
+  if (n > V->book_rows_cap) {                // its own [B * R] int buffer: grows only when a larger batch arrives
+    if (V->book_rows) { HIPCK(hipStreamSynchronize((hipStream_t)stream)); V->mem.free_one(V->book_rows); V->book_rows = nullptr; V->book_rows_cap = 0; }
+    FCK(V->mem.alloc_t(&V->book_rows, n));
+    V->book_rows_cap = n;
+  }
+  FCK(fdm_op_argmax_rows(emo, V->book_rows, (long long)B * (R / V->d.G), V->d.n_books, V->d.G, V->d.n_books, stream));
+  *book = V->book_rows;
+  return FDM_OK;
+}
+
+int fdm_vq_quant_tracks(fdm_vq* V, const float* z, const float* emo, int B, int R, float* zq_bcl, long long* idx, void* stream) {
+  if (!V || !z || !zq_bcl || !idx) return fail(FDM_ERR_ARG, "vq_quant_tracks: null argument");
+  if (V->d.n_books <= 1) return fdm_vq_quant(V, z, nullptr, B, R, zq_bcl, idx, stream);
+  if (!emo) return fail(FDM_ERR_ARG, "vq_quant_tracks: null emotion track");
+  if (B < 1 || R < 1) return fail(FDM_ERR_SHAPE, "vq_quant_tracks: bad shape");
+  if (R % V->d.G) return fail(FDM_ERR_SHAPE, "vq_quant_tracks: R=%d is not a whole number of frames of %d latent vectors", R, V->d.G);
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vq_quant_tracks: no gfx950 device visible (there is no CPU fallback)");
+  const int* book = nullptr;
+  FCK(vq_row_books(V, emo, B, R, &book, stream));
+  return fdm_op_vq_quant_rows(z, V->codebook, book, V->d.n_books, B, R, V->d.c, V->d.K, zq_bcl, idx, stream);
+}
+
+int fdm_vq_quant_stats_tracks(fdm_vq* V, const float* z, const float* emo, const long long* idx, int B, int R, float beta,
+                              float* min_encodings, float* out2, void* stream) {
+  if (!V || !z || !idx || !out2) return fail(FDM_ERR_ARG, "vq_quant_stats_tracks: null argument");
+  if (V->d.n_books <= 1) return fdm_vq_quant_stats(V, z, nullptr, idx, B, R, beta, min_encodings, out2, stream);
+  if (!emo) return fail(FDM_ERR_ARG, "vq_quant_stats_tracks: null emotion track");
+  if (B < 1 || R < 1) return fail(FDM_ERR_SHAPE, "vq_quant_stats_tracks: bad shape");
+  if (R % V->d.G) return fail(FDM_ERR_SHAPE, "vq_quant_stats_tracks: R=%d is not a whole number of frames of %d latent vectors", R, V->d.G);
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vq_quant_stats_tracks: no gfx950 device visible (there is no CPU fallback)");
+  const int* book = nullptr;
+  FCK(vq_row_books(V, emo, B, R, &book, stream));
+  return fdm_op_vq_stats_rows(z, V->codebook, book, V->d.n_books, idx, B, R, V->d.c, V->d.K, beta, min_encodings, V->stat_partial, V->stat_hist, out2, stream);
 }
 
 // frames: per-clip frame counts (host, validated by the caller) of a batch padded to L = R / G frames, or nullptr

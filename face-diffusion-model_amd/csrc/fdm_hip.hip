@@ -447,6 +447,25 @@ int fdm_op_small_linear(const float* x, const float* W, const float* bias, float
   }, stream, "small_linear");
 }
 
+int fdm_op_cond_rows(const float* pe, const float* style, const float* emo, const float* sw, const float* sb, const float* ew,
+                     const float* eb, float* out, long long uncond_off, int B, int L, int L_clip, int L_track, int d, int n_style,
+                     int n_emo, int act, void* stream) {
+  if (!pe || !style || !sw || !out) return fail(FDM_ERR_ARG, "cond_rows: null operand (pe, style track, style weight, out)");
+  if (emo && !ew) return fail(FDM_ERR_ARG, "cond_rows: an emotion track needs the emotion weight");
+  if (act < FDM_ACT_NONE || act > FDM_ACT_LEAKY02) return fail(FDM_ERR_ARG, "cond_rows: bad activation %d", act);
+  if (B <= 0 || L <= 0 || d <= 0 || (long long)B * L > 0x7fffffffLL) return fail(FDM_ERR_SHAPE, "cond_rows: bad shape (B %d, L %d, d %d)", B, L, d);
+  if (L_clip < 1 || L_clip > L || L_track < L_clip) return fail(FDM_ERR_SHAPE, "cond_rows: L_clip=%d outside [1, L %d] or beyond the track's %d rows per clip", L_clip, L, L_track);
+  if (n_style < 1 || n_style > fdm::COND_ROWS_MAX_K || (emo && (n_emo < 1 || n_emo > fdm::COND_ROWS_MAX_K)))
+    return fail(FDM_ERR_SHAPE, "cond_rows: vector widths (%d, %d) outside [1, %d]", n_style, n_emo, fdm::COND_ROWS_MAX_K);
+  if (uncond_off < 0 || uncond_off % d || (uncond_off && uncond_off < (long long)B * L * d))
+    return fail(FDM_ERR_SHAPE, "cond_rows: uncond_off=%lld is not a whole number of rows past the cond half", uncond_off);
+  fdm::CondRowsArgs p{pe, style, emo, sw, sb, ew, eb, out, uncond_off, B * L, L, L_clip, L_track, d, n_style, emo ? n_emo : 0, act};
+  return submit([p](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::cond_rows_kernel, dim3((unsigned)p.rows), dim3(256), 0, s, p);
+    return hipGetLastError();
+  }, stream, "cond_rows");
+}
+
 int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream) {
   if (!in || !out || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "pad_rows: bad argument");
   if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "pad_rows: bad dtype %d", dtype);
@@ -707,6 +726,45 @@ int fdm_op_vq_stats(const float* z, const float* codebook, const int* book, cons
     hipLaunchKernelGGL(fdm::vq_stats_final_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nblk, (const int*)hist, K, rows, c, beta, out);
     return hipGetLastError();
   }, stream, "vq_stats");
+}
+
+// ---- per-row codebook (condition tracks): book has one entry per latent vector, [B * R] ------------------------------------------
+int fdm_op_argmax_rows(const float* x, int* book, long long rows, int n, int rep, int n_books, void* stream) {
+  if (!x || !book) return fail(FDM_ERR_ARG, "argmax_rows: null operand");
+  if (rows <= 0 || n <= 0 || rep <= 0 || rows * rep > 0x7fffffffLL) return fail(FDM_ERR_SHAPE, "argmax_rows: bad shape (rows %lld, n %d, rep %d)", rows, n, rep);
+  if (n_books < 1 || n > n_books) return fail(FDM_ERR_SHAPE, "argmax_rows: an argmax over %d columns can name a book outside the %d of the codebook", n, n_books);
+  return submit([=](hipStream_t s) {
+    hipLaunchKernelGGL(fdm::argmax_rows_rep_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, book, rows, n, rep);
+    return hipGetLastError();
+  }, stream, "argmax_rows");
+}
+
+int fdm_op_vq_quant_rows(const float* z, const float* codebook, const int* book_rows, int n_books, int B, int R, int c, int K,
+                         float* zq_bcl, long long* idx, void* stream) {
+  if (!z || !codebook || !book_rows || !zq_bcl || !idx) return fail(FDM_ERR_ARG, "vq_quant_rows: null operand");
+  if (B <= 0 || R <= 0 || K <= 0 || c <= 0 || c > 128) return fail(FDM_ERR_SHAPE, "vq_quant_rows: bad shape (c=%d must be <= 128)", c);
+  if (n_books < 1) return fail(FDM_ERR_SHAPE, "vq_quant_rows: n_books=%d", n_books);
+  return submit([=](hipStream_t s) {
+    const long long rows = (long long)B * R;
+    hipLaunchKernelGGL(fdm::vq_quant_rowbook_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, z, codebook, book_rows, n_books, B, R, c, K, zq_bcl, idx);
+    return hipGetLastError();
+  }, stream, "vq_quant_rows");
+}
+
+int fdm_op_vq_stats_rows(const float* z, const float* codebook, const int* book_rows, int n_books, const long long* idx, int B, int R, int c,
+                         int K, float beta, float* min_encodings, double* partial, int* hist, float* out, void* stream) {
+  if (!z || !codebook || !book_rows || !idx || !partial || !hist || !out) return fail(FDM_ERR_ARG, "vq_stats_rows: null operand");
+  if (B <= 0 || R <= 0 || K <= 0 || c <= 0) return fail(FDM_ERR_SHAPE, "vq_stats_rows: bad shape");
+  if (n_books < 1) return fail(FDM_ERR_SHAPE, "vq_stats_rows: n_books=%d", n_books);
+  const long long rows = (long long)B * R;
+  const int nblk = (int)std::min<long long>(1024, (rows + 3) / 4);
+  return submit([=](hipStream_t s) {
+    hipError_t e = hipMemsetAsync(hist, 0, (size_t)K * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fdm::vq_stats_partial_rowbook_kernel, dim3(nblk), dim3(256), 0, s, z, codebook, book_rows, n_books, idx, B, R, c, K, min_encodings, partial, hist);
+    hipLaunchKernelGGL(fdm::vq_stats_final_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nblk, (const int*)hist, K, rows, c, beta, out);
+    return hipGetLastError();
+  }, stream, "vq_stats_rows");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -874,13 +874,25 @@ int zero_mat(const fdm_plan* P, const Mat& mt, size_t at, size_t n, void* stream
 // One slot's rows of AF, C1_l (both CFG halves) and E0 for a clip (or a window of a long clip) of L_clip frames whose audio rows start
 // at hub_clip: the per-clip GEMMs of fdm_audio_prepare_conds on L_clip rows, zero addends in the rows L_clip .. L.  Shared by
 // fdm_slot_admit and fdm_slot_admit_long.
+// the audio half of a slot's rows: AF and C1_l (both CFG halves) on L_clip rows, zero C1_l rows beyond (slot_rows, slot_rows_tracks)
+int slot_audio_rows(fdm_plan* P, int slot, const float* hub_clip, int L_clip, void* stream) {
+  const fdm_model_desc& m = P->m;
+  const int d = m.d, L = P->L, M = P->M, row0 = slot * L, pad = L - L_clip;
+  const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
+  FCK(clip_audio_in(P, hub_clip, row0, L_clip, stream));
+  FCK(clip_tables(P, row0, L_clip, P->rep == 2 ? (size_t)M * d : 0, stream));
+  if (pad)        // rows L_clip .. L of the slot: zero addends (the denoiser is causal: they never reach the clip's own frames)
+    for (int r = 0; r < P->rep; ++r)
+      for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l] + (size_t)r * M * d + o + nclip, 0, npad * 4, (hipStream_t)stream));
+  return FDM_OK;
+}
+
 int slot_rows(fdm_plan* P, int slot, const float* hub_clip, const float* style, const float* emo, int L_clip, void* stream) {
   const fdm_model_desc& m = P->m;
   hipStream_t s = (hipStream_t)stream;
   const int d = m.d, L = P->L, M = P->M, row0 = slot * L, pad = L - L_clip;
   const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
-  FCK(clip_audio_in(P, hub_clip, row0, L_clip, stream));
-  FCK(clip_tables(P, row0, L_clip, P->rep == 2 ? (size_t)M * d : 0, stream));
+  FCK(slot_audio_rows(P, slot, hub_clip, L_clip, stream));
   const float *sw = nullptr, *sbias = nullptr, *ew = nullptr, *eb = nullptr;
   FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
   float *sty = P->sty + (size_t)slot * d, *em = P->em + (size_t)slot * d, *emu = P->emu + (size_t)slot * d;
@@ -894,12 +906,31 @@ int slot_rows(fdm_plan* P, int slot, const float* hub_clip, const float* style, 
     const float* e = m.n_emo ? (r == 1 ? emu : em) : nullptr;
     const size_t ro = (size_t)r * M * d + o;
     FCK(fdm_op_add_rows(P->pe, 1, L_clip, sty, L_clip, 1, e, L_clip, 1, P->E0 + ro, L_clip, d, stream));
-    if (pad) {      // rows L_clip .. L of the slot: zero addends (the denoiser is causal: they never reach the clip's own frames)
-      HIPCK(hipMemsetAsync(P->E0 + ro + nclip, 0, npad * 4, s));
-      for (int l = 0; l < m.n_layers; ++l) HIPCK(hipMemsetAsync(P->C1[l] + ro + nclip, 0, npad * 4, s));
-    }
+    if (pad) HIPCK(hipMemsetAsync(P->E0 + ro + nclip, 0, npad * 4, s));      // (zero addends in the rows L_clip .. L, as the C1_l rows)
   }
   return FDM_OK;
+}
+
+// Condition tracks: the E0 rows (both CFG halves) of `clips` row blocks from block0 on, from per-frame tracks style [clips, L_track,
+// n_style] / emo [clips, L_track, n_emo] of which the rows < L_clip are read; the rows L_clip .. L of every block become zeros.  One
+// launch (fdm_op_cond_rows), bit for bit the small_linear + add_rows sequence of slot_rows / fdm_audio_prepare_conds per row.
+int cond_tracks(fdm_plan* P, int block0, int clips, int L_clip, int L_track, const float* style, const float* emo, void* stream) {
+  const fdm_model_desc& m = P->m;
+  const int d = m.d;
+  const float *sw = nullptr, *sbias = nullptr, *ew = nullptr, *eb = nullptr;
+  FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
+  if (m.n_emo) { FCK(need(P, "emotion_embedd.weight", (long long)d * m.n_emo, &ew)); FCK(need(P, "emotion_embedd.bias", d, &eb)); }
+  return fdm_op_cond_rows(P->pe, style, m.n_emo ? emo : nullptr, sw, sbias, ew, eb, P->E0 + (size_t)block0 * P->L * d,
+                          P->rep == 2 ? (long long)P->M * d : 0, clips, P->L, L_clip, L_track, d, m.n_style, m.n_emo,
+                          m.style_mish ? FDM_ACT_MISH : FDM_ACT_NONE, stream);
+}
+
+// slot_rows with per-frame conditions: the slot's AF / C1_l rows as there, E0 (and its zero rows) through cond_tracks.  track0 = the
+// first track row of this clip or window.  Shared by fdm_slot_admit_tracks and fdm_slot_admit_long_tracks.
+int slot_rows_tracks(fdm_plan* P, int slot, const float* hub_clip, const float* style, const float* emo, int track0, int L_clip, void* stream) {
+  const fdm_model_desc& m = P->m;
+  FCK(slot_audio_rows(P, slot, hub_clip, L_clip, stream));
+  return cond_tracks(P, slot, 1, L_clip, L_clip, style + (size_t)track0 * m.n_style, m.n_emo ? emo + (size_t)track0 * m.n_emo : nullptr, stream);
 }
 
 int check_slots(const fdm_plan* P, const char* who) {
@@ -978,8 +1009,9 @@ int fdm_audio_prepare(fdm_plan* P, const float* hub, int B, int N, int fw, const
   return fdm_audio_prepare_conds(P, hub, B, N, fw, 1, style, emo, L, cfg, stream);
 }
 
-int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw, int S, const float* style, const float* emo, int L, int cfg, void* stream) {
-  if (!P || !hub || !style) return fail(FDM_ERR_ARG, "audio_prepare: null argument");
+// The part of a prepare that does not depend on the conditions: checks, workspaces, the plan's shape and the audio tables AF / C1_l.
+// Shared by fdm_audio_prepare_conds (one vector per clip and condition) and fdm_audio_prepare_tracks (one vector per frame).
+static int prepare_tables(fdm_plan* P, const float* hub, int B0, int N, int fw, int S, bool emo_missing, int L, int cfg, void* stream) {
   const fdm_model_desc& m = P->m;
   if (B0 < 1 || N < 1 || fw < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: bad feature shape [%d, %d, %d]", B0, N, fw);
   if (S < 1) return fail(FDM_ERR_SHAPE, "audio_prepare: S=%d conditions per clip", S);
@@ -989,7 +1021,7 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   P->bank_rows = P->bank_t_cap = P->bank_c_cap = 0;
   if (m.pair * fw != m.audio_in) return fail(FDM_ERR_SHAPE, "audio_prepare: audio feature width %d x pair %d != audio_extract input %d", fw, m.pair, m.audio_in);
   if (L < 1 || L > N / m.pair || L > m.max_len) return fail(FDM_ERR_SHAPE, "audio_prepare: latent frames L=%d outside [1, min(%d, %d)] (models/fdm_vocaset.py:44,64-66)", L, N / m.pair, m.max_len);
-  if (m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
+  if (m.n_emo && emo_missing) return fail(FDM_ERR_ARG, "audio_prepare: this model needs an emotion one-hot");
   const int B = B0 * S;                      // row blocks of the step program
   FCK(commit(P, stream));
   FCK(reserve(P, B, L, cfg));
@@ -1009,6 +1041,24 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
   // S > 1: ONE block of [B0 * L, d] per layer, every condition (and both CFG halves) of a clip reads its clip's rows through
   // the LayerNorm kernel's row map (fdm_ln_args.add_mat_group) -- no table work per condition
   FCK(clip_tables(P, 0, M0, (rep == 2 && S == 1) ? (size_t)M * d : 0, stream));
+  return FDM_OK;
+}
+// ... and its end: the plan is prepared, tiles chosen
+static int prepare_done(fdm_plan* P, void* stream) {
+  P->prepared = true;
+  select_tiles(P);
+  // A request path never tunes by itself: fdm_plan_tune does, when the caller schedules it (fdm_plan_get "needs_tune" says when a
+  // shape has served >= 2000 steps on heuristic tiles).  Opt-in (fdm_plan_set "tune_lazy"): tune here / inside fdm_sample_graph
+  // once that is the case -- and even then a tuner failure keeps the heuristic tiles instead of failing the request.
+  if (P->tune_lazy) tune_soft(P, stream);
+  return FDM_OK;
+}
+
+int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw, int S, const float* style, const float* emo, int L, int cfg, void* stream) {
+  if (!P || !hub || !style) return fail(FDM_ERR_ARG, "audio_prepare: null argument");
+  FCK(prepare_tables(P, hub, B0, N, fw, S, !emo, L, cfg, stream));
+  const fdm_model_desc& m = P->m;
+  const int d = m.d, B = P->B, M = P->M, rep = P->rep;
   // conditioning addend E0 = PE[l] + style[b] (+ emotion[b]) (:75-84), one row block per (clip, condition)
   const float *sw = nullptr, *sbias = nullptr;
   FCK(need(P, "style_embedd.weight", (long long)d * m.n_style, &sw)); FCK(need(P, "style_embedd.bias", d, &sbias));
@@ -1024,17 +1074,23 @@ int fdm_audio_prepare_conds(fdm_plan* P, const float* hub, int B0, int N, int fw
     const float* e = m.n_emo ? (r == 1 ? P->emu : P->em) : nullptr;
     FCK(fdm_op_add_rows(P->pe, 1, L, P->sty, L, B, e, L, B, P->E0 + (size_t)r * M * d, M, d, stream));
   }
-  P->prepared = true;
-  select_tiles(P);
-  // A request path never tunes by itself: fdm_plan_tune does, when the caller schedules it (fdm_plan_get "needs_tune" says when a
-  // shape has served >= 2000 steps on heuristic tiles).  Opt-in (fdm_plan_set "tune_lazy"): tune here / inside fdm_sample_graph
-  // once that is the case -- and even then a tuner failure keeps the heuristic tiles instead of failing the request.
-  if (P->tune_lazy) tune_soft(P, stream);
-  return FDM_OK;
+  return prepare_done(P, stream);
 }
 
-int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L_total,
-                              int window, int overlap, int cfg, void* stream) {
+// fdm_audio_prepare with one style / emotion vector per latent frame: the same tables, E0 from the tracks in one launch
+int fdm_audio_prepare_tracks(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L, int cfg, void* stream) {
+  if (!P || !hub) return fail(FDM_ERR_ARG, "audio_prepare_tracks: null argument");
+  if (!style) return fail(FDM_ERR_ARG, "audio_prepare_tracks: null style track");
+  if (P->m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare_tracks: this model needs an emotion track");
+  FCK(prepare_tables(P, hub, B, N, fw, 1, false, L, cfg, stream));
+  FCK(cond_tracks(P, 0, P->B, P->L, P->L, style, emo, stream));
+  return prepare_done(P, stream);
+}
+
+// fdm_audio_prepare_windows (tracks = false: one style / emotion vector per long clip) and fdm_audio_prepare_windows_tracks (tracks =
+// true: [B, L_total, n] per-frame rows, window w is staged with the rows [s_w, s_w + W) of its clip)
+static int prepare_windows_impl(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, bool tracks,
+                                int L_total, int window, int overlap, int cfg, void* stream) {
   if (!P || !hub || !style) return fail(FDM_ERR_ARG, "audio_prepare_windows: null argument");
   const fdm_model_desc& m = P->m;
   P->win_n = 0;
@@ -1049,7 +1105,8 @@ int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int f
   if (n < 0) return n;
   const int W = std::min(window, L_total), Bw = B * n, d = m.d;
   const size_t rows = (size_t)W * m.pair;                       // encoder frames per window
-  const size_t n_hub = (size_t)Bw * rows * fw, n_sty = (size_t)Bw * m.n_style, n_emo = m.n_emo ? (size_t)Bw * m.n_emo : 0;
+  const size_t per = tracks ? (size_t)W : 1;                     // condition rows per window
+  const size_t n_hub = (size_t)Bw * rows * fw, n_sty = (size_t)Bw * per * m.n_style, n_emo = m.n_emo ? (size_t)Bw * per * m.n_emo : 0;
   hipStream_t s = (hipStream_t)stream;
   FCK(grow(P, (void**)&P->win_stage, &P->win_stage_cap, (n_hub + n_sty + n_emo) * 4, stream));
   FCK(grow(P, (void**)&P->xlong, &P->xlong_cap, (size_t)B * L_total * d * 4, stream));
@@ -1060,8 +1117,9 @@ int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int f
     for (int w = 0; w < n; ++w) {
       const size_t k = (size_t)b * n + w;
       HIPCK(hipMemcpyAsync(hw + k * rows * fw, hub + ((size_t)b * N + (size_t)starts[w] * m.pair) * fw, rows * fw * 4, hipMemcpyDefault, s));
-      HIPCK(hipMemcpyAsync(sw + k * m.n_style, style + (size_t)b * m.n_style, (size_t)m.n_style * 4, hipMemcpyDefault, s));
-      if (m.n_emo) HIPCK(hipMemcpyAsync(ew + k * m.n_emo, emo + (size_t)b * m.n_emo, (size_t)m.n_emo * 4, hipMemcpyDefault, s));
+      const size_t src = tracks ? (size_t)b * L_total + starts[w] : (size_t)b;      // first condition row of the window
+      HIPCK(hipMemcpyAsync(sw + k * per * m.n_style, style + src * m.n_style, per * m.n_style * 4, hipMemcpyDefault, s));
+      if (m.n_emo) HIPCK(hipMemcpyAsync(ew + k * per * m.n_emo, emo + src * m.n_emo, per * m.n_emo * 4, hipMemcpyDefault, s));
     }
   // covering windows per frame (ascending window order) with their normalised weights
   std::vector<float> wt;
@@ -1078,9 +1136,22 @@ int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int f
   HIPCK(hipMemcpyAsync(P->win_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCK(hipMemcpyAsync(P->win_ent, ent.data(), ent.size() * sizeof(fdm::WinEnt), hipMemcpyHostToDevice, s));
   HIPCK(hipStreamSynchronize(s));            // (off / ent are host vectors of this call)
-  FCK(fdm_audio_prepare_conds(P, hw, Bw, (int)rows, fw, 1, sw, m.n_emo ? ew : nullptr, W, cfg, stream));
+  if (tracks) FCK(fdm_audio_prepare_tracks(P, hw, Bw, (int)rows, fw, sw, m.n_emo ? ew : nullptr, W, cfg, stream));
+  else FCK(fdm_audio_prepare_conds(P, hw, Bw, (int)rows, fw, 1, sw, m.n_emo ? ew : nullptr, W, cfg, stream));
   P->win_n = n; P->win_len = W; P->win_total = L_total; P->win_overlap = overlap; P->win_B = B;
   return FDM_OK;
+}
+
+int fdm_audio_prepare_windows(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L_total,
+                              int window, int overlap, int cfg, void* stream) {
+  return prepare_windows_impl(P, hub, B, N, fw, style, emo, false, L_total, window, overlap, cfg, stream);
+}
+
+int fdm_audio_prepare_windows_tracks(fdm_plan* P, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L_total,
+                                     int window, int overlap, int cfg, void* stream) {
+  if (!style) return fail(FDM_ERR_ARG, "audio_prepare_windows_tracks: null style track");
+  if (P && P->m.n_emo && !emo) return fail(FDM_ERR_ARG, "audio_prepare_windows_tracks: this model needs an emotion track");
+  return prepare_windows_impl(P, hub, B, N, fw, style, emo, true, L_total, window, overlap, cfg, stream);
 }
 
 int fdm_denoise_step(fdm_plan* P, const float* x_t, int t, float cfg_scale, float* x0_hat, float* x0_uncond, void* stream) {
@@ -1114,6 +1185,14 @@ int fdm_sample_windows(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   if (P->slots) return fail(FDM_ERR_STATE, "sample_windows: the plan is in slot mode (fdm_slots_run)");
   if (!P->win_n) return fail(FDM_ERR_STATE, "sample_windows: call fdm_audio_prepare_windows first");
   return sample_impl(P, a, stream);
+}
+
+int fdm_window_peek(fdm_plan* P, float* out, void* stream) {
+  FCK(check_ready(P));
+  if (!out) return fail(FDM_ERR_ARG, "window_peek: null output");
+  if (!P->win_n) return fail(FDM_ERR_STATE, "window_peek: the plan is not in window mode (fdm_audio_prepare_windows)");
+  HIPCK(hipMemcpyAsync(out, P->x, (size_t)P->M * P->m.d * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return FDM_OK;
 }
 
 // ---- in-flight batching (include/fdm_hip.h, "Slots") -------------------------------------------------------------------
@@ -1238,8 +1317,10 @@ int fdm_slot_admit(fdm_plan* P, int slot, const float* hub, int N, int fw, const
   return fdm_slot_admit_as(P, slot, hub, N, fw, style, emo, L_clip, x_T, seed, clip_id, 0, P->slot_cfg_scale, stream);
 }
 
-int fdm_slot_admit_as(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
-                      const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
+// fdm_slot_admit_as (tracks = false: style / emo are the clip's one vector each) and fdm_slot_admit_tracks (tracks = true: [L_clip, n]
+// per-frame rows): everything but the E0 rows is the same work
+static int slot_admit_impl(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, bool tracks, int L_clip,
+                           const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
   if (!P || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit: null argument");
   FCK(check_slots(P, "slot_admit"));
   const fdm_model_desc& m = P->m;
@@ -1254,7 +1335,8 @@ int fdm_slot_admit_as(fdm_plan* P, int slot, const float* hub, int N, int fw, co
   hipStream_t s = (hipStream_t)stream;
   const int d = m.d, L = P->L, row0 = slot * L, pad = L - L_clip;
   const size_t o = (size_t)row0 * d, nclip = (size_t)L_clip * d, npad = (size_t)pad * d;
-  FCK(slot_rows(P, slot, hub, style, emo, L_clip, stream));
+  if (tracks) FCK(slot_rows_tracks(P, slot, hub, style, emo, 0, L_clip, stream));
+  else FCK(slot_rows(P, slot, hub, style, emo, L_clip, stream));
   // x_T (+ zero tail) and its operand copy into the slot's rows; the history starts at zero
   HIPCK(hipMemcpyAsync(P->x + o, x_T, nclip * 4, hipMemcpyDeviceToDevice, s));
   if (pad) HIPCK(hipMemsetAsync(P->x + o + nclip, 0, npad * 4, s));
@@ -1270,6 +1352,18 @@ int fdm_slot_admit_as(fdm_plan* P, int slot, const float* hub, int N, int fw, co
   FCK(slot_start(P, slot, t0, seed, clip_id, sampler, cfg_scale, stream));
   h.status = 1; h.done = 0; h.L = L_clip; h.sampler = sampler; h.total = total;
   return FDM_OK;
+}
+
+int fdm_slot_admit_as(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                      const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
+  return slot_admit_impl(P, slot, hub, N, fw, style, emo, false, L_clip, x_T, seed, clip_id, sampler, cfg_scale, stream);
+}
+
+int fdm_slot_admit_tracks(fdm_plan* P, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                          const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream) {
+  if (!style) return fail(FDM_ERR_ARG, "slot_admit_tracks: null style track");
+  if (P && P->m.n_emo && !emo) return fail(FDM_ERR_ARG, "slot_admit_tracks: this model needs an emotion track");
+  return slot_admit_impl(P, slot, hub, N, fw, style, emo, true, L_clip, x_T, seed, clip_id, sampler, cfg_scale, stream);
 }
 
 int fdm_slots_run(fdm_plan* P, int n_steps, void* stream) {
@@ -1355,9 +1449,11 @@ int fdm_slot_admit_long(fdm_plan* P, const int* slots, int n, const float* hub, 
   return fdm_slot_admit_long_as(P, slots, n, hub, N, fw, style, emo, L_total, overlap, x_T, seed, clip_id, 0, P->slot_cfg_scale, stream);
 }
 
-int fdm_slot_admit_long_as(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
-                           int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale,
-                           void* stream) {
+// fdm_slot_admit_long_as (tracks = false) and fdm_slot_admit_long_tracks (tracks = true: style / emo are [L_total, n] per-frame rows and
+// window w reads the rows [s_w, s_w + L)): everything but the E0 rows is the same work
+static int slot_admit_long_impl(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                                bool tracks, int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler,
+                                float cfg_scale, void* stream) {
   if (!P || !slots || !hub || !style || !x_T) return fail(FDM_ERR_ARG, "slot_admit_long: null argument");
   FCK(check_slots(P, "slot_admit_long"));
   const fdm_model_desc& m = P->m;
@@ -1424,7 +1520,11 @@ int fdm_slot_admit_long_as(fdm_plan* P, const int* slots, int n, const float* hu
   for (int w = 0; w < n; ++w) HIPCK(hipMemcpyAsync(P->slot_member + slots[w], &member[w], 4, hipMemcpyHostToDevice, s));
   HIPCK(hipStreamSynchronize(s));            // (the tables are host vectors of this call)
   // every member's rows of AF, C1_l and E0: window w is an ordinary clip of L frames on the audio rows [s_w pair, (s_w + L) pair)
-  for (int w = 0; w < n; ++w) FCK(slot_rows(P, slots[w], hub + (size_t)starts[w] * m.pair * fw, style, emo, L, stream));
+  for (int w = 0; w < n; ++w) {
+    const float* hw = hub + (size_t)starts[w] * m.pair * fw;
+    if (tracks) FCK(slot_rows_tracks(P, slots[w], hw, style, emo, starts[w], L, stream));
+    else FCK(slot_rows(P, slots[w], hw, style, emo, L, stream));
+  }
   // x_T into the arena, the group's history to zero, then the window rows (+ operand copies) through the pass's init form
   const size_t ao = (size_t)a0 * d, nl = (size_t)L_total * d;
   HIPCK(hipMemcpyAsync(P->long_x + ao, x_T, nl * 4, hipMemcpyDeviceToDevice, s));
@@ -1444,6 +1544,20 @@ int fdm_slot_admit_long_as(fdm_plan* P, const int* slots, int n, const float* hu
   fdm_plan::GroupHost& gh = P->group_host[gi];
   gh.used = true; gh.L_total = L_total; gh.first = a0; gh.e0 = e0; gh.ne = ne; gh.slots.assign(slots, slots + n);
   return FDM_OK;
+}
+
+int fdm_slot_admit_long_as(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                           int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale,
+                           void* stream) {
+  return slot_admit_long_impl(P, slots, n, hub, N, fw, style, emo, false, L_total, overlap, x_T, seed, clip_id, sampler, cfg_scale, stream);
+}
+
+int fdm_slot_admit_long_tracks(fdm_plan* P, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                               int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler,
+                               float cfg_scale, void* stream) {
+  if (!style) return fail(FDM_ERR_ARG, "slot_admit_long_tracks: null style track");
+  if (P && P->m.n_emo && !emo) return fail(FDM_ERR_ARG, "slot_admit_long_tracks: this model needs an emotion track");
+  return slot_admit_long_impl(P, slots, n, hub, N, fw, style, emo, true, L_total, overlap, x_T, seed, clip_id, sampler, cfg_scale, stream);
 }
 
 int fdm_slot_group(fdm_plan* P, int slot, int* leader, int* n, int* L_total) {

@@ -113,13 +113,24 @@ def main(dataset=None, argv=None):
                     help="build-added: table-driven multistep sampler (DPM-Solver++ 2M | DDIM with --eta) instead of the shipped one")
     ap.add_argument("--sampler_steps", type=int, default=20, help="steps of --sampler")
     ap.add_argument("--eta", type=float, default=0.0, help="eta of --sampler ddim_eta, in [0, 1]")
+    named = dataset is not None
+    if named:
+        pipeline.add_track_arguments(ap, presets.get(dataset))
+    else:      # (the dataset is a flag here: every track flag is offered, --emotion_track is refused below on a preset without emotions)
+        pipeline.add_track_arguments(ap, presets.get("mead"))
     a = ap.parse_args(argv)
     fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
-    named = dataset is not None
     dataset = dataset or a.dataset
     p = presets.get(dataset)
+    if getattr(a, "emotion_track", None) and not p.n_emo:
+        ap.error(f"--emotion_track: the {dataset} model takes no emotion")
+    # build-added: style / emotion per time for every clip of the run (one vector per latent frame; animate() takes the frames it needs)
+    trk = pipeline.track_arguments(a, p, p.max_len)
+    if trk and a.all_styles:
+        ap.error("--style_track / --emotion_track take one condition per clip: not with --all_styles")
+    fast.update(trk)
     steps = a.ddim_steps if a.ddim_steps is not None else (SHIPPED_DDIM_STEPS[dataset] or 100)
-    all_styles = a.all_styles or (named and dataset == "vocaset")      # samples/sample_diffusion_vocaset.py:71 loops every one-hot
+    all_styles = a.all_styles or (named and dataset == "vocaset" and not trk)      # samples/sample_diffusion_vocaset.py:71 loops every one-hot
     # one clip, one condition per sampling call (the reference's bs = 1 loop): the step program's single-clip setting
     single = a.batch <= 1 and (not all_styles or a.sequential)
     diffusion, ae = pipeline.build_models(dataset, None, a.device, a.stage1_model_path, a.stage2_model_path, single_clip=single)

@@ -171,6 +171,17 @@ SYMBOLS = {
     "fdm_slot_sampler_info": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
     "fdm_slot_admit_as": (ci, [vp, ci, vp, ci, ci, vp, vp, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
     "fdm_slot_admit_long_as": (ci, [vp, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
+    "fdm_op_cond_rows": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ll, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "fdm_audio_prepare_tracks": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp]),
+    "fdm_audio_prepare_windows_tracks": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+    "fdm_slot_admit_tracks": (ci, [vp, ci, vp, ci, ci, vp, vp, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
+    "fdm_slot_admit_long_tracks": (ci, [vp, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp, C.c_ulonglong, ci, ci, cf, vp]),
+    "fdm_window_peek": (ci, [vp, vp, vp]),
+    "fdm_op_argmax_rows": (ci, [vp, vp, ll, ci, ci, ci, vp]),
+    "fdm_op_vq_quant_rows": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "fdm_op_vq_stats_rows": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
+    "fdm_vq_quant_tracks": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    "fdm_vq_quant_stats_tracks": (ci, [vp, vp, vp, vp, ci, ci, cf, vp, vp, vp]),
     "fdm_plan_tune": (ci, [vp, vp]),
     "fdm_plan_get": (ci, [vp, C.c_char_p, C.POINTER(ll)]),
     "fdm_plan_set": (ci, [vp, C.c_char_p, ll]),

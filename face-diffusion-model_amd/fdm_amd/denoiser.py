@@ -103,8 +103,36 @@ class DenoiserPlan:
             pass
 
     # ------------------------------------------------------------------------------------------
-    def prepare(self, hub, style, emo=None, L=None, cfg=False, n_conds=1):
+    def _track(self, what, n, B, L, vec, track):
+        """One condition as a device track [B, L, n]: `track` ([L', n] or [B, L', n], L' >= L: the first L rows are taken), or the
+        per-clip vector `vec` ([n] or [B, n]) broadcast to frames on the device."""
+        if track is not None:
+            t = torch.as_tensor(track)
+            t = t.unsqueeze(0).expand(B, -1, -1) if t.dim() == 2 else t
+            if t.dim() != 3 or t.shape[0] != B or t.shape[1] < L or t.shape[2] != n:
+                raise FdmError(f"{what} track has shape {tuple(torch.as_tensor(track).shape)}, expected [{B}, >= {L}, {n}] (or [>= {L}, {n}])")
+            return _dev(t[:, :L], self.device)
+        if vec is None:
+            raise FdmError(f"this preset needs a {what} vector or a {what} track")
+        v = _dev(vec, self.device)
+        v = v.unsqueeze(0).expand(B, -1) if v.dim() == 1 else v
+        if v.shape != (B, n):
+            raise FdmError(f"{what} has shape {tuple(v.shape)}, expected [{B}, {n}]")
+        return v.unsqueeze(1).expand(B, L, n).contiguous()
+
+    def _tracks(self, B, L, style, emo, style_track, emotion_track):
+        p = self.p
+        if emotion_track is not None and not p.n_emo:
+            raise FdmError(f"preset {p.name} takes no emotion")
+        return (self._track("style", p.n_style, B, L, style, style_track),
+                self._track("emotion", p.n_emo, B, L, emo, emotion_track) if p.n_emo else None)
+
+    def prepare(self, hub, style=None, emo=None, L=None, cfg=False, n_conds=1, style_track=None, emotion_track=None):
         """hub [B, N, fw] audio-encoder features; style [B, n_style]; emo [B, n_emo]; L latent frames.
+
+        style_track [B, L, n_style] / emotion_track [B, L, n_emo] (or [L, n], shared by the clips): one vector per latent frame
+        instead of one per clip (fdm_audio_prepare_tracks; tracks.keyframes builds them).  Either may be given alone: the other
+        condition's per-clip vector is broadcast to frames.  Frames before a change keep the bits of the unchanged run.
 
         n_conds = S > 1: S conditions per clip in ONE step program (fdm_audio_prepare_conds) -- what the reference's
         samplers do as S sequential B = 1 calls with the same audio (samples/sample_diffusion_vocaset.py:71-83).  style
@@ -120,6 +148,18 @@ class DenoiserPlan:
         L = nfa if L is None else min(L, nfa)
         if L < 1 or L > p.max_len:
             raise FdmError(f"latent frames L={L} outside [1, {p.max_len}] (models/fdm_vocaset.py:44)")
+        if style_track is not None or emotion_track is not None:
+            if S != 1:
+                raise FdmError("condition tracks are not available with n_conds > 1")
+            st, et = self._tracks(B, L, style, emo, style_track, emotion_track)
+            with torch.cuda.device(dv):
+                check(lib().fdm_audio_prepare_tracks(self.h, hub.data_ptr(), B, N, fw, st.data_ptr(), et.data_ptr() if et is not None else None,
+                                                     L, int(bool(cfg)), _stream()))
+            self._inputs = (hub, st, et)
+            self.B, self.L, self.M, self.cfg, self.S = B, L, B * L, bool(cfg), 1
+            return L
+        if style is None:
+            raise FdmError("prepare needs style (or style_track)")
         if style.dim() == 1:
             style = style.unsqueeze(0).expand(B * S, -1)
         if style.shape[0] != B * S:
@@ -239,7 +279,7 @@ class DenoiserPlan:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def prepare_windows(self, hub, style, emo=None, L_total=None, window=None, overlap=60, cfg=False):
+    def prepare_windows(self, hub, style=None, emo=None, L_total=None, window=None, overlap=60, cfg=False, style_track=None, emotion_track=None):
         """Clips longer than max_len (fdm_audio_prepare_windows): hub [B, N, fw] features of B whole long clips, style [B, n_style],
         emo [B, n_emo]; L_total latent frames (default N // pair, no cap) as windows of `window` (default max_len) frames overlapping
         by >= `overlap`.  The plan's batch becomes B * n windows; sample_windows takes and returns latents in the long layout
@@ -250,6 +290,18 @@ class DenoiserPlan:
         L_total = N // p.pair if L_total is None else int(L_total)
         window = p.max_len if window is None else int(window)
         starts = window_starts(L_total, window, overlap)
+        if style_track is not None or emotion_track is not None:      # [B, L_total, n] per-frame conditions (fdm_audio_prepare_windows_tracks)
+            st, et = self._tracks(B, L_total, style, emo, style_track, emotion_track)
+            with torch.cuda.device(dv):
+                check(lib().fdm_audio_prepare_windows_tracks(self.h, hub.data_ptr(), B, N, fw, st.data_ptr(), et.data_ptr() if et is not None else None,
+                                                             L_total, window, int(overlap), int(bool(cfg)), _stream()))
+            self._inputs = (hub, st, et)
+            W = min(window, L_total)
+            self.B, self.L, self.M, self.cfg, self.S = B * len(starts), W, B * len(starts) * W, bool(cfg), 1
+            self.B_long, self.L_total, self.starts = B, L_total, starts
+            return starts
+        if style is None:
+            raise FdmError("prepare_windows needs style (or style_track)")
         if style.dim() == 1:
             style = style.unsqueeze(0).expand(B, -1)
         style = _dev(style, dv)
@@ -314,6 +366,15 @@ class DenoiserPlan:
             record.extend(rec[i] for i in range(n_rec))
         return out
 
+    def peek_windows(self):
+        """fdm_window_peek: the window rows of a windowed plan as they stand, [B, n_windows, W*G, c] (inspection; changes nothing)."""
+        if not self.get("windows"):
+            raise FdmError("call prepare_windows() first")
+        out = torch.empty(self.B_long, len(self.starts), self.L * self.p.G, self.p.c, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().fdm_window_peek(self.h, out.data_ptr(), _stream()))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def _sampler_args(self, a, kind, steps=None, t_list=None, tables=None):
         """kind / steps / t_list / tables of a sampler definition into fdm_sample_args; returns what must stay alive during the call."""
@@ -373,7 +434,8 @@ class DenoiserPlan:
         check(lib().fdm_slot_sampler_info(self.h, int(id), C.byref(k), C.byref(n)))
         return k.value, n.value
 
-    def admit(self, slot, hub, style, emo=None, x_T=None, L=None, seed=0, clip_id=0, sampler=0, cfg_scale=None):
+    def admit(self, slot, hub, style=None, emo=None, x_T=None, L=None, seed=0, clip_id=0, sampler=0, cfg_scale=None, style_track=None,
+              emotion_track=None):
         """fdm_slot_admit: one clip into an idle slot, between steps.  hub [N, fw] (or [1, N, fw]) audio-encoder features, style
         [n_style], emo [n_emo], x_T [L_clip*G, c] (or [1, ...]); L = latent frames of the clip (default N // pair).  Its latent will
         equal the solo sample_* call on a (1, L_clip) plan with the same x_T, seed and clip0 = clip_id -- with the sampler the
@@ -382,11 +444,20 @@ class DenoiserPlan:
         hub = _dev(hub, dv).reshape(-1, hub.shape[-1])
         N, fw = hub.shape
         L = N // p.pair if L is None else int(L)
-        style = _dev(style, dv).reshape(-1)
-        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
         x = _dev(x_T, dv).reshape(-1)
         if x.numel() != L * p.d:
             raise FdmError(f"x_T has {x.numel()} elements, expected L_clip*G*c = {L * p.d}")
+        if style_track is not None or emotion_track is not None:      # [L_clip, n] per-frame conditions (fdm_slot_admit_tracks)
+            st, et = self._tracks(1, L, None if style is None else torch.as_tensor(style).reshape(-1),
+                                  None if emo is None else torch.as_tensor(emo).reshape(-1), style_track, emotion_track)
+            scale = self._slot_scale if cfg_scale is None else float(cfg_scale)
+            with torch.cuda.device(dv):
+                check(lib().fdm_slot_admit_tracks(self.h, int(slot), hub.data_ptr(), N, fw, st.data_ptr(), et.data_ptr() if et is not None else None,
+                                                  L, x.data_ptr(), int(seed), int(clip_id), int(sampler), scale, _stream()))
+            self._slot_inputs[int(slot)] = (hub, st, et, x)
+            return L
+        style = _dev(style, dv).reshape(-1)
+        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
         with torch.cuda.device(dv):
             if sampler == 0 and cfg_scale is None:
                 check(lib().fdm_slot_admit(self.h, int(slot), hub.data_ptr(), N, fw, style.data_ptr(), emo.data_ptr() if emo is not None else None,
@@ -398,7 +469,8 @@ class DenoiserPlan:
         self._slot_inputs[int(slot)] = (hub, style, emo, x)      # read asynchronously on this stream: kept until the slot is admitted again
         return L
 
-    def admit_long(self, slots, hub, style, emo=None, x_T=None, L_total=None, overlap=60, seed=0, clip_id=0, sampler=0, cfg_scale=None):
+    def admit_long(self, slots, hub, style=None, emo=None, x_T=None, L_total=None, overlap=60, seed=0, clip_id=0, sampler=0, cfg_scale=None,
+                   style_track=None, emotion_track=None):
         """fdm_slot_admit_long: a recording of L_total > L latent frames into the idle slots `slots`, one window each (slots[0] leads
         the group); len(slots) must be the window count of window_starts(L_total, L, overlap).  hub [N, fw] (or [1, N, fw]) features
         of the whole recording, x_T [L_total*G, c] (or [1, ...]).  Its latent will equal sample_windows on a B = 1 windowed plan
@@ -407,12 +479,22 @@ class DenoiserPlan:
         hub = _dev(hub, dv).reshape(-1, hub.shape[-1])
         N, fw = hub.shape
         L_total = N // p.pair if L_total is None else int(L_total)
-        style = _dev(style, dv).reshape(-1)
-        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
         x = _dev(x_T, dv).reshape(-1)
         if x.numel() != L_total * p.d:
             raise FdmError(f"x_T has {x.numel()} elements, expected L_total*G*c = {L_total * p.d}")
         ids = (C.c_int * len(slots))(*[int(s) for s in slots])
+        if style_track is not None or emotion_track is not None:      # [L_total, n] per-frame conditions (fdm_slot_admit_long_tracks)
+            st, et = self._tracks(1, L_total, None if style is None else torch.as_tensor(style).reshape(-1),
+                                  None if emo is None else torch.as_tensor(emo).reshape(-1), style_track, emotion_track)
+            scale = self._slot_scale if cfg_scale is None else float(cfg_scale)
+            with torch.cuda.device(dv):
+                check(lib().fdm_slot_admit_long_tracks(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, st.data_ptr(),
+                                                       et.data_ptr() if et is not None else None, L_total, int(overlap), x.data_ptr(),
+                                                       int(seed), int(clip_id), int(sampler), scale, _stream()))
+            self._slot_inputs[int(slots[0])] = (hub, st, et, x)
+            return L_total
+        style = _dev(style, dv).reshape(-1)
+        emo = _dev(emo, dv).reshape(-1) if (p.n_emo and emo is not None) else None
         with torch.cuda.device(dv):
             if sampler == 0 and cfg_scale is None:
                 check(lib().fdm_slot_admit_long(self.h, C.cast(ids, C.c_void_p), len(slots), hub.data_ptr(), N, fw, style.data_ptr(),

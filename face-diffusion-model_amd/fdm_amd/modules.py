@@ -327,18 +327,27 @@ class _FDMBase(ParamTree):
             self._hub_key = _TensorKey(audio)
         return self._hub
 
-    def prepare(self, audio, L, style, emo=None, cfg=False):
+    def prepare(self, audio, L, style, emo=None, cfg=False, style_track=None, emotion_track=None):
         """Per-batch tables of the plan.  style [B, n] (one condition per clip, the reference's call shape) or [B*S, n] with
         S > 1: S conditions per clip -- the style loop of samples/sample_diffusion_vocaset.py:71-83 as ONE step program
-        (rows in (clip, condition) order; the audio encoder and the audio tables still run once per clip)."""
+        (rows in (clip, condition) order; the audio encoder and the audio tables still run once per clip).
+        style_track / emotion_track ([L', n] or [B, L', n], L' >= L): one vector per latent frame (DenoiserPlan.prepare); S = 1 only,
+        and the tables are rebuilt on every call (a track is not part of the cache key)."""
         hub = self.audio_features(audio)
         plan = self.plan(hub.device)
+        B = hub.shape[0]
+        st = style.reshape(-1, style.shape[-1])
+        em = None if emo is None else emo.reshape(-1, emo.shape[-1])
+        if style_track is not None or emotion_track is not None:
+            if st.shape[0] not in (1, B) or (em is not None and em.shape[0] not in (1, B)):
+                raise FdmError("condition tracks take one style / emotion row per clip (no conditions per clip)")
+            plan.prepare(hub, st if st.shape[0] == B else st[0], em if (em is None or em.shape[0] == B) else em[0], L=L, cfg=cfg,
+                         style_track=style_track, emotion_track=emotion_track)
+            self._prep_key = None
+            return plan
         key = (L, bool(cfg), tuple(style.flatten().tolist()), None if emo is None else tuple(emo.flatten().tolist()))
         pk = self._prep_key
         if not (pk is not None and pk[0].matches(hub) and pk[1] == key):
-            B = hub.shape[0]
-            st = style.reshape(-1, style.shape[-1])
-            em = None if emo is None else emo.reshape(-1, emo.shape[-1])
             rows = max(st.shape[0], 1 if em is None else em.shape[0], B)
             if rows % B:
                 raise FdmError(f"{rows} condition rows for {B} clips: expected a multiple (conditions per clip)")
@@ -502,12 +511,12 @@ class GaussianDiffusion(nn.Module):
             return model, style, emo.reshape(-1, emo.shape[-1])
         return model, cond[0], None
 
-    def _plan(self, audio, shape, cond, guidance_scale=None):
+    def _plan(self, audio, shape, cond, guidance_scale=None, style_track=None, emotion_track=None):
         model, style, emo = self._split_cond(cond)
         cfg = isinstance(self.denoise_fn, ClassifierFreeSampleModel) or guidance_scale is not None
         scale = guidance_scale if guidance_scale is not None else getattr(self.denoise_fn, "level", 2.5)
         L = shape[1] // model.preset.G
-        return model.prepare(audio, L, style, emo, cfg=cfg), scale
+        return model.prepare(audio, L, style, emo, cfg=cfg, style_track=style_track, emotion_track=emotion_track), scale
 
     @torch.no_grad()
     def p_mean_variance(self, x, t, clip_denoised, audio, *cond):
@@ -529,11 +538,12 @@ class GaussianDiffusion(nn.Module):
         return plan.sample_ddpm(x.float().contiguous(), [tt], noise=z.reshape(1, *x.shape), cfg_scale=scale, use_graph=False)
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, audio, *cond, noise=None, seed=None, t_range=None, guidance_scale=None, x_T=None, clip0=0):
+    def p_sample_loop(self, shape, audio, *cond, noise=None, seed=None, t_range=None, guidance_scale=None, x_T=None, clip0=0,
+                      style_track=None, emotion_track=None):
         """Build-added keywords (default = reference behaviour): noise=(x_T, z[T]) injects everything (parity runs); x_T= fixes the
         start with in-kernel Philox noise keyed by (seed, clip0 + row block, step): a clip's result depends on its index, not on
-        the batch it is sampled in."""
-        plan, scale = self._plan(audio, shape, cond, guidance_scale)
+        the batch it is sampled in.  style_track / emotion_track: per-frame conditions (FDM.prepare)."""
+        plan, scale = self._plan(audio, shape, cond, guidance_scale, style_track, emotion_track)
         dev = plan.device
         if t_range is None:
             t_range = (self.num_timesteps - 1, -1) if self.full_chain else (999, 499)
@@ -550,24 +560,24 @@ class GaussianDiffusion(nn.Module):
         return self.p_sample_loop(latent_motion_shape, audio, *cond, **kw)
 
     @torch.no_grad()
-    def ddim_sample(self, audio, latent_motion_shape, id_one_hot, steps=500, *, x_T=None, guidance_scale=None):
+    def ddim_sample(self, audio, latent_motion_shape, id_one_hot, steps=500, *, x_T=None, guidance_scale=None, style_track=None):
         """id_one_hot [1, n] / [B, n]: the reference's call.  [B*S, n] with S > 1: the S style conditions of every clip in
         one call (the sampler's style loop, samples/sample_diffusion_vocaset.py:71-83, batched); returns [B*S, L*G, c] in
         (clip, condition) order, each block bit-identical to the one-condition call with the same x_T block."""
-        plan, scale = self._plan(audio, latent_motion_shape, (id_one_hot,), guidance_scale)
+        plan, scale = self._plan(audio, latent_motion_shape, (id_one_hot,), guidance_scale, style_track, None)
         shape = (plan.B,) + tuple(latent_motion_shape[1:])
         x_T = torch.randn(shape, device=plan.device) if x_T is None else x_T.to(plan.device)
         return plan.sample_ddim(x_T.float().contiguous(), steps, cfg_scale=scale)
 
     @torch.no_grad()
     def fast_sample(self, audio, latent_motion_shape, *cond, steps=20, sampler="dpmpp2m", eta=0.0, x_T=None, seed=None,
-                    guidance_scale=None, clip0=0):
+                    guidance_scale=None, clip0=0, style_track=None, emotion_track=None):
         """Build-added: few-step sampling with a table-driven multistep solver (DenoiserPlan.sample_tables).  sampler "dpmpp2m"
         (DPM-Solver++ 2M: second order, one denoiser call per step) or "ddim_eta" (DDIM with eta in [0, 1]; eta > 0 draws
         Philox noise keyed by (seed, clip0 + row block, step)).  `steps` pairs of the reference's DDIM grid, all executed: the
         last one goes to data.  cond / x_T / seed / clip0 / guidance_scale as sample().  What 20 steps do to perceptual quality
         on trained checkpoints is unmeasured."""
-        plan, scale = self._plan(audio, latent_motion_shape, cond, guidance_scale)
+        plan, scale = self._plan(audio, latent_motion_shape, cond, guidance_scale, style_track, emotion_track)
         t_list, tables = schedule.sampler_tables(sampler, steps, eta, self.num_timesteps)
         shape = (plan.B,) + tuple(latent_motion_shape[1:])
         x_T = torch.randn(shape, device=plan.device) if x_T is None else x_T.to(plan.device)
@@ -639,7 +649,7 @@ class VQAutoEncoder(ParamTree):
         emo = None if one_hot is None else one_hot.reshape(-1, one_hot.shape[-1])
         return self.plan(x.device).encode(x, emo)
 
-    def quant(self, x, one_hot=None, stats=True):
+    def quant(self, x, one_hot=None, stats=True, emotion_track=None):
         """-> (z_q [B, c, L*G], emb_loss, (perplexity, min_encodings [B*L*G, 256], indices [B*L*G, 1])): the reference's
         whole tuple (models/vq_vae_vocaset.py:31-33 -> models/lib/quantizer.py:35-64, beta = 0.25), all of it on the device.
         stats=False (what the sampling pipeline passes: it uses z_q only, as every sampler of the reference does) skips the
@@ -648,9 +658,9 @@ class VQAutoEncoder(ParamTree):
             raise FdmError("VQAutoEncoder.quant runs on the HIP path only")
         emo = None if one_hot is None else one_hot.reshape(-1, one_hot.shape[-1])
         if not stats:
-            zq, idx = self.plan(x.device).quant(x, emo)
+            zq, idx = self.plan(x.device).quant(x, emo, emotion_track=emotion_track)      # (a track: every frame in its own emotion's codebook)
             return zq, None, (None, None, idx)
-        return self.plan(x.device).quant_full(x, emo, beta=0.25)
+        return self.plan(x.device).quant_full(x, emo, beta=0.25, emotion_track=emotion_track)
 
     def decode(self, quant):
         if not quant.is_cuda:

@@ -269,6 +269,14 @@ def small_linear(x, W, bias, out, B, K, d, act=ACT_NONE):
     check(lib().fdm_op_small_linear(_p(x), _p(W), _p(bias), _p(out), B, K, d, act, stream()))
 
 
+def cond_rows(pe, style, emo, sw, sb, ew, eb, out, B, L, L_clip, d, *, L_track=None, uncond_off=0, act=ACT_NONE):
+    """fdm_op_cond_rows: out [B*L, d] (and the uncond half uncond_off elements on) from per-frame tracks style [B, L_track, n_style],
+    emo [B, L_track, n_emo] or None."""
+    check(lib().fdm_op_cond_rows(_p(pe), _p(style), _p(emo), _p(sw), _p(sb), _p(ew), _p(eb), _p(out), int(uncond_off), B, L, L_clip,
+                                 style.shape[-2] if L_track is None else L_track, d, style.shape[-1], emo.shape[-1] if emo is not None else 0,
+                                 act, stream()))
+
+
 def pad_rows(inp, out, B, L, d, pad, zero=False):
     check(lib().fdm_op_pad_rows(_p(inp), _p(out), B, L, d, pad, code_of(inp), int(zero), stream()))
 

@@ -81,8 +81,12 @@ def _clip_x_T(shape, S, seed):
 
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
-            ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0):
+            ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    style_track [L', n_style] / emotion_track [L', n_emo] (or [B, L', n]; L' >= L, fdm_amd.tracks.keyframes): one vector per latent
+    frame instead of one per clip, either alone or both; the quantiser takes every frame in the codebook of its own emotion.  One
+    condition per clip only (S = 1).  A track whose rows are all equal gives the result of the one-hot call, bit for bit.
 
     sampler "dpmpp2m" | "ddim_eta" (with eta=): `sampler_steps` steps of the table-driven multistep sampler
     (GaussianDiffusion.fast_sample) from the same per-clip x_T, on every preset; None = the paths below, unchanged.
@@ -112,7 +116,16 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     hub = model.audio_features(audio)
     L = min(hub.shape[1] // p.pair, p.max_len)        # samples/sample_diffusion_vocaset.py:76 (no interpolation, a17b)
     shape = (B, L * p.G, p.c)
+    trk = {}
+    if style_track is not None or emotion_track is not None:
+        if S != 1:
+            raise ValueError("condition tracks take one condition per clip")
+        if emotion_track is not None and not p.n_emo:
+            raise ValueError(f"preset {p.name} takes no emotion")
+        trk = dict(style_track=style_track)
     if p.n_emo:
+        if trk:
+            trk["emotion_track"] = emotion_track
         if emotion_one_hot is None:
             emotion_one_hot = torch.eye(p.n_emo)[4:5].expand(rows, -1)
         emotion_one_hot = emotion_one_hot.reshape(-1, emotion_one_hot.shape[-1]).to(device)
@@ -122,20 +135,21 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
             id_one_hot = id_one_hot.expand(rows, -1)
         if sampler:
             latent = diffusion.fast_sample(audio, shape, emotion_one_hot, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta,
-                                           seed=seed, x_T=_clip_x_T(shape, S, seed))
+                                           seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
         else:
-            latent = diffusion.sample(audio, shape, emotion_one_hot, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed))
-        quanted, _, _ = autoencoder.quant(latent, emotion_one_hot, stats=False)
+            latent = diffusion.sample(audio, shape, emotion_one_hot, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
+        et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L, :]
+        quanted, _, _ = autoencoder.quant(latent, emotion_one_hot, stats=False, emotion_track=et)
     else:
         if sampler:
             latent = diffusion.fast_sample(audio, shape, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta, seed=seed,
-                                           x_T=_clip_x_T(shape, S, seed))
+                                           x_T=_clip_x_T(shape, S, seed), **trk)
         elif ddim_steps:
             g = torch.Generator(device="cpu").manual_seed(seed)
             x_T = torch.randn(shape, generator=g).repeat_interleave(S, dim=0)
-            latent = diffusion.ddim_sample(audio, shape, id_one_hot, ddim_steps, x_T=x_T)
+            latent = diffusion.ddim_sample(audio, shape, id_one_hot, ddim_steps, x_T=x_T, **trk)
         else:
-            latent = diffusion.sample(audio, shape, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed))
+            latent = diffusion.sample(audio, shape, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
         quanted, _, _ = autoencoder.quant(latent, stats=False)
     out = autoencoder.decode(quanted)
     if template is not None:
@@ -146,7 +160,8 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
-                 seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False):
+                 seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
+                 style_track=None, emotion_track=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
 
     The reference's samplers take the clips of a loader one at a time (bs = 1: samples/sample_diffusion_vocaset.py:51,71-83),
@@ -164,7 +179,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     batch_stages: the two stages that are not causal run batched too -- ONE audio-encoder call over all clips of the call
     (encode_many) and, per group, ONE padded quant and ONE decode (VQAutoEncoder.decode_many); every kernel that looks across time
     carries the clips' own lengths, and the returned lists are torch.equal to the per-clip path's.  Off by default: its gain is
-    unmeasured (profiles/ragged/README.md)."""
+    unmeasured (profiles/ragged/README.md).
+    style_track / emotion_track: per-frame conditions as in animate(), one per clip: a list with a track [L', n] (L' >= the clip's
+    frames) or None per clip, or one track for all.  A group with a track in it is sampled and quantised with tracks throughout (a
+    clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
     n = len(audios)
@@ -180,6 +198,23 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             return default
         x = torch.as_tensor(x[b] if isinstance(x, (list, tuple)) else x, dtype=torch.float32).reshape(-1, width)
         return x[b:b + 1] if x.shape[0] == n else x[:1]
+    per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
+
+    def group_track(tr, vecs, grp, Lmax, width):
+        """[len(grp), Lmax, width]: clip i's track on its own frames (its last row repeated on the tail rows, which belong to no
+        frame), its one-hot on every frame when it has no track; None when no clip of the group has a track"""
+        if not width or all(per(tr, b) is None for b in grp):
+            return None
+        out = vecs.reshape(len(grp), 1, width).expand(len(grp), Lmax, width).clone()
+        for i, b in enumerate(grp):
+            t = per(tr, b)
+            if t is not None:
+                t = torch.as_tensor(t, dtype=torch.float32).reshape(-1, width)
+                if t.shape[0] < Ls[b]:
+                    raise ValueError(f"clip {b}: a track of {t.shape[0]} rows for {Ls[b]} latent frames")
+                out[i, :Ls[b]] = t[:Ls[b]].to(out.device)
+                out[i, Ls[b]:] = out[i, Ls[b] - 1]
+        return out
     ddim = bool(ddim_steps) and not p.n_emo and not sampler
     order = sorted(range(n), key=lambda b: Ls[b]) if ddim else list(range(n))
     verts, lats = [None] * n, [None] * n
@@ -203,26 +238,33 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             shape = (len(grp), Lmax * p.G, p.c)
             if p.n_emo:
                 emos = torch.cat([row(emotion_one_hots, b, p.n_emo, torch.eye(p.n_emo)[4:5]) for b in grp]).to(device)
+            st_g = group_track(style_track, ids, grp, Lmax, p.n_style)
+            et_g = group_track(emotion_track, emos, grp, Lmax, p.n_emo) if p.n_emo else None
+            trk = {}
+            if st_g is not None or et_g is not None:
+                trk = dict(style_track=st_g, emotion_track=et_g) if p.n_emo else dict(style_track=st_g)
             if sampler:
                 lat = diffusion.fast_sample(dummy, shape, *((emos, ids) if p.n_emo else (ids,)), steps=sampler_steps, sampler=sampler,
-                                            eta=eta, seed=seed, x_T=x_T, clip0=g0)
+                                            eta=eta, seed=seed, x_T=x_T, clip0=g0, **trk)
             elif p.n_emo:
-                lat = diffusion.sample(dummy, shape, emos, ids, seed=seed, x_T=x_T, clip0=g0)
+                lat = diffusion.sample(dummy, shape, emos, ids, seed=seed, x_T=x_T, clip0=g0, **trk)
             elif ddim_steps:
-                lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T)
+                lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T, **trk)
             else:
-                lat = diffusion.sample(dummy, shape, ids, seed=seed, x_T=x_T, clip0=g0)
+                lat = diffusion.sample(dummy, shape, ids, seed=seed, x_T=x_T, clip0=g0, **trk)
             outs = None
             if batch_stages:        # one padded quant (per row) and one decode that knows each clip's length
                 lat_g = lat[:, :max(Ls[b] for b in grp) * p.G].contiguous()        # (not the bucket's rows: they belong to no clip)
-                qs = autoencoder.quant(lat_g, emos, stats=False)[0] if p.n_emo else autoencoder.quant(lat_g, stats=False)[0]
+                etq = None if et_g is None else et_g[:, :lat_g.shape[1] // p.G]
+                qs = autoencoder.quant(lat_g, emos, stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lat_g, stats=False)[0]
                 outs = autoencoder.decode_many(qs, [Ls[b] for b in grp])
             for i, b in enumerate(grp):
                 lb = lat[i:i + 1, :Ls[b] * p.G].contiguous()
                 if outs is not None:
                     out = outs[i:i + 1, :Ls[b]].contiguous()
                 else:
-                    q = autoencoder.quant(lb, emos[i:i + 1], stats=False)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
+                    etq = None if et_g is None else et_g[i:i + 1, :Ls[b]]
+                    q = autoencoder.quant(lb, emos[i:i + 1], stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
                     out = autoencoder.decode(q)
                 if templates is not None:
                     tp = templates[b] if isinstance(templates, (list, tuple)) else templates
@@ -235,7 +277,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
-                 window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0):
+                 window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None):
     """audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
     encoder frames // pair (no 600-frame cap: animate() keeps the reference's crop).
 
@@ -267,7 +309,9 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     L_total = hub.shape[1] // p.pair
     plan = model.plan(hub.device)
     model._prep_key = None            # the plan leaves the state FDM.prepare() cached
-    plan.prepare_windows(hub, style, emo, L_total=L_total, window=window, overlap=overlap, cfg=cfg)
+    # style_track / emotion_track [L', n] or [B, L', n], L' >= L_total: one vector per latent frame of the whole recording (animate())
+    plan.prepare_windows(hub, style, emo, L_total=L_total, window=window, overlap=overlap, cfg=cfg, style_track=style_track,
+                         emotion_track=emotion_track)
     shape = (B, L_total * p.G, p.c)
     x_T = torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
     if sampler:
@@ -279,7 +323,8 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     else:
         ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
         latent = plan.sample_windows(x_T, "ddpm", t_list=ts, seed=seed, cfg_scale=scale)
-    quanted = autoencoder.quant(latent, emo, stats=False)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
+    et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
+    quanted = autoencoder.quant(latent, emo, stats=False, emotion_track=et)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
     out = autoencoder.decode(quanted)
     if template is not None:
         out = out + torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
@@ -414,7 +459,7 @@ class SlotServer:
 
     @torch.no_grad()
     def submit(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
-               sampler_steps=None, eta=None, cfg_scale=None):
+               sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
         """One processor-normalised waveform [n] -> a handle.  Runs the audio encoder at the clip's own length, draws x_T as
         animate() does and admits the clip, or queues it until a slot is free.  ddim_steps / sampler / sampler_steps / eta /
         cfg_scale: the request's own sampler and guidance scale (class docstring); none given = the server's."""
@@ -434,16 +479,30 @@ class SlotServer:
         x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
         h = self._next
         self._next += 1
-        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, sampler=key, scale=scale))
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, sampler=key, scale=scale,
+                                **self._tracks(L, style_track, emotion_track)))
         self._fill()
         return h
 
+    def _tracks(self, L, style_track, emotion_track):
+        """The request's condition tracks (animate()): [L', n] with L' >= L, cut to the clip's frames; {} for a request without."""
+        if style_track is None and emotion_track is None:
+            return {}
+        cut = lambda t, n: None if (t is None or not n) else torch.as_tensor(t, dtype=torch.float32).reshape(-1, n)[:L].to(self.device)  # noqa: E731
+        return dict(st=cut(style_track, self.p.n_style), et=cut(emotion_track, self.p.n_emo), tracks=True)
+
+    def _quant(self, lat, r):
+        if not self.p.n_emo:
+            return self.ae.quant(lat, stats=False)[0]
+        return self.ae.quant(lat, r["emo"], stats=False, emotion_track=r.get("et"))[0]
+
     @torch.no_grad()
     def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0, ddim_steps=None, sampler=None,
-                    sampler_steps=None, eta=None, cfg_scale=None):
+                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
         """Several requests at once: ONE audio-encoder call over the waveforms' unequal lengths (encode_many), then each request is
         admitted or queued exactly as submit() does it, in the given order.  templates / id_one_hots / emotion_one_hots / seeds:
         one per request (lists) or one for all, and so are ddim_steps / sampler / sampler_steps / eta / cfg_scale (submit()).
+        style_track / emotion_track: a list with one track (or None) per request, or one for all (submit()).
         Returns the handles; results equal submit() in a loop bit for bit."""
         self._check()
         p, dev = self.p, self.device
@@ -467,7 +526,7 @@ class SlotServer:
             h = self._next
             self._next += 1
             self._queue.append(dict(handle=h, hub=hubs[b], L=Ls[b], ids=ids.to(dev), emo=emo, x_T=x_T, seed=seed, template=per(templates, b),
-                                    sampler=reqs[b][0], scale=reqs[b][1]))
+                                    sampler=reqs[b][0], scale=reqs[b][1], **self._tracks(Ls[b], per(style_track, b), per(emotion_track, b))))
             handles.append(h)
         self._fill()
         return handles
@@ -488,6 +547,8 @@ class SlotServer:
                 if r["sid"] is None:       # the bank is full of samplers in use: wait for a slot to leave
                     return
                 own = dict(sampler=r["sid"], cfg_scale=r["scale"])
+            if r.get("tracks"):                # per-frame conditions (fdm_slot_admit_tracks / fdm_slot_admit_long_tracks)
+                own = dict(own, style_track=r["st"], emotion_track=r["et"])
             if r.get("windows"):
                 try:
                     self.plan.admit_long(free[:r["windows"]], r["hub"], r["ids"], r["emo"], r["x_T"], L_total=r["L"], overlap=self.overlap,
@@ -507,7 +568,7 @@ class SlotServer:
 
     @torch.no_grad()
     def submit_long(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
-                    sampler_steps=None, eta=None, cfg_scale=None):
+                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
         """One processor-normalised waveform [n] of ANY length -> a handle.  The audio encoder runs over the whole waveform and
         L_total = frames // pair is kept whole (submit() crops to a slot).  L_total <= max_frames is an ordinary request; a longer
         one becomes a group of slots (class docstring) with x_T drawn as animate_long draws it.  ValueError if the request can
@@ -538,7 +599,7 @@ class SlotServer:
         h = self._next
         self._next += 1
         self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, windows=windows,
-                                sampler=key, scale=scale))
+                                sampler=key, scale=scale, **self._tracks(L, style_track, emotion_track)))
         self._fill()
         return h
 
@@ -560,7 +621,7 @@ class SlotServer:
             if r is None or self.plan.slot_state(s)[2] != SLOT_FINISHED:
                 continue
             lat = self.plan.read_slot(s, r["L"])
-            q = self.ae.quant(lat, r["emo"], stats=False)[0] if self.p.n_emo else self.ae.quant(lat, stats=False)[0]
+            q = self._quant(lat, r)
             out = self.ae.decode(q)
             if r["template"] is not None:
                 out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
@@ -580,7 +641,7 @@ class SlotServer:
             if r is None or not r.get("windows") or r["slots"][0] != s or self.plan.slot_state(s)[2] != SLOT_FINISHED:
                 continue
             lat = self.plan.read_long(s)
-            q = self.ae.quant(lat, r["emo"], stats=False)[0] if self.p.n_emo else self.ae.quant(lat, stats=False)[0]
+            q = self._quant(lat, r)
             out = self.ae.decode(q)
             if r["template"] is not None:
                 out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
@@ -602,7 +663,15 @@ class SlotServer:
         pad = torch.zeros(len(done), max(r["L"] for r in reqs) * p.G, p.c, device=lats[0].device)
         for i, lat in enumerate(lats):
             pad[i, :lat.shape[1]] = lat[0]
-        qs = self.ae.quant(pad, torch.cat([r["emo"] for r in reqs]), stats=False)[0] if p.n_emo else self.ae.quant(pad, stats=False)[0]
+        if p.n_emo and any(r.get("et") is not None for r in reqs):      # a track in the batch: every clip as a track (its one-hot on every frame otherwise)
+            Lm = pad.shape[1] // p.G
+            et = torch.stack([r["emo"].reshape(1, -1).expand(Lm, -1).clone() for r in reqs])
+            for i, r in enumerate(reqs):
+                if r.get("et") is not None:
+                    et[i, :r["L"]] = r["et"]
+            qs = self.ae.quant(pad, None, stats=False, emotion_track=et)[0]
+        else:
+            qs = self.ae.quant(pad, torch.cat([r["emo"] for r in reqs]), stats=False)[0] if p.n_emo else self.ae.quant(pad, stats=False)[0]
         outs = self.ae.decode_many(qs, [r["L"] for r in reqs])
         self.batched_decodes.append(len(done))
         for i, (s, r) in enumerate(zip(done, reqs)):
@@ -630,6 +699,27 @@ class SlotServer:
         return self.results()
 
 
+def add_track_arguments(ap, p):
+    """--style_track / --emotion_track / --track_ramp of the demo and sampler command lines (fdm_amd.tracks.from_spec)."""
+    ap.add_argument("--style_track", type=str, default=None,
+                    help='build-added: style per time, "seconds:index,..." e.g. "0:0,3.5:2" (one vector per latent frame)')
+    if p.n_emo:
+        ap.add_argument("--emotion_track", type=str, default=None,
+                        help=f'build-added: emotion per time, "seconds:name,..." e.g. "0:happy,21.0:sad,40.0:happy" ({" | ".join(EMOTIONS)})')
+    ap.add_argument("--track_ramp", type=float, default=0.0, help="build-added: seconds of linear cross-fade centred on every change of a track")
+
+
+def track_arguments(a, p, L):
+    """{style_track=, emotion_track=} of animate() from the parsed flags, as tracks of L latent frames; {} when none was given."""
+    from . import tracks
+    out = {}
+    if a.style_track:
+        out["style_track"] = tracks.from_spec(p, L, a.style_track, [str(i) for i in range(p.n_style)], ramp=a.track_ramp)
+    if p.n_emo and a.emotion_track:
+        out["emotion_track"] = tracks.from_spec(p, L, a.emotion_track, EMOTIONS, ramp=a.track_ramp)
+    return out
+
+
 def demo_main(preset, argv=None):
     """CLI of demo/demo_{vocaset,biwi,3d_mead}.py:109-121: same flags, output = np.save(<audio_path>/<stem>.npy, [1, L, V3])."""
     import argparse
@@ -654,6 +744,7 @@ def demo_main(preset, argv=None):
     ap.add_argument("--long_audio", type=str, default="truncate", choices=["truncate", "window"],
                     help="build-added: audio past max_len latent frames: truncate (the reference's crop) or window (animate it all)")
     ap.add_argument("--window_overlap", type=int, default=60, help="build-added: frames shared by neighbouring windows (--long_audio window)")
+    add_track_arguments(ap, p)
     a = ap.parse_args(argv)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
                                  cfg_level=None)
@@ -665,6 +756,8 @@ def demo_main(preset, argv=None):
     if p.n_emo:
         emo = torch.eye(p.n_emo)[EMOTIONS.index(a.emotion)].unsqueeze(0)
     fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
+    # tracks cover every latent frame the audio can give (16 kHz, 320 samples per encoder frame); the calls take the frames they need
+    fast.update(track_arguments(a, p, max(len(wav) // 320 // p.pair + 2, p.max_len)))
     if a.long_audio == "window":
         out, _ = animate_long(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed,
                               overlap=a.window_overlap, device=a.device, **fast)

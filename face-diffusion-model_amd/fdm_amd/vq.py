@@ -84,14 +84,33 @@ class VQPlan:
         self._in = (x, em)
         return out
 
-    def quant(self, z, emo=None):
-        """z [B, R, c] fp32 -> (z_q [B, c, R] fp32, idx [B*R, 1] int64), book chosen by argmax(one_hot)."""
+    def _emo_track(self, track, B, R):
+        """emotion_track [L, n_books] or [B, L, n_books] with L = R / G -> device [B, L, n_books]"""
+        p = self.p
+        t = torch.as_tensor(track).detach().to(device=self.device, dtype=torch.float32)
+        t = t.unsqueeze(0).expand(B, -1, -1) if t.dim() == 2 else t
+        if R % p.G or t.dim() != 3 or tuple(t.shape) != (B, R // p.G, p.n_books):
+            raise FdmError(f"emotion track has shape {tuple(t.shape)}, expected [{B}, R / G = {R / p.G:g}, {p.n_books}]")
+        return t.contiguous()
+
+    def quant(self, z, emo=None, emotion_track=None):
+        """z [B, R, c] fp32 -> (z_q [B, c, R] fp32, idx [B*R, 1] int64), book chosen by argmax(one_hot).  emotion_track [B, R / G,
+        n_books] (or [R / G, n_books]): every frame in the codebook of its own emotion, argmax of its row (fdm_vq_quant_tracks)."""
         from ._lib import check, lib
         p, dv = self.p, self.device
         z = z.detach().to(device=dv, dtype=torch.float32).contiguous()
         B, R, c = z.shape
         if c != p.c:
             raise FdmError(f"latent width {c} != zquant_dim {p.c}")
+        if emotion_track is not None and p.n_books > 1:
+            et = self._emo_track(emotion_track, B, R)
+            zq = torch.empty(B, c, R, device=dv)
+            idx = torch.empty(B * R, 1, device=dv, dtype=torch.int64)
+            with torch.cuda.device(dv):
+                check(lib().fdm_vq_quant_tracks(self.h, z.data_ptr(), et.data_ptr(), B, R, zq.data_ptr(), idx.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream))
+            self._in = (z, None, et)
+            return zq, idx
         if p.n_books > 1 and emo is None:
             raise FdmError("this preset needs the emotion one-hot to pick the codebook slice")
         em = self._emo(emo, B, p.n_books) if p.n_books > 1 else None
@@ -100,19 +119,25 @@ class VQPlan:
         with torch.cuda.device(dv):
             check(lib().fdm_vq_quant(self.h, z.data_ptr(), em.data_ptr() if em is not None else None, B, R, zq.data_ptr(), idx.data_ptr(),
                                      torch.cuda.current_stream().cuda_stream))
-        self._in = (z, em)
+        self._in = (z, em, None)
         return zq, idx
 
-    def quant_full(self, z, emo=None, beta=0.25, min_encodings=True):
+    def quant_full(self, z, emo=None, beta=0.25, min_encodings=True, emotion_track=None):
         """The reference's whole quant() tuple (models/lib/quantizer.py:35-64, models/vq_vae_vocaset.py:16-18,31-33):
         (z_q [B, c, R], emb_loss, (perplexity, min_encodings [B*R, 256], indices [B*R, 1]))."""
         from ._lib import check, lib
-        zq, idx = self.quant(z, emo)
-        z_, em = self._in
+        zq, idx = self.quant(z, emo, emotion_track=emotion_track)
+        z_, em, et = self._in
         B, R, _ = z_.shape
         dv = self.device
         me = torch.empty(B * R, self.p.K, device=dv) if min_encodings else None
         out2 = torch.empty(2, device=dv)
+        if et is not None:
+            with torch.cuda.device(dv):
+                check(lib().fdm_vq_quant_stats_tracks(self.h, z_.data_ptr(), et.data_ptr(), idx.data_ptr(), B, R, float(beta),
+                                                      me.data_ptr() if me is not None else None, out2.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream))
+            return zq, out2[0], (out2[1], me, idx)
         with torch.cuda.device(dv):
             check(lib().fdm_vq_quant_stats(self.h, z_.data_ptr(), em.data_ptr() if em is not None else None, idx.data_ptr(), B, R,
                                            float(beta), me.data_ptr() if me is not None else None, out2.data_ptr(),

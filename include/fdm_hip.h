@@ -372,6 +372,17 @@ int fdm_op_add_rows(const float* a, int a_div, int a_mod, const float* b, int b_
  * emotion_embedd, models/fdm_vocaset.py:34,75; models/fdm_vqvae_mead.py:34-36,85 */
 int fdm_op_small_linear(const float* x, const float* W, const float* bias, float* out, int B, int K, int d,
                         int act, void* stream);
+/* Condition tracks: the conditioning addend from PER-FRAME vectors, one launch for B clips of L rows each.  style [B, L_track,
+ * n_style] and emo [B, L_track, n_emo] (or NULL) hold one vector per latent frame; only the rows l < L_clip of a clip are read.
+ *   out[b L + l] = pe[l] + act(sw style[b, l] + sb) (+ ew emo[b, l] + eb)          l <  L_clip
+ *   out[b L + l] = 0                                                                L_clip <= l < L
+ * uncond_off > 0 (elements, a whole number of rows at or past B L d): the uncond half of a CFG plan goes out at out + uncond_off in
+ * the same launch, with the row's style term and the emotion bias only (the null condition is a zero vector, models/fdm_vqvae_mead.py:
+ * 56-57).  Every element is, bit for bit, what fdm_op_small_linear on the row's vectors followed by fdm_op_add_rows gives.
+ * n_style, n_emo <= 128.  FDM_ERR_ARG for a null pe / style / sw / out or emo without ew; FDM_ERR_SHAPE for the lengths. */
+int fdm_op_cond_rows(const float* pe, const float* style, const float* emo, const float* sw, const float* sb, const float* ew,
+                     const float* eb, float* out, long long uncond_off, int B, int L, int L_clip, int L_track, int d, int n_style,
+                     int n_emo, int act, void* stream);
 /* out[b, k, :] = in[b, clamp(k - pad, 0, L-1), :] for k in [0, L + 2*pad): replicate padding, channels-last */
 int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream);
 /* the replicate form with per-clip lengths ([B] device ints, 1 <= lens[b] <= L): out[b, k, :] = in[b, clamp(k - pad, 0, lens[b]-1), :],
@@ -444,6 +455,15 @@ int fdm_op_vq_quant(const float* z, const float* codebook, const int* book, int 
  * min_encodings.  partial: >= 1024 doubles, hist: K ints of scratch.  Deterministic (fixed reduction order, integer histogram). */
 int fdm_op_vq_stats(const float* z, const float* codebook, const int* book, const long long* idx, int B, int R, int c, int K, float beta,
                     float* min_encodings, double* partial, int* hist, float* out, void* stream);
+/* The per-row forms (condition tracks): book_rows [B * R] holds one codebook slice per latent vector; an entry outside [0, n_books)
+ * reads slice 0.  fdm_op_argmax_rows writes book[r * rep + g] = argmax(x[r, 0 .. n)) for g < rep: the first maximum as torch.argmax, but a
+ * NaN never wins a comparison (torch.argmax returns a NaN's index; a row that starts with NaN gives 0), as the per-clip quantiser's
+ * argmax; it refuses, on the host, n > n_books: an argmax over more columns than the codebook has slices could name a slice that does not exist. */
+int fdm_op_argmax_rows(const float* x, int* book, long long rows, int n, int rep, int n_books, void* stream);
+int fdm_op_vq_quant_rows(const float* z, const float* codebook, const int* book_rows, int n_books, int B, int R, int c, int K,
+                         float* zq_bcl, long long* idx, void* stream);
+int fdm_op_vq_stats_rows(const float* z, const float* codebook, const int* book_rows, int n_books, const long long* idx, int B, int R, int c,
+                         int K, float beta, float* min_encodings, double* partial, int* hist, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step programs: record fdm_op_* calls, run them eagerly or as a hipGraph replayed n times.  */
@@ -568,6 +588,9 @@ int fdm_audio_prepare_windows(fdm_plan* p, const float* hub, int B, int N, int f
  * with x_T / out / noise / record in LONG layout.  Step program: the denoiser chain with its scheduler update unfused, then the blend
  * + update pass (one launch more per step than a plain plan without guidance). */
 int fdm_sample_windows(fdm_plan* p, const fdm_sample_args* a, void* stream);
+/* Inspection: the window rows of a windowed plan as they stand, out [B * n_windows, W * d] fp32 (plan clip b * n + w = window w of long
+ * clip b).  After fdm_sample_windows every frame that two windows cover holds the same bits in both, the long buffer's. */
+int fdm_window_peek(fdm_plan* p, float* out, void* stream);
 /* Slots (in-flight batching).  A plan in slot mode holds B SLOTS of up to L latent frames; every slot is a clip at ITS OWN step of one
  * shared sampler, so a clip joins a running batch at any step boundary and leaves when its own chain ends -- and its latent is, bit
  * for bit, what fdm_sample_graph returns for it on a (1, L_clip) plan with the same weights, x_T, seed and clip0 = clip_id.
@@ -689,6 +712,28 @@ int fdm_slot_admit_as(fdm_plan* p, int slot, const float* hub, int N, int fw, co
 int fdm_slot_admit_long_as(fdm_plan* p, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
                            int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale,
                            void* stream);
+/* Condition tracks: one style and one emotion vector PER LATENT FRAME instead of one per clip ("neutral, happy from frame 210 on").
+ * The conditions enter the denoiser through the addend table E0 only, one row per frame; these calls build that table from per-frame
+ * rows in one fdm_op_cond_rows launch and are otherwise the calls they are named after -- the step program, its launch count and its
+ * cached programs are the same, and a track whose rows are all equal gives the bits of the per-clip call.  Self-attention is causal
+ * and every other kernel of the step is row-local, so a change of condition at frame f0 leaves the frames before f0 bit for bit what
+ * they are without it, at every step of every sampler.  Tracks are device (or device-visible) float rows, read in stream order as
+ * hub is.  A NULL style track, or a NULL emotion track on a model with emotions: FDM_ERR_ARG; lengths: FDM_ERR_SHAPE as the per-clip
+ * call.  The S-conditions form has no track variant.
+ *   fdm_audio_prepare_tracks:         fdm_audio_prepare, style [B, L, n_style], emo [B, L, n_emo].
+ *   fdm_audio_prepare_windows_tracks: fdm_audio_prepare_windows, style [B, L_total, n_style], emo [B, L_total, n_emo]; window w reads the
+ *                                     track rows [s_w, s_w + W') of its clip; positions stay window-local.
+ *   fdm_slot_admit_tracks:            fdm_slot_admit_as, style [L_clip, n_style], emo [L_clip, n_emo].
+ *   fdm_slot_admit_long_tracks:       fdm_slot_admit_long_as, style [L_total, n_style], emo [L_total, n_emo]. */
+int fdm_audio_prepare_tracks(fdm_plan* p, const float* hub, int B, int N, int fw, const float* style, const float* emo, int L, int cfg,
+                             void* stream);
+int fdm_audio_prepare_windows_tracks(fdm_plan* p, const float* hub, int B, int N, int fw, const float* style, const float* emo,
+                                     int L_total, int window, int overlap, int cfg, void* stream);
+int fdm_slot_admit_tracks(fdm_plan* p, int slot, const float* hub, int N, int fw, const float* style, const float* emo, int L_clip,
+                          const float* x_T, unsigned long long seed, int clip_id, int sampler, float cfg_scale, void* stream);
+int fdm_slot_admit_long_tracks(fdm_plan* p, const int* slots, int n, const float* hub, int N, int fw, const float* style, const float* emo,
+                               int L_total, int overlap, const float* x_T, unsigned long long seed, int clip_id, int sampler,
+                               float cfg_scale, void* stream);
 /* Plan-time tuning of the GEMM output tiles at the prepared shape (times candidates per call site; changes speed only, every
  * tile accumulates k in the same order).  This call is the ONLY place the library tunes by itself: request paths
  * (fdm_audio_prepare*, fdm_sample_graph) never do -- fdm_plan_get(p, "needs_tune") turns 1 once the prepared shape has served
@@ -761,6 +806,13 @@ int fdm_vq_quant(fdm_vq* v, const float* z, const float* emo_one_hot, int B, int
  * beta = 0.25 :16-18): out2 = {loss, perplexity} device floats, min_encodings [B*R, K] device fp32 or NULL. */
 int fdm_vq_quant_stats(fdm_vq* v, const float* z, const float* emo_one_hot, const long long* idx, int B, int R, float beta,
                        float* min_encodings, float* out2, void* stream);
+/* Condition tracks in the quantiser: emo [B, L, n_books] with L = R / G holds one emotion vector per latent FRAME, and every frame is
+ * quantised in the codebook slice of its own emotion: argmax(emo[b, l, :]), the first maximum as torch.argmax except that a NaN never
+ * wins (a cross-fade row of a track takes its heavier side).  A track whose rows are all equal gives the bits of fdm_vq_quant / fdm_vq_quant_stats.  A model
+ * without emotion-sliced codebooks: the per-clip call (emo ignored).  NULL emo: FDM_ERR_ARG; R not a multiple of G: FDM_ERR_SHAPE. */
+int fdm_vq_quant_tracks(fdm_vq* v, const float* z, const float* emo, int B, int R, float* zq_bcl, long long* idx, void* stream);
+int fdm_vq_quant_stats_tracks(fdm_vq* v, const float* z, const float* emo, const long long* idx, int B, int R, float beta,
+                              float* min_encodings, float* out2, void* stream);
 int fdm_vq_decode(fdm_vq* v, const float* zq_bcl, int B, int R, float* out, void* stream);
 /* B clips of unequal length in one call, padded to the longest: z_q [B, c, R_max], frames [B] HOST ints (2 <= frames[b] <= R_max / G;
  * copied into the object's workspace in stream order, not read after the call returns) -> out [B, L_max, V3], L_max = R_max / G.
