@@ -228,6 +228,55 @@ int fdm_pe_table_host(int d, int periodic, int period, int rows, float* out) {
   return FDM_OK;
 }
 
+// ---- audio front end (include/fdm_hip.h, fdm_frontend_*): ratio, output length and taps of the polyphase resampler to 16 kHz
+int fdm_resample_ratio_host(int rate, int* up, int* down) {
+  if (rate < 1 || !up || !down) return fail(FDM_ERR_ARG, "resample_ratio_host: rate = %d (or a null output)", rate);
+  int a = rate, b = 16000;
+  while (b) { const int t = a % b; a = b; b = t; }
+  const int u = 16000 / a, d = rate / a;
+  if (std::max(u, d) > 2048) return fail(FDM_ERR_SHAPE, "resample_ratio_host: %d Hz -> 16000 Hz is %d / %d (the larger may be at most 2048)", rate, u, d);
+  *up = u; *down = d;
+  return FDM_OK;
+}
+
+long long fdm_resample_len_host(int rate, long long frames) {
+  int up = 0, down = 0;
+  const int r = fdm_resample_ratio_host(rate, &up, &down);
+  if (r != FDM_OK) return r;
+  if (frames < 1) return fail(FDM_ERR_SHAPE, "resample_len_host: %lld sample frames", frames);
+  if (frames > 0x7fffffffffffffffLL / up - down) return fail(FDM_ERR_SHAPE, "resample_len_host: %lld sample frames overflow 64 bits", frames);
+  return (frames * up + down - 1) / down;
+}
+
+// scipy.signal.resample_poly's default filter: firwin(2 half + 1, 1 / m, window = ('kaiser', 5.0)) * up with m = max(up, down), half = 10 m
+int fdm_resample_taps_host(int up, int down, double* taps) {
+  if (up < 1 || down < 1 || !taps) return fail(FDM_ERR_ARG, "resample_taps_host: up = %d, down = %d (or null taps)", up, down);
+  const int m = std::max(up, down);
+  if (m > 2048) return fail(FDM_ERR_SHAPE, "resample_taps_host: %d / %d (the larger may be at most 2048)", up, down);
+  auto i0 = [](double x) {          // modified Bessel function of the first kind, order 0: sum_k ((x / 2)^k / k!)^2
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+      term *= q / ((double)k * (double)k);
+      sum += term;
+      if (term < 1e-17 * sum) break;
+    }
+    return sum;
+  };
+  const int half = 10 * m, n = 2 * half + 1;
+  const double fc = 1.0 / m, beta = 5.0, den = i0(beta);
+  double total = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double t = (double)(k - half), a = fc * t;
+    const double sinc = a == 0.0 ? 1.0 : std::sin(M_PI * a) / (M_PI * a);
+    const double r = t / half, w = i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / den;
+    taps[k] = fc * sinc * w;
+    total += taps[k];
+  }
+  for (int k = 0; k < n; ++k) taps[k] = taps[k] / total * up;
+  return n;
+}
+
 int fdm_model_preset(const char* name, fdm_model_desc* o) {
   if (!name || !o) return fail(FDM_ERR_ARG, "model_preset: null argument");
   const fdm_model_desc vocaset = {1024, 8, 8, 2048, 16, 64, 8, 0, 1024, 1, 1, 30, 1, 0, 600};

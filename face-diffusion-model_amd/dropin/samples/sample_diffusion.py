@@ -39,9 +39,20 @@ def save_name(dataset, file_name, style_index):
     return f"{stem}_condition_{subjects[style_index]}" if subjects else stem
 
 
-def synthetic_loader(p, clips, seconds, seed=0, names=None):
+RAW_RATE = 48000      # --device_audio: the synthetic clips arrive as stereo int16 PCM at this rate
+
+
+def synthetic_loader(p, clips, seconds, seed=0, names=None, raw=False):
+    """raw (--device_audio): every clip as a numpy array of raw PCM, [frames, 2] int16 at RAW_RATE Hz, which the device front end
+    converts, downmixes, resamples, normalises and pads with 1 s of zeros as the demos do (pipeline.prepare_audio); otherwise a
+    normalised 16 kHz waveform [1, n] without padding."""
     g = torch.Generator().manual_seed(seed)
     for i in range(clips):
+        if raw:
+            pcm = (torch.randn(int(seconds * RAW_RATE), 2, generator=g) * 0.1 * 32768.0).clamp(-32768, 32767).to(torch.int16).numpy()
+            name = names[i] if names else f"synthetic_{i:03d}.wav"
+            yield pcm, torch.zeros(1, p.V3), torch.eye(p.n_style).unsqueeze(0), name
+            continue
         wav = pipeline.processor_normalize((torch.randn(int(seconds * 16000), generator=g) * 0.1).numpy(), pad_seconds=0)
         name = names[i] if names else f"synthetic_{i:03d}.wav"
         yield torch.from_numpy(wav).unsqueeze(0), torch.zeros(1, p.V3), torch.eye(p.n_style).unsqueeze(0), name
@@ -81,7 +92,7 @@ def sample_batched(loader, dev, diffusion, autoencoder, save_folder, p, ddim_ste
     reference's one B = 1 call per clip (samples/sample_diffusion_vocaset.py:51: batch size 1)."""
     os.makedirs(save_folder, exist_ok=True)
     items = list(loader)
-    audios = [a[0].numpy() for a, _, _, _ in items]
+    audios = [a if isinstance(a, np.ndarray) else a[0].numpy() for a, _, _, _ in items]      # (--device_audio: raw PCM arrays)
     tmpl = [t for _, t, _, _ in items]
     ids = [oh[:, 0, :] for _, _, oh, _ in items]
     emo = [torch.eye(p.n_emo)[emotion:emotion + 1]] * len(items) if p.n_emo else None
@@ -113,6 +124,9 @@ def main(dataset=None, argv=None):
                     help="build-added: table-driven multistep sampler (DPM-Solver++ 2M | DDIM with --eta) instead of the shipped one")
     ap.add_argument("--sampler_steps", type=int, default=20, help="steps of --sampler")
     ap.add_argument("--eta", type=float, default=0.0, help="eta of --sampler ddim_eta, in [0, 1]")
+    ap.add_argument("--device_audio", action="store_true",
+                    help="build-added: the synthetic clips arrive as raw 48 kHz stereo int16 PCM and go through the device front end "
+                         "(pipeline.prepare_audio: conversion, downmix, resampling, normalisation, 1 s of zeros); no file is read")
     named = dataset is not None
     if named:
         pipeline.add_track_arguments(ap, presets.get(dataset))
@@ -120,6 +134,8 @@ def main(dataset=None, argv=None):
         pipeline.add_track_arguments(ap, presets.get("mead"))
     a = ap.parse_args(argv)
     fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
+    if a.device_audio:
+        fast.update(rate=RAW_RATE)
     dataset = dataset or a.dataset
     p = presets.get(dataset)
     if getattr(a, "emotion_track", None) and not p.n_emo:
@@ -135,9 +151,9 @@ def main(dataset=None, argv=None):
     single = a.batch <= 1 and (not all_styles or a.sequential)
     diffusion, ae = pipeline.build_models(dataset, None, a.device, a.stage1_model_path, a.stage2_model_path, single_clip=single)
     if a.batch > 1 and not all_styles:
-        sample_batched(synthetic_loader(p, a.clips, a.seconds), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset, fast=fast)
+        sample_batched(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset, fast=fast)
     else:
-        sample_step(synthetic_loader(p, a.clips, a.seconds), a.device, diffusion, ae, a.out, p, steps,
+        sample_step(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio), a.device, diffusion, ae, a.out, p, steps,
                     all_styles=all_styles, batched=not a.sequential, dataset=dataset, fast=fast)
 
 

@@ -89,10 +89,16 @@ class SlotBankArgs(C.Structure):
     _fields_ = [("req", vp), ("desc", vp), ("t", vp), ("coef", vp), ("n_samplers", ci), ("n_t", ci), ("n_coef", ci), ("reserved", ci)]
 
 
+class Pcm(C.Structure):
+    _fields_ = [("data", vp), ("format", ci), ("channels", ci), ("rate", ci), ("frames", ll)]
+
+
+PCM_S16, PCM_S32, PCM_U8, PCM_F32 = range(4)      # fdm_pcm.format
+
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
            "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs,
-           "fdm_slot_bank_args": SlotBankArgs}
+           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -191,6 +197,10 @@ SYMBOLS = {
     "fdm_hubert_frames": (ci, [ci]),
     "fdm_hubert_forward_ragged": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "fdm_hubert_destroy": (ci, [vp]),
+    "fdm_frontend_create": (ci, [vp, ci, C.POINTER(vp)]),
+    "fdm_frontend_samples": (ci, [C.POINTER(Pcm), ci, C.POINTER(ll)]),
+    "fdm_frontend_forward": (ci, [vp, C.POINTER(Pcm), ci, ci, ci, vp, ll, vp, vp]),
+    "fdm_frontend_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
@@ -204,6 +214,9 @@ SYMBOLS = {
     "fdm_sampler_tables_host": (ci, [ci, ci, ci, C.c_double, vp, vp, vp, vp, vp]),
     "fdm_alibi_slopes_host": (ci, [ci, vp]),
     "fdm_pe_table_host": (ci, [ci, ci, ci, ci, vp]),
+    "fdm_resample_ratio_host": (ci, [ci, C.POINTER(ci), C.POINTER(ci)]),
+    "fdm_resample_len_host": (ll, [ci, ll]),
+    "fdm_resample_taps_host": (ci, [ci, ci, vp]),
 }
 
 _lib = None

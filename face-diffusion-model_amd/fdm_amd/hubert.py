@@ -64,6 +64,69 @@ def num_frames(n_samples):
     return t - (t % 2)
 
 
+class FrontendPlan:
+    """Thin binding of the library's audio front end (include/fdm_hip.h: fdm_frontend_create / _samples / _forward; kernels
+    csrc/audio_front.hpp): raw PCM at the given sample rates -> the 16 kHz, mono, processor-normalised, padded waveform batch and
+    lengths that HubertPlan.forward_padded takes.  The tap tables of `rates` are built and uploaded here; forward() only passes
+    pointers.  A plan holds one statistics scratch: it serves one stream at a time (one plan per stream for concurrent calls)."""
+
+    def __init__(self, rates, device="cuda:0"):
+        import ctypes as C
+        from ._lib import check, lib
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise FdmError("FrontendPlan runs on the HIP path only (no CPU fallback)")
+        self.rates = tuple(sorted({int(r) for r in rates}))
+        self.h = None
+        h = C.c_void_p()
+        arr = (C.c_int * max(len(self.rates), 1))(*self.rates)
+        with torch.cuda.device(self.device):
+            check(lib().fdm_frontend_create(arr, len(self.rates), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h:
+                from ._lib import lib
+                lib().fdm_frontend_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def samples(self, frames, rate, pad=0):
+        """Samples a clip of `frames` sample frames at `rate` Hz gives, padding included (fdm_frontend_samples; host only)."""
+        import ctypes as C
+        from ._lib import Pcm, check, lib
+        n = C.c_longlong(0)
+        check(lib().fdm_frontend_samples(C.byref(Pcm(None, 0, 1, int(rate), int(frames))), int(pad), C.byref(n)))
+        return n.value
+
+    def forward(self, pcms, rates, pad=0, normalize=True, n_max=None, out=None):
+        """pcms: list of device tensors [frames] or [frames, C] (int16 / int32 / uint8 / float32, interleaved), rates: one per clip
+        -> (wav [B, n_max] fp32, n_samples).  Clip b's first n_samples[b] samples do not depend on the batch or on n_max; the rest
+        of its row is zeros.  out: a [B, n_max] fp32 device tensor to write instead of a new one."""
+        from . import ops
+        dv = self.device
+        rates = [int(r) for r in rates]
+        if len(rates) != len(pcms):
+            raise FdmError(f"{len(rates)} rates for {len(pcms)} clips")
+        ps = [p.detach().contiguous() for p in pcms]
+        if any(p.device != dv for p in ps):
+            raise FdmError("FrontendPlan.forward takes tensors on its own device (no CPU fallback)")
+        ns = [self.samples(p.shape[0], r, pad) for p, r in zip(ps, rates)]
+        if out is None:
+            out = torch.empty(len(ps), max(ns + [1]) if n_max is None else int(n_max), device=dv)
+        elif (out.dtype != torch.float32 or out.device != dv or out.dim() != 2 or out.shape[0] != len(ps) or not out.is_contiguous()
+              or (n_max is not None and out.shape[1] != int(n_max))):
+            raise FdmError(f"out must be a contiguous float32 [{len(ps)}, n_max] tensor on {dv}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        with torch.cuda.device(dv):
+            got = ops.frontend_forward(self.h, ps, rates, out, pad=pad, normalize=normalize)
+        if got != ns:
+            raise FdmError(f"fdm_frontend_forward produced {got} samples, expected {ns}")
+        self._pcms = ps          # read asynchronously on this stream
+        return out, ns
+
+
 class HubertPlan:
     """Thin binding of the library's audio-encoder object (include/fdm_hip.h: fdm_hubert_create / _set_weights / _forward;
     implementation csrc/encoders.hip).  Weights go in by transformers state-dict name and are repacked on the device;

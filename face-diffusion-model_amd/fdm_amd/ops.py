@@ -346,6 +346,52 @@ def vq_quant(z, codebook, book, B, R, c, K, zq_bcl, idx):
     check(lib().fdm_op_vq_quant(_p(z), _p(codebook), _p(book), B, R, c, K, _p(zq_bcl), _p(idx), stream()))
 
 
+PCM_FORMATS = {torch.int16: _lib.PCM_S16, torch.int32: _lib.PCM_S32, torch.uint8: _lib.PCM_U8, torch.float32: _lib.PCM_F32}
+
+
+def resample_ratio(rate):
+    """(up, down) of `rate` -> 16 kHz (fdm_resample_ratio_host)."""
+    up, down = C.c_int(0), C.c_int(0)
+    check(lib().fdm_resample_ratio_host(int(rate), C.byref(up), C.byref(down)))
+    return up.value, down.value
+
+
+def resample_len(rate, frames):
+    """ceil(frames * up / down): the samples `frames` sample frames at `rate` give at 16 kHz (fdm_resample_len_host)."""
+    n = lib().fdm_resample_len_host(int(rate), int(frames))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def resample_taps(up, down):
+    """The 20 max(up, down) + 1 taps of the resampler in float64 (fdm_resample_taps_host), as a numpy array."""
+    import numpy as np
+    taps = np.empty(20 * max(int(up), int(down), 1) + 1, dtype=np.float64)
+    n = lib().fdm_resample_taps_host(int(up), int(down), taps.ctypes.data)
+    if n < 0:
+        check(n)
+    return taps[:n]
+
+
+def pcm_desc(pcm, rate):
+    """fdm_pcm of an interleaved device tensor [frames] or [frames, C] of dtype int16 / int32 / uint8 / float32."""
+    if pcm.dtype not in PCM_FORMATS:
+        raise _lib.FdmError(f"PCM dtype {pcm.dtype} (int16, int32, uint8 or float32)")
+    if pcm.dim() not in (1, 2) or not pcm.is_contiguous():
+        raise _lib.FdmError(f"PCM tensor of shape {tuple(pcm.shape)} (contiguous [frames] or [frames, C])")
+    return _lib.Pcm(_p(pcm), PCM_FORMATS[pcm.dtype], 1 if pcm.dim() == 1 else int(pcm.shape[1]), int(rate), int(pcm.shape[0]))
+
+
+def frontend_forward(handle, pcms, rates, wav, *, pad=0, normalize=True):
+    """fdm_frontend_forward over device tensors: pcms[b] at rates[b] Hz -> wav [B, n_max] fp32 (written whole); returns n_samples."""
+    B = len(pcms)
+    clips = (_lib.Pcm * max(B, 1))(*[pcm_desc(p, r) for p, r in zip(pcms, rates)])
+    ns = (C.c_int * max(B, 1))()
+    check(lib().fdm_frontend_forward(handle, clips, B, int(pad), int(bool(normalize)), _p(wav), int(wav.shape[-1]), ns, stream()))
+    return list(ns)[:B]
+
+
 class Program:
     """A recorded sequence of fdm_op_* launches, replayable as a hipGraph (fdm_prog_*)."""
 

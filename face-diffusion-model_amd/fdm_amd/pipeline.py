@@ -41,6 +41,62 @@ def processor_normalize(x, pad_seconds=1.0, sr=16000):
     return x.astype(np.float32)
 
 
+def load_pcm(path):
+    """(samples, rate) of a WAV file as stored: int16 / int32 / uint8 / float32, [frames] or [frames, C].  No arithmetic: conversion,
+    downmix, resampling and normalisation are prepare_audio()'s, on the device."""
+    from scipy.io import wavfile
+    rate, x = wavfile.read(path)
+    if x.dtype not in (np.int16, np.int32, np.uint8, np.float32):
+        raise ValueError(f"{path}: sample type {x.dtype} (int16, int32, uint8 or float32)")
+    return x, int(rate)
+
+
+_FRONTENDS = {}      # (device, stream) -> hubert.FrontendPlan holding every rate seen there so far
+
+
+def _frontend(rates, device):
+    """The front-end plan of `device` and the current stream (a plan serves one stream at a time).  ONE plan per (device, stream): a
+    rate it has not seen replaces it by a plan for the union (16 kHz needs no table), so what the process keeps is bounded by the
+    distinct rates it meets, not by their combinations."""
+    from .hubert import FrontendPlan
+    dv = torch.device(device)
+    key = (str(dv), torch.cuda.current_stream(dv).cuda_stream)
+    want = {int(r) for r in rates} - {16000}
+    plan = _FRONTENDS.get(key)
+    if plan is None or not want <= set(plan.rates):
+        _FRONTENDS[key] = plan = FrontendPlan(want | set(plan.rates if plan else ()), device)
+    return plan
+
+
+def _pcm_tensor(pcm, device):
+    """A raw PCM array or tensor on `device`, dtype kept.  A CPU TENSOR is refused as everywhere on the HIP path (the caller's numpy
+    array is the host input and is uploaded as it is: no arithmetic happens on the host)."""
+    from ._lib import FdmError
+    if torch.device(device).type != "cuda":
+        raise FdmError("prepare_audio runs on the HIP path only (no CPU fallback)")
+    if isinstance(pcm, torch.Tensor):
+        if not pcm.is_cuda:
+            raise FdmError("prepare_audio needs device tensors or numpy arrays (no CPU fallback on the product path)")
+        return pcm.to(device)
+    return torch.from_numpy(np.ascontiguousarray(pcm)).to(device)
+
+
+def prepare_audio_many(pcms, rates, pad_seconds=1.0, device="cuda:0", normalize=True):
+    """Raw PCM clips (int16 / int32 / uint8 / float32, [frames] or [frames, C], numpy or device tensors) at rates[b] Hz (or one rate
+    for all) -> (wav [B, n_max] fp32 on `device`, lens): load_wav's conversion, downmix and resample_poly, processor_normalize's
+    normalisation and padding, in ONE device call (FrontendPlan; include/fdm_hip.h, fdm_frontend_forward).  wav[b, :lens[b]] is
+    the clip's waveform, bit for bit what its own prepare_audio() returns; the rest of the row is zeros."""
+    rates = [int(rates)] * len(pcms) if np.isscalar(rates) else [int(r) for r in rates]
+    ts = [_pcm_tensor(p, device) for p in pcms]
+    return _frontend(rates, device).forward(ts, rates, pad=int(pad_seconds * 16000), normalize=normalize)
+
+
+def prepare_audio(pcm, rate, pad_seconds=1.0, device="cuda:0", normalize=True):
+    """One raw PCM clip at `rate` Hz -> the [n] fp32 device waveform animate() takes (prepare_audio_many with B = 1)."""
+    wav, lens = prepare_audio_many([pcm], [rate], pad_seconds, device, normalize)
+    return wav[0, :lens[0]]
+
+
 def build_models(preset="vocaset", feature_dim=None, device="cuda:0", stage1=None, stage2=None, dtype=None, cfg_level=None, single_clip=False):
     """(diffusion, autoencoder) with reference-compatible state dicts; checkpoints are loaded when the
     files exist ('model' / 'state_dict' keys as samples/sample_diffusion_vocaset.py:26,91-97), otherwise the
@@ -81,8 +137,12 @@ def _clip_x_T(shape, S, seed):
 
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
-            ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None):
+            ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
+            rate=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    rate: `audio` is ONE raw PCM clip at that sample rate (int16 / int32 / uint8 / float32, [frames] or [frames, C]) and goes through
+    the device front end first: animate(prepare_audio(audio, rate)), 1 s of trailing zeros included.  None: every path as before.
 
     style_track [L', n_style] / emotion_track [L', n_emo] (or [B, L', n]; L' >= L, fdm_amd.tracks.keyframes): one vector per latent
     frame instead of one per clip, either alone or both; the quantiser takes every frame in the codebook of its own emotion.  One
@@ -102,6 +162,8 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     sequential calls draw from one running generator), not bit for bit."""
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
+    if rate is not None:
+        audio = prepare_audio(audio, rate, device=device)
     audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
     if audio.dim() == 1:
         audio = audio.unsqueeze(0)
@@ -161,8 +223,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
-                 style_track=None, emotion_track=None):
+                 style_track=None, emotion_track=None, rate=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    rate (one for all, or a list): `audios` are raw PCM clips at those sample rates and go through the device front end in ONE call
+    (prepare_audio_many) before anything else; None: every path as before.
 
     The reference's samplers take the clips of a loader one at a time (bs = 1: samples/sample_diffusion_vocaset.py:51,71-83),
     which is the few-hundred-row regime where this path reaches 1-2 % of the MFMA roofline.  Clips of different lengths batch
@@ -186,6 +251,9 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
     n = len(audios)
+    if rate is not None:
+        wav_b, lens_b = prepare_audio_many(audios, rate, device=device)
+        audios = [wav_b[b, :lens_b[b]] for b in range(n)]
     wavs = [torch.as_tensor(a, dtype=torch.float32, device=device).reshape(1, -1) for a in audios]
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
         hubs = model.audio_encoder.encode_many([w[0] for w in wavs], device)
@@ -277,8 +345,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
-                 window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None):
-    """audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
+                 window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
+                 rate=None):
+    """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
     encoder frames // pair (no 600-frame cap: animate() keeps the reference's crop).
 
     The audio encoder runs once over each whole waveform; sampling runs on windows of `window` (default max_len) latent frames
@@ -293,6 +363,8 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
     scale = float(diffusion.denoise_fn.level) if cfg else 2.5
     p = model.preset
+    if rate is not None:
+        audio = prepare_audio(audio, rate, device=device)
     audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
     if audio.dim() == 1:
         audio = audio.unsqueeze(0)
@@ -459,13 +531,16 @@ class SlotServer:
 
     @torch.no_grad()
     def submit(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
-               sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
-        """One processor-normalised waveform [n] -> a handle.  Runs the audio encoder at the clip's own length, draws x_T as
+               sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None, rate=None):
+        """rate: `audio` is raw PCM at that sample rate and goes through the device front end first (prepare_audio).
+        One processor-normalised waveform [n] -> a handle.  Runs the audio encoder at the clip's own length, draws x_T as
         animate() does and admits the clip, or queues it until a slot is free.  ddim_steps / sampler / sampler_steps / eta /
         cfg_scale: the request's own sampler and guidance scale (class docstring); none given = the server's."""
         self._check()
         key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
         p, dev = self.p, self.device
+        if rate is not None:
+            audio = prepare_audio(audio, rate, device=dev)
         wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
         hub = self.model.audio_encoder(wav).last_hidden_state
         L = min(hub.shape[1] // p.pair, p.max_len)
@@ -498,8 +573,10 @@ class SlotServer:
 
     @torch.no_grad()
     def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0, ddim_steps=None, sampler=None,
-                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
-        """Several requests at once: ONE audio-encoder call over the waveforms' unequal lengths (encode_many), then each request is
+                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None, rate=None):
+        """rate (one for all, or a list): `audios` are raw PCM clips; ONE front-end call over all of them (prepare_audio_many), then
+        the one encoder call.
+        Several requests at once: ONE audio-encoder call over the waveforms' unequal lengths (encode_many), then each request is
         admitted or queued exactly as submit() does it, in the given order.  templates / id_one_hots / emotion_one_hots / seeds:
         one per request (lists) or one for all, and so are ddim_steps / sampler / sampler_steps / eta / cfg_scale (submit()).
         style_track / emotion_track: a list with one track (or None) per request, or one for all (submit()).
@@ -509,6 +586,9 @@ class SlotServer:
         n = len(audios)
         per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
         reqs = [self._request(per(ddim_steps, b), per(sampler, b), per(sampler_steps, b), per(eta, b), per(cfg_scale, b)) for b in range(n)]
+        if rate is not None:
+            wav_b, lens_b = prepare_audio_many(audios, rate, device=dev)
+            audios = [wav_b[b, :lens_b[b]] for b in range(n)]
         hubs = self.model.audio_encoder.encode_many([torch.as_tensor(a, dtype=torch.float32).reshape(-1) for a in audios], dev)
         Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
         for L in Ls:
@@ -568,8 +648,9 @@ class SlotServer:
 
     @torch.no_grad()
     def submit_long(self, audio, template=None, id_one_hot=None, emotion_one_hot=None, seed=0, ddim_steps=None, sampler=None,
-                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None):
-        """One processor-normalised waveform [n] of ANY length -> a handle.  The audio encoder runs over the whole waveform and
+                    sampler_steps=None, eta=None, cfg_scale=None, style_track=None, emotion_track=None, rate=None):
+        """rate: `audio` is raw PCM at that sample rate and goes through the device front end first (prepare_audio).
+        One processor-normalised waveform [n] of ANY length -> a handle.  The audio encoder runs over the whole waveform and
         L_total = frames // pair is kept whole (submit() crops to a slot).  L_total <= max_frames is an ordinary request; a longer
         one becomes a group of slots (class docstring) with x_T drawn as animate_long draws it.  ValueError if the request can
         never fit: more windows than slots, or L_total > long_frames.  ddim_steps / sampler / sampler_steps / eta / cfg_scale as
@@ -578,6 +659,8 @@ class SlotServer:
         self._check()
         key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
         p, dev = self.p, self.device
+        if rate is not None:
+            audio = prepare_audio(audio, rate, device=dev)
         wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
         hub = self.model.audio_encoder(wav).last_hidden_state
         L = hub.shape[1] // p.pair
@@ -744,11 +827,16 @@ def demo_main(preset, argv=None):
     ap.add_argument("--long_audio", type=str, default="truncate", choices=["truncate", "window"],
                     help="build-added: audio past max_len latent frames: truncate (the reference's crop) or window (animate it all)")
     ap.add_argument("--window_overlap", type=int, default=60, help="build-added: frames shared by neighbouring windows (--long_audio window)")
+    ap.add_argument("--device_audio", action="store_true",
+                    help="build-added: convert, downmix, resample and normalise the file's raw samples on the device (prepare_audio)")
     add_track_arguments(ap, p)
     a = ap.parse_args(argv)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
                                  cfg_level=None)
-    wav = processor_normalize(load_wav(a.audio_file))
+    if a.device_audio:
+        wav = prepare_audio(*load_pcm(a.audio_file), device=a.device)
+    else:
+        wav = processor_normalize(load_wav(a.audio_file))
     template = None
     if os.path.exists(a.template_file) and a.template_file.endswith(".npy"):
         template = np.load(a.template_file).reshape(1, -1)

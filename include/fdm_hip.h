@@ -787,6 +787,47 @@ int fdm_hubert_forward_ragged(fdm_audio_encoder* e, const float* wav, const int*
 int fdm_hubert_destroy(fdm_audio_encoder* e);
 
 /* ------------------------------------------------------------------------------------------
+ * Audio front end: raw PCM -> the waveform the encoders take (16 kHz, mono, processor-normalised, padded), batched over clips of
+ * unequal length, rate, format and channel count.  What the demos do on the host (librosa.load(sr=16000) + Wav2Vec2Processor + 1 s of
+ * zeros, demo/demo_vocaset.py:84-90) in this project's definition: scipy.signal.resample_poly + (x - mean) / sqrt(var + 1e-7).
+ * For a clip of `frames` sample frames of `channels` interleaved channels at `rate` Hz:
+ *   convert   int16: x / 2^15, int32: x / 2^31, uint8: (x - 128) / 128, float32 as is                              (fp32, exact)
+ *   downmix   ((c0 + c1) + c2 ...) / channels in fp32: numpy's x.mean(axis=1) bit for bit up to 7 channels (numpy adds 8 in pairs)
+ *   resample  g = gcd(rate, 16000), up = 16000 / g, down = rate / g, m = max(up, down), half = 10 m;
+ *             h[k], k = 0 .. 2 half: firwin(2 half + 1, 1 / m, window = ('kaiser', 5.0)) * up, i.e. sinc(k - half; cutoff 1 / m) times
+ *             I0(5 sqrt(1 - ((k - half) / half)^2)) / I0(5), divided by its sum, times up; in double, stored as fp32;
+ *             n_out = ceil(frames * up / down);  y[j] = sum_i x[i] h[half + j down - i up] over the i inside the clip whose tap index is
+ *             in range, i ascending, products and sum in fp64, rounded once to fp32.  The value of y[j] depends on nothing but the
+ *             clip (not on the batch, n_max or a tile size).  rate == 16000: no filter, y = x bit for bit.  64-bit indices.
+ *   normalise (normalize != 0) (y - mean) / sqrt(var + 1e-7), mean and population variance over the clip's n_out samples in fp64,
+ *             two passes over chunks whose count and width follow from n_out alone, partials folded in chunk order (no atomics);
+ *             each element is formed in fp64 and rounded once.  A constant clip gives zeros.
+ *   pad       `pad` zeros follow and count as samples: n_samples[b] = n_out + pad; everything from there to n_max is zero.
+ * Rates with max(up, down) > 2048 are refused (FDM_ERR_SHAPE): their tap tables would run to megabytes.
+ * fdm_frontend_create computes the tap tables of `rates` (laid out by phase: the taps one output needs are contiguous); with a
+ * device visible it uploads them and allocates the statistics scratch -- nothing is allocated later; without one the object still
+ * validates arguments and fdm_frontend_forward ends in FDM_ERR_STATE.  fdm_frontend_samples is host only: *n = n_out + pad.
+ * fdm_frontend_forward: clips [B] HOST structs (data: DEVICE pointer, aligned to its sample type; the structs are not read after
+ * the call returns) -> wav [B, n_max] fp32 device, n_samples [B] HOST ints: the input layout of fdm_hubert_forward_ragged.  Launches
+ * on `stream`, never synchronises.  An object holds ONE statistics scratch, which every call with normalize != 0 writes: it serves one
+ * stream at a time (calls on the same stream follow each other in stream order; use one object per stream for concurrent calls, or
+ * order the streams with events).  Every check is made before the first launch: FDM_ERR_ARG (null pointer, unknown format, a rate
+ * the object was not created for -- 16000 needs no table and is always taken --, channels outside 1..8, pad < 0, misaligned data),
+ * FDM_ERR_SHAPE (B < 1, frames < 1, n_samples[b] > n_max, n_max > INT_MAX, the ratio cap).  Speed: unmeasured
+ * (profiles/audio_frontend/README.md). */
+#define FDM_PCM_S16 0
+#define FDM_PCM_S32 1
+#define FDM_PCM_U8 2
+#define FDM_PCM_F32 3
+typedef struct fdm_pcm { const void* data; int format; int channels; int rate; long long frames; } fdm_pcm;
+typedef struct fdm_frontend fdm_frontend;
+int fdm_frontend_create(const int* rates, int n_rates, fdm_frontend** out);
+int fdm_frontend_samples(const fdm_pcm* clip, int pad, long long* n);
+int fdm_frontend_forward(fdm_frontend* f, const fdm_pcm* clips, int B, int pad, int normalize, float* wav, long long n_max, int* n_samples,
+                         void* stream);
+int fdm_frontend_destroy(fdm_frontend* f);
+
+/* ------------------------------------------------------------------------------------------
  * (E)VQ-VAE: quantise, decode, encode (models/vq_vae_vocaset.py:23-43, models/vq_vae_emotion.py:9-41, models/vq_vae.py).
  * Geometry from the reference's *_vq_vae_args (models/utils/config.py): G = face_quan_num, c = zquant_dim, K = 256 codes
  * per book, n_books = n_embed / 256 (emotion-sliced codebook), V3 = in_dim; pre = decoder_linear_embedding_pre /
@@ -847,6 +888,12 @@ int fdm_ddim_schedule_host(int steps, int T, int* t, int* t_next, float* sqrt_an
 int fdm_sampler_tables_host(int kind, int steps, int T, double eta, int* t, float* a, float* b, float* c, float* s);
 int fdm_alibi_slopes_host(int n_head, float* out);
 int fdm_pe_table_host(int d, int periodic, int period, int rows, float* out);
+/* Tables of the audio front end (fdm_frontend_*): the resampling ratio of `rate` -> 16 kHz (up = 16000 / gcd, down = rate / gcd;
+ * FDM_ERR_ARG: rate < 1 or a NULL output, FDM_ERR_SHAPE: max(up, down) > 2048); n_out = ceil(frames * up / down) in 64 bits (negative:
+ * the same errors, or frames < 1); the 20 max(up, down) + 1 taps in double, I0 by its power series (returns their count). */
+int fdm_resample_ratio_host(int rate, int* up, int* down);
+long long fdm_resample_len_host(int rate, long long frames);
+int fdm_resample_taps_host(int up, int down, double* taps);
 
 #ifdef __cplusplus
 }
