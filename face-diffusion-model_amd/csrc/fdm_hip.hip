@@ -64,7 +64,7 @@ bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 extern "C" {
 
 const char* fdm_last_error(void) { return g_err.c_str(); }
-int fdm_version(void) { return 105; }      // 1.05: round 5 (fdm_gemm_args.ksplit / batch2, fdm_ln_args.x_planes, plan keys ksplit.*; lanes, FDM_BF16X3 and three tile ids removed); additions since keep the number: fdm_frontend_* / fdm_pcm / fdm_resample_*_host (audio front end) among them
+int fdm_version(void) { return 105; }      // 1.05: round 5 (fdm_gemm_args.ksplit / batch2, fdm_ln_args.x_planes, plan keys ksplit.*; lanes, FDM_BF16X3 and three tile ids removed); additions since keep the number: fdm_frontend_* / fdm_pcm / fdm_resample_*_host (audio front end) and fdm_mesh_* (mesh hand-off) among them
 
 // sizeof() of a public struct as THIS build sees it: a binding compares it with its own mirror before the first call
 int fdm_abi_struct_size(const char* name) {

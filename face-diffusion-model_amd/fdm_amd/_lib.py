@@ -94,6 +94,7 @@ class Pcm(C.Structure):
 
 
 PCM_S16, PCM_S32, PCM_U8, PCM_F32 = range(4)      # fdm_pcm.format
+MESH_INTERLEAVED, MESH_F16, MESH_NORMALS = 1, 2, 4      # fdm_mesh_forward flags
 
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
@@ -201,6 +202,11 @@ SYMBOLS = {
     "fdm_frontend_samples": (ci, [C.POINTER(Pcm), ci, C.POINTER(ll)]),
     "fdm_frontend_forward": (ci, [vp, C.POINTER(Pcm), ci, ci, ci, vp, ll, vp, vp]),
     "fdm_frontend_destroy": (ci, [vp]),
+    "fdm_mesh_adjacency_host": (ci, [vp, ci, ci, vp, vp]),
+    "fdm_mesh_create": (ci, [vp, ci, ci, C.POINTER(vp)]),
+    "fdm_mesh_frames": (ci, [ci, C.c_double, C.c_double, C.POINTER(ci)]),
+    "fdm_mesh_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, ci, vp, vp, ci, vp, vp]),
+    "fdm_mesh_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),

@@ -97,6 +97,65 @@ def prepare_audio(pcm, rate, pad_seconds=1.0, device="cuda:0", normalize=True):
     return wav[0, :lens[0]]
 
 
+_MESH_PLANS = {}      # (device, stream, V, digest of the faces) -> mesh.MeshOutPlan
+
+
+def _mesh_plan(faces, V, device):
+    """The mesh hand-off plan of `device`, the current stream and this topology (a plan serves one stream at a time), kept as
+    _frontend() keeps front ends: what the process holds is bounded by the distinct meshes it meets."""
+    import hashlib
+    from .mesh import MeshOutPlan, faces_array
+    dv = torch.device(device)
+    f = faces_array(faces)
+    key = (str(dv), torch.cuda.current_stream(dv).cuda_stream, int(V), hashlib.sha1(f.tobytes()).hexdigest())
+    plan = _MESH_PLANS.get(key)
+    if plan is None:
+        _MESH_PLANS[key] = plan = MeshOutPlan(f, V, dv)
+    return plan
+
+
+def _mesh_fps(p, in_fps, out_fps):
+    """(fps_in, fps_out) of a hand-off, or None without out_fps: fps_in is the preset's frame rate unless in_fps= states one."""
+    if out_fps is None:
+        return None
+    fi = in_fps or p.fps
+    if not fi:
+        raise ValueError(f"preset {p.name} states no frame rate: pass in_fps= with out_fps=")
+    return float(fi), float(out_fps)
+
+
+def _split_mesh(mf):
+    """A batched MeshFrames -> one per clip, each cut to its own frames ([1, L_out, V, 3 or 6])."""
+    return [type(mf)(mf.positions[b:b + 1, :n], None if mf.normals is None else mf.normals[b:b + 1, :n], [n]) for b, n in enumerate(mf.frames)]
+
+
+@torch.no_grad()
+def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, interleaved=False, half=False, device=None):
+    """Vertex offsets (what the decoder writes; or vertices, with template=None) -> mesh.MeshFrames: positions = offsets + template,
+    resampled in time when fps = (fps_in, fps_out) names two different rates, and area-weighted vertex normals over the triangle
+    list `faces` [F, 3], in ONE device call (mesh.MeshOutPlan; include/fdm_hip.h, fdm_mesh_forward).
+    offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None: all L) -> one MeshFrames for the batch; or a
+    ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of MeshFrames, each cut to its own frames and bit for bit what its
+    own call returns.  template: [1 or B, 3 V], or for a list one per clip.  normals / interleaved / half: the output options."""
+    many = isinstance(offsets, (list, tuple))
+    if many:
+        clips = [o.reshape(-1, o.shape[-1]) for o in offsets]
+        frames = [int(c.shape[0]) for c in clips]
+        x = torch.zeros(len(clips), max(frames + [1]), clips[0].shape[-1], device=clips[0].device)
+        for b, c in enumerate(clips):
+            x[b, :frames[b]] = c
+        if isinstance(template, (list, tuple)):
+            template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
+    else:
+        x = offsets if offsets.dim() == 3 else offsets.unsqueeze(0)
+    dv = x.device if device is None else torch.device(device)
+    if dv.type != "cuda" or not x.is_cuda:
+        from ._lib import FdmError
+        raise FdmError("to_mesh runs on the HIP path only (no CPU fallback)")
+    mf = _mesh_plan(faces, x.shape[-1] // 3, dv).forward(x.to(dv), frames, template, fps, normals, interleaved, half)
+    return _split_mesh(mf) if many else mf
+
+
 def build_models(preset="vocaset", feature_dim=None, device="cuda:0", stage1=None, stage2=None, dtype=None, cfg_level=None, single_clip=False):
     """(diffusion, autoencoder) with reference-compatible state dicts; checkpoints are loaded when the
     files exist ('model' / 'state_dict' keys as samples/sample_diffusion_vocaset.py:26,91-97), otherwise the
@@ -138,8 +197,13 @@ def _clip_x_T(shape, S, seed):
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    faces [F, 3]: the decoder's output goes through the device mesh hand-off (to_mesh) and the call returns (mesh.MeshFrames,
+    latent): positions [B, L_out, V, 3] -- the template added there, the same bits as the vertices returned without faces -- and
+    vertex normals; out_fps: resampled in time from the preset's frame rate (in_fps= where the preset states none); mesh: a dict of
+    to_mesh's output options (normals, interleaved, half).  None: every path as before.
 
     rate: `audio` is ONE raw PCM clip at that sample rate (int16 / int32 / uint8 / float32, [frames] or [frames, C]) and goes through
     the device front end first: animate(prepare_audio(audio, rate)), 1 s of trailing zeros included.  None: every path as before.
@@ -214,6 +278,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
             latent = diffusion.sample(audio, shape, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
         quanted, _, _ = autoencoder.quant(latent, stats=False)
     out = autoencoder.decode(quanted)
+    if faces is not None:
+        tp = None if template is None else torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, out.shape[-1])
+        if tp is not None and S > 1 and tp.shape[0] == B and B > 1:
+            tp = tp.repeat_interleave(S, dim=0)
+        return to_mesh(out, faces, tp, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {})), latent
     if template is not None:
         tp = torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
         out = out + (tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp)
@@ -223,8 +292,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
-                 style_track=None, emotion_track=None, rate=None):
+                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    faces / out_fps / mesh / in_fps: as animate(); each group's decoded clips go through ONE ragged hand-off call and the first
+    returned list holds a mesh.MeshFrames per clip ([1, L_out_b, V, 3] positions and normals).  None: every path as before.
 
     rate (one for all, or a list): `audios` are raw PCM clips at those sample rates and go through the device front end in ONE call
     (prepare_audio_many) before anything else; None: every path as before.
@@ -320,7 +392,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                 lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T, **trk)
             else:
                 lat = diffusion.sample(dummy, shape, ids, seed=seed, x_T=x_T, clip0=g0, **trk)
-            outs = None
+            outs, offs = None, []
             if batch_stages:        # one padded quant (per row) and one decode that knows each clip's length
                 lat_g = lat[:, :max(Ls[b] for b in grp) * p.G].contiguous()        # (not the bucket's rows: they belong to no clip)
                 etq = None if et_g is None else et_g[:, :lat_g.shape[1] // p.G]
@@ -334,10 +406,16 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                     etq = None if et_g is None else et_g[i:i + 1, :Ls[b]]
                     q = autoencoder.quant(lb, emos[i:i + 1], stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
                     out = autoencoder.decode(q)
-                if templates is not None:
+                if faces is not None:
+                    offs.append(out)
+                elif templates is not None:
                     tp = templates[b] if isinstance(templates, (list, tuple)) else templates
                     out = out + torch.as_tensor(tp, dtype=torch.float32, device=device).reshape(1, 1, -1)
                 verts[b], lats[b] = out, lb
+            if faces is not None:       # the group's clips, each at its own length, through one hand-off call
+                tps = None if templates is None else [per(templates, b) for b in grp]
+                for b, mf in zip(grp, to_mesh(offs, faces, tps, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))):
+                    verts[b] = mf
     finally:
         model._hub_key, model._hub = prev
     return verts, lats
@@ -346,8 +424,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    faces / out_fps / mesh / in_fps: as animate(): the whole recording's decode goes through the mesh hand-off and the call returns
+    (mesh.MeshFrames, latent).
     audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
     encoder frames // pair (no 600-frame cap: animate() keeps the reference's crop).
 
@@ -398,6 +478,8 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     quanted = autoencoder.quant(latent, emo, stats=False, emotion_track=et)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
     out = autoencoder.decode(quanted)
+    if faces is not None:
+        return to_mesh(out, faces, template, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {})), latent
     if template is not None:
         out = out + torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
     return out, latent
@@ -429,17 +511,24 @@ class SlotServer:
     sampler), and cfg_scale= under guidance (None = the model's level).  The server keeps a {definition: bank id} map; when the
     bank is full it drops the least recently used sampler no slot holds, and if none can go the request waits at the head of the
     queue like a long request that does not fit.  Every result equals animate() / animate_long() with the same arguments and seed.
-    samplers = 0 (default): the single-sampler slot program; a request that names another sampler is refused (ValueError)."""
+    samplers = 0 (default): the single-sampler slot program; a request that names another sampler is refused (ValueError).
+
+    faces / out_fps / mesh / in_fps: as animate(): every finished clip's decode goes through the mesh hand-off (the template added
+    there) and results() yields a mesh.MeshFrames in place of the vertices; the clips of one batched decode share one ragged call.
+    None (default): unchanged."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
-                 device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0):
+                 device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
+                 faces=None, out_fps=None, mesh=None, in_fps=None):
         from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
+        self.faces, self.mesh = faces, dict(mesh or {})
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
         self.batched_decodes = []                   # clips per batched decode, in call order
         self.cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
         self.model = diffusion.denoise_fn.model if self.cfg else diffusion.denoise_fn
         p = self.p = self.model.preset
+        self.mesh_fps = _mesh_fps(p, in_fps, out_fps) if faces is not None else None
         self.n_slots = int(slots)
         self.L = min(int(max_frames), p.max_len) if max_frames else p.max_len
         self.plan = self.model.plan(device)
@@ -706,13 +795,19 @@ class SlotServer:
             lat = self.plan.read_slot(s, r["L"])
             q = self._quant(lat, r)
             out = self.ae.decode(q)
-            if r["template"] is not None:
-                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
-            self._done.append((r["handle"], out, lat))
+            self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
             self._slot[s] = None
             fin += 1
         self._fill()
         return fin
+
+    def _vertices(self, out, template):
+        """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames."""
+        if self.faces is not None:
+            return to_mesh(out, self.faces, template, fps=self.mesh_fps, **self.mesh)
+        if template is not None:
+            out = out + torch.as_tensor(template, dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
+        return out
 
     def _finish_long(self):
         """The groups whose chains ended: read the long latent, quantise and decode the whole L_total (the decoder is not causal), as
@@ -726,9 +821,7 @@ class SlotServer:
             lat = self.plan.read_long(s)
             q = self._quant(lat, r)
             out = self.ae.decode(q)
-            if r["template"] is not None:
-                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
-            self._done.append((r["handle"], out, lat))
+            self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
             for m in r["slots"]:
                 self._slot[m] = None
             fin += 1
@@ -757,10 +850,12 @@ class SlotServer:
             qs = self.ae.quant(pad, torch.cat([r["emo"] for r in reqs]), stats=False)[0] if p.n_emo else self.ae.quant(pad, stats=False)[0]
         outs = self.ae.decode_many(qs, [r["L"] for r in reqs])
         self.batched_decodes.append(len(done))
+        tps = [r["template"] for r in reqs]
+        ragged = None
+        if self.faces is not None and (all(t is None for t in tps) or all(t is not None for t in tps)):      # one call over the unequal lengths
+            ragged = to_mesh([outs[i, :r["L"]] for i, r in enumerate(reqs)], self.faces, None if tps[0] is None else tps, fps=self.mesh_fps, **self.mesh)
         for i, (s, r) in enumerate(zip(done, reqs)):
-            out = outs[i:i + 1, :r["L"]].contiguous()
-            if r["template"] is not None:
-                out = out + torch.as_tensor(r["template"], dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
+            out = ragged[i] if ragged else self._vertices(outs[i:i + 1, :r["L"]].contiguous(), r["template"])
             self._done.append((r["handle"], out, lats[i]))
             self._slot[s] = None
         return len(done)
@@ -771,7 +866,7 @@ class SlotServer:
         return len(self._queue) + len({r["handle"] for r in self._slot if r is not None})
 
     def results(self):
-        """[(handle, vertices [1, L, V3], latent [1, L*G, c])] of the clips finished since the last call."""
+        """[(handle, vertices [1, L, V3] -- with faces= a mesh.MeshFrames --, latent [1, L*G, c])] of the clips finished since the last call."""
         out, self._done = self._done, []
         return out
 
@@ -829,6 +924,11 @@ def demo_main(preset, argv=None):
     ap.add_argument("--window_overlap", type=int, default=60, help="build-added: frames shared by neighbouring windows (--long_audio window)")
     ap.add_argument("--device_audio", action="store_true",
                     help="build-added: convert, downmix, resample and normalise the file's raw samples on the device (prepare_audio)")
+    ap.add_argument("--faces_file", type=str, default=None,
+                    help="build-added: triangle list (.npy, int [F, 3]): positions and vertex normals through the device mesh hand-off")
+    ap.add_argument("--out_fps", type=float, default=None, help=f"build-added: frame rate of the saved motion (with --faces_file; the model's is {p.fps or 'given by --in_fps'})")
+    ap.add_argument("--in_fps", type=float, default=None, help="build-added: the model's frame rate where the preset states none (with --out_fps)")
+    ap.add_argument("--save_normals", action="store_true", help="build-added: also save <stem>_normals.npy [1, L_out, 3V] (with --faces_file)")
     add_track_arguments(ap, p)
     a = ap.parse_args(argv)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
@@ -846,6 +946,8 @@ def demo_main(preset, argv=None):
     fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
     # tracks cover every latent frame the audio can give (16 kHz, 320 samples per encoder frame); the calls take the frames they need
     fast.update(track_arguments(a, p, max(len(wav) // 320 // p.pair + 2, p.max_len)))
+    if a.faces_file:
+        fast.update(faces=np.load(a.faces_file), out_fps=a.out_fps, in_fps=a.in_fps, mesh=dict(normals=a.save_normals))
     if a.long_audio == "window":
         out, _ = animate_long(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed,
                               overlap=a.window_overlap, device=a.device, **fast)
@@ -853,6 +955,12 @@ def demo_main(preset, argv=None):
         out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device, **fast)
     os.makedirs(a.audio_path, exist_ok=True)
     dst = os.path.join(a.audio_path, os.path.basename(a.audio_file)[:-4])
+    if a.faces_file:        # positions keep the reference's name and shape
+        if a.save_normals:
+            nr = out.normals.reshape(out.normals.shape[0], out.normals.shape[1], -1)
+            np.save(dst + "_normals", nr.detach().cpu().numpy())
+            print(f"saved {dst}_normals.npy {tuple(nr.shape)}")
+        out = out.positions.reshape(out.positions.shape[0], out.positions.shape[1], -1)
     np.save(dst, out.detach().cpu().numpy())
     print(f"saved {dst}.npy {tuple(out.shape)}")
     return dst + ".npy"

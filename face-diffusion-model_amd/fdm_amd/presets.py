@@ -31,16 +31,17 @@ class Preset:
     latent_mish: bool = True
     style_mish: bool = False
     max_len: int = 600     # init_biased_mask(max_seq_len=600), models/fdm_vocaset.py:44
+    fps: int = 0           # frames per second of the decoded motion (the reference's render --fps); 0 = not stated: callers pass in_fps=
 
     @property
     def head_dim(self):
         return self.d // self.n_head
 
 
-VOCASET = Preset("vocaset", 1024, 8, 8, 2048, 16, 64, 8, 0, 1024, 1, "periodic", 30)
+VOCASET = Preset("vocaset", 1024, 8, 8, 2048, 16, 64, 8, 0, 1024, 1, "periodic", 30, fps=30)
 MEAD = Preset("mead", 512, 4, 8, 1024, 8, 64, 25, 7, 2048, 2, "sinus", 30, n_books=7, vq_pre=True, vq_out_bias=False)
 BIWI = Preset("biwi", 1024, 4, 8, 2048, 8, 128, 6, 0, 1536, 2, "sinus", 25, V3=70110, vq_pre=True, vq_out_bias=False,
-              latent_mish=False, style_mish=True)
+              latent_mish=False, style_mish=True, fps=25)
 # small structural twins used by tests (head_dim stays 128)
 VOCASET_TINY = replace(VOCASET, name="vocaset_tiny", d=256, n_head=2, n_layers=2, ffn=512, c=16, V3=96)
 MEAD_TINY = replace(MEAD, name="mead_tiny", d=256, n_head=2, n_layers=2, ffn=512, c=32, V3=96)

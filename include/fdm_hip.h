@@ -834,7 +834,7 @@ int fdm_frontend_destroy(fdm_frontend* f);
  * encoder_linear_embedding_post present (3D-MEAD, BIWI).  Weights by reference state-dict name.
  * quant:  z [B, R, c] (+ emotion one-hot [B, n_books]) -> z_q [B, c, R] (the reference's permuted output), idx [B*R] int64;
  *         quant_stats: emb_loss, perplexity, min_encodings of that call
- * decode: z_q [B, c, L*G] -> vertex offsets [B, L, V3] (the caller adds the template; every clip gets pe[0], a20)
+ * decode: z_q [B, c, L*G] -> vertex offsets [B, L, V3] (the caller adds the template: fdm_mesh_forward below does; every clip gets pe[0], a20)
  * encode: x [B, L, V3] (+ emotion one-hot [B, 7]) -> latent [B, L*G, c]
  * dtype: FDM_F32, FDM_BF16, or FDM_F16X3 = the two 6-layer transformers on split-fp16 operands, convolutions / embeddings /
  *        vertex map / quantiser in fp32 (indices and z_q identical to the fp32 object's; decode 1.4-4.6e-5 from the reference) */
@@ -863,6 +863,50 @@ int fdm_vq_decode(fdm_vq* v, const float* zq_bcl, int B, int R, float* out, void
 int fdm_vq_decode_ragged(fdm_vq* v, const float* zq_bcl, const int* frames, int B, int R_max, float* out, void* stream);
 int fdm_vq_encode(fdm_vq* v, const float* x, const float* emo_one_hot, int B, int L, float* latent, void* stream);
 int fdm_vq_destroy(fdm_vq* v);
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh hand-off: the offsets fdm_vq_decode(_ragged) writes -> what a renderer or engine takes: positions (+ template) at its own
+ * frame rate and area-weighted vertex normals, planar or interleaved, fp32 or fp16 (the reference's render/ recomputes normals per
+ * frame on the CPU and takes --fps 30 / 25).  fp32 throughout, fixed order, no contraction.  For clip b of L = frames[b] frames
+ * over a triangle list faces [F, 3] on V vertices:
+ *   positions p = offset + template (one fp32 add; no template: p = offset): the vertices pipeline.animate returns.
+ *   frame rate with fps_in, fps_out > 0 and different: L_out = max(1, (int)((double)L / fps_in * fps_out)) frames, each the reference's
+ *             linear_interpolation (align_corners = True) of the clip's own templated frames in the expression of fdm_op_linear_interp:
+ *             scale = (float)(L-1) / (float)(L_out-1) (0 when L_out = 1), src = scale * t, i0 = min((int)src, L-1), i1 = min(i0+1, L-1),
+ *             l1 = src - i0, l0 = 1 - l1, y = l0 * p[i0] + l1 * p[i1], every operation rounded.  Otherwise (0 = not given, or equal
+ *             rates) L_out = L and the positions pass through bit for bit.  L = 0 gives L_out = 0.
+ *   normals   from the OUTPUT positions of the same frame (fp32, before any fp16 rounding).  Face f = (a, b, c): e1 = p_b - p_a,
+ *             e2 = p_c - p_a, n_f = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x), two rounded products and
+ *             one rounded subtraction each.  Vertex v: s = the sum of n_f over its incident faces in ascending face index, one term
+ *             per corner occurrence, starting from the first term; d = (s.x s.x + s.y s.y) + s.z s.z; the normal is s / sqrtf(d) with
+ *             correctly rounded square root and division when d > 0, else (0, 0, 0) (isolated vertices, degenerate faces).
+ *   output    planar: pos [B, L_out_max, V, 3] and nrm the same; FDM_MESH_INTERLEAVED: pos [B, L_out_max, V, 6], position then normal
+ *             (nrm = NULL; needs FDM_MESH_NORMALS).  FDM_MESH_F16: both outputs fp16, rounded to nearest even at the store.  Without
+ *             FDM_MESH_NORMALS nrm is not touched.  Rows at or past L_out[b] are written as zeros; input rows at or past frames[b] are
+ *             never read (they may be NaN).  No atomics: a clip's rows do not depend on the batch, L_max, L_out_max or a tile size.
+ * fdm_mesh_adjacency_host (no device): the vertex -> incident-face lists in CSR form, offsets [V + 1] and items [3 F] = face indices,
+ * ascending per vertex, one entry per corner.  FDM_ERR_ARG: a null pointer, F < 0, V <= 0, an index outside [0, V).
+ * fdm_mesh_create checks the faces (HOST ints, not read after the call), builds the lists and, with a device visible, uploads both;
+ * without one the object still validates and fdm_mesh_forward ends in FDM_ERR_STATE.  fdm_mesh_frames is host only: the L_out rule.
+ * fdm_mesh_forward: offsets [B, L_max, 3 V] fp32 device, frames [B] HOST ints in [0, L_max] (NULL: every clip has L_max frames; copied
+ * in stream order, not read after the call returns), tmpl [tmpl_rows, 3 V] fp32 device with tmpl_rows = 0 (none), 1 (shared) or B,
+ * frames_out [B] HOST ints or NULL.  Launches on `stream`, never synchronises -- except that a call larger than any before it grows
+ * the object's scratch first (fp32 positions for the normals whenever the planar fp32 output does not hold them; the lengths), which
+ * waits for the device.  An object holds ONE such scratch: it serves one stream at a time (calls on the same stream follow each other
+ * in stream order; use one object per stream for concurrent calls, or order the streams with events).  Every check is made before
+ * the first launch: FDM_ERR_ARG (null m / offsets / pos, unknown flag bits, tmpl_rows not 0, 1 or B, a null template with tmpl_rows > 0,
+ * interleaved with nrm or without normals, planar normals without nrm, a negative or non-finite rate), FDM_ERR_SHAPE (B, L_max or
+ * L_out_max < 1, frames[b] outside [0, L_max], L_out_max below the largest L_out[b]).  Call times against torch and the byte floor: profiles/mesh_out/README.md. */
+#define FDM_MESH_INTERLEAVED 1
+#define FDM_MESH_F16 2
+#define FDM_MESH_NORMALS 4
+typedef struct fdm_mesh fdm_mesh;
+int fdm_mesh_adjacency_host(const int* faces, int F, int V, int* offsets, int* items);
+int fdm_mesh_create(const int* faces, int F, int V, fdm_mesh** out);
+int fdm_mesh_frames(int frames_in, double fps_in, double fps_out, int* frames_out);
+int fdm_mesh_forward(fdm_mesh* m, const float* offsets, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
+                     double fps_out, int flags, void* pos, void* nrm, int L_out_max, int* frames_out, void* stream);
+int fdm_mesh_destroy(fdm_mesh* m);
 
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
  * (diffusion_BIWI_encoder_decoder.py:565-603: cosine schedule in fp64, fp32 cast); DDIM pairs and per-pair coefficients
