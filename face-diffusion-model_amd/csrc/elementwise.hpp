@@ -162,8 +162,19 @@ static hipError_t ln_launch_t(const fdm_ln_args& a, hipStream_t s) {
 __global__ __launch_bounds__(256) void sched_kernel(const fdm_sched_args p) {
   const SchedCoef c = p.mode == 3 ? sched_coef_load<true>(p) : sched_coef_load<false>(p);
   const int k = c.k;
+  // Every WAVE reads *step for itself (sched_coef_load), but only thread 0 takes the block's ticket.  The ticket may be taken only
+  // once all four waves hold their k: without the barrier, waves 1-3 were ordered against nothing (the emitted code had no
+  // s_barrier between their flat_load of *step and wave 0's global_atomic_add), so a wave that issued its read late -- the last
+  // waves to be dispatched of a grid that does not fit the device at once -- could read the k + 1 that the last-ticket block had
+  // already stored and update its elements with the next step's coefficients.  The wait comes first: a workgroup-scope barrier
+  // alone does not wait for vector loads that are still in flight.  (p.arrive and p.advance are launch arguments: the branch
+  // is uniform.)
+  if (p.arrive && p.advance) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
   if (p.arrive && p.advance && threadIdx.x == 0) {
-    // every block reads *step first, then takes a ticket; the block holding the last ticket knows all
+    // every wave of every block has read *step before its block takes a ticket; the block holding the last ticket knows all
     // reads are done and advances the counter (and re-arms the ticket word) -- no separate launch
     const unsigned tk = atomicAdd(p.arrive, 1u);
     if (tk == gridDim.x - 1) {

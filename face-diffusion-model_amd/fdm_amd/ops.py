@@ -173,8 +173,9 @@ def layernorm(x, gamma, beta, M, d, *, add_mat=None, add_tab=None, tab_index=Non
 
 def sched_args(mode, x0, x, x_out, n, *, x0u=None, cfg_scale=0.0, n_per_clip=0, tseq=None, step=None, advance=0,
                c1=None, c2=None, sigma=None, sra=None, srm1=None, sqrt_an=None, c_n=None, noise=None, noise_stride=0,
-               seed=0, clip0=0, x_out_t=None, arrive=None, lm_a=None, lm_b=None, lm_c=None, lm_s=None, x0_hist=None):
-    """fdm_sched_args for fdm_op_sched_step, or (with x0 / x / x_out None) for gemm(..., sched=...)."""
+               seed=0, clip0=0, x_out_t=None, arrive=None, lm_a=None, lm_b=None, lm_c=None, lm_s=None, x0_hist=None, seed_dev=None):
+    """fdm_sched_args for fdm_op_sched_step, or (with x0 / x / x_out None) for gemm(..., sched=...).
+    seed_dev: device int64 [2] = {seed, clip0}, read by the kernel in place of seed / clip0 (fdm_sched_args.seed_dev)."""
     a = SchedArgs()
     a.x0, a.x0u, a.cfg_scale, a.x, a.x_out = _p(x0), _p(x0u), cfg_scale, _p(x), _p(x_out)
     a.n, a.n_per_clip, a.tseq, a.step, a.advance = n, n_per_clip, _p(tseq), _p(step), advance
@@ -184,6 +185,8 @@ def sched_args(mode, x0, x, x_out, n, *, x0u=None, cfg_scale=0.0, n_per_clip=0, 
     a.x_out_t, a.out_dtype, a.arrive = _p(x_out_t), (code_of(x_out_t) if x_out_t is not None else 0), _p(arrive)
     a.x_out_t_lo_off = _lo(x_out_t)
     a.lm_a, a.lm_b, a.lm_c, a.lm_s, a.x0_hist = _p(lm_a), _p(lm_b), _p(lm_c), _p(lm_s), _p(x0_hist)      # mode 3: tables by step k
+    if seed_dev is not None:
+        a.seed_dev = _p(seed_dev)
     return a
 
 
