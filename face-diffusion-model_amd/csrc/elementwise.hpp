@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "sched.hpp"
 #include "../../include/fdm_hip.h"
+#include "host.hpp"      // grid_for: the 1-D launch grid
 
 namespace fdm {
 
@@ -185,25 +186,16 @@ __global__ __launch_bounds__(256) void sched_kernel(const fdm_sched_args p) {
   const long long nq = p.n / 4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
     f32x4 x0 = *(const f32x4*)(p.x0 + 4 * i);
-    if (p.x0u) {
-      f32x4 u = *(const f32x4*)(p.x0u + 4 * i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x0[j] = __fadd_rn(u[j], __fmul_rn(p.cfg_scale, __fsub_rn(x0[j], u[j])));
-    }
+    if (p.x0u) sched_cfg_mix4(x0, *(const f32x4*)(p.x0u + 4 * i), p.cfg_scale);
     f32x4 o;
     if (p.mode == 2) {
       o = x0;
     } else {
       const f32x4 x = *(const f32x4*)(p.x + 4 * i);
-      o = p.mode == 3 ? sched_update4<true>(p, c, x0, x, 4 * i) : sched_update4<false>(p, c, x0, x, 4 * i);
+      o = sched_update4_rt(p, c, x0, x, 4 * i);
     }
     *(f32x4*)(p.x_out + 4 * i) = o;
-    if (p.x_out_t) {
-      if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + 4 * i, 0, o);
-      else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + 4 * i, p.x_out_t_lo_off, o);
-      else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + 4 * i, 0, o);
-      else *(f32x4*)((float*)p.x_out_t + 4 * i) = o;
-    }
+    sched_store_t4(p, 4 * i, o);
   }
 }
 
@@ -212,11 +204,7 @@ __global__ __launch_bounds__(256) void sched_kernel(const fdm_sched_args p) {
 __global__ void step_advance_kernel(int* step) { *step += 1; }
 
 static hipError_t sched_launch(const fdm_sched_args& a, hipStream_t s) {
-  const long long nq = a.n / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sched_kernel, dim3(blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(sched_kernel, dim3(grid_for(a.n / 4)), dim3(256), 0, s, a);
   if (a.advance && a.step && !a.arrive) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, a.step);
   return hipGetLastError();
 }

@@ -243,55 +243,6 @@ int fdm_op_sched_step(const fdm_sched_args* a, void* stream) {
   return submit([c](hipStream_t s) { return fdm::sched_launch(c, s); }, stream, "sched");
 }
 
-int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, void* stream) {
-  if (!a || !a->x0 || !a->x || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_sched: null operand");
-  if (a->noise) return fail(FDM_ERR_ARG, "slot_sched: injected noise is not supported (Philox keyed per slot)");
-  if (a->mode != 0 && a->mode != 1 && a->mode != 3) return fail(FDM_ERR_ARG, "slot_sched: mode %d (0 DDPM, 1 DDIM, 3 table-driven)", a->mode);
-  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_sched: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
-  if (a->mode == 0 && (!a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "slot_sched: DDPM tables missing");
-  if (a->mode == 1 && (!a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "slot_sched: DDIM tables missing");
-  if (a->mode == 3 && (!a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist)) return fail(FDM_ERR_ARG, "slot_sched: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist");
-  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_sched: bad out_dtype %d", a->out_dtype);
-  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_sched: split x_out_t needs x_out_t_lo_off");
-  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state))
-    return fail(FDM_ERR_ARG, "slot_sched: operands and the state words must be 16-byte aligned");
-  fdm_sched_args c = *a;
-  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
-  return submit([c, state, keys](hipStream_t s) { return fdm::slot_sched_launch(c, state, keys, s); }, stream, "slot_sched");
-}
-
-int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
-                            const fdm_slot_group_args* g, void* stream) {
-  if (!a || !g || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_group_sched: null operand");
-  if (!g->member || !g->frames || !g->entries || !g->groups || !g->x_long) return fail(FDM_ERR_ARG, "slot_group_sched: null table or arena");
-  if (!g->init && (!a->x0 || !a->x)) return fail(FDM_ERR_ARG, "slot_group_sched: null operand");
-  if (g->init && g->plain) return fail(FDM_ERR_ARG, "slot_group_sched: init loads the arena into the window rows only (plain must be 0)");
-  if (a->noise) return fail(FDM_ERR_ARG, "slot_group_sched: injected noise is not supported (Philox keyed per slot / group)");
-  if (!g->init && a->mode != 0 && a->mode != 1 && a->mode != 3) return fail(FDM_ERR_ARG, "slot_group_sched: mode %d (0 DDPM, 1 DDIM, 3 table-driven)", a->mode);
-  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
-  if (g->L < 1 || g->d < 4 || g->d % 4 || (long long)g->L * g->d != a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched: L=%d x d=%d (a multiple of 4) must be n_per_clip=%lld", g->L, g->d, a->n_per_clip);
-  if (g->arena_frames < 1 || g->n_groups < 1 || g->n_entries < 1 || g->frame0 < 0 || g->frame1 < g->frame0 || g->frame1 > g->arena_frames)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched: arena frames [%d, %d) outside [0, %d), or no groups / entries", g->frame0, g->frame1, g->arena_frames);
-  if (!g->init) {
-    if (a->mode == 0 && (!a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "slot_group_sched: DDPM tables missing");
-    if (a->mode == 1 && (!a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "slot_group_sched: DDIM tables missing");
-    if (a->mode == 3 && (!a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist || !g->hist_long))
-      return fail(FDM_ERR_ARG, "slot_group_sched: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist and hist_long");
-  }
-  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_group_sched: bad out_dtype %d", a->out_dtype);
-  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_group_sched: split x_out_t needs x_out_t_lo_off");
-  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state) ||
-      !aligned16(g->frames) || !aligned16(g->entries) || !aligned16(g->groups) || !aligned16(g->x_long) || !aligned16(g->hist_long))
-    return fail(FDM_ERR_ARG, "slot_group_sched: operands, table rows and the state words must be 16-byte aligned");
-  fdm_sched_args c = *a;
-  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
-  const fdm_slot_group_args gg = *g;
-  return submit([c, state, keys, gg, n_slots](hipStream_t s) { return fdm::slot_group_sched_launch(c, state, keys, gg, n_slots, s); }, stream, "slot_group_sched");
-}
-
 // what the two bank operators share: the bank's own pointers and sizes (the kernel checks every row against them)
 static int check_bank(const fdm_slot_bank_args* b, const char* who) {
   if (!b || !b->req || !b->desc || !b->t) return fail(FDM_ERR_ARG, "%s: null bank table", who);
@@ -300,49 +251,83 @@ static int check_bank(const fdm_slot_bank_args* b, const char* who) {
   return FDM_OK;
 }
 
-int fdm_op_slot_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
-                           const fdm_slot_bank_args* b, void* stream) {
-  if (!a || !a->x0 || !a->x || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_sched_bank: null operand");
-  FCK(check_bank(b, "slot_sched_bank"));
-  if (a->noise) return fail(FDM_ERR_ARG, "slot_sched_bank: injected noise is not supported (Philox keyed per slot)");
+// The argument checks of the four slot scheduler passes, in one order.  g = the group tables of the group forms (null: plain slots
+// only), b = the bank of the bank forms (null: the mode and the step-indexed tables are a's, and are checked here).
+static int check_slot_pass(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, const fdm_slot_group_args* g,
+                           const fdm_slot_bank_args* b, const char* who) {
+  if (!a || !a->x_out || !state || !keys || (!g && (!a->x0 || !a->x))) return fail(FDM_ERR_ARG, "%s: null operand", who);
+  if (b) FCK(check_bank(b, who));
+  if (g) {
+    if (!g->member || !g->frames || !g->entries || !g->groups || !g->x_long) return fail(FDM_ERR_ARG, "%s: null table or arena", who);
+    if (!g->init && (!a->x0 || !a->x)) return fail(FDM_ERR_ARG, "%s: null operand", who);
+    if (g->init && g->plain) return fail(FDM_ERR_ARG, "%s: init loads the arena into the window rows only (plain must be 0)", who);
+  }
+  const bool own_sampler = !b && !(g && g->init);      // a's mode and tables are read: no bank holds them, and the launch updates
+  if (a->noise) return fail(FDM_ERR_ARG, "%s: injected noise is not supported (Philox keyed per slot%s)", who, g ? " / group" : "");
+  if (own_sampler && a->mode != 0 && a->mode != 1 && a->mode != 3) return fail(FDM_ERR_ARG, "%s: mode %d (0 DDPM, 1 DDIM, 3 table-driven)", who, a->mode);
   if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_sched_bank: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
-  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_sched_bank: bad out_dtype %d", a->out_dtype);
-  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_sched_bank: split x_out_t needs x_out_t_lo_off");
-  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state))
-    return fail(FDM_ERR_ARG, "slot_sched_bank: operands and the state words must be 16-byte aligned");
+    return fail(FDM_ERR_SHAPE, "%s: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", who, a->n, n_slots, a->n_per_clip);
+  if (g) {
+    if (g->L < 1 || g->d < 4 || g->d % 4 || (long long)g->L * g->d != a->n_per_clip)
+      return fail(FDM_ERR_SHAPE, "%s: L=%d x d=%d (a multiple of 4) must be n_per_clip=%lld", who, g->L, g->d, a->n_per_clip);
+    if (g->arena_frames < 1 || g->n_groups < 1 || g->n_entries < 1 || g->frame0 < 0 || g->frame1 < g->frame0 || g->frame1 > g->arena_frames)
+      return fail(FDM_ERR_SHAPE, "%s: arena frames [%d, %d) outside [0, %d), or no groups / entries", who, g->frame0, g->frame1, g->arena_frames);
+  }
+  if (own_sampler) {
+    if (a->mode == 0 && (!a->c1 || !a->c2 || !a->sigma)) return fail(FDM_ERR_ARG, "%s: DDPM tables missing", who);
+    if (a->mode == 1 && (!a->sra || !a->srm1 || !a->sqrt_an || !a->c_n)) return fail(FDM_ERR_ARG, "%s: DDIM tables missing", who);
+    if (a->mode == 3 && (!a->lm_a || !a->lm_b || !a->lm_c || !a->lm_s || !a->x0_hist || (g && !g->hist_long)))
+      return fail(FDM_ERR_ARG, "%s: table-driven sampler needs lm_a, lm_b, lm_c, lm_s, x0_hist%s", who, g ? " and hist_long" : "");
+  }
+  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "%s: bad out_dtype %d", who, a->out_dtype);
+  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "%s: split x_out_t needs x_out_t_lo_off", who);
+  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state) ||
+      (g && (!aligned16(g->frames) || !aligned16(g->entries) || !aligned16(g->groups) || !aligned16(g->x_long) || !aligned16(g->hist_long))))
+    return fail(FDM_ERR_ARG, "%s: operands%s and the state words must be 16-byte aligned", who, g ? ", table rows" : "");
+  return FDM_OK;
+}
+// a bank form called without a bank: the null-operand check comes first, then check_bank refuses this one ("null bank table")
+static const fdm_slot_bank_args no_bank = {};
+
+// the pass's copy of the arguments: the fields no slot pass reads are cleared, and with a bank the step-indexed tables it holds
+static fdm_sched_args slot_pass_args(const fdm_sched_args* a, bool bank) {
   fdm_sched_args c = *a;
   c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
-  c.sqrt_an = c.c_n = nullptr; c.lm_a = c.lm_b = c.lm_c = c.lm_s = nullptr;      // (the bank holds every step-indexed table)
+  if (bank) { c.sqrt_an = c.c_n = nullptr; c.lm_a = c.lm_b = c.lm_c = c.lm_s = nullptr; }
+  return c;
+}
+
+int fdm_op_slot_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots, void* stream) {
+  FCK(check_slot_pass(a, state, keys, n_slots, nullptr, nullptr, "slot_sched"));
+  const fdm_sched_args c = slot_pass_args(a, false);
+  return submit([c, state, keys](hipStream_t s) { return fdm::slot_sched_launch(c, state, keys, nullptr, s); }, stream, "slot_sched");
+}
+
+int fdm_op_slot_group_sched(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                            const fdm_slot_group_args* g, void* stream) {
+  if (!g) return fail(FDM_ERR_ARG, "slot_group_sched: null operand");
+  FCK(check_slot_pass(a, state, keys, n_slots, g, nullptr, "slot_group_sched"));
+  const fdm_sched_args c = slot_pass_args(a, false);
+  const fdm_slot_group_args gg = *g;
+  return submit([c, state, keys, gg, n_slots](hipStream_t s) { return fdm::slot_group_sched_launch(c, state, keys, gg, n_slots, nullptr, s); }, stream, "slot_group_sched");
+}
+
+int fdm_op_slot_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
+                           const fdm_slot_bank_args* b, void* stream) {
+  FCK(check_slot_pass(a, state, keys, n_slots, nullptr, b ? b : &no_bank, "slot_sched_bank"));
+  const fdm_sched_args c = slot_pass_args(a, true);
   const fdm_slot_bank_args bb = *b;
-  return submit([c, state, keys, bb](hipStream_t s) { return fdm::slot_sched_bank_launch(c, state, keys, bb, s); }, stream, "slot_sched_bank");
+  return submit([c, state, keys, bb](hipStream_t s) { return fdm::slot_sched_launch(c, state, keys, &bb, s); }, stream, "slot_sched_bank");
 }
 
 int fdm_op_slot_group_sched_bank(const fdm_sched_args* a, const int* state, const unsigned long long* keys, int n_slots,
                                  const fdm_slot_group_args* g, const fdm_slot_bank_args* b, void* stream) {
-  if (!a || !g || !a->x_out || !state || !keys) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null operand");
-  FCK(check_bank(b, "slot_group_sched_bank"));
-  if (!g->member || !g->frames || !g->entries || !g->groups || !g->x_long) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null table or arena");
-  if (!g->init && (!a->x0 || !a->x)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null operand");
-  if (g->init && g->plain) return fail(FDM_ERR_ARG, "slot_group_sched_bank: init loads the arena into the window rows only (plain must be 0)");
-  if (a->noise) return fail(FDM_ERR_ARG, "slot_group_sched_bank: injected noise is not supported (Philox keyed per slot / group)");
-  if (n_slots < 1 || a->n_per_clip <= 0 || a->n_per_clip % 4 || a->n != (long long)n_slots * a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: n=%lld must be n_slots=%d x n_per_clip=%lld (a multiple of 4)", a->n, n_slots, a->n_per_clip);
-  if (g->L < 1 || g->d < 4 || g->d % 4 || (long long)g->L * g->d != a->n_per_clip)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: L=%d x d=%d (a multiple of 4) must be n_per_clip=%lld", g->L, g->d, a->n_per_clip);
-  if (g->arena_frames < 1 || g->n_groups < 1 || g->n_entries < 1 || g->frame0 < 0 || g->frame1 < g->frame0 || g->frame1 > g->arena_frames)
-    return fail(FDM_ERR_SHAPE, "slot_group_sched_bank: arena frames [%d, %d) outside [0, %d), or no groups / entries", g->frame0, g->frame1, g->arena_frames);
-  if (a->x_out_t && !kind_ok(a->out_dtype)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: bad out_dtype %d", a->out_dtype);
-  if (a->x_out_t && a->out_dtype == FDM_F16X3 && (a->x_out_t_lo_off <= 0 || a->x_out_t_lo_off % 4)) return fail(FDM_ERR_ARG, "slot_group_sched_bank: split x_out_t needs x_out_t_lo_off");
-  if (!aligned16(a->x0) || !aligned16(a->x0u) || !aligned16(a->x) || !aligned16(a->x_out) || !aligned16(a->x_out_t) || !aligned16(a->x0_hist) || !aligned16(state) ||
-      !aligned16(g->frames) || !aligned16(g->entries) || !aligned16(g->groups) || !aligned16(g->x_long) || !aligned16(g->hist_long))
-    return fail(FDM_ERR_ARG, "slot_group_sched_bank: operands, table rows and the state words must be 16-byte aligned");
-  fdm_sched_args c = *a;
-  c.noise = nullptr; c.step = nullptr; c.tseq = nullptr; c.seed_dev = nullptr; c.arrive = nullptr;
-  c.sqrt_an = c.c_n = nullptr; c.lm_a = c.lm_b = c.lm_c = c.lm_s = nullptr;
+  if (!g) return fail(FDM_ERR_ARG, "slot_group_sched_bank: null operand");
+  FCK(check_slot_pass(a, state, keys, n_slots, g, b ? b : &no_bank, "slot_group_sched_bank"));
+  const fdm_sched_args c = slot_pass_args(a, true);
   const fdm_slot_group_args gg = *g;
   const fdm_slot_bank_args bb = *b;
-  return submit([c, state, keys, gg, n_slots, bb](hipStream_t s) { return fdm::slot_group_sched_bank_launch(c, state, keys, gg, n_slots, bb, s); }, stream,
+  return submit([c, state, keys, gg, n_slots, bb](hipStream_t s) { return fdm::slot_group_sched_launch(c, state, keys, gg, n_slots, &bb, s); }, stream,
                 "slot_group_sched_bank");
 }
 

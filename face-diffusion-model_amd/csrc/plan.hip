@@ -560,28 +560,24 @@ int get_program(fdm_plan* P, const ProgSpec& sp, void* stream, fdm_prog** out) {
       // slot program: advance every slot's word, the chain with per-slot table rows and its scheduler update unfused, then the
       // pass that updates the live slots only -- two launches more than the plain program without guidance
       sc.n_per_clip = (long long)P->L * d; sc.noise = nullptr; sc.seed_dev = nullptr; sc.step = nullptr; sc.tseq = nullptr;
+      const fdm_slot_bank_args bk = bank_args(P);
       if (sp.bank) {
-        // sampler bank: the same three parts, both ends reading every slot's own sampler; sc carries the t-indexed tables of every
-        // mode and the plain slots' history (mode, scale and the step-indexed tables come from the bank)
-        const fdm_slot_bank_args bk = bank_args(P);
+        // sampler bank: both ends read every slot's own sampler; sc carries the t-indexed tables of every mode and the plain slots'
+        // history (mode, scale and the step-indexed tables come from the bank)
         sc.mode = 0; sc.cfg_scale = 0.f;
         sc.c1 = P->c1; sc.c2 = P->c2; sc.sigma = P->sigma; sc.sra = P->sra; sc.srm1 = P->srm1; sc.x0_hist = P->x0_hist;
         rc = fdm::slot_advance_bank_op(P->slot_state, bk, P->slots, stream);
-        if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
-        if (rc == FDM_OK) {
-          if (P->long_frames) { const fdm_slot_group_args lg = long_args(P, 0, P->long_frames, 1, 0); rc = fdm_op_slot_group_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &lg, &bk, stream); }
-          else rc = fdm_op_slot_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &bk, stream);
-        }
-        continue;
+      } else {
+        rc = fdm::slot_advance_op(P->slot_state, P->tseq, sp.slot_steps, P->slots, stream);
       }
-      rc = fdm::slot_advance_op(P->slot_state, P->tseq, sp.slot_steps, P->slots, stream);
       if (rc == FDM_OK) rc = record_chain(P, nullptr, stream);
-      if (rc == FDM_OK) {
-        // long capacity: the same launch also updates the groups over the long arena (fdm_op_slot_group_sched); without it the
-        // program is the plain slot program
-        if (P->long_frames) { const fdm_slot_group_args lg = long_args(P, 0, P->long_frames, 1, 0); rc = fdm_op_slot_group_sched(&sc, P->slot_state, P->slot_keys, P->slots, &lg, stream); }
-        else rc = fdm_op_slot_sched(&sc, P->slot_state, P->slot_keys, P->slots, stream);
-      }
+      if (rc != FDM_OK) break;
+      // long capacity: the same launch also updates the groups over the long arena; without it the pass is the plain slots' one
+      const fdm_slot_group_args lg = long_args(P, 0, P->long_frames, 1, 0);
+      if (sp.bank) rc = P->long_frames ? fdm_op_slot_group_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &lg, &bk, stream)
+                                       : fdm_op_slot_sched_bank(&sc, P->slot_state, P->slot_keys, P->slots, &bk, stream);
+      else rc = P->long_frames ? fdm_op_slot_group_sched(&sc, P->slot_state, P->slot_keys, P->slots, &lg, stream)
+                               : fdm_op_slot_sched(&sc, P->slot_state, P->slot_keys, P->slots, stream);
       continue;
     }
     if (sp.kind != 0 && P->win_n) {
@@ -634,20 +630,22 @@ int set_steps(fdm_plan* P, const int* ts, int n, void* stream) {
   return FDM_OK;
 }
 
+// The operand-kind copy of the n fp32 elements at src (rows of P->x) into dst_t (the same rows of P->xt), whatever the plane distance
+// P->xt.lo: the scheduler's mix-only mode (x_out = x0 = src) rewrites src in place and writes the copy through its store path.
+int operand_copy(fdm_plan* P, float* src, void* dst_t, long long n, void* stream) {
+  fdm_sched_args sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.mode = 2; sc.x0 = src; sc.x_out = src; sc.n = n; sc.x_out_t = dst_t; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo;
+  return fdm_op_sched_step(&sc, stream);
+}
+
 int load_x(fdm_plan* P, const float* x, void* stream) {
   const long long n = (long long)P->M * P->m.d;
   HIPCK(hipMemcpyAsync(P->x, x, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (P->dtype != FDM_F32) {
-    // (the plane distance of ws.xt is its capacity, not n: cast plane by plane through the op's contract lo = dst + n only
-    //  when they coincide; otherwise use the scheduler's store path with identity coefficients -- simpler: a strided cast)
-    if (kind(P->dtype).planes == 1 || P->xt.lo == n) return fdm_op_cast(P->x, P->xt.p, n, P->dtype, stream);
-    // capacity > current shape: run the mix-only scheduler mode (x_out = x0), which writes the operand copy with any plane distance
-    fdm_sched_args sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.mode = 2; sc.x0 = P->x; sc.x_out = P->x; sc.n = n; sc.x_out_t = P->xt.p; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo;
-    return fdm_op_sched_step(&sc, stream);
-  }
-  return FDM_OK;
+  if (P->dtype == FDM_F32) return FDM_OK;
+  // fdm_op_cast's contract is lo = dst + n; the plane distance of xt is its capacity, so a plan below capacity takes the other path
+  if (kind(P->dtype).planes == 1 || P->xt.lo == n) return fdm_op_cast(P->x, P->xt.p, n, P->dtype, stream);
+  return operand_copy(P, P->x, P->xt.p, n, stream);
 }
 
 // windowed plan: x_T in long layout -> the long buffer, then the window rows (+ their operand copy) through the window pass's store path
@@ -697,52 +695,6 @@ int take_steps(const fdm_sample_args* a, std::vector<int>& ts) {
   return FDM_OK;
 }
 
-// the sampler of a call: its timestep list, its program kind and its device tables (DDIM: cached per step count; table-driven:
-// uploaded per call, history zeroed).  Shared by fdm_sample_graph / fdm_sample_windows and fdm_slots_open.
-int sampler_setup(fdm_plan* P, const fdm_sample_args* a, void* stream, std::vector<int>& ts, ProgSpec& sp) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a->kind == 0) {
-    if (!a->t_list || a->n_steps <= 0) return fail(FDM_ERR_ARG, "sample_graph: DDPM needs t_list / n_steps");
-    FCK(take_steps(a, ts));
-    sp.kind = 1; sp.noise = a->noise;
-  } else if (a->kind == 1) {
-    if (a->ddim_steps <= 0) return fail(FDM_ERR_ARG, "sample_graph: DDIM needs ddim_steps");
-    if (!P->ddim.count(a->ddim_steps)) {
-      std::vector<int> t(a->ddim_steps), tn(a->ddim_steps);
-      std::vector<float> tab(2 * (size_t)a->ddim_steps);
-      const int n = fdm_ddim_schedule_host(a->ddim_steps, 1000, t.data(), tn.data(), tab.data(), tab.data() + a->ddim_steps);
-      if (n < 0) return n;
-      float* dv = nullptr;
-      FCK(zalloc(P->mem, &dv, 2 * (size_t)a->ddim_steps));
-      HIPCK(hipMemcpyAsync(dv, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-      HIPCK(hipStreamSynchronize(s));
-      t.resize(n);
-      P->ddim[a->ddim_steps] = {n, dv};
-      P->ddim_t[a->ddim_steps] = t;
-    }
-    ts = P->ddim_t[a->ddim_steps];
-    sp.kind = 2; sp.san = P->ddim[a->ddim_steps].second; sp.cn = sp.san + a->ddim_steps;
-  } else if (a->kind == 2) {
-    FCK(check_tables_args(a));
-    FCK(take_steps(a, ts));
-    if (a->n_steps > P->lm_cap) {      // a longer table than any before: a new buffer (recorded programs point at the old one)
-      FCK(drop_programs(P, stream));
-      P->mem.free_one(P->lm_tab);
-      P->lm_tab = nullptr; P->lm_cap = a->n_steps;
-      FCK(zalloc(P->mem, &P->lm_tab, (size_t)4 * P->lm_cap));
-    }
-    for (int j = 0; j < 4; ++j)        // set_steps() below drains the copies (the tables are caller memory)
-      HIPCK(hipMemcpyAsync(P->lm_tab + (size_t)j * P->lm_cap, a->lm_tables + (size_t)j * a->n_steps, (size_t)a->n_steps * 4, hipMemcpyHostToDevice, s));
-    // a call never sees the history of the one before it (the shipped tables have c[0] = 0 and do not read it at step 0)
-    if (P->win_n) HIPCK(hipMemsetAsync(P->hist_long, 0, (size_t)P->win_B * P->win_total * P->m.d * 4, s));
-    else HIPCK(hipMemsetAsync(P->x0_hist, 0, (size_t)P->M * P->m.d * 4, s));
-    sp.kind = 3; sp.noise = a->noise; sp.san = P->lm_tab;
-  } else {
-    return fail(FDM_ERR_ARG, "sample_graph: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", a->kind);
-  }
-  return FDM_OK;
-}
-
 // A sampler definition as the bank stores it (slots.hpp): the scheduler mode, the timestep list and the step-indexed coefficients
 // in bank layout -- the values sampler_setup puts on the device for the same arguments, so a slot's bits match the solo path.
 struct SamplerDef { int kind = 0, mode = 0; std::vector<int> ts; std::vector<float> coef; };
@@ -758,8 +710,7 @@ int sampler_def(const fdm_sample_args* a, const char* who, SamplerDef& o) {
     std::vector<float> tab(2 * (size_t)a->ddim_steps);
     const int n = fdm_ddim_schedule_host(a->ddim_steps, 1000, t.data(), tn.data(), tab.data(), tab.data() + a->ddim_steps);
     if (n < 0) return n;
-    if (n == 0) return fail(FDM_ERR_ARG, "%s: the sampler has no live step (ddim_steps = %d)", who, a->ddim_steps);
-    o.mode = 1;
+    o.mode = 1;              // (n == 0, only the dead pair: an empty list -- a solo call copies x_T through, the bank's callers refuse it)
     o.ts.assign(t.begin(), t.begin() + n);                                   // (the dead last pair is skipped)
     o.coef.assign(tab.begin(), tab.begin() + n);                             // sqrt_an[n] | c_n[n]
     o.coef.insert(o.coef.end(), tab.begin() + a->ddim_steps, tab.begin() + a->ddim_steps + n);
@@ -770,6 +721,69 @@ int sampler_def(const fdm_sample_args* a, const char* who, SamplerDef& o) {
     o.coef.assign(a->lm_tables, a->lm_tables + 4 * (size_t)a->n_steps);      // a | b | c | s, each n_steps
   } else {
     return fail(FDM_ERR_ARG, "%s: kind %d (0 = DDPM, 1 = DDIM, 2 = table-driven)", who, a->kind);
+  }
+  return FDM_OK;
+}
+
+// the sampler of a call: its timestep list, its program kind and its device tables (DDIM: cached per step count; table-driven:
+// uploaded per call, history zeroed).  Shared by fdm_sample_graph / fdm_sample_windows and fdm_slots_open.  The list and the DDIM
+// tables are sampler_def's, so the solo path and the bank cannot drift.
+int sampler_setup(fdm_plan* P, const fdm_sample_args* a, void* stream, std::vector<int>& ts, ProgSpec& sp) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool cached = a->kind == 1 && P->ddim.count(a->ddim_steps);      // a DDIM step count seen before: list and tables are on the plan
+  SamplerDef def;
+  if (!cached) FCK(sampler_def(a, "sample_graph", def));
+  if (a->kind == 0) {
+    ts = def.ts;
+    sp.kind = 1; sp.noise = a->noise;
+  } else if (a->kind == 1) {
+    if (!cached) {           // sqrt_an[n] | c_n[n] of the n live pairs (n = 0, e.g. ddim_steps = 1: an empty list, nothing is read)
+      float* dv = nullptr;
+      FCK(zalloc(P->mem, &dv, std::max<size_t>(def.coef.size(), 1)));
+      if (!def.coef.empty()) HIPCK(hipMemcpyAsync(dv, def.coef.data(), def.coef.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCK(hipStreamSynchronize(s));
+      P->ddim[a->ddim_steps] = {(int)def.ts.size(), dv};
+      P->ddim_t[a->ddim_steps] = def.ts;
+    }
+    ts = P->ddim_t[a->ddim_steps];
+    sp.kind = 2; sp.san = P->ddim[a->ddim_steps].second; sp.cn = sp.san + ts.size();
+  } else {                   // table-driven (sampler_def refused every other kind)
+    ts = def.ts;
+    if (a->n_steps > P->lm_cap) {      // a longer table than any before: a new buffer (recorded programs point at the old one)
+      FCK(drop_programs(P, stream));
+      P->mem.free_one(P->lm_tab);
+      P->lm_tab = nullptr; P->lm_cap = a->n_steps;
+      FCK(zalloc(P->mem, &P->lm_tab, (size_t)4 * P->lm_cap));
+    }
+    for (int j = 0; j < 4; ++j)        // set_steps() below drains the copies (the tables are caller memory)
+      HIPCK(hipMemcpyAsync(P->lm_tab + (size_t)j * P->lm_cap, a->lm_tables + (size_t)j * a->n_steps, (size_t)a->n_steps * 4, hipMemcpyHostToDevice, s));
+    // a call never sees the history of the one before it (the shipped tables have c[0] = 0 and do not read it at step 0)
+    if (P->win_n) HIPCK(hipMemsetAsync(P->hist_long, 0, (size_t)P->win_B * P->win_total * P->m.d * 4, s));
+    else HIPCK(hipMemsetAsync(P->x0_hist, 0, (size_t)P->M * P->m.d * 4, s));
+    sp.kind = 3; sp.noise = a->noise; sp.san = P->lm_tab;
+  }
+  return FDM_OK;
+}
+
+// n_steps steps of the program sp as graph launches: K steps per launch (the K-step program of the same spec; graph_steps, 10 when
+// not set), then the remainder one step per launch on the 1-step program p1.  Shared by fdm_sample_graph / _windows and fdm_slots_run.
+int replay_steps(fdm_plan* P, const ProgSpec& sp, fdm_prog* p1, int n_steps, int graph_steps, void* stream) {
+  int K = graph_steps > 0 ? graph_steps : 10;
+  if (K > n_steps) K = n_steps;
+  int left = n_steps;
+  if (K > 1) {
+    ProgSpec spk = sp; spk.reps = K;
+    fdm_prog* pk = nullptr;
+    FCK(get_program(P, spk, stream, &pk));
+    FCK(fdm_prog_instantiate(pk, stream));
+    FCK(fdm_prog_replay(pk, left / K, stream));
+    P->last_graph_launches += left / K;
+    left %= K;
+  }
+  if (left) {
+    FCK(fdm_prog_instantiate(p1, stream));
+    FCK(fdm_prog_replay(p1, left, stream));
+    P->last_graph_launches += left;
   }
   return FDM_OK;
 }
@@ -808,23 +822,7 @@ int sample_impl(fdm_plan* P, const fdm_sample_args* a, void* stream) {
       if (a->record) HIPCK(hipMemcpyAsync(a->record + (size_t)i * nx, xc, nb, hipMemcpyDeviceToDevice, s));
     }
   } else {
-    int K = a->graph_steps > 0 ? a->graph_steps : 10;
-    if (K > n_steps) K = n_steps;
-    int left = n_steps;
-    if (K > 1) {
-      ProgSpec spk = sp; spk.reps = K;
-      fdm_prog* pk = nullptr;
-      FCK(get_program(P, spk, stream, &pk));
-      FCK(fdm_prog_instantiate(pk, stream));
-      FCK(fdm_prog_replay(pk, left / K, stream));
-      P->last_graph_launches += left / K;
-      left %= K;
-    }
-    if (left) {
-      FCK(fdm_prog_instantiate(p1, stream));
-      FCK(fdm_prog_replay(p1, left, stream));
-      P->last_graph_launches += left;
-    }
+    FCK(replay_steps(P, sp, p1, n_steps, a->graph_steps, stream));
   }
   HIPCK(hipMemcpyAsync(a->out, xc, nb, hipMemcpyDeviceToDevice, s));
   return FDM_OK;
@@ -1240,6 +1238,7 @@ int fdm_slots_open(fdm_plan* P, int B, int L, int cfg, const fdm_sample_args* a,
   P->sampler_host.clear();
   if (want_bank) {
     FCK(sampler_def(a, "slots_open", def0));
+    if (def0.ts.empty()) return fail(FDM_ERR_ARG, "slots_open: the sampler has no live step (ddim_steps = %d)", a->ddim_steps);
     const int rows = 1 + P->want_samplers, nt = (int)def0.ts.size() + P->want_sampler_steps;
     FCK(grow(P, &P->slot_req, &P->slot_req_cap, (size_t)B * 16, stream));
     FCK(grow(P, (void**)&P->bank_desc, &P->bank_desc_cap, (size_t)rows * 16, stream));
@@ -1341,13 +1340,7 @@ static int slot_admit_impl(fdm_plan* P, int slot, const float* hub, int N, int f
   HIPCK(hipMemcpyAsync(P->x + o, x_T, nclip * 4, hipMemcpyDeviceToDevice, s));
   if (pad) HIPCK(hipMemsetAsync(P->x + o + nclip, 0, npad * 4, s));
   HIPCK(hipMemsetAsync(P->x0_hist + o, 0, (size_t)L * d * 4, s));
-  if (P->dtype != FDM_F32) {      // (the scheduler's mix-only mode writes an operand copy at any plane distance, as load_x does)
-    fdm_sched_args sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.mode = 2; sc.x0 = P->x + o; sc.x_out = P->x + o; sc.n = (long long)L * d;
-    sc.x_out_t = (char*)P->xt.p + o * kind(P->dtype).bytes; sc.out_dtype = P->dtype; sc.x_out_t_lo_off = P->xt.lo;
-    FCK(fdm_op_sched_step(&sc, stream));
-  }
+  if (P->dtype != FDM_F32) FCK(operand_copy(P, P->x + o, (char*)P->xt.p + o * kind(P->dtype).bytes, (long long)L * d, stream));
   // {k = -1, running}: the next step's advance launch makes it step 0 of this slot's chain
   FCK(slot_start(P, slot, t0, seed, clip_id, sampler, cfg_scale, stream));
   h.status = 1; h.done = 0; h.L = L_clip; h.sampler = sampler; h.total = total;
@@ -1384,23 +1377,7 @@ int fdm_slots_run(fdm_plan* P, int n_steps, void* stream) {
   if (P->slot_eager) {
     for (int i = 0; i < n_steps; ++i) FCK(fdm_prog_run(p1, stream));
   } else {
-    int K = P->slot_graph_steps > 0 ? P->slot_graph_steps : 10;
-    if (K > n_steps) K = n_steps;
-    int left = n_steps;
-    if (K > 1) {
-      ProgSpec spk = sp; spk.reps = K;
-      fdm_prog* pk = nullptr;
-      FCK(get_program(P, spk, stream, &pk));
-      FCK(fdm_prog_instantiate(pk, stream));
-      FCK(fdm_prog_replay(pk, left / K, stream));
-      P->last_graph_launches += left / K;
-      left %= K;
-    }
-    if (left) {
-      FCK(fdm_prog_instantiate(p1, stream));
-      FCK(fdm_prog_replay(p1, left, stream));
-      P->last_graph_launches += left;
-    }
+    FCK(replay_steps(P, sp, p1, n_steps, P->slot_graph_steps, stream));
   }
   // the host mirror: a running slot does min(n_steps, what ITS chain has left) steps and freezes when the chain ends
   for (auto& h : P->slot_host)
@@ -1602,6 +1579,7 @@ int fdm_slot_sampler_add(fdm_plan* P, const fdm_sample_args* a, void* stream) {
   FCK(check_slots(P, "slot_sampler_add"));
   SamplerDef def;
   FCK(sampler_def(a, "slot_sampler_add", def));
+  if (def.ts.empty()) return fail(FDM_ERR_ARG, "slot_sampler_add: the sampler has no live step (ddim_steps = %d)", a->ddim_steps);
   if (!P->bank_rows) return fail(FDM_ERR_STATE, "slot_sampler_add: the session has no sampler bank (fdm_plan_set slot_samplers / slot_sampler_steps before fdm_slots_open)");
   int id = -1;
   for (int i = 1; i < P->bank_rows && id < 0; ++i)

@@ -1,6 +1,7 @@
 // Device functions of the diffusion scheduler update (DDPM posterior sample / DDIM eta = 0 / table-driven linear multistep) and its
-// Philox noise, shared by sched_kernel (elementwise.hpp), the GEMM epilogue's fused form (gemm.hpp) and window_sched_kernel
-// (window.hpp) so all three produce the same bits.
+// Philox noise, shared by sched_kernel (elementwise.hpp), the GEMM epilogue's fused form (gemm.hpp), window_sched_kernel
+// (window.hpp) and the slot passes (slots.hpp) so all of them produce the same bits.  The pieces of a scheduler pass around the
+// update -- guidance mix, window blend, mode dispatch, operand copy -- are at the end of this file, once, for the same reason.
 #pragma once
 #include "common.hpp"
 #include "../../include/fdm_hip.h"
@@ -111,6 +112,42 @@ __device__ __forceinline__ f32x4 sched_update4(const fdm_sched_args& p, const Sc
     }
   }
   return o;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The pieces of a scheduler pass around the update.  "A slot's bits are the solo call's bits, a group's bits are the windowed
+// call's bits" holds because every pass goes through the SAME expression in the same operand order: change one here and every
+// form named at it changes with it.  (Their launchers share the grid as well: grid_for of host.hpp, 256 lanes per block.)
+// ------------------------------------------------------------------------------------------------
+// Guidance mix of a quad, x0 <- u + scale * (x0 - u) (utiles/classifierfree.py:20-21), unfused.  Must agree: sched_kernel,
+// slot_update_quad (both slot kernels, plain slots of both group kernels), the per-window mix of slot_group_sched_kernel and of
+// window_sched_kernel.
+__device__ __forceinline__ void sched_cfg_mix4(f32x4& x0, const f32x4& u, float scale) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x0[j] = __fadd_rn(u[j], __fmul_rn(scale, __fsub_rn(x0[j], u[j])));
+}
+// One term of the window blend, terms taken in ascending window order.  The first term STARTS the sum (it is not added to a
+// zero): one window of weight 1 passes x0 through bit for bit, -0 included.  Must agree: window_sched_kernel and the arena walk of
+// slot_group_sched_kernel (a long request in slots against fdm_sample_windows).
+__device__ __forceinline__ void sched_blend4(f32x4& acc, bool first, float wt, const f32x4& x0) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = first ? __fmul_rn(wt, x0[j]) : __fadd_rn(acc[j], __fmul_rn(wt, x0[j]));
+}
+// sched_update4 with the mode chosen at run time (p.mode 0 / 1 / 3).  Must agree: sched_kernel, window_sched_kernel and the slot
+// kernels; the GEMM epilogue's fused form picks the same two specialisations at compile time (GEMM_LM).
+__device__ __forceinline__ f32x4 sched_update4_rt(const fdm_sched_args& p, const SchedCoef& c, const f32x4& x0, const f32x4& x, long long e) {
+  return p.mode == 3 ? sched_update4<true>(p, c, x0, x, e) : sched_update4<false>(p, c, x0, x, e);
+}
+// The operand-kind copy of an updated quad at flat element q of p.x_out_t (nothing when there is none): what the next step's first
+// GEMM reads.  F32 = the fp32 kind is compiled in; window_sched_kernel is never given x_out_t on an fp32 plan and has no such
+// store.  Must agree: sched_kernel (+ its mix-only mode, which admits and loads go through), the slot kernels, window_sched_kernel.
+template <bool F32 = true>
+__device__ __forceinline__ void sched_store_t4(const fdm_sched_args& p, long long q, const f32x4& o) {
+  if (!p.x_out_t) return;
+  if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + q, 0, o);
+  else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + q, p.x_out_t_lo_off, o);
+  else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + q, 0, o);
+  else if constexpr (F32) *(f32x4*)((float*)p.x_out_t + q) = o;
 }
 
 }  // namespace fdm

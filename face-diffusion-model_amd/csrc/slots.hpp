@@ -1,13 +1,14 @@
 // In-flight batching (fdm_slots_open / fdm_slot_admit / fdm_slots_run): the slots of a plan are clips at DIFFERENT diffusion
 // steps inside one step program.  Per-slot device state, advanced once per diffusion step before anything reads it, and the
-// scheduler pass that updates every live slot with its own (k, t, seed, clip id) -- sched_update4 / sched_noise4 of sched.hpp, so a
-// slot's bits are those of sched_kernel on the clip alone.  Vector loads and stores only; state words are written in plain C++.
+// scheduler pass that updates every live slot with its own (k, t, seed, clip id) -- the mix, update, noise and stores of sched.hpp,
+// so a slot's bits are those of sched_kernel on the clip alone.  Vector loads and stores only; state words are written in plain C++.
 // Long requests (fdm_slot_admit_long): a recording longer than a slot occupies a GROUP of slots, one window each; with long capacity
 // the scheduler pass is slot_group_sched_kernel, which does the plain slots' update and, over the long arena, window_sched_kernel's
-// blend + update per group at the group's own (k, t).
+// blend + update per group at the group's own (k, t) (its own table walk, sched.hpp's blend term).
 // Sampler bank (fdm_slot_sampler_add / fdm_slot_admit_as): with bank capacity every slot names ITS OWN sampler and guidance scale.
-// The bank forms below (slot_advance_bank_kernel, slot_sched_bank_kernel, slot_group_sched_bank_kernel) read them through
-// fdm_slot_bank_args; the forms without a bank keep their code.  Layout of the bank, all plan-owned device memory:
+// Each pass is ONE body, slot_sched_kernel<BANK> and slot_group_sched_kernel<BANK>: the <true> instantiations read the sampler and
+// the scale through fdm_slot_bank_args (behind `if constexpr (BANK)`), the <false> ones compile to the code without a bank.  The
+// advance launch has two kernels (slot_advance_kernel, slot_advance_bank_kernel).  Layout of the bank, all plan-owned device memory:
 //   req    [n_slots]     rows {int sampler, float cfg_scale, int 0, int 0}      -- its own array: SlotState keeps its stride
 //   desc   [n_samplers]  rows {int mode (0 DDPM / 1 DDIM / 3 table-driven), int n_steps, int t_off, int c_off}; n_steps == 0 = free row
 //   t      [n_t]         ints: sampler i's timesteps are t[t_off .. t_off + n_steps)
@@ -20,6 +21,7 @@
 #include "sched.hpp"
 #include "../../include/fdm_hip.h"
 #include "kernels.hpp"
+#include "host.hpp"      // grid_for: the 1-D launch grid of the pass
 
 namespace fdm {
 
@@ -110,9 +112,8 @@ __device__ __forceinline__ bool slot_bank_view(const fdm_sched_args& p, const fd
 
 // The per-step scalars of a slot at ITS (k, t), noise keyed (seed, clip0 + clip of the element).  BANK: p.mode is the mode of the slot's
 // sampler and the step-indexed tables are the slot's range of the bank (bv, checked by slot_bank_view); the t-indexed ones are p's.
-template <bool BANK = false>
-__device__ __forceinline__ SchedCoef slot_coef(const fdm_sched_args& p, const SlotState& s, unsigned long long seed, int clip0,
-                                               const SlotBankView* bv = nullptr) {
+template <bool BANK>
+__device__ __forceinline__ SchedCoef slot_coef(const fdm_sched_args& p, const SlotState& s, unsigned long long seed, int clip0, const SlotBankView& bv) {
   SchedCoef c;
   c.k = s.k; c.t = s.t;
   c.c1 = c.c2 = c.sg = c.sra = c.san = c.cn = 0.f;
@@ -120,8 +121,8 @@ __device__ __forceinline__ SchedCoef slot_coef(const fdm_sched_args& p, const Sl
   c.seed = seed;
   c.clip0 = clip0;
   if constexpr (BANK) {
-    const float* co = bv->coef;
-    const int n = bv->n_steps;
+    const float* co = bv.coef;
+    const int n = bv.n_steps;
     if (p.mode == 3) { c.c2 = co[c.k]; c.c1 = co[n + c.k]; c.cn = co[2 * n + c.k]; c.sg = co[3 * n + c.k]; }
     else if (p.mode == 0) { c.c1 = p.c1[c.t]; c.c2 = p.c2[c.t]; c.sg = p.sigma[c.t]; }
     else { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = co[c.k]; c.cn = co[n + c.k]; }
@@ -132,53 +133,42 @@ __device__ __forceinline__ SchedCoef slot_coef(const fdm_sched_args& p, const Sl
   else { c.sra = p.sra[c.t]; c.srm1 = p.srm1[c.t]; c.san = p.sqrt_an[c.k]; c.cn = p.c_n[c.k]; }
   return c;
 }
-// the operand-kind copy of four updated elements at flat element q of x_out_t
-__device__ __forceinline__ void slot_store_t(const fdm_sched_args& p, long long q, f32x4 o) {
-  if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + q, 0, o);
-  else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + q, p.x_out_t_lo_off, o);
-  else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + q, 0, o);
-  else *(f32x4*)((float*)p.x_out_t + q) = o;
-}
 // One plain slot's four elements starting at flat element e (the slot is live): CFG mix, update at the slot's (k, t), stores.
-// BANK: p is the slot's view of the arguments (mode and cfg_scale of its request), bv its range of the bank.
-template <bool BANK = false>
-__device__ __forceinline__ void slot_update_quad(const fdm_sched_args& p, const SlotState& s, const unsigned long long* keys, int clip, long long e,
-                                                 const SlotBankView* bv = nullptr) {
+// BANK: the mode and guidance scale are those of the slot's request (p is a copy: the slot's view of the arguments); a bad row
+// stores nothing.
+template <bool BANK>
+__device__ __forceinline__ void slot_update_quad(fdm_sched_args p, const fdm_slot_bank_args& b, const SlotState& s, const unsigned long long* keys,
+                                                 int clip, long long e) {
+  SlotBankView bv;
+  if constexpr (BANK) {
+    if (!slot_bank_view(p, b, clip, s, bv)) return;
+    p.mode = bv.mode; p.cfg_scale = bv.cfg_scale;
+  }
   // sched_noise4 keys by clip0 + (e / n_per_clip) = the slot's clip id
   const SchedCoef c = slot_coef<BANK>(p, s, keys[2 * clip], (int)keys[2 * clip + 1] - clip, bv);
   f32x4 x0 = *(const f32x4*)(p.x0 + e);
-  if (p.x0u) {
-    const f32x4 u = *(const f32x4*)(p.x0u + e);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x0[j] = __fadd_rn(u[j], __fmul_rn(p.cfg_scale, __fsub_rn(x0[j], u[j])));
-  }
+  if (p.x0u) sched_cfg_mix4(x0, *(const f32x4*)(p.x0u + e), p.cfg_scale);
   const f32x4 x = *(const f32x4*)(p.x + e);
-  const f32x4 o = p.mode == 3 ? sched_update4<true>(p, c, x0, x, e) : sched_update4<false>(p, c, x0, x, e);
+  const f32x4 o = sched_update4_rt(p, c, x0, x, e);
   *(f32x4*)(p.x_out + e) = o;
-  if (p.x_out_t) slot_store_t(p, e, o);
-}
-
-// One plain slot's quad in the bank forms: the slot's view of the arguments (mode and guidance scale of its request), then the update
-__device__ __forceinline__ void slot_bank_quad(const fdm_sched_args& p, const fdm_slot_bank_args& b, const SlotState& s, const unsigned long long* keys,
-                                               int clip, long long e) {
-  SlotBankView bv;
-  if (!slot_bank_view(p, b, clip, s, bv)) return;
-  fdm_sched_args pv = p;
-  pv.mode = bv.mode; pv.cfg_scale = bv.cfg_scale;
-  slot_update_quad<true>(pv, s, keys, clip, e, &bv);
+  sched_store_t4(p, e, o);
 }
 
 // The scheduler pass of the slot program.  p: x0 (+ x0u, cfg_scale), x, x_out, x_out_t, n = n_slots * n_per_clip, mode 0 / 1 / 3 with
 // its tables and x0_hist; p.step / tseq / seed / clip0 / seed_dev / arrive / noise are not read.  A slot that is not live is
 // skipped whole: nothing of it is stored.
-__global__ __launch_bounds__(256) void slot_sched_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys) {
+// BANK (fdm_op_slot_sched_bank): p.mode and p.cfg_scale are not read, every live slot takes them from its request row; p carries the
+// t-indexed tables of every mode the bank may hold.  Without BANK, b is not read.
+template <bool BANK>
+__global__ __launch_bounds__(256) void slot_sched_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys,
+                                                         const fdm_slot_bank_args b) {
   const long long nq = p.n / 4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
     const long long e = 4 * i;
     const int clip = (int)(e / p.n_per_clip);
     const SlotState s = st[clip];
     if (!s.live) continue;
-    slot_update_quad(p, s, keys, clip, e);
+    slot_update_quad<BANK>(p, b, s, keys, clip, e);
   }
 }
 
@@ -193,8 +183,10 @@ __global__ __launch_bounds__(256) void slot_sched_kernel(const fdm_sched_args p,
 //                 the result goes to the arena and to every window row holding the frame (p.x_out + operand copy).
 //                 g.init: no update -- the arena (x_T) is copied into the window rows, whatever the leader's word says.
 // Every table row is checked against the sizes in g before it is used as an index; a row outside them stores nothing.
+// BANK (fdm_op_slot_group_sched_bank): the same walk, a plain slot reading its own request row and a group its LEADER's.
+template <bool BANK>
 __global__ __launch_bounds__(256) void slot_group_sched_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys,
-                                                               const fdm_slot_group_args g, int n_slots) {
+                                                               const fdm_slot_group_args g, int n_slots, const fdm_slot_bank_args b) {
   const long long nq_plain = g.plain ? p.n / 4 : 0;
   const long long nq = nq_plain + (long long)(g.frame1 - g.frame0) * g.d / 4;
   const LongFrame* frames = (const LongFrame*)g.frames;
@@ -206,7 +198,7 @@ __global__ __launch_bounds__(256) void slot_group_sched_kernel(const fdm_sched_a
       const int clip = (int)(e / p.n_per_clip);
       const SlotState s = st[clip];
       if (!s.live || g.member[clip] >= 0) continue;
-      slot_update_quad(p, s, keys, clip, e);
+      slot_update_quad<BANK>(p, b, s, keys, clip, e);
       continue;
     }
     const long long ea = (long long)g.frame0 * g.d + 4 * (i - nq_plain);      // element of the arena
@@ -218,92 +210,19 @@ __global__ __launch_bounds__(256) void slot_group_sched_kernel(const fdm_sched_a
     if (gr.leader < 0 || gr.leader >= n_slots || fl < 0 || fl >= gr.L_total) continue;
     const SlotState s = st[gr.leader];
     if (!g.init && !s.live) continue;
-    f32x4 o;
-    if (g.init) {
-      o = *(const f32x4*)(g.x_long + ea);
-    } else {
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j = fr.e0; j < fr.e1; ++j) {
-        const LongEnt en = ents[j];
-        const int r = fl - en.start;
-        if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
-        const long long q = ((long long)en.slot * g.L + r) * g.d + col;
-        f32x4 x0 = *(const f32x4*)(p.x0 + q);
-        if (p.x0u) {      // CFG mix per window, before the blend (window_sched_kernel's expression)
-          const f32x4 u = *(const f32x4*)(p.x0u + q);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) x0[k] = __fadd_rn(u[k], __fmul_rn(p.cfg_scale, __fsub_rn(x0[k], u[k])));
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = j == fr.e0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
-      }
-      // the group's view of the arguments: one clip of L_total frames whose history starts at its first arena frame; the element
-      // index inside the long clip keys the noise (clip0 = the group's clip id) and indexes the history
-      fdm_sched_args pl = p;
-      pl.n_per_clip = (long long)gr.L_total * g.d;
-      pl.x0_hist = g.hist_long ? g.hist_long + (long long)gr.first * g.d : nullptr;
-      pl.noise = nullptr;
-      const SchedCoef c = slot_coef(p, s, keys[2 * gr.leader], (int)keys[2 * gr.leader + 1]);
-      const long long el = (long long)fl * g.d + col;
-      const f32x4 x = *(const f32x4*)(g.x_long + ea);
-      o = p.mode == 3 ? sched_update4<true>(pl, c, acc, x, el) : sched_update4<false>(pl, c, acc, x, el);
-      *(f32x4*)(g.x_long + ea) = o;
-    }
-    for (int j = fr.e0; j < fr.e1; ++j) {
-      const LongEnt en = ents[j];
-      const int r = fl - en.start;
-      if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
-      const long long q = ((long long)en.slot * g.L + r) * g.d + col;
-      *(f32x4*)(p.x_out + q) = o;
-      if (p.x_out_t) slot_store_t(p, q, o);
-    }
-  }
-}
-
-// The bank forms of the two passes (fdm_op_slot_sched_bank / fdm_op_slot_group_sched_bank): p.mode and p.cfg_scale are not read, every
-// live slot (group) takes them from its (leader's) request row; p carries the t-indexed tables of every mode the bank may hold.
-__global__ __launch_bounds__(256) void slot_sched_bank_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys,
-                                                              const fdm_slot_bank_args b) {
-  const long long nq = p.n / 4;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
-    const long long e = 4 * i;
-    const int clip = (int)(e / p.n_per_clip);
-    const SlotState s = st[clip];
-    if (!s.live) continue;
-    slot_bank_quad(p, b, s, keys, clip, e);
-  }
-}
-
-// slot_group_sched_kernel with a bank: the same walk, a plain slot reading its own request row and a group its LEADER's.
-__global__ __launch_bounds__(256) void slot_group_sched_bank_kernel(const fdm_sched_args p, const SlotState* st, const unsigned long long* keys,
-                                                                    const fdm_slot_group_args g, int n_slots, const fdm_slot_bank_args b) {
-  const long long nq_plain = g.plain ? p.n / 4 : 0;
-  const long long nq = nq_plain + (long long)(g.frame1 - g.frame0) * g.d / 4;
-  const LongFrame* frames = (const LongFrame*)g.frames;
-  const LongEnt* ents = (const LongEnt*)g.entries;
-  const LongGroup* groups = (const LongGroup*)g.groups;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
-    if (i < nq_plain) {
-      const long long e = 4 * i;
-      const int clip = (int)(e / p.n_per_clip);
-      const SlotState s = st[clip];
-      if (!s.live || g.member[clip] >= 0) continue;
-      slot_bank_quad(p, b, s, keys, clip, e);
-      continue;
-    }
-    const long long ea = (long long)g.frame0 * g.d + 4 * (i - nq_plain);      // element of the arena
-    const int f = (int)(ea / g.d), col = (int)(ea - (long long)f * g.d);
-    const LongFrame fr = frames[f];
-    if (fr.group < 0 || fr.group >= g.n_groups || fr.e0 < 0 || fr.e1 > g.n_entries) continue;
-    const LongGroup gr = groups[fr.group];
-    const int fl = f - gr.first;                                              // frame inside the long clip
-    if (gr.leader < 0 || gr.leader >= n_slots || fl < 0 || fl >= gr.L_total) continue;
-    const SlotState s = st[gr.leader];
-    if (!g.init && !s.live) continue;
-    // the group's sampler and guidance scale are its leader's request; a bad row stores nothing
+    // the group's view of the arguments: one clip of L_total frames whose history starts at its first arena frame; the element
+    // index inside the long clip keys the noise (clip0 = the group's clip id) and indexes the history
+    fdm_sched_args pl = p;
+    pl.n_per_clip = (long long)gr.L_total * g.d;
+    pl.x0_hist = g.hist_long ? g.hist_long + (long long)gr.first * g.d : nullptr;
+    pl.noise = nullptr;
     SlotBankView bv;
-    bv.mode = 0; bv.cfg_scale = 0.f; bv.coef = nullptr; bv.n_steps = 0;
-    if (!g.init && (!slot_bank_view(p, b, gr.leader, s, bv) || (bv.mode == 3 && !g.hist_long))) continue;
+    if constexpr (BANK) {
+      // ... with the sampler and guidance scale of its leader's request; a bad row stores nothing
+      bv.mode = 0; bv.cfg_scale = 0.f; bv.coef = nullptr; bv.n_steps = 0;
+      if (!g.init && (!slot_bank_view(p, b, gr.leader, s, bv) || (bv.mode == 3 && !g.hist_long))) continue;
+      pl.mode = bv.mode; pl.cfg_scale = bv.cfg_scale;
+    }
     f32x4 o;
     if (g.init) {
       o = *(const f32x4*)(g.x_long + ea);
@@ -315,25 +234,13 @@ __global__ __launch_bounds__(256) void slot_group_sched_bank_kernel(const fdm_sc
         if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
         const long long q = ((long long)en.slot * g.L + r) * g.d + col;
         f32x4 x0 = *(const f32x4*)(p.x0 + q);
-        if (p.x0u) {      // CFG mix per window, before the blend (window_sched_kernel's expression)
-          const f32x4 u = *(const f32x4*)(p.x0u + q);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) x0[k] = __fadd_rn(u[k], __fmul_rn(bv.cfg_scale, __fsub_rn(x0[k], u[k])));
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = j == fr.e0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
+        if (p.x0u) sched_cfg_mix4(x0, *(const f32x4*)(p.x0u + q), pl.cfg_scale);      // per window, before the blend
+        sched_blend4(acc, j == fr.e0, en.wt, x0);
       }
-      // the group's view of the arguments: one clip of L_total frames whose history starts at its first arena frame; the element
-      // index inside the long clip keys the noise (clip0 = the group's clip id) and indexes the history
-      fdm_sched_args pl = p;
-      pl.n_per_clip = (long long)gr.L_total * g.d;
-      pl.x0_hist = g.hist_long ? g.hist_long + (long long)gr.first * g.d : nullptr;
-      pl.noise = nullptr;
-      pl.mode = bv.mode;
-      const SchedCoef c = slot_coef<true>(pl, s, keys[2 * gr.leader], (int)keys[2 * gr.leader + 1], &bv);
+      const SchedCoef c = slot_coef<BANK>(pl, s, keys[2 * gr.leader], (int)keys[2 * gr.leader + 1], bv);
       const long long el = (long long)fl * g.d + col;
       const f32x4 x = *(const f32x4*)(g.x_long + ea);
-      o = bv.mode == 3 ? sched_update4<true>(pl, c, acc, x, el) : sched_update4<false>(pl, c, acc, x, el);
+      o = sched_update4_rt(pl, c, acc, x, el);
       *(f32x4*)(g.x_long + ea) = o;
     }
     for (int j = fr.e0; j < fr.e1; ++j) {
@@ -342,48 +249,26 @@ __global__ __launch_bounds__(256) void slot_group_sched_bank_kernel(const fdm_sc
       if (en.slot < 0 || en.slot >= n_slots || r < 0 || r >= g.L) continue;
       const long long q = ((long long)en.slot * g.L + r) * g.d + col;
       *(f32x4*)(p.x_out + q) = o;
-      if (p.x_out_t) slot_store_t(p, q, o);
+      sched_store_t4(p, q, o);
     }
   }
 }
 
-
-static hipError_t slot_sched_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, hipStream_t s) {
-  const long long nq = a.n / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(slot_sched_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys);
+// b = the bank of the bank forms, null for the forms without one (their kernels get an empty struct that they do not read)
+static hipError_t slot_sched_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, const fdm_slot_bank_args* b, hipStream_t s) {
+  const dim3 grid(grid_for(a.n / 4));
+  if (b) hipLaunchKernelGGL(slot_sched_kernel<true>, grid, dim3(256), 0, s, a, (const SlotState*)state, keys, *b);
+  else hipLaunchKernelGGL(slot_sched_kernel<false>, grid, dim3(256), 0, s, a, (const SlotState*)state, keys, fdm_slot_bank_args{});
   return hipGetLastError();
 }
 
 static hipError_t slot_group_sched_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, const fdm_slot_group_args& g,
-                                          int n_slots, hipStream_t s) {
-  const long long nq = (g.plain ? a.n / 4 : 0) + (long long)(g.frame1 - g.frame0) * g.d / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(slot_group_sched_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys, g, n_slots);
-  return hipGetLastError();
-}
-
-static hipError_t slot_sched_bank_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, const fdm_slot_bank_args& b, hipStream_t s) {
-  const long long nq = a.n / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(slot_sched_bank_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys, b);
-  return hipGetLastError();
-}
-
-static hipError_t slot_group_sched_bank_launch(const fdm_sched_args& a, const int* state, const unsigned long long* keys, const fdm_slot_group_args& g,
-                                               int n_slots, const fdm_slot_bank_args& b, hipStream_t s) {
-  const long long nq = (g.plain ? a.n / 4 : 0) + (long long)(g.frame1 - g.frame0) * g.d / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(slot_group_sched_bank_kernel, dim3(blocks), dim3(256), 0, s, a, (const SlotState*)state, keys, g, n_slots, b);
+                                          int n_slots, const fdm_slot_bank_args* b, hipStream_t s) {
+  const dim3 grid(grid_for((g.plain ? a.n / 4 : 0) + (long long)(g.frame1 - g.frame0) * g.d / 4));
+  if (b) hipLaunchKernelGGL(slot_group_sched_kernel<true>, grid, dim3(256), 0, s, a, (const SlotState*)state, keys, g, n_slots, *b);
+  else hipLaunchKernelGGL(slot_group_sched_kernel<false>, grid, dim3(256), 0, s, a, (const SlotState*)state, keys, g, n_slots, fdm_slot_bank_args{});
   return hipGetLastError();
 }
 
 }  // namespace fdm
+

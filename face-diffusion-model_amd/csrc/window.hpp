@@ -1,12 +1,16 @@
 // Windowed sampling of clips longer than the denoiser's max_len (fdm_audio_prepare_windows / fdm_sample_windows): one pass over
 // the LONG layout [B, L_total * d] per diffusion step that blends the overlapping windows' x0 predictions, applies the scheduler
-// update once per long-clip element (sched_update4: the same bits and the same Philox stream as sched_kernel) and writes the
-// result back to the long buffer and to every window row that holds the frame (fp32 x + the operand-kind copy of the next step).
+// update once per long-clip element (the same bits and the same Philox stream as sched_kernel) and writes the result back to the
+// long buffer and to every window row that holds the frame (fp32 x + the operand-kind copy of the next step).
+// The walk over the off[] CSR and WinEnt rows is this kernel's own (its host builder is trusted: no bounds checks); the per-term
+// arithmetic -- guidance mix, blend term, update, operand copy -- is sched.hpp's, shared with slot_group_sched_kernel (slots.hpp),
+// which walks the group tables of a long request in slots and must produce this kernel's bits.
 #pragma once
 #include "common.hpp"
 #include "sched.hpp"
 #include "../../include/fdm_hip.h"
 #include "kernels.hpp"
+#include "host.hpp"      // grid_for: the 1-D launch grid of the pass
 
 namespace fdm {
 
@@ -33,38 +37,24 @@ __global__ __launch_bounds__(256) void window_sched_kernel(const fdm_sched_args 
         const WinEnt en = w.ent[j];
         const long long q = base + (long long)en.w * wrows - (long long)en.start * w.d;
         f32x4 x0 = *(const f32x4*)(p.x0 + q);
-        if (p.x0u) {      // CFG mix per window, before the blend (utiles/classifierfree.py:20-21; sched_kernel's expression)
-          const f32x4 u = *(const f32x4*)(p.x0u + q);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) x0[k] = __fadd_rn(u[k], __fmul_rn(p.cfg_scale, __fsub_rn(x0[k], u[k])));
-        }
-        // ascending window order, the first term starts the sum (one window: weight 1, x0 passes through bit for bit, -0 included)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = j == j0 ? __fmul_rn(en.wt, x0[k]) : __fadd_rn(acc[k], __fmul_rn(en.wt, x0[k]));
+        if (p.x0u) sched_cfg_mix4(x0, *(const f32x4*)(p.x0u + q), p.cfg_scale);      // per window, before the blend
+        sched_blend4(acc, j == j0, en.wt, x0);
       }
       const f32x4 x = *(const f32x4*)(p.x + e);
-      o = p.mode == 3 ? sched_update4<true>(p, c, acc, x, e) : sched_update4<false>(p, c, acc, x, e);
+      o = sched_update4_rt(p, c, acc, x, e);
       *(f32x4*)(p.x_out + e) = o;
     }
     for (int j = j0; j < j1; ++j) {
       const WinEnt en = w.ent[j];
       const long long q = base + (long long)en.w * wrows - (long long)en.start * w.d;
       *(f32x4*)(w.xw + q) = o;
-      if (p.x_out_t) {
-        if (p.out_dtype == FDM_BF16) store_opnd4<bf16>((bf16*)p.x_out_t + q, 0, o);
-        else if (p.out_dtype == FDM_F16X3) store_opnd4<f16x3_t>((f16*)p.x_out_t + q, p.x_out_t_lo_off, o);
-        else if (p.out_dtype == FDM_F16) store_opnd4<f16>((f16*)p.x_out_t + q, 0, o);
-      }
+      sched_store_t4<false>(p, q, o);      // (never given x_out_t on an fp32 plan)
     }
   }
 }
 
 static hipError_t window_launch(const fdm_sched_args& a, const WinArgs& w, hipStream_t s) {
-  const long long nq = a.n / 4;
-  int blocks = (int)((nq + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(window_sched_kernel, dim3(blocks), dim3(256), 0, s, a, w);
+  hipLaunchKernelGGL(window_sched_kernel, dim3(grid_for(a.n / 4)), dim3(256), 0, s, a, w);
   return hipGetLastError();
 }
 

@@ -111,8 +111,9 @@ def drive(plan, admits, pieces, overlap=10):
 
 
 # 1 ---------------------------------------------------------------------------------------------
-def group_tables(groups, n_slots, F, n_entries):
-    """groups: [(slots, L_total, overlap, first arena frame, first entry)] -> device tables of fdm_slot_group_args (+ the starts)."""
+def group_tables(groups, n_slots, F, n_entries, L=L):
+    """groups: [(slots, L_total, overlap, first arena frame, first entry)] -> device tables of fdm_slot_group_args (+ the starts);
+    L = frames per slot."""
     member = np.full(n_slots, -1, np.int32)
     frames = np.full((F, 4), -1, np.int32)
     ents = np.zeros((n_entries, 4), np.int32)

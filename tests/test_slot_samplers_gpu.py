@@ -203,6 +203,88 @@ def test_op_slot_sched_bank_equals_sched_step_per_live_clip(cfg):
         assert torch.equal(o2[npc:2 * npc], got["f32"][npc:2 * npc]) and not torch.equal(o2[:npc], got["f32"][:npc])
 
 
+@pytest.mark.parametrize("cfg", [False, True])
+@pytest.mark.parametrize("mode", [0, 1, 3])
+def test_op_slot_group_sched_bank_equals_slot_group_sched(mode, cfg):
+    """The two forms of the group pass against each other, byte for byte: fdm_op_slot_group_sched_bank with a bank whose sampler 0
+    holds exactly the tables and the scale given to fdm_op_slot_group_sched.  4 slots x 8 frames, d = 8: slot 0 plain and live,
+    slot 1 idle (NaN rows), slots 3 and 2 -- in that order, the leader is not the lowest slot -- a group of two windows over
+    L_total = 12 with overlap 4, inside a larger arena.  Every slot is at k = 1 of a 3-step sampler: the DDIM offsets are not zero,
+    the DDPM step draws noise (t = 500) and the table-driven step reads its history (c[1] != 0) and draws noise (s[1] != 0).
+    Compared: x_out, the operand copy in every kind, the arena, x0_hist and hist_long, and the rows neither may touch."""
+    from test_slot_long_gpu import bits, group_tables
+    slots, Lw, d, F, NE, first, e0 = 4, 8, 8, 16, 20, 2, 3
+    npc, n = Lw * d, slots * Lw * d
+    PLAIN, IDLE, GROUP, LT = 0, 1, [3, 2], 12
+    (member, frames, ents, gdesc), starts = group_tables([(GROUP, LT, 4, first, e0)], slots, F, NE, L=Lw)
+    assert [list(s) for s in starts] == [[0, 4]]
+    g = torch.Generator().manual_seed(50 + mode)
+    x0, x0u, hist_p, xs0 = [torch.randn(n, generator=g) * 2 for _ in range(4)]
+    xs0[IDLE * npc:(IDLE + 1) * npc] = float("nan")
+    xl0, hl0 = torch.randn(F * d, generator=g) * 2, torch.randn(F * d, generator=g) * 2
+    tseq, san, cn = [999, 500, 0], [0.3, 0.6, 0.9], [0.95, 0.8, 0.43]
+    lm = dict(lm_a=[0.9518, 0.853, 0.7313], lm_b=[0.3067, 0.3352, 0.5269], lm_c=[0.0, -0.013, -0.1491], lm_s=[0.25, 0.125, 0.4338])
+    assert lm["lm_c"][1] != 0.0 and lm["lm_s"][1] != 0.0
+    state = torch.tensor([[1, tseq[1], 1, 1], [0, 0, 0, 0], [1, tseq[1], 1, 1], [1, tseq[1], 1, 1]], dtype=torch.int32)
+    keys = dv(torch.tensor([[99, 5], [77, 1], [1234, 3], [2 ** 40 + 5, 8]], dtype=torch.int64))      # the group's key is its leader's (slot 3)
+    buf = schedule.make_buffers(1000)
+    c1, c2, sg = schedule.ddpm_tables(buf)
+    shared = dict(c1=dv(c1), c2=dv(c2), sigma=dv(sg), sra=dv(buf["sqrt_recip_alphas_cumprod"]), srm1=dv(buf["sqrt_recipm1_alphas_cumprod"]))
+    own = {0: {}, 1: dict(sqrt_an=dv(torch.tensor(san)), c_n=dv(torch.tensor(cn))), 3: {k: dv(torch.tensor(v)) for k, v in lm.items()}}[mode]
+    coef = {0: [], 1: san + cn, 3: lm["lm_a"] + lm["lm_b"] + lm["lm_c"] + lm["lm_s"]}[mode]
+    bank = dict(req=dv(torch.tensor([[0, f32_bits(2.5), 0, 0]] * slots, dtype=torch.int32)),
+                desc=dv(torch.tensor([[mode, 3, 0, 0]], dtype=torch.int32)), t=dv(torch.tensor(tseq, dtype=torch.int32)),
+                coef=dv(torch.tensor(coef, dtype=torch.float32)))
+    SENT = 7.5
+
+    def copy_out(name):
+        if name == "split":      # (plane distance 5 rows larger than n)
+            return ops.Split(torch.full((2, n // d + 5, d), SENT, device=DEV, dtype=torch.float16), F16X3)
+        return torch.full((n,), SENT, device=DEV, dtype={"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[name])
+
+    def planes(t):
+        return [t.planes[0].reshape(-1), t.planes[1].reshape(-1)] if isinstance(t, ops.Split) else [t]
+
+    def run(name, with_bank):
+        xs, xl, hl, hp, ot = dv(xs0.clone()), dv(xl0.clone()), dv(hl0.clone()), dv(hist_p.clone()), copy_out(name)
+        common = dict(member=member, frames=frames, entries=ents, groups=gdesc, x_long=xl, hist_long=hl, L=Lw, d=d, n_per_clip=npc,
+                      x0u=dv(x0u) if cfg else None, x_out_t=ot, x0_hist=hp)
+        if with_bank:
+            ops.slot_group_sched_bank(dv(x0), xs, xs, n, dv(state), keys, slots, **bank, **shared, **common)
+        else:
+            ops.slot_group_sched(mode, dv(x0), xs, xs, n, dv(state), keys, slots, cfg_scale=2.5, **shared, **own, **common)
+        return [xs, xl, hl, hp] + planes(ot)
+
+    def rows(t, s):
+        return t[s * npc:(s + 1) * npc]
+
+    for name in ("f32", "bf16", "f16", "split"):
+        plain, banked = run(name, False), run(name, True)
+        for i, (a, b) in enumerate(zip(plain, banked)):
+            assert torch.equal(bits(a), bits(b)), (name, i)
+        xs, xl, hl, hp, *ot = banked
+        # both did the work: the plain slot, both member slots and the group's arena frames moved ...
+        for s in [PLAIN] + GROUP:
+            assert not torch.equal(rows(xs, s), dv(rows(xs0, s))), (name, s)
+            for t in ot:
+                assert not torch.equal(rows(t, s).float(), torch.full((npc,), SENT, device=DEV)), (name, s)
+        a0, a1 = first * d, (first + LT) * d
+        assert not torch.equal(xl[a0:a1], dv(xl0[a0:a1]))
+        # ... the seam frames hold one value in both member slots (window starts 0 and 4: frames 4..7 of the long clip)
+        assert torch.equal(rows(xs, GROUP[0])[4 * d:], rows(xs, GROUP[1])[:4 * d])
+        assert torch.equal(rows(xs, GROUP[0])[4 * d:], xl[a0 + 4 * d:a0 + 8 * d])
+        # ... and neither touched the idle slot (x keeps its NaN bits, the copy its sentinel), the free arena frames, or a history
+        # that the mode does not write (mode 3: the plain slot's rows of x0_hist and the group's frames of hist_long only)
+        assert torch.equal(bits(rows(xs, IDLE)), bits(dv(rows(xs0, IDLE))))
+        for t in ot:
+            assert torch.equal(rows(t, IDLE).float(), torch.full((npc,), SENT, device=DEV)), name
+        for t, t0 in ((xl, xl0), (hl, hl0)):
+            assert torch.equal(t[:a0], dv(t0[:a0])) and torch.equal(t[a1:], dv(t0[a1:])), name
+        for s in range(slots):
+            assert torch.equal(rows(hp, s), dv(rows(hist_p, s))) == (mode != 3 or s != PLAIN), (name, s)
+        assert torch.equal(hl[a0:a1], dv(hl0[a0:a1])) == (mode != 3), name
+
+
 # 2 ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ALL_MODES)
 def test_mixed_chains_equal_their_solo_chains(dtype):
