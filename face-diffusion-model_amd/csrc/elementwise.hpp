@@ -242,41 +242,31 @@ __global__ void add_rows_kernel(const AddRowsArgs p) {
   }
 }
 
-// out[b, k, :] = in[b, clamp(k - pad), :] (replicate) or 0 outside (zero)
-template <typename T>
-__global__ void pad_rows_kernel(const T* in, T* out, int B, int L, int d, int pad, int zero) {
+// out[b, k, :] = in[b, clamp(k - pad), :] (replicate) or 0 outside (zero).
+// LENS: the replicate form for clips of unequal length inside one padded [B, L, d] batch: clip b is lens[b] frames long, so its end
+// padding -- and every row beyond -- copies ITS last frame, lens[b] - 1; rows of `in` at or beyond lens[b] are never read and
+// `zero` is not read.  Without LENS, lens is not read.
+// (The two padding kernels clamp a clip's length differently, on purpose: here it is floored at 1 -- there is always a frame to
+//  replicate -- while group_pad_kernel takes a length of 0 as it is and writes an all-zero clip.)
+template <typename T, bool LENS>
+__global__ void pad_rows_kernel(const T* in, T* out, int B, int L, int d, int pad, int zero, const int* lens) {
   const long long n = (long long)B * (L + 2 * pad) * d;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int col = (int)(i % d);
     const long long r = i / d;
     const int k = (int)(r % (L + 2 * pad));
     const int b = (int)(r / (L + 2 * pad));
+    int Lb = L;
+    if constexpr (LENS) Lb = min(max(lens[b], 1), L);
     int src = k - pad;
     T v;
-    if (zero && (src < 0 || src >= L)) {
+    if (!LENS && zero && (src < 0 || src >= L)) {
       v = from_f32<T>(0.f);
     } else {
-      src = src < 0 ? 0 : (src >= L ? L - 1 : src);
+      src = src < 0 ? 0 : (src >= Lb ? Lb - 1 : src);
       v = in[((size_t)b * L + src) * d + col];
     }
     out[i] = v;
-  }
-}
-
-// The replicate form for clips of unequal length inside one padded [B, L, d] batch: clip b is lens[b] frames long, so its end
-// padding -- and every row beyond -- copies ITS last frame, lens[b] - 1; rows of `in` at or beyond lens[b] are never read.
-template <typename T>
-__global__ void pad_rows_lens_kernel(const T* in, T* out, int B, int L, int d, int pad, const int* lens) {
-  const long long n = (long long)B * (L + 2 * pad) * d;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int col = (int)(i % d);
-    const long long r = i / d;
-    const int k = (int)(r % (L + 2 * pad));
-    const int b = (int)(r / (L + 2 * pad));
-    const int Lb = min(max(lens[b], 1), L);
-    int src = k - pad;
-    src = src < 0 ? 0 : (src >= Lb ? Lb - 1 : src);
-    out[i] = in[((size_t)b * L + src) * d + col];
   }
 }
 
@@ -290,9 +280,11 @@ __global__ void zero_pad_rows_kernel(float* x, int B, int L, int d, const int* l
   }
 }
 
-// [B, T, d] -> [groups, B, T + 2*pad, d/groups], zero padded in time
-template <typename T>
-__global__ void group_pad_kernel(const T* in, T* out, int B, int Tn, int d, int groups, int pad) {
+// [B, T, d] -> [groups, B, T + 2*pad, d/groups], zero padded in time.
+// LENS: clips of unequal length inside one padded [B, Tn, d] batch: frames at or beyond lens[b] are written as zeros, so a
+// convolution over a clip's last frames sees the zero padding its own launch sees.  Without LENS, lens is not read.
+template <typename T, bool LENS>
+__global__ void group_pad_kernel(const T* in, T* out, int B, int Tn, int d, int groups, int pad, const int* lens) {
   const int dg = d / groups;
   const long long n = (long long)groups * B * (Tn + 2 * pad) * dg;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -303,28 +295,10 @@ __global__ void group_pad_kernel(const T* in, T* out, int B, int Tn, int d, int 
     const int b = (int)(r % B);
     const int gi = (int)(r / B);
     const int src = k - pad;
+    int Tb = Tn;
+    if constexpr (LENS) Tb = min(lens[b], Tn);
     T v = from_f32<T>(0.f);
-    if (src >= 0 && src < Tn) v = in[((size_t)b * Tn + src) * d + gi * dg + col];
-    out[i] = v;
-  }
-}
-
-// The same for clips of unequal length inside one padded [B, Tn, d] batch: frames at or beyond lens[b] are written as zeros, so a
-// convolution over a clip's last frames sees the zero padding its own launch sees
-template <typename T>
-__global__ void group_pad_lens_kernel(const T* in, T* out, int B, int Tn, int d, int groups, int pad, const int* lens) {
-  const int dg = d / groups;
-  const long long n = (long long)groups * B * (Tn + 2 * pad) * dg;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int col = (int)(i % dg);
-    long long r = i / dg;
-    const int k = (int)(r % (Tn + 2 * pad));
-    r /= (Tn + 2 * pad);
-    const int b = (int)(r % B);
-    const int gi = (int)(r / B);
-    const int src = k - pad;
-    T v = from_f32<T>(0.f);
-    if (src >= 0 && src < min(lens[b], Tn)) v = in[((size_t)b * Tn + src) * d + gi * dg + col];
+    if (src >= 0 && src < Tb) v = in[((size_t)b * Tn + src) * d + gi * dg + col];
     out[i] = v;
   }
 }
@@ -505,112 +479,94 @@ __global__ __launch_bounds__(256) void conv0_ln_gelu_kernel(const float* wav, co
   }
 }
 
-// LeakyReLU(0.2) then InstanceNorm1d (biased variance, no affine) over L per (clip, channel).  Workgroup = 16 time-lanes x 64
-// channels (coalesced across channels): the time-lanes stride over l and combine through LDS in a fixed order; three passes
-// (mean, centred variance, normalise) as the reference's two-pass statistics.  (Round 4: the first form ran one thread per
-// channel over all of L -- 16 workgroups of 1500 dependent strided loads each, 261 us at 4 x 498 frames, 8 % of a VQ decode.)
-template <typename T>
-__global__ __launch_bounds__(1024) void leaky_instnorm_kernel(const float* x, float* y_f32, T* y_t, int L, int d, float eps) {
-  __shared__ float red[16][64];
-  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
-  const bool ok = ch < d;
-  const float* xp = x + (size_t)b * L * d + (ok ? ch : 0);
+// The statistics of the two per-(clip, channel) time norms below: mean and 1 / sqrt(biased variance + eps) of pre(x) over the n
+// frames of one column, in a workgroup of 16 time-lanes x 64 channels (coalesced across channels).  Lane tl sums frames tl, tl + 16,
+// ...; the 16 partials go through red and are added in index order; the centred squares fold the same way (two passes, as the
+// reference's statistics).  Every thread of the workgroup calls it (three barriers); a lane that is not ok adds nothing.  The bits
+// depend on the column and n alone: the ragged forms call it with n = the clip's own length, which is what gives a clip of a ragged
+// batch the bits of its solo launch.
+struct MeanRstd { float mean, rstd; };
+template <typename PRE>
+__device__ __forceinline__ MeanRstd time_mean_rstd(const float* xp, int stride, int n, int tl, int cl, bool ok, float (&red)[16][64],
+                                                   float eps, PRE pre) {
   float s = 0.f;
-  if (ok) for (int l = tl; l < L; l += 16) s += act_apply(xp[(size_t)l * d], ACT_LEAKY02);
+  if (ok) for (int t = tl; t < n; t += 16) s += pre(xp[(size_t)t * stride]);
   red[tl][cl] = s;
   __syncthreads();
   float mean = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) mean += red[i][cl];
-  mean /= L;
+  mean /= n;
   __syncthreads();
   float q = 0.f;
-  if (ok) for (int l = tl; l < L; l += 16) { const float c = act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean; q += c * c; }
+  if (ok) for (int t = tl; t < n; t += 16) { const float c = pre(xp[(size_t)t * stride]) - mean; q += c * c; }
   red[tl][cl] = q;
   __syncthreads();
   float var = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) var += red[i][cl];
-  const float rstd = 1.f / sqrtf(var / L + eps);
+  return {mean, 1.f / sqrtf(var / n + eps)};
+}
+
+// LeakyReLU(0.2) then InstanceNorm1d (biased variance, no affine) over L per (clip, channel): statistics (time_mean_rstd), then a
+// third pass that normalises.  (Round 4: the first form ran one thread per channel over all of L -- 16 workgroups of 1500 dependent
+// strided loads each, 261 us at 4 x 498 frames, 8 % of a VQ decode.)
+// LENS: clips of unequal length inside one padded [B, L, d] batch: clip b's statistics run over its first Lb = lens[b] frames; frames
+// at or beyond Lb are written as zeros.  Without LENS, lens is not read.
+template <typename T, bool LENS>
+__global__ __launch_bounds__(1024) void leaky_instnorm_kernel(const float* x, float* y_f32, T* y_t, int L, int d, float eps, const int* lens) {
+  __shared__ float red[16][64];
+  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
+  const bool ok = ch < d;
+  int Lb = L;
+  if constexpr (LENS) Lb = min(max(lens[b], 1), L);
+  const float* xp = x + (size_t)b * L * d + (ok ? ch : 0);
+  const auto leaky = [](float v) { return act_apply(v, ACT_LEAKY02); };
+  const MeanRstd st = time_mean_rstd(xp, d, Lb, tl, cl, ok, red, eps, leaky);
   if (!ok) return;
   for (int l = tl; l < L; l += 16) {
-    const float v = (act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean) * rstd;
+    const float v = (!LENS || l < Lb) ? (leaky(xp[(size_t)l * d]) - st.mean) * st.rstd : 0.f;
     const size_t o = ((size_t)b * L + l) * d + ch;
     if (y_f32) y_f32[o] = v;
     if (y_t) y_t[o] = from_f32<T>(v);
   }
 }
 
-// The same over clips of unequal length inside one padded [B, L, d] batch: clip b's statistics run over its first Lb = lens[b]
-// frames with the time-lanes striding and folding exactly as the kernel above does for L = Lb (the bits of the clip's own
-// launch); frames at or beyond Lb are written as zeros.
-template <typename T>
-__global__ __launch_bounds__(1024) void leaky_instnorm_lens_kernel(const float* x, float* y_f32, T* y_t, int L, int d, float eps, const int* lens) {
-  __shared__ float red[16][64];
-  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
-  const bool ok = ch < d;
-  const int Lb = min(max(lens[b], 1), L);
-  const float* xp = x + (size_t)b * L * d + (ok ? ch : 0);
-  float s = 0.f;
-  if (ok) for (int l = tl; l < Lb; l += 16) s += act_apply(xp[(size_t)l * d], ACT_LEAKY02);
-  red[tl][cl] = s;
-  __syncthreads();
-  float mean = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mean += red[i][cl];
-  mean /= Lb;
-  __syncthreads();
-  float q = 0.f;
-  if (ok) for (int l = tl; l < Lb; l += 16) { const float c = act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean; q += c * c; }
-  red[tl][cl] = q;
-  __syncthreads();
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) var += red[i][cl];
-  const float rstd = 1.f / sqrtf(var / Lb + eps);
-  if (!ok) return;
-  for (int l = tl; l < L; l += 16) {
-    const float v = l < Lb ? (act_apply(xp[(size_t)l * d], ACT_LEAKY02) - mean) * rstd : 0.f;
-    const size_t o = ((size_t)b * L + l) * d + ch;
-    if (y_f32) y_f32[o] = v;
-    if (y_t) y_t[o] = from_f32<T>(v);
-  }
+// The time-chunk rule of the group norm below, written once for the launcher and the kernels: clips of TIME_CHUNKED_FROM frames or
+// more are normalised over min(64, ceil(T / 1024)) chunks (return) of one width, T's share rounded up to 16 frames.
+constexpr int TIME_CHUNKED_FROM = 4096;
+__host__ __device__ inline int time_chunks_of(int T, int* chunk) {
+  const int n = (T + 1023) / 1024, nch = n < 64 ? n : 64;
+  *chunk = ((T + nch - 1) / nch + 15) / 16 * 16;
+  return nch;
 }
 
-// GroupNorm(num_groups = C) of wav2vec2's first conv layer: per (clip, channel) statistics over time
-// (biased variance), affine, then activation.  Workgroup = 16 time-lanes x 64 channels; the time-lanes
-// stride over t and combine through LDS; three passes (mean, centred variance, normalise).
-template <typename T>
+// GroupNorm(num_groups = C) of wav2vec2's first conv layer: per (clip, channel) statistics over time (biased variance, time_mean_rstd),
+// then affine and activation in a third pass.
+// LENS: clips of unequal length inside one padded [B, Tn, C] batch (lens[b] frames each).  A clip takes the form its own launch takes
+// -- this kernel below TIME_CHUNKED_FROM frames, the fp64 chunk pair from there on, with the chunk count and width computed from ITS
+// length -- so its statistics fold in the solo order; all three kernels are launched, and a workgroup whose clip belongs to the other
+// form leaves at once.  Frames at or beyond lens[b] are written as zeros.  Without LENS, lens is not read.
+template <typename T, bool LENS>
 __global__ __launch_bounds__(1024) void time_groupnorm_kernel(const float* x, const float* gamma, const float* beta, float* y_f32,
-                                                              typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act) {
+                                                              typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
   __shared__ float red[16][64];
   const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
   const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
+  int Tb = Tn;
+  if constexpr (LENS) {
+    Tb = min(max(lens[b], 1), Tn);
+    if (Tb >= TIME_CHUNKED_FROM) return;       // (uniform over the workgroup, before any barrier) the chunk pair's clip
+  }
   const bool ok = ch < C;
   const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
-  float s = 0.f;
-  if (ok) for (int t = tl; t < Tn; t += 16) s += xp[(size_t)t * C];
-  red[tl][cl] = s;
-  __syncthreads();
-  float mean = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mean += red[i][cl];
-  mean /= Tn;
-  __syncthreads();
-  float q = 0.f;
-  if (ok) for (int t = tl; t < Tn; t += 16) { const float c = xp[(size_t)t * C] - mean; q += c * c; }
-  red[tl][cl] = q;
-  __syncthreads();
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) var += red[i][cl];
-  const float rstd = 1.f / sqrtf(var / Tn + eps);
+  const MeanRstd st = time_mean_rstd(xp, C, Tb, tl, cl, ok, red, eps, [](float v) { return v; });
   if (!ok) return;
   const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
   for (int t = tl; t < Tn; t += 16) {
-    const float v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
+    float v = 0.f;
+    if (!LENS || t < Tb) v = act_apply_t<T>((xp[(size_t)t * C] - st.mean) * st.rstd * gm + bt, act);
     const size_t o = ((size_t)b * Tn + t) * C + ch;
     if (y_f32) y_f32[o] = v;
     if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
@@ -623,108 +579,22 @@ __global__ __launch_bounds__(1024) void time_groupnorm_kernel(const float* x, co
 //                            enough in fp64: the variance is formed as q / T - mean^2 in double), time-lanes combined in a fixed order
 //   time_norm_apply_kernel   grid (C / 64, chunks, B): every workgroup folds the chunk partials of its 64 channels in chunk order
 //                            (so the statistics do not depend on which workgroup reads them), then normalises its own chunk
-__global__ __launch_bounds__(1024) void time_stats_kernel(const float* x, double* part, int Tn, int C, int chunk) {
-  __shared__ double rs[16][64], rq[16][64];
-  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-  const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nch = gridDim.y;
-  const bool ok = ch < C;
-  const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
-  const int t1 = min(Tn, (c + 1) * chunk);
-  double s = 0.0, q = 0.0;
-  if (ok) for (int t = c * chunk + tl; t < t1; t += 16) { const double v = (double)xp[(size_t)t * C]; s += v; q += v * v; }
-  rs[tl][cl] = s; rq[tl][cl] = q;
-  __syncthreads();
-  if (tl == 0 && ok) {
-    double ss = 0.0, qq = 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { ss += rs[i][cl]; qq += rq[i][cl]; }
-    double* o = part + (((size_t)b * nch + c) * C + ch) * 2;
-    o[0] = ss; o[1] = qq;
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(1024) void time_norm_apply_kernel(const float* x, const double* part, const float* gamma, const float* beta,
-                                                               float* y_f32, typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, int chunk, float eps, int act) {
-  __shared__ float st[64][2];
-  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-  const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nch = gridDim.y;
-  const bool ok = ch < C;
-  if (tl == 0) {
-    double ss = 0.0, qq = 0.0;
-    if (ok) for (int i = 0; i < nch; ++i) { const double* o = part + (((size_t)b * nch + i) * C + ch) * 2; ss += o[0]; qq += o[1]; }
-    const double mean = ss / Tn, var = fmax(qq / Tn - mean * mean, 0.0);
-    st[cl][0] = (float)mean; st[cl][1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-  __syncthreads();
-  if (!ok) return;
-  const float mean = st[cl][0], rstd = st[cl][1];
-  const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
-  const float* xp = x + (size_t)b * Tn * C + ch;
-  const int t1 = min(Tn, (c + 1) * chunk);
-  for (int t = c * chunk + tl; t < t1; t += 16) {
-    const float v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
-    const size_t o = ((size_t)b * Tn + t) * C + ch;
-    if (y_f32) y_f32[o] = v;
-    if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
-  }
-}
-
-// The three kernels above for clips of unequal length inside one padded [B, Tn, C] batch (lens[b] frames each).  A clip takes the
-// form its own launch takes -- the three-pass kernel below 4096 frames, the fp64 chunk pair from there on, with the chunk count and
-// width computed from ITS length -- so its statistics fold in the solo order; all three kernels are launched, and a workgroup whose
-// clip belongs to the other form leaves at once.  Frames at or beyond lens[b] are written as zeros.
-__device__ __forceinline__ int time_chunks_of(int Tb, int* chunk) {
-  const int nch = min(64, (Tb + 1023) / 1024);
-  *chunk = ((Tb + nch - 1) / nch + 15) / 16 * 16;
-  return nch;
-}
-template <typename T>
-__global__ __launch_bounds__(1024) void time_groupnorm_lens_kernel(const float* x, const float* gamma, const float* beta, float* y_f32,
-                                                                   typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
-  __shared__ float red[16][64];
-  const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-  const int ch = blockIdx.x * 64 + cl, b = blockIdx.y;
-  const int Tb = min(max(lens[b], 1), Tn);
-  if (Tb >= 4096) return;       // (uniform over the workgroup) the chunk pair's clip
-  const bool ok = ch < C;
-  const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
-  float s = 0.f;
-  if (ok) for (int t = tl; t < Tb; t += 16) s += xp[(size_t)t * C];
-  red[tl][cl] = s;
-  __syncthreads();
-  float mean = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mean += red[i][cl];
-  mean /= Tb;
-  __syncthreads();
-  float q = 0.f;
-  if (ok) for (int t = tl; t < Tb; t += 16) { const float c = xp[(size_t)t * C] - mean; q += c * c; }
-  red[tl][cl] = q;
-  __syncthreads();
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) var += red[i][cl];
-  const float rstd = 1.f / sqrtf(var / Tb + eps);
-  if (!ok) return;
-  const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
-  for (int t = tl; t < Tn; t += 16) {
-    float v = 0.f;
-    if (t < Tb) v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
-    const size_t o = ((size_t)b * Tn + t) * C + ch;
-    if (y_f32) y_f32[o] = v;
-    if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
-  }
-}
-// (part: [B, gridDim.y, C, 2] doubles; a clip uses its first time_chunks_of(lens[b]) chunk slots)
-__global__ __launch_bounds__(1024) void time_stats_lens_kernel(const float* x, double* part, int Tn, int C, const int* lens) {
+// part: [B, gridDim.y, C, 2] doubles.  Without LENS the grid has time_chunks_of(Tn) chunks and lens is not read.  LENS: the grid has
+// the chunks of the padded length, a clip uses its first time_chunks_of(lens[b]) chunk slots, and its pad frames' zero stores are
+// shared out among all of its workgroups.
+template <bool LENS>
+__global__ __launch_bounds__(1024) void time_stats_kernel(const float* x, double* part, int Tn, int C, const int* lens) {
   __shared__ double rs[16][64], rq[16][64];
   const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
   const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nmax = gridDim.y;
-  const int Tb = min(max(lens[b], 1), Tn);
-  if (Tb < 4096) return;
+  int Tb = Tn;
+  if constexpr (LENS) {
+    Tb = min(max(lens[b], 1), Tn);
+    if (Tb < TIME_CHUNKED_FROM) return;
+  }
   int chunk;
   const int nch = time_chunks_of(Tb, &chunk);
-  if (c >= nch) return;
+  if (LENS && c >= nch) return;
   const bool ok = ch < C;
   const float* xp = x + (size_t)b * Tn * C + (ok ? ch : 0);
   const int t1 = min(Tb, (c + 1) * chunk);
@@ -740,14 +610,17 @@ __global__ __launch_bounds__(1024) void time_stats_lens_kernel(const float* x, d
     o[0] = ss; o[1] = qq;
   }
 }
-template <typename T>
-__global__ __launch_bounds__(1024) void time_norm_apply_lens_kernel(const float* x, const double* part, const float* gamma, const float* beta,
-                                                                    float* y_f32, typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
+template <typename T, bool LENS>
+__global__ __launch_bounds__(1024) void time_norm_apply_kernel(const float* x, const double* part, const float* gamma, const float* beta,
+                                                               float* y_f32, typename Opnd<T>::E* y_t, long long lo_off, int Tn, int C, float eps, int act, const int* lens) {
   __shared__ float st[64][2];
   const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
   const int ch = blockIdx.x * 64 + cl, c = blockIdx.y, b = blockIdx.z, nmax = gridDim.y;
-  const int Tb = min(max(lens[b], 1), Tn);
-  if (Tb < 4096) return;
+  int Tb = Tn;
+  if constexpr (LENS) {
+    Tb = min(max(lens[b], 1), Tn);
+    if (Tb < TIME_CHUNKED_FROM) return;
+  }
   int chunk;
   const int nch = time_chunks_of(Tb, &chunk);
   const bool ok = ch < C;
@@ -762,7 +635,7 @@ __global__ __launch_bounds__(1024) void time_norm_apply_lens_kernel(const float*
   const float mean = st[cl][0], rstd = st[cl][1];
   const float gm = gamma ? gamma[ch] : 1.f, bt = beta ? beta[ch] : 0.f;
   const float* xp = x + (size_t)b * Tn * C + ch;
-  if (c < nch) {
+  if (!LENS || c < nch) {
     const int t1 = min(Tb, (c + 1) * chunk);
     for (int t = c * chunk + tl; t < t1; t += 16) {
       const float v = act_apply_t<T>((xp[(size_t)t * C] - mean) * rstd * gm + bt, act);
@@ -771,10 +644,12 @@ __global__ __launch_bounds__(1024) void time_norm_apply_lens_kernel(const float*
       if (y_t) store_opnd1<T>(y_t + o, lo_off, v);
     }
   }
-  for (int t = Tb + c * 16 + tl; t < Tn; t += nmax * 16) {       // the clip's pad frames, shared out among its workgroups
-    const size_t o = ((size_t)b * Tn + t) * C + ch;
-    if (y_f32) y_f32[o] = 0.f;
-    if (y_t) store_opnd1<T>(y_t + o, lo_off, 0.f);
+  if constexpr (LENS) {
+    for (int t = Tb + c * 16 + tl; t < Tn; t += nmax * 16) {       // the clip's pad frames, shared out among its workgroups
+      const size_t o = ((size_t)b * Tn + t) * C + ch;
+      if (y_f32) y_f32[o] = 0.f;
+      if (y_t) store_opnd1<T>(y_t + o, lo_off, 0.f);
+    }
   }
 }
 

@@ -59,6 +59,22 @@ int submit(Op op, void* stream, const char* what) {
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// The kernel type behind a dtype code, handed to a generic lambda as a value (`using T = decltype(tag)`).
+// with_move_type: a pure move -- every 2-byte kind (one plane of a split operand included: the caller passes each plane) moves as
+// bf16 bit patterns, FDM_F32 as float.
+template <typename F>
+void with_move_type(int dtype, F&& f) {
+  if (kind(dtype).bytes == 2) f(fdm::bf16{});
+  else f(float{});
+}
+// with_out_kind: the operand copy y_t of a time norm -- f(tag, lo_off) with bf16, f16x3_t (the only kind that has a lo plane) or float
+template <typename F>
+void with_out_kind(int dtype, long long lo_off, F&& f) {
+  if (dtype == FDM_BF16) f(fdm::bf16{}, 0LL);
+  else if (dtype == FDM_F16X3) f(fdm::f16x3_t{}, lo_off);
+  else f(float{}, 0LL);
+}
+
 }  // namespace
 
 extern "C" {
@@ -452,28 +468,27 @@ int fdm_op_cond_rows(const float* pe, const float* style, const float* emo, cons
   }, stream, "cond_rows");
 }
 
-int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream) {
-  if (!in || !out || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "pad_rows: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "pad_rows: bad dtype %d", dtype);
+// The ops that exist in a fixed and a ragged (`_lens`) form share one implementation each: `ragged` chooses the kernel instantiation
+// (lens is null and unread in the fixed form) and `name` is the entry's name in its messages.
+static int pad_rows_impl(const char* name, const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, bool ragged, const int* lens,
+                         void* stream) {
+  if (!in || !out || (ragged && !lens) || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "%s: bad argument", name);
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "%s: bad dtype %d", name, dtype);
   const long long n = (long long)B * (L + 2 * pad) * d;
-  const bool two_byte = kind(dtype).bytes == 2;      // a pure move: every 2-byte kind (one plane of a split operand included) moves as bf16 bit patterns
   return submit([=](hipStream_t s) {
-    if (two_byte) hipLaunchKernelGGL((fdm::pad_rows_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, L, d, pad, zero);
-    else hipLaunchKernelGGL((fdm::pad_rows_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, L, d, pad, zero);
+    with_move_type(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      const auto k = ragged ? fdm::pad_rows_kernel<T, true> : fdm::pad_rows_kernel<T, false>;
+      hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(256), 0, s, (const T*)in, (T*)out, B, L, d, pad, zero, lens);
+    });
     return hipGetLastError();
-  }, stream, "pad_rows");
+  }, stream, name);
 }
-
+int fdm_op_pad_rows(const void* in, void* out, int B, int L, int d, int pad, int dtype, int zero, void* stream) {
+  return pad_rows_impl("pad_rows", in, out, B, L, d, pad, dtype, zero, false, nullptr, stream);
+}
 int fdm_op_pad_rows_lens(const void* in, void* out, int B, int L, int d, int pad, int dtype, const int* lens, void* stream) {
-  if (!in || !out || !lens || B <= 0 || L <= 0 || d <= 0 || pad < 0) return fail(FDM_ERR_ARG, "pad_rows_lens: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "pad_rows_lens: bad dtype %d", dtype);
-  const bool two_byte = kind(dtype).bytes == 2;
-  return submit([=](hipStream_t s) {
-    const long long n = (long long)B * (L + 2 * pad) * d;
-    if (two_byte) hipLaunchKernelGGL((fdm::pad_rows_lens_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, L, d, pad, lens);
-    else hipLaunchKernelGGL((fdm::pad_rows_lens_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, L, d, pad, lens);
-    return hipGetLastError();
-  }, stream, "pad_rows_lens");
+  return pad_rows_impl("pad_rows_lens", in, out, B, L, d, pad, dtype, 0, true, lens, stream);
 }
 
 int fdm_op_zero_pad_rows(float* x, int B, int L, int d, const int* lens, void* stream) {
@@ -484,30 +499,25 @@ int fdm_op_zero_pad_rows(float* x, int B, int L, int d, const int* lens, void* s
   }, stream, "zero_pad_rows");
 }
 
-int fdm_op_group_pad(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, void* stream) {
-  if (!in || !out || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "group_pad: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "group_pad: bad dtype %d", dtype);
+static int group_pad_impl(const char* name, const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, bool ragged, const int* lens,
+                          void* stream) {
+  if (!in || !out || (ragged && !lens) || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "%s: bad argument", name);
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "%s: bad dtype %d", name, dtype);
   const long long n = (long long)B * (T + 2 * pad) * d;
-  const bool two_byte = kind(dtype).bytes == 2;      // (one plane of a split operand moves like any 2-byte matrix: the caller passes each plane)
   return submit([=](hipStream_t s) {
-    if (two_byte)
-      hipLaunchKernelGGL((fdm::group_pad_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, T, d, groups, pad);
-    else hipLaunchKernelGGL((fdm::group_pad_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, T, d, groups, pad);
+    with_move_type(dtype, [&](auto tag) {
+      using E = decltype(tag);
+      const auto k = ragged ? fdm::group_pad_kernel<E, true> : fdm::group_pad_kernel<E, false>;
+      hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(256), 0, s, (const E*)in, (E*)out, B, T, d, groups, pad, lens);
+    });
     return hipGetLastError();
-  }, stream, "group_pad");
+  }, stream, name);
 }
-
+int fdm_op_group_pad(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, void* stream) {
+  return group_pad_impl("group_pad", in, out, B, T, d, groups, pad, dtype, false, nullptr, stream);
+}
 int fdm_op_group_pad_lens(const void* in, void* out, int B, int T, int d, int groups, int pad, int dtype, const int* lens, void* stream) {
-  if (!in || !out || !lens || B <= 0 || T <= 0 || d <= 0 || groups <= 0 || d % groups || pad < 0) return fail(FDM_ERR_ARG, "group_pad_lens: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "group_pad_lens: bad dtype %d", dtype);
-  const long long n = (long long)B * (T + 2 * pad) * d;
-  const bool two_byte = kind(dtype).bytes == 2;
-  return submit([=](hipStream_t s) {
-    if (two_byte)
-      hipLaunchKernelGGL((fdm::group_pad_lens_kernel<fdm::bf16>), dim3(grid_for(n)), dim3(256), 0, s, (const fdm::bf16*)in, (fdm::bf16*)out, B, T, d, groups, pad, lens);
-    else hipLaunchKernelGGL((fdm::group_pad_lens_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, (const float*)in, (float*)out, B, T, d, groups, pad, lens);
-    return hipGetLastError();
-  }, stream, "group_pad_lens");
+  return group_pad_impl("group_pad_lens", in, out, B, T, d, groups, pad, dtype, true, lens, stream);
 }
 
 int fdm_op_mask_samples(const float* wav, float* out, int B, int n, const int* lens, void* stream) {
@@ -556,87 +566,72 @@ int fdm_op_conv0_ln_gelu(const float* wav, const float* w, const float* bias, co
   }, stream, "conv0_ln_gelu");
 }
 
+static int leaky_instnorm_impl(const char* name, const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, bool ragged,
+                               const int* lens, void* stream) {
+  if (!x || (!y_f32 && !y_t) || (ragged && !lens) || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "%s: bad argument", name);
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "%s: bad dtype %d", name, dtype);
+  if (y_t && dtype != FDM_F32 && dtype != FDM_BF16) return fail(FDM_ERR_ARG, "%s: y_t dtype %d (fp32 or bf16 output)", name, dtype);
+  return submit([=](hipStream_t s) {
+    const dim3 grid((d + 63) / 64, B);
+    const auto launch = [&](auto tag) {
+      using T = decltype(tag);
+      const auto k = ragged ? fdm::leaky_instnorm_kernel<T, true> : fdm::leaky_instnorm_kernel<T, false>;
+      hipLaunchKernelGGL(k, grid, dim3(1024), 0, s, x, y_f32, (T*)y_t, L, d, eps, lens);
+    };
+    if (dtype == FDM_BF16) launch(fdm::bf16{});
+    else launch(float{});
+    return hipGetLastError();
+  }, stream, name);
+}
 int fdm_op_leaky_instnorm(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, void* stream) {
-  if (!x || (!y_f32 && !y_t) || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "leaky_instnorm: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "leaky_instnorm: bad dtype %d", dtype);
-  if (y_t && dtype != FDM_F32 && dtype != FDM_BF16) return fail(FDM_ERR_ARG, "leaky_instnorm: y_t dtype %d (fp32 or bf16 output)", dtype);
-  return submit([=](hipStream_t s) {
-    dim3 grid((d + 63) / 64, B);
-    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::leaky_instnorm_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, y_f32, (fdm::bf16*)y_t, L, d, eps);
-    else hipLaunchKernelGGL((fdm::leaky_instnorm_kernel<float>), grid, dim3(1024), 0, s, x, y_f32, (float*)y_t, L, d, eps);
-    return hipGetLastError();
-  }, stream, "leaky_instnorm");
+  return leaky_instnorm_impl("leaky_instnorm", x, y_f32, y_t, B, L, d, eps, dtype, false, nullptr, stream);
 }
-
 int fdm_op_leaky_instnorm_lens(const float* x, float* y_f32, void* y_t, int B, int L, int d, float eps, int dtype, const int* lens, void* stream) {
-  if (!x || (!y_f32 && !y_t) || !lens || B <= 0 || L <= 0 || d <= 0) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: bad dtype %d", dtype);
-  if (y_t && dtype != FDM_F32 && dtype != FDM_BF16) return fail(FDM_ERR_ARG, "leaky_instnorm_lens: y_t dtype %d (fp32 or bf16 output)", dtype);
-  return submit([=](hipStream_t s) {
-    dim3 grid((d + 63) / 64, B);
-    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::leaky_instnorm_lens_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, y_f32, (fdm::bf16*)y_t, L, d, eps, lens);
-    else hipLaunchKernelGGL((fdm::leaky_instnorm_lens_kernel<float>), grid, dim3(1024), 0, s, x, y_f32, (float*)y_t, L, d, eps, lens);
-    return hipGetLastError();
-  }, stream, "leaky_instnorm_lens");
+  return leaky_instnorm_impl("leaky_instnorm_lens", x, y_f32, y_t, B, L, d, eps, dtype, true, lens, stream);
 }
 
-int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
-                          float eps, int act, int dtype, void* scratch, long long scratch_bytes, void* stream) {
-  if (!x || (!y_f32 && !y_t) || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "time_groupnorm: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "time_groupnorm: bad dtype %d", dtype);
-  if (y_t && dtype == FDM_F16) return fail(FDM_ERR_ARG, "time_groupnorm: y_t dtype %d (fp32, bf16 or FDM_F16X3 output)", dtype);
-  if (y_t && dtype == FDM_F16X3 && y_t_lo_off <= 0) return fail(FDM_ERR_ARG, "time_groupnorm: split y_t needs y_t_lo_off");
-  // long clips with a scratch buffer: statistics and normalisation over time chunks (two launches, hundreds of workgroups)
-  const int nch = T >= 4096 ? std::min(64, (T + 1023) / 1024) : 1;
-  const int chunk = ((T + nch - 1) / nch + 15) / 16 * 16;
+// Clips of TIME_CHUNKED_FROM frames or more take the chunked form (statistics and normalisation over time chunks: two launches, hundreds
+// of workgroups), which needs scratch.  The two forms differ on purpose when the scratch is missing, too small or misaligned: the fixed
+// form falls back to the three-pass kernel; the ragged form, whose clips must take the form of their own launch, refuses.
+static int time_groupnorm_impl(const char* name, const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off,
+                               int B, int T, int C, float eps, int act, int dtype, void* scratch, long long scratch_bytes, bool ragged, const int* lens,
+                               void* stream) {
+  if (!x || (!y_f32 && !y_t) || (ragged && !lens) || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "%s: bad argument", name);
+  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "%s: bad dtype %d", name, dtype);
+  if (y_t && dtype == FDM_F16) return fail(FDM_ERR_ARG, "%s: y_t dtype %d (fp32, bf16 or FDM_F16X3 output)", name, dtype);
+  if (y_t && dtype == FDM_F16X3 && y_t_lo_off <= 0) return fail(FDM_ERR_ARG, "%s: split y_t needs y_t_lo_off", name);
+  int chunk;
+  const int nch = T >= fdm::TIME_CHUNKED_FROM ? fdm::time_chunks_of(T, &chunk) : 0;
   const long long need = (long long)B * nch * C * 2 * (long long)sizeof(double);
-  const long long lo = y_t_lo_off;
-  if (scratch && nch > 1 && scratch_bytes >= need && ((uintptr_t)scratch % 8) == 0) {
-    double* part = (double*)scratch;
-    return submit([=](hipStream_t s) {
-      const dim3 grid((C + 63) / 64, nch, B);
-      hipLaunchKernelGGL(fdm::time_stats_kernel, grid, dim3(1024), 0, s, x, part, T, C, chunk);
-      if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_norm_apply_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, chunk, eps, act);
-      else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_norm_apply_kernel<fdm::f16x3_t>), grid, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, chunk, eps, act);
-      else hipLaunchKernelGGL((fdm::time_norm_apply_kernel<float>), grid, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, chunk, eps, act);
-      return hipGetLastError();
-    }, stream, "time_groupnorm");
-  }
-  return submit([=](hipStream_t s) {
-    dim3 grid((C + 63) / 64, B);
-    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_groupnorm_kernel<fdm::bf16>), grid, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, eps, act);
-    else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_groupnorm_kernel<fdm::f16x3_t>), grid, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, eps, act);
-    else hipLaunchKernelGGL((fdm::time_groupnorm_kernel<float>), grid, dim3(1024), 0, s, x, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act);
-    return hipGetLastError();
-  }, stream, "time_groupnorm");
-}
-
-int fdm_op_time_groupnorm_lens(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
-                               float eps, int act, int dtype, void* scratch, long long scratch_bytes, const int* lens, void* stream) {
-  if (!x || (!y_f32 && !y_t) || !lens || B <= 0 || T <= 0 || C <= 0) return fail(FDM_ERR_ARG, "time_groupnorm_lens: bad argument");
-  if (!kind_ok(dtype)) return fail(FDM_ERR_ARG, "time_groupnorm_lens: bad dtype %d", dtype);
-  if (y_t && dtype == FDM_F16) return fail(FDM_ERR_ARG, "time_groupnorm_lens: y_t dtype %d (fp32, bf16 or FDM_F16X3 output)", dtype);
-  if (y_t && dtype == FDM_F16X3 && y_t_lo_off <= 0) return fail(FDM_ERR_ARG, "time_groupnorm_lens: split y_t needs y_t_lo_off");
-  // a clip of >= 4096 frames takes the chunked form, as fdm_op_time_groupnorm does when it is given scratch: here the scratch is required
-  const int nch = T >= 4096 ? std::min(64, (T + 1023) / 1024) : 0;
-  const long long need = (long long)B * nch * C * 2 * (long long)sizeof(double);
-  if (nch && (!scratch || scratch_bytes < need || ((uintptr_t)scratch % 8) != 0))
-    return fail(FDM_ERR_ARG, "time_groupnorm_lens: T = %d needs %lld bytes of 8-byte aligned scratch", T, need);
-  const long long lo = y_t_lo_off;
+  const bool chunked = nch && scratch && scratch_bytes >= need && ((uintptr_t)scratch % 8) == 0;
+  if (ragged && nch && !chunked) return fail(FDM_ERR_ARG, "%s: T = %d needs %lld bytes of 8-byte aligned scratch", name, T, need);
   double* part = (double*)scratch;
   return submit([=](hipStream_t s) {
     const dim3 g1((C + 63) / 64, B), g2((C + 63) / 64, nch ? nch : 1, B);
-    if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<fdm::bf16>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, eps, act, lens);
-    else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<fdm::f16x3_t>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, eps, act, lens);
-    else hipLaunchKernelGGL((fdm::time_groupnorm_lens_kernel<float>), g1, dim3(1024), 0, s, x, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act, lens);
-    if (nch) {
-      hipLaunchKernelGGL(fdm::time_stats_lens_kernel, g2, dim3(1024), 0, s, x, part, T, C, lens);
-      if (dtype == FDM_BF16) hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<fdm::bf16>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::bf16*)y_t, 0LL, T, C, eps, act, lens);
-      else if (dtype == FDM_F16X3) hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<fdm::f16x3_t>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (fdm::f16*)y_t, lo, T, C, eps, act, lens);
-      else hipLaunchKernelGGL((fdm::time_norm_apply_lens_kernel<float>), g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, (float*)y_t, 0LL, T, C, eps, act, lens);
-    }
+    with_out_kind(dtype, y_t_lo_off, [&](auto tag, long long lo) {
+      using K = decltype(tag);
+      auto* yt = (typename fdm::Opnd<K>::E*)y_t;
+      if (ragged || !chunked) {      // (ragged: every form is launched, a workgroup whose clip belongs to the other form leaves at once)
+        const auto k = ragged ? fdm::time_groupnorm_kernel<K, true> : fdm::time_groupnorm_kernel<K, false>;
+        hipLaunchKernelGGL(k, g1, dim3(1024), 0, s, x, gamma, beta, y_f32, yt, lo, T, C, eps, act, lens);
+      }
+      if (chunked) {
+        const auto ks = ragged ? fdm::time_stats_kernel<true> : fdm::time_stats_kernel<false>;
+        const auto ka = ragged ? fdm::time_norm_apply_kernel<K, true> : fdm::time_norm_apply_kernel<K, false>;
+        hipLaunchKernelGGL(ks, g2, dim3(1024), 0, s, x, part, T, C, lens);
+        hipLaunchKernelGGL(ka, g2, dim3(1024), 0, s, x, (const double*)part, gamma, beta, y_f32, yt, lo, T, C, eps, act, lens);
+      }
+    });
     return hipGetLastError();
-  }, stream, "time_groupnorm_lens");
+  }, stream, name);
+}
+int fdm_op_time_groupnorm(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
+                          float eps, int act, int dtype, void* scratch, long long scratch_bytes, void* stream) {
+  return time_groupnorm_impl("time_groupnorm", x, gamma, beta, y_f32, y_t, y_t_lo_off, B, T, C, eps, act, dtype, scratch, scratch_bytes, false, nullptr, stream);
+}
+int fdm_op_time_groupnorm_lens(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, long long y_t_lo_off, int B, int T, int C,
+                               float eps, int act, int dtype, void* scratch, long long scratch_bytes, const int* lens, void* stream) {
+  return time_groupnorm_impl("time_groupnorm_lens", x, gamma, beta, y_f32, y_t, y_t_lo_off, B, T, C, eps, act, dtype, scratch, scratch_bytes, true, lens, stream);
 }
 
 int fdm_op_mean_diff(const float* a, const float* b, float* partial, float* out, long long n, int l1, void* stream) {

@@ -297,6 +297,11 @@ def group_pad(inp, out, B, T, d, groups, pad):
     check(lib().fdm_op_group_pad(_p(inp), _p(out), B, T, d, groups, pad, code_of(inp), stream()))
 
 
+def group_pad_lens(inp, out, B, T, d, groups, pad, lens):
+    """Grouped zero padding of clips of unequal length (lens: device int32 [B]): frames at or beyond lens[b] are written as zeros."""
+    check(lib().fdm_op_group_pad_lens(_p(inp), _p(out), B, T, d, groups, pad, code_of(inp), _p(lens), stream()))
+
+
 def conv0(wav, w, bias, out, B, n, T0):
     check(lib().fdm_op_conv0(_p(wav), _p(w), _p(bias), _p(out), B, n, T0, stream()))
 
@@ -319,6 +324,14 @@ def time_groupnorm(x, gamma, beta, B, T, C, *, y_f32=None, y_t=None, eps=1e-5, a
     time chunks (two launches, hundreds of workgroups) instead of C / 64 workgroups per clip."""
     nbytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
     check(lib().fdm_op_time_groupnorm(_p(x), _p(gamma), _p(beta), _p(y_f32), _p(y_t), _lo(y_t), B, T, C, eps, act, dtype, _p(scratch), nbytes, stream()))
+
+
+def time_groupnorm_lens(x, gamma, beta, B, T, C, lens, *, y_f32=None, y_t=None, eps=1e-5, act=ACT_NONE, dtype=F32, scratch=None):
+    """time_groupnorm over clips of unequal length (lens: device int32 [B]): each clip is normalised as its own launch with scratch
+    would be; here the scratch is required once the padded T reaches 4096 frames."""
+    nbytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
+    check(lib().fdm_op_time_groupnorm_lens(_p(x), _p(gamma), _p(beta), _p(y_f32), _p(y_t), _lo(y_t), B, T, C, eps, act, dtype, _p(scratch), nbytes,
+                                           _p(lens), stream()))
 
 
 def mean_diff(a, b, l1=False):

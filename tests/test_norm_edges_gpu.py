@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 import norm_cases as NC  # noqa: E402
 from norm_cases import ACT_GELU_ERF, ACT_NONE, BF16, F16, F16X3, F32  # noqa: E402
-from fdm_amd import _lib, ops  # noqa: E402
+from fdm_amd import ops  # noqa: E402
 from fdm_amd._lib import FdmError  # noqa: E402
 
 DEV = "cuda:0"
@@ -328,9 +328,7 @@ def gn_launch(kind, case, o, x=None, lens=None):
     scratch = gn_scratch(case, B, T)
     yt = arg(o, "t")
     if lens is not None:
-        nbytes = scratch.numel() * 8 if scratch is not None else 0
-        _lib.check(_lib.lib().fdm_op_time_groupnorm_lens(ops._p(x), ops._p(inp["gamma"]), ops._p(inp["beta"]), ops._p(arg(o, "f32")), ops._p(yt), ops._lo(yt),
-                                                         B, T, case.C, inp["eps"], case.act, kind, ops._p(scratch), nbytes, ops._p(lens), ops.stream()))
+        ops.time_groupnorm_lens(x, inp["gamma"], inp["beta"], B, T, case.C, lens, y_f32=arg(o, "f32"), y_t=yt, eps=inp["eps"], act=case.act, dtype=kind, scratch=scratch)
     else:
         ops.time_groupnorm(x, inp["gamma"], inp["beta"], B, T, case.C, y_f32=arg(o, "f32"), y_t=yt, eps=inp["eps"], act=case.act, dtype=kind, scratch=scratch)
     return scratch      # (kept alive by the caller until the synchronize)

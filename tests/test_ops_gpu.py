@@ -640,6 +640,64 @@ def test_pad_rows_and_group_pad_move_fp16_by_element_size():
         assert torch.equal(got, want)       # (an op that moved nothing would leave two different sentinel bit patterns behind)
 
 
+def _guarded_move(dtype, shape, op):
+    """Run op(out) on an output of `shape` between two guard zones; the output's bits as integers, on the host."""
+    GUARD, SENT = 64, -7.0
+    n_out = math.prod(shape)
+    buf = torch.full((GUARD + n_out + GUARD,), SENT, dtype=dtype, device=DEV)
+    op(buf[GUARD:GUARD + n_out])
+    torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == SENT).all()) and bool((buf[GUARD + n_out:] == SENT).all()), "wrote outside the output"
+    return buf[GUARD:GUARD + n_out].view(torch.int16 if buf.element_size() == 2 else torch.int32).cpu().reshape(shape)
+
+
+def _int_bits(x):
+    return x.contiguous().view(torch.int16 if x.element_size() == 2 else torch.int32).cpu()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("lens", [(1, 3, 5), (0, 9, 5)], ids=["lens135", "lens095"])
+def test_pad_rows_lens_moves_each_clip_as_its_own_launch(lens, dtype):
+    """ops.pad_rows_lens, a pure move: out[b, k] = in[b, clamp(k - pad, 0, Lb - 1)] with Lb = lens[b] clamped to [1, L] (0 -> 1, 9 -> 5),
+    bit for bit against a host index computation, and a clip's first Lb + 2 pad rows are those of ops.pad_rows on the clip alone."""
+    B, L, d, pad = 3, 5, 8, 2
+    x = torch.randn(B, L, d, generator=torch.Generator().manual_seed(11)).to(dtype).to(DEV)
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    got = _guarded_move(dtype, (B, L + 2 * pad, d), lambda o: ops.pad_rows_lens(x, o, B, L, d, pad, lens_d))
+    xb = _int_bits(x)
+    for b in range(B):
+        Lb = min(max(lens[b], 1), L)
+        src = [min(max(k - pad, 0), Lb - 1) for k in range(L + 2 * pad)]
+        assert torch.equal(got[b], xb[b, src]), f"clip {b}: host index computation"
+        clip = x[b:b + 1, :Lb].contiguous()
+        solo = _guarded_move(dtype, (Lb + 2 * pad, d), lambda o: ops.pad_rows(clip, o, 1, Lb, d, pad))
+        assert torch.equal(got[b, :Lb + 2 * pad], solo), f"clip {b}: its own launch"
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_group_pad_lens_moves_each_clip_as_its_own_launch(dtype):
+    """ops.group_pad_lens, a pure move: out[g, b, k] = in[b, k - pad, g's columns] for 0 <= k - pad < min(lens[b], T) and +0.0 elsewhere
+    (a length of 0 gives an all-zero clip, 7 clamps to T = 5), bit for bit against a host index computation, and a clip's first
+    Tb + 2 pad rows are those of ops.group_pad on the clip alone."""
+    B, T, d, groups, pad, lens = 3, 5, 8, 2, 3, (0, 3, 7)
+    dg = d // groups
+    x = torch.randn(B, T, d, generator=torch.Generator().manual_seed(12)).to(dtype).to(DEV)
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    got = _guarded_move(dtype, (groups, B, T + 2 * pad, dg), lambda o: ops.group_pad_lens(x, o, B, T, d, groups, pad, lens_d))
+    xb = _int_bits(x)
+    for b in range(B):
+        Tb = min(lens[b], T)
+        want = torch.zeros(groups, T + 2 * pad, dg, dtype=xb.dtype)
+        for g in range(groups):
+            want[g, pad:pad + Tb] = xb[b, :Tb, g * dg:(g + 1) * dg]
+        assert torch.equal(got[:, b], want), f"clip {b}: host index computation"
+        if Tb == 0:       # (all zeros, by the check above; the fixed op takes no empty clip, so there is no launch of its own)
+            continue
+        clip = x[b:b + 1, :Tb].contiguous()
+        solo = _guarded_move(dtype, (groups, Tb + 2 * pad, dg), lambda o: ops.group_pad(clip, o, 1, Tb, d, groups, pad))
+        assert torch.equal(got[:, b, :Tb + 2 * pad], solo), f"clip {b}: its own launch"
+
+
 def test_program_record_graph_replay():
     """Record two ops, run eagerly, then replay as a hipGraph with a device-side step counter."""
     n = 4096
