@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <string>
@@ -57,6 +58,24 @@ struct Arena {
   }
   void release() { for (void* p : allocs) (void)hipFree(p); allocs.clear(); }
 };
+
+// a scratch array of an object that grows when a call is larger than any before it (that call waits for the device first: the old
+// array may still be read)
+template <typename T> int grow(Arena& mem, T** p, long long* cap, long long n) {
+  if (n <= *cap) return FDM_OK;
+  if (*p) { HIPCK(hipDeviceSynchronize()); mem.free_one(*p); *p = nullptr; *cap = 0; }
+  FCK(mem.alloc_t(p, (size_t)n));
+  *cap = n;
+  return FDM_OK;
+}
+
+// the frame rates of the hand-offs (fdm_mesh_*, fdm_rig_*): finite and >= 0; resampling happens when both are given and differ
+inline int check_fps(const char* who, double fps_in, double fps_out) {
+  if (!(fps_in >= 0.0) || !(fps_out >= 0.0) || std::isinf(fps_in) || std::isinf(fps_out))
+    return fail(FDM_ERR_ARG, "%s: frame rates %g -> %g (finite and >= 0; 0 = no resampling)", who, fps_in, fps_out);
+  return FDM_OK;
+}
+inline bool resamples(double fps_in, double fps_out) { return fps_in > 0.0 && fps_out > 0.0 && fps_in != fps_out; }
 
 inline int need_weight(const std::map<std::string, Wt>& w, const char* who, const std::string& name, long long n, const float** out) {
   auto it = w.find(name);

@@ -26,12 +26,6 @@ using namespace fdm;
 
 const int MESH_FLAGS = FDM_MESH_INTERLEAVED | FDM_MESH_F16 | FDM_MESH_NORMALS;
 
-int check_fps(const char* who, double fps_in, double fps_out) {
-  if (!(fps_in >= 0.0) || !(fps_out >= 0.0) || std::isinf(fps_in) || std::isinf(fps_out))
-    return fail(FDM_ERR_ARG, "%s: frame rates %g -> %g (finite and >= 0; 0 = no resampling)", who, fps_in, fps_out);
-  return FDM_OK;
-}
-bool resamples(double fps_in, double fps_out) { return fps_in > 0.0 && fps_out > 0.0 && fps_in != fps_out; }
 
 // L_out of a clip of L frames (the rule of the audio encoder's interpolated length); < 0: does not fit an int
 long long frames_out_of(int L, double fps_in, double fps_out) {
@@ -49,14 +43,6 @@ int check_topology(const char* who, const int* faces, int F, int V) {
   if (F > 0x7fffffff / 3 || V > 0x7fffffff / 6) return fail(FDM_ERR_ARG, "%s: F = %d, V = %d (3 F and 6 V are 32-bit ints)", who, F, V);
   for (long long i = 0; i < 3LL * F; ++i)
     if (faces[i] < 0 || faces[i] >= V) return fail(FDM_ERR_ARG, "%s: face %lld names vertex %d of %d", who, i / 3, faces[i], V);
-  return FDM_OK;
-}
-
-template <typename T> int grow(Arena& mem, T** p, long long* cap, long long n) {
-  if (n <= *cap) return FDM_OK;
-  if (*p) { HIPCK(hipDeviceSynchronize()); mem.free_one(*p); *p = nullptr; *cap = 0; }
-  FCK(mem.alloc_t(p, (size_t)n));
-  *cap = n;
   return FDM_OK;
 }
 

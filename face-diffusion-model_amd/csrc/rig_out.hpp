@@ -1,0 +1,228 @@
+// Kernels of the rig hand-off (include/fdm_hip.h, fdm_rig_*; launched by rig_out.hip): decoded vertex offsets -> blendshape coefficients
+// per frame, a ridge-regularised, box-constrained least-squares fit onto a basis.  DESIGN section 2 item 19 is the definition.
+//   rig_proj_kernel   grid (tiles of RIG_FT rows of [B * L_max], chunks of RIG_CHUNK elements of 3V), 4 wavefronts.  Stages the tile's
+//                     offsets in LDS: a row starts on a 4-byte boundary only (12 V bytes per row), so each row is peeled to its own
+//                     16-byte boundary (<= 3 single loads, 16-byte loads for the body, <= 3 single loads behind it) and lands at its
+//                     logical position; the chunk's tail is zero-filled.  Every wavefront then takes the whole tile into registers
+//                     (RIG_FT x RIG_CHUNK / 64 values per lane) and walks k = wave, wave + 4, ...: 16-byte loads of P[k] (rows padded
+//                     with zeros to whole chunks, so aligned and in bounds; K x RIG_CHUNK x 4 bytes per chunk, shared by every tile
+//                     of the chunk: workgroup ids run over the tiles first, so the slab is served by the L2), RIG_FT fused
+//                     multiply-add chains per lane, then a halving butterfly over the lanes (RIG_FT + 2 exchanges) whose shape is the
+//                     same for every row slot.  Partial sums go to part [chunk][row][k] through LDS (whole lines).  Plain VALU: the
+//                     fp32 MFMA rate on gfx950 is the vector rate, and the kernel is fed by the L2, not bound by either.
+//   rig_solve_kernel  one wavefront per output frame, RIG_SW frames per workgroup, coefficient k on lane k mod 64 (two registers at
+//                     K > 64).  r[k] = the partial sums of the frame's row in ascending chunk order, starting from the first; the
+//                     frame-rate rule of mesh_pos_kernel applied to r; then the Cholesky solve and the projected Gauss-Seidel sweeps
+//                     in the column order of the header, every operation rounded on its own.  G [K][K], L [K][K | 1] (an odd stride:
+//                     its column reads are conflict-free), lo and hi sit in LDS: 132.6 KB at K = 128.  A NaN coefficient stays
+//                     NaN through the clamp, as numpy's minimum / maximum keep it.
+// A frame's values are a function of its own row: no atomics, and neither the batch, L_max, the row's slot in its tile nor the
+// workgroup enters an expression.  Input rows at or past frames[b] are never read.  Resource use: profiles/rig_out/resources.txt.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/fdm_hip.h"
+
+namespace fdm {
+
+constexpr int RIG_CHUNK = 768;            // elements of 3V per partial sum (12 per lane; a multiple of 3: chunks end on vertices)
+constexpr int RIG_FT = 8;                 // rows of [B * L_max] per workgroup of rig_proj_kernel
+constexpr int RIG_SW = 8;                 // wavefronts (= output frames) per workgroup of rig_solve_kernel
+constexpr int RIG_KMAX = 128;
+
+// min(max(x, lo), hi) that keeps a NaN x (fminf / fmaxf would return the bound)
+__device__ __forceinline__ float rig_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+__device__ __forceinline__ float rig_xor(float v, int mask) { return __shfl_xor(v, mask, 64); }
+__device__ __forceinline__ float rig_lane(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
+
+// off: [rows][V3] (rows = B * L_max; lens: [B][2] = {L, L_out}).  P: [K][ldp], ldp = chunks * RIG_CHUNK, zero behind V3.
+// part: [chunks][rows][K].  A tile without a live row writes nothing (its partial sums are never read).
+__global__ __launch_bounds__(256) void rig_proj_kernel(const float* off, const int* lens, int L_max, int rows, int V3, const float* P, int ldp,
+                                                       int K, float* part) {
+  __shared__ __attribute__((aligned(16))) float sd[RIG_FT * RIG_CHUNK];
+  __shared__ float so[RIG_FT * RIG_KMAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * RIG_FT, c0 = blockIdx.y * RIG_CHUNK;
+  const int n = min(RIG_CHUNK, V3 - c0);
+  bool any = false;
+#pragma unroll
+  for (int r = 0; r < RIG_FT; ++r) {
+    const int row = row0 + r;
+    float* d = sd + r * RIG_CHUNK;
+    bool live = false;
+    if (row < rows) { const int b = row / L_max; live = row - b * L_max < lens[2 * b]; }
+    any |= live;
+    if (!live) {
+      for (int j = tid; j < RIG_CHUNK; j += 256) d[j] = 0.f;
+      continue;
+    }
+    const float* src = off + (size_t)row * V3 + c0;
+    const int head = min(n, (int)((4 - (((uintptr_t)src >> 2) & 3)) & 3));
+    const int nb = (n - head) >> 2, done = head + 4 * nb;
+    for (int m = tid; m < nb; m += 256) {
+      const float4 v = *reinterpret_cast<const float4*>(src + head + 4 * m);
+      float* q = d + head + 4 * m;
+      q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
+    }
+    if (tid < head) d[tid] = src[tid];
+    if (tid >= 64 && tid - 64 < n - done) d[done + tid - 64] = src[done + tid - 64];
+    for (int j = n + tid; j < RIG_CHUNK; j += 256) d[j] = 0.f;
+  }
+  if (!any) return;                                         // (uniform over the workgroup)
+  __syncthreads();
+  constexpr int Q = RIG_CHUNK / 256;                        // 16-byte pieces per lane and row
+  float4 x[RIG_FT][Q];
+#pragma unroll
+  for (int r = 0; r < RIG_FT; ++r)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) x[r][q] = *reinterpret_cast<const float4*>(sd + r * RIG_CHUNK + 4 * (lane + 64 * q));
+  for (int k = wave; k < K; k += 4) {
+    const float* pk = P + (size_t)k * ldp + c0;
+    float4 p[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) p[q] = *reinterpret_cast<const float4*>(pk + 4 * (lane + 64 * q));
+    float a[RIG_FT];
+#pragma unroll
+    for (int r = 0; r < RIG_FT; ++r) {
+      float s = __fmul_rn(p[0].x, x[r][0].x);
+      s = __builtin_fmaf(p[0].y, x[r][0].y, s); s = __builtin_fmaf(p[0].z, x[r][0].z, s); s = __builtin_fmaf(p[0].w, x[r][0].w, s);
+#pragma unroll
+      for (int q = 1; q < Q; ++q) {
+        s = __builtin_fmaf(p[q].x, x[r][q].x, s); s = __builtin_fmaf(p[q].y, x[r][q].y, s);
+        s = __builtin_fmaf(p[q].z, x[r][q].z, s); s = __builtin_fmaf(p[q].w, x[r][q].w, s);
+      }
+      a[r] = s;
+    }
+    // halving butterfly: after the masks 32, 16, 8 lane l holds row slot (l >> 3) & 7 summed over the lanes that share l & 7
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+    float b4[4], b2[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float keep = h5 ? a[j + 4] : a[j], give = h5 ? a[j] : a[j + 4]; b4[j] = __fadd_rn(keep, rig_xor(give, 32)); }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { const float keep = h4 ? b4[j + 2] : b4[j], give = h4 ? b4[j] : b4[j + 2]; b2[j] = __fadd_rn(keep, rig_xor(give, 16)); }
+    float s = __fadd_rn(h3 ? b2[1] : b2[0], rig_xor(h3 ? b2[0] : b2[1], 8));
+    s = __fadd_rn(s, rig_xor(s, 4)); s = __fadd_rn(s, rig_xor(s, 2)); s = __fadd_rn(s, rig_xor(s, 1));
+    if ((lane & 7) == 0) so[(lane >> 3) * K + k] = s;
+  }
+  __syncthreads();
+  const int live_rows = min(RIG_FT, rows - row0);
+  float* o = part + ((size_t)blockIdx.y * rows + row0) * K;
+  for (int i = tid; i < live_rows * K; i += 256) o[i] = so[i];
+}
+
+// G [K][K], Lc [K][K] (lower Cholesky factor, row-major), lo / hi [K] (bounded = 0: not read).  coef / proj: [B][Lo_max][K] (proj may
+// be null); rows at or past L_out[b] are written as zeros.  Dynamic LDS: (K * K + K * (K | 1) + 2 * K) floats.
+__global__ __launch_bounds__(RIG_SW * 64) void rig_solve_kernel(const float* part, int chunks, int rows_in, const int* lens, int L_max, int Lo_max,
+                                                                int rows_out, int K, int resample, const float* G, const float* Lc,
+                                                                const float* lo, const float* hi, int bounded, int sweeps, float* coef,
+                                                                float* proj) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sG = reinterpret_cast<float*>(smem);
+  float* sL = sG + K * K;
+  float* slo = sL + K * (K | 1);
+  float* shi = slo + K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ld = K | 1;
+  for (int i = tid; i < K * K; i += RIG_SW * 64) { sG[i] = G[i]; sL[(i / K) * ld + i % K] = Lc[i]; }
+  if (bounded) for (int i = tid; i < K; i += RIG_SW * 64) { slo[i] = lo[i]; shi[i] = hi[i]; }
+  __syncthreads();
+  const int row = blockIdx.x * RIG_SW + wave;
+  if (row >= rows_out) return;                              // (uniform over the wavefront; no barrier follows)
+  const int b = row / Lo_max, t = row - b * Lo_max;
+  const int L = lens[2 * b], Lo = lens[2 * b + 1];
+  const int H = K > 64 ? 2 : 1;
+  float* oc = coef + (size_t)row * K;
+  float* op = proj ? proj + (size_t)row * K : nullptr;
+  if (t >= Lo) {
+    for (int h = 0; h < H; ++h) { const int k = lane + 64 * h; if (k < K) { oc[k] = 0.f; if (op) op[k] = 0.f; } }
+    return;
+  }
+  int i0 = t, i1 = t;
+  float l0 = 1.f, l1 = 0.f;
+  if (resample) {                         // mesh_pos_kernel's expression with Tin = L, Tout = Lo
+    const float scale = Lo > 1 ? (float)(L - 1) / (float)(Lo - 1) : 0.f;
+    const float src = __fmul_rn(scale, (float)t);
+    i0 = min((int)src, L - 1);
+    i1 = i0 + (i0 < L - 1 ? 1 : 0);
+    l1 = __fsub_rn(src, (float)i0);
+    l0 = __fsub_rn(1.f, l1);
+  }
+  float r[2] = {0.f, 0.f}, g[2], c[2] = {0.f, 0.f};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = lane + 64 * h;
+    if (k >= K) continue;
+    const float* p0 = part + ((size_t)b * L_max + i0) * K + k;
+    const float* p1 = part + ((size_t)b * L_max + i1) * K + k;
+    const size_t cs = (size_t)rows_in * K;
+    float s0 = p0[0], s1 = resample ? p1[0] : 0.f;
+    for (int q = 1; q < chunks; ++q) {
+      s0 = __fadd_rn(s0, p0[q * cs]);
+      if (resample) s1 = __fadd_rn(s1, p1[q * cs]);
+    }
+    r[h] = resample ? __fadd_rn(__fmul_rn(l0, s0), __fmul_rn(l1, s1)) : s0;
+    if (op) op[k] = r[h];
+  }
+  g[0] = r[0]; g[1] = r[1];
+  // forward: y_i = g_i / L_ii; g_k -= L_ki y_i for k > i (g becomes y in place)
+  for (int i = 0; i < K; ++i) {
+    const float gi = i < 64 ? rig_lane(g[0], i) : rig_lane(g[1], i - 64);
+    const float y = __fdiv_rn(gi, sL[i * ld + i]);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k == i) g[h] = y;
+      else if (k > i && k < K) g[h] = __fsub_rn(g[h], __fmul_rn(sL[k * ld + i], y));
+    }
+  }
+  // backward: x_i = y_i / L_ii; y_k -= L_ik x_i for k < i (g becomes x in place)
+  for (int i = K - 1; i >= 0; --i) {
+    const float yi = i < 64 ? rig_lane(g[0], i) : rig_lane(g[1], i - 64);
+    const float x = __fdiv_rn(yi, sL[i * ld + i]);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k == i) g[h] = x;
+      else if (k < i) g[h] = __fsub_rn(g[h], __fmul_rn(sL[i * ld + k], x));
+    }
+  }
+  if (!bounded) {
+    c[0] = g[0]; c[1] = g[1];
+  } else {
+    float lo_k[2] = {0.f, 0.f}, hi_k[2] = {0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < K) { lo_k[h] = slo[k]; hi_k[h] = shi[k]; }
+      c[h] = rig_clamp(g[h], lo_k[h], hi_k[h]);
+      g[h] = r[h];
+    }
+    // residual g = r - G c, one column of G at a time (G is symmetric: column j is row j)
+    for (int j = 0; j < K; ++j) {
+      const float cj = j < 64 ? rig_lane(c[0], j) : rig_lane(c[1], j - 64);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        if (k < K) g[h] = __fsub_rn(g[h], __fmul_rn(sG[j * K + k], cj));
+      }
+    }
+    for (int s = 0; s < sweeps; ++s)
+      for (int j = 0; j < K; ++j) {
+        const float cj = j < 64 ? rig_lane(c[0], j) : rig_lane(c[1], j - 64);
+        const float gj = j < 64 ? rig_lane(g[0], j) : rig_lane(g[1], j - 64);
+        const float nj = rig_clamp(__fadd_rn(cj, __fdiv_rn(gj, sG[j * K + j])), slo[j], shi[j]);
+        const float delta = __fsub_rn(nj, cj);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int k = lane + 64 * h;
+          if (k == j) c[h] = nj;
+          if (k < K) g[h] = __fsub_rn(g[h], __fmul_rn(sG[j * K + k], delta));
+        }
+      }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; if (k < K) oc[k] = c[h]; }
+}
+
+}  // namespace fdm

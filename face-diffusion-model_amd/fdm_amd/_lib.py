@@ -207,6 +207,10 @@ SYMBOLS = {
     "fdm_mesh_frames": (ci, [ci, C.c_double, C.c_double, C.POINTER(ci)]),
     "fdm_mesh_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, ci, vp, vp, ci, vp, vp]),
     "fdm_mesh_destroy": (ci, [vp]),
+    "fdm_rig_gram_host": (ci, [vp, vp, ci, ci, C.c_double, vp, vp]),
+    "fdm_rig_create": (ci, [vp, ci, ci, vp, C.c_double, vp, vp, ci, C.POINTER(vp)]),
+    "fdm_rig_forward": (ci, [vp, vp, vp, ci, ci, C.c_double, C.c_double, vp, vp, ci, vp, vp]),
+    "fdm_rig_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),

@@ -156,6 +156,62 @@ def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, 
     return _split_mesh(mf) if many else mf
 
 
+_RIG_PLANS = {}       # (device, stream, identity of the rig: rig.RigPlan.key) -> rig.RigPlan
+
+
+def _rig_plan(rig, device):
+    """The rig hand-off plan of `device`, the current stream and this rig (a plan serves one stream at a time), kept as _mesh_plan()
+    keeps mesh plans.  rig: a rig.RigPlan (used as it is where it was made for this device and stream, made again from its
+    arguments otherwise) or the dict of RigPlan's arguments (every call then digests the basis to recognise it: animate_many,
+    animate_long and SlotServer come here once and go on with the plan)."""
+    from .rig import RigPlan, identity
+    dv = torch.device(device)
+    stream = torch.cuda.current_stream(dv).cuda_stream
+    mine = isinstance(rig, RigPlan)
+    key = (str(dv), stream, rig.key if mine else identity(**rig))
+    plan = _RIG_PLANS.get(key)
+    if plan is None:
+        if mine:
+            plan = rig if (rig.device == dv and rig.stream == stream) else RigPlan(device=dv, **rig.arguments())
+        else:
+            plan = RigPlan(device=dv, **rig)
+        _RIG_PLANS[key] = plan
+    return plan
+
+
+def _split_rig(rf):
+    """A batched RigFrames -> one per clip, each cut to its own frames ([1, L_out, K])."""
+    return [type(rf)(rf.weights[b:b + 1, :n], [n], rf.names) for b, n in enumerate(rf.frames)]
+
+
+@torch.no_grad()
+def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bounds=None, sweeps=16, names=None, device=None):
+    """Vertex offsets (what the decoder writes, BEFORE the template is added) -> rig.RigFrames: per frame the coefficients c of the
+    ridge-regularised, box-constrained least-squares fit of the offsets onto the blendshape basis [K, 3 V] (weights [V] per vertex,
+    bounds = (lo, hi), `sweeps` of projected Gauss-Seidel), resampled in time when fps = (fps_in, fps_out) names two different rates,
+    in ONE device call (rig.RigPlan; include/fdm_hip.h, fdm_rig_forward).  basis may be a rig.RigPlan or the dict of its arguments
+    (the other rig arguments are then not read).  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None:
+    all L) -> one RigFrames for the batch; or a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of RigFrames, each cut to
+    its own frames and bit for bit what its own call returns."""
+    from .rig import RigPlan
+    many = isinstance(offsets, (list, tuple))
+    if many:
+        clips = [o.reshape(-1, o.shape[-1]) for o in offsets]
+        frames = [int(c.shape[0]) for c in clips]
+        x = torch.zeros(len(clips), max(frames + [1]), clips[0].shape[-1], device=clips[0].device)
+        for b, c in enumerate(clips):
+            x[b, :frames[b]] = c
+    else:
+        x = offsets if offsets.dim() == 3 else offsets.unsqueeze(0)
+    dv = x.device if device is None else torch.device(device)
+    if dv.type != "cuda" or not x.is_cuda:
+        from ._lib import FdmError
+        raise FdmError("to_rig runs on the HIP path only (no CPU fallback)")
+    rig = basis if isinstance(basis, (RigPlan, dict)) else dict(basis=basis, weights=weights, ridge=ridge, bounds=bounds, sweeps=sweeps, names=names)
+    rf = _rig_plan(rig, dv).forward(x.to(dv), frames, fps)
+    return _split_rig(rf) if many else rf
+
+
 def build_models(preset="vocaset", feature_dim=None, device="cuda:0", stage1=None, stage2=None, dtype=None, cfg_level=None, single_clip=False):
     """(diffusion, autoencoder) with reference-compatible state dicts; checkpoints are loaded when the
     files exist ('model' / 'state_dict' keys as samples/sample_diffusion_vocaset.py:26,91-97), otherwise the
@@ -197,8 +253,13 @@ def _clip_x_T(shape, S, seed):
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    rig (a rig.RigPlan or the dict of its arguments: basis, weights, ridge, bounds, sweeps, names): the decoder's offsets -- never the
+    templated vertices -- go through the device rig hand-off (to_rig) and the call returns (rig.RigFrames, latent) in place of the
+    vertices: blendshape coefficients [B, L_out, K] at out_fps.  With faces= too it returns ((mesh.MeshFrames, rig.RigFrames),
+    latent); the two read the same offsets.  None: every path as before.
 
     faces [F, 3]: the decoder's output goes through the device mesh hand-off (to_mesh) and the call returns (mesh.MeshFrames,
     latent): positions [B, L_out, V, 3] -- the template added there, the same bits as the vertices returned without faces -- and
@@ -278,11 +339,15 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
             latent = diffusion.sample(audio, shape, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
         quanted, _, _ = autoencoder.quant(latent, stats=False)
     out = autoencoder.decode(quanted)
+    rf = None if rig is None else to_rig(out, rig, fps=_mesh_fps(p, in_fps, out_fps))
     if faces is not None:
         tp = None if template is None else torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, out.shape[-1])
         if tp is not None and S > 1 and tp.shape[0] == B and B > 1:
             tp = tp.repeat_interleave(S, dim=0)
-        return to_mesh(out, faces, tp, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {})), latent
+        mf = to_mesh(out, faces, tp, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))
+        return (mf if rf is None else (mf, rf)), latent
+    if rf is not None:
+        return rf, latent
     if template is not None:
         tp = torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
         out = out + (tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp)
@@ -292,8 +357,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
-                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
+                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    rig: as animate(); each group's decoded clips go through ONE ragged rig hand-off call and the first returned list holds a
+    rig.RigFrames per clip ([1, L_out_b, K]), or with faces= a (mesh.MeshFrames, rig.RigFrames) pair.  None: every path as before.
 
     faces / out_fps / mesh / in_fps: as animate(); each group's decoded clips go through ONE ragged hand-off call and the first
     returned list holds a mesh.MeshFrames per clip ([1, L_out_b, V, 3] positions and normals).  None: every path as before.
@@ -322,6 +390,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
     p = model.preset
+    rig = None if rig is None else _rig_plan(rig, device)        # a dict is digested and made into a plan once, not per group
     n = len(audios)
     if rate is not None:
         wav_b, lens_b = prepare_audio_many(audios, rate, device=device)
@@ -406,7 +475,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                     etq = None if et_g is None else et_g[i:i + 1, :Ls[b]]
                     q = autoencoder.quant(lb, emos[i:i + 1], stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
                     out = autoencoder.decode(q)
-                if faces is not None:
+                if faces is not None or rig is not None:
                     offs.append(out)
                 elif templates is not None:
                     tp = templates[b] if isinstance(templates, (list, tuple)) else templates
@@ -416,6 +485,9 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                 tps = None if templates is None else [per(templates, b) for b in grp]
                 for b, mf in zip(grp, to_mesh(offs, faces, tps, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))):
                     verts[b] = mf
+            if rig is not None:         # and through one rig hand-off call
+                for b, rf in zip(grp, to_rig(offs, rig, fps=_mesh_fps(p, in_fps, out_fps))):
+                    verts[b] = rf if faces is None else (verts[b], rf)
     finally:
         model._hub_key, model._hub = prev
     return verts, lats
@@ -424,8 +496,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    rig: as animate(): the whole recording's offsets go through the rig hand-off and the call returns (rig.RigFrames, latent), or
+    ((mesh.MeshFrames, rig.RigFrames), latent) with faces=.
     faces / out_fps / mesh / in_fps: as animate(): the whole recording's decode goes through the mesh hand-off and the call returns
     (mesh.MeshFrames, latent).
     audio [B, n] (processor-normalised) of ANY length -> (vertices [B, L_total, V3], latent [B, L_total*G, c]), L_total =
@@ -443,6 +517,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
     scale = float(diffusion.denoise_fn.level) if cfg else 2.5
     p = model.preset
+    rig = None if rig is None else _rig_plan(rig, device)
     if rate is not None:
         audio = prepare_audio(audio, rate, device=device)
     audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
@@ -478,8 +553,12 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     quanted = autoencoder.quant(latent, emo, stats=False, emotion_track=et)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
     out = autoencoder.decode(quanted)
+    rf = None if rig is None else to_rig(out, rig, fps=_mesh_fps(p, in_fps, out_fps))
     if faces is not None:
-        return to_mesh(out, faces, template, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {})), latent
+        mf = to_mesh(out, faces, template, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))
+        return (mf if rf is None else (mf, rf)), latent
+    if rf is not None:
+        return rf, latent
     if template is not None:
         out = out + torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
     return out, latent
@@ -515,20 +594,24 @@ class SlotServer:
 
     faces / out_fps / mesh / in_fps: as animate(): every finished clip's decode goes through the mesh hand-off (the template added
     there) and results() yields a mesh.MeshFrames in place of the vertices; the clips of one batched decode share one ragged call.
-    None (default): unchanged."""
+    None (default): unchanged.
+
+    rig: as animate(): every finished clip's offsets go through the rig hand-off and results() yields a rig.RigFrames in place of
+    the vertices (with faces= a (mesh.MeshFrames, rig.RigFrames) pair); the clips of one batched decode share one ragged call."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
-                 faces=None, out_fps=None, mesh=None, in_fps=None):
+                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
         from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.faces, self.mesh = faces, dict(mesh or {})
+        self.rig = None if rig is None else _rig_plan(rig, device)     # a dict is digested and made into a plan once, not per finished clip
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
         self.batched_decodes = []                   # clips per batched decode, in call order
         self.cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
         self.model = diffusion.denoise_fn.model if self.cfg else diffusion.denoise_fn
         p = self.p = self.model.preset
-        self.mesh_fps = _mesh_fps(p, in_fps, out_fps) if faces is not None else None
+        self.mesh_fps = _mesh_fps(p, in_fps, out_fps) if faces is not None or rig is not None else None
         self.n_slots = int(slots)
         self.L = min(int(max_frames), p.max_len) if max_frames else p.max_len
         self.plan = self.model.plan(device)
@@ -802,9 +885,14 @@ class SlotServer:
         return fin
 
     def _vertices(self, out, template):
-        """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames."""
+        """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames, with rig= its
+        rig.RigFrames, with both the pair."""
+        rf = None if self.rig is None else to_rig(out, self.rig, fps=self.mesh_fps)
         if self.faces is not None:
-            return to_mesh(out, self.faces, template, fps=self.mesh_fps, **self.mesh)
+            mf = to_mesh(out, self.faces, template, fps=self.mesh_fps, **self.mesh)
+            return mf if rf is None else (mf, rf)
+        if rf is not None:
+            return rf
         if template is not None:
             out = out + torch.as_tensor(template, dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
         return out
@@ -854,6 +942,9 @@ class SlotServer:
         ragged = None
         if self.faces is not None and (all(t is None for t in tps) or all(t is not None for t in tps)):      # one call over the unequal lengths
             ragged = to_mesh([outs[i, :r["L"]] for i, r in enumerate(reqs)], self.faces, None if tps[0] is None else tps, fps=self.mesh_fps, **self.mesh)
+        if self.rig is not None and (ragged or self.faces is None):          # and one rig hand-off call
+            fits = to_rig([outs[i, :r["L"]] for i, r in enumerate(reqs)], self.rig, fps=self.mesh_fps)
+            ragged = [(m, f) for m, f in zip(ragged, fits)] if ragged else fits
         for i, (s, r) in enumerate(zip(done, reqs)):
             out = ragged[i] if ragged else self._vertices(outs[i:i + 1, :r["L"]].contiguous(), r["template"])
             self._done.append((r["handle"], out, lats[i]))
@@ -866,7 +957,8 @@ class SlotServer:
         return len(self._queue) + len({r["handle"] for r in self._slot if r is not None})
 
     def results(self):
-        """[(handle, vertices [1, L, V3] -- with faces= a mesh.MeshFrames --, latent [1, L*G, c])] of the clips finished since the last call."""
+        """[(handle, vertices [1, L, V3] -- with faces= a mesh.MeshFrames, with rig= a rig.RigFrames --, latent [1, L*G, c])] of the clips
+        finished since the last call."""
         out, self._done = self._done, []
         return out
 
@@ -898,6 +990,28 @@ def track_arguments(a, p, L):
     return out
 
 
+def add_rig_arguments(ap):
+    """--rig_file / --rig_ridge / --rig_sweeps of the demo command lines (the device rig hand-off, to_rig)."""
+    ap.add_argument("--rig_file", type=str, default=None,
+                    help="build-added: blendshape rig (.npz: basis [K, 3V], optional names, weights [V], lo, hi): also save <stem>_rig.npy "
+                         "[1, L_out, K], the coefficients fitted to the decoded offsets on the device.  Without --faces_file, --out_fps resamples "
+                         "<stem>_rig.npy alone: <stem>.npy keeps the model's frame rate")
+    ap.add_argument("--rig_ridge", type=float, default=0.0, help="build-added: ridge of the fit (with --rig_file)")
+    ap.add_argument("--rig_sweeps", type=int, default=16, help="build-added: projected Gauss-Seidel sweeps of a bounded fit (with --rig_file)")
+
+
+def rig_arguments(a):
+    """rig= of animate() from the parsed flags (the dict of rig.RigPlan's arguments), or None without --rig_file."""
+    if not a.rig_file:
+        return None
+    with np.load(a.rig_file, allow_pickle=False) as z:
+        if "basis" not in z or ("lo" in z) != ("hi" in z):
+            raise ValueError(f"{a.rig_file}: needs the key basis, and lo and hi together (has {sorted(z.files)})")
+        return dict(basis=z["basis"], weights=z["weights"] if "weights" in z else None, ridge=a.rig_ridge,
+                    bounds=(z["lo"], z["hi"]) if "lo" in z else None, sweeps=a.rig_sweeps,
+                    names=[str(n) for n in z["names"]] if "names" in z else None)
+
+
 def demo_main(preset, argv=None):
     """CLI of demo/demo_{vocaset,biwi,3d_mead}.py:109-121: same flags, output = np.save(<audio_path>/<stem>.npy, [1, L, V3])."""
     import argparse
@@ -926,11 +1040,13 @@ def demo_main(preset, argv=None):
                     help="build-added: convert, downmix, resample and normalise the file's raw samples on the device (prepare_audio)")
     ap.add_argument("--faces_file", type=str, default=None,
                     help="build-added: triangle list (.npy, int [F, 3]): positions and vertex normals through the device mesh hand-off")
-    ap.add_argument("--out_fps", type=float, default=None, help=f"build-added: frame rate of the saved motion (with --faces_file; the model's is {p.fps or 'given by --in_fps'})")
+    ap.add_argument("--out_fps", type=float, default=None, help=f"build-added: frame rate of the saved motion (with --faces_file or --rig_file; the model's is {p.fps or 'given by --in_fps'})")
     ap.add_argument("--in_fps", type=float, default=None, help="build-added: the model's frame rate where the preset states none (with --out_fps)")
     ap.add_argument("--save_normals", action="store_true", help="build-added: also save <stem>_normals.npy [1, L_out, 3V] (with --faces_file)")
     add_track_arguments(ap, p)
+    add_rig_arguments(ap)
     a = ap.parse_args(argv)
+    rig = rig_arguments(a)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
                                  cfg_level=None)
     if a.device_audio:
@@ -947,7 +1063,9 @@ def demo_main(preset, argv=None):
     # tracks cover every latent frame the audio can give (16 kHz, 320 samples per encoder frame); the calls take the frames they need
     fast.update(track_arguments(a, p, max(len(wav) // 320 // p.pair + 2, p.max_len)))
     if a.faces_file:
-        fast.update(faces=np.load(a.faces_file), out_fps=a.out_fps, in_fps=a.in_fps, mesh=dict(normals=a.save_normals))
+        fast.update(faces=np.load(a.faces_file), out_fps=a.out_fps, in_fps=a.in_fps, mesh=dict(normals=a.save_normals), rig=rig)
+    if rig is not None and not a.faces_file:        # the offsets come back bare: the rig is fitted to them, the template added after
+        tmpl_after, template = template, None
     if a.long_audio == "window":
         out, _ = animate_long(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed,
                               overlap=a.window_overlap, device=a.device, **fast)
@@ -955,6 +1073,15 @@ def demo_main(preset, argv=None):
         out, _ = animate(diffusion, ae, wav, template, None, emo, ddim_steps=a.ddim_steps, seed=a.seed, device=a.device, **fast)
     os.makedirs(a.audio_path, exist_ok=True)
     dst = os.path.join(a.audio_path, os.path.basename(a.audio_file)[:-4])
+    if rig is not None:
+        if a.faces_file:
+            out, rf = out
+        else:
+            rf = to_rig(out, rig, fps=_mesh_fps(p, a.in_fps, a.out_fps))
+            if tmpl_after is not None:
+                out = out + torch.as_tensor(tmpl_after, dtype=torch.float32, device=a.device).reshape(-1, 1, out.shape[-1])
+        np.save(dst + "_rig", rf.weights.detach().cpu().numpy())
+        print(f"saved {dst}_rig.npy {tuple(rf.weights.shape)}" + (f" ({', '.join(rf.names[:4])}, ...)" if rf.names else ""))
     if a.faces_file:        # positions keep the reference's name and shape
         if a.save_normals:
             nr = out.normals.reshape(out.normals.shape[0], out.normals.shape[1], -1)

@@ -908,6 +908,54 @@ int fdm_mesh_forward(fdm_mesh* m, const float* offsets, const int* frames, int B
                      double fps_out, int flags, void* pos, void* nrm, int L_out_max, int* frames_out, void* stream);
 int fdm_mesh_destroy(fdm_mesh* m);
 
+/* ------------------------------------------------------------------------------------------
+ * Rig hand-off: the offsets fdm_vq_decode(_ragged) writes -> what an engine's face rig plays: blendshape coefficients per frame
+ * (ARKit's 52 in [0, 1], FLAME expression coefficients, a studio's own set), at the consumer's frame rate.  The fit is the standard
+ * one: ridge-regularised, box-constrained least squares of the offsets onto a basis.  Inputs: basis E [K, 3 V] of blendshape deltas
+ * from the neutral face, 1 <= K <= 128; optional per-vertex weights w [V] >= 0 (NULL: all 1); ridge lambda >= 0; optional bounds
+ * lo [K] <= hi [K] (both or neither); a sweep count S >= 0.  For a frame with offset row d (before the template is added):
+ *   c = argmin 1/2 sum_i w_v(i) (sum_k E_ki c_k - d_i)^2 + 1/2 lambda |c|^2   subject to lo <= c <= hi.
+ *   create    (host, fp64, no device needed) P = E diag(w) rounded to fp32 (the only large array uploaded); G = E diag(w) E^T + lambda I
+ *             and its Cholesky factor L (G = L L^T, lower) in fp64, both then rounded to fp32.  A pivot <= 0 (to fp64 rounding: <= K 2^-52 G_ii) or a non-finite value:
+ *             FDM_ERR_ARG, "basis is rank deficient under these weights: raise ridge".
+ *   project   r[f, k] = sum_i P[k, i] d[f, i] in fp32.  3 V is cut into chunks of 768 elements; each chunk's partial sum is formed in
+ *             an order that depends on nothing but the chunk (fused multiply-adds per lane, then a fixed tree over the lanes), and the
+ *             partial sums are added in ascending chunk order starting from the first.  No atomics: a frame's r does not depend on
+ *             the batch, L_max, its position in the launch or the workgroup that ran it.  |error| <= gamma_n sum_i |P_ki| |d_i| with
+ *             n = 3 V + chunks.
+ *   frame rate with fps_in, fps_out > 0 and different: L_out and (i0, i1, l0, l1) are exactly those of fdm_mesh_frames / fdm_mesh_forward,
+ *             applied to r: r_out = l0 * r[i0] + l1 * r[i1], every operation rounded (projection is linear: this is the fit of the
+ *             resampled offsets).  Otherwise r passes through bit for bit.
+ *   solve     fp32, every product, subtraction and division rounded on its own, in a fixed column order (a function of K alone):
+ *               forward   g = r; for i = 0..K-1: y_i = g_i / L_ii; for all k > i: g_k = g_k - (L_ki * y_i)
+ *               backward  for i = K-1..0: x_i = y_i / L_ii; for all k < i: y_k = y_k - (L_ik * x_i)
+ *               no bounds c = x
+ *               bounds    c = min(max(x, lo), hi); g = r; for j = 0..K-1, all k: g_k = g_k - (G_kj * c_j); then S sweeps of projected
+ *                         Gauss-Seidel, for j = 0..K-1: n = min(max(c_j + g_j / G_jj, lo_j), hi_j); delta = n - c_j; c_j = n;
+ *                         for all k, j included: g_k = g_k - (G_kj * delta)
+ *             (min / max keep a NaN operand: a non-finite live offset row gives NaN coefficients, never a bound)
+ *   output    coef [B, L_out_max, K] fp32 and, when proj is not NULL, proj [B, L_out_max, K]: the r the solve consumed.  Rows at or past
+ *             L_out[b] are written as zeros; input rows at or past frames[b] are never read (they may be NaN).
+ * fdm_rig_gram_host (no device): gram [K, K] fp64 = G, chol [K, K] fp32 = L rounded (zeros above the diagonal).
+ * fdm_rig_create: basis, vweight, lo, hi are HOST arrays, not read after the call; sweeps = S (16 is the library's default in Python;
+ * how many an ill-conditioned artist rig needs is unmeasured).  With a device visible it uploads P, G, L and the bounds; without one
+ * the object still validates and fdm_rig_forward ends in FDM_ERR_STATE.  FDM_ERR_ARG: a null pointer, K outside [1, 128], V < 1, a
+ * negative or non-finite weight or ridge, exactly one of lo and hi, lo_k > hi_k or a non-finite bound, sweeps < 0, a rank-deficient Gram.
+ * fdm_rig_forward: offsets [B, L_max, 3 V] fp32 device, frames [B] HOST ints in [0, L_max] (NULL: every clip has L_max frames; copied
+ * in stream order, not read after the call returns), coef and proj device, frames_out [B] HOST ints or NULL.  Launches on `stream`,
+ * never synchronises -- except that a call larger than any before it grows the object's scratch first (the partial sums, the
+ * lengths), which waits for the device.  An object holds ONE such scratch: it serves one stream at a time.  Every check is made
+ * before the first launch: FDM_ERR_ARG (null r / offsets / coef, a negative or non-finite rate), FDM_ERR_SHAPE (B, L_max or
+ * L_out_max < 1, frames[b] outside [0, L_max], L_out_max below the largest L_out[b]).  Not built: a per-frame fit residual, temporal
+ * regularisation across frames, head and jaw pose, fp16 output.  Call times: profiles/rig_out/README.md. */
+typedef struct fdm_rig fdm_rig;
+int fdm_rig_gram_host(const float* basis, const float* vweight, int K, int V, double ridge, double* gram, float* chol);
+int fdm_rig_create(const float* basis, int K, int V, const float* vweight, double ridge, const float* lo, const float* hi, int sweeps,
+                   fdm_rig** out);
+int fdm_rig_forward(fdm_rig* r, const float* offsets, const int* frames, int B, int L_max, double fps_in, double fps_out, float* coef,
+                    float* proj, int L_out_max, int* frames_out, void* stream);
+int fdm_rig_destroy(fdm_rig* r);
+
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
  * (diffusion_BIWI_encoder_decoder.py:565-603: cosine schedule in fp64, fp32 cast); DDIM pairs and per-pair coefficients
  * (:684-708, eta = 0; returns the number of live pairs, the dead (t, -1) pair excluded); get_slopes (models/fdm_vocaset.py:96-106);
