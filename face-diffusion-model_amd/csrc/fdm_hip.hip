@@ -10,6 +10,7 @@
 #include "window.hpp"
 #include "slots.hpp"
 #include "host.hpp"
+#include "gemm_tiles.hpp"
 
 namespace fdm {
 thread_local std::string g_err;
@@ -163,7 +164,7 @@ int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
     if (a->N % 64 || a->ldo_f32 % 4 || !aligned16(a->out_f32) || a->ksplit_stride % 4 || a->ksplit_stride < (long long)(a->M - 1) * a->ldo_f32 + a->N ||
         (a->resid && (a->ldr % 4 || !aligned16(a->resid))))
       return fail(FDM_ERR_SHAPE, "gemm: ksplit needs N %% 64 == 0, 16-byte aligned rows and ksplit_stride >= one output plane");
-    if (tl != 0 && tl != FDM_TILE_64x64 && tl != FDM_TILE_64x64_S2 && tl != FDM_TILE_32x64_S3)
+    if (tl != 0 && !gemm_tile_can(tl, TILE_KSPLIT))
       return fail(FDM_ERR_ARG, "gemm: ksplit runs on the 64-column tiles (FDM_TILE_64x64, FDM_TILE_64x64_S2, FDM_TILE_32x64_S3), not tile %d", tl);
   }
   if (a->batch2 < 0) return fail(FDM_ERR_ARG, "gemm: negative batch2");
@@ -172,7 +173,7 @@ int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
     if (a->ksplit > 1 || a->out_kp || a->out_vp || a->stat_out || a->ln_stat_in || a->sched_fuse || a->resid_row_mod || a->incr_counter)
       return fail(FDM_ERR_ARG, "gemm: batch2 cannot be combined with ksplit, packed K/V, LayerNorm folds, the fused scheduler or resid_row_mod");
     if (a->a_batch_stride2 % epc) return fail(FDM_ERR_ARG, "gemm: a_batch_stride2 needs 16-byte alignment");
-    if (tl != 0 && tl != FDM_TILE_64x64 && tl != FDM_TILE_64x64_S2 && tl != FDM_TILE_128x64)
+    if (tl != 0 && !gemm_tile_can(tl, TILE_BATCH2))
       return fail(FDM_ERR_ARG, "gemm: batch2 runs on the 64-column tiles (FDM_TILE_64x64, FDM_TILE_64x64_S2, FDM_TILE_128x64), not tile %d", tl);
     if (a->batch < 1) return fail(FDM_ERR_ARG, "gemm: batch2 needs batch >= 1 (the group count of the second batch level)");
   }
@@ -182,7 +183,11 @@ int fdm_op_gemm(const fdm_gemm_args* a, void* stream) {
 
 int fdm_gemm_heuristic_tile(const fdm_gemm_args* a) {
   if (!a) return fail(FDM_ERR_ARG, "gemm_heuristic_tile: null argument");
-  return fdm::gemm_heuristic_tile_of(*a);
+  fdm_gemm_args b = *a;
+  b.tile = 0;
+  // (the query has always named the forced tile for a second-batch-level launch too, although the launch itself is exempt from FDM_GEMM_TILE)
+  if (b.batch2 >= 1 && b.ksplit <= 1 && !b.sched_fuse && gemm_tile_override() > 0) return gemm_tile_override();
+  return gemm_requested_tile(b);
 }
 
 int fdm_op_attention(const fdm_attn_args* a, void* stream) {

@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "sched.hpp"
+#include "gemm_tiles.hpp"
 #include "../../include/fdm_hip.h"
 
 namespace fdm {
@@ -1020,280 +1021,103 @@ static bool gemm_all_tiles_lean(const fdm_gemm_args& a) {
   }
   return true;
 }
-template <typename T, int BM, int BN, int WM, int WN, int NST, int KCH, int LW>
-static hipError_t gemm_glds_launch_lw(const fdm_gemm_args& a, hipStream_t s) {
-  const bool no_lean = (a.tile & FDM_TILE_GENERAL) != 0;      // tests: the edge-handling kernel on a shape that does not need it
-  if (a.ksplit > 1) {       // K-sliced launch (validated by fdm_op_gemm: plain fp32 output, no activation): the 64-column tiles only
-    if constexpr (BN == 64 && (BM == 64 || BM == 32)) {
-      if (!gemm_all_tiles_lean<T, BM, BN>(a)) return hipErrorInvalidValue;
-      return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, GEMM_LEAN | GEMM_KSPLIT, LW>(a, s);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if (a.batch2 >= 1) {       // second batch level (validated by fdm_op_gemm): two kernels per tile, both with every activation compiled in
-    if constexpr (BN == 64 && (BM == 64 || BM == 128)) {
-      if (!no_lean && gemm_all_tiles_lean<T, BM, BN>(a) && a.out_batch_stride2 % 4 == 0)
-        return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, true, false, GEMM_LEAN | GEMM_B2, LW>(a, s);
-      return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, true, false, GEMM_B2, LW>(a, s);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if (gemm_act_is_heavy(a.act)) {
-    if (!no_lean && !a.out_kp && !a.out_vp && !a.stat_out && !a.ln_stat_in && gemm_all_tiles_lean<T, BM, BN>(a))
-      return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, true, false, GEMM_LEAN, LW>(a, s);
-    return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, true, false, 0, LW>(a, s);
-  }
-  if (!no_lean && gemm_all_tiles_lean<T, BM, BN>(a)) {
-    const bool kv = a.out_kp || a.out_vp, fold = a.stat_out || a.ln_stat_in;
-    if (kv && fold) return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, GEMM_LEAN | GEMM_KV | GEMM_FOLD, LW>(a, s);
-    if (kv) return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, GEMM_LEAN | GEMM_KV, LW>(a, s);
-    if (fold) return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, GEMM_LEAN | GEMM_FOLD, LW>(a, s);
-    return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, GEMM_LEAN, LW>(a, s);
-  }
-  return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, false, false, 0, LW>(a, s);
+
+// ---- one launch: its kernel variant, its main loop, its tile (gemm_tiles.hpp) ----------------------------------------------------
+// The HEAVY / SCHED / SPEC instantiation the arguments need, for either main loop.  spec < 0: no kernel of the launch's form fits them.
+struct GemmVariant { bool heavy, sched; int spec; };
+template <typename T, int BM, int BN>
+static GemmVariant gemm_variant(const fdm_gemm_args& a) {
+  if (a.sched_fuse)      // the scheduler-fused latent decoder (validated: interior tiles only -> the lean epilogue); the table-driven form has its own kernels
+    return {false, true, GEMM_LEAN | (a.ln_stat_in ? GEMM_FOLD : 0) | (a.sched.mode == 3 ? GEMM_LM : 0)};
+  const bool all_lean = gemm_all_tiles_lean<T, BM, BN>(a);
+  const bool lean = all_lean && !(a.tile & FDM_TILE_GENERAL);      // (FDM_TILE_GENERAL, tests: the edge-handling kernel on a shape that does not need it)
+  if (a.ksplit > 1)      // K-sliced launch (validated by fdm_op_gemm: plain fp32 output, no activation)
+    return {false, false, all_lean ? GEMM_LEAN | GEMM_KSPLIT : -1};
+  if (a.batch2 >= 1)     // second batch level (validated by fdm_op_gemm): two kernels per tile, both with every activation compiled in
+    return {true, false, GEMM_B2 | (lean && a.out_batch_stride2 % 4 == 0 ? GEMM_LEAN : 0)};
+  const bool kv = a.out_kp || a.out_vp, fold = a.stat_out || a.ln_stat_in;
+  if (gemm_act_is_heavy(a.act)) return {true, false, lean && !kv && !fold ? GEMM_LEAN : 0};
+  return {false, false, lean ? GEMM_LEAN | (kv ? GEMM_KV : 0) | (fold ? GEMM_FOLD : 0) : 0};
 }
 
-// Tile launcher: the loader-wave form (LW_ waves that only issue the tile loads) for the 16-bit operand kinds unless the caller asks
-// for the lockstep loop (FDM_TILE_LOCKSTEP: A/B and tests -- the two are bit-identical); fp32 is MFMA-bound and keeps the lockstep loop.
-template <typename T, int BM, int BN, int WM, int WN, int NST, int LW_ = 0, int KCH = 8>
-static hipError_t gemm_glds_launch_t(const fdm_gemm_args& a, hipStream_t s) {
-  if constexpr (LW_ > 0 && !std::is_same<T, float>::value) {
-    if (!(a.tile & FDM_TILE_LOCKSTEP) && !gemm_lockstep_env()) return gemm_glds_launch_lw<T, BM, BN, WM, WN, NST, KCH, LW_>(a, s);
+// A main loop at one geometry as a launcher of variants: the LDS-DMA ring (LW loader waves), or the ping-pong loop.  OK = false: the
+// tile does not run the variant's launch form, so the kernel is not instantiated and the launch fails.
+template <typename T_, int BM_, int BN_, int WM, int WN, int NST, int KCH, int LW, bool PP_>
+struct GemmLoop {
+  using T = T_;
+  static constexpr int BM = BM_, BN = BN_;
+  static constexpr bool PP = PP_;
+  template <bool OK, bool HEAVY, bool SCHED, int SPEC>
+  static hipError_t launch(const fdm_gemm_args& a, hipStream_t s) {
+    if constexpr (!OK) return hipErrorInvalidValue;
+    else if constexpr (PP) return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, HEAVY, SCHED, SPEC, KCH>(a, s);
+    else return gemm_glds_launch_h<T, BM, BN, WM, WN, NST, KCH, HEAVY, SCHED, SPEC, LW>(a, s);
   }
-  return gemm_glds_launch_lw<T, BM, BN, WM, WN, NST, KCH, 0>(a, s);
+};
+
+// The one instantiation switch: every kernel the library can launch is named here, once per loop and geometry.  CAN = GemmTile::can.
+constexpr int gemm_variant_key(bool heavy, bool sched, int spec) { return (heavy ? 0x100 : 0) | (sched ? 0x200 : 0) | spec; }
+template <class Loop, unsigned CAN>
+static hipError_t gemm_launch_variant(const fdm_gemm_args& a, hipStream_t s) {
+  constexpr bool KS = CAN & TILE_KSPLIT, B2 = CAN & TILE_BATCH2, SC = CAN & TILE_SCHED;
+  constexpr bool SC_FOLD = SC && !Loop::PP;      // (the ping-pong decoder takes no LayerNorm fold: gemm_requested_tile)
+  const GemmVariant v = gemm_variant<typename Loop::T, Loop::BM, Loop::BN>(a);
+  switch (v.spec < 0 ? -1 : gemm_variant_key(v.heavy, v.sched, v.spec)) {
+    case gemm_variant_key(false, false, 0): return Loop::template launch<true, false, false, 0>(a, s);
+    case gemm_variant_key(false, false, GEMM_LEAN): return Loop::template launch<true, false, false, GEMM_LEAN>(a, s);
+    case gemm_variant_key(false, false, GEMM_LEAN | GEMM_KV): return Loop::template launch<true, false, false, GEMM_LEAN | GEMM_KV>(a, s);
+    case gemm_variant_key(false, false, GEMM_LEAN | GEMM_FOLD): return Loop::template launch<true, false, false, GEMM_LEAN | GEMM_FOLD>(a, s);
+    case gemm_variant_key(false, false, GEMM_LEAN | GEMM_KV | GEMM_FOLD): return Loop::template launch<true, false, false, GEMM_LEAN | GEMM_KV | GEMM_FOLD>(a, s);
+    case gemm_variant_key(true, false, 0): return Loop::template launch<true, true, false, 0>(a, s);
+    case gemm_variant_key(true, false, GEMM_LEAN): return Loop::template launch<true, true, false, GEMM_LEAN>(a, s);
+    case gemm_variant_key(false, false, GEMM_LEAN | GEMM_KSPLIT): return Loop::template launch<KS, false, false, GEMM_LEAN | GEMM_KSPLIT>(a, s);
+    case gemm_variant_key(true, false, GEMM_B2): return Loop::template launch<B2, true, false, GEMM_B2>(a, s);
+    case gemm_variant_key(true, false, GEMM_B2 | GEMM_LEAN): return Loop::template launch<B2, true, false, GEMM_B2 | GEMM_LEAN>(a, s);
+    case gemm_variant_key(false, true, GEMM_LEAN): return Loop::template launch<SC, false, true, GEMM_LEAN>(a, s);
+    case gemm_variant_key(false, true, GEMM_LEAN | GEMM_LM): return Loop::template launch<SC, false, true, GEMM_LEAN | GEMM_LM>(a, s);
+    case gemm_variant_key(false, true, GEMM_LEAN | GEMM_FOLD): return Loop::template launch<SC_FOLD, false, true, GEMM_LEAN | GEMM_FOLD>(a, s);
+    case gemm_variant_key(false, true, GEMM_LEAN | GEMM_FOLD | GEMM_LM): return Loop::template launch<SC_FOLD, false, true, GEMM_LEAN | GEMM_FOLD | GEMM_LM>(a, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NST>
-static hipError_t gemm_pp_launch_t(const fdm_gemm_args& a, hipStream_t s) {
-  const bool no_lean = (a.tile & FDM_TILE_GENERAL) != 0;      // tests: the edge-handling kernel on a shape that does not need it
-  if (gemm_act_is_heavy(a.act)) {
-    if (!no_lean && !a.out_kp && !a.out_vp && !a.stat_out && !a.ln_stat_in && gemm_all_tiles_lean<T, BM, BN>(a))
-      return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, true, false, GEMM_LEAN>(a, s);
-    return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, true>(a, s);
+// A tile at one ring depth: the loader-wave form (GemmTile::lw waves that only issue the tile loads) for the 16-bit operand kinds unless
+// the caller asks for the lockstep loop (FDM_TILE_LOCKSTEP: A/B and tests -- the two are bit-identical); fp32 is MFMA-bound and keeps the
+// lockstep loop.
+template <typename T, int ID, int NST>
+static hipError_t gemm_depth_launch(const fdm_gemm_args& a, hipStream_t s) {
+  constexpr GemmTile t = gemm_tile(ID);
+  if constexpr (t.lw > 0 && !std::is_same<T, float>::value) {
+    if (!(a.tile & FDM_TILE_LOCKSTEP) && !gemm_lockstep_env()) return gemm_launch_variant<GemmLoop<T, t.bm, t.bn, t.wm, t.wn, NST, t.kch, t.lw, t.pp>, t.can>(a, s);
   }
-  if (!no_lean && gemm_all_tiles_lean<T, BM, BN>(a)) {
-    const bool kv = a.out_kp || a.out_vp, fold = a.stat_out || a.ln_stat_in;
-    if (kv && fold) return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, false, false, GEMM_LEAN | GEMM_KV | GEMM_FOLD>(a, s);
-    if (kv) return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, false, false, GEMM_LEAN | GEMM_KV>(a, s);
-    if (fold) return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, false, false, GEMM_LEAN | GEMM_FOLD>(a, s);
-    return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, false, false, GEMM_LEAN>(a, s);
-  }
-  return gemm_pp_launch_h<T, BM, BN, WM, WN, NST, false>(a, s);
+  return gemm_launch_variant<GemmLoop<T, t.bm, t.bn, t.wm, t.wn, NST, t.kch, 0, t.pp>, t.can>(a, s);
 }
 
-// ---- tile choice -------------------------------------------------------------------------------------------------------
-// fdm_gemm_args.tile (the caller's plan-time choice; FDM_TILE_GENERAL may be or-ed in), else the FDM_GEMM_TILE override (env, read
-// once: the FDM_TILE_* value forced for every GEMM, for A/B measurements), else the heuristic below: gemm_heuristic_tile names the FDM_TILE_* a launch
-// with tile = 0 resolves to (also exported as fdm_gemm_heuristic_tile, so that the plan-time tuner does not time a candidate
-// against itself).  Every tile accumulates k in the same order: the choice changes speed, never results.
-static int gemm_tile_override() {
-  static int v = [] { const char* e = getenv("FDM_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  return v;
-}
-static bool gemm_one_round(long long tiles) { return tiles > 192 && tiles <= 256; }
-// 80x128 tiles that fill the chip in exactly one round (225..256 workgroups, e.g. 800 rows x 3072 columns = 240): every CU
-// streams one (80 + 128)-row operand pair instead of two or three 64x64 ones (12.7 vs 14.6 us bf16, 22.2 vs 28.4 us f16x3
-// on that shape; profiles/README.md round 3)
-static bool gemm_one_round_80(const fdm_gemm_args& a) {
-  const long long t80 = (long long)((a.M + 79) / 80) * ((a.N + 127) / 128) * (a.batch > 0 ? a.batch : 1);
-  return t80 > 224 && t80 <= 256 && (a.M % 80 == 0 || a.M % 80 > 40);   // (a mostly empty last row tile wastes the round)
-}
-
-// 64x128 tiles that fill the chip in exactly one round for a wide projection (FFN1 at the step's 800 rows: 13 x 16 = 208 workgroups): with
-// loader waves (round 5) the k loop runs at the CU's L2 -> LDS rate, so the tile with fewer bytes per CU wins -- 8.45 us against 9.71 for two
-// co-resident 64x64 tiles per CU in bf16, 14.9 against 18.7 in f16x3 (profiles/r5_ldw/isolated.txt)
-static bool gemm_one_round_64x128(const fdm_gemm_args& a) {
-  const long long t = (long long)((a.M + 63) / 64) * ((a.N + 127) / 128) * (a.batch > 0 ? a.batch : 1);
-  return gemm_one_round(t) && a.N >= 2048 && a.N % 128 == 0;
-}
-
-// elem_bytes: 4 (fp32) or 2; split: the two-plane kinds (a ring stage is twice as large there, so their tile set is the part
-// of the one-plane set whose ring fits 160 KB of LDS)
-static int gemm_heuristic_tile(const fdm_gemm_args& a, int elem_bytes, bool split) {
-  if (a.batch2 >= 1) {       // grouped conv over clips: 128-row tiles once they fill the chip (one round of 256: 4 row tiles x 16 groups x 4 clips), else 64
-    const long long t128b = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64) * (a.batch > 0 ? a.batch : 1) * a.batch2;
-    return t128b >= 192 ? FDM_TILE_128x64 : FDM_TILE_64x64;
-  }
-  const long long batch = a.batch > 0 ? a.batch : 1;
-  const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128) * batch;
-  const long long t128x64 = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64) * batch;
-  const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64) * batch;
-  const long long t64x128 = (long long)((a.M + 63) / 64) * ((a.N + 127) / 128) * batch;
-  // Round 5 (the loop runs at the CU's L2 -> LDS rate: fewer bytes on the busiest CU wins; rules from the tuner's picks over 66 shapes on
-  // the loader-wave build, profiles/r5_tile_sweep/):
-  //  * narrow outputs (N <= 512: MEAD's out-proj / FFN2 / decoder at 2400-4000 rows) whose 64x64 grid needs two workgroups per CU or two
-  //    rounds while the 64x128 grid is one round: 64x128 (-4...-8 % on those chains)
-  const bool narrow_one_round = elem_bytes == 2 && a.N <= 512 && a.N % 128 == 0 && t64 > 256 && t64x128 <= 256;
-  //  * a few hundred rows and a wide projection whose 128x64 grid is (nearly) one round: 128x64 instead of two co-resident 64x64 tiles
-  //    per CU (QKV at 400-600 rows, FFN1 at 600: -2.5...-4 %)
-  const bool wide_128x64 = elem_bytes == 2 && a.M <= 1024 && a.N >= 2048 && t128x64 >= 160 && t128x64 <= 256;
-  if (!split) {
-    // Measured on MI355X (profiles/README.md): the biggest tile wins only once it still yields >= 2 blocks per CU;
-    // below that the 64x64 tile's extra blocks beat its higher L2->LDS traffic.
-    constexpr long long thr128 = 512, thr128x64 = 700;
-    const long long t256 = (long long)((a.M + 255) / 256) * ((a.N + 127) / 128) * batch;
-    // thousands of rows: the ping-pong loop on the 256x128 tile (the tuner's pick for the N <= 2048 sites from 6400 rows and
-    // for FFN1 from 3200; `profiles/r3_rows_sweep`, `r3_tile_sweep`; bf16 only, whole column tiles)
-    const bool pp_ok = elem_bytes == 2 && a.N % 128 == 0 && a.K >= 1024;
-    if (pp_ok && a.M >= 6000 && a.N <= 2048 && t256 >= 150) return FDM_TILE_256x128_PP;
-    // a wide projection whose 256x128 grid is exactly one round (HuBERT's FFN1 at 4 x 10 s: 1992 x 4096 = 8 x 32 tiles; 29.6 us
-    // against 33.3 on the 512 tiles of 128x128, profiles/r4_pmc_hubert; the lockstep 256x128 kernel of rounds 2-4 measured 29.9 against
-    // 29.4 for the ping-pong loop there and is retired: profiles/r5_xcd_band/gemm_tiles_hubert_ffn.txt)
-    if (elem_bytes == 2 && a.M > 1024 && t128 >= thr128 && gemm_one_round(t256)) return FDM_TILE_256x128_PP;
-    if (t128 >= thr128) {
-      // 128x128 unless its last round is less than half full (600 tiles = 2.34 rounds: QKV at 3200 rows, MEAD's at 6400): 128x64 on the
-      // 3-stage ring, two workgroups per CU, balances that tail (-4 % on those chains)
-      const long long tail = t128 % 256;
-      if (elem_bytes == 2 && t128 < 1024 && tail > 0 && tail < 128) return FDM_TILE_128x64;
-      return FDM_TILE_128x128;
-    }
-    if (gemm_one_round_80(a)) return FDM_TILE_80x128;
-    if (elem_bytes == 2 && gemm_one_round_64x128(a)) return FDM_TILE_64x128;
-    if (wide_128x64) return FDM_TILE_128x64;
-    if (narrow_one_round && a.M > 1024) return FDM_TILE_64x128;
-    // one short clip (and MEAD's d = 512 sites up to ~800 rows): 64x64 tiles leave most CUs idle -> 32-row tiles, twice the workgroups
-    // (the split kinds have had this rule since round 3; with loader waves it pays in bf16 too: -3.5...-5.5 % on MEAD's chains at 200-800 rows)
-    if (elem_bytes == 2 && t64 <= 128 && a.N <= 1536) return FDM_TILE_32x64_S3;
-    // (measured in bf16 only: the fp32 kind keeps its rules; short-K products whose 64x64 grid is resident in one round -- two
-    //  64 KB rings per CU -- stay on it: MEAD's d = 512 sites at 1200-1600 rows lost 3-5 % on larger tiles)
-    if (elem_bytes == 2 && a.M > 1024 && (t64 > 512 || a.K >= 1024)) {
-      // 1100..4000 rows (batched clips, long clips, CFG): what the plan-time tuner picks there (profiles/r3_tile_sweep/), as rules.
-      // A grid that fills the chip in exactly ONE round wins; else 128x64 -- on the 4-stage ring while its grid is one round, on the
-      // 3-stage ring (72 KB: two workgroups per CU, all of <= 512 tiles resident) beyond.
-      if (gemm_one_round(t128)) return FDM_TILE_128x128;
-      if (gemm_one_round(t256)) return FDM_TILE_256x128_PP;
-      if (t128x64 > 128) return FDM_TILE_128x64;          // (4-stage ring while its grid is one round, 3-stage beyond: the tile picks)
-    }
-    if (t128x64 >= thr128x64) return FDM_TILE_128x64;
-    return FDM_TILE_64x64;
-  }
-  if (t128 >= 512) return FDM_TILE_128x128;
-  if (gemm_one_round_80(a)) return FDM_TILE_80x128;
-  if (gemm_one_round_64x128(a)) return FDM_TILE_64x128;
-  if (wide_128x64) return FDM_TILE_128x64;
-  if (a.M > 1024) {            // the tuner's picks at 1100..4000 rows as rules (see above)
-    if (gemm_one_round(t128)) return FDM_TILE_128x128;
-    if (narrow_one_round) return FDM_TILE_64x128;
-    if (t128x64 > 128 && t128x64 <= 256) return FDM_TILE_128x64;     // (split kinds: 3-stage, 144 KB ring -- one per CU, so one round only)
-    // Beyond the rules (1600+ rows in the split kinds, where every ring is one workgroup per CU): the tile with the fewest operand rows on
-    // the busiest CU, rounds x (BM + BN) -- the model the tuner prunes with; it reproduces the tuner's picks at 1600-4800 rows (80x128 for
-    // QKV at 1600 and FFN1 at 2400, 128x128 for QKV at 2400: -3.6...-8.6 % on those chains)
-    struct { int id, bm, bn; } cand[] = {{FDM_TILE_64x64, 64, 64}, {FDM_TILE_128x64, 128, 64}, {FDM_TILE_64x128, 64, 128}, {FDM_TILE_80x128, 80, 128}, {FDM_TILE_128x128, 128, 128}};
-    int best = FDM_TILE_64x64; long long best_rows = -1;
-    for (auto& c : cand) {
-      if (a.N % c.bn) continue;
-      const long long tiles = (long long)((a.M + c.bm - 1) / c.bm) * (a.N / c.bn) * batch;
-      const long long rows = ((tiles + 255) / 256) * (c.bm + c.bn);
-      if (best_rows < 0 || rows < best_rows) { best = c.id; best_rows = rows; }
-    }
-    return best;
+// A live tile: its loop and ring depth from the table, by the operand kind's plane count
+template <typename T, int ID>
+static hipError_t gemm_tile_launch(const fdm_gemm_args& a, hipStream_t s) {
+  constexpr GemmTile t = gemm_tile(ID);
+  if constexpr (Opnd<T>::NP == 2 && t.split_id != ID) {      // (gemm_resolve_tile never names such an id for a two-plane launch: it has no kernel there)
+    return gemm_tile_launch<T, t.split_id>(a, s);
+  } else if constexpr (Opnd<T>::NP == 2) {
+    return gemm_depth_launch<T, ID, t.nst2>(a, s);
   } else {
-    // a single short clip: 64x64 tiles leave half the CUs idle -> 32-row tiles (72 KB rings, two per CU); 257..512 tiles of a
-    // wide projection: the 2-stage ring (64 KB) keeps all of them resident in one round instead of two
-    if (t64 <= 128) return FDM_TILE_32x64_S3;
-    // more than one round of 64x64 tiles (one 128 KB ring per CU) where the 64x128 grid is a single round: MEAD's QKV at 800 rows (-6...-8 %)
-    if (t64 > 256 && t64x128 <= 256 && a.N % 128 == 0) return FDM_TILE_64x128;
-    if (t64 > 256 && t64 <= 512 && a.N >= 2048) return FDM_TILE_64x64_S2;
-  }
-  if (t128x64 >= 700) return FDM_TILE_128x64;
-  return FDM_TILE_64x64;
-}
-
-// the scheduler-fused latent decoder has two forms (64x64, ping-pong 256x128): the same rule as its unfused shape
-static bool gemm_sched_fuse_heuristic_pp(const fdm_gemm_args& a, int elem_bytes) {
-  fdm_gemm_args b = a;
-  b.sched_fuse = 0;
-  return gemm_heuristic_tile(b, elem_bytes, false) == FDM_TILE_256x128_PP;
-}
-
-// the scheduler-fused latent decoder on the 64x64 tile (lean kernels only), loader-wave form for the 16-bit kinds
-template <typename T, int LM = 0>
-static hipError_t gemm_sched_fuse_launch(const fdm_gemm_args& a, hipStream_t s) {
-  if constexpr (LM == 0) {
-    if (a.sched.mode == 3) return gemm_sched_fuse_launch<T, GEMM_LM>(a, s);      // the table-driven form: its own kernels
-  }
-  if constexpr (!std::is_same<T, float>::value) {
-    if (!(a.tile & FDM_TILE_LOCKSTEP) && !gemm_lockstep_env())
-      return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD | LM, 4>(a, s)
-                          : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | LM, 4>(a, s);
-  }
-  return a.ln_stat_in ? gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | GEMM_FOLD | LM>(a, s)
-                      : gemm_glds_launch_h<T, 64, 64, 2, 4, 4, 8, false, true, GEMM_LEAN | LM>(a, s);
-}
-
-// K-sliced launches (fdm_gemm_args.ksplit): the 64-column tiles, ring depth by tile id.  With S slices per output tile the grid
-// is S times as large and a slice's chain 1 / S as long, so shallower rings (more co-resident slices per CU) are the candidates.
-static int gemm_ksplit_heuristic_tile(const fdm_gemm_args& a) { return a.M <= 256 ? FDM_TILE_32x64_S3 : FDM_TILE_64x64; }   // (profiles/r5_splitk/; the tuner's pick at 249 rows on the loader-wave build)
-template <typename T>
-static hipError_t gemm_dispatch_ksplit(const fdm_gemm_args& a, int tile_id, hipStream_t s) {
-  switch (tile_id > 0 ? tile_id : gemm_ksplit_heuristic_tile(a)) {
-    case FDM_TILE_64x64_S2: return gemm_glds_launch_t<T, 64, 64, 2, 4, 2, 4>(a, s);
-    case FDM_TILE_32x64_S3: return gemm_glds_launch_t<T, 32, 64, 2, 2, 3, 2>(a, s);
-    default: return gemm_glds_launch_t<T, 64, 64, 2, 4, 4, 4>(a, s);
+    const long long wgs = (long long)((a.M + t.bm - 1) / t.bm) * ((a.N + t.bn - 1) / t.bn) * (a.batch > 0 ? a.batch : 1) * (a.batch2 > 0 ? a.batch2 : 1);
+    return wgs <= 256 ? gemm_depth_launch<T, ID, t.nst>(a, s) : gemm_depth_launch<T, ID, t.nst_many>(a, s);
   }
 }
 
 template <typename T>
 static hipError_t gemm_dispatch(const fdm_gemm_args& a, hipStream_t s) {
-  if (a.sched_fuse) {     // (validated: interior tiles only -> the lean epilogue)
-    // thousands of rows: the scheduler-fused latent decoder on the ping-pong tile when the plan's tuner picked it
-    const int tile_id = a.tile & FDM_TILE_ID_MASK;
-    const bool pp = tile_id == FDM_TILE_256x128_PP || (tile_id == 0 && gemm_tile_override() == 0 && gemm_sched_fuse_heuristic_pp(a, (int)sizeof(typename Opnd<T>::E)));
-    if (pp && !a.ln_stat_in && a.N % 128 == 0)
-      return a.sched.mode == 3 ? gemm_pp_launch_h<T, 256, 128, 4, 2, 3, false, true, GEMM_LEAN | GEMM_LM>(a, s)
-                               : gemm_pp_launch_h<T, 256, 128, 4, 2, 3, false, true, GEMM_LEAN>(a, s);
-    return gemm_sched_fuse_launch<T>(a, s);
-  }
-  const int tile_id = a.tile & FDM_TILE_ID_MASK;
-  if (a.ksplit > 1) return gemm_dispatch_ksplit<T>(a, tile_id, s);
-  // (FDM_GEMM_TILE forces one tile on the plain launches only: a second-batch-level launch runs on its own tile set -- like ksplit above)
-  const int want = tile_id > 0 ? tile_id : (a.batch2 >= 1 ? 0 : gemm_tile_override());
-  switch (want > 0 ? want : gemm_heuristic_tile(a, (int)sizeof(typename Opnd<T>::E), false)) {
-    case FDM_TILE_128x64_S3:                                                       // (retired id: the tile picks its ring depth)
-    case FDM_TILE_128x64: {                                                        // 8 waves, 32x32 per wave
-      // 4-stage ring (96 KB, one per CU) while the grid is one round; beyond that the 3-stage ring (72 KB): two workgroups per CU
-      const long long wgs = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64) * (a.batch > 0 ? a.batch : 1) * (a.batch2 > 0 ? a.batch2 : 1);
-      // (Round 6, measured and not adopted: four compute waves of 64x32 instead of eight of 32x32 beyond one round -- fewer fragment bytes read
-      //  from LDS per staged byte -- is 7-11 % faster on the isolated QKV / FFN1 shapes at 1992 rows with a plain epilogue and 1-1.7 % SLOWER
-      //  inside cfg5's step program and HuBERT-large, where the epilogue's residual / packed-K,V operands share the registers:
-      //  profiles/r6_loop_ablation/.)
-      return wgs <= 256 ? gemm_glds_launch_t<T, 128, 64, 4, 2, 4, 4>(a, s) : gemm_glds_launch_t<T, 128, 64, 4, 2, 3, 4>(a, s);
-    }
-    case FDM_TILE_96x128:                                                          // (retired id: nearest member)
-    case FDM_TILE_128x128: return gemm_glds_launch_t<T, 128, 128, 2, 4, 3, 4>(a, s);  // 8 waves, 64x32 per wave
-    case FDM_TILE_64x64_S2: return gemm_glds_launch_t<T, 64, 64, 2, 4, 2, 4>(a, s);    // 32 KB -> 4 workgroups per CU
-    case FDM_TILE_32x64_S3: return gemm_glds_launch_t<T, 32, 64, 2, 2, 3, 2>(a, s);    // 4 waves, 16x32 per wave, 36 KB
-    case FDM_TILE_256x128:                                                           // (retired id: the lockstep loop on this tile)
-    case FDM_TILE_256x128_PP: return gemm_pp_launch_t<T, 256, 128, 4, 2, 3>(a, s);   // ping-pong loop, 64x64 per wave, 146 KB
-    case FDM_TILE_80x128: return gemm_glds_launch_t<T, 80, 128, 1, 8, 4, 4>(a, s);      // 8 waves, 80x16 per wave: 800 rows x 3072 = 240 workgroups
-    case FDM_TILE_64x128: return gemm_glds_launch_t<T, 64, 128, 2, 4, 4, 4>(a, s);      // 8 waves, 32x32 per wave
-    default: return gemm_glds_launch_t<T, 64, 64, 2, 4, 4, 4>(a, s);                    // FDM_TILE_64x64: 8 waves, 32x16 per wave
-  }
-}
-
-// Split kinds: a ring stage is twice as large (hi and lo planes of both operands), so the tile set is the part of the
-// one above whose ring fits 160 KB of LDS; other FDM_TILE_* values map to the nearest member.
-template <typename T>
-static hipError_t gemm_dispatch_split(const fdm_gemm_args& a, hipStream_t s) {
-  if (a.sched_fuse)
-    return gemm_sched_fuse_launch<T>(a, s);
-  const int tile_id = a.tile & FDM_TILE_ID_MASK;
-  if (a.ksplit > 1) return gemm_dispatch_ksplit<T>(a, tile_id, s);
-  const int want = tile_id > 0 ? tile_id : (a.batch2 >= 1 ? 0 : gemm_tile_override());
-  switch (want > 0 ? want : gemm_heuristic_tile(a, 2, true)) {
-    case FDM_TILE_64x64_S2: return gemm_glds_launch_t<T, 64, 64, 2, 4, 2, 4>(a, s);  // 64 KB -> 2 workgroups per CU
-    case FDM_TILE_32x64_S3: return gemm_glds_launch_t<T, 32, 64, 2, 2, 3, 2>(a, s);  // 72 KB -> 2 workgroups per CU
-    case FDM_TILE_128x64:
-    case FDM_TILE_128x64_S3: return gemm_glds_launch_t<T, 128, 64, 4, 2, 3, 4>(a, s);   // 144 KB
-    case FDM_TILE_128x128:
-    case FDM_TILE_96x128:
-    case FDM_TILE_256x128:
-    case FDM_TILE_256x128_PP: return gemm_glds_launch_t<T, 128, 128, 2, 4, 2, 4>(a, s);    // 128 KB, one tile in flight
-    case FDM_TILE_80x128: return gemm_glds_launch_t<T, 80, 128, 1, 8, 3, 4>(a, s);      // 156 KB
-    case FDM_TILE_64x128: return gemm_glds_launch_t<T, 64, 128, 2, 4, 3, 4>(a, s);      // 144 KB
-    default: return gemm_glds_launch_t<T, 64, 64, 2, 4, 4, 4>(a, s);                    // FDM_TILE_64x64: 128 KB ring
+  switch (gemm_resolve_tile(a)) {
+    case FDM_TILE_64x64_S2: return gemm_tile_launch<T, FDM_TILE_64x64_S2>(a, s);
+    case FDM_TILE_32x64_S3: return gemm_tile_launch<T, FDM_TILE_32x64_S3>(a, s);
+    case FDM_TILE_128x64: return gemm_tile_launch<T, FDM_TILE_128x64>(a, s);
+    case FDM_TILE_128x128: return gemm_tile_launch<T, FDM_TILE_128x128>(a, s);
+    case FDM_TILE_80x128: return gemm_tile_launch<T, FDM_TILE_80x128>(a, s);
+    case FDM_TILE_64x128: return gemm_tile_launch<T, FDM_TILE_64x128>(a, s);
+    case FDM_TILE_256x128_PP: return gemm_tile_launch<T, FDM_TILE_256x128_PP>(a, s);
+    default: return gemm_tile_launch<T, FDM_TILE_64x64>(a, s);
   }
 }
 

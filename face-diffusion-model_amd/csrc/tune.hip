@@ -5,6 +5,7 @@
 
 #include <unistd.h>
 
+#include "gemm_tiles.hpp"
 #include "plan.hpp"
 
 namespace {
@@ -138,29 +139,17 @@ int tune_tiles_impl(fdm_plan* P, void* stream) {
     }
     return FDM_OK;
   };
-  std::vector<int> cands = {FDM_TILE_64x64, FDM_TILE_64x64_S2, FDM_TILE_32x64_S3, FDM_TILE_128x64, FDM_TILE_128x128, FDM_TILE_80x128, FDM_TILE_64x128};
-  if (!split && P->R >= 1024) cands.push_back(FDM_TILE_256x128_PP);
+  std::vector<int> cands;      // every kernel of the plan's operand kind, in table order; the ping-pong tile from 1024 rows
+  for (const GemmTile& t : kGemmTiles)
+    if (gemm_tile_runs(t.id, split) == t.id && !(t.pp && P->R < 1024)) cands.push_back(t.id);
   // Which of them are worth a stopwatch is decided by a wave-quantisation model first.  What bounds these GEMMs is the
   // bytes a CU pulls from L2 into LDS: a BM x BN tile costs (BM + BN) * K * bytes-per-element (x planes)
   // and the busiest CU runs ceil(tiles / 256) of them (the whole grid is resident, or queued behind, at <= 160 KB / ring per CU),
   // on top of a fixed cost per kernel (~5 us: boundary, ring fill, epilogue; in-situ timings of profiles/README.md fit
   // 5 us + bytes / 70 GB/s within ~15 % for tiles up to 128x64; larger tiles run above the model).  Candidates modelled
   // more than 35 % above the best one are not timed.
-  struct Geo { int bm, bn, nst; };
-  auto geo = [&](int tile) -> Geo {
-    switch (tile) {
-      case FDM_TILE_64x64_S2: return {64, 64, 2};
-      case FDM_TILE_32x64_S3: return {32, 64, 3};
-      case FDM_TILE_128x64: return {128, 64, split ? 3 : 4};
-      case FDM_TILE_128x128: return {128, 128, split ? 2 : 3};
-      case FDM_TILE_80x128: return {80, 128, split ? 3 : 4};
-      case FDM_TILE_64x128: return {64, 128, split ? 3 : 4};
-      case FDM_TILE_256x128_PP: return {256, 128, 3};
-      default: return {64, 64, 4};
-    }
-  };
   auto modelled_us = [&](const fdm_gemm_args& a, int tile) {
-    const Geo g = geo(tile);
+    const GemmTile& g = gemm_tile(tile);
     const double planes = kd.planes, eb = kd.bytes;
     const long long tiles = (long long)((a.M + g.bm - 1) / g.bm) * ((a.N + g.bn - 1) / g.bn) * (a.batch > 0 ? a.batch : 1);
     const long long rounds = (tiles + 255) / 256;                                   // tiles on the busiest CU
@@ -178,15 +167,12 @@ int tune_tiles_impl(fdm_plan* P, void* stream) {
     for (int tile : cands) best_model = std::min(best_model, modelled_us(kv.second[0], tile));
     // the heuristic's own tile is `base`: timing it again as a candidate only lets noise "pick" it (the split kinds alias
     // several ids to one kernel: compare what the ids launch)
-    auto launched = [&](int tile) {
-      if (!split) return tile;
-      return tile == FDM_TILE_256x128_PP ? FDM_TILE_128x128 : tile;
-    };
-    const int heur = launched(fdm_gemm_heuristic_tile(&kv.second[0]));
+    auto launched = [&](int tile) { fdm_gemm_args a = kv.second[0]; a.tile = tile; return gemm_resolve_tile(a); };
+    const int heur = launched(0);
+    const unsigned form = (kv.second[0].ksplit > 1 ? TILE_KSPLIT : 0) | (kv.second[0].sched_fuse ? TILE_SCHED : 0);
     for (int tile : cands) {
       if (launched(tile) == heur) continue;
-      if (kv.second[0].ksplit > 1 && tile != FDM_TILE_64x64 && tile != FDM_TILE_64x64_S2 && tile != FDM_TILE_32x64_S3) continue;   // K-sliced sites
-      if (kv.second[0].sched_fuse && tile != FDM_TILE_256x128_PP && tile != FDM_TILE_64x64) continue;      // the scheduler-fused decoder has two forms: 64x64 and the ping-pong tile
+      if (!gemm_tile_can(tile, form)) continue;      // K-sliced sites and the scheduler-fused decoder run on their own tile sets
       if (modelled_us(kv.second[0], tile) > 1.35 * best_model) continue;
       float t = 0.f;
       FCK(timed(inst, tile, &t));

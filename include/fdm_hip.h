@@ -268,7 +268,8 @@ typedef struct fdm_gemm_args {
 #define FDM_TILE_ID_MASK 0xff
 int fdm_op_gemm(const fdm_gemm_args* a, void* stream);
 /* The FDM_TILE_* value a launch of *a with tile = 0 resolves to (the library heuristic on M, N, K, batch and the operand kind;
- * no device work, a->tile is ignored).  The plan-time tuner uses it to leave the heuristic's own tile out of its candidates. */
+ * no device work, a->tile is ignored).  What each id runs -- geometry, ring depths, launch forms, retired ids -- is the one table of
+ * csrc/gemm_tiles.hpp; the plan-time tuner leaves the heuristic's own kernel out of its candidates with that header's resolver. */
 int fdm_gemm_heuristic_tile(const fdm_gemm_args* a);
 
 /* ------------------------------------------------------------------------------------------

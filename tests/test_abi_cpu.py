@@ -295,3 +295,39 @@ def test_tile_heuristic_is_a_pure_function_of_the_shape():
     # round 5 (loader-wave build, profiles/r5_tile_sweep/): a half-empty last round of 128x128 -> 128x64; narrow outputs on one round of 64x128
     assert tile(B, 3200, 3072, 1024) == _lib.TILE_128x64 and tile(B, 2400, 512, 1024) == _lib.TILE_64x128 and tile(S, 800, 1536, 512) == _lib.TILE_64x128
     assert tile(S, 1600, 3072, 1024) == _lib.TILE_80x128 and tile(S, 2400, 3072, 1024) == _lib.TILE_128x128
+
+
+def test_tile_checks_refuse_only_outside_their_sets():
+    """K-sliced and second-batch-level launches run on their own tile sets (the capability flags of csrc/gemm_tiles.hpp): every id
+    0..12, with and without FDM_TILE_LOCKSTEP, is refused with the form's message exactly outside the set -- retired ids included.
+    Recorded, so nothing is launched; what becomes of an accepted launch is not asserted."""
+    from fdm_amd import _lib
+    l = _lib.lib()
+
+    def ksplit(tile):
+        a = _lib.GemmArgs()
+        a.A, a.W, a.M, a.N, a.K, a.dtype, a.lda, a.ldw, a.out_f32, a.ldo_f32, a.ldr, a.ldo_t = 16, 16, 64, 128, 256, _lib.BF16, 256, 256, 16, 128, 128, 128
+        a.batch, a.ksplit, a.ksplit_stride, a.tile = 1, 2, 64 * 128, tile
+        return a
+
+    def batch2(tile):
+        a = _lib.GemmArgs()
+        a.A, a.W, a.M, a.N, a.K, a.dtype, a.lda, a.ldw, a.out_f32, a.ldo_f32, a.ldr, a.ldo_t = 16, 16, 16, 64, 64, _lib.BF16, 64, 64, 16, 1024, 1024, 1024
+        a.batch, a.batch2, a.a_batch_stride, a.w_batch_stride, a.out_batch_stride, a.a_batch_stride2, a.out_batch_stride2, a.tile = 16, 4, 16 * 64, 64 * 64, 64, 16 * 16 * 64, 16 * 1024, tile
+        return a
+    forms = ((ksplit, b"ksplit runs on the 64-column tiles", {0, _lib.TILE_64x64, _lib.TILE_64x64_S2, _lib.TILE_32x64_S3}),
+             (batch2, b"batch2 runs on the 64-column tiles", {0, _lib.TILE_64x64, _lib.TILE_64x64_S2, _lib.TILE_128x64}))
+    h = C.c_void_p()
+    assert l.fdm_prog_create(C.byref(h)) == 0 and l.fdm_prog_begin(h) == 0
+    try:
+        for make, msg, allowed in forms:
+            for tid in range(13):
+                for flag in (0, 0x200):                          # FDM_TILE_LOCKSTEP
+                    a = make(tid | flag)
+                    rc = l.fdm_op_gemm(C.byref(a), None)
+                    refused = rc != 0 and msg in l.fdm_last_error()
+                    assert refused == (tid not in allowed), (msg, tid, flag, rc, l.fdm_last_error())
+                    if refused:
+                        assert rc == -1 and (b"not tile %d" % tid) in l.fdm_last_error()
+    finally:
+        assert l.fdm_prog_end(h) == 0 and l.fdm_prog_destroy(h) == 0
