@@ -7,7 +7,8 @@ import os
 import numpy as np
 import torch
 
-from . import presets
+from . import presets, schedule
+from ._lib import SLOT_FINISHED, FdmError
 from .modules import (FDM, ClassifierFreeSampleModel, FDMBiwi, FDMMead, GaussianDiffusion, VQAutoEncoder)
 
 EMOTIONS = ["angry", "contempt", "disgusted", "fear", "happy", "sad", "surprised"]     # demo/demo_3d_mead.py:118
@@ -51,6 +52,12 @@ def load_pcm(path):
     return x, int(rate)
 
 
+def _on_stream(device):
+    """(torch.device, (its name, the current stream on it)): what every plan cache below starts its key with."""
+    dv = torch.device(device)
+    return dv, (str(dv), torch.cuda.current_stream(dv).cuda_stream)
+
+
 _FRONTENDS = {}      # (device, stream) -> hubert.FrontendPlan holding every rate seen there so far
 
 
@@ -59,8 +66,7 @@ def _frontend(rates, device):
     rate it has not seen replaces it by a plan for the union (16 kHz needs no table), so what the process keeps is bounded by the
     distinct rates it meets, not by their combinations."""
     from .hubert import FrontendPlan
-    dv = torch.device(device)
-    key = (str(dv), torch.cuda.current_stream(dv).cuda_stream)
+    key = _on_stream(device)[1]
     want = {int(r) for r in rates} - {16000}
     plan = _FRONTENDS.get(key)
     if plan is None or not want <= set(plan.rates):
@@ -71,7 +77,6 @@ def _frontend(rates, device):
 def _pcm_tensor(pcm, device):
     """A raw PCM array or tensor on `device`, dtype kept.  A CPU TENSOR is refused as everywhere on the HIP path (the caller's numpy
     array is the host input and is uploaded as it is: no arithmetic happens on the host)."""
-    from ._lib import FdmError
     if torch.device(device).type != "cuda":
         raise FdmError("prepare_audio runs on the HIP path only (no CPU fallback)")
     if isinstance(pcm, torch.Tensor):
@@ -105,9 +110,9 @@ def _mesh_plan(faces, V, device):
     _frontend() keeps front ends: what the process holds is bounded by the distinct meshes it meets."""
     import hashlib
     from .mesh import MeshOutPlan, faces_array
-    dv = torch.device(device)
+    dv, at = _on_stream(device)
     f = faces_array(faces)
-    key = (str(dv), torch.cuda.current_stream(dv).cuda_stream, int(V), hashlib.sha1(f.tobytes()).hexdigest())
+    key = at + (int(V), hashlib.sha1(f.tobytes()).hexdigest())
     plan = _MESH_PLANS.get(key)
     if plan is None:
         _MESH_PLANS[key] = plan = MeshOutPlan(f, V, dv)
@@ -129,6 +134,25 @@ def _split_mesh(mf):
     return [type(mf)(mf.positions[b:b + 1, :n], None if mf.normals is None else mf.normals[b:b + 1, :n], [n]) for b, n in enumerate(mf.frames)]
 
 
+def _pack_offsets(offsets, frames, device, who):
+    """What to_mesh / to_rig hand their plan: (x [B, L_max, 3 V] on the device, frames per clip, whether `offsets` was a list).  A
+    ragged list of [1, L_b, 3 V] / [L_b, 3 V] clips is packed into one zero-padded batch with frames = its own lengths; a tensor
+    goes as it is with the caller's `frames`.  Host tensors or a host `device` are refused in the name of `who`."""
+    many = isinstance(offsets, (list, tuple))
+    if many:
+        clips = [o.reshape(-1, o.shape[-1]) for o in offsets]
+        frames = [int(c.shape[0]) for c in clips]
+        x = torch.zeros(len(clips), max(frames + [1]), clips[0].shape[-1], device=clips[0].device)
+        for b, c in enumerate(clips):
+            x[b, :frames[b]] = c
+    else:
+        x = offsets if offsets.dim() == 3 else offsets.unsqueeze(0)
+    dv = x.device if device is None else torch.device(device)
+    if dv.type != "cuda" or not x.is_cuda:
+        raise FdmError(f"{who} runs on the HIP path only (no CPU fallback)")
+    return x.to(dv), frames, many
+
+
 @torch.no_grad()
 def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, interleaved=False, half=False, device=None):
     """Vertex offsets (what the decoder writes; or vertices, with template=None) -> mesh.MeshFrames: positions = offsets + template,
@@ -137,22 +161,10 @@ def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, 
     offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None: all L) -> one MeshFrames for the batch; or a
     ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of MeshFrames, each cut to its own frames and bit for bit what its
     own call returns.  template: [1 or B, 3 V], or for a list one per clip.  normals / interleaved / half: the output options."""
-    many = isinstance(offsets, (list, tuple))
-    if many:
-        clips = [o.reshape(-1, o.shape[-1]) for o in offsets]
-        frames = [int(c.shape[0]) for c in clips]
-        x = torch.zeros(len(clips), max(frames + [1]), clips[0].shape[-1], device=clips[0].device)
-        for b, c in enumerate(clips):
-            x[b, :frames[b]] = c
-        if isinstance(template, (list, tuple)):
-            template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
-    else:
-        x = offsets if offsets.dim() == 3 else offsets.unsqueeze(0)
-    dv = x.device if device is None else torch.device(device)
-    if dv.type != "cuda" or not x.is_cuda:
-        from ._lib import FdmError
-        raise FdmError("to_mesh runs on the HIP path only (no CPU fallback)")
-    mf = _mesh_plan(faces, x.shape[-1] // 3, dv).forward(x.to(dv), frames, template, fps, normals, interleaved, half)
+    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
+        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
+    x, frames, many = _pack_offsets(offsets, frames, device, "to_mesh")
+    mf = _mesh_plan(faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, interleaved, half)
     return _split_mesh(mf) if many else mf
 
 
@@ -165,14 +177,13 @@ def _rig_plan(rig, device):
     arguments otherwise) or the dict of RigPlan's arguments (every call then digests the basis to recognise it: animate_many,
     animate_long and SlotServer come here once and go on with the plan)."""
     from .rig import RigPlan, identity
-    dv = torch.device(device)
-    stream = torch.cuda.current_stream(dv).cuda_stream
+    dv, at = _on_stream(device)
     mine = isinstance(rig, RigPlan)
-    key = (str(dv), stream, rig.key if mine else identity(**rig))
+    key = at + (rig.key if mine else identity(**rig),)
     plan = _RIG_PLANS.get(key)
     if plan is None:
         if mine:
-            plan = rig if (rig.device == dv and rig.stream == stream) else RigPlan(device=dv, **rig.arguments())
+            plan = rig if (rig.device == dv and rig.stream == at[1]) else RigPlan(device=dv, **rig.arguments())
         else:
             plan = RigPlan(device=dv, **rig)
         _RIG_PLANS[key] = plan
@@ -194,21 +205,9 @@ def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bound
     all L) -> one RigFrames for the batch; or a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of RigFrames, each cut to
     its own frames and bit for bit what its own call returns."""
     from .rig import RigPlan
-    many = isinstance(offsets, (list, tuple))
-    if many:
-        clips = [o.reshape(-1, o.shape[-1]) for o in offsets]
-        frames = [int(c.shape[0]) for c in clips]
-        x = torch.zeros(len(clips), max(frames + [1]), clips[0].shape[-1], device=clips[0].device)
-        for b, c in enumerate(clips):
-            x[b, :frames[b]] = c
-    else:
-        x = offsets if offsets.dim() == 3 else offsets.unsqueeze(0)
-    dv = x.device if device is None else torch.device(device)
-    if dv.type != "cuda" or not x.is_cuda:
-        from ._lib import FdmError
-        raise FdmError("to_rig runs on the HIP path only (no CPU fallback)")
+    x, frames, many = _pack_offsets(offsets, frames, device, "to_rig")
     rig = basis if isinstance(basis, (RigPlan, dict)) else dict(basis=basis, weights=weights, ridge=ridge, bounds=bounds, sweeps=sweeps, names=names)
-    rf = _rig_plan(rig, dv).forward(x.to(dv), frames, fps)
+    rf = _rig_plan(rig, x.device).forward(x, frames, fps)
     return _split_rig(rf) if many else rf
 
 
@@ -242,12 +241,123 @@ def build_models(preset="vocaset", feature_dim=None, device="cuda:0", stage1=Non
     return diffusion, ae
 
 
-def _clip_x_T(shape, S, seed):
-    """DDPM start of a sampling call: one x_T per CLIP from a CPU generator seeded with `seed` (the DDIM branch draws it the
-    same way), shared by the clip's S conditions -- so `seed=` reproduces a call, and the sequential S = 1 calls of a style loop
-    start where the batched call starts."""
-    x = torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
-    return x.repeat_interleave(S, dim=0) if S > 1 else x
+# ---- one request path: what animate, animate_many, animate_long and SlotServer all do, stated once -------------------------------
+def _unwrap(diffusion):
+    """(model, preset, cfg, scale) of a GaussianDiffusion: cfg = it wraps a ClassifierFreeSampleModel (classifier-free guidance at
+    that model's level); scale is 2.5 without guidance, where nothing reads it."""
+    cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
+    model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
+    return model, model.preset, cfg, float(diffusion.denoise_fn.level) if cfg else 2.5
+
+
+def _per(x, b):
+    """Entry b of an argument given per clip (a list), or the one value given for all."""
+    return x[b] if isinstance(x, (list, tuple)) else x
+
+
+def _waveform(audio, rate, device):
+    """One call's audio as [B, n] fp32 on `device` ([n] is one clip); rate: it is ONE raw PCM clip, through the front end first."""
+    if rate is not None:
+        audio = prepare_audio(audio, rate, device=device)
+    audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
+    return audio.unsqueeze(0) if audio.dim() == 1 else audio
+
+
+def _waveforms(audios, rate, device, upload=True):
+    """A list of clips as [n_b] fp32 tensors; rate (one for all, or a list): they are raw PCM, through the front end in ONE call.
+    upload=False leaves a host waveform where it is (encode_many packs the clips into its own device batch)."""
+    if rate is not None:
+        wav, lens = prepare_audio_many(audios, rate, device=device)
+        audios = [wav[b, :lens[b]] for b in range(len(audios))]
+    return [torch.as_tensor(a, dtype=torch.float32, device=device if upload else None).reshape(-1) for a in audios]
+
+
+_STYLE_DEFAULT = 0        # eye(n_style)[:1]: the first subject, the one-hot the demos are written with (demo/demo_vocaset.py:88)
+_EMOTION_DEFAULT = 4      # eye(n_emo)[4:5]: EMOTIONS[4], "happy" -- the default of the demo's --emotion
+
+
+def _condition(x, width, default, rows, device=None):
+    """A style or emotion argument as the fp32 [rows, width] tensor the samplers take, on `device` (None: where it is): None is row
+    `default` of the identity, [width] / [1, width] is that one row for every row (expanded, not copied), [r, width] stays as it is."""
+    x = torch.eye(width)[default:default + 1] if x is None else x
+    x = torch.as_tensor(x, dtype=torch.float32, device=device).reshape(-1, width)
+    return x.expand(rows, -1) if (x.shape[0] == 1 and rows > 1) else x
+
+
+def _start_noise(shape, seed):
+    """x_T of a request: ONE draw of `shape` from a CPU generator seeded with `seed`, so `seed=` reproduces a call on any device.
+    The shape is the caller's: [B, n, c] drawn at once is not the bits of B draws of [1, n, c]."""
+    return torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
+
+
+def _sampler_definition(p, ddim_steps, sampler, sampler_steps, eta, ddim_on_emotion=False):
+    """The sampler of a request as a hashable definition: sampler= ("dpmpp2m" | "ddim_eta" with eta=, sampler_steps), else ddim_steps,
+    else the DDPM chain.  animate, animate_many and SlotServer ignore ddim_steps on a preset with an emotion input (the reference
+    samples those with DDPM only); animate_long honours it on every preset: ddim_on_emotion=True."""
+    if sampler:
+        return ("tables", str(sampler), int(sampler_steps), float(eta))
+    if ddim_steps and (ddim_on_emotion or not p.n_emo):
+        return ("ddim", int(ddim_steps))
+    return ("ddpm",)
+
+
+def _sampler_args(key, diffusion):
+    """A definition as the kind / steps / t_list / tables arguments of the plan (sample_windows, open_slots, add_sampler)."""
+    if key[0] == "tables":
+        t_list, tables = schedule.sampler_tables(key[1], key[2], key[3], diffusion.num_timesteps)
+        return dict(kind="tables", t_list=t_list, tables=tables)
+    if key[0] == "ddim":
+        return dict(kind="ddim", steps=key[1])
+    ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
+    return dict(kind="ddpm", t_list=ts)
+
+
+def _sample(diffusion, key, audio, shape, cond, x_T, seed, clip0=0, **tracks):
+    """One sampling call of a definition through the GaussianDiffusion methods; cond = (style,) or (emotion, style)."""
+    if key[0] == "tables":
+        return diffusion.fast_sample(audio, shape, *cond, steps=key[2], sampler=key[1], eta=key[3], seed=seed, x_T=x_T, clip0=clip0, **tracks)
+    if key[0] == "ddim":      # (noise-free: no seed, no clip index)
+        return diffusion.ddim_sample(audio, shape, cond[-1], key[1], x_T=x_T, **tracks)
+    return diffusion.sample(audio, shape, *cond, seed=seed, x_T=x_T, clip0=clip0, **tracks)
+
+
+def _quantise(autoencoder, p, latent, emo=None, emotion_track=None):
+    """z_q of a latent: every frame in the codebook of the clip's emotion (of its own emotion with a track) where the preset has one."""
+    if p.n_emo:
+        return autoencoder.quant(latent, emo, stats=False, emotion_track=emotion_track)[0]
+    return autoencoder.quant(latent, stats=False)[0]
+
+
+def _template_rows(template, width, device, S=1, B=1):
+    """template [1 or B, width] (any shape of that many numbers) as fp32 rows on `device`; with S > 1 conditions per clip, a
+    template per clip repeats per condition: rows in (clip, condition) order."""
+    tp = torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, width)
+    return tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp
+
+
+def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1):
+    """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
+    template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair."""
+    rf = None if rig is None else to_rig(out, rig, fps=fps)
+    if faces is None and rf is not None:
+        return rf
+    tp = None if template is None else _template_rows(template, out.shape[-1], device, S, B)
+    if faces is None:
+        return out if tp is None else out + tp.unsqueeze(1)
+    mf = to_mesh(out, faces, tp, fps=fps, **(mesh or {}))
+    return mf if rf is None else (mf, rf)
+
+
+def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None):
+    """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip: ONE mesh call and ONE rig call
+    over the unequal lengths, each result bit for bit its own call's."""
+    if faces is None and rig is None:
+        return clips if templates is None else [c + _template_rows(t, c.shape[-1], device).unsqueeze(1) for c, t in zip(clips, templates)]
+    res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
+    if rig is not None:
+        fits = to_rig(clips, rig, fps=fps)
+        res = fits if res is None else list(zip(res, fits))
+    return res
 
 
 @torch.no_grad()
@@ -285,17 +395,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     Philox keyed by (seed, ROW = clip * S + condition, step), so a sequential call (row 0) draws the stream of the batched call's
     row 0 only: the other conditions differ from their sequential calls by that stream -- equal in distribution (the reference's
     sequential calls draw from one running generator), not bit for bit."""
-    model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
-    p = model.preset
-    if rate is not None:
-        audio = prepare_audio(audio, rate, device=device)
-    audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
-    if audio.dim() == 1:
-        audio = audio.unsqueeze(0)
+    model, p, _, _ = _unwrap(diffusion)
+    audio = _waveform(audio, rate, device)
     B = audio.shape[0]
-    if id_one_hot is None:
-        id_one_hot = torch.eye(p.n_style)[:1].expand(B, -1)
-    id_one_hot = id_one_hot.reshape(-1, id_one_hot.shape[-1]).to(device)
+    # the default style is a row per clip; a style that was given counts with the rows it has
+    id_one_hot = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B if id_one_hot is None else 1, device)
     rows = max(id_one_hot.shape[0], 1 if emotion_one_hot is None else emotion_one_hot.reshape(-1, emotion_one_hot.shape[-1]).shape[0], B)
     if rows % B:
         raise ValueError(f"{rows} condition rows for {B} clips")
@@ -310,48 +414,20 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
         if emotion_track is not None and not p.n_emo:
             raise ValueError(f"preset {p.name} takes no emotion")
         trk = dict(style_track=style_track)
+    cond, et = (id_one_hot,), None
     if p.n_emo:
         if trk:
             trk["emotion_track"] = emotion_track
-        if emotion_one_hot is None:
-            emotion_one_hot = torch.eye(p.n_emo)[4:5].expand(rows, -1)
-        emotion_one_hot = emotion_one_hot.reshape(-1, emotion_one_hot.shape[-1]).to(device)
-        if emotion_one_hot.shape[0] == 1 and rows > 1:
-            emotion_one_hot = emotion_one_hot.expand(rows, -1)
-        if id_one_hot.shape[0] == 1 and rows > 1:
-            id_one_hot = id_one_hot.expand(rows, -1)
-        if sampler:
-            latent = diffusion.fast_sample(audio, shape, emotion_one_hot, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta,
-                                           seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
-        else:
-            latent = diffusion.sample(audio, shape, emotion_one_hot, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
+        emotion_one_hot = _condition(emotion_one_hot, p.n_emo, _EMOTION_DEFAULT, rows, device)
+        cond = (emotion_one_hot, _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, rows))       # a one-row style rides every row
         et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L, :]
-        quanted, _, _ = autoencoder.quant(latent, emotion_one_hot, stats=False, emotion_track=et)
-    else:
-        if sampler:
-            latent = diffusion.fast_sample(audio, shape, id_one_hot, steps=sampler_steps, sampler=sampler, eta=eta, seed=seed,
-                                           x_T=_clip_x_T(shape, S, seed), **trk)
-        elif ddim_steps:
-            g = torch.Generator(device="cpu").manual_seed(seed)
-            x_T = torch.randn(shape, generator=g).repeat_interleave(S, dim=0)
-            latent = diffusion.ddim_sample(audio, shape, id_one_hot, ddim_steps, x_T=x_T, **trk)
-        else:
-            latent = diffusion.sample(audio, shape, id_one_hot, seed=seed, x_T=_clip_x_T(shape, S, seed), **trk)
-        quanted, _, _ = autoencoder.quant(latent, stats=False)
-    out = autoencoder.decode(quanted)
-    rf = None if rig is None else to_rig(out, rig, fps=_mesh_fps(p, in_fps, out_fps))
-    if faces is not None:
-        tp = None if template is None else torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, out.shape[-1])
-        if tp is not None and S > 1 and tp.shape[0] == B and B > 1:
-            tp = tp.repeat_interleave(S, dim=0)
-        mf = to_mesh(out, faces, tp, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))
-        return (mf if rf is None else (mf, rf)), latent
-    if rf is not None:
-        return rf, latent
-    if template is not None:
-        tp = torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
-        out = out + (tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp)
-    return out, latent
+    # one x_T per CLIP, shared by the clip's S conditions: the sequential S = 1 calls of a style loop start where this call starts
+    x_T = _start_noise(shape, seed)
+    key = _sampler_definition(p, ddim_steps, sampler, sampler_steps, eta)
+    latent = _sample(diffusion, key, audio, shape, cond, x_T.repeat_interleave(S, dim=0) if S > 1 else x_T, seed, **trk)
+    out = autoencoder.decode(_quantise(autoencoder, p, latent, emotion_one_hot, et))
+    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
+    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B), latent
 
 
 @torch.no_grad()
@@ -388,35 +464,30 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     style_track / emotion_track: per-frame conditions as in animate(), one per clip: a list with a track [L', n] (L' >= the clip's
     frames) or None per clip, or one track for all.  A group with a track in it is sampled and quantised with tracks throughout (a
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
-    model = diffusion.denoise_fn.model if isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel) else diffusion.denoise_fn
-    p = model.preset
+    model, p, _, _ = _unwrap(diffusion)
     rig = None if rig is None else _rig_plan(rig, device)        # a dict is digested and made into a plan once, not per group
     n = len(audios)
-    if rate is not None:
-        wav_b, lens_b = prepare_audio_many(audios, rate, device=device)
-        audios = [wav_b[b, :lens_b[b]] for b in range(n)]
-    wavs = [torch.as_tensor(a, dtype=torch.float32, device=device).reshape(1, -1) for a in audios]
+    wavs = _waveforms(audios, rate, device)
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
-        hubs = model.audio_encoder.encode_many([w[0] for w in wavs], device)
+        hubs = model.audio_encoder.encode_many(wavs, device)
     else:
-        hubs = [model.audio_encoder(w).last_hidden_state for w in wavs]             # [1, N_b, fw] each, own length
+        hubs = [model.audio_encoder(w.reshape(1, -1)).last_hidden_state for w in wavs]             # [1, N_b, fw] each, own length
     Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
+    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
 
     def row(x, b, width, default):
-        if x is None:
-            return default
-        x = torch.as_tensor(x[b] if isinstance(x, (list, tuple)) else x, dtype=torch.float32).reshape(-1, width)
+        """clip b's condition [1, width]: its entry of a list, its row of one [n, width] tensor, or the one row given for all"""
+        x = _condition(_per(x, b), width, default, 1)
         return x[b:b + 1] if x.shape[0] == n else x[:1]
-    per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
 
     def group_track(tr, vecs, grp, Lmax, width):
         """[len(grp), Lmax, width]: clip i's track on its own frames (its last row repeated on the tail rows, which belong to no
         frame), its one-hot on every frame when it has no track; None when no clip of the group has a track"""
-        if not width or all(per(tr, b) is None for b in grp):
+        if not width or all(_per(tr, b) is None for b in grp):
             return None
         out = vecs.reshape(len(grp), 1, width).expand(len(grp), Lmax, width).clone()
         for i, b in enumerate(grp):
-            t = per(tr, b)
+            t = _per(tr, b)
             if t is not None:
                 t = torch.as_tensor(t, dtype=torch.float32).reshape(-1, width)
                 if t.shape[0] < Ls[b]:
@@ -424,8 +495,8 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                 out[i, :Ls[b]] = t[:Ls[b]].to(out.device)
                 out[i, Ls[b]:] = out[i, Ls[b] - 1]
         return out
-    ddim = bool(ddim_steps) and not p.n_emo and not sampler
-    order = sorted(range(n), key=lambda b: Ls[b]) if ddim else list(range(n))
+    key = _sampler_definition(p, ddim_steps, sampler, sampler_steps, eta)
+    order = sorted(range(n), key=lambda b: Ls[b]) if key[0] == "ddim" else list(range(n))
     verts, lats = [None] * n, [None] * n
     prev = (model._hub_key, model._hub)
     try:
@@ -439,55 +510,34 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             x_T = torch.zeros(len(grp), Lmax * p.G, p.c)
             for i, b in enumerate(grp):
                 hub[i, :hubs[b].shape[1]] = hubs[b][0]
-                gen = torch.Generator(device="cpu").manual_seed(seed)                 # what animate() draws for this clip alone
-                x_T[i, :Ls[b] * p.G] = torch.randn((1, Ls[b] * p.G, p.c), generator=gen)[0]
-            ids = torch.cat([row(id_one_hots, b, p.n_style, torch.eye(p.n_style)[:1]) for b in grp]).to(device)
+                x_T[i, :Ls[b] * p.G] = _start_noise((1, Ls[b] * p.G, p.c), seed)[0]      # what animate() draws for this clip alone
+            ids = torch.cat([row(id_one_hots, b, p.n_style, _STYLE_DEFAULT) for b in grp]).to(device)
             model.set_audio_features(hub)
             dummy = torch.zeros(len(grp), 1, device=device)
             shape = (len(grp), Lmax * p.G, p.c)
-            if p.n_emo:
-                emos = torch.cat([row(emotion_one_hots, b, p.n_emo, torch.eye(p.n_emo)[4:5]) for b in grp]).to(device)
+            emos = torch.cat([row(emotion_one_hots, b, p.n_emo, _EMOTION_DEFAULT) for b in grp]).to(device) if p.n_emo else None
             st_g = group_track(style_track, ids, grp, Lmax, p.n_style)
             et_g = group_track(emotion_track, emos, grp, Lmax, p.n_emo) if p.n_emo else None
             trk = {}
             if st_g is not None or et_g is not None:
                 trk = dict(style_track=st_g, emotion_track=et_g) if p.n_emo else dict(style_track=st_g)
-            if sampler:
-                lat = diffusion.fast_sample(dummy, shape, *((emos, ids) if p.n_emo else (ids,)), steps=sampler_steps, sampler=sampler,
-                                            eta=eta, seed=seed, x_T=x_T, clip0=g0, **trk)
-            elif p.n_emo:
-                lat = diffusion.sample(dummy, shape, emos, ids, seed=seed, x_T=x_T, clip0=g0, **trk)
-            elif ddim_steps:
-                lat = diffusion.ddim_sample(dummy, shape, ids, ddim_steps, x_T=x_T, **trk)
-            else:
-                lat = diffusion.sample(dummy, shape, ids, seed=seed, x_T=x_T, clip0=g0, **trk)
+            lat = _sample(diffusion, key, dummy, shape, (emos, ids) if p.n_emo else (ids,), x_T, seed, clip0=g0, **trk)
             outs, offs = None, []
             if batch_stages:        # one padded quant (per row) and one decode that knows each clip's length
                 lat_g = lat[:, :max(Ls[b] for b in grp) * p.G].contiguous()        # (not the bucket's rows: they belong to no clip)
                 etq = None if et_g is None else et_g[:, :lat_g.shape[1] // p.G]
-                qs = autoencoder.quant(lat_g, emos, stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lat_g, stats=False)[0]
-                outs = autoencoder.decode_many(qs, [Ls[b] for b in grp])
+                outs = autoencoder.decode_many(_quantise(autoencoder, p, lat_g, emos, etq), [Ls[b] for b in grp])
             for i, b in enumerate(grp):
-                lb = lat[i:i + 1, :Ls[b] * p.G].contiguous()
+                lats[b] = lat[i:i + 1, :Ls[b] * p.G].contiguous()
                 if outs is not None:
-                    out = outs[i:i + 1, :Ls[b]].contiguous()
+                    offs.append(outs[i:i + 1, :Ls[b]].contiguous())
                 else:
                     etq = None if et_g is None else et_g[i:i + 1, :Ls[b]]
-                    q = autoencoder.quant(lb, emos[i:i + 1], stats=False, emotion_track=etq)[0] if p.n_emo else autoencoder.quant(lb, stats=False)[0]
-                    out = autoencoder.decode(q)
-                if faces is not None or rig is not None:
-                    offs.append(out)
-                elif templates is not None:
-                    tp = templates[b] if isinstance(templates, (list, tuple)) else templates
-                    out = out + torch.as_tensor(tp, dtype=torch.float32, device=device).reshape(1, 1, -1)
-                verts[b], lats[b] = out, lb
-            if faces is not None:       # the group's clips, each at its own length, through one hand-off call
-                tps = None if templates is None else [per(templates, b) for b in grp]
-                for b, mf in zip(grp, to_mesh(offs, faces, tps, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))):
-                    verts[b] = mf
-            if rig is not None:         # and through one rig hand-off call
-                for b, rf in zip(grp, to_rig(offs, rig, fps=_mesh_fps(p, in_fps, out_fps))):
-                    verts[b] = rf if faces is None else (verts[b], rf)
+                    offs.append(autoencoder.decode(_quantise(autoencoder, p, lats[b], emos[i:i + 1] if p.n_emo else None, etq)))
+            # the group's clips, each at its own length, through one mesh and one rig hand-off call
+            tps = None if templates is None else [_per(templates, b) for b in grp]
+            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps)):
+                verts[b] = v
     finally:
         model._hub_key, model._hub = prev
     return verts, lats
@@ -513,25 +563,12 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     bit-identical to animate()'s.  DDIM (eta = 0) when ddim_steps, on every preset; classifier-free guidance when `diffusion`
     wraps a ClassifierFreeSampleModel.  sampler / sampler_steps / eta: as animate() (the history of the multistep solver is the
     blended x0 in the long layout)."""
-    cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
-    model = diffusion.denoise_fn.model if cfg else diffusion.denoise_fn
-    scale = float(diffusion.denoise_fn.level) if cfg else 2.5
-    p = model.preset
+    model, p, cfg, scale = _unwrap(diffusion)
     rig = None if rig is None else _rig_plan(rig, device)
-    if rate is not None:
-        audio = prepare_audio(audio, rate, device=device)
-    audio = torch.as_tensor(audio, dtype=torch.float32, device=device)
-    if audio.dim() == 1:
-        audio = audio.unsqueeze(0)
+    audio = _waveform(audio, rate, device)
     B = audio.shape[0]
-    style = (torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32))
-    style = style.reshape(-1, p.n_style).expand(B, -1) if style.reshape(-1, p.n_style).shape[0] == 1 else style.reshape(-1, p.n_style)
-    emo = None
-    if p.n_emo:
-        emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32)
-        emo = emo.reshape(-1, p.n_emo)
-        emo = (emo.expand(B, -1) if emo.shape[0] == 1 else emo).to(device)
-    style = style.to(device)
+    style = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B, device)
+    emo = _condition(emotion_one_hot, p.n_emo, _EMOTION_DEFAULT, B, device) if p.n_emo else None
     hub = model.audio_features(audio)
     L_total = hub.shape[1] // p.pair
     plan = model.plan(hub.device)
@@ -539,29 +576,12 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     # style_track / emotion_track [L', n] or [B, L', n], L' >= L_total: one vector per latent frame of the whole recording (animate())
     plan.prepare_windows(hub, style, emo, L_total=L_total, window=window, overlap=overlap, cfg=cfg, style_track=style_track,
                          emotion_track=emotion_track)
-    shape = (B, L_total * p.G, p.c)
-    x_T = torch.randn(shape, generator=torch.Generator(device="cpu").manual_seed(seed))
-    if sampler:
-        from . import schedule
-        t_list, tables = schedule.sampler_tables(sampler, sampler_steps, eta, diffusion.num_timesteps)
-        latent = plan.sample_windows(x_T, "tables", t_list=t_list, tables=tables, seed=seed, cfg_scale=scale)
-    elif ddim_steps:
-        latent = plan.sample_windows(x_T, "ddim", steps=ddim_steps, cfg_scale=scale)
-    else:
-        ts = list(range(diffusion.num_timesteps - 1, -1, -1)) if diffusion.full_chain else list(range(999, 499, -1))
-        latent = plan.sample_windows(x_T, "ddpm", t_list=ts, seed=seed, cfg_scale=scale)
+    key = _sampler_definition(p, ddim_steps, sampler, sampler_steps, eta, ddim_on_emotion=True)
+    latent = plan.sample_windows(_start_noise((B, L_total * p.G, p.c), seed), seed=seed, cfg_scale=scale, **_sampler_args(key, diffusion))
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
-    quanted = autoencoder.quant(latent, emo, stats=False, emotion_track=et)[0] if p.n_emo else autoencoder.quant(latent, stats=False)[0]
-    out = autoencoder.decode(quanted)
-    rf = None if rig is None else to_rig(out, rig, fps=_mesh_fps(p, in_fps, out_fps))
-    if faces is not None:
-        mf = to_mesh(out, faces, template, fps=_mesh_fps(p, in_fps, out_fps), **(mesh or {}))
-        return (mf if rf is None else (mf, rf)), latent
-    if rf is not None:
-        return rf, latent
-    if template is not None:
-        out = out + torch.as_tensor(template, dtype=torch.float32, device=device).reshape(-1, 1, out.shape[-1])
-    return out, latent
+    out = autoencoder.decode(_quantise(autoencoder, p, latent, emo, et))
+    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
+    return _hand_off(out, template, device, faces, mesh, rig, fps), latent
 
 
 class SlotServer:
@@ -602,21 +622,19 @@ class SlotServer:
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
                  faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
-        from . import schedule
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.faces, self.mesh = faces, dict(mesh or {})
         self.rig = None if rig is None else _rig_plan(rig, device)     # a dict is digested and made into a plan once, not per finished clip
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
         self.batched_decodes = []                   # clips per batched decode, in call order
-        self.cfg = isinstance(diffusion.denoise_fn, ClassifierFreeSampleModel)
-        self.model = diffusion.denoise_fn.model if self.cfg else diffusion.denoise_fn
-        p = self.p = self.model.preset
+        self.model, p, self.cfg, self.scale = _unwrap(diffusion)
+        self.p = p
         self.mesh_fps = _mesh_fps(p, in_fps, out_fps) if faces is not None or rig is not None else None
         self.n_slots = int(slots)
         self.L = min(int(max_frames), p.max_len) if max_frames else p.max_len
         self.plan = self.model.plan(device)
         self.model._prep_key = None           # the plan leaves the state FDM.prepare() cached
-        kw = dict(cfg=self.cfg, cfg_scale=float(diffusion.denoise_fn.level) if self.cfg else 2.5)
+        kw = dict(cfg=self.cfg, cfg_scale=self.scale)
         self.long_frames, self.overlap = int(long_frames), int(overlap)
         if self.long_frames:
             if not 0 <= self.overlap < self.L:
@@ -625,7 +643,6 @@ class SlotServer:
         self.bank_samplers, self.bank_steps = int(samplers), int(bank_steps)
         if self.bank_samplers and self.bank_steps:
             kw.update(samplers=self.bank_samplers, sampler_steps=self.bank_steps)
-        self.scale = kw["cfg_scale"]
         self.default = self._definition(ddim_steps, sampler, sampler_steps, eta)
         self.chain = self.plan.open_slots(self.n_slots, self.L, **self._definition_args(self.default), **kw)
         self._defs, self._lru = {self.default: 0}, []        # definition -> bank id; ids beyond 0, least recently used first
@@ -633,22 +650,11 @@ class SlotServer:
 
     def _definition(self, ddim_steps, sampler, sampler_steps, eta):
         """A sampler definition (hashable), chosen as animate() chooses it."""
-        if sampler:
-            return ("tables", str(sampler), int(sampler_steps), float(eta))
-        if ddim_steps and not self.p.n_emo:
-            return ("ddim", int(ddim_steps))
-        return ("ddpm",)
+        return _sampler_definition(self.p, ddim_steps, sampler, sampler_steps, eta)
 
     def _definition_args(self, key):
         """open_slots / add_sampler arguments of a definition."""
-        from . import schedule
-        if key[0] == "tables":
-            t_list, tables = schedule.sampler_tables(key[1], key[2], key[3], self.diffusion.num_timesteps)
-            return dict(kind="tables", t_list=t_list, tables=tables)
-        if key[0] == "ddim":
-            return dict(kind="ddim", steps=key[1])
-        ts = list(range(self.diffusion.num_timesteps - 1, -1, -1)) if self.diffusion.full_chain else list(range(999, 499, -1))
-        return dict(kind="ddpm", t_list=ts)
+        return _sampler_args(key, self.diffusion)
 
     def _request(self, ddim_steps, sampler, sampler_steps, eta, cfg_scale):
         """(definition, cfg_scale) of a request; (None, None) = it names nothing: the server's sampler and scale, admitted as before.
@@ -664,7 +670,6 @@ class SlotServer:
             raise ValueError(f"request with sampler {key} / cfg_scale {cfg_scale}: this server was opened without a sampler bank (samplers=, bank_steps=)")
         if key not in self._defs:
             a = self._definition_args(key)
-            from . import schedule
             n = sum(1 for pr in schedule.ddim_time_pairs(a["steps"]) if pr[1] >= 0) if a["kind"] == "ddim" else len(a["t_list"])
             if n < 1 or n > self.bank_steps:
                 raise ValueError(f"sampler {key} has {n} steps, the server's bank holds [1, {self.bank_steps}] (bank_steps=)")
@@ -673,7 +678,6 @@ class SlotServer:
     def _sampler_id(self, key):
         """The bank id of a definition, added on first use.  A full bank drops its least recently used sampler that no slot holds;
         None = nothing can be dropped yet: the request waits."""
-        from ._lib import FdmError
         if key in self._defs:
             sid = self._defs[key]
         else:
@@ -697,7 +701,6 @@ class SlotServer:
         return sid
 
     def _check(self):
-        from ._lib import FdmError
         if self.plan.get("slots") != self.n_slots:
             raise FdmError("SlotServer: the model's plan left slot mode (another sampling call used it)")
 
@@ -709,26 +712,27 @@ class SlotServer:
         animate() does and admits the clip, or queues it until a slot is free.  ddim_steps / sampler / sampler_steps / eta /
         cfg_scale: the request's own sampler and guidance scale (class docstring); none given = the server's."""
         self._check()
-        key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
-        p, dev = self.p, self.device
-        if rate is not None:
-            audio = prepare_audio(audio, rate, device=dev)
-        wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
-        hub = self.model.audio_encoder(wav).last_hidden_state
-        L = min(hub.shape[1] // p.pair, p.max_len)
+        request = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
+        hub = self.model.audio_encoder(_waveform(audio, rate, self.device).reshape(1, -1)).last_hidden_state
+        L = min(hub.shape[1] // self.p.pair, self.p.max_len)
         if L < 1 or L > self.L:
             raise ValueError(f"clip of {L} latent frames, slots hold [1, {self.L}]")
-        ids = torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32).reshape(-1, p.n_style)[:1]
-        emo = None
-        if p.n_emo:
-            emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
-            emo = emo.to(dev)
-        x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
+        h = self._enqueue(hub, L, template, id_one_hot, emotion_one_hot, seed, request, style_track, emotion_track)
+        self._fill()
+        return h
+
+    def _enqueue(self, hub, L, template, id_one_hot, emotion_one_hot, seed, request, style_track, emotion_track, windows=0):
+        """One request of L latent frames at the tail of the queue -> its handle.  The record holds the first row of its conditions
+        (defaults as animate()), x_T drawn as animate() / animate_long() draw it for this clip alone, its sampler and scale
+        (_request) and its tracks; windows > 0: a long request, a group of that many slots."""
+        p, dev = self.p, self.device
+        ids = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, 1)[:1].to(dev)
+        emo = _condition(emotion_one_hot, p.n_emo, _EMOTION_DEFAULT, 1)[:1].to(dev) if p.n_emo else None
         h = self._next
         self._next += 1
-        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, sampler=key, scale=scale,
+        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids, emo=emo, x_T=_start_noise((1, L * p.G, p.c), int(seed)), seed=int(seed),
+                                template=template, windows=windows, sampler=request[0], scale=request[1],
                                 **self._tracks(L, style_track, emotion_track)))
-        self._fill()
         return h
 
     def _tracks(self, L, style_track, emotion_track):
@@ -739,9 +743,7 @@ class SlotServer:
         return dict(st=cut(style_track, self.p.n_style), et=cut(emotion_track, self.p.n_emo), tracks=True)
 
     def _quant(self, lat, r):
-        if not self.p.n_emo:
-            return self.ae.quant(lat, stats=False)[0]
-        return self.ae.quant(lat, r["emo"], stats=False, emotion_track=r.get("et"))[0]
+        return _quantise(self.ae, self.p, lat, r["emo"], r.get("et"))
 
     @torch.no_grad()
     def submit_many(self, audios, templates=None, id_one_hots=None, emotion_one_hots=None, seeds=0, ddim_steps=None, sampler=None,
@@ -754,32 +756,15 @@ class SlotServer:
         style_track / emotion_track: a list with one track (or None) per request, or one for all (submit()).
         Returns the handles; results equal submit() in a loop bit for bit."""
         self._check()
-        p, dev = self.p, self.device
-        n = len(audios)
-        per = lambda x, b: x[b] if isinstance(x, (list, tuple)) else x  # noqa: E731
-        reqs = [self._request(per(ddim_steps, b), per(sampler, b), per(sampler_steps, b), per(eta, b), per(cfg_scale, b)) for b in range(n)]
-        if rate is not None:
-            wav_b, lens_b = prepare_audio_many(audios, rate, device=dev)
-            audios = [wav_b[b, :lens_b[b]] for b in range(n)]
-        hubs = self.model.audio_encoder.encode_many([torch.as_tensor(a, dtype=torch.float32).reshape(-1) for a in audios], dev)
+        p, n = self.p, len(audios)
+        reqs = [self._request(_per(ddim_steps, b), _per(sampler, b), _per(sampler_steps, b), _per(eta, b), _per(cfg_scale, b)) for b in range(n)]
+        hubs = self.model.audio_encoder.encode_many(_waveforms(audios, rate, self.device, upload=False), self.device)
         Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
         for L in Ls:
             if L < 1 or L > self.L:
                 raise ValueError(f"clip of {L} latent frames, slots hold [1, {self.L}]")
-        handles = []
-        for b in range(n):
-            ido, emo_in, seed = per(id_one_hots, b), per(emotion_one_hots, b), int(per(seeds, b))
-            ids = torch.eye(p.n_style)[:1] if ido is None else torch.as_tensor(ido, dtype=torch.float32).reshape(-1, p.n_style)[:1]
-            emo = None
-            if p.n_emo:
-                emo = torch.eye(p.n_emo)[4:5] if emo_in is None else torch.as_tensor(emo_in, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
-                emo = emo.to(dev)
-            x_T = torch.randn((1, Ls[b] * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
-            h = self._next
-            self._next += 1
-            self._queue.append(dict(handle=h, hub=hubs[b], L=Ls[b], ids=ids.to(dev), emo=emo, x_T=x_T, seed=seed, template=per(templates, b),
-                                    sampler=reqs[b][0], scale=reqs[b][1], **self._tracks(Ls[b], per(style_track, b), per(emotion_track, b))))
-            handles.append(h)
+        handles = [self._enqueue(hubs[b], Ls[b], _per(templates, b), _per(id_one_hots, b), _per(emotion_one_hots, b), _per(seeds, b), reqs[b],
+                                 _per(style_track, b), _per(emotion_track, b)) for b in range(n)]
         self._fill()
         return handles
 
@@ -787,7 +772,6 @@ class SlotServer:
         """Admit from the head of the queue while the head fits: a plain request needs one idle slot (the lowest), a long one needs
         its window count in idle slots, an arena range and a descriptor (FDM_ERR_STATE from admit_long = not yet); a request with
         its own sampler also needs that sampler in the bank (_sampler_id).  Nothing passes a request that waits."""
-        from ._lib import FdmError
         while self._queue:
             r = self._queue[0]
             free = [s for s in range(self.n_slots) if self._slot[s] is None]
@@ -829,13 +813,9 @@ class SlotServer:
         submit(): the result equals animate_long() with them."""
         from .denoiser import window_starts
         self._check()
-        key, scale = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
-        p, dev = self.p, self.device
-        if rate is not None:
-            audio = prepare_audio(audio, rate, device=dev)
-        wav = torch.as_tensor(audio, dtype=torch.float32, device=dev).reshape(1, -1)
-        hub = self.model.audio_encoder(wav).last_hidden_state
-        L = hub.shape[1] // p.pair
+        request = self._request(ddim_steps, sampler, sampler_steps, eta, cfg_scale)
+        hub = self.model.audio_encoder(_waveform(audio, rate, self.device).reshape(1, -1)).last_hidden_state
+        L = hub.shape[1] // self.p.pair
         if L < 1:
             raise ValueError(f"clip of {L} latent frames")
         windows = 0
@@ -845,16 +825,7 @@ class SlotServer:
             windows = len(window_starts(L, self.L, self.overlap))
             if windows > self.n_slots:
                 raise ValueError(f"recording of {L} latent frames needs {windows} windows of {self.L}, the server has {self.n_slots} slots")
-        ids = torch.eye(p.n_style)[:1] if id_one_hot is None else torch.as_tensor(id_one_hot, dtype=torch.float32).reshape(-1, p.n_style)[:1]
-        emo = None
-        if p.n_emo:
-            emo = torch.eye(p.n_emo)[4:5] if emotion_one_hot is None else torch.as_tensor(emotion_one_hot, dtype=torch.float32).reshape(-1, p.n_emo)[:1]
-            emo = emo.to(dev)
-        x_T = torch.randn((1, L * p.G, p.c), generator=torch.Generator(device="cpu").manual_seed(seed))
-        h = self._next
-        self._next += 1
-        self._queue.append(dict(handle=h, hub=hub, L=L, ids=ids.to(dev), emo=emo, x_T=x_T, seed=int(seed), template=template, windows=windows,
-                                sampler=key, scale=scale, **self._tracks(L, style_track, emotion_track)))
+        h = self._enqueue(hub, L, template, id_one_hot, emotion_one_hot, seed, request, style_track, emotion_track, windows)
         self._fill()
         return h
 
@@ -862,62 +833,45 @@ class SlotServer:
     def step(self, n=10):
         """n diffusion steps for every running clip; clips whose chain ended are read, quantised and decoded at their own length
         (as animate_many does) and their slots go to the queue.  Returns the number of clips finished by this call."""
-        from ._lib import SLOT_FINISHED
         self._check()
         self._fill()
         self.plan.run(n)
-        if self.batch_stages:
-            fin = self._finish_long() + self._finish_batched()
-            self._fill()
-            return fin
         fin = self._finish_long()
-        for s in range(self.n_slots):
-            r = self._slot[s]
-            if r is None or self.plan.slot_state(s)[2] != SLOT_FINISHED:
-                continue
-            lat = self.plan.read_slot(s, r["L"])
-            q = self._quant(lat, r)
-            out = self.ae.decode(q)
-            self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
-            self._slot[s] = None
-            fin += 1
+        if self.batch_stages:
+            fin += self._finish_batched()
+        else:
+            for s in range(self.n_slots):
+                r = self._slot[s]
+                if r is not None and self.plan.slot_state(s)[2] == SLOT_FINISHED:
+                    fin += self._finish_one([s], self.plan.read_slot(s, r["L"]), r)
         self._fill()
         return fin
 
     def _vertices(self, out, template):
         """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames, with rig= its
         rig.RigFrames, with both the pair."""
-        rf = None if self.rig is None else to_rig(out, self.rig, fps=self.mesh_fps)
-        if self.faces is not None:
-            mf = to_mesh(out, self.faces, template, fps=self.mesh_fps, **self.mesh)
-            return mf if rf is None else (mf, rf)
-        if rf is not None:
-            return rf
-        if template is not None:
-            out = out + torch.as_tensor(template, dtype=torch.float32, device=self.device).reshape(-1, 1, out.shape[-1])
-        return out
+        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps)
+
+    def _finish_one(self, slots, lat, r):
+        """One finished request: its latent quantised and decoded at its own length, the result kept for results(), its slots idle."""
+        out = self.ae.decode(self._quant(lat, r))
+        self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
+        for s in slots:
+            self._slot[s] = None
+        return 1
 
     def _finish_long(self):
         """The groups whose chains ended: read the long latent, quantise and decode the whole L_total (the decoder is not causal), as
         animate_long does; every member slot goes back to the queue.  A long result has its own decode call, batch_stages or not."""
-        from ._lib import SLOT_FINISHED
         fin = 0
         for s in range(self.n_slots):
             r = self._slot[s]
-            if r is None or not r.get("windows") or r["slots"][0] != s or self.plan.slot_state(s)[2] != SLOT_FINISHED:
-                continue
-            lat = self.plan.read_long(s)
-            q = self._quant(lat, r)
-            out = self.ae.decode(q)
-            self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
-            for m in r["slots"]:
-                self._slot[m] = None
-            fin += 1
+            if r is not None and r.get("windows") and r["slots"][0] == s and self.plan.slot_state(s)[2] == SLOT_FINISHED:
+                fin += self._finish_one(r["slots"], self.plan.read_long(s), r)
         return fin
 
     def _finish_batched(self):
         """batch_stages: the clips whose chains ended in this call through ONE padded quant and ONE decode over their unequal lengths."""
-        from ._lib import SLOT_FINISHED
         p = self.p
         done = [s for s in range(self.n_slots) if self._slot[s] is not None and self.plan.slot_state(s)[2] == SLOT_FINISHED]
         if not done:
@@ -933,21 +887,20 @@ class SlotServer:
             for i, r in enumerate(reqs):
                 if r.get("et") is not None:
                     et[i, :r["L"]] = r["et"]
-            qs = self.ae.quant(pad, None, stats=False, emotion_track=et)[0]
+            qs = _quantise(self.ae, p, pad, None, et)
         else:
-            qs = self.ae.quant(pad, torch.cat([r["emo"] for r in reqs]), stats=False)[0] if p.n_emo else self.ae.quant(pad, stats=False)[0]
+            qs = _quantise(self.ae, p, pad, torch.cat([r["emo"] for r in reqs]) if p.n_emo else None)
         outs = self.ae.decode_many(qs, [r["L"] for r in reqs])
         self.batched_decodes.append(len(done))
-        tps = [r["template"] for r in reqs]
-        ragged = None
-        if self.faces is not None and (all(t is None for t in tps) or all(t is not None for t in tps)):      # one call over the unequal lengths
-            ragged = to_mesh([outs[i, :r["L"]] for i, r in enumerate(reqs)], self.faces, None if tps[0] is None else tps, fps=self.mesh_fps, **self.mesh)
-        if self.rig is not None and (ragged or self.faces is None):          # and one rig hand-off call
-            fits = to_rig([outs[i, :r["L"]] for i, r in enumerate(reqs)], self.rig, fps=self.mesh_fps)
-            ragged = [(m, f) for m, f in zip(ragged, fits)] if ragged else fits
-        for i, (s, r) in enumerate(zip(done, reqs)):
-            out = ragged[i] if ragged else self._vertices(outs[i:i + 1, :r["L"]].contiguous(), r["template"])
-            self._done.append((r["handle"], out, lats[i]))
+        clips, tps = [outs[i:i + 1, :r["L"]] for i, r in enumerate(reqs)], [r["template"] for r in reqs]
+        mixed = any(t is None for t in tps) and any(t is not None for t in tps)
+        if (self.faces is None and self.rig is None) or (self.faces is not None and mixed):
+            # no hand-off call to share, or a mesh with a template on some requests only: clip by clip
+            res = [self._vertices(c.contiguous(), t) for c, t in zip(clips, tps)]
+        else:       # one mesh call and one rig call over the unequal lengths
+            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps)
+        for s, r, out, lat in zip(done, reqs, res, lats):
+            self._done.append((r["handle"], out, lat))
             self._slot[s] = None
         return len(done)
 
@@ -1078,8 +1031,7 @@ def demo_main(preset, argv=None):
             out, rf = out
         else:
             rf = to_rig(out, rig, fps=_mesh_fps(p, a.in_fps, a.out_fps))
-            if tmpl_after is not None:
-                out = out + torch.as_tensor(tmpl_after, dtype=torch.float32, device=a.device).reshape(-1, 1, out.shape[-1])
+            out = _hand_off(out, tmpl_after, a.device)
         np.save(dst + "_rig", rf.weights.detach().cpu().numpy())
         print(f"saved {dst}_rig.npy {tuple(rf.weights.shape)}" + (f" ({', '.join(rf.names[:4])}, ...)" if rf.names else ""))
     if a.faces_file:        # positions keep the reference's name and shape
