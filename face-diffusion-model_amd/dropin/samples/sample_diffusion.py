@@ -127,6 +127,7 @@ def main(dataset=None, argv=None):
     ap.add_argument("--device_audio", action="store_true",
                     help="build-added: the synthetic clips arrive as raw 48 kHz stereo int16 PCM and go through the device front end "
                          "(pipeline.prepare_audio: conversion, downmix, resampling, normalisation, 1 s of zeros); no file is read")
+    pipeline.add_flame_arguments(ap)
     named = dataset is not None
     if named:
         pipeline.add_track_arguments(ap, presets.get(dataset))
@@ -149,11 +150,16 @@ def main(dataset=None, argv=None):
     all_styles = a.all_styles or (named and dataset == "vocaset" and not trk)      # samples/sample_diffusion_vocaset.py:71 loops every one-hot
     # one clip, one condition per sampling call (the reference's bs = 1 loop): the step program's single-clip setting
     single = a.batch <= 1 and (not all_styles or a.sequential)
+    # build-added: --flame_model: every clip's template from FLAME parameters on the device (samples/sample_diffusion_mead.py:76)
+    tmpl = pipeline.flame_arguments(a, a.device)
+    if tmpl is not None and tmpl.shape[-1] != p.V3:
+        ap.error(f"--flame_model has {tmpl.shape[-1] // 3} vertices, the {dataset} model {p.V3 // 3}")
+    with_template = lambda loader: loader if tmpl is None else ((au, tmpl.cpu(), oh, fn) for au, _, oh, fn in loader)  # noqa: E731
     diffusion, ae = pipeline.build_models(dataset, None, a.device, a.stage1_model_path, a.stage2_model_path, single_clip=single)
     if a.batch > 1 and not all_styles:
-        sample_batched(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset, fast=fast)
+        sample_batched(with_template(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio)), a.device, diffusion, ae, a.out, p, steps, max_batch=a.batch, dataset=dataset, fast=fast)
     else:
-        sample_step(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio), a.device, diffusion, ae, a.out, p, steps,
+        sample_step(with_template(synthetic_loader(p, a.clips, a.seconds, raw=a.device_audio)), a.device, diffusion, ae, a.out, p, steps,
                     all_styles=all_styles, batched=not a.sequential, dataset=dataset, fast=fast)
 
 

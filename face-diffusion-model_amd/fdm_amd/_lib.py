@@ -93,13 +93,18 @@ class Pcm(C.Structure):
     _fields_ = [("data", vp), ("format", ci), ("channels", ci), ("rate", ci), ("frames", ll)]
 
 
+class FlameModelDesc(C.Structure):
+    _fields_ = [("V", ci), ("J", ci), ("NB", ci), ("expr_at", ci), ("v_template", vp), ("shapedirs", vp), ("posedirs", vp),
+                ("j_regressor", vp), ("parents", vp), ("lbs_weights", vp)]
+
+
 PCM_S16, PCM_S32, PCM_U8, PCM_F32 = range(4)      # fdm_pcm.format
 MESH_INTERLEAVED, MESH_F16, MESH_NORMALS = 1, 2, 4      # fdm_mesh_forward flags
 
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
            "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs,
-           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm}
+           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm, "fdm_flame_model": FlameModelDesc}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -211,6 +216,10 @@ SYMBOLS = {
     "fdm_rig_create": (ci, [vp, ci, ci, vp, C.c_double, vp, vp, ci, C.POINTER(vp)]),
     "fdm_rig_forward": (ci, [vp, vp, vp, ci, ci, C.c_double, C.c_double, vp, vp, ci, vp, vp]),
     "fdm_rig_destroy": (ci, [vp]),
+    "fdm_flame_tables_host": (ci, [C.POINTER(FlameModelDesc), vp, vp, vp]),
+    "fdm_flame_create": (ci, [C.POINTER(FlameModelDesc), vp, vp, ci, C.POINTER(vp)]),
+    "fdm_flame_forward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+    "fdm_flame_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),

@@ -2,8 +2,8 @@
 mean vertex error, emotion mean error, upper-face dynamics deviation (FDD) and diversity.
 
 Mirrors computer_metrix.py:6-136 (BIWI / VOCASET evaluation, `main`), :139-194 (`compute_diversity`) and the
-vertex-error block of metric/metric.py:115-138 (3D-MEAD; its ground truth needs the FLAME model, which is
-outside this path, so only the arithmetic on vertex arrays is provided).  The reductions run in
+vertex-error block of metric/metric.py:115-138 (3D-MEAD; its ground truth comes from FLAME parameters: pass
+gt_params= and a flame.FlamePlan made from the user's model file, or vertex arrays).  The reductions run in
 libfdm_hip.so (fdm_op_vertex_err, fdm_op_motion_std); numpy/pickle are used for file IO only."""
 import argparse
 import os
@@ -166,11 +166,94 @@ def diversity(pred_path, train_subjects, test_subjects, dataset="BIWI", device="
     return total / num
 
 
-def mead_vertex_metrics(gt, pred, face_vertex, lip_vertex, emotion_vertex, device="cuda:0"):
+def mead_vertex_metrics(gt, pred, face_vertex, lip_vertex, emotion_vertex, device="cuda:0", gt_params=None, flame=None):
     """The vertex-error block of metric/metric.py:115-138 on [F, 5023, 3] arrays: FVE, LVE (max over the region),
-    EME (mean over the region) and the all-vertex error."""
+    EME (mean over the region) and the all-vertex error.  gt_params = (expression [F, NE], pose [F, 6]) with flame = a
+    flame.FlamePlan, in place of gt (pass gt=None): the ground truth is made on the device as the reference makes it
+    (flame.torch2mesh: zero shape, zero neck and eyes, 4 decimals)."""
+    if gt_params is not None:
+        if gt is not None or flame is None:
+            raise ValueError("gt_params takes flame= (a flame.FlamePlan) and gt=None")
+        from .flame import torch2mesh
+        gt = torch2mesh(flame, gt_params[0], gt_params[1]).reshape(-1, flame.V, 3)
     return dict(FVE=vertex_error(gt, pred, face_vertex, device)["max"], LVE=vertex_error(gt, pred, lip_vertex, device)["max"],
                 EME=vertex_error(gt, pred, emotion_vertex, device)["mean_sq"], ALL=vertex_error(gt, pred, None, device)["max"])
+
+
+MEAD_REGIONS = ("face_vertices.npy", "lip_vertices.npy", "emotion_vertices.npy")
+
+
+def mead_gt_name(pred):
+    """(subject directory, ground-truth file) of a MEAD prediction file, the naming rule of metric/metric.py:67-70: the name with
+    '_' turned into '-', cut before its last 10 characters, then '_', the 5 characters before the extension, '.npz'."""
+    s = pred.replace("_", "-")
+    return pred.split("_")[0], s[:-10] + "_" + s[-9:-4] + ".npz"
+
+
+def mead_evaluate(pred_path, gt_path, flame_model, region_path="region", device="cuda:0", pick="angry", expr_at=None, verbose=True):
+    """metric/metric.py:63-138 with the ground truth and the neutral template made on the device from FLAME parameters.  For every
+    prediction <pred_path>/*.npy whose name holds `pick` (None: all) and whose ground truth <gt_path>/<subject>/<name>.npz (keys
+    expression [T, NE], pose [T, 6]) exists: gt = torch2mesh(expression, (0, jaw pose)) -- the global rotation is dropped, as the
+    reference drops it --, both cut to the shorter; then FVE / LVE / EME / ALL over all kept frames (mead_vertex_metrics) with the
+    regions <region_path>/{face,lip,emotion}_vertices.npy, and per file the motion statistic of the emotion region about the neutral
+    template (motion_std) for ground truth and prediction.  flame_model: a model file, a flame.FlameModel or a flame.FlamePlan.
+    -> dict(FVE, LVE, EME, ALL, frames, files, motion_std_gt, motion_std_pred, template [V, 3])."""
+    from .flame import FlameModel, FlamePlan, torch2mesh
+    if isinstance(flame_model, FlamePlan):
+        plan = flame_model
+    else:
+        plan = FlamePlan(flame_model if isinstance(flame_model, FlameModel) else FlameModel.load(flame_model, expr_at=expr_at), device=device)
+    face, lip, emotion = (np.load(os.path.join(region_path, f)) for f in MEAD_REGIONS)
+    V = plan.V
+    n_expr = plan.NB - plan.model.expr_at
+    template = torch2mesh(plan, torch.zeros(1, min(50, n_expr)), torch.zeros(1, 6)).reshape(V, 3)
+    gts, preds, files, std_gt, std_pred = [], [], [], [], []
+    for pred in sorted(os.listdir(pred_path)):
+        if not pred.endswith(".npy") or (pick and pick not in pred):
+            continue
+        sub, name = mead_gt_name(pred)
+        src = os.path.join(gt_path, sub, name)
+        if not os.path.exists(src):
+            if verbose:
+                print(f"{pred}: ground truth {src} not found")
+            continue
+        with np.load(src) as z:
+            ex, jaw = torch.from_numpy(z["expression"].astype(np.float32)), torch.from_numpy(z["pose"].astype(np.float32))[:, 3:6]
+        vp = torch.from_numpy(np.load(os.path.join(pred_path, pred)).astype(np.float32).reshape(-1, V, 3)).to(device)
+        vg = torch2mesh(plan, ex[:, :n_expr], torch.cat([torch.zeros_like(jaw), jaw], 1)).reshape(-1, V, 3)
+        n = min(vp.shape[0], vg.shape[0])
+        vp, vg = vp[:n].contiguous(), vg[:n].contiguous()
+        gts.append(vg)
+        preds.append(vp)
+        files.append(pred)
+        std_gt.append(motion_std(vg, template, emotion, device))
+        std_pred.append(motion_std(vp, template, emotion, device))
+    if not files:
+        raise FdmError(f"no prediction in {pred_path} has a ground truth under {gt_path}")
+    res = mead_vertex_metrics(torch.cat(gts), torch.cat(preds), face, lip, emotion, device)
+    res.update(frames=int(sum(g.shape[0] for g in gts)), files=files, motion_std_gt=std_gt, motion_std_pred=std_pred, template=template)
+    if verbose:
+        print(f"Frame Number: {res['frames']}")
+        print(f"Face Vertex Error (FVE): {res['FVE']:.4e}\nLip Vertex Error (LVE): {res['LVE']:.4e}")
+        print(f"Emotion Mean Error (EME): {res['EME']:.4e}\nAll Vertex Error: {res['ALL']:.4e}")
+    return res
+
+
+def mead_main(argv=None):
+    """CLI of metric/metric.py (:19-24) plus --flame_model: the model file the ground truth is made with."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--train_subjects", type=str, default="F2 F3 F4 M3 M4 M5")
+    ap.add_argument("--pred_path", type=str, default="result/npy")
+    ap.add_argument("--gt_path", type=str, default="MEAD/FLAME_ALL")
+    ap.add_argument("--region_path", type=str, default="region")
+    ap.add_argument("--templates_path", type=str, default="BIWI/templates.pkl")
+    ap.add_argument("--flame_model", type=str, required=True,
+                    help="build-added: FLAME-type model file (.npz or a pickled dict of plain arrays): ground truth and neutral template on the device")
+    ap.add_argument("--flame_expr_at", type=int, default=None, help="build-added: index of the first expression coefficient (FLAME: 300)")
+    ap.add_argument("--pick", type=str, default="angry", help="build-added: substring a prediction's name must hold (the reference's 'angry'; '' = all)")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    a = ap.parse_args(argv)
+    return mead_evaluate(a.pred_path, a.gt_path, a.flame_model, a.region_path, a.device, a.pick or None, a.flame_expr_at)
 
 
 def main(argv=None):

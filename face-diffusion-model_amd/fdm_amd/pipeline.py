@@ -211,6 +211,88 @@ def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bound
     return _split_rig(rf) if many else rf
 
 
+_FLAME_PLANS = {}     # (device, stream, identity of the model and its landmarks: flame.FlamePlan.key) -> flame.FlamePlan
+
+
+def _flame_plan(model, device, landmarks=None):
+    """The parametric-head plan of `device`, the current stream and this model (a plan serves one stream at a time), kept as
+    _rig_plan() keeps rig plans.  model: a flame.FlamePlan (used as it is where it was made for this device and stream, made again
+    from its model otherwise), a flame.FlameModel (digested once), or the path of a model file (loaded per call: pass a FlameModel)."""
+    from .flame import FlameModel, FlamePlan, plan_key
+    dv, at = _on_stream(device)
+    if isinstance(model, FlamePlan):
+        plan = _FLAME_PLANS.get(at + (model.key,))
+        if plan is None:
+            plan = model if (model.device == dv and model.stream == at[1]) else FlamePlan(model.model, None if model.lv is None else (model.lv, model.lb), dv)
+            _FLAME_PLANS[at + (plan.key,)] = plan
+        return plan
+    if not isinstance(model, FlameModel):
+        model = FlameModel.load(model)
+    key = at + (plan_key(model, landmarks),)
+    plan = _FLAME_PLANS.get(key)
+    if plan is None:
+        _FLAME_PLANS[key] = plan = FlamePlan(model, landmarks, dv)
+    return plan
+
+
+@torch.no_grad()
+def to_flame(pose, model, expression=None, shape=None, transl=None, extra=None, frames=None, landmarks=None, device=None):
+    """Parameters -> flame.FlameFrames (posed vertices [B, L, V, 3], landmarks or None) in ONE device call (flame.FlamePlan;
+    include/fdm_hip.h, fdm_flame_forward).  model: a flame.FlameModel, a flame.FlamePlan or a model file; pose [B, L, 3 J] (or
+    [L, 3 J]) axis-angle; expression [B, L, NE]; shape [NS] or [B, NS]; transl [B, L, 3]; extra [B, L, 3 V]: displacements added before
+    skinning -- the decoder's offsets; frames: L per clip; landmarks = (verts [NL, 3], bary [NL, 3]), the static embedding."""
+    from .flame import FlamePlan
+    if device is None:
+        device = next((x.device for x in (extra, pose, expression) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+        if device is None and isinstance(model, FlamePlan):
+            device = model.device
+    if device is None or torch.device(device).type != "cuda":
+        raise FdmError("to_flame runs on the HIP path only (no CPU fallback)")
+    return _flame_plan(model, device, landmarks).forward(pose, expression, shape, transl, extra, frames)
+
+
+def _flame_rows(x, L, R, what):
+    """A per-frame argument of flame= for R clips of L frames: [L', n] (for all) or [R, L', n], L' >= L -> [R, L, n]"""
+    x = torch.as_tensor(x, dtype=torch.float32)
+    x = x.unsqueeze(0).expand(R, -1, -1) if x.dim() == 2 else x
+    if x.dim() != 3 or x.shape[0] != R or x.shape[1] < L:
+        raise ValueError(f"flame {what}: {tuple(x.shape)} for {R} clips of {L} frames")
+    return x[:, :L]
+
+
+FLAME_KEYS = ("model", "pose", "shape", "expression", "transl")
+
+
+def _flame_check(flame):
+    """flame= of animate*: a dict with model and pose, and no key but FLAME_KEYS"""
+    if not isinstance(flame, dict) or "model" not in flame or flame.get("pose") is None or set(flame) - set(FLAME_KEYS):
+        raise ValueError(f"flame= takes a dict with model and pose, optionally shape, expression and transl; got {sorted(flame) if isinstance(flame, dict) else type(flame).__name__}")
+
+
+def _flame_posed(out, flame, device, frames=None, S=1, B=1):
+    """The decoder's offsets [R, L, V3] as `extra` of the head flame = dict(model=, pose=, shape=, expression=, transl=) -> posed
+    vertices [R, L, V3], at the model's frame rate.  With S > 1 conditions per clip (R = B * S rows in (clip, condition) order) a
+    per-clip argument [B, L', n] or shape [B, NS] repeats per condition, as a per-clip template does."""
+    _flame_check(flame)
+    R, L = int(out.shape[0]), int(out.shape[1])
+
+    def rows(k):
+        x = flame.get(k)
+        if x is None:
+            return None
+        x = torch.as_tensor(x, dtype=torch.float32)
+        if S > 1 and B > 1 and x.dim() == 3 and x.shape[0] == B:
+            x = x.repeat_interleave(S, dim=0)
+        return _flame_rows(x, L, R, k)
+    shape = flame.get("shape")
+    if shape is not None:
+        shape = torch.as_tensor(shape, dtype=torch.float32)
+        if S > 1 and B > 1 and shape.dim() == 2 and shape.shape[0] == B:
+            shape = shape.repeat_interleave(S, dim=0)
+    ff = to_flame(rows("pose"), flame["model"], rows("expression"), shape, rows("transl"), out, frames, device=device)
+    return ff.vertices.reshape(R, L, -1)
+
+
 def build_models(preset="vocaset", feature_dim=None, device="cuda:0", stage1=None, stage2=None, dtype=None, cfg_level=None, single_clip=False):
     """(diffusion, autoencoder) with reference-compatible state dicts; checkpoints are loaded when the
     files exist ('model' / 'state_dict' keys as samples/sample_diffusion_vocaset.py:26,91-97), otherwise the
@@ -335,12 +417,21 @@ def _template_rows(template, width, device, S=1, B=1):
     return tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp
 
 
-def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1):
+def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None):
     """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
-    template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair."""
+    template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair.
+    flame=: the offsets pose the model's head (_flame_posed) and the posed vertices stand where offsets + template stood (the
+    template argument is not read); rig= still fits the un-posed offsets; rig= without faces= returns no vertices, so flame= is
+    refused with it."""
+    if flame is not None:
+        _flame_check(flame)
+        if rig is not None and faces is None:
+            raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
     rf = None if rig is None else to_rig(out, rig, fps=fps)
     if faces is None and rf is not None:
         return rf
+    if flame is not None:
+        out, template = _flame_posed(out, flame, device, S=S, B=B), None
     tp = None if template is None else _template_rows(template, out.shape[-1], device, S, B)
     if faces is None:
         return out if tp is None else out + tp.unsqueeze(1)
@@ -348,14 +439,32 @@ def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, 
     return mf if rf is None else (mf, rf)
 
 
-def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None):
+def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None):
     """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip: ONE mesh call and ONE rig call
-    over the unequal lengths, each result bit for bit its own call's."""
+    over the unequal lengths, each result bit for bit its own call's.  flame=: ONE ragged head call first (pose / expression /
+    transl [L', n] for all clips or a list with one per clip); its posed clips stand where offsets + template stood."""
+    offsets = clips
+    if flame is not None:
+        _flame_check(flame)
+        if rig is not None and faces is None:
+            raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
+        x, frames, _ = _pack_offsets(clips, None, device, "to_flame")
+        per = dict(flame)
+        for k in ("pose", "expression", "transl"):
+            v = flame.get(k)
+            if isinstance(v, (list, tuple)):      # one per clip: padded with zeros to the batch's length (rows past a clip's frames are never read)
+                rows = [torch.as_tensor(a, dtype=torch.float32).reshape(-1, torch.as_tensor(a).shape[-1]) for a in v]
+                pad = torch.zeros(len(rows), max(int(x.shape[1]), max(int(r.shape[0]) for r in rows)), rows[0].shape[-1])
+                for b, r in enumerate(rows):
+                    pad[b, :r.shape[0]] = r
+                per[k] = pad
+        posed = _flame_posed(x, per, device, frames)
+        clips, templates = [posed[b:b + 1, :n] for b, n in enumerate(frames)], None
     if faces is None and rig is None:
         return clips if templates is None else [c + _template_rows(t, c.shape[-1], device).unsqueeze(1) for c, t in zip(clips, templates)]
     res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
     if rig is not None:
-        fits = to_rig(clips, rig, fps=fps)
+        fits = to_rig(offsets, rig, fps=fps)
         res = fits if res is None else list(zip(res, fits))
     return res
 
@@ -363,8 +472,14 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    flame = dict(model= a flame.FlameModel / FlamePlan / model file, pose= [L', 3 J] or [B, L', 3 J] axis-angle (L' >= L), shape=,
+    expression=, transl=; per-clip arguments repeat per condition when S > 1): the decoder's offsets enter the parametric head as `extra` (to_flame) at the model's frame rate and the
+    posed vertices are returned in place of offsets + template (the template argument is then not read: the model has its own).
+    With faces= the mesh.MeshFrames are made from the posed vertices; rig= still fits the un-posed offsets (rig= without faces=
+    returns no vertices: flame= is refused with it).  None: every path as before.  (SlotServer does not take it.)
 
     rig (a rig.RigPlan or the dict of its arguments: basis, weights, ridge, bounds, sweeps, names): the decoder's offsets -- never the
     templated vertices -- go through the device rig hand-off (to_rig) and the call returns (rig.RigFrames, latent) in place of the
@@ -427,14 +542,17 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     latent = _sample(diffusion, key, audio, shape, cond, x_T.repeat_interleave(S, dim=0) if S > 1 else x_T, seed, **trk)
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emotion_one_hot, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame), latent
 
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
-                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
+                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    flame: as animate(), with pose / expression / transl one [L', n] for all clips or a list with one per clip; each group's decoded
+    clips go through ONE ragged head call.  None: every path as before.
 
     rig: as animate(); each group's decoded clips go through ONE ragged rig hand-off call and the first returned list holds a
     rig.RigFrames per clip ([1, L_out_b, K]), or with faces= a (mesh.MeshFrames, rig.RigFrames) pair.  None: every path as before.
@@ -536,7 +654,8 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
                     offs.append(autoencoder.decode(_quantise(autoencoder, p, lats[b], emos[i:i + 1] if p.n_emo else None, etq)))
             # the group's clips, each at its own length, through one mesh and one rig hand-off call
             tps = None if templates is None else [_per(templates, b) for b in grp]
-            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps)):
+            fl = None if flame is None else {k: ([v[b] for b in grp] if (k in ("pose", "expression", "transl") and isinstance(v, (list, tuple))) else v) for k, v in flame.items()}
+            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl)):
                 verts[b] = v
     finally:
         model._hub_key, model._hub = prev
@@ -546,8 +665,9 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    flame: as animate(): the whole recording's offsets pose the model's head (pose [L', 3 J] with L' >= L_total).
     rig: as animate(): the whole recording's offsets go through the rig hand-off and the call returns (rig.RigFrames, latent), or
     ((mesh.MeshFrames, rig.RigFrames), latent) with faces=.
     faces / out_fps / mesh / in_fps: as animate(): the whole recording's decode goes through the mesh hand-off and the call returns
@@ -581,7 +701,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emo, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame), latent
 
 
 class SlotServer:
@@ -965,6 +1085,41 @@ def rig_arguments(a):
                     names=[str(n) for n in z["names"]] if "names" in z else None)
 
 
+def add_flame_arguments(ap):
+    """--flame_model / --flame_expr_at / --template_params of the MEAD command lines (the device parametric head, to_flame)."""
+    ap.add_argument("--flame_model", type=str, default=None,
+                    help="build-added: FLAME-type model file (.npz or a pickled dict of plain arrays: flame.FlameModel.load): the template is "
+                         "made from parameters on the device as the reference's torch2mesh does (the neutral face without --template_params)")
+    ap.add_argument("--flame_expr_at", type=int, default=None, help="build-added: index of the first expression coefficient (FLAME: 300; default the file's expr_at, else NB)")
+    ap.add_argument("--template_params", type=str, default=None, help="build-added: .npy of [1, NE + 6] FLAME parameters (expression, then global and jaw pose) for the template (with --flame_model)")
+
+
+def flame_template(model, params=None, device="cuda:0", n_expr=50):
+    """The MEAD template of samples/sample_diffusion_mead.py:76 from parameters: params [..., NE + 6] (expression, then global and jaw
+    pose; None: zeros, the neutral face) -> [1, 3 V] on the device (flame.torch2mesh: zero shape, 4 decimals).  model: a
+    flame.FlameModel / FlamePlan / model file."""
+    from .flame import torch2mesh
+    plan = _flame_plan(model, device)
+    if params is None:
+        prm = torch.zeros(1, min(n_expr, plan.NB - plan.model.expr_at) + 6)
+    else:
+        prm = torch.as_tensor(params, dtype=torch.float32).detach().cpu()
+        prm = prm.reshape(-1, prm.shape[-1])[:1]
+    if prm.shape[-1] < 6:
+        raise ValueError(f"template parameters are expression coefficients then 6 pose numbers, got {prm.shape[-1]} numbers")
+    return torch2mesh(plan, prm[:, :prm.shape[-1] - 6], prm[:, prm.shape[-1] - 6:])[0]
+
+
+def flame_arguments(a, device):
+    """template of animate() from the parsed flags ([1, 3 V] on the device), or None without --flame_model."""
+    if not getattr(a, "flame_model", None):
+        if getattr(a, "template_params", None):
+            raise ValueError("--template_params needs --flame_model")
+        return None
+    from .flame import FlameModel
+    return flame_template(FlameModel.load(a.flame_model, expr_at=a.flame_expr_at), None if not a.template_params else np.load(a.template_params), device)
+
+
 def demo_main(preset, argv=None):
     """CLI of demo/demo_{vocaset,biwi,3d_mead}.py:109-121: same flags, output = np.save(<audio_path>/<stem>.npy, [1, L, V3])."""
     import argparse
@@ -998,6 +1153,8 @@ def demo_main(preset, argv=None):
     ap.add_argument("--save_normals", action="store_true", help="build-added: also save <stem>_normals.npy [1, L_out, 3V] (with --faces_file)")
     add_track_arguments(ap, p)
     add_rig_arguments(ap)
+    if p.n_emo:        # MEAD: the template comes from FLAME parameters
+        add_flame_arguments(ap)
     a = ap.parse_args(argv)
     rig = rig_arguments(a)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
@@ -1009,6 +1166,9 @@ def demo_main(preset, argv=None):
     template = None
     if os.path.exists(a.template_file) and a.template_file.endswith(".npy"):
         template = np.load(a.template_file).reshape(1, -1)
+    ft = flame_arguments(a, a.device)        # --flame_model: the template from parameters, in place of --template_file
+    if ft is not None:
+        template = ft
     emo = None
     if p.n_emo:
         emo = torch.eye(p.n_emo)[EMOTIONS.index(a.emotion)].unsqueeze(0)

@@ -957,6 +957,64 @@ int fdm_rig_forward(fdm_rig* r, const float* offsets, const int* frames, int B, 
                     float* proj, int L_out_max, int* frames_out, void* stream);
 int fdm_rig_destroy(fdm_rig* r);
 
+/* ------------------------------------------------------------------------------------------
+ * Parametric head: parameters in, vertices out.  A head of the SMPL / FLAME family (Loper et al. 2015; Li et al. 2017): blend shapes,
+ * pose correctives and linear blend skinning over a small kinematic tree.  The reverse direction of the rig hand-off, and the way a
+ * sampled animation gets head, neck, jaw and eye motion: the decoder's offsets enter as `extra`.
+ * Model (fdm_flame_model, HOST arrays, not read after the call): V vertices; J joints, 1 <= J <= 8; NB blend coefficients, 0 <= NB <= 512,
+ *   of which [0, expr_at) are shape and [expr_at, NB) expression; v_template [V, 3]; shapedirs [V, 3, NB]; posedirs [9 (J - 1), 3 V]
+ *   (NULL when J = 1); j_regressor [J, V] dense; parents [J] (entry 0 ignored, parents[j] in [0, j)); lbs_weights [V, J].  Optional
+ *   landmarks: NL <= 256 vertex triples lmk_verts [NL, 3] with barycentric weights lmk_bary [NL, 3] (the static embedding, each face
+ *   already resolved to its three vertices).
+ * Per call: shape [shape_rows, NS] (shape_rows = 1 or B; NS <= expr_at), expr [B, L_max, NE] (NE <= NB - expr_at), pose [B, L_max, 3 J]
+ *   axis-angle (FLAME: global, neck, jaw, left eye, right eye), optional transl [B, L_max, 3] and extra [B, L_max, 3 V] (the layout
+ *   fdm_vq_decode_ragged writes), frames [B] HOST ints as in fdm_mesh_forward.  Coefficients not given are not accumulated (they are
+ *   zeros: the result is that of the padded vector).
+ *   create    (host, fp64, rounded once to fp32; fdm_flame_tables_host returns the same arrays, no device needed)
+ *             D [NB + 9 (J - 1), 3 V]: D[k, 3 v + a] = shapedirs[v, a, k], then the posedirs rows; JT [J, 3] = j_regressor v_template;
+ *             JD [NB, 3 J] = j_regressor shapedirs, sums over v ascending: joints are linear in the coefficients.
+ *   pose      fp32, EVERY operation rounded on its own (no fused multiply-add), per frame:
+ *             joints    Jf = JT; Jf += shape_k * JD[k] for k = 0..NS-1; Jf += expr_k * JD[expr_at + k] for k = 0..NE-1.
+ *             rotation  per joint with r = its axis-angle: e = r + 1e-8 (each component), angle = sqrt((e.x e.x + e.y e.y) + e.z e.z),
+ *                       (x, y, z) = r / angle, s = sinf(angle), m = 1 - cosf(angle), K = [0 -z y; z 0 -x; -y x 0],
+ *                       KK = [-(yy + zz) xy xz; xy -(xx + zz) yz; xz yz -(xx + yy)], R = (I + s K) + m KK.  r = 0 gives R = I exactly.
+ *             chain     G_0 = [R_0 | Jf_0]; for j >= 1 with p = parents[j] and d = Jf_j - Jf_p: G_j.R = G_p.R R_j, G_j.t = G_p.R d + G_p.t,
+ *                       every 3-term product sum as (a0 b0 + a1 b1) + a2 b2.  Relative to the rest pose: A_j = [G_j.R | G_j.t - G_j.R Jf_j].
+ *             feature   (R_j - I) for j >= 1, row-major, [9 (J - 1)].
+ *             xforms [B, L_max, J, 12] (A_j as a row-major 3 x 4) and posefeat [B, L_max, 9 (J - 1)] live in the object's scratch and are
+ *             copied out when the caller passes pointers.
+ *   blend     fp32, FUSED multiply-adds (one rounding per term), fixed order.  Per clip v_id = v_template, then v_id = fma(shape_k, D[k],
+ *             v_id) for k = 0..NS-1, stored once per shape row.  Per frame v = v_id; v = fma(expr_k, D[expr_at + k], v), k = 0..NE-1;
+ *             v = fma(posefeat_p, D[NB + p], v), p = 0..9 (J - 1) - 1; then v = v + extra (one rounded add) when extra is given.
+ *   skin      per vertex T = w_v0 * A_0 (a rounded product), T = fma(w_vj, A_j, T) for j = 1..J-1; out_c = fma(T_c2, v.z, fma(T_c1, v.y,
+ *             T_c0 * v.x)) + T_c3, then + transl_c when transl is given (rounded adds).
+ *   landmarks lmk [B, L_max, NL, 3] = fma(b2, out[v2], fma(b1, out[v1], b0 * out[v0])).  The dynamic contour is not built.
+ *   output    verts [B, L_max, V, 3] fp32.  Rows at or past frames[b] come out as zeros in every output; input rows at or past
+ *             frames[b] are never read (they may be NaN).  Every vertex of every frame follows the same operation sequence, a function
+ *             of the model alone: no atomics, and a frame's values do not depend on the batch, L_max, its slot in a tile, the workgroup
+ *             or which optional outputs were asked for.  extra of zeros equals no extra (x + 0 = x).
+ * fdm_flame_create: FDM_ERR_ARG with a message naming the field for a null required pointer, V < 1, J outside [1, 8], NB outside
+ * [0, 512], expr_at outside [0, NB], parents[j] outside [0, j), a non-finite model value, NL outside [0, 256], a landmark vertex outside
+ * [0, V).  With a device visible it uploads the tables; without one the object still validates and fdm_flame_forward ends in
+ * FDM_ERR_STATE.  fdm_flame_forward: device pointers except frames; lmk, xforms, posefeat, transl, extra, frames may be NULL (frames
+ * NULL: every clip has L_max frames).  Launches on `stream`, never synchronises -- except that a call larger than any before it grows
+ * the object's scratch first, which waits for the device.  An object holds ONE scratch: it serves one stream at a time.  Every check is
+ * made before the first launch: FDM_ERR_ARG (null f / pose / verts, null shape with NS > 0 or expr with NE > 0, NS outside [0, expr_at],
+ * NE outside [0, NB - expr_at], shape_rows not 1 or B, lmk without an embedding), FDM_ERR_SHAPE (B or L_max < 1, frames[b] outside
+ * [0, L_max]).  Not built: the dynamic contour landmarks, fitting pose from vertices, fp16 output.  Call times: profiles/flame_out/README.md. */
+typedef struct fdm_flame_model {
+  int V, J, NB, expr_at;
+  const float* v_template; const float* shapedirs; const float* posedirs; const float* j_regressor;
+  const int* parents; const float* lbs_weights;
+} fdm_flame_model;
+typedef struct fdm_flame fdm_flame;
+int fdm_flame_tables_host(const fdm_flame_model* m, float* D, float* JT, float* JD);
+int fdm_flame_create(const fdm_flame_model* m, const int* lmk_verts, const float* lmk_bary, int NL, fdm_flame** out);
+int fdm_flame_forward(fdm_flame* f, const float* shape, int NS, int shape_rows, const float* expr, int NE, const float* pose, const float* transl,
+                      const float* extra, const int* frames, int B, int L_max, float* verts, float* lmk, float* xforms, float* posefeat,
+                      void* stream);
+int fdm_flame_destroy(fdm_flame* f);
+
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
  * (diffusion_BIWI_encoder_decoder.py:565-603: cosine schedule in fp64, fp32 cast); DDIM pairs and per-pair coefficients
  * (:684-708, eta = 0; returns the number of live pairs, the dead (t, -1) pair excluded); get_slopes (models/fdm_vocaset.py:96-106);
