@@ -3,6 +3,7 @@
 // All of these are bandwidth kernels: 16-byte accesses per lane, no re-reads, grid-stride where large.
 #pragma once
 #include "common.hpp"
+#include "handoff.hpp"    // interp_taps: the frame-rate rule of linear_interp_kernel
 #include "sched.hpp"
 #include "../../include/fdm_hip.h"
 #include "host.hpp"      // grid_for: the 1-D launch grid
@@ -927,17 +928,16 @@ __global__ __launch_bounds__(256) void motion_final_kernel(const double* partial
 
 // F.interpolate(mode='linear', align_corners=True) over time, channels-last x [B, Tin, C] -> y [B, Tout, C]
 // (linear_interpolation, models/hubert.py:62-69 / models/wav2vec.py:61-67: the 50 -> 30 fps resampling of the audio features)
+// The taps are interp_taps (handoff.hpp), the one statement of the rule.
 __global__ void linear_interp_kernel(const float* x, float* y, int B, int Tin, int Tout, int C) {
   const size_t n = (size_t)B * Tout * C;
-  const float scale = Tout > 1 ? (float)(Tin - 1) / (float)(Tout - 1) : 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const int t = (int)((i / C) % Tout);
     const int b = (int)(i / ((size_t)C * Tout));
-    const float src = __fmul_rn(scale, (float)t);
-    const int i0 = min((int)src, Tin - 1);
-    const int i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
-    const float l1 = __fsub_rn(src, (float)i0), l0 = __fsub_rn(1.f, l1);
+    int i0, i1;
+    float l0, l1;
+    interp_taps(Tin, Tout, t, i0, i1, l0, l1);
     const float* xb = x + (size_t)b * Tin * C + c;
     y[i] = __fadd_rn(__fmul_rn(l0, xb[(size_t)i0 * C]), __fmul_rn(l1, xb[(size_t)i1 * C]));
   }

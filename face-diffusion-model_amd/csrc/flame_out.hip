@@ -11,17 +11,13 @@
 #include "flame_out.hpp"
 #include "host.hpp"
 
-struct fdm_flame {
+struct fdm_flame : fdm::Handoff {         // lens: frames per clip
   int V = 0, J = 0, NB = 0, expr_at = 0, NL = 0, chunks = 0;
   std::vector<int> parents;
-  fdm::Arena mem;
   float *D = nullptr, *T = nullptr, *JT = nullptr, *JD = nullptr, *wts = nullptr, *lb = nullptr;   // device: the model
   int *par = nullptr, *lv = nullptr;
-  int* lens = nullptr;          // device: frames per clip of the call in flight
-  long long lens_cap = 0;
   float *xf = nullptr, *pf = nullptr, *cf = nullptr, *vid = nullptr;       // scratch of the call in flight
   long long xf_cap = 0, pf_cap = 0, cf_cap = 0, vid_cap = 0;
-  bool on_device = false;
 };
 
 namespace {
@@ -35,7 +31,7 @@ int finite_field(const char* who, const char* field, const float* p, long long n
 
 int check_model(const char* who, const fdm_flame_model* m) {
   if (!m) return fail(FDM_ERR_ARG, "%s: null model", who);
-  if (m->V < 1 || m->V > 0x7fffffff / 3 - FLAME_CHUNK) return fail(FDM_ERR_ARG, "%s: V = %d (3 V is a positive 32-bit int)", who, m->V);
+  if (m->V < 1 || m->V > 0x7fffffff / 3 - ROW_CHUNK) return fail(FDM_ERR_ARG, "%s: V = %d (3 V is a positive 32-bit int)", who, m->V);
   if (m->J < 1 || m->J > FLAME_JMAX) return fail(FDM_ERR_ARG, "%s: J = %d (1..%d)", who, m->J, FLAME_JMAX);
   if (m->NB < 0 || m->NB > FLAME_NBMAX) return fail(FDM_ERR_ARG, "%s: NB = %d (0..%d)", who, m->NB, FLAME_NBMAX);
   if (m->expr_at < 0 || m->expr_at > m->NB) return fail(FDM_ERR_ARG, "%s: expr_at = %d (0..NB = %d)", who, m->expr_at, m->NB);
@@ -109,46 +105,28 @@ int fdm_flame_create(const fdm_flame_model* m, const int* lmk_verts, const float
   const int V = m->V, J = m->J, NB = m->NB, P = 9 * (J - 1);
   const long long V3 = 3LL * V;
   F->V = V; F->J = J; F->NB = NB; F->expr_at = m->expr_at; F->NL = NL;
-  F->chunks = (int)((V3 + FLAME_CHUNK - 1) / FLAME_CHUNK);
+  F->chunks = (int)((V3 + ROW_CHUNK - 1) / ROW_CHUNK);
   F->parents.assign(m->parents, m->parents + J);
   F->parents[0] = 0;
-  if (fdm_device_ok()) {
-    auto upload = [&]() {
-      const size_t ld = (size_t)F->chunks * FLAME_CHUNK;
-      std::vector<float> D((size_t)(NB + P) * ld, 0.f), T(ld, 0.f), JT((size_t)3 * J), JD((size_t)NB * 3 * J);
-      tables(m, D.data(), (long long)ld, JT.data(), JD.data());
-      for (long long i = 0; i < V3; ++i) T[i] = m->v_template[i];
-      auto put = [&](auto** dst, const auto* src, size_t n) {
-        FCK(F->mem.alloc_t(dst, n));
-        if (n) HIPCK(hipMemcpy(*dst, src, n * sizeof(**dst), hipMemcpyHostToDevice));
-        return (int)FDM_OK;
-      };
-      FCK(put(&F->D, D.data(), D.size()));
-      FCK(put(&F->T, T.data(), T.size()));
-      FCK(put(&F->JT, JT.data(), JT.size()));
-      FCK(put(&F->JD, JD.data(), JD.size()));
-      FCK(put(&F->wts, m->lbs_weights, (size_t)V * J));
-      FCK(put(&F->par, F->parents.data(), (size_t)J));
-      if (NL) { FCK(put(&F->lv, lmk_verts, (size_t)3 * NL)); FCK(put(&F->lb, lmk_bary, (size_t)3 * NL)); }
-      HIPCK(hipFuncSetAttribute((const void*)flame_skin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)flame_skin_lds(FLAME_NBMAX + 9 * (FLAME_JMAX - 1), FLAME_JMAX)));
-      return (int)FDM_OK;
-    };
-    const int r = upload();
-    if (r != FDM_OK) { F->mem.release(); delete F; return r; }
-    F->on_device = true;
-  }
-  *out = F;
-  return FDM_OK;
+  return handoff_finish(F, out, [&]() {
+    const size_t ld = (size_t)F->chunks * ROW_CHUNK;
+    std::vector<float> D((size_t)(NB + P) * ld, 0.f), T(ld, 0.f), JT((size_t)3 * J), JD((size_t)NB * 3 * J);
+    tables(m, D.data(), (long long)ld, JT.data(), JD.data());
+    for (long long i = 0; i < V3; ++i) T[i] = m->v_template[i];
+    FCK(put(F->mem, &F->D, D.data(), D.size()));
+    FCK(put(F->mem, &F->T, T.data(), T.size()));
+    FCK(put(F->mem, &F->JT, JT.data(), JT.size()));
+    FCK(put(F->mem, &F->JD, JD.data(), JD.size()));
+    FCK(put(F->mem, &F->wts, m->lbs_weights, (size_t)V * J));
+    FCK(put(F->mem, &F->par, F->parents.data(), (size_t)J));
+    if (NL) { FCK(put(F->mem, &F->lv, lmk_verts, (size_t)3 * NL)); FCK(put(F->mem, &F->lb, lmk_bary, (size_t)3 * NL)); }
+    HIPCK(hipFuncSetAttribute((const void*)flame_skin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)flame_skin_lds(FLAME_NBMAX + 9 * (FLAME_JMAX - 1), FLAME_JMAX)));
+    return (int)FDM_OK;
+  });
 }
 
-int fdm_flame_destroy(fdm_flame* F) {
-  if (!F) return FDM_OK;
-  if (F->on_device) (void)hipDeviceSynchronize();
-  F->mem.release();
-  delete F;
-  return FDM_OK;
-}
+int fdm_flame_destroy(fdm_flame* F) { return handoff_destroy(F); }
 
 int fdm_flame_forward(fdm_flame* F, const float* shape, int NS, int shape_rows, const float* expr, int NE, const float* pose, const float* transl,
                       const float* extra, const int* frames, int B, int L_max, float* verts, float* lmk, float* xforms, float* posefeat,
@@ -160,25 +138,22 @@ int fdm_flame_forward(fdm_flame* F, const float* shape, int NS, int shape_rows, 
   if (lmk && !F->NL) return fail(FDM_ERR_ARG, "flame_forward: landmarks asked of an object made without an embedding");
   if (B < 1 || L_max < 1) return fail(FDM_ERR_SHAPE, "flame_forward: B = %d, L_max = %d", B, L_max);
   if (shape_rows != 1 && shape_rows != B) return fail(FDM_ERR_ARG, "flame_forward: shape_rows = %d (1 or B = %d)", shape_rows, B);
-  std::vector<int> hl((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    hl[b] = frames ? frames[b] : L_max;
-    if (hl[b] < 0 || hl[b] > L_max) return fail(FDM_ERR_SHAPE, "flame_forward: clip %d has %d frames, the batch is %d long", b, hl[b], L_max);
-  }
+  std::vector<int> hl;
+  const ClipLens c = clip_lens(frames, B, L_max, 0.0, 0.0, 0, hl);
+  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "flame_forward: clip %d has %d frames, the batch is %d long", c.clip, c.L, L_max);
   const long long rows = (long long)B * L_max;
   if (rows > 0x7fffffffLL - 64 || F->chunks > 65535)
     return fail(FDM_ERR_SHAPE, "flame_forward: %lld rows of %d vertices exceed one launch", rows, F->V);
-  if (!F->on_device || !fdm_device_ok()) return fail(FDM_ERR_STATE, "flame_forward: no gfx950 device visible (there is no CPU fallback)");
+  FCK(handoff_device(*F, "flame_forward"));
   hipStream_t s = (hipStream_t)stream;
-  const int J = F->J, P = 9 * (J - 1), NT = NE + P, V3 = 3 * F->V, ld = F->chunks * FLAME_CHUNK;
-  const long long tiles = (rows + FLAME_FT - 1) / FLAME_FT;
-  FCK(grow(F->mem, &F->lens, &F->lens_cap, (long long)B));
-  FCK(grow(F->mem, &F->xf, &F->xf_cap, tiles * FLAME_FT * J * 12));
+  const int J = F->J, P = 9 * (J - 1), NT = NE + P, V3 = 3 * F->V, ld = F->chunks * ROW_CHUNK;
+  const long long tiles = (rows + ROW_TILE - 1) / ROW_TILE;
+  FCK(grow(F->mem, &F->xf, &F->xf_cap, tiles * ROW_TILE * J * 12));
   FCK(grow(F->mem, &F->pf, &F->pf_cap, rows * P));
-  FCK(grow(F->mem, &F->cf, &F->cf_cap, tiles * NT * FLAME_FT));
+  FCK(grow(F->mem, &F->cf, &F->cf_cap, tiles * NT * ROW_TILE));
   FCK(grow(F->mem, &F->vid, &F->vid_cap, (long long)shape_rows * ld));
-  HIPCK(hipMemcpyAsync(F->lens, hl.data(), hl.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(flame_pose_kernel, dim3((unsigned)((tiles * FLAME_FT + 63) / 64)), dim3(64), 0, s, shape, shape_rows, NS, expr, NE, pose,
+  FCK(handoff_lens(*F, hl, s));
+  hipLaunchKernelGGL(flame_pose_kernel, dim3((unsigned)((tiles * ROW_TILE + 63) / 64)), dim3(64), 0, s, shape, shape_rows, NS, expr, NE, pose,
                      (const int*)F->lens, L_max, (int)rows, J, F->expr_at, (const float*)F->JT, (const float*)F->JD, (const int*)F->par, F->xf, F->pf,
                      F->cf);
   hipLaunchKernelGGL(flame_shape_kernel, dim3((unsigned)((ld / 4 + 255) / 256), (unsigned)shape_rows), dim3(256), 0, s, (const float*)F->T,

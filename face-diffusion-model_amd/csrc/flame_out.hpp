@@ -5,17 +5,16 @@
 //                       folded regressor (JT + JD coef), a Rodrigues rotation per joint, the kinematic chain made relative to the rest
 //                       joints, the pose feature.  The chain reads its parent by a run-time index, so the joints and the chain live in LDS
 //                       columns (element-major: lane l reads bank l), never in indexed registers: no scratch.  It also writes the row's
-//                       blend coefficients (expression, then pose feature) transposed per tile of FLAME_FT rows, [tile][term][FLAME_FT],
+//                       blend coefficients (expression, then pose feature) transposed per tile of ROW_TILE rows, [tile][term][ROW_TILE],
 //                       which is what flame_skin_kernel reads.
 //   flame_shape_kernel  v_id = v_template + sum_k shape_k D_k per shape row, 16 bytes per lane, fused multiply-adds, k ascending.
-//   flame_skin_kernel   grid (tiles of FLAME_FT rows, chunks of FLAME_CHUNK elements of 3V), ONE wavefront per workgroup.  The tile's
+//   flame_skin_kernel   grid (tiles of ROW_TILE rows, chunks of ROW_CHUNK elements of 3V), ONE wavefront per workgroup.  The tile's
 //                       coefficients, transforms and the chunk's skinning weights are staged in LDS (wave-uniform reads are broadcasts).
-//                       Each lane holds FLAME_FT x 12 accumulators (16-byte pieces lane + 64 q of the chunk) and walks the terms in
+//                       Each lane holds ROW_TILE x 12 accumulators (16-byte pieces lane + 64 q of the chunk) and walks the terms in
 //                       ascending order: one 16-byte load of D per piece (rows padded with zeros to whole chunks, so aligned and in
 //                       bounds; the slab of a chunk is shared by every tile of the chunk: workgroup ids run over the tiles first, so it
-//                       is served by the L2), FLAME_FT x 12 fused multiply-adds.  Then per row: the blended chunk goes to a 3 KB LDS row;
-//                       `extra` is added there (a row starts on a 4-byte boundary only, 12 V bytes per row, so each row is peeled to its
-//                       own 16-byte boundary: <= 3 single loads, 16-byte loads for the body, <= 3 single loads behind it); the lanes
+//                       is served by the L2), ROW_TILE x 12 fused multiply-adds.  Then per row: the blended chunk goes to a 3 KB LDS row;
+//                       `extra` is added there through the 16-byte peel of handoff.hpp (a row starts on a 4-byte boundary only); the lanes
 //                       change to one vertex each (lane + 64 i: stride-3 reads, conflict-free), blend the transforms in ascending joint
 //                       order, apply them and write the vertex back; the row leaves through the same peel as 16-byte stores.  Plain
 //                       VALU: the fp32 MFMA rate on gfx950 is the vector rate, and the order of the sum is part of the rule.
@@ -25,14 +24,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-
 #include "../../include/fdm_hip.h"
+#include "handoff.hpp"
 
 namespace fdm {
 
-constexpr int FLAME_CHUNK = 768;          // elements of 3V per workgroup of flame_skin_kernel (12 per lane; 256 whole vertices)
-constexpr int FLAME_FT = 8;               // rows of [B * L_max] per workgroup of flame_skin_kernel
+// (flame_skin_kernel's geometry is handoff.hpp's: ROW_CHUNK elements of 3V = 256 whole vertices and ROW_TILE rows per workgroup)
 constexpr int FLAME_JMAX = 8;
 constexpr int FLAME_NBMAX = 512;
 constexpr int FLAME_NLMAX = 256;
@@ -43,25 +40,23 @@ __device__ __forceinline__ float flame_dot3(float a0, float a1, float a2, float 
 }
 
 // shape [shape_rows][NS], expr [rows][NE], pose [rows][3 J]; lens [B]; JT [3 J], JD [NB][3 J], parents [J].
-// xf [tiles * FLAME_FT][J][12] (row-major 3 x 4 per joint), pf [rows][9 (J - 1)], cf [tiles][NE + 9 (J - 1)][FLAME_FT].  Dead rows: zeros.
+// xf [tiles * ROW_TILE][J][12] (row-major 3 x 4 per joint), pf [rows][9 (J - 1)], cf [tiles][NE + 9 (J - 1)][ROW_TILE].  Dead rows: zeros.
 __global__ __launch_bounds__(64) void flame_pose_kernel(const float* shape, int shape_rows, int NS, const float* expr, int NE, const float* pose,
                                                        const int* lens, int L_max, int rows, int J, int expr_at, const float* JT, const float* JD,
                                                        const int* parents, float* xf, float* pf, float* cf) {
   __shared__ float sJ[3 * FLAME_JMAX][64];                  // the row's joints
   __shared__ float sG[12 * FLAME_JMAX][64];                 // the row's chain (world transforms)
   const int tid = threadIdx.x;
-  const int row = blockIdx.x * 64 + tid;                    // < tiles * FLAME_FT rounded up to 64: guarded below
-  const int rows_pad = (rows + FLAME_FT - 1) / FLAME_FT * FLAME_FT;
+  const int row = blockIdx.x * 64 + tid;                    // < tiles * ROW_TILE rounded up to 64: guarded below
+  const int rows_pad = (rows + ROW_TILE - 1) / ROW_TILE * ROW_TILE;
   if (row >= rows_pad) return;
   const int J3 = 3 * J, P = 9 * (J - 1), NT = NE + P;
   float* ox = xf + (size_t)row * J * 12;
-  float* oc = cf + ((size_t)(row / FLAME_FT) * NT) * FLAME_FT + (row % FLAME_FT);
-  bool live = false;
-  int b = 0;
-  if (row < rows) { b = row / L_max; live = row - b * L_max < lens[b]; }
-  if (!live) {
+  float* oc = cf + ((size_t)(row / ROW_TILE) * NT) * ROW_TILE + (row % ROW_TILE);
+  int b;
+  if (!row_live(lens, 1, 0, row, L_max, rows, b)) {
     for (int i = 0; i < J * 12; ++i) ox[i] = 0.f;
-    for (int i = 0; i < NT; ++i) oc[(size_t)i * FLAME_FT] = 0.f;
+    for (int i = 0; i < NT; ++i) oc[(size_t)i * ROW_TILE] = 0.f;
     if (row < rows) for (int i = 0; i < P; ++i) pf[(size_t)row * P + i] = 0.f;
     return;
   }
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(64) void flame_pose_kernel(const float* shape, int 
   const float* ex = expr + (size_t)row * NE;
   for (int k = 0; k < NE; ++k) {
     const float c = ex[k];
-    oc[(size_t)k * FLAME_FT] = c;
+    oc[(size_t)k * ROW_TILE] = c;
     const float* d = JD + (size_t)(expr_at + k) * J3;
 #pragma unroll
     for (int i = 0; i < 3 * FLAME_JMAX; ++i) if (i < J3) jf[i] = __fadd_rn(jf[i], __fmul_rn(c, d[i]));
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(64) void flame_pose_kernel(const float* shape, int 
       for (int e = 0; e < 9; ++e) {
         const float f = __fsub_rn(R[e], e % 4 == 0 ? 1.f : 0.f);
         pf[(size_t)row * P + 9 * (j - 1) + e] = f;
-        oc[(size_t)(NE + 9 * (j - 1) + e) * FLAME_FT] = f;
+        oc[(size_t)(NE + 9 * (j - 1) + e) * ROW_TILE] = f;
       }
     }
     const float jx = sJ[3 * j][tid], jy = sJ[3 * j + 1][tid], jz = sJ[3 * j + 2][tid];
@@ -157,8 +152,8 @@ struct FlameSkinArgs {
   const float* vid; int shape_rows;       // [shape_rows][ld]
   const float* D; int ld;                 // [NB + 9 (J - 1)][ld]
   int row_expr, NE, row_pose, P;          // the terms: D rows row_expr + k (k < NE), then row_pose + p (p < P)
-  const float* cf;                        // [tiles][NE + P][FLAME_FT]
-  const float* xf;                        // [tiles * FLAME_FT][J][12]
+  const float* cf;                        // [tiles][NE + P][ROW_TILE]
+  const float* xf;                        // [tiles * ROW_TILE][J][12]
   const float* wts; int J;                // [V][J]
   const float* transl;                    // [rows][3] or null
   const float* extra;                     // [rows][V3] or null
@@ -166,85 +161,73 @@ struct FlameSkinArgs {
   float* out;                             // [rows][V3]
 };
 
-// dynamic LDS (floats): cf (NE + P) * FLAME_FT | xf FLAME_FT * J * 12 | weights J * 256 | one row FLAME_CHUNK
-__host__ __device__ inline size_t flame_skin_lds(int NT, int J) { return ((size_t)NT * FLAME_FT + (size_t)FLAME_FT * J * 12 + (size_t)J * 256 + FLAME_CHUNK) * sizeof(float); }
+// dynamic LDS (floats): cf (NE + P) * ROW_TILE | xf ROW_TILE * J * 12 | weights J * 256 | one row ROW_CHUNK
+__host__ __device__ inline size_t flame_skin_lds(int NT, int J) { return ((size_t)NT * ROW_TILE + (size_t)ROW_TILE * J * 12 + (size_t)J * 256 + ROW_CHUNK) * sizeof(float); }
 
 __global__ __launch_bounds__(64) void flame_skin_kernel(const FlameSkinArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int NT = a.NE + a.P, J = a.J;
-  float* s_cf = reinterpret_cast<float*>(smem);             // [NT][FLAME_FT]
-  float* s_xf = s_cf + NT * FLAME_FT;                       // [FLAME_FT][J][12]
-  float* s_w = s_xf + FLAME_FT * J * 12;                    // [J][256]
-  float* s_v = s_w + J * 256;                               // [FLAME_CHUNK]
+  float* s_cf = reinterpret_cast<float*>(smem);             // [NT][ROW_TILE]
+  float* s_xf = s_cf + NT * ROW_TILE;                       // [ROW_TILE][J][12]
+  float* s_w = s_xf + ROW_TILE * J * 12;                    // [J][256]
+  float* s_v = s_w + J * 256;                               // [ROW_CHUNK]
   const int lane = threadIdx.x;
-  const int row0 = blockIdx.x * FLAME_FT, c0 = blockIdx.y * FLAME_CHUNK;
-  const int n = min(FLAME_CHUNK, a.V3 - c0);                // live elements of the chunk: a multiple of 3
-  int clip[FLAME_FT];
-  bool live[FLAME_FT], any = false;
+  const int row0 = blockIdx.x * ROW_TILE, c0 = blockIdx.y * ROW_CHUNK;
+  const int n = min(ROW_CHUNK, a.V3 - c0);                // live elements of the chunk: a multiple of 3
+  int clip[ROW_TILE];
+  bool live[ROW_TILE], any = false;
 #pragma unroll
-  for (int r = 0; r < FLAME_FT; ++r) {
+  for (int r = 0; r < ROW_TILE; ++r) {
     const int row = row0 + r;
-    clip[r] = 0; live[r] = false;
-    if (row < a.rows) { clip[r] = row / a.L_max; live[r] = row - clip[r] * a.L_max < a.lens[clip[r]]; }
+    live[r] = row_live(a.lens, 1, 0, row, a.L_max, a.rows, clip[r]);
     any |= live[r];
   }
   {
-    const float4* g = reinterpret_cast<const float4*>(a.cf + (size_t)blockIdx.x * NT * FLAME_FT);
-    for (int i = lane; i < NT * FLAME_FT / 4; i += 64) reinterpret_cast<float4*>(s_cf)[i] = g[i];
+    const float4* g = reinterpret_cast<const float4*>(a.cf + (size_t)blockIdx.x * NT * ROW_TILE);
+    for (int i = lane; i < NT * ROW_TILE / 4; i += 64) reinterpret_cast<float4*>(s_cf)[i] = g[i];
     const float4* x = reinterpret_cast<const float4*>(a.xf + (size_t)row0 * J * 12);
-    for (int i = lane; i < FLAME_FT * J * 3; i += 64) reinterpret_cast<float4*>(s_xf)[i] = x[i];
+    for (int i = lane; i < ROW_TILE * J * 3; i += 64) reinterpret_cast<float4*>(s_xf)[i] = x[i];
     const int nv = n / 3, v0 = c0 / 3;
     for (int i = lane; i < nv * J; i += 64) s_w[(i % J) * 256 + i / J] = a.wts[(size_t)v0 * J + i];
   }
   __syncthreads();
-  constexpr int Q = FLAME_CHUNK / 256;                      // 16-byte pieces per lane and row
-  float4 acc[FLAME_FT][Q];
+  float4 acc[ROW_TILE][ROW_Q];
   if (any) {                                                // (uniform over the workgroup)
 #pragma unroll
-    for (int r = 0; r < FLAME_FT; ++r) {
+    for (int r = 0; r < ROW_TILE; ++r) {
       const float* v = a.vid + (size_t)(a.shape_rows == 1 ? 0 : clip[r]) * a.ld + c0;
 #pragma unroll
-      for (int q = 0; q < Q; ++q) acc[r][q] = *reinterpret_cast<const float4*>(v + 4 * (lane + 64 * q));
+      for (int q = 0; q < ROW_Q; ++q) acc[r][q] = *reinterpret_cast<const float4*>(v + 4 * (lane + 64 * q));
     }
     for (int t = 0; t < NT; ++t) {
       const float* dk = a.D + (size_t)(t < a.NE ? a.row_expr + t : a.row_pose + (t - a.NE)) * a.ld + c0;
-      float4 d[Q];
+      float4 d[ROW_Q];
 #pragma unroll
-      for (int q = 0; q < Q; ++q) d[q] = *reinterpret_cast<const float4*>(dk + 4 * (lane + 64 * q));
-      const float4 ca = *reinterpret_cast<const float4*>(s_cf + t * FLAME_FT), cb = *reinterpret_cast<const float4*>(s_cf + t * FLAME_FT + 4);
-      const float c[FLAME_FT] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
+      for (int q = 0; q < ROW_Q; ++q) d[q] = *reinterpret_cast<const float4*>(dk + 4 * (lane + 64 * q));
+      const float4 ca = *reinterpret_cast<const float4*>(s_cf + t * ROW_TILE), cb = *reinterpret_cast<const float4*>(s_cf + t * ROW_TILE + 4);
+      const float c[ROW_TILE] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
 #pragma unroll
-      for (int r = 0; r < FLAME_FT; ++r)
+      for (int r = 0; r < ROW_TILE; ++r)
 #pragma unroll
-        for (int q = 0; q < Q; ++q) {
+        for (int q = 0; q < ROW_Q; ++q) {
           acc[r][q].x = __builtin_fmaf(c[r], d[q].x, acc[r][q].x); acc[r][q].y = __builtin_fmaf(c[r], d[q].y, acc[r][q].y);
           acc[r][q].z = __builtin_fmaf(c[r], d[q].z, acc[r][q].z); acc[r][q].w = __builtin_fmaf(c[r], d[q].w, acc[r][q].w);
         }
     }
   }
 #pragma unroll
-  for (int r = 0; r < FLAME_FT; ++r) {
+  for (int r = 0; r < ROW_TILE; ++r) {
     const int row = row0 + r;
     if (row >= a.rows) break;                               // (uniform)
     float* dst = a.out + (size_t)row * a.V3 + c0;
-    // the row's own 16-byte boundary: head single elements, nb 16-byte pieces, then the rest
-    const int head = min(n, (int)((4 - (((uintptr_t)dst >> 2) & 3)) & 3));
-    const int nb = (n - head) >> 2, done = head + 4 * nb;
+    const Peel pd = peel_of(dst, n);                        // the row's own 16-byte boundary
     if (live[r]) {
 #pragma unroll
-      for (int q = 0; q < Q; ++q) *reinterpret_cast<float4*>(s_v + 4 * (lane + 64 * q)) = acc[r][q];
+      for (int q = 0; q < ROW_Q; ++q) *reinterpret_cast<float4*>(s_v + 4 * (lane + 64 * q)) = acc[r][q];
       __syncthreads();
       if (a.extra) {                                        // `extra` rows are 4-byte aligned like the output's: a peel of their own
         const float* src = a.extra + (size_t)row * a.V3 + c0;
-        const int he = min(n, (int)((4 - (((uintptr_t)src >> 2) & 3)) & 3));
-        const int ne = (n - he) >> 2, de = he + 4 * ne;
-        for (int m = lane; m < ne; m += 64) {
-          const float4 e = *reinterpret_cast<const float4*>(src + he + 4 * m);
-          float* q = s_v + he + 4 * m;
-          q[0] = __fadd_rn(q[0], e.x); q[1] = __fadd_rn(q[1], e.y); q[2] = __fadd_rn(q[2], e.z); q[3] = __fadd_rn(q[3], e.w);
-        }
-        if (lane < he) s_v[lane] = __fadd_rn(s_v[lane], src[lane]);
-        if (lane >= 32 && lane - 32 < n - de) s_v[de + lane - 32] = __fadd_rn(s_v[de + lane - 32], src[de + lane - 32]);
+        peel_walk<64, 32>(peel_of(src, n), n, lane, PeelAdd{src, s_v});
         __syncthreads();
       }
       const float* X = s_xf + r * J * 12;
@@ -271,15 +254,10 @@ __global__ __launch_bounds__(64) void flame_skin_kernel(const FlameSkinArgs a) {
         s_v[3 * vl] = o[0]; s_v[3 * vl + 1] = o[1]; s_v[3 * vl + 2] = o[2];
       }
     } else {
-      for (int i = lane; i < FLAME_CHUNK; i += 64) s_v[i] = 0.f;
+      for (int i = lane; i < ROW_CHUNK; i += 64) s_v[i] = 0.f;
     }
     __syncthreads();
-    for (int m = lane; m < nb; m += 64) {
-      const float* q = s_v + head + 4 * m;
-      *reinterpret_cast<float4*>(dst + head + 4 * m) = make_float4(q[0], q[1], q[2], q[3]);
-    }
-    if (lane < head) dst[lane] = s_v[lane];
-    if (lane >= 32 && lane - 32 < n - done) dst[done + lane - 32] = s_v[done + lane - 32];
+    peel_walk<64, 32>(pd, n, lane, PeelStore{dst, s_v});
     __syncthreads();
   }
 }
@@ -290,9 +268,9 @@ __global__ __launch_bounds__(256) void flame_lmk_kernel(const float* out, const 
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)rows * NL) return;
   const int row = (int)(i / NL), l = (int)(i - (long long)row * NL);
-  const int b = row / L_max;
   float* o = lmk + (size_t)i * 3;
-  if (row - b * L_max >= lens[b]) { o[0] = o[1] = o[2] = 0.f; return; }
+  int b;
+  if (!row_live(lens, 1, 0, row, L_max, b)) { o[0] = o[1] = o[2] = 0.f; return; }
   const float* p = out + (size_t)row * V3;
   const float* p0 = p + 3 * (size_t)lv[3 * l];
   const float* p1 = p + 3 * (size_t)lv[3 * l + 1];

@@ -1,5 +1,6 @@
 // Host-side helpers shared by the C layers of libfdm_hip.so (fdm_hip.hip, plan.hip, tune.hip, host_tables.hip, encoders.hip):
-// error macros, the operand-kind table, device-memory arenas and the operand / GEMM-argument constructors.  No device code;
+// error macros, the operand-kind table, device-memory arenas, the operand / GEMM-argument constructors, and what the hand-off units
+// (mesh_out.hip, rig_out.hip, flame_out.hip) share: the frame rule, the clip lengths of a call and the object lifecycle.  No device code;
 // the kernel units (gemm_*.hip, attn_*.hip) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +77,73 @@ inline int check_fps(const char* who, double fps_in, double fps_out) {
   return FDM_OK;
 }
 inline bool resamples(double fps_in, double fps_out) { return fps_in > 0.0 && fps_out > 0.0 && fps_in != fps_out; }
+
+// L_out of a clip of L frames (the rule of the audio encoder's interpolated length); < 0: does not fit an int
+inline long long frames_out_of(int L, double fps_in, double fps_out) {
+  if (L == 0 || !resamples(fps_in, fps_out)) return L;
+  const double x = (double)L / fps_in * fps_out;
+  if (!(x < 2147483648.0)) return -1;
+  const long long n = (long long)x;
+  return n < 1 ? 1 : n;
+}
+
+// The clip lengths of a hand-off call as the kernels read them: hl = {L, L_out} per clip, or L alone (L_out_max = 0: no frame rates).
+// frames: L per clip, null = L_max.  `bad` says what failed at clip `clip` (the caller words the refusal).
+struct ClipLens { enum { OK, LENGTH, OUTPUT } bad = OK; int clip = 0, L = 0; long long Lo = 0; };
+inline ClipLens clip_lens(const int* frames, int B, int L_max, double fps_in, double fps_out, int L_out_max, std::vector<int>& hl) {
+  const int per = L_out_max > 0 ? 2 : 1;
+  hl.resize((size_t)per * B);
+  ClipLens c;
+  for (c.clip = 0; c.clip < B; ++c.clip) {
+    c.L = frames ? frames[c.clip] : L_max;
+    if (c.L < 0 || c.L > L_max) { c.bad = ClipLens::LENGTH; return c; }
+    hl[(size_t)per * c.clip] = c.L;
+    if (per == 1) continue;
+    c.Lo = frames_out_of(c.L, fps_in, fps_out);
+    if (c.Lo < 0 || c.Lo > L_out_max) { c.bad = ClipLens::OUTPUT; return c; }
+    hl[2 * (size_t)c.clip + 1] = (int)c.Lo;
+  }
+  return c;
+}
+
+// ---- what the hand-off objects (fdm_mesh, fdm_rig, fdm_flame) share.  Made without a visible device, one refuses forward().
+struct Handoff {
+  Arena mem;
+  int* lens = nullptr;          // device: hl of clip_lens for the call in flight
+  long long lens_cap = 0;
+  bool on_device = false;
+};
+template <typename T, typename S> int put(Arena& mem, T** dst, const S* src, size_t n) {      // src in a new device array
+  FCK(mem.alloc_t(dst, n));
+  if (n) HIPCK(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return FDM_OK;
+}
+// the tail of *_create: with a device, run `upload` (on failure the object is released and deleted); hand the object out
+template <typename T, typename F> int handoff_finish(T* obj, T** out, F upload) {
+  if (fdm_device_ok()) {
+    const int r = upload();
+    if (r != FDM_OK) { obj->mem.release(); delete obj; return r; }
+    obj->on_device = true;
+  }
+  *out = obj;
+  return FDM_OK;
+}
+template <typename T> int handoff_destroy(T* obj) {
+  if (!obj) return FDM_OK;
+  if (obj->on_device) (void)hipDeviceSynchronize();
+  obj->mem.release();
+  delete obj;
+  return FDM_OK;
+}
+inline int handoff_device(const Handoff& h, const char* who) {
+  if (!h.on_device || !fdm_device_ok()) return fail(FDM_ERR_STATE, "%s: no gfx950 device visible (there is no CPU fallback)", who);
+  return FDM_OK;
+}
+inline int handoff_lens(Handoff& h, const std::vector<int>& hl, hipStream_t s) {
+  FCK(grow(h.mem, &h.lens, &h.lens_cap, (long long)hl.size()));
+  HIPCK(hipMemcpyAsync(h.lens, hl.data(), hl.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  return FDM_OK;
+}
 
 inline int need_weight(const std::map<std::string, Wt>& w, const char* who, const std::string& name, long long n, const float** out) {
   auto it = w.find(name);

@@ -10,31 +10,17 @@
 #include "host.hpp"
 #include "mesh_out.hpp"
 
-struct fdm_mesh {
+struct fdm_mesh : fdm::Handoff {          // lens: {L, L_out} per clip
   int F = 0, V = 0;
-  fdm::Arena mem;
   int *faces = nullptr, *adj_off = nullptr, *adj = nullptr;      // device: [F][3], [V + 1], [3F]
-  int* lens = nullptr;          // device: {L, L_out} per clip of the call in flight
-  long long lens_cap = 0;
   float* P = nullptr;           // fp32 positions of the call in flight when no fp32 planar output holds them
   long long P_cap = 0;
-  bool on_device = false;
 };
 
 namespace {
 using namespace fdm;
 
 const int MESH_FLAGS = FDM_MESH_INTERLEAVED | FDM_MESH_F16 | FDM_MESH_NORMALS;
-
-
-// L_out of a clip of L frames (the rule of the audio encoder's interpolated length); < 0: does not fit an int
-long long frames_out_of(int L, double fps_in, double fps_out) {
-  if (L == 0 || !resamples(fps_in, fps_out)) return L;
-  const double x = (double)L / fps_in * fps_out;
-  if (!(x < 2147483648.0)) return -1;
-  const long long n = (long long)x;
-  return n < 1 ? 1 : n;
-}
 
 // a triangle list over V vertices: every index inside [0, V), 3 F and 6 V inside an int
 int check_topology(const char* who, const int* faces, int F, int V) {
@@ -70,31 +56,15 @@ int fdm_mesh_create(const int* faces, int F, int V, fdm_mesh** out) {
   fdm_mesh* M = new (std::nothrow) fdm_mesh();
   if (!M) return fail(FDM_ERR_STATE, "mesh_create: out of memory");
   M->F = F; M->V = V;
-  if (fdm_device_ok()) {
-    auto upload = [&]() {
-      FCK(M->mem.alloc_t(&M->faces, (size_t)F * 3));
-      FCK(M->mem.alloc_t(&M->adj, (size_t)F * 3));
-      FCK(M->mem.alloc_t(&M->adj_off, (size_t)V + 1));
-      if (F) HIPCK(hipMemcpy(M->faces, faces, (size_t)F * 12, hipMemcpyHostToDevice));
-      if (F) HIPCK(hipMemcpy(M->adj, items.data(), (size_t)F * 12, hipMemcpyHostToDevice));
-      HIPCK(hipMemcpy(M->adj_off, off.data(), ((size_t)V + 1) * 4, hipMemcpyHostToDevice));
-      return (int)FDM_OK;
-    };
-    const int r = upload();
-    if (r != FDM_OK) { M->mem.release(); delete M; return r; }
-    M->on_device = true;
-  }
-  *out = M;
-  return FDM_OK;
+  return handoff_finish(M, out, [&]() {
+    FCK(put(M->mem, &M->faces, faces, (size_t)F * 3));
+    FCK(put(M->mem, &M->adj, items.data(), (size_t)F * 3));
+    FCK(put(M->mem, &M->adj_off, off.data(), (size_t)V + 1));
+    return (int)FDM_OK;
+  });
 }
 
-int fdm_mesh_destroy(fdm_mesh* M) {
-  if (!M) return FDM_OK;
-  if (M->on_device) (void)hipDeviceSynchronize();
-  M->mem.release();
-  delete M;
-  return FDM_OK;
-}
+int fdm_mesh_destroy(fdm_mesh* M) { return handoff_destroy(M); }
 
 int fdm_mesh_frames(int frames_in, double fps_in, double fps_out, int* frames_out) {
   if (!frames_out) return fail(FDM_ERR_ARG, "mesh_frames: null frames_out");
@@ -118,25 +88,20 @@ int fdm_mesh_forward(fdm_mesh* M, const float* offsets, const int* frames, int B
   if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "mesh_forward: tmpl_rows = %d with a null template", tmpl_rows);
   FCK(check_fps("mesh_forward", fps_in, fps_out));
   if (B < 1 || L_max < 1 || L_out_max < 1) return fail(FDM_ERR_SHAPE, "mesh_forward: B = %d, L_max = %d, L_out_max = %d", B, L_max, L_out_max);
-  std::vector<int> hl((size_t)2 * B);
-  for (int b = 0; b < B; ++b) {
-    const int L = frames ? frames[b] : L_max;
-    if (L < 0 || L > L_max) return fail(FDM_ERR_SHAPE, "mesh_forward: clip %d has %d frames, the batch is %d long", b, L, L_max);
-    const long long Lo = frames_out_of(L, fps_in, fps_out);
-    if (Lo < 0 || Lo > L_out_max) return fail(FDM_ERR_SHAPE, "mesh_forward: clip %d gives %lld frames, the output is %d long", b, Lo, L_out_max);
-    hl[2 * b] = L; hl[2 * b + 1] = (int)Lo;
-  }
+  std::vector<int> hl;
+  const ClipLens c = clip_lens(frames, B, L_max, fps_in, fps_out, L_out_max, hl);
+  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "mesh_forward: clip %d has %d frames, the batch is %d long", c.clip, c.L, L_max);
+  if (c.bad == ClipLens::OUTPUT) return fail(FDM_ERR_SHAPE, "mesh_forward: clip %d gives %lld frames, the output is %d long", c.clip, c.Lo, L_out_max);
   const long long rows = (long long)B * L_out_max, V3 = 3LL * M->V;
   const int nblk = (M->V + MESH_VB - 1) / MESH_VB;
   if (rows > 0x7fffffffLL || (rows + 7) / 8 * 8 * nblk > 0x7fffffffLL || (V3 + MESH_POS_TILE - 1) / MESH_POS_TILE > 65535)
     return fail(FDM_ERR_SHAPE, "mesh_forward: %lld output rows of %d vertices exceed one launch", rows, M->V);
-  if (!M->on_device || !fdm_device_ok()) return fail(FDM_ERR_STATE, "mesh_forward: no gfx950 device visible (there is no CPU fallback)");
+  FCK(handoff_device(*M, "mesh_forward"));
   hipStream_t s = (hipStream_t)stream;
   // fp32 positions for the normals: the planar fp32 output itself, scratch otherwise
   const bool own = normals && (inter || half);
-  FCK(grow(M->mem, &M->lens, &M->lens_cap, 2LL * B));
   if (own) FCK(grow(M->mem, &M->P, &M->P_cap, rows * V3));
-  HIPCK(hipMemcpyAsync(M->lens, hl.data(), hl.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  FCK(handoff_lens(*M, hl, s));
   const int rs = resamples(fps_in, fps_out) ? 1 : 0, tstride = tmpl_rows == B && B > 1 ? (int)V3 : 0;
   const float* tp = tmpl_rows ? tmpl : nullptr;
   const dim3 gp((unsigned)rows, (unsigned)((V3 + MESH_POS_TILE - 1) / MESH_POS_TILE));

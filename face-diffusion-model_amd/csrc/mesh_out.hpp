@@ -1,10 +1,10 @@
 // Kernels of the mesh hand-off (include/fdm_hip.h, fdm_mesh_*; launched by mesh_out.hip): decoded vertex offsets -> positions at the
 // consumer's frame rate and area-weighted vertex normals, planar or interleaved, fp32 or fp16.  DESIGN section 2 item 18 is the definition.
 //   mesh_pos_kernel   grid (rows of [B, L_out_max], blocks of MESH_POS_TILE elements of 3V): p = offset + template (one fp32 add), then,
-//                     when the rates differ, the time resampling of linear_interp_kernel (elementwise.hpp) in its own expression at the
-//                     clip's own length.  A thread owns elements 256 apart, so a wavefront's loads and stores are whole lines.  Writes the
-//                     planar position output (rounded at the store for fp16; rows at or past L_out[b] as zeros) and / or the fp32 copy
-//                     the normals are computed from (`P`: the fp32 planar output itself when there is one, scratch otherwise).
+//                     when the rates differ, the time resampling of interp_taps (handoff.hpp) at the clip's own length.  A thread owns
+//                     elements 256 apart, so a wavefront's loads and stores are whole lines.  Writes the planar position output
+//                     (rounded at the store for fp16; rows at or past L_out[b] as zeros) and / or the fp32 copy the normals are
+//                     computed from (`P`: the fp32 planar output itself when there is one, scratch otherwise).
 //   mesh_nrm_kernel   one workgroup = MESH_VB consecutive vertices of one output frame, one thread per vertex: walks the vertex's CSR
 //                     list of incident faces in ascending face index, recomputes each face normal from P (the frame's positions are 12 V
 //                     bytes: the gathers hit the L2) and adds it to a running sum that starts from the first term; normalises; stages
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fdm_hip.h"
+#include "handoff.hpp"
 
 namespace fdm {
 
@@ -28,19 +29,13 @@ constexpr int MESH_VB = 256;              // vertices per workgroup of mesh_nrm_
 template <typename PT>
 __global__ __launch_bounds__(256) void mesh_pos_kernel(const float* off, const float* tmpl, int tmpl_stride, const int* lens, int L_max,
                                                        int Lo_max, int V3, int resample, PT* pos, float* P) {
-  const int row = blockIdx.x, b = row / Lo_max, t = row - b * Lo_max;
-  const int L = lens[2 * b], Lo = lens[2 * b + 1];
-  const bool live = t < Lo;
+  const int row = blockIdx.x;
+  int b;
+  const bool live = row_live(lens, 2, 1, row, Lo_max, b);
+  const int t = row - b * Lo_max;
   int i0 = t, i1 = t;
   float l0 = 1.f, l1 = 0.f;
-  if (live && resample) {                 // linear_interp_kernel's expression with Tin = L, Tout = Lo
-    const float scale = Lo > 1 ? (float)(L - 1) / (float)(Lo - 1) : 0.f;
-    const float src = __fmul_rn(scale, (float)t);
-    i0 = min((int)src, L - 1);
-    i1 = i0 + (i0 < L - 1 ? 1 : 0);
-    l1 = __fsub_rn(src, (float)i0);
-    l0 = __fsub_rn(1.f, l1);
-  }
+  if (live && resample) interp_taps(lens[2 * b], lens[2 * b + 1], t, i0, i1, l0, l1);
   const float* x0 = off + ((size_t)b * L_max + i0) * V3;
   const float* x1 = off + ((size_t)b * L_max + i1) * V3;
   const float* tp = tmpl ? tmpl + (size_t)b * tmpl_stride : nullptr;
@@ -72,8 +67,8 @@ __global__ __launch_bounds__(MESH_VB) void mesh_nrm_kernel(const float* P, const
   const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
   const int row = (k / nblk) * 8 + xcd, blk = k % nblk;
   if (row >= rows) return;                                  // (uniform over the workgroup)
-  const int b = row / Lo_max, t = row - b * Lo_max;
-  const bool live = t < lens[2 * b + 1];
+  int b;
+  const bool live = row_live(lens, 2, 1, row, Lo_max, b);
   const int tid = threadIdx.x, v0 = blk * MESH_VB, v = v0 + tid;
   const float* p = P + (size_t)row * V * 3;
   float sx = 0.f, sy = 0.f, sz = 0.f;

@@ -11,16 +11,12 @@
 #include "host.hpp"
 #include "rig_out.hpp"
 
-struct fdm_rig {
+struct fdm_rig : fdm::Handoff {           // lens: {L, L_out} per clip
   int K = 0, V = 0, sweeps = 0, chunks = 0;
   bool bounded = false;
-  fdm::Arena mem;
-  float *P = nullptr, *G = nullptr, *Lc = nullptr, *lo = nullptr, *hi = nullptr;      // device: [K][chunks * RIG_CHUNK], [K][K] x 2, [K] x 2
-  int* lens = nullptr;          // device: {L, L_out} per clip of the call in flight
-  long long lens_cap = 0;
+  float *P = nullptr, *G = nullptr, *Lc = nullptr, *lo = nullptr, *hi = nullptr;      // device: [K][chunks * ROW_CHUNK], [K][K] x 2, [K] x 2
   float* part = nullptr;        // partial sums of the call in flight [chunks][B * L_max][K]
   long long part_cap = 0;
-  bool on_device = false;
 };
 
 namespace {
@@ -30,7 +26,7 @@ using namespace fdm;
 int check_basis(const char* who, const float* basis, const float* vweight, int K, int V, double ridge) {
   if (!basis) return fail(FDM_ERR_ARG, "%s: null basis", who);
   if (K < 1 || K > RIG_KMAX || V < 1) return fail(FDM_ERR_ARG, "%s: K = %d (1..%d), V = %d", who, K, RIG_KMAX, V);
-  if (V > 0x7fffffff / 3 - RIG_CHUNK) return fail(FDM_ERR_ARG, "%s: V = %d (3 V is a 32-bit int)", who, V);
+  if (V > 0x7fffffff / 3 - ROW_CHUNK) return fail(FDM_ERR_ARG, "%s: V = %d (3 V is a 32-bit int)", who, V);
   if (!(ridge >= 0.0) || std::isinf(ridge)) return fail(FDM_ERR_ARG, "%s: ridge = %g (finite and >= 0)", who, ridge);
   if (vweight)
     for (int v = 0; v < V; ++v)
@@ -101,70 +97,44 @@ int fdm_rig_create(const float* basis, int K, int V, const float* vweight, doubl
   if (!R) return fail(FDM_ERR_STATE, "rig_create: out of memory");
   const long long V3 = 3LL * V;
   R->K = K; R->V = V; R->sweeps = sweeps; R->bounded = lo != nullptr;
-  R->chunks = (int)((V3 + RIG_CHUNK - 1) / RIG_CHUNK);
-  if (fdm_device_ok()) {
-    auto upload = [&]() {
-      const size_t ldp = (size_t)R->chunks * RIG_CHUNK;
-      std::vector<float> P((size_t)K * ldp, 0.f);           // E diag(w) rounded to fp32, rows padded with zeros to whole chunks
-      for (int k = 0; k < K; ++k)
-        for (long long i = 0; i < V3; ++i)
-          P[k * ldp + i] = (float)((double)basis[k * V3 + i] * (vweight ? (double)vweight[i / 3] : 1.0));
-      FCK(R->mem.alloc_t(&R->P, P.size()));
-      FCK(R->mem.alloc_t(&R->G, g32.size()));
-      FCK(R->mem.alloc_t(&R->Lc, chol.size()));
-      HIPCK(hipMemcpy(R->P, P.data(), P.size() * sizeof(float), hipMemcpyHostToDevice));
-      HIPCK(hipMemcpy(R->G, g32.data(), g32.size() * sizeof(float), hipMemcpyHostToDevice));
-      HIPCK(hipMemcpy(R->Lc, chol.data(), chol.size() * sizeof(float), hipMemcpyHostToDevice));
-      if (lo) {
-        FCK(R->mem.alloc_t(&R->lo, (size_t)K));
-        FCK(R->mem.alloc_t(&R->hi, (size_t)K));
-        HIPCK(hipMemcpy(R->lo, lo, (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(R->hi, hi, (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-      }
-      HIPCK(hipFuncSetAttribute((const void*)rig_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds(RIG_KMAX)));
-      return (int)FDM_OK;
-    };
-    const int r = upload();
-    if (r != FDM_OK) { R->mem.release(); delete R; return r; }
-    R->on_device = true;
-  }
-  *out = R;
-  return FDM_OK;
+  R->chunks = (int)((V3 + ROW_CHUNK - 1) / ROW_CHUNK);
+  return handoff_finish(R, out, [&]() {
+    const size_t ldp = (size_t)R->chunks * ROW_CHUNK;
+    std::vector<float> P((size_t)K * ldp, 0.f);             // E diag(w) rounded to fp32, rows padded with zeros to whole chunks
+    for (int k = 0; k < K; ++k)
+      for (long long i = 0; i < V3; ++i)
+        P[k * ldp + i] = (float)((double)basis[k * V3 + i] * (vweight ? (double)vweight[i / 3] : 1.0));
+    FCK(put(R->mem, &R->P, P.data(), P.size()));
+    FCK(put(R->mem, &R->G, g32.data(), g32.size()));
+    FCK(put(R->mem, &R->Lc, chol.data(), chol.size()));
+    if (lo) { FCK(put(R->mem, &R->lo, lo, (size_t)K)); FCK(put(R->mem, &R->hi, hi, (size_t)K)); }
+    HIPCK(hipFuncSetAttribute((const void*)rig_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds(RIG_KMAX)));
+    return (int)FDM_OK;
+  });
 }
 
-int fdm_rig_destroy(fdm_rig* R) {
-  if (!R) return FDM_OK;
-  if (R->on_device) (void)hipDeviceSynchronize();
-  R->mem.release();
-  delete R;
-  return FDM_OK;
-}
+int fdm_rig_destroy(fdm_rig* R) { return handoff_destroy(R); }
 
 int fdm_rig_forward(fdm_rig* R, const float* offsets, const int* frames, int B, int L_max, double fps_in, double fps_out, float* coef,
                     float* proj, int L_out_max, int* frames_out, void* stream) {
   if (!R || !offsets || !coef) return fail(FDM_ERR_ARG, "rig_forward: null argument");
   FCK(check_fps("rig_forward", fps_in, fps_out));
   if (B < 1 || L_max < 1 || L_out_max < 1) return fail(FDM_ERR_SHAPE, "rig_forward: B = %d, L_max = %d, L_out_max = %d", B, L_max, L_out_max);
-  std::vector<int> hl((size_t)2 * B);
-  for (int b = 0; b < B; ++b) {
-    const int L = frames ? frames[b] : L_max;
-    if (L < 0 || L > L_max) return fail(FDM_ERR_SHAPE, "rig_forward: clip %d has %d frames, the batch is %d long", b, L, L_max);
-    int Lo = 0;
-    if (fdm_mesh_frames(L, fps_in, fps_out, &Lo) != FDM_OK || Lo > L_out_max)
-      return fail(FDM_ERR_SHAPE, "rig_forward: clip %d of %d frames at %g -> %g fps does not fit an output %d long", b, L, fps_in, fps_out, L_out_max);
-    hl[2 * b] = L; hl[2 * b + 1] = Lo;
-  }
+  std::vector<int> hl;
+  const ClipLens c = clip_lens(frames, B, L_max, fps_in, fps_out, L_out_max, hl);
+  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "rig_forward: clip %d has %d frames, the batch is %d long", c.clip, c.L, L_max);
+  if (c.bad == ClipLens::OUTPUT)
+    return fail(FDM_ERR_SHAPE, "rig_forward: clip %d of %d frames at %g -> %g fps does not fit an output %d long", c.clip, c.L, fps_in, fps_out, L_out_max);
   const long long rows_in = (long long)B * L_max, rows_out = (long long)B * L_out_max;
-  if (rows_in > 0x7fffffffLL - RIG_FT || rows_out > 0x7fffffffLL - RIG_SW || R->chunks > 65535)
+  if (rows_in > 0x7fffffffLL - ROW_TILE || rows_out > 0x7fffffffLL - RIG_SW || R->chunks > 65535)
     return fail(FDM_ERR_SHAPE, "rig_forward: %lld input and %lld output rows of %d vertices exceed one launch", rows_in, rows_out, R->V);
-  if (!R->on_device || !fdm_device_ok()) return fail(FDM_ERR_STATE, "rig_forward: no gfx950 device visible (there is no CPU fallback)");
+  FCK(handoff_device(*R, "rig_forward"));
   hipStream_t s = (hipStream_t)stream;
-  FCK(grow(R->mem, &R->lens, &R->lens_cap, 2LL * B));
   FCK(grow(R->mem, &R->part, &R->part_cap, (long long)R->chunks * rows_in * R->K));
-  HIPCK(hipMemcpyAsync(R->lens, hl.data(), hl.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  const dim3 gp((unsigned)((rows_in + RIG_FT - 1) / RIG_FT), (unsigned)R->chunks);
+  FCK(handoff_lens(*R, hl, s));
+  const dim3 gp((unsigned)((rows_in + ROW_TILE - 1) / ROW_TILE), (unsigned)R->chunks);
   hipLaunchKernelGGL(rig_proj_kernel, gp, dim3(256), 0, s, offsets, (const int*)R->lens, L_max, (int)rows_in, 3 * R->V, (const float*)R->P,
-                     R->chunks * RIG_CHUNK, R->K, R->part);
+                     R->chunks * ROW_CHUNK, R->K, R->part);
   const dim3 gs((unsigned)((rows_out + RIG_SW - 1) / RIG_SW));
   hipLaunchKernelGGL(rig_solve_kernel, gs, dim3(RIG_SW * 64), solve_lds(R->K), s, (const float*)R->part, R->chunks, (int)rows_in, (const int*)R->lens,
                      L_max, L_out_max, (int)rows_out, R->K, resamples(fps_in, fps_out) ? 1 : 0, (const float*)R->G, (const float*)R->Lc,

@@ -1,18 +1,17 @@
 // Kernels of the rig hand-off (include/fdm_hip.h, fdm_rig_*; launched by rig_out.hip): decoded vertex offsets -> blendshape coefficients
 // per frame, a ridge-regularised, box-constrained least-squares fit onto a basis.  DESIGN section 2 item 19 is the definition.
-//   rig_proj_kernel   grid (tiles of RIG_FT rows of [B * L_max], chunks of RIG_CHUNK elements of 3V), 4 wavefronts.  Stages the tile's
-//                     offsets in LDS: a row starts on a 4-byte boundary only (12 V bytes per row), so each row is peeled to its own
-//                     16-byte boundary (<= 3 single loads, 16-byte loads for the body, <= 3 single loads behind it) and lands at its
-//                     logical position; the chunk's tail is zero-filled.  Every wavefront then takes the whole tile into registers
-//                     (RIG_FT x RIG_CHUNK / 64 values per lane) and walks k = wave, wave + 4, ...: 16-byte loads of P[k] (rows padded
-//                     with zeros to whole chunks, so aligned and in bounds; K x RIG_CHUNK x 4 bytes per chunk, shared by every tile
-//                     of the chunk: workgroup ids run over the tiles first, so the slab is served by the L2), RIG_FT fused
-//                     multiply-add chains per lane, then a halving butterfly over the lanes (RIG_FT + 2 exchanges) whose shape is the
+//   rig_proj_kernel   grid (tiles of ROW_TILE rows of [B * L_max], chunks of ROW_CHUNK elements of 3V), 4 wavefronts.  Stages the tile's
+//                     offsets in LDS through the 16-byte peel of handoff.hpp (a row starts on a 4-byte boundary only), each element at
+//                     its logical position; the chunk's tail is zero-filled.  Every wavefront then takes the whole tile into registers
+//                     (ROW_TILE x ROW_CHUNK / 64 values per lane) and walks k = wave, wave + 4, ...: 16-byte loads of P[k] (rows padded
+//                     with zeros to whole chunks, so aligned and in bounds; K x ROW_CHUNK x 4 bytes per chunk, shared by every tile
+//                     of the chunk: workgroup ids run over the tiles first, so the slab is served by the L2), ROW_TILE fused
+//                     multiply-add chains per lane, then a halving butterfly over the lanes (ROW_TILE + 2 exchanges) whose shape is the
 //                     same for every row slot.  Partial sums go to part [chunk][row][k] through LDS (whole lines).  Plain VALU: the
 //                     fp32 MFMA rate on gfx950 is the vector rate, and the kernel is fed by the L2, not bound by either.
 //   rig_solve_kernel  one wavefront per output frame, RIG_SW frames per workgroup, coefficient k on lane k mod 64 (two registers at
 //                     K > 64).  r[k] = the partial sums of the frame's row in ascending chunk order, starting from the first; the
-//                     frame-rate rule of mesh_pos_kernel applied to r; then the Cholesky solve and the projected Gauss-Seidel sweeps
+//                     frame-rate rule (interp_taps, handoff.hpp) applied to r; then the Cholesky solve and the projected Gauss-Seidel sweeps
 //                     in the column order of the header, every operation rounded on its own.  G [K][K], L [K][K | 1] (an odd stride:
 //                     its column reads are conflict-free), lo and hi sit in LDS: 132.6 KB at K = 128.  A NaN coefficient stays
 //                     NaN through the clamp, as numpy's minimum / maximum keep it.
@@ -21,14 +20,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-
 #include "../../include/fdm_hip.h"
+#include "handoff.hpp"
 
 namespace fdm {
 
-constexpr int RIG_CHUNK = 768;            // elements of 3V per partial sum (12 per lane; a multiple of 3: chunks end on vertices)
-constexpr int RIG_FT = 8;                 // rows of [B * L_max] per workgroup of rig_proj_kernel
+// (rig_proj_kernel's geometry is handoff.hpp's: one partial sum per ROW_CHUNK elements of 3V, ROW_TILE rows per workgroup)
 constexpr int RIG_SW = 8;                 // wavefronts (= output frames) per workgroup of rig_solve_kernel
 constexpr int RIG_KMAX = 128;
 
@@ -37,59 +34,50 @@ __device__ __forceinline__ float rig_clamp(float x, float lo, float hi) { return
 __device__ __forceinline__ float rig_xor(float v, int mask) { return __shfl_xor(v, mask, 64); }
 __device__ __forceinline__ float rig_lane(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
 
-// off: [rows][V3] (rows = B * L_max; lens: [B][2] = {L, L_out}).  P: [K][ldp], ldp = chunks * RIG_CHUNK, zero behind V3.
+// off: [rows][V3] (rows = B * L_max; lens: [B][2] = {L, L_out}).  P: [K][ldp], ldp = chunks * ROW_CHUNK, zero behind V3.
 // part: [chunks][rows][K].  A tile without a live row writes nothing (its partial sums are never read).
 __global__ __launch_bounds__(256) void rig_proj_kernel(const float* off, const int* lens, int L_max, int rows, int V3, const float* P, int ldp,
                                                        int K, float* part) {
-  __shared__ __attribute__((aligned(16))) float sd[RIG_FT * RIG_CHUNK];
-  __shared__ float so[RIG_FT * RIG_KMAX];
+  __shared__ __attribute__((aligned(16))) float sd[ROW_TILE * ROW_CHUNK];
+  __shared__ float so[ROW_TILE * RIG_KMAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.x * RIG_FT, c0 = blockIdx.y * RIG_CHUNK;
-  const int n = min(RIG_CHUNK, V3 - c0);
+  const int row0 = blockIdx.x * ROW_TILE, c0 = blockIdx.y * ROW_CHUNK;
+  const int n = min(ROW_CHUNK, V3 - c0);
   bool any = false;
 #pragma unroll
-  for (int r = 0; r < RIG_FT; ++r) {
+  for (int r = 0; r < ROW_TILE; ++r) {
     const int row = row0 + r;
-    float* d = sd + r * RIG_CHUNK;
-    bool live = false;
-    if (row < rows) { const int b = row / L_max; live = row - b * L_max < lens[2 * b]; }
+    float* d = sd + r * ROW_CHUNK;
+    int b;
+    const bool live = row_live(lens, 2, 0, row, L_max, rows, b);
     any |= live;
     if (!live) {
-      for (int j = tid; j < RIG_CHUNK; j += 256) d[j] = 0.f;
+      for (int j = tid; j < ROW_CHUNK; j += 256) d[j] = 0.f;
       continue;
     }
     const float* src = off + (size_t)row * V3 + c0;
-    const int head = min(n, (int)((4 - (((uintptr_t)src >> 2) & 3)) & 3));
-    const int nb = (n - head) >> 2, done = head + 4 * nb;
-    for (int m = tid; m < nb; m += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(src + head + 4 * m);
-      float* q = d + head + 4 * m;
-      q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
-    }
-    if (tid < head) d[tid] = src[tid];
-    if (tid >= 64 && tid - 64 < n - done) d[done + tid - 64] = src[done + tid - 64];
-    for (int j = n + tid; j < RIG_CHUNK; j += 256) d[j] = 0.f;
+    peel_walk<256, 64>(peel_of(src, n), n, tid, PeelLoad{src, d});
+    for (int j = n + tid; j < ROW_CHUNK; j += 256) d[j] = 0.f;
   }
   if (!any) return;                                         // (uniform over the workgroup)
   __syncthreads();
-  constexpr int Q = RIG_CHUNK / 256;                        // 16-byte pieces per lane and row
-  float4 x[RIG_FT][Q];
+  float4 x[ROW_TILE][ROW_Q];
 #pragma unroll
-  for (int r = 0; r < RIG_FT; ++r)
+  for (int r = 0; r < ROW_TILE; ++r)
 #pragma unroll
-    for (int q = 0; q < Q; ++q) x[r][q] = *reinterpret_cast<const float4*>(sd + r * RIG_CHUNK + 4 * (lane + 64 * q));
+    for (int q = 0; q < ROW_Q; ++q) x[r][q] = *reinterpret_cast<const float4*>(sd + r * ROW_CHUNK + 4 * (lane + 64 * q));
   for (int k = wave; k < K; k += 4) {
     const float* pk = P + (size_t)k * ldp + c0;
-    float4 p[Q];
+    float4 p[ROW_Q];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) p[q] = *reinterpret_cast<const float4*>(pk + 4 * (lane + 64 * q));
-    float a[RIG_FT];
+    for (int q = 0; q < ROW_Q; ++q) p[q] = *reinterpret_cast<const float4*>(pk + 4 * (lane + 64 * q));
+    float a[ROW_TILE];
 #pragma unroll
-    for (int r = 0; r < RIG_FT; ++r) {
+    for (int r = 0; r < ROW_TILE; ++r) {
       float s = __fmul_rn(p[0].x, x[r][0].x);
       s = __builtin_fmaf(p[0].y, x[r][0].y, s); s = __builtin_fmaf(p[0].z, x[r][0].z, s); s = __builtin_fmaf(p[0].w, x[r][0].w, s);
 #pragma unroll
-      for (int q = 1; q < Q; ++q) {
+      for (int q = 1; q < ROW_Q; ++q) {
         s = __builtin_fmaf(p[q].x, x[r][q].x, s); s = __builtin_fmaf(p[q].y, x[r][q].y, s);
         s = __builtin_fmaf(p[q].z, x[r][q].z, s); s = __builtin_fmaf(p[q].w, x[r][q].w, s);
       }
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(256) void rig_proj_kernel(const float* off, const i
     if ((lane & 7) == 0) so[(lane >> 3) * K + k] = s;
   }
   __syncthreads();
-  const int live_rows = min(RIG_FT, rows - row0);
+  const int live_rows = min(ROW_TILE, rows - row0);
   float* o = part + ((size_t)blockIdx.y * rows + row0) * K;
   for (int i = tid; i < live_rows * K; i += 256) o[i] = so[i];
 }
@@ -140,14 +128,7 @@ __global__ __launch_bounds__(RIG_SW * 64) void rig_solve_kernel(const float* par
   }
   int i0 = t, i1 = t;
   float l0 = 1.f, l1 = 0.f;
-  if (resample) {                         // mesh_pos_kernel's expression with Tin = L, Tout = Lo
-    const float scale = Lo > 1 ? (float)(L - 1) / (float)(Lo - 1) : 0.f;
-    const float src = __fmul_rn(scale, (float)t);
-    i0 = min((int)src, L - 1);
-    i1 = i0 + (i0 < L - 1 ? 1 : 0);
-    l1 = __fsub_rn(src, (float)i0);
-    l0 = __fsub_rn(1.f, l1);
-  }
+  if (resample) interp_taps(L, Lo, t, i0, i1, l0, l1);
   float r[2] = {0.f, 0.f}, g[2], c[2] = {0.f, 0.f};
 #pragma unroll
   for (int h = 0; h < 2; ++h) {

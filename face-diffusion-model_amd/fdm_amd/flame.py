@@ -2,7 +2,6 @@
 section 2 item 20 is the definition).  A head of the SMPL / FLAME family: shape and expression blend shapes, pose correctives and
 linear blend skinning; the decoder's offsets enter as `extra`.  No model file ships with the library (FLAME's is licensed):
 FlameModel.load reads the user's, FlameModel.synthetic makes seeded ones for tests."""
-import contextlib
 import ctypes as C
 import hashlib
 from collections import namedtuple
@@ -11,6 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import FdmError, FlameModelDesc, check, lib
+from .handoff import HandoffPlan, frames_list
 
 # vertices [B, L_max, V, 3] fp32 (rows at or past frames[b] are zeros), landmarks [B, L_max, NL, 3] or None, frames per clip
 FlameFrames = namedtuple("FlameFrames", "vertices landmarks frames")
@@ -165,38 +165,22 @@ def plan_key(model, landmarks=None):
     return (model.V, model.J, k.hexdigest())
 
 
-class FlamePlan:
+class FlamePlan(HandoffPlan):
     """Thin binding of fdm_flame_create / fdm_flame_forward for one model (and one static landmark embedding): the tables are formed
     and uploaded here, forward() only passes pointers.  A plan holds one scratch: it serves one stream at a time (pipeline.to_flame
     keeps them per (device, stream, model)).  Without a visible device the plan still validates and forward() raises."""
 
+    _destroy = "fdm_flame_destroy"
+
     def __init__(self, model, landmarks=None, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise FdmError("FlamePlan runs on the HIP path only (no CPU fallback)")
+        super().__init__(device)
         self.model = model
         self.lv, self.lb = landmark_arrays(landmarks)
         self.NL = 0 if self.lv is None else int(self.lv.shape[0])
         self.V, self.J, self.NB = model.V, model.J, model.NB
         self.key = plan_key(model, landmarks)
-        self.h = None
-        h = C.c_void_p()
-        self.stream = None
         d = model.desc()
-        with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
-            check(lib().fdm_flame_create(C.byref(d), None if self.lv is None else self.lv.ctypes.data, None if self.lb is None else self.lb.ctypes.data,
-                                         self.NL, C.byref(h)))
-            if torch.cuda.is_available():
-                self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.h = h
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().fdm_flame_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        self._create("fdm_flame_create", C.byref(d), None if self.lv is None else self.lv.ctypes.data, None if self.lb is None else self.lb.ctypes.data, self.NL)
 
     def _dev(self, x, what, last, B=None, L=None):
         """x as a contiguous float32 device tensor [B, L, last] ([L, last] gains the batch)"""
@@ -231,9 +215,7 @@ class FlamePlan:
         if extra is not None:
             xt = torch.as_tensor(extra)
             xt = self._dev(xt.reshape(*xt.shape[:-2], -1) if (xt.shape[-1] == 3 and xt.shape[-2] == self.V) else xt, "extra", 3 * self.V, B, L)
-        fr = [L] * B if frames is None else [int(f) for f in frames]
-        if len(fr) != B:
-            raise FdmError(f"{len(fr)} frame counts for {B} clips")
+        fr = frames_list(frames, B, L)
         if out is None:
             verts = torch.empty(B, L, self.V, 3, dtype=torch.float32, device=dv)
         else:

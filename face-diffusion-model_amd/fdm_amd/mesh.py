@@ -8,6 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import FdmError, check, lib
+from .handoff import HandoffPlan, fps_pair, frames_list, frames_out, frames_out_max, offsets_batch  # noqa: F401  (frames_out: fdm_mesh_frames, public here)
 
 # positions [B, L_out_max, V, 3] (interleaved: [B, L_out_max, V, 6] = position then normal, and normals is None), normals the same
 # shape as planar positions or None, frames = L_out per clip (rows at or past it are zeros)
@@ -30,53 +31,26 @@ def adjacency(faces, V):
     return off, items[:3 * len(f)]
 
 
-def frames_out(frames_in, fps_in, fps_out):
-    """L_out of a clip of frames_in frames (fdm_mesh_frames; host only)."""
-    n = C.c_int(0)
-    check(lib().fdm_mesh_frames(int(frames_in), float(fps_in or 0), float(fps_out or 0), C.byref(n)))
-    return n.value
-
-
-class MeshOutPlan:
+class MeshOutPlan(HandoffPlan):
     """Thin binding of fdm_mesh_create / fdm_mesh_forward for one topology: the incident-face lists are built and uploaded here,
     forward() only passes pointers.  A plan holds one scratch: it serves one stream at a time (one plan per stream for concurrent
     calls; pipeline.to_mesh keeps them per (device, stream, topology))."""
 
-    def __init__(self, faces, V, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise FdmError("MeshOutPlan runs on the HIP path only (no CPU fallback)")
-        self.faces, self.V = faces_array(faces), int(V)
-        self.h = None
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().fdm_mesh_create(self.faces.ctypes.data, len(self.faces), self.V, C.byref(h)))
-        self.h = h
+    _destroy = "fdm_mesh_destroy"
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().fdm_mesh_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+    def __init__(self, faces, V, device="cuda:0"):
+        super().__init__(device)
+        self.faces, self.V = faces_array(faces), int(V)
+        self._create("fdm_mesh_create", self.faces.ctypes.data, len(self.faces), self.V)
 
     def forward(self, offsets, frames=None, template=None, fps=None, normals=True, interleaved=False, half=False, out=None):
         """offsets [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device, frames: L per clip (None: L_max), template [1 or B, 3 V],
         fps = (fps_in, fps_out) or None -> MeshFrames.  out: (positions, normals) tensors to write instead of new ones (normals
         None where the call writes none); their second dimension is L_out_max.  New outputs are L_out_max = max(frames out) long."""
         dv = self.device
-        x = offsets.detach()
-        if x.dim() == 2:
-            x = x.unsqueeze(0)
-        if x.device != dv or x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != 3 * self.V:
-            raise FdmError(f"offsets must be float32 [B, L, {3 * self.V}] on {dv}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        x = x.contiguous()
+        x = offsets_batch(offsets, self.V, dv)
         B, L_max = int(x.shape[0]), int(x.shape[1])
-        fr = [L_max] * B if frames is None else [int(f) for f in frames]
-        if len(fr) != B:
-            raise FdmError(f"{len(fr)} frame counts for {B} clips")
-        fi, fo = (0.0, 0.0) if fps is None else (float(fps[0] or 0), float(fps[1] or 0))
+        fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
         tp, rows = None, 0
         if template is not None:
             tp = torch.as_tensor(template, dtype=torch.float32).to(dv).reshape(-1, 3 * self.V).contiguous()
@@ -84,7 +58,7 @@ class MeshOutPlan:
         flags = (_lib.MESH_INTERLEAVED if interleaved else 0) | (_lib.MESH_F16 if half else 0) | (_lib.MESH_NORMALS if normals else 0)
         dt = torch.float16 if half else torch.float32
         if out is None:
-            Lo = max([frames_out(f, fi, fo) for f in fr] + [1])
+            Lo = frames_out_max(fr, fi, fo)
             pos = torch.empty(B, Lo, self.V, 6 if interleaved else 3, dtype=dt, device=dv)
             nrm = torch.empty(B, Lo, self.V, 3, dtype=dt, device=dv) if normals and not interleaved else None
         else:

@@ -9,6 +9,7 @@ import torch
 
 from . import presets, schedule
 from ._lib import SLOT_FINISHED, FdmError
+from .handoff import cached_plan
 from .modules import (FDM, ClassifierFreeSampleModel, FDMBiwi, FDMMead, GaussianDiffusion, VQAutoEncoder)
 
 EMOTIONS = ["angry", "contempt", "disgusted", "fear", "happy", "sad", "surprised"]     # demo/demo_3d_mead.py:118
@@ -102,21 +103,13 @@ def prepare_audio(pcm, rate, pad_seconds=1.0, device="cuda:0", normalize=True):
     return wav[0, :lens[0]]
 
 
-_MESH_PLANS = {}      # (device, stream, V, digest of the faces) -> mesh.MeshOutPlan
-
-
 def _mesh_plan(faces, V, device):
-    """The mesh hand-off plan of `device`, the current stream and this topology (a plan serves one stream at a time), kept as
-    _frontend() keeps front ends: what the process holds is bounded by the distinct meshes it meets."""
+    """The mesh hand-off plan of `device`, the current stream and this topology (V, digest of the faces): handoff.cached_plan."""
     import hashlib
     from .mesh import MeshOutPlan, faces_array
     dv, at = _on_stream(device)
     f = faces_array(faces)
-    key = at + (int(V), hashlib.sha1(f.tobytes()).hexdigest())
-    plan = _MESH_PLANS.get(key)
-    if plan is None:
-        _MESH_PLANS[key] = plan = MeshOutPlan(f, V, dv)
-    return plan
+    return cached_plan(at, "mesh", (int(V), hashlib.sha1(f.tobytes()).hexdigest()), lambda: MeshOutPlan(f, V, dv))
 
 
 def _mesh_fps(p, in_fps, out_fps):
@@ -168,26 +161,15 @@ def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, 
     return _split_mesh(mf) if many else mf
 
 
-_RIG_PLANS = {}       # (device, stream, identity of the rig: rig.RigPlan.key) -> rig.RigPlan
-
-
 def _rig_plan(rig, device):
-    """The rig hand-off plan of `device`, the current stream and this rig (a plan serves one stream at a time), kept as _mesh_plan()
-    keeps mesh plans.  rig: a rig.RigPlan (used as it is where it was made for this device and stream, made again from its
-    arguments otherwise) or the dict of RigPlan's arguments (every call then digests the basis to recognise it: animate_many,
-    animate_long and SlotServer come here once and go on with the plan)."""
+    """The rig hand-off plan of `device`, the current stream and this rig (rig.RigPlan.key).  rig: a rig.RigPlan (used as it is where
+    it was made for this device and stream, made again from its arguments otherwise) or the dict of RigPlan's arguments (every call
+    then digests the basis to recognise it: animate_many, animate_long and SlotServer come here once and go on with the plan)."""
     from .rig import RigPlan, identity
     dv, at = _on_stream(device)
-    mine = isinstance(rig, RigPlan)
-    key = at + (rig.key if mine else identity(**rig),)
-    plan = _RIG_PLANS.get(key)
-    if plan is None:
-        if mine:
-            plan = rig if (rig.device == dv and rig.stream == at[1]) else RigPlan(device=dv, **rig.arguments())
-        else:
-            plan = RigPlan(device=dv, **rig)
-        _RIG_PLANS[key] = plan
-    return plan
+    if isinstance(rig, RigPlan):
+        return cached_plan(at, "rig", rig.key, lambda: RigPlan(device=dv, **rig.arguments()), rig)
+    return cached_plan(at, "rig", identity(**rig), lambda: RigPlan(device=dv, **rig))
 
 
 def _split_rig(rf):
@@ -211,28 +193,18 @@ def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bound
     return _split_rig(rf) if many else rf
 
 
-_FLAME_PLANS = {}     # (device, stream, identity of the model and its landmarks: flame.FlamePlan.key) -> flame.FlamePlan
-
-
 def _flame_plan(model, device, landmarks=None):
-    """The parametric-head plan of `device`, the current stream and this model (a plan serves one stream at a time), kept as
-    _rig_plan() keeps rig plans.  model: a flame.FlamePlan (used as it is where it was made for this device and stream, made again
-    from its model otherwise), a flame.FlameModel (digested once), or the path of a model file (loaded per call: pass a FlameModel)."""
+    """The parametric-head plan of `device`, the current stream and this model with its landmarks (flame.FlamePlan.key).  model: a
+    flame.FlamePlan (used as it is where it was made for this device and stream, made again from its model otherwise), a
+    flame.FlameModel (digested once), or the path of a model file (loaded per call: pass a FlameModel)."""
     from .flame import FlameModel, FlamePlan, plan_key
     dv, at = _on_stream(device)
     if isinstance(model, FlamePlan):
-        plan = _FLAME_PLANS.get(at + (model.key,))
-        if plan is None:
-            plan = model if (model.device == dv and model.stream == at[1]) else FlamePlan(model.model, None if model.lv is None else (model.lv, model.lb), dv)
-            _FLAME_PLANS[at + (plan.key,)] = plan
-        return plan
+        lm = None if model.lv is None else (model.lv, model.lb)
+        return cached_plan(at, "flame", model.key, lambda: FlamePlan(model.model, lm, dv), model)
     if not isinstance(model, FlameModel):
         model = FlameModel.load(model)
-    key = at + (plan_key(model, landmarks),)
-    plan = _FLAME_PLANS.get(key)
-    if plan is None:
-        _FLAME_PLANS[key] = plan = FlamePlan(model, landmarks, dv)
-    return plan
+    return cached_plan(at, "flame", plan_key(model, landmarks), lambda: FlamePlan(model, landmarks, dv))
 
 
 @torch.no_grad()

@@ -1,7 +1,6 @@
 """Rig hand-off: decoded vertex offsets -> blendshape coefficients per frame at the consumer's frame rate, a ridge-regularised,
 box-constrained least-squares fit onto a basis, on the device (include/fdm_hip.h, fdm_rig_*; kernels csrc/rig_out.hpp; DESIGN.md
 section 2 item 19 is the definition)."""
-import contextlib
 import ctypes as C
 import hashlib
 from collections import namedtuple
@@ -10,6 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import FdmError, check, lib
+from .handoff import HandoffPlan, fps_pair, frames_list, frames_out_max, offsets_batch
 
 # weights [B, L_out_max, K] fp32 (rows at or past frames[b] are zeros), frames = L_out per clip, names = the K coefficient names or None
 RigFrames = namedtuple("RigFrames", "weights frames names")
@@ -76,65 +76,40 @@ def identity(basis, weights=None, ridge=0.0, bounds=None, sweeps=SWEEPS, names=N
     return _key(_arguments(basis, weights, ridge, bounds, sweeps, names))
 
 
-class RigPlan:
+class RigPlan(HandoffPlan):
     """Thin binding of fdm_rig_create / fdm_rig_forward for one rig: the fp64 Gram matrix and its Cholesky factor are formed and
     uploaded here, forward() only passes pointers.  basis [K, 3 V] blendshape deltas, weights [V] >= 0 or None, ridge >= 0, bounds =
     (lo, hi) (scalars or [K]) or None, sweeps of projected Gauss-Seidel, names of the K coefficients.  A plan holds one scratch: it
     serves one stream at a time (pipeline.to_rig keeps them per (device, stream, rig)).  Without a visible device the plan still
     validates its arguments and forward() raises."""
 
+    _destroy = "fdm_rig_destroy"
+
     def __init__(self, basis, weights=None, ridge=0.0, bounds=None, sweeps=SWEEPS, names=None, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise FdmError("RigPlan runs on the HIP path only (no CPU fallback)")
+        super().__init__(device)
         a = _arguments(basis, weights, ridge, bounds, sweeps, names)
         self.basis, self.weights, self.ridge, self.lo, self.hi, self.sweeps, self.names = a
         self.K, self.V = int(self.basis.shape[0]), int(self.basis.shape[1]) // 3
         self.key = _key(a)            # the rig's identity: what pipeline.to_rig caches plans by
-        self.h = None
-        h = C.c_void_p()
         ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        self.stream = None
-        with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
-            check(lib().fdm_rig_create(self.basis.ctypes.data, self.K, self.V, ptr(self.weights), self.ridge, ptr(self.lo), ptr(self.hi),
-                                       self.sweeps, C.byref(h)))
-            if torch.cuda.is_available():
-                self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.h = h
+        self._create("fdm_rig_create", self.basis.ctypes.data, self.K, self.V, ptr(self.weights), self.ridge, ptr(self.lo), ptr(self.hi), self.sweeps)
 
     def arguments(self):
         """The arguments that make this plan again (on another device or stream)."""
         return dict(basis=self.basis, weights=self.weights, ridge=self.ridge, bounds=None if self.lo is None else (self.lo, self.hi),
                     sweeps=self.sweeps, names=self.names)
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().fdm_rig_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
     def forward(self, offsets, frames=None, fps=None, proj=False, out=None):
         """offsets [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device: the decoder's output BEFORE the template is added; frames:
         L per clip (None: L_max); fps = (fps_in, fps_out) or None -> RigFrames, or (RigFrames, proj [B, L_out_max, K]) with proj=True
         (the projections the solve consumed).  out: a weights tensor to write instead of a new one (its second dimension is
         L_out_max).  New outputs are L_out_max = max(frames out) long."""
-        from .mesh import frames_out
         dv = self.device
-        x = offsets.detach()
-        if x.dim() == 2:
-            x = x.unsqueeze(0)
-        if x.device != dv or x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != 3 * self.V:
-            raise FdmError(f"offsets must be float32 [B, L, {3 * self.V}] on {dv}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        x = x.contiguous()
+        x = offsets_batch(offsets, self.V, dv)
         B, L_max = int(x.shape[0]), int(x.shape[1])
-        fr = [L_max] * B if frames is None else [int(f) for f in frames]
-        if len(fr) != B:
-            raise FdmError(f"{len(fr)} frame counts for {B} clips")
-        fi, fo = (0.0, 0.0) if fps is None else (float(fps[0] or 0), float(fps[1] or 0))
+        fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
         if out is None:
-            Lo = max([frames_out(f, fi, fo) for f in fr] + [1])
+            Lo = frames_out_max(fr, fi, fo)
             coef = torch.empty(B, Lo, self.K, dtype=torch.float32, device=dv)
         else:
             coef = out

@@ -3,7 +3,7 @@ solve() restates stage 2 in numpy float32 in exactly the stated column order, ve
 is one rounded IEEE operation: no contraction).  lerp() is the frame rule applied to the projections."""
 import numpy as np
 
-CHUNK = 768                       # csrc/rig_out.hpp RIG_CHUNK: elements of 3V per partial sum
+CHUNK = 768                       # csrc/handoff.hpp ROW_CHUNK: elements of 3V per partial sum
 V3S = [3, 15, (CHUNK - 1) // 3 * 3, (CHUNK // 3 + 1) * 3, 2 * CHUNK + 3]       # 3, 15, 765, 771, 1539 -> chunks 1, 1, 1, 2, 3
 KS = [1, 3, 52, 64, 65, 128]
 FRAMES, L_MAX = [0, 1, 7], 7

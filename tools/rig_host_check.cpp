@@ -1,10 +1,10 @@
 // Host side of the rig hand-off under AddressSanitizer + UBSan, as a stand-alone CPU program (no GPU, no Python): the fp64 Gram matrix
 // and its Cholesky factor, fdm_rig_create's checks with the rank-deficient path, fdm_rig_forward's argument checks and destroy
-// (csrc/rig_out.hip, with mesh_out.hip for the frame rule), with the two symbols those units take from fdm_hip.hip supplied here (no
-// device is ever reported).
+// (csrc/rig_out.hip; the frame rule is host.hpp's), with the two symbols that unit takes from fdm_hip.hip supplied here (no device is
+// ever reported).
 //   cd face-diffusion-model_amd/csrc && /opt/rocm/bin/hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off \
 //     -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -fno-gpu-sanitize \
-//     -x hip ../../tools/rig_host_check.cpp rig_out.hip mesh_out.hip -o ../../tools/_build/rig_host_check
+//     -x hip ../../tools/rig_host_check.cpp rig_out.hip -o ../../tools/_build/rig_host_check
 //   ../../tools/_build/rig_host_check          -> "rig_host_check ok", exit status 0
 #include <cmath>
 #include <cstdarg>
