@@ -17,6 +17,7 @@
 //                     NaN through the clamp, as numpy's minimum / maximum keep it.
 // A frame's values are a function of its own row: no atomics, and neither the batch, L_max, the row's slot in its tile nor the
 // workgroup enters an expression.  Input rows at or past frames[b] are never read.  Resource use: profiles/rig_out/resources.txt.
+// The kernels of the temporal fit (fdm_rig_set_temporal) follow the two above, under their own heading.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -204,6 +205,195 @@ __global__ __launch_bounds__(RIG_SW * 64) void rig_solve_kernel(const float* par
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; if (k < K) oc[k] = c[h]; }
+}
+
+// ---- the temporal fit (include/fdm_hip.h, fdm_rig_set_temporal): the clip's frames coupled by
+// 1/2 (c_f - c_{f-1})^T M (c_f - c_{f-1}).  Q^T G Q = Lam and Q^T M Q = I turn the block-tridiagonal system of a clip into K scalar
+// tridiagonal systems along time.  After rig_proj_kernel:
+//   rig_modal_in_kernel   rig_solve_kernel's geometry and its chunk sum and frame-rate step, then z_k = sum_j QT[k][j] r_j.  Q sits in LDS
+//                         row-major, so lane k reads QT[k][j] = Q[j][k] at j K + k: consecutive banks.  Writes r (the sweeps read it
+//                         again), z, proj; the rows at and past L_out[b] of coef and proj as zeros.
+//   rig_time_kernel       one lane per (clip, k): grid (B, K / 64 rounded up), one wavefront each.  A lane walks its clip's frames forward
+//                         (u over z in place, 1 / w beside it) and back (y over u); at every frame the wavefront's loads and stores are
+//                         64 consecutive floats.  The recurrence is sequential by nature: its cost is Lo dependent divisions.
+//   rig_modal_out_kernel  x_k = sum_j Q[k][j] y_j with Q^T in LDS (the same bank pattern), the clamp when bounded, coef.
+//   rig_sweep_kernel      one colour of one projected Gauss-Seidel sweep: one wavefront per frame of that parity, which reads its two
+//                         neighbours (the other parity: nobody writes them in this launch) and rewrites its own row of coef.  G, mu m,
+//                         lo, hi in LDS: 65.5 KB at K = 128.  The launch boundary is the only synchronisation between half-sweeps.
+// Every expression names the clip's own rows, its own L_out and the frame's index inside the clip; every operation is rounded on its own.
+// Resource use: profiles/rig_temporal/resources.txt.
+
+// o_k = sum_j sT[j K + k] v_j: j ascending, the first product starts the sum.  v, o: coefficient k on lane k mod 64, half k / 64.
+__device__ __forceinline__ void rig_modal(const float* sT, int K, int lane, const float (&v)[2], float (&o)[2]) {
+  o[0] = 0.f; o[1] = 0.f;
+  for (int j = 0; j < K; ++j) {
+    const float vj = j < 64 ? rig_lane(v[0], j) : rig_lane(v[1], j - 64);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < K) { const float p = __fmul_rn(sT[j * K + k], vj); o[h] = j ? __fadd_rn(o[h], p) : p; }
+    }
+  }
+}
+
+// part, lens, coef, proj: as rig_solve_kernel.  Q [K][K] (column k = mode k).  rbuf, zbuf: [B * Lo_max][K], live rows only.
+// Dynamic LDS: K * K floats.
+__global__ __launch_bounds__(RIG_SW * 64) void rig_modal_in_kernel(const float* part, int chunks, int rows_in, const int* lens, int L_max, int Lo_max,
+                                                                   int rows_out, int K, int resample, const float* Q, float* rbuf, float* zbuf,
+                                                                   float* coef, float* proj) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sT = reinterpret_cast<float*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < K * K; i += RIG_SW * 64) sT[i] = Q[i];
+  __syncthreads();
+  const int row = blockIdx.x * RIG_SW + wave;
+  if (row >= rows_out) return;                              // (uniform over the wavefront; no barrier follows)
+  const int b = row / Lo_max, t = row - b * Lo_max;
+  const int L = lens[2 * b], Lo = lens[2 * b + 1];
+  const int H = K > 64 ? 2 : 1;
+  float* op = proj ? proj + (size_t)row * K : nullptr;
+  if (t >= Lo) {
+    float* oc = coef + (size_t)row * K;
+    for (int h = 0; h < H; ++h) { const int k = lane + 64 * h; if (k < K) { oc[k] = 0.f; if (op) op[k] = 0.f; } }
+    return;
+  }
+  int i0 = t, i1 = t;
+  float l0 = 1.f, l1 = 0.f;
+  if (resample) interp_taps(L, Lo, t, i0, i1, l0, l1);
+  float r[2] = {0.f, 0.f}, z[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = lane + 64 * h;
+    if (k >= K) continue;
+    const float* p0 = part + ((size_t)b * L_max + i0) * K + k;
+    const float* p1 = part + ((size_t)b * L_max + i1) * K + k;
+    const size_t cs = (size_t)rows_in * K;
+    float s0 = p0[0], s1 = resample ? p1[0] : 0.f;
+    for (int q = 1; q < chunks; ++q) {
+      s0 = __fadd_rn(s0, p0[q * cs]);
+      if (resample) s1 = __fadd_rn(s1, p1[q * cs]);
+    }
+    r[h] = resample ? __fadd_rn(__fmul_rn(l0, s0), __fmul_rn(l1, s1)) : s0;
+    if (op) op[k] = r[h];
+    rbuf[(size_t)row * K + k] = r[h];
+  }
+  rig_modal(sT, K, lane, r, z);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; if (k < K) zbuf[(size_t)row * K + k] = z[h]; }
+}
+
+// lam [K].  zu [B * Lo_max][K]: z in, y out.  iw [B * Lo_max][K]: scratch (1 / w_f).  Grid (B, (K + 63) / 64), 64 threads.
+__global__ __launch_bounds__(64) void rig_time_kernel(const int* lens, int Lo_max, int K, const float* lam, float* zu, float* iw) {
+  const int b = blockIdx.x, k = blockIdx.y * 64 + threadIdx.x;
+  const int Lo = lens[2 * b + 1];
+  if (k >= K || Lo < 1) return;
+  const size_t base = (size_t)b * Lo_max * K + k;
+  float* u = zu + base;
+  float* w = iw + base;
+  const float lk = lam[k];
+  const float d_end = __fadd_rn(lk, Lo > 1 ? 1.f : 0.f), d_in = __fadd_rn(lk, 2.f);      // n_f = 1 at the two ends (0 when alone), 2 inside
+  float iwp = __fdiv_rn(1.f, d_end), up = u[0];
+  w[0] = iwp;
+  for (int f = 1; f < Lo; ++f) {
+    const float wf = __fsub_rn(f == Lo - 1 ? d_end : d_in, iwp);
+    up = __fadd_rn(u[(size_t)f * K], __fmul_rn(up, iwp));
+    iwp = __fdiv_rn(1.f, wf);
+    u[(size_t)f * K] = up;
+    w[(size_t)f * K] = iwp;
+  }
+  float y = __fmul_rn(up, iwp);
+  u[(size_t)(Lo - 1) * K] = y;
+  for (int f = Lo - 2; f >= 0; --f) {
+    y = __fmul_rn(__fadd_rn(u[(size_t)f * K], y), w[(size_t)f * K]);
+    u[(size_t)f * K] = y;
+  }
+}
+
+// y [B * Lo_max][K] (live rows).  QT [K][K] = Q transposed.  lo / hi [K] (bounded = 0: not read).  Writes the live rows of coef.
+// Dynamic LDS: K * K floats.
+__global__ __launch_bounds__(RIG_SW * 64) void rig_modal_out_kernel(const float* y, const int* lens, int Lo_max, int rows_out, int K, const float* QT,
+                                                                    const float* lo, const float* hi, int bounded, float* coef) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sT = reinterpret_cast<float*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < K * K; i += RIG_SW * 64) sT[i] = QT[i];
+  __syncthreads();
+  const int row = blockIdx.x * RIG_SW + wave;
+  if (row >= rows_out) return;                              // (uniform over the wavefront; no barrier follows)
+  const int b = row / Lo_max, t = row - b * Lo_max;
+  if (t >= lens[2 * b + 1]) return;
+  float v[2] = {0.f, 0.f}, x[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; if (k < K) v[h] = y[(size_t)row * K + k]; }
+  rig_modal(sT, K, lane, v, x);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = lane + 64 * h;
+    if (k < K) coef[(size_t)row * K + k] = bounded ? rig_clamp(x[h], lo[k], hi[k]) : x[h];
+  }
+}
+
+// One colour (0: even frames of a clip, 1: odd) of one sweep, in place in coef.  per = frames of this colour in Lo_max, rows = B * per.
+// r [B * Lo_max][K], G [K][K], mvec [K] = mu m, lo / hi [K].  Dynamic LDS: (K * K + 3 * K) floats.
+__global__ __launch_bounds__(RIG_SW * 64) void rig_sweep_kernel(const float* r, const int* lens, int Lo_max, int per, int rows, int colour, int K,
+                                                                const float* G, const float* mvec, const float* lo, const float* hi, float* coef) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sG = reinterpret_cast<float*>(smem);
+  float* smv = sG + K * K;
+  float* slo = smv + K;
+  float* shi = slo + K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < K * K; i += RIG_SW * 64) sG[i] = G[i];
+  for (int i = tid; i < K; i += RIG_SW * 64) { smv[i] = mvec[i]; slo[i] = lo[i]; shi[i] = hi[i]; }
+  __syncthreads();
+  const int i = blockIdx.x * RIG_SW + wave;
+  if (i >= rows) return;                                    // (uniform over the wavefront; no barrier follows)
+  const int b = i / per, t = 2 * (i - b * per) + colour;
+  const int Lo = lens[2 * b + 1];
+  if (t >= Lo) return;
+  const int nf = Lo == 1 ? 0 : (t == 0 || t == Lo - 1 ? 1 : 2);
+  const float fn = (float)nf;
+  const size_t at = ((size_t)b * Lo_max + t) * K;
+  float* own = coef + at;
+  float c[2] = {0.f, 0.f}, g[2] = {0.f, 0.f}, e[2] = {0.f, 0.f};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = lane + 64 * h;
+    if (k >= K) continue;
+    c[h] = own[k];
+    g[h] = r[at + k];
+    if (nf) {
+      const float s = nf == 2 ? __fadd_rn(own[k - K], own[k + K]) : (t > 0 ? own[k - K] : own[k + K]);
+      g[h] = __fadd_rn(g[h], __fmul_rn(smv[k], s));
+    }
+    e[h] = __fmul_rn(fn, smv[k]);
+  }
+  for (int j = 0; j < K; ++j) {
+    const float cj = j < 64 ? rig_lane(c[0], j) : rig_lane(c[1], j - 64);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < K) g[h] = __fsub_rn(g[h], __fmul_rn(sG[j * K + k], cj));
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) g[h] = __fsub_rn(g[h], __fmul_rn(e[h], c[h]));
+  for (int j = 0; j < K; ++j) {
+    const float cj = j < 64 ? rig_lane(c[0], j) : rig_lane(c[1], j - 64);
+    const float gj = j < 64 ? rig_lane(g[0], j) : rig_lane(g[1], j - 64);
+    const float ej = __fmul_rn(fn, smv[j]);
+    const float nj = rig_clamp(__fadd_rn(cj, __fdiv_rn(gj, __fadd_rn(sG[j * K + j], ej))), slo[j], shi[j]);
+    const float delta = __fsub_rn(nj, cj);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k == j) c[h] = nj;
+      if (k < K) g[h] = __fsub_rn(g[h], __fmul_rn(sG[j * K + k], delta));
+      if (k == j) g[h] = __fsub_rn(g[h], __fmul_rn(ej, delta));
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; if (k < K) own[k] = c[h]; }
 }
 
 }  // namespace fdm

@@ -216,6 +216,8 @@ SYMBOLS = {
     "fdm_rig_create": (ci, [vp, ci, ci, vp, C.c_double, vp, vp, ci, C.POINTER(vp)]),
     "fdm_rig_forward": (ci, [vp, vp, vp, ci, ci, C.c_double, C.c_double, vp, vp, ci, vp, vp]),
     "fdm_rig_destroy": (ci, [vp]),
+    "fdm_rig_temporal_tables_host": (ci, [vp, ci, C.c_double, vp, vp, vp]),
+    "fdm_rig_set_temporal": (ci, [vp, C.c_double, vp]),
     "fdm_flame_tables_host": (ci, [C.POINTER(FlameModelDesc), vp, vp, vp]),
     "fdm_flame_create": (ci, [C.POINTER(FlameModelDesc), vp, vp, ci, C.POINTER(vp)]),
     "fdm_flame_forward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),

@@ -178,17 +178,21 @@ def _split_rig(rf):
 
 
 @torch.no_grad()
-def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bounds=None, sweeps=16, names=None, device=None):
+def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bounds=None, sweeps=16, names=None, device=None, smooth=0.0,
+           smooth_weights=None):
     """Vertex offsets (what the decoder writes, BEFORE the template is added) -> rig.RigFrames: per frame the coefficients c of the
     ridge-regularised, box-constrained least-squares fit of the offsets onto the blendshape basis [K, 3 V] (weights [V] per vertex,
     bounds = (lo, hi), `sweeps` of projected Gauss-Seidel), resampled in time when fps = (fps_in, fps_out) names two different rates,
     in ONE device call (rig.RigPlan; include/fdm_hip.h, fdm_rig_forward).  basis may be a rig.RigPlan or the dict of its arguments
     (the other rig arguments are then not read).  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None:
     all L) -> one RigFrames for the batch; or a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of RigFrames, each cut to
-    its own frames and bit for bit what its own call returns."""
+    its own frames and bit for bit what its own call returns.  smooth > 0 (with smooth_weights [K] or None) fits each clip's frames
+    together under a penalty on the change between neighbouring OUTPUT frames (rig.RigPlan): smooth
+    curves that still respect the bounds, on the device.  A clip's result does not depend on the clips batched with it."""
     from .rig import RigPlan
     x, frames, many = _pack_offsets(offsets, frames, device, "to_rig")
-    rig = basis if isinstance(basis, (RigPlan, dict)) else dict(basis=basis, weights=weights, ridge=ridge, bounds=bounds, sweeps=sweeps, names=names)
+    rig = basis if isinstance(basis, (RigPlan, dict)) else dict(basis=basis, weights=weights, ridge=ridge, bounds=bounds, sweeps=sweeps, names=names,
+                                                                smooth=smooth, smooth_weights=smooth_weights)
     rf = _rig_plan(rig, x.device).forward(x, frames, fps)
     return _split_rig(rf) if many else rf
 
@@ -453,10 +457,11 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     With faces= the mesh.MeshFrames are made from the posed vertices; rig= still fits the un-posed offsets (rig= without faces=
     returns no vertices: flame= is refused with it).  None: every path as before.  (SlotServer does not take it.)
 
-    rig (a rig.RigPlan or the dict of its arguments: basis, weights, ridge, bounds, sweeps, names): the decoder's offsets -- never the
+    rig (a rig.RigPlan or the dict of its arguments: basis, weights, ridge, bounds, sweeps, names, smooth, smooth_weights): the decoder's offsets -- never the
     templated vertices -- go through the device rig hand-off (to_rig) and the call returns (rig.RigFrames, latent) in place of the
     vertices: blendshape coefficients [B, L_out, K] at out_fps.  With faces= too it returns ((mesh.MeshFrames, rig.RigFrames),
-    latent); the two read the same offsets.  None: every path as before.
+    latent); the two read the same offsets.  None: every path as before.  rig=dict(..., smooth=mu) fits each clip's frames together
+    (to_rig); animate_many, animate_long and SlotServer pass the same dict on, and a clip's curves do not depend on its batch.
 
     faces [F, 3]: the decoder's output goes through the device mesh hand-off (to_mesh) and the call returns (mesh.MeshFrames,
     latent): positions [B, L_out, V, 3] -- the template added there, the same bits as the vertices returned without faces -- and
@@ -1036,13 +1041,16 @@ def track_arguments(a, p, L):
 
 
 def add_rig_arguments(ap):
-    """--rig_file / --rig_ridge / --rig_sweeps of the demo command lines (the device rig hand-off, to_rig)."""
+    """--rig_file / --rig_ridge / --rig_sweeps / --rig_smooth of the demo command lines (the device rig hand-off, to_rig)."""
     ap.add_argument("--rig_file", type=str, default=None,
-                    help="build-added: blendshape rig (.npz: basis [K, 3V], optional names, weights [V], lo, hi): also save <stem>_rig.npy "
+                    help="build-added: blendshape rig (.npz: basis [K, 3V], optional names, weights [V], lo, hi, smooth_weights [K]): also save <stem>_rig.npy "
                          "[1, L_out, K], the coefficients fitted to the decoded offsets on the device.  Without --faces_file, --out_fps resamples "
                          "<stem>_rig.npy alone: <stem>.npy keeps the model's frame rate")
     ap.add_argument("--rig_ridge", type=float, default=0.0, help="build-added: ridge of the fit (with --rig_file)")
     ap.add_argument("--rig_sweeps", type=int, default=16, help="build-added: projected Gauss-Seidel sweeps of a bounded fit (with --rig_file)")
+    ap.add_argument("--rig_smooth", type=float, default=0.0,
+                    help="build-added: strength of the smoothness penalty between neighbouring saved frames, in the units of the rig's Gram "
+                         "matrix (with --rig_file; 0: every frame is fitted on its own).  The .npz key smooth_weights [K] scales it per coefficient")
 
 
 def rig_arguments(a):
@@ -1052,9 +1060,12 @@ def rig_arguments(a):
     with np.load(a.rig_file, allow_pickle=False) as z:
         if "basis" not in z or ("lo" in z) != ("hi" in z):
             raise ValueError(f"{a.rig_file}: needs the key basis, and lo and hi together (has {sorted(z.files)})")
-        return dict(basis=z["basis"], weights=z["weights"] if "weights" in z else None, ridge=a.rig_ridge,
-                    bounds=(z["lo"], z["hi"]) if "lo" in z else None, sweeps=a.rig_sweeps,
-                    names=[str(n) for n in z["names"]] if "names" in z else None)
+        kw = dict(basis=z["basis"], weights=z["weights"] if "weights" in z else None, ridge=a.rig_ridge,
+                  bounds=(z["lo"], z["hi"]) if "lo" in z else None, sweeps=a.rig_sweeps,
+                  names=[str(n) for n in z["names"]] if "names" in z else None)
+        if getattr(a, "rig_smooth", 0.0):      # (a per-frame rig keeps the dict it always had)
+            kw.update(smooth=a.rig_smooth, smooth_weights=z["smooth_weights"] if "smooth_weights" in z else None)
+        return kw
 
 
 def add_flame_arguments(ap):

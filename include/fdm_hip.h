@@ -939,7 +939,8 @@ int fdm_mesh_destroy(fdm_mesh* m);
  *             L_out[b] are written as zeros; input rows at or past frames[b] are never read (they may be NaN).
  * fdm_rig_gram_host (no device): gram [K, K] fp64 = G, chol [K, K] fp32 = L rounded (zeros above the diagonal).
  * fdm_rig_create: basis, vweight, lo, hi are HOST arrays, not read after the call; sweeps = S (16 is the library's default in Python;
- * how many an ill-conditioned artist rig needs is unmeasured).  With a device visible it uploads P, G, L and the bounds; without one
+ * how many an ill-conditioned artist rig needs is unmeasured; under the temporal fit below convergence also slows as mu grows, and
+ * its table is there).  With a device visible it uploads P, G, L and the bounds; without one
  * the object still validates and fdm_rig_forward ends in FDM_ERR_STATE.  FDM_ERR_ARG: a null pointer, K outside [1, 128], V < 1, a
  * negative or non-finite weight or ridge, exactly one of lo and hi, lo_k > hi_k or a non-finite bound, sweeps < 0, a rank-deficient Gram.
  * fdm_rig_forward: offsets [B, L_max, 3 V] fp32 device, frames [B] HOST ints in [0, L_max] (NULL: every clip has L_max frames; copied
@@ -947,8 +948,48 @@ int fdm_mesh_destroy(fdm_mesh* m);
  * never synchronises -- except that a call larger than any before it grows the object's scratch first (the partial sums, the
  * lengths), which waits for the device.  An object holds ONE such scratch: it serves one stream at a time.  Every check is made
  * before the first launch: FDM_ERR_ARG (null r / offsets / coef, a negative or non-finite rate), FDM_ERR_SHAPE (B, L_max or
- * L_out_max < 1, frames[b] outside [0, L_max], L_out_max below the largest L_out[b]).  Not built: a per-frame fit residual, temporal
- * regularisation across frames, head and jaw pose, fp16 output.  Call times: profiles/rig_out/README.md. */
+ * L_out_max < 1, frames[b] outside [0, L_max], L_out_max below the largest L_out[b]).  Not built: a per-frame fit residual, head and
+ * jaw pose, fp16 output.  Call times: profiles/rig_out/README.md.
+ *
+ * Temporal fit (fdm_rig_set_temporal).  The per-frame fit above passes frame-to-frame decoder noise, the
+ * null-space drift of an ill-conditioned rig and coefficients snapping on and off their bounds straight into the curves.  With
+ * smooth = mu > 0 and optional sweights m [K] > 0 (NULL: all 1), M = mu diag(m), the frames of a clip are fitted together.  Everything
+ * up to and including the frame-rate step is as above (P, G, r, L_out, the taps applied to r); then per clip with Lo = L_out[b] frames
+ *   min over c_0..c_{Lo-1} of  sum_f (1/2 c_f^T G c_f - r_f^T c_f) + 1/2 sum_{f>=1} (c_f - c_{f-1})^T M (c_f - c_{f-1})   s.t. lo <= c_f <= hi.
+ * The penalty is on OUTPUT frames: at another fps_out the same mu smooths over a different time span.  mu = 0 is the per-frame fit.
+ * n_f = the number of neighbours of frame f inside its clip: 0 when Lo = 1, 1 at the two ends, 2 inside.
+ *   tables    fdm_rig_temporal_tables_host (host, fp64, no device): D = diag(1 / sqrt(mu m_k)); A = D G D = U Lam U^T by cyclic Jacobi
+ *             rotations (written in the library); eigenvalues ascending; each eigenvector's sign such that its largest-magnitude entry is
+ *             positive (lowest index on a tie); Q = D U, so Q^T G Q = Lam and Q^T M Q = I.  lam [K], Q [K, K] (column k = mode k) fp64.
+ *             The object keeps lam, Q, Q^T and mvec_k = mu m_k, each rounded once to fp32.  FDM_ERR_ARG: mu negative or non-finite (0
+ *             too for the tables: there are none), m_k <= 0 or non-finite, lam_k <= 0 or a value that does not fit fp32.
+ *   modal in  per output frame z_k = sum_j QT[k][j] r_j: j ascending, the first product starts the sum, every product and sum rounded.
+ *   time      per (clip, k), fp32, every operation rounded on its own, with d_f = lam_k + (float)n_f:
+ *               w_0 = d_0; iw_0 = 1 / w_0; u_0 = z_0; for f = 1..Lo-1: w_f = d_f - iw_{f-1}; iw_f = 1 / w_f; u_f = z_f + (u_{f-1} * iw_{f-1})
+ *               y_{Lo-1} = u_{Lo-1} * iw_{Lo-1}; for f = Lo-2..0: y_f = (u_f + y_{f+1}) * iw_f
+ *             (strictly diagonally dominant since lam_k > 0: no pivoting).  u and iw live in the object's scratch.
+ *   modal out x_k = sum_j Q[k][j] y_j, the same order and rounding.  No bounds: c = x.  Bounds: c = min(max(x, lo), hi), a NaN kept.
+ *   bounds    S sweeps of red-black projected Gauss-Seidel in place in coef; a sweep is colour 0 (even f inside the clip), then colour 1
+ *             (odd f), one launch each.  For a frame of the current colour, reading its neighbours' current values:
+ *               s = c_{f-1}, or c_{f+1}, or (c_{f-1} + c_{f+1}), or absent (n_f = 0); g = r_f when s is absent, else r_f + (mvec * s)
+ *               for j = 0..K-1, all k: g_k = g_k - (G_kj * c_j);   e_k = (float)n_f * mvec_k;   g_k = g_k - (e_k * c_k)
+ *               for j = 0..K-1: den = G_jj + e_j; n = min(max(c_j + g_j / den, lo_j), hi_j); delta = n - c_j; c_j = n;
+ *                               for all k: g_k = g_k - (G_kj * delta); then g_j = g_j - (e_j * delta)
+ *             Frames of one colour never read each other; the launch boundary is the only synchronisation between half-sweeps (no grid
+ *             barrier, no atomics).  Convergence slows as mu grows against G.  Measured on the float32 restatement against fp64 bounded
+ *             least squares of the stacked system (K = 12, 3 V = 96, Lo = 24, bounds [0, 1]; tests/test_rig_temporal_cpu.py), max-abs
+ *             distance at 16 / 64 sweeps: mu = 0.1 tr(G)/K 2.3e-07 / 2.3e-07; mu = tr(G)/K 2.8e-05 / 4.8e-07; mu = 10 tr(G)/K
+ *             2.1e-02 / 3.9e-04.  Raise S with mu.
+ *   output    as above.  L_out[b] = 0 gives no rows; L_out[b] = 1 is the modal solve with n = 0: the per-frame answer mathematically,
+ *             not bit for bit.  A non-finite live offset row makes every coefficient of ITS CLIP NaN (the frames are coupled), never a
+ *             bound; other clips keep their bits.
+ * A clip's bits do not depend on the batch: every step names only the clip's own rows, its own Lo and the frame's parity inside the
+ * clip; B, L_max, L_out_max and the tiling only decide who computes it.
+ * fdm_rig_set_temporal: builds the tables from the object's fp64 G, uploads them and waits for the device (before and after: a call in
+ * flight may read the old ones); smooth = 0 returns the object to the per-frame path.  Without a device it still validates.  An object
+ * on which it was never called, or was last called with 0, runs exactly the launches of the per-frame fit.  fdm_rig_forward keeps its
+ * signature and fdm_version() its value: callers detect the feature by the symbol.  A bounded temporal call is 3 + 2 S launches after
+ * the projection.  Call times: profiles/rig_temporal/README.md. */
 typedef struct fdm_rig fdm_rig;
 int fdm_rig_gram_host(const float* basis, const float* vweight, int K, int V, double ridge, double* gram, float* chol);
 int fdm_rig_create(const float* basis, int K, int V, const float* vweight, double ridge, const float* lo, const float* hi, int sweeps,
@@ -956,6 +997,8 @@ int fdm_rig_create(const float* basis, int K, int V, const float* vweight, doubl
 int fdm_rig_forward(fdm_rig* r, const float* offsets, const int* frames, int B, int L_max, double fps_in, double fps_out, float* coef,
                     float* proj, int L_out_max, int* frames_out, void* stream);
 int fdm_rig_destroy(fdm_rig* r);
+int fdm_rig_temporal_tables_host(const double* gram, int K, double smooth, const float* sweights, double* lam, double* Q);
+int fdm_rig_set_temporal(fdm_rig* r, double smooth, const float* sweights);
 
 /* ------------------------------------------------------------------------------------------
  * Parametric head: parameters in, vertices out.  A head of the SMPL / FLAME family (Loper et al. 2015; Li et al. 2017): blend shapes,
