@@ -100,6 +100,7 @@ class FlameModelDesc(C.Structure):
 
 PCM_S16, PCM_S32, PCM_U8, PCM_F32 = range(4)      # fdm_pcm.format
 MESH_INTERLEAVED, MESH_F16, MESH_NORMALS = 1, 2, 4      # fdm_mesh_forward flags
+WRAP_OFFSETS = 1      # fdm_wrap_forward flags
 
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
@@ -222,6 +223,11 @@ SYMBOLS = {
     "fdm_flame_create": (ci, [C.POINTER(FlameModelDesc), vp, vp, ci, C.POINTER(vp)]),
     "fdm_flame_forward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
     "fdm_flame_destroy": (ci, [vp]),
+    "fdm_wrap_coords_host": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp]),
+    "fdm_wrap_create": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, C.POINTER(vp)]),
+    "fdm_wrap_binding": (ci, [vp, vp, vp, vp]),
+    "fdm_wrap_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]),
+    "fdm_wrap_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),
     "fdm_vq_quant": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),

@@ -227,6 +227,35 @@ def to_flame(pose, model, expression=None, shape=None, transl=None, extra=None, 
     return _flame_plan(model, device, landmarks).forward(pose, expression, shape, transl, extra, frames)
 
 
+def _wrap_plan(wrap, device):
+    """The wrap hand-off plan of `device`, the current stream and this binding (wrap.WrapPlan.key).  wrap: a wrap.WrapPlan (used as it is
+    where it was made for this device and stream, made again from its arguments -- the binding it found included -- otherwise) or the
+    dict of WrapPlan's arguments (every call then digests the meshes to recognise them: animate_many, animate_long and SlotServer come
+    here once and go on with the plan)."""
+    from .wrap import WrapPlan, identity
+    dv, at = _on_stream(device)
+    if isinstance(wrap, WrapPlan):
+        return cached_plan(at, "wrap", wrap.key, lambda: WrapPlan(device=dv, **wrap.arguments()), wrap)
+    return cached_plan(at, "wrap", identity(**wrap), lambda: WrapPlan(device=dv, **wrap))
+
+
+@torch.no_grad()
+def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device=None):
+    """Vertex offsets of the model's topology (or vertices, with template=None) -> the vertices [B, L, 3 Vt] of a mesh of ANOTHER
+    topology that is bound to the model's rest surface, in ONE device call (wrap.WrapPlan; include/fdm_hip.h, fdm_wrap_forward).
+    wrap: a wrap.WrapPlan or the dict of its arguments (src_rest, faces, dst_rest, face_idx, weights).  offsets: a device tensor
+    [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None: all L; rows past a clip's frames come out as zeros); or a ragged LIST of
+    [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of [1, L_b, 3 Vt], each bit for bit what its own call returns.  template: [1 or B, 3 V] of
+    the SOURCE, or for a list one per clip.  offsets_out: displacements from the target's rest position instead of positions -- a rig
+    on the target's own blendshapes is to_rig(to_wrap(..., offsets_out=True), basis_t).  There is no frame-rate step here: resample
+    AFTER, with to_mesh(wrapped, faces_t, None, fps=) or to_rig(..., fps=)."""
+    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
+        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
+    x, frames, many = _pack_offsets(offsets, frames, device, "to_wrap")
+    y = _wrap_plan(wrap, x.device).forward(x, frames, template, offsets_out)
+    return [y[b:b + 1, :n] for b, n in enumerate(frames)] if many else y
+
+
 def _flame_rows(x, L, R, what):
     """A per-frame argument of flame= for R clips of L frames: [L', n] (for all) or [R, L', n], L' >= L -> [R, L, n]"""
     x = torch.as_tensor(x, dtype=torch.float32)
@@ -393,33 +422,43 @@ def _template_rows(template, width, device, S=1, B=1):
     return tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp
 
 
-def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None):
+def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None, wrap=None):
     """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
     template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair.
     flame=: the offsets pose the model's head (_flame_posed) and the posed vertices stand where offsets + template stood (the
     template argument is not read); rig= still fits the un-posed offsets; rig= without faces= returns no vertices, so flame= is
-    refused with it."""
+    refused with it.  wrap=: the vertices of the bound mesh (to_wrap) stand where offsets + template stood -- after flame= they follow
+    the posed head; with faces= the mesh hand-off runs on them with no template, so `faces` is then the TARGET's triangle list and fps
+    applies there; rig= keeps fitting the model's own offsets (a rig on the target topology is to_rig(to_wrap(..., offsets_out=True),
+    basis_t)), and rig= without faces= is refused with it as with flame=."""
     if flame is not None:
         _flame_check(flame)
         if rig is not None and faces is None:
             raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
+    if wrap is not None and rig is not None and faces is None:
+        raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
     rf = None if rig is None else to_rig(out, rig, fps=fps)
     if faces is None and rf is not None:
         return rf
     if flame is not None:
         out, template = _flame_posed(out, flame, device, S=S, B=B), None
     tp = None if template is None else _template_rows(template, out.shape[-1], device, S, B)
+    if wrap is not None:
+        out, tp = to_wrap(out, wrap, tp, device=device), None
     if faces is None:
         return out if tp is None else out + tp.unsqueeze(1)
     mf = to_mesh(out, faces, tp, fps=fps, **(mesh or {}))
     return mf if rf is None else (mf, rf)
 
 
-def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None):
+def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None, wrap=None):
     """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip: ONE mesh call and ONE rig call
     over the unequal lengths, each result bit for bit its own call's.  flame=: ONE ragged head call first (pose / expression /
-    transl [L', n] for all clips or a list with one per clip); its posed clips stand where offsets + template stood."""
+    transl [L', n] for all clips or a list with one per clip); its posed clips stand where offsets + template stood.  wrap=: ONE ragged
+    wrap call after that; the wrapped clips stand where offsets + template stood (as _hand_off)."""
     offsets = clips
+    if wrap is not None and rig is not None and faces is None:
+        raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
     if flame is not None:
         _flame_check(flame)
         if rig is not None and faces is None:
@@ -436,6 +475,8 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
                 per[k] = pad
         posed = _flame_posed(x, per, device, frames)
         clips, templates = [posed[b:b + 1, :n] for b, n in enumerate(frames)], None
+    if wrap is not None:
+        clips, templates = to_wrap(clips, wrap, templates, device=device), None
     if faces is None and rig is None:
         return clips if templates is None else [c + _template_rows(t, c.shape[-1], device).unsqueeze(1) for c, t in zip(clips, templates)]
     res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
@@ -448,8 +489,15 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    wrap (a wrap.WrapPlan or the dict of its arguments: src_rest, faces, dst_rest, face_idx, weights): a mesh of ANOTHER topology,
+    bound once to the model's rest surface, follows the animation (to_wrap): its vertices [B, L, 3 Vt] are returned where
+    offsets + template stood; after flame= they follow the posed head.  With faces= the mesh hand-off runs on the wrapped vertices, so
+    faces= is then the TARGET's triangle list and out_fps= applies there.  rig= keeps fitting the model's own offsets exactly as
+    without wrap= (and is refused with wrap= unless faces= is given, as with flame=); a rig on the target topology is
+    to_rig(to_wrap(offsets, wrap, offsets_out=True), basis_t).  None: every path as before.
 
     flame = dict(model= a flame.FlameModel / FlamePlan / model file, pose= [L', 3 J] or [B, L', 3 J] axis-angle (L' >= L), shape=,
     expression=, transl=; per-clip arguments repeat per condition when S > 1): the decoder's offsets enter the parametric head as `extra` (to_flame) at the model's frame rate and the
@@ -519,14 +567,18 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     latent = _sample(diffusion, key, audio, shape, cond, x_T.repeat_interleave(S, dim=0) if S > 1 else x_T, seed, **trk)
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emotion_one_hot, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame, wrap), latent
 
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
-                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
+                 style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None,
+                 wrap=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    wrap: as animate(); each group's decoded clips go through ONE ragged wrap call and the first returned list holds [1, L_b, 3 Vt]
+    per clip (or what faces= makes of them).  None: every path as before.
 
     flame: as animate(), with pose / expression / transl one [L', n] for all clips or a list with one per clip; each group's decoded
     clips go through ONE ragged head call.  None: every path as before.
@@ -561,6 +613,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model, p, _, _ = _unwrap(diffusion)
     rig = None if rig is None else _rig_plan(rig, device)        # a dict is digested and made into a plan once, not per group
+    wrap = None if wrap is None else _wrap_plan(wrap, device)
     n = len(audios)
     wavs = _waveforms(audios, rate, device)
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
@@ -632,7 +685,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             # the group's clips, each at its own length, through one mesh and one rig hand-off call
             tps = None if templates is None else [_per(templates, b) for b in grp]
             fl = None if flame is None else {k: ([v[b] for b in grp] if (k in ("pose", "expression", "transl") and isinstance(v, (list, tuple))) else v) for k, v in flame.items()}
-            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl)):
+            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl, wrap)):
                 verts[b] = v
     finally:
         model._hub_key, model._hub = prev
@@ -642,8 +695,9 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    wrap: as animate(): the bound mesh follows the whole recording.
     flame: as animate(): the whole recording's offsets pose the model's head (pose [L', 3 J] with L' >= L_total).
     rig: as animate(): the whole recording's offsets go through the rig hand-off and the call returns (rig.RigFrames, latent), or
     ((mesh.MeshFrames, rig.RigFrames), latent) with faces=.
@@ -662,6 +716,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     blended x0 in the long layout)."""
     model, p, cfg, scale = _unwrap(diffusion)
     rig = None if rig is None else _rig_plan(rig, device)
+    wrap = None if wrap is None else _wrap_plan(wrap, device)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     style = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B, device)
@@ -678,7 +733,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emo, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame, wrap=wrap), latent
 
 
 class SlotServer:
@@ -714,12 +769,15 @@ class SlotServer:
     None (default): unchanged.
 
     rig: as animate(): every finished clip's offsets go through the rig hand-off and results() yields a rig.RigFrames in place of
-    the vertices (with faces= a (mesh.MeshFrames, rig.RigFrames) pair); the clips of one batched decode share one ragged call."""
+    the vertices (with faces= a (mesh.MeshFrames, rig.RigFrames) pair); the clips of one batched decode share one ragged call.
+
+    wrap: as animate(): every finished clip's vertices are those of the bound mesh ([1, L, 3 Vt], or what faces= makes of them)."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
-                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None):
+                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None):
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
+        self.wrap = None if wrap is None else _wrap_plan(wrap, device)
         self.faces, self.mesh = faces, dict(mesh or {})
         self.rig = None if rig is None else _rig_plan(rig, device)     # a dict is digested and made into a plan once, not per finished clip
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
@@ -947,7 +1005,7 @@ class SlotServer:
     def _vertices(self, out, template):
         """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames, with rig= its
         rig.RigFrames, with both the pair."""
-        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps)
+        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap)
 
     def _finish_one(self, slots, lat, r):
         """One finished request: its latent quantised and decoded at its own length, the result kept for results(), its slots idle."""
@@ -991,11 +1049,11 @@ class SlotServer:
         self.batched_decodes.append(len(done))
         clips, tps = [outs[i:i + 1, :r["L"]] for i, r in enumerate(reqs)], [r["template"] for r in reqs]
         mixed = any(t is None for t in tps) and any(t is not None for t in tps)
-        if (self.faces is None and self.rig is None) or (self.faces is not None and mixed):
+        if (self.faces is None and self.rig is None and self.wrap is None) or ((self.faces is not None or self.wrap is not None) and mixed):
             # no hand-off call to share, or a mesh with a template on some requests only: clip by clip
             res = [self._vertices(c.contiguous(), t) for c, t in zip(clips, tps)]
         else:       # one mesh call and one rig call over the unequal lengths
-            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps)
+            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap)
         for s, r, out, lat in zip(done, reqs, res, lats):
             self._done.append((r["handle"], out, lat))
             self._slot[s] = None
@@ -1068,6 +1126,45 @@ def rig_arguments(a):
         return kw
 
 
+def add_wrap_arguments(ap):
+    """--wrap_file / --wrap_falloff of the demo command lines (the device wrap hand-off, to_wrap)."""
+    ap.add_argument("--wrap_file", type=str, default=None,
+                    help="build-added: a mesh of another topology (.npz: vertices [Vt, 3] in the template's space, optional faces [Ft, 3], "
+                         "weights [Vt], face_idx [Vt]) that follows the animation: also save <stem>_wrap.npy [1, L, 3 Vt], one frame per frame "
+                         "of <stem>.npy, which keeps its content.  Needs --faces_file (the model's triangles) and a template.  With faces in "
+                         "the file and --save_normals: <stem>_wrap_normals.npy")
+    ap.add_argument("--wrap_falloff", type=str, default=None,
+                    help="build-added: r0,r1 -- target vertices closer than r0 to the face follow it fully, those beyond r1 stay at rest, "
+                         "smoothstep between (with --wrap_file; for a body mesh of which only the face should move)")
+
+
+def wrap_arguments(a, faces, template, device):
+    """(wrap.WrapPlan, the target's faces or None) from the parsed flags, or (None, None) without --wrap_file.  faces: the model's
+    triangle list; template: its rest vertices [1, 3 V]."""
+    if not getattr(a, "wrap_file", None):
+        if getattr(a, "wrap_falloff", None):
+            raise ValueError("--wrap_falloff needs --wrap_file")
+        return None, None
+    if faces is None or template is None:
+        raise ValueError("--wrap_file binds to the model's rest surface: it needs --faces_file and a template")
+    from .wrap import WrapPlan, falloff_weights
+    src = torch.as_tensor(template, dtype=torch.float32).detach().cpu().numpy().reshape(-1, 3)
+    with np.load(a.wrap_file, allow_pickle=False) as z:
+        if "vertices" not in z:
+            raise ValueError(f"{a.wrap_file}: needs the key vertices (has {sorted(z.files)})")
+        kw = dict(src_rest=src, faces=faces, dst_rest=z["vertices"], face_idx=z["face_idx"] if "face_idx" in z else None,
+                  weights=z["weights"] if "weights" in z else None)
+        faces_t = z["faces"] if "faces" in z else None
+    plan = WrapPlan(device=device, **kw)
+    if a.wrap_falloff:
+        if kw["weights"] is not None:
+            raise ValueError("--wrap_falloff with weights in the file: give one of them")
+        r0, r1 = (float(x) for x in a.wrap_falloff.split(","))
+        fi, _, dist = plan.binding()
+        plan = WrapPlan(device=device, **dict(kw, face_idx=fi, weights=falloff_weights(dist, r0, r1)))
+    return plan, faces_t
+
+
 def add_flame_arguments(ap):
     """--flame_model / --flame_expr_at / --template_params of the MEAD command lines (the device parametric head, to_flame)."""
     ap.add_argument("--flame_model", type=str, default=None,
@@ -1136,6 +1233,7 @@ def demo_main(preset, argv=None):
     ap.add_argument("--save_normals", action="store_true", help="build-added: also save <stem>_normals.npy [1, L_out, 3V] (with --faces_file)")
     add_track_arguments(ap, p)
     add_rig_arguments(ap)
+    add_wrap_arguments(ap)
     if p.n_emo:        # MEAD: the template comes from FLAME parameters
         add_flame_arguments(ap)
     a = ap.parse_args(argv)
@@ -1152,6 +1250,7 @@ def demo_main(preset, argv=None):
     ft = flame_arguments(a, a.device)        # --flame_model: the template from parameters, in place of --template_file
     if ft is not None:
         template = ft
+    wp, faces_t = wrap_arguments(a, np.load(a.faces_file) if a.faces_file else None, template, a.device)
     emo = None
     if p.n_emo:
         emo = torch.eye(p.n_emo)[EMOTIONS.index(a.emotion)].unsqueeze(0)
@@ -1183,6 +1282,14 @@ def demo_main(preset, argv=None):
             np.save(dst + "_normals", nr.detach().cpu().numpy())
             print(f"saved {dst}_normals.npy {tuple(nr.shape)}")
         out = out.positions.reshape(out.positions.shape[0], out.positions.shape[1], -1)
+    if wp is not None:      # the bound mesh follows the saved frames: one wrapped frame per frame of <stem>.npy
+        wv = to_wrap(out, wp)
+        if faces_t is not None and a.save_normals:
+            nr = to_mesh(wv, faces_t, None, normals=True).normals.reshape(wv.shape[0], wv.shape[1], -1)
+            np.save(dst + "_wrap_normals", nr.detach().cpu().numpy())
+            print(f"saved {dst}_wrap_normals.npy {tuple(nr.shape)}")
+        np.save(dst + "_wrap", wv.detach().cpu().numpy())
+        print(f"saved {dst}_wrap.npy {tuple(wv.shape)}")
     np.save(dst, out.detach().cpu().numpy())
     print(f"saved {dst}.npy {tuple(out.shape)}")
     return dst + ".npy"

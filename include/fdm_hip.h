@@ -1058,6 +1058,72 @@ int fdm_flame_forward(fdm_flame* f, const float* shape, int NS, int shape_rows, 
                       void* stream);
 int fdm_flame_destroy(fdm_flame* f);
 
+/* ------------------------------------------------------------------------------------------
+ * Wrap hand-off: the animated face drives a mesh of ANOTHER topology (a character head with its own vertex count and UV seams, another
+ * LOD, a face patch of a body mesh).  A surface binding: every vertex of the target is bound once, at create, to one triangle of the
+ * source's REST surface and follows that triangle in every frame.  The output has the layout fdm_mesh_forward and fdm_rig_forward read
+ * ([B, L_max, 3 Vt]), so target normals, the frame rate, fp16 and a rig fit on the target's own blendshapes are those calls, AFTER this
+ * one: there is no frame-rate step here (resample the wrapped frames with the mesh or rig hand-off).
+ * Everything on the device is fp32, fixed order, no contraction, no atomics.  dot(x, y) = (x.x y.x + x.y y.y) + x.z y.z; cross(x, y) =
+ * (x.y y.z - x.z y.y, x.z y.x - x.x y.z, x.x y.y - x.y y.x), two rounded products and one rounded subtraction per component (the mesh
+ * hand-off's); vector sums and differences are per component.
+ * Inputs at create (HOST arrays, not read after the call): source rest S [V, 3], source triangles faces [F, 3], target rest T [Vt, 3],
+ *   optional face_idx [Vt] (a binding brought from a DCC tool or a cache), optional weights [Vt] in [0, 1].
+ * Nearest face (device, fp32; only when face_idx is NULL).  Per face f = (a, b, c) of the rest surface, once: ab = b - a, ac = c - a,
+ *   bc = c - b, n = cross(ab, ac), d = dot(n, n); the face is a candidate only when d > 0.  Per target vertex q and candidate face, the
+ *   closest point by the region walk of Ericson, Real-Time Collision Detection 5.1.5, every operation rounded on its own:
+ *     ap = q - a, bp = q - b, cp = q - c; d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp),
+ *     d6 = dot(ac, cp); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4 (two products, one subtraction); d43 = d4 - d3,
+ *     d56 = d5 - d6.  The FIRST region in this order whose test holds:
+ *       0 vertex a   d1 <= 0 and d2 <= 0                    P = a
+ *       1 vertex b   d3 >= 0 and d4 <= d3                   P = b
+ *       2 edge ab    vc <= 0 and d1 >= 0 and d3 <= 0        t1 = d1 / (d1 - d3),        P = a + t1 ab
+ *       3 vertex c   d6 >= 0 and d5 <= d6                   P = c
+ *       4 edge ac    vb <= 0 and d2 >= 0 and d6 <= 0        t2 = d2 / (d2 - d6),        P = a + t2 ac
+ *       5 edge bc    va <= 0 and d43 >= 0 and d56 >= 0      t1 = d43 / (d43 + d56),     P = b + t1 bc
+ *       6 interior   otherwise: s = (va + vb) + vc,         t1 = vb / s, t2 = vc / s,   P = a + t1 ab + t2 ac
+ *     written as selects: P = (base + t1 dir) + t2 ac with base = a, b or c, dir = ab (bc in region 5), and t1 = 0 / 1, t2 = 0 / 1
+ *     where the region states none (so a vertex region gives the vertex itself); divisions correctly rounded.  r = q - P,
+ *     dist2 = dot(r, r).  q takes the face with the strictly smallest dist2 scanning f ascending from best = +inf: a tie keeps the
+ *     lowest index and a NaN or infinite dist2 never wins.  A vertex left with no candidate fails the create (FDM_ERR_ARG, the message
+ *     names the vertex).  The result is a function of q and the face list alone: not of Vt, the face tile of the kernel or how the
+ *     faces are split over workgroups (partial minima combine to the lowest dist2, then the lowest index).
+ * Coordinates (host, fp64, rounded once to fp32; fdm_wrap_coords_host, no device needed).  For q bound to face (a, b, c): e1 = b - a,
+ *   e2 = c - a, r = q - a, n = cross(e1, e2), nn = dot(n, n), nh = n / sqrt(nn); g11 = dot(e1, e1), g12 = dot(e1, e2), g22 = dot(e2, e2),
+ *   r1 = dot(e1, r), r2 = dot(e2, r), det = g11 g22 - g12 g12; u = (g22 r1 - g12 r2) / det, v = (g11 r2 - g12 r1) / det (the 2 x 2 normal
+ *   equations), h = dot(r, nh): q = a + u e1 + v e2 + h nh.  (u, v) are plane coordinates and leave [0, 1] when the closest point is on
+ *   an edge.  dist = sqrt(dist2) of the region walk above in fp64 for that face, rounded to fp32: the value a falloff reads, the same
+ *   whichever way face_idx was obtained.  FDM_ERR_ARG: a null pointer, F, V or Vt < 1, an index outside its range, a face without area
+ *   (nn or det not > 0), a non-finite coordinate.
+ * Follow (device, fp32, per live frame row of clip b and target vertex j with face (a, b, c), (u, v, h), rest T_j, weight w_j):
+ *   p = offset + template for the three source vertices (one fp32 add; no template: p = offset), as in fdm_mesh_forward;
+ *   e1 = p_b - p_a, e2 = p_c - p_a, n = cross(e1, e2), d = dot(n, n); nh = n / sqrtf(d) with correctly rounded root and division when
+ *   d > 0, else nh = 0 (a face that lost its area in this frame); y = ((p_a + u e1) + v e2) + h nh, every operation rounded on its own.
+ *   With weights o = w_j (y - T_j), without o = y - T_j; the output is T_j + o, or o itself under FDM_WRAP_OFFSETS (the layout a rig
+ *   fit on the target topology reads).  Without weights and without FDM_WRAP_OFFSETS the output is y: no subtract and add back.
+ *   out [B, L_max, 3 Vt] fp32; rows at or past frames[b] are written as zeros, input rows at or past frames[b] are never read (they may
+ *   be NaN); a clip's rows do not depend on the batch, L_max or a tile size.
+ * Not built: scaling h with the triangle's area, smoothing across binding seams, binding to more than one face, fp16 output (the mesh
+ * hand-off does that).
+ * fdm_wrap_create: with face_idx given it validates (and computes the coordinates) without a device, and fdm_wrap_forward then ends in
+ * FDM_ERR_STATE; with face_idx NULL and no device it returns FDM_ERR_STATE.  It may wait for the device.  FDM_ERR_ARG also for a weight
+ * outside [0, 1] or non-finite.  fdm_wrap_binding copies face_idx [Vt], uvh [Vt, 3] and dist [Vt] to HOST arrays (any may be NULL).
+ * fdm_wrap_forward: offsets [B, L_max, 3 V] fp32 device, frames [B] HOST ints (NULL: L_max each), tmpl [tmpl_rows, 3 V] fp32 device,
+ * tmpl_rows = 0, 1 or B, out device.  Launches on `stream` and never synchronises, except to grow the lengths scratch; an object serves
+ * one stream at a time.  Every check is made before the first launch: FDM_ERR_ARG (null w / offsets / out, unknown flag bits, tmpl_rows
+ * not 0, 1 or B, a null template with tmpl_rows > 0), FDM_ERR_SHAPE (B or L_max < 1, frames[b] outside [0, L_max]).  fdm_version() keeps
+ * its value: callers detect the feature by the symbol.  Call times: profiles/wrap_out/README.md. */
+#define FDM_WRAP_OFFSETS 1
+typedef struct fdm_wrap fdm_wrap;
+int fdm_wrap_coords_host(const float* src_rest, const int* faces, int F, int V, const float* dst_rest, int Vt, const int* face_idx,
+                         float* uvh /*[Vt,3]*/, float* dist /*[Vt]*/);
+int fdm_wrap_create(const float* src_rest, const int* faces, int F, int V, const float* dst_rest, int Vt,
+                    const int* face_idx /*or NULL: search on the device*/, const float* weights /*or NULL*/, fdm_wrap** out);
+int fdm_wrap_binding(const fdm_wrap* w, int* face_idx, float* uvh, float* dist);      /* host copies; any may be NULL */
+int fdm_wrap_forward(fdm_wrap* w, const float* offsets, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, int flags,
+                     float* out, void* stream);
+int fdm_wrap_destroy(fdm_wrap* w);
+
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
  * (diffusion_BIWI_encoder_decoder.py:565-603: cosine schedule in fp64, fp32 cast); DDIM pairs and per-pair coefficients
  * (:684-708, eta = 0; returns the number of live pairs, the dead (t, -1) pair excluded); get_slopes (models/fdm_vocaset.py:96-106);
