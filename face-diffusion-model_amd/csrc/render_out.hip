@@ -1,0 +1,206 @@
+// Render hand-off behind plain C calls (include/fdm_hip.h, fdm_render_*): positions as the mesh, wrap and head hand-offs write them ->
+// shaded image frames, a depth image and a face-id image.  Kernels: render_out.hpp.  fdm_render_create checks and uploads the topology
+// and keeps the view on the host (it travels to the kernels as an argument, so fdm_render_set_view touches no device memory); a forward
+// call validates (every check before the first launch), lists the live output frames, grows the scratch to one chunk of them and loops
+// over the chunks on the caller's stream.  The vertex normals are the mesh hand-off's own: an internal fdm_mesh over the same faces runs
+// mesh_nrm_kernel on each chunk's positions, unless the caller brings normals.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "host.hpp"
+#include "render_out.hpp"
+
+struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
+  int F = 0, V = 0, W = 0, H = 0;
+  long long chunk_frames = 0;             // 0: the default (scratch under RENDER_SCRATCH_BYTES)
+  fdm::RenderView view;
+  fdm_mesh* mesh = nullptr;               // the normals of a chunk (fdm_mesh_forward on the chunk's positions)
+  int* faces = nullptr;                   // device [F][3]
+  int2* rowtab = nullptr;                 // device: the call's live rows {clip, output frame}
+  float *P = nullptr, *N = nullptr;       // device scratch of one chunk: [n][3V] each
+  int4* xyw = nullptr;                    // [n][V]
+  float4* nc = nullptr;                   // [n][V]
+  unsigned long long* vis = nullptr;      // [n][H][W], zero between calls (render_resolve_kernel leaves it so)
+  long long rowtab_cap = 0, P_cap = 0, N_cap = 0, xyw_cap = 0, nc_cap = 0, vis_cap = 0;
+  std::vector<int2> rows;                 // host: the live rows of the call in flight (the asynchronous upload reads it)
+  bool vis_dirty = false;                 // a call ended between raster and resolve: clear before the next use
+};
+
+namespace {
+using namespace fdm;
+
+constexpr long long RENDER_SCRATCH_BYTES = 256LL << 20;
+constexpr long long RENDER_CHUNK_MAX = 4096;      // rows of one launch (grid y <= 65535)
+
+bool finite_all(const float* x, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(x[i])) return false;
+  return true;
+}
+
+// camera [6] = {fx, fy, cx, cy, near, far}, R [9] row-major world -> camera, t [3], lights [n][4] = {unit direction towards the light
+// in camera space, intensity}: checked, then written into `vw` (untouched on a refusal)
+int check_view(const char* who, const float* camera, const float* R, const float* t, const float* lights, int n_lights, float ambient,
+               RenderView& vw) {
+  if (!camera || !R || !t) return fail(FDM_ERR_ARG, "%s: null camera, R or t", who);
+  if (!finite_all(camera, 6) || !finite_all(R, 9) || !finite_all(t, 3)) return fail(FDM_ERR_ARG, "%s: a non-finite camera number", who);
+  if (!(camera[0] > 0.f) || !(camera[1] > 0.f)) return fail(FDM_ERR_ARG, "%s: focal lengths %g, %g (> 0)", who, (double)camera[0], (double)camera[1]);
+  if (!(camera[4] > 0.f) || !(camera[4] < camera[5])) return fail(FDM_ERR_ARG, "%s: near = %g, far = %g (0 < near < far)", who, (double)camera[4], (double)camera[5]);
+  if (n_lights < 0 || n_lights > RENDER_MAX_LIGHTS) return fail(FDM_ERR_ARG, "%s: %d lights (0 .. %d)", who, n_lights, RENDER_MAX_LIGHTS);
+  if (n_lights && !lights) return fail(FDM_ERR_ARG, "%s: %d lights with a null array", who, n_lights);
+  if (!(ambient >= 0.f) || !std::isfinite(ambient)) return fail(FDM_ERR_ARG, "%s: ambient = %g (finite, >= 0)", who, (double)ambient);
+  for (int l = 0; l < n_lights; ++l) {
+    const float* q = lights + 4 * l;
+    if (!finite_all(q, 4) || !(q[3] >= 0.f)) return fail(FDM_ERR_ARG, "%s: light %d is not finite or has a negative intensity", who, l);
+    const double n2 = (double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2];
+    if (std::fabs(n2 - 1.0) > 1e-4) return fail(FDM_ERR_ARG, "%s: the direction of light %d has squared length %g (a unit vector)", who, l, n2);
+  }
+  vw.fx = camera[0]; vw.fy = camera[1]; vw.cx = camera[2]; vw.cy = camera[3]; vw.znear = camera[4]; vw.zfar = camera[5];
+  std::memcpy(vw.R, R, sizeof(vw.R));
+  std::memcpy(vw.t, t, sizeof(vw.t));
+  vw.n_lights = n_lights;
+  std::memset(vw.dir, 0, sizeof(vw.dir));
+  std::memset(vw.intensity, 0, sizeof(vw.intensity));
+  for (int l = 0; l < n_lights; ++l) {
+    for (int k = 0; k < 3; ++k) vw.dir[l][k] = lights[4 * l + k];
+    vw.intensity[l] = lights[4 * l + 3];
+  }
+  vw.ambient = ambient;
+  return FDM_OK;
+}
+
+long long frame_bytes(const fdm_render& R) {
+  return (long long)R.V * (12 + 12 + 16 + 16) + (long long)R.W * R.H * 8;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdm_render_create(const int* faces, int F, int V, int W, int H, const float* camera, const float* R, const float* t, const float* lights,
+                      int n_lights, float ambient, const float* base, const float* background, fdm_render** out) {
+  if (!out) return fail(FDM_ERR_ARG, "render_create: null out");
+  if (!faces || !base || !background) return fail(FDM_ERR_ARG, "render_create: null faces, base or background");
+  if (F < 1 || V < 1) return fail(FDM_ERR_ARG, "render_create: F = %d, V = %d", F, V);
+  if (F > 0x7fffffff / 3 || V > 0x7fffffff / 6) return fail(FDM_ERR_ARG, "render_create: F = %d, V = %d (3 F and 6 V are 32-bit ints)", F, V);
+  if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(FDM_ERR_ARG, "render_create: a viewport of %d x %d (1 .. 4096 each)", W, H);
+  for (long long i = 0; i < 3LL * F; ++i)
+    if (faces[i] < 0 || faces[i] >= V) return fail(FDM_ERR_ARG, "render_create: face %lld names vertex %d of %d", i / 3, faces[i], V);
+  for (int k = 0; k < 3; ++k) {
+    if (!(base[k] >= 0.f) || !std::isfinite(base[k])) return fail(FDM_ERR_ARG, "render_create: base[%d] = %g (finite, >= 0)", k, (double)base[k]);
+    if (!(background[k] >= 0.f && background[k] <= 1.f)) return fail(FDM_ERR_ARG, "render_create: background[%d] = %g (in [0, 1])", k, (double)background[k]);
+  }
+  RenderView vw;
+  std::memset(&vw, 0, sizeof(vw));
+  FCK(check_view("render_create", camera, R, t, lights, n_lights, ambient, vw));
+  for (int k = 0; k < 3; ++k) { vw.base[k] = base[k]; vw.background[k] = background[k]; }
+  fdm_render* r = new (std::nothrow) fdm_render();
+  if (!r) return fail(FDM_ERR_STATE, "render_create: out of memory");
+  r->F = F; r->V = V; r->W = W; r->H = H; r->view = vw;
+  const int rc = fdm_mesh_create(faces, F, V, &r->mesh);
+  if (rc != FDM_OK) { delete r; return rc; }
+  fdm_mesh* m = r->mesh;
+  const int rf = handoff_finish(r, out, [&]() { return put(r->mem, &r->faces, faces, (size_t)F * 3); });
+  if (rf != FDM_OK) (void)fdm_mesh_destroy(m);      // (handoff_finish has deleted r)
+  return rf;
+}
+
+int fdm_render_destroy(fdm_render* r) {
+  if (!r) return FDM_OK;
+  fdm_mesh* m = r->mesh;
+  (void)handoff_destroy(r);                         // (waits for the device)
+  return fdm_mesh_destroy(m);
+}
+
+int fdm_render_set_view(fdm_render* r, const float* camera, const float* R, const float* t, const float* lights, int n_lights, float ambient) {
+  if (!r) return fail(FDM_ERR_ARG, "render_set_view: null argument");
+  RenderView vw = r->view;
+  FCK(check_view("render_set_view", camera, R, t, lights, n_lights, ambient, vw));
+  r->view = vw;
+  return FDM_OK;
+}
+
+int fdm_render_set(fdm_render* r, const char* key, long long value) {
+  if (!r || !key) return fail(FDM_ERR_ARG, "render_set: null argument");
+  if (std::strcmp(key, "chunk_frames") != 0) return fail(FDM_ERR_ARG, "render_set: unknown key %s (chunk_frames)", key);
+  if (value < 0 || value > RENDER_CHUNK_MAX) return fail(FDM_ERR_ARG, "render_set: chunk_frames = %lld (0 = the default, at most %lld)", value, RENDER_CHUNK_MAX);
+  r->chunk_frames = value;
+  return FDM_OK;
+}
+
+int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
+                       double fps_out, const float* normals, unsigned char* rgb, float* depth, int* face, int L_out_max, int* frames_out,
+                       void* stream) {
+  if (!r || !positions || !rgb) return fail(FDM_ERR_ARG, "render_forward: null argument");
+  if (tmpl_rows != 0 && tmpl_rows != 1 && tmpl_rows != B) return fail(FDM_ERR_ARG, "render_forward: tmpl_rows = %d (0, 1 or B = %d)", tmpl_rows, B);
+  if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "render_forward: tmpl_rows = %d with a null template", tmpl_rows);
+  FCK(check_fps("render_forward", fps_in, fps_out));
+  if (B < 1 || L_max < 1 || L_out_max < 1) return fail(FDM_ERR_SHAPE, "render_forward: B = %d, L_max = %d, L_out_max = %d", B, L_max, L_out_max);
+  std::vector<int> hl;
+  const ClipLens c = clip_lens(frames, B, L_max, fps_in, fps_out, L_out_max, hl);
+  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "render_forward: clip %d has %d frames, the batch is %d long", c.clip, c.L, L_max);
+  if (c.bad == ClipLens::OUTPUT) return fail(FDM_ERR_SHAPE, "render_forward: clip %d gives %lld frames, the output is %d long", c.clip, c.Lo, L_out_max);
+  const long long V3 = 3LL * r->V, WH = (long long)r->W * r->H;
+  if ((long long)B * L_out_max > 0x7fffffffLL || (V3 + RENDER_POS_TILE - 1) / RENDER_POS_TILE > 65535)
+    return fail(FDM_ERR_SHAPE, "render_forward: %lld output rows of %d vertices exceed one launch", (long long)B * L_out_max, r->V);
+  FCK(handoff_device(*r, "render_forward"));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int2>& rows = r->rows;      // the live output frames, in (clip, frame) order
+  rows.clear();
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < hl[2 * b + 1]; ++t) rows.push_back(make_int2(b, t));
+  const long long live = (long long)rows.size();
+  long long chunk = r->chunk_frames ? r->chunk_frames : std::max(1LL, RENDER_SCRATCH_BYTES / frame_bytes(*r));
+  chunk = std::min(std::min(chunk, RENDER_CHUNK_MAX), std::max(live, 1LL));
+  FCK(grow(r->mem, &r->rowtab, &r->rowtab_cap, std::max(live, 1LL)));
+  FCK(grow(r->mem, &r->P, &r->P_cap, chunk * V3));
+  if (!normals) FCK(grow(r->mem, &r->N, &r->N_cap, chunk * V3));
+  FCK(grow(r->mem, &r->xyw, &r->xyw_cap, chunk * r->V));
+  FCK(grow(r->mem, &r->nc, &r->nc_cap, chunk * r->V));
+  const long long vis_before = r->vis_cap;
+  FCK(grow(r->mem, &r->vis, &r->vis_cap, chunk * WH));
+  if (r->vis_cap != vis_before || r->vis_dirty) {
+    HIPCK(hipMemsetAsync(r->vis, 0, (size_t)r->vis_cap * sizeof(unsigned long long), s));
+    r->vis_dirty = false;
+  }
+  FCK(handoff_lens(*r, hl, s));
+  if (live) HIPCK(hipMemcpyAsync(r->rowtab, rows.data(), (size_t)live * sizeof(int2), hipMemcpyHostToDevice, s));
+  // rows at or past a clip's L_out: zeros in every output
+  for (int b = 0; b < B; ++b) {
+    const long long lo = hl[2 * b + 1], n = (L_out_max - lo) * WH, at = ((long long)b * L_out_max + lo) * WH;
+    if (!n) continue;
+    HIPCK(hipMemsetAsync(rgb + 3 * at, 0, (size_t)(3 * n), s));
+    if (depth) HIPCK(hipMemsetAsync(depth + at, 0, (size_t)n * sizeof(float), s));
+    if (face) HIPCK(hipMemsetAsync(face + at, 0, (size_t)n * sizeof(int), s));
+  }
+  const int rs = resamples(fps_in, fps_out) ? 1 : 0, tstride = tmpl_rows == B && B > 1 ? (int)V3 : 0;
+  const float* tp = tmpl_rows ? tmpl : nullptr;
+  const unsigned vblocks = (unsigned)((r->V + RENDER_TB - 1) / RENDER_TB), fblocks = (unsigned)((r->F + RENDER_TB - 1) / RENDER_TB);
+  const unsigned pblocks = (unsigned)((WH + RENDER_TB - 1) / RENDER_TB);
+  for (long long r0 = 0; r0 < live; r0 += chunk) {
+    const int n = (int)std::min(chunk, live - r0);
+    const int2* tab = r->rowtab + r0;
+    hipLaunchKernelGGL(render_pos_kernel, dim3((unsigned)n, (unsigned)((V3 + RENDER_POS_TILE - 1) / RENDER_POS_TILE)), dim3(256), 0, s, positions, tp,
+                       tstride, (const int*)r->lens, tab, L_max, (int)V3, rs, r->P);
+    if (!normals) {      // one clip of n frames, no template, no rates: positions in place, normals to N
+      const int rc = fdm_mesh_forward(r->mesh, r->P, nullptr, 1, n, nullptr, 0, 0.0, 0.0, FDM_MESH_NORMALS, r->P, r->N, n, nullptr, stream);
+      if (rc != FDM_OK) return rc;
+    }
+    hipLaunchKernelGGL(render_vertex_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const float*)r->P, normals ? normals : (const float*)r->N,
+                       normals ? tab : (const int2*)nullptr, L_out_max, r->V, r->view, r->xyw, r->nc);
+    r->vis_dirty = true;
+    hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
+                       r->W, r->H, r->vis);
+    hipLaunchKernelGGL(render_resolve_kernel, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
+    HIPCK(hipGetLastError());
+    r->vis_dirty = false;
+  }
+  if (frames_out) for (int b = 0; b < B; ++b) frames_out[b] = hl[2 * b + 1];
+  return FDM_OK;
+}
+
+}  // extern "C"

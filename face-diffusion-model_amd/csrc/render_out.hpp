@@ -1,0 +1,245 @@
+// Kernels of the render hand-off (include/fdm_hip.h, fdm_render_*; launched by render_out.hip): the animated mesh -> shaded image frames.
+// DESIGN section 2 item 23 is the definition; the header spells out every operation.  A call works through its live output frames a
+// chunk at a time; per chunk:
+//   render_pos_kernel      grid (chunk rows, blocks of RENDER_POS_TILE elements of 3V): p = offset + template, then the time resampling of
+//                          interp_taps (handoff.hpp) at the clip's own length -- mesh_pos_kernel's expressions on a table of (clip, frame)
+//                          rows instead of the whole [B, L_out_max] rectangle.  The vertex normals of the chunk are mesh_nrm_kernel's
+//                          (render_out.hip calls the mesh hand-off on these positions) unless the caller brings them.
+//   render_vertex_kernel   one lane per (chunk row, vertex): camera transform, projection, snapping to 8 sub-pixel bits, the `bad` test and
+//                          the camera-space normal; two 16-byte records per vertex.
+//   render_raster_kernel   one lane per (chunk row, face): setup (drop, int64 area, orientation) and the clamped box.  A box of at most
+//                          RENDER_LANE_BOX pixels is walked by its own lane; a larger one is handed to the whole wavefront (the lanes that
+//                          hold one are taken in turn by ballot, the triangle travels by shuffles, the 64 lanes take the box's pixels 64
+//                          apart).  Every covered pixel's key goes into the visibility buffer with a 64-bit atomicMax (a vector global
+//                          atomic): a maximum, so the buffer does not depend on the order the triangles arrive in.
+//   render_resolve_kernel  one lane per (chunk row, pixel): reads the key and writes 0 back (the buffer is clear for the next chunk),
+//                          recomputes the winning face's fragment, interpolates the normal, shades, writes rgb / depth / face.
+// No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt; times are unmeasured.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/fdm_hip.h"
+#include "handoff.hpp"
+
+namespace fdm {
+
+constexpr int RENDER_POS_TILE = 1024;     // elements of a row per workgroup of render_pos_kernel (4 per thread, 256 apart)
+constexpr int RENDER_TB = 256;            // threads per workgroup of the vertex, raster and resolve kernels
+constexpr int RENDER_LANE_BOX = 16;       // a clamped box of more pixels than this is walked by the whole wavefront
+constexpr int RENDER_MAX_LIGHTS = 8;
+constexpr int RENDER_SNAP_MAX = 1 << 20;  // |X|, |Y| of a vertex that is not bad
+
+struct RenderView {                       // kernel argument (by value): fdm_render_set_view changes it without touching the device
+  float fx, fy, cx, cy, znear, zfar;
+  float R[9], t[3];
+  int n_lights;
+  float dir[RENDER_MAX_LIGHTS][3], intensity[RENDER_MAX_LIGHTS];
+  float ambient, base[3], background[3];
+};
+
+__device__ __forceinline__ float render_dot(float ax, float ay, float az, float bx, float by, float bz) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
+}
+__device__ __forceinline__ bool render_finite(float x) { return fabsf(x) < __builtin_inff(); }      // false for NaN
+
+// rowtab: [n] {clip, output frame} of the chunk's rows.  lens: [B][2] = {L, L_out}.  P: [n][V3].  tmpl_stride: 0 or V3.
+__global__ __launch_bounds__(256) void render_pos_kernel(const float* off, const float* tmpl, int tmpl_stride, const int* lens, const int2* rowtab,
+                                                         int L_max, int V3, int resample, float* P) {
+  const int2 bt = rowtab[blockIdx.x];
+  const int b = bt.x, t = bt.y;
+  int i0 = t, i1 = t;
+  float l0 = 1.f, l1 = 0.f;
+  if (resample) interp_taps(lens[2 * b], lens[2 * b + 1], t, i0, i1, l0, l1);
+  const float* x0 = off + ((size_t)b * L_max + i0) * V3;
+  const float* x1 = off + ((size_t)b * L_max + i1) * V3;
+  const float* tp = tmpl ? tmpl + (size_t)b * tmpl_stride : nullptr;
+  float* o = P + (size_t)blockIdx.x * V3;
+#pragma unroll
+  for (int k = 0; k < RENDER_POS_TILE / 256; ++k) {
+    const int e = blockIdx.y * RENDER_POS_TILE + k * 256 + threadIdx.x;
+    if (e >= V3) break;
+    float y;
+    if (!resample) {
+      y = tp ? __fadd_rn(x0[e], tp[e]) : x0[e];
+    } else {
+      const float p0 = tp ? __fadd_rn(x0[e], tp[e]) : x0[e], p1 = tp ? __fadd_rn(x1[e], tp[e]) : x1[e];
+      y = __fadd_rn(__fmul_rn(l0, p0), __fmul_rn(l1, p1));
+    }
+    o[e] = y;
+  }
+}
+
+// P: [n][V][3] positions of the chunk.  N: the chunk's normals [n][V][3] (rowtab == null), or the caller's [B][Lo_max][V][3] read at the
+// row's (clip, frame).  xyw: [n][V] {X, Y, bits(w), bad}; nc: [n][V] {nc.x, nc.y, nc.z, 0}.
+__global__ __launch_bounds__(RENDER_TB) void render_vertex_kernel(const float* P, const float* N, const int2* rowtab, int Lo_max, int V,
+                                                                  const RenderView vw, int4* xyw, float4* nc) {
+  const int row = blockIdx.y, v = blockIdx.x * RENDER_TB + threadIdx.x;
+  if (v >= V) return;
+  const float* p = P + ((size_t)row * V + v) * 3;
+  size_t nrow = row;
+  if (rowtab) { const int2 bt = rowtab[row]; nrow = (size_t)bt.x * Lo_max + bt.y; }
+  const float* n = N + (nrow * V + v) * 3;
+  const float px = p[0], py = p[1], pz = p[2], nx = n[0], ny = n[1], nz = n[2];
+  const float* R = vw.R;
+  const float pcx = __fadd_rn(render_dot(R[0], R[1], R[2], px, py, pz), vw.t[0]);
+  const float pcy = __fadd_rn(render_dot(R[3], R[4], R[5], px, py, pz), vw.t[1]);
+  const float pcz = __fadd_rn(render_dot(R[6], R[7], R[8], px, py, pz), vw.t[2]);
+  const float d = -pcz;
+  const float w = __fdiv_rn(1.f, d);
+  const float sx = __fadd_rn(__fmul_rn(vw.fx, __fmul_rn(pcx, w)), vw.cx);
+  const float sy = __fsub_rn(vw.cy, __fmul_rn(vw.fy, __fmul_rn(pcy, w)));
+  const float rx = rintf(__fmul_rn(256.f, sx)), ry = rintf(__fmul_rn(256.f, sy));
+  bool bad = !(render_finite(px) && render_finite(py) && render_finite(pz) && render_finite(d) && render_finite(sx) && render_finite(sy));
+  bad = bad || !(d > vw.znear) || !(d < vw.zfar) || !(fabsf(rx) <= (float)RENDER_SNAP_MAX) || !(fabsf(ry) <= (float)RENDER_SNAP_MAX);
+  const size_t o = (size_t)row * V + v;
+  xyw[o] = make_int4(bad ? 0 : (int)rx, bad ? 0 : (int)ry, __float_as_int(w), bad ? 1 : 0);
+  nc[o] = make_float4(render_dot(R[0], R[1], R[2], nx, ny, nz), render_dot(R[3], R[4], R[5], nx, ny, nz), render_dot(R[6], R[7], R[8], nx, ny, nz), 0.f);
+}
+
+// ---- the oriented triangle of a face and its fragment at a pixel: the one statement the raster and resolve kernels share
+struct RenderTri {
+  int X0, Y0, X1, Y1, X2, Y2;             // snapped, oriented: A > 0
+  float w0, w1, w2;
+  long long A;
+  bool swapped, ok;                       // ok: no bad vertex and A != 0
+};
+__device__ __forceinline__ RenderTri render_setup(const int4& a, const int4& b, const int4& c) {
+  RenderTri T;
+  T.X0 = a.x; T.Y0 = a.y; T.w0 = __int_as_float(a.z);
+  const long long A = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
+  T.swapped = A < 0;
+  const int4& u = T.swapped ? c : b;
+  const int4& v = T.swapped ? b : c;
+  T.X1 = u.x; T.Y1 = u.y; T.w1 = __int_as_float(u.z);
+  T.X2 = v.x; T.Y2 = v.y; T.w2 = __int_as_float(v.z);
+  T.A = T.swapped ? -A : A;
+  T.ok = !(a.w | b.w | c.w) && A != 0;
+  return T;
+}
+// the edge function of the edge a -> b at (px, py), and whether the pixel centre on it belongs to the triangle (top-left rule: with
+// A > 0 in x-right, y-down coordinates a left edge runs up, dy < 0, and a top edge runs right, dy == 0 and dx > 0)
+__device__ __forceinline__ bool render_edge(int Xa, int Ya, int Xb, int Yb, int px, int py, long long& E) {
+  const int dx = Xb - Xa, dy = Yb - Ya;
+  E = (long long)dx * (py - Ya) - (long long)dy * (px - Xa);
+  return E > 0 || (E == 0 && (dy < 0 || (dy == 0 && dx > 0)));
+}
+// covered: E_i, l_i = (float)E_i / (float)A, iw = (l0 w0 + l1 w1) + l2 w2
+__device__ __forceinline__ bool render_fragment(const RenderTri& T, int x, int y, float& l0, float& l1, float& l2, float& iw) {
+  const int px = 256 * x + 128, py = 256 * y + 128;
+  long long E0, E1, E2;
+  const bool in0 = render_edge(T.X1, T.Y1, T.X2, T.Y2, px, py, E0);
+  const bool in1 = render_edge(T.X2, T.Y2, T.X0, T.Y0, px, py, E1);
+  const bool in2 = render_edge(T.X0, T.Y0, T.X1, T.Y1, px, py, E2);
+  const float fA = (float)T.A;
+  l0 = __fdiv_rn((float)E0, fA); l1 = __fdiv_rn((float)E1, fA); l2 = __fdiv_rn((float)E2, fA);
+  iw = __fadd_rn(__fadd_rn(__fmul_rn(l0, T.w0), __fmul_rn(l1, T.w1)), __fmul_rn(l2, T.w2));
+  return in0 && in1 && in2;
+}
+__device__ __forceinline__ void render_hit(const RenderTri& T, int x, int y, int face, int W, unsigned long long* vis) {
+  float l0, l1, l2, iw;
+  if (!render_fragment(T, x, y, l0, l1, l2, iw)) return;
+  if (!(iw > 0.f) || !render_finite(iw)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(iw) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)face);
+  atomicMax(vis + (size_t)y * W + x, key);
+}
+
+// xyw: [n][V]; faces [F][3]; vis: [n][H][W] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
+__global__ __launch_bounds__(RENDER_TB) void render_raster_kernel(const int4* xyw, const int* faces, int F, int V, int W, int H,
+                                                                  unsigned long long* vis) {
+  const int row = blockIdx.y, f = blockIdx.x * RENDER_TB + threadIdx.x;
+  const int4* rec = xyw + (size_t)row * V;
+  unsigned long long* img = vis + (size_t)row * W * H;
+  RenderTri T = {};
+  int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+  if (f < F) {
+    const int* fv = faces + 3 * (size_t)f;
+    T = render_setup(rec[fv[0]], rec[fv[1]], rec[fv[2]]);
+    if (T.ok) {      // pixels whose centre 256 x + 128 lies inside the triangle's box, clamped to the viewport
+      x0 = max((min(T.X0, min(T.X1, T.X2)) + 127) >> 8, 0);
+      x1 = min((max(T.X0, max(T.X1, T.X2)) - 128) >> 8, W - 1);
+      y0 = max((min(T.Y0, min(T.Y1, T.Y2)) + 127) >> 8, 0);
+      y1 = min((max(T.Y0, max(T.Y1, T.Y2)) - 128) >> 8, H - 1);
+    }
+  }
+  const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+  const int npix = (bw > 0 && bh > 0) ? bw * bh : 0;      // <= W H <= 2^24
+  if (npix > 0 && npix <= RENDER_LANE_BOX)
+    for (int y = y0; y <= y1; ++y)
+      for (int x = x0; x <= x1; ++x) render_hit(T, x, y, f, W, img);
+  // the large boxes of this wavefront, one after the other, by all 64 lanes (every lane of the wavefront comes here)
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(npix > RENDER_LANE_BOX);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    RenderTri S;
+    S.X0 = __shfl(T.X0, src); S.Y0 = __shfl(T.Y0, src); S.X1 = __shfl(T.X1, src); S.Y1 = __shfl(T.Y1, src);
+    S.X2 = __shfl(T.X2, src); S.Y2 = __shfl(T.Y2, src);
+    S.w0 = __shfl(T.w0, src); S.w1 = __shfl(T.w1, src); S.w2 = __shfl(T.w2, src);
+    S.A = (long long)(S.X1 - S.X0) * (S.Y2 - S.Y0) - (long long)(S.Y1 - S.Y0) * (S.X2 - S.X0);
+    const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), sbw = __shfl(bw, src), sn = __shfl(npix, src), sf = __shfl(f, src);
+    for (int i = lane; i < sn; i += 64) {
+      const int dy = i / sbw;
+      render_hit(S, sx0 + (i - dy * sbw), sy0 + dy, sf, W, img);
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned char render_u8(float c, float bg) {      // c: base_c k, or the background's channel itself
+  if (c != c) c = bg;
+  c = c < 1.f ? c : 1.f;
+  return (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, c), 0.5f);
+}
+
+// rgb / depth / face: the call's outputs [B][Lo_max][H][W](3); depth and face may be null.  grid (blocks of RENDER_TB pixels, chunk rows).
+__global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
+                                                                   const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
+                                                                   unsigned char* rgb, float* depth, int* face) {
+  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
+  if (i >= W * H) return;
+  const int2 bt = rowtab[row];
+  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
+  unsigned long long* slot = vis + (size_t)row * W * H + i;
+  const unsigned long long key = *slot;
+  *slot = 0ull;
+  float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2], dep = 0.f;
+  int id = -1;
+  const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+  if (key && won < (unsigned)F) {         // (a key names a face of the list: the raster kernel wrote it)
+    id = (int)won;
+    const int* fv = faces + 3 * (size_t)id;
+    const size_t r0 = (size_t)row * V;
+    const RenderTri T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
+    const float4 n0 = nc[r0 + fv[0]], n1 = nc[r0 + fv[T.swapped ? 2 : 1]], n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
+    const int y = i / W, x = i - y * W;
+    float l0, l1, l2, iw;
+    (void)render_fragment(T, x, y, l0, l1, l2, iw);
+    const float b0 = __fdiv_rn(__fmul_rn(l0, T.w0), iw), b1 = __fdiv_rn(__fmul_rn(l1, T.w1), iw), b2 = __fdiv_rn(__fmul_rn(l2, T.w2), iw);
+    float nx = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.x), __fmul_rn(b1, n1.x)), __fmul_rn(b2, n2.x));
+    float ny = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.y), __fmul_rn(b1, n1.y)), __fmul_rn(b2, n2.y));
+    float nz = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.z), __fmul_rn(b1, n1.z)), __fmul_rn(b2, n2.z));
+    const float s = render_dot(nx, ny, nz, nx, ny, nz);
+    if (s > 0.f) {
+      const float r = sqrtf(s);           // the correctly rounded expansion, as in mesh_nrm_kernel
+      nx = __fdiv_rn(nx, r); ny = __fdiv_rn(ny, r); nz = __fdiv_rn(nz, r);
+    } else {
+      nx = ny = nz = 0.f;
+    }
+    if (nz < 0.f) { nx = -nx; ny = -ny; nz = -nz; }
+    float k = vw.ambient;
+#pragma unroll
+    for (int l = 0; l < RENDER_MAX_LIGHTS; ++l) {      // (unrolled: the view stays in scalar registers)
+      if (l >= vw.n_lights) break;
+      const float d = render_dot(nx, ny, nz, vw.dir[l][0], vw.dir[l][1], vw.dir[l][2]);
+      k = __fadd_rn(k, __fmul_rn(vw.intensity[l], d > 0.f ? d : 0.f));
+    }
+    cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
+    dep = __fdiv_rn(1.f, iw);
+  }
+  unsigned char* px = rgb + 3 * o;
+  px[0] = render_u8(cr, vw.background[0]); px[1] = render_u8(cg, vw.background[1]); px[2] = render_u8(cb, vw.background[2]);
+  if (depth) depth[o] = dep;
+  if (face) face[o] = id;
+}
+
+}  // namespace fdm

@@ -256,6 +256,66 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
     return [y[b:b + 1, :n] for b, n in enumerate(frames)] if many else y
 
 
+_RENDER_OUTPUTS = ("depth", "face_ids")      # keys of a render= dict that choose outputs, not the plan
+
+
+def _render_plan(render, faces, V, device):
+    """The render hand-off plan of `device`, the current stream, this topology and this view (render.RenderPlan.key).  render: a
+    render.RenderPlan (used as it is where it was made for this device and stream, made again from its arguments otherwise; `faces`
+    is then not read) or the dict of RenderPlan's arguments after faces and V (camera, lights, ambient, base, background,
+    chunk_frames)."""
+    from .render import RenderPlan, identity
+    dv, at = _on_stream(device)
+    if isinstance(render, RenderPlan):
+        if render.V != int(V):
+            raise FdmError(f"the render plan is for {render.V} vertices, the frames have {int(V)}")
+        key, make, given = render.key, (lambda: RenderPlan(device=dv, **render.arguments())), render
+    else:
+        if faces is None:
+            raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn")
+        kw = {k: v for k, v in render.items() if k not in _RENDER_OUTPUTS}
+        key, make, given = identity(faces, V, **kw), (lambda: RenderPlan(faces, V, device=dv, **kw)), None
+    plan = cached_plan(at, "render", key, make, given)
+    if plan.key != key:      # its view was changed (RenderPlan.set_view) after it was kept under this key
+        from .handoff import _PLANS
+        _PLANS[tuple(at) + ("render", key)] = plan = make()
+    return plan
+
+
+def _split_images(im):
+    """A batched ImageFrames -> one per clip, each cut to its own frames ([1, L_out, H, W, 3])."""
+    cut = lambda t, b, n: None if t is None else t[b:b + 1, :n]  # noqa: E731
+    return [type(im)(cut(im.images, b, n), cut(im.depth, b, n), cut(im.face_ids, b, n), [n]) for b, n in enumerate(im.frames)]
+
+
+@torch.no_grad()
+def to_images(offsets, faces, render, template=None, frames=None, fps=None, normals=None, depth=None, face_ids=None, device=None):
+    """Vertices (or vertex offsets with template=) -> render.ImageFrames: shaded uint8 frames [B, L_out, H, W, 3] of the mesh with the
+    triangle list `faces` [F, 3], drawn on the device in ONE call (render.RenderPlan; include/fdm_hip.h, fdm_render_forward; DESIGN.md
+    section 2 item 23 states every operation).  render: a render.RenderPlan, or the dict of its arguments after faces and V -- camera (a
+    render.Camera or "vocaset" | "biwi" | "mead"), lights, ambient, base, background, chunk_frames -- which may also carry depth=True
+    and face_ids=True for the depth [B, L_out, H, W] and face-id images.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with
+    frames = L per clip (None: all L); a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of ImageFrames, each cut to its own
+    frames and bit for bit what its own call returns; or a mesh.MeshFrames (planar fp32): its positions, normals and frames are drawn
+    as they are.  template: [1 or B, 3 V], or for a list one per clip.  fps = (fps_in, fps_out): the positions are resampled by
+    to_mesh's rule first.  normals [B, L_out, V, 3]: the caller's instead of the ones computed here (to_mesh's)."""
+    from .mesh import MeshFrames
+    opts = render if isinstance(render, dict) else {}
+    depth = bool(opts.get("depth", False)) if depth is None else depth
+    face_ids = bool(opts.get("face_ids", False)) if face_ids is None else face_ids
+    if isinstance(offsets, MeshFrames):
+        mf = offsets
+        if mf.positions.dtype != torch.float32 or mf.positions.shape[-1] != 3:
+            raise FdmError("to_images draws planar float32 MeshFrames (not interleaved, not half)")
+        B, Lo, V = (int(n) for n in mf.positions.shape[:3])
+        offsets, frames, normals = mf.positions.reshape(B, Lo, 3 * V), mf.frames, (mf.normals if normals is None else normals)
+    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
+        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
+    x, frames, many = _pack_offsets(offsets, frames, device, "to_images")
+    im = _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, depth, face_ids)
+    return _split_images(im) if many else im
+
+
 def _flame_rows(x, L, R, what):
     """A per-frame argument of flame= for R clips of L frames: [L', n] (for all) or [R, L', n], L' >= L -> [R, L, n]"""
     x = torch.as_tensor(x, dtype=torch.float32)
@@ -422,7 +482,7 @@ def _template_rows(template, width, device, S=1, B=1):
     return tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp
 
 
-def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None, wrap=None):
+def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None, wrap=None, render=None):
     """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
     template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair.
     flame=: the offsets pose the model's head (_flame_posed) and the posed vertices stand where offsets + template stood (the
@@ -430,7 +490,11 @@ def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, 
     refused with it.  wrap=: the vertices of the bound mesh (to_wrap) stand where offsets + template stood -- after flame= they follow
     the posed head; with faces= the mesh hand-off runs on them with no template, so `faces` is then the TARGET's triangle list and fps
     applies there; rig= keeps fitting the model's own offsets (a rig on the target topology is to_rig(to_wrap(..., offsets_out=True),
-    basis_t)), and rig= without faces= is refused with it as with flame=."""
+    basis_t)), and rig= without faces= is refused with it as with flame=.  render=: the render.ImageFrames of the mesh `faces` (to_images)
+    stand where its mesh.MeshFrames stood -- the template added, fps applied, the posed or wrapped vertices drawn; faces= is required
+    and mesh= is not read."""
+    if render is not None and faces is None:
+        raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
     if flame is not None:
         _flame_check(flame)
         if rig is not None and faces is None:
@@ -447,16 +511,19 @@ def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, 
         out, tp = to_wrap(out, wrap, tp, device=device), None
     if faces is None:
         return out if tp is None else out + tp.unsqueeze(1)
-    mf = to_mesh(out, faces, tp, fps=fps, **(mesh or {}))
+    mf = to_mesh(out, faces, tp, fps=fps, **(mesh or {})) if render is None else to_images(out, faces, render, tp, fps=fps, device=device)
     return mf if rf is None else (mf, rf)
 
 
-def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None, wrap=None):
+def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None, wrap=None, render=None):
     """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip: ONE mesh call and ONE rig call
     over the unequal lengths, each result bit for bit its own call's.  flame=: ONE ragged head call first (pose / expression /
     transl [L', n] for all clips or a list with one per clip); its posed clips stand where offsets + template stood.  wrap=: ONE ragged
-    wrap call after that; the wrapped clips stand where offsets + template stood (as _hand_off)."""
+    wrap call after that; the wrapped clips stand where offsets + template stood (as _hand_off).  render=: ONE ragged render call
+    in place of the mesh call (as _hand_off)."""
     offsets = clips
+    if render is not None and faces is None:
+        raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
     if wrap is not None and rig is not None and faces is None:
         raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
     if flame is not None:
@@ -479,7 +546,10 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
         clips, templates = to_wrap(clips, wrap, templates, device=device), None
     if faces is None and rig is None:
         return clips if templates is None else [c + _template_rows(t, c.shape[-1], device).unsqueeze(1) for c, t in zip(clips, templates)]
-    res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
+    if render is not None:
+        res = to_images(clips, faces, render, templates, fps=fps, device=device)
+    else:
+        res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
     if rig is not None:
         fits = to_rig(offsets, rig, fps=fps)
         res = fits if res is None else list(zip(res, fits))
@@ -489,8 +559,15 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    render (a render.RenderPlan or the dict of its arguments after faces and V: camera, lights, ambient, base, background,
+    chunk_frames; depth=True / face_ids=True for those images too): with faces= the call returns (render.ImageFrames, latent) in place
+    of the mesh.MeshFrames -- shaded uint8 frames [B, L_out, H, W, 3] of the mesh `faces`, drawn on the device (to_images) from the
+    positions and normals the mesh hand-off would have returned; out_fps= is honoured; after flame= or wrap= the posed or wrapped mesh
+    is drawn (faces= is then that mesh's triangle list).  faces= is required; mesh= is not read; with rig= the call returns
+    ((render.ImageFrames, rig.RigFrames), latent).  None: every path as before.
 
     wrap (a wrap.WrapPlan or the dict of its arguments: src_rest, faces, dst_rest, face_idx, weights): a mesh of ANOTHER topology,
     bound once to the model's rest surface, follows the animation (to_wrap): its vertices [B, L, 3 Vt] are returned where
@@ -567,15 +644,18 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     latent = _sample(diffusion, key, audio, shape, cond, x_T.repeat_interleave(S, dim=0) if S > 1 else x_T, seed, **trk)
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emotion_one_hot, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame, wrap), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame, wrap, render), latent
 
 
 @torch.no_grad()
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
                  style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None,
-                 wrap=None):
+                 wrap=None, render=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    render: as animate(); each group's clips are drawn in ONE ragged render call and the first returned list holds a
+    render.ImageFrames per clip.
 
     wrap: as animate(); each group's decoded clips go through ONE ragged wrap call and the first returned list holds [1, L_b, 3 Vt]
     per clip (or what faces= makes of them).  None: every path as before.
@@ -685,7 +765,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             # the group's clips, each at its own length, through one mesh and one rig hand-off call
             tps = None if templates is None else [_per(templates, b) for b in grp]
             fl = None if flame is None else {k: ([v[b] for b in grp] if (k in ("pose", "expression", "transl") and isinstance(v, (list, tuple))) else v) for k, v in flame.items()}
-            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl, wrap)):
+            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl, wrap, render)):
                 verts[b] = v
     finally:
         model._hub_key, model._hub = prev
@@ -695,8 +775,9 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    render: as animate(): the whole recording is drawn (a chunk of frames at a time inside the call).
     wrap: as animate(): the bound mesh follows the whole recording.
     flame: as animate(): the whole recording's offsets pose the model's head (pose [L', 3 J] with L' >= L_total).
     rig: as animate(): the whole recording's offsets go through the rig hand-off and the call returns (rig.RigFrames, latent), or
@@ -733,7 +814,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emo, et))
     fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame, wrap=wrap), latent
+    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame, wrap=wrap, render=render), latent
 
 
 class SlotServer:
@@ -771,12 +852,17 @@ class SlotServer:
     rig: as animate(): every finished clip's offsets go through the rig hand-off and results() yields a rig.RigFrames in place of
     the vertices (with faces= a (mesh.MeshFrames, rig.RigFrames) pair); the clips of one batched decode share one ragged call.
 
-    wrap: as animate(): every finished clip's vertices are those of the bound mesh ([1, L, 3 Vt], or what faces= makes of them)."""
+    wrap: as animate(): every finished clip's vertices are those of the bound mesh ([1, L, 3 Vt], or what faces= makes of them).
+
+    render: as animate(): results() yields a render.ImageFrames in place of the mesh.MeshFrames (faces= is required)."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
-                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None):
+                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None):
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
+        if render is not None and faces is None:
+            raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
+        self.render = render
         self.wrap = None if wrap is None else _wrap_plan(wrap, device)
         self.faces, self.mesh = faces, dict(mesh or {})
         self.rig = None if rig is None else _rig_plan(rig, device)     # a dict is digested and made into a plan once, not per finished clip
@@ -1005,7 +1091,7 @@ class SlotServer:
     def _vertices(self, out, template):
         """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames, with rig= its
         rig.RigFrames, with both the pair."""
-        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap)
+        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap, render=self.render)
 
     def _finish_one(self, slots, lat, r):
         """One finished request: its latent quantised and decoded at its own length, the result kept for results(), its slots idle."""
@@ -1053,7 +1139,8 @@ class SlotServer:
             # no hand-off call to share, or a mesh with a template on some requests only: clip by clip
             res = [self._vertices(c.contiguous(), t) for c, t in zip(clips, tps)]
         else:       # one mesh call and one rig call over the unequal lengths
-            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap)
+            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap,
+                                 render=self.render)
         for s, r, out, lat in zip(done, reqs, res, lats):
             self._done.append((r["handle"], out, lat))
             self._slot[s] = None
@@ -1136,6 +1223,29 @@ def add_wrap_arguments(ap):
     ap.add_argument("--wrap_falloff", type=str, default=None,
                     help="build-added: r0,r1 -- target vertices closer than r0 to the face follow it fully, those beyond r1 stay at rest, "
                          "smoothstep between (with --wrap_file; for a body mesh of which only the face should move)")
+
+
+def add_render_arguments(ap):
+    """--render / --render_size / --background_black of the demo command lines (the device render hand-off, to_images)."""
+    ap.add_argument("--render", action="store_true",
+                    help="build-added: also save <stem>_frames.npy, uint8 [1, L_out, N, N, 3]: the frames of <stem>.npy drawn on the device with the "
+                         "reference's camera and light directions (needs --faces_file), and print the ffmpeg line that makes an .mp4 of them")
+    ap.add_argument("--render_size", type=int, default=800, help="build-added: N, the side of the rendered frames in pixels (with --render)")
+    ap.add_argument("--background_black", action="store_true", help="a black background instead of white (with --render)")
+
+
+def save_frames(a, p, verts, faces, dst):
+    """--render: verts [1, L_out, 3 V] -> <dst>_frames.npy and the ffmpeg line (not run: video encoding is not part of this project)."""
+    from .render import Camera
+    name = next((n for n in ("biwi", "mead") if n in p.name.lower()), "vocaset")
+    N = int(a.render_size)
+    bg = (0.0, 0.0, 0.0) if a.background_black else (1.0, 1.0, 1.0)
+    im = to_images(verts, faces, dict(camera=Camera.preset(name).resized(N, N), background=bg))
+    np.save(dst + "_frames", im.images.detach().cpu().numpy())
+    print(f"saved {dst}_frames.npy {tuple(im.images.shape)}")
+    rate = a.out_fps or a.in_fps or p.fps or 30
+    print(f"python -c \"import numpy as np, sys; sys.stdout.buffer.write(np.load('{dst}_frames.npy').tobytes())\" | "
+          f"ffmpeg -f rawvideo -pix_fmt rgb24 -s {N}x{N} -r {rate:g} -i - -i {a.audio_file} -c:v libx264 -pix_fmt yuv420p -shortest {dst}.mp4")
 
 
 def wrap_arguments(a, faces, template, device):
@@ -1234,9 +1344,12 @@ def demo_main(preset, argv=None):
     add_track_arguments(ap, p)
     add_rig_arguments(ap)
     add_wrap_arguments(ap)
+    add_render_arguments(ap)
     if p.n_emo:        # MEAD: the template comes from FLAME parameters
         add_flame_arguments(ap)
     a = ap.parse_args(argv)
+    if a.render and not a.faces_file:
+        raise ValueError("--render draws the model's triangles: it needs --faces_file")
     rig = rig_arguments(a)
     diffusion, ae = build_models(p.name, a.feature_dim, a.device, a.stage1_model_path, a.stage2_model_path,
                                  cfg_level=None)
@@ -1290,6 +1403,8 @@ def demo_main(preset, argv=None):
             print(f"saved {dst}_wrap_normals.npy {tuple(nr.shape)}")
         np.save(dst + "_wrap", wv.detach().cpu().numpy())
         print(f"saved {dst}_wrap.npy {tuple(wv.shape)}")
+    if a.render:            # the saved frames drawn on the device: one image per frame of <stem>.npy
+        save_frames(a, p, out, np.load(a.faces_file), dst)
     np.save(dst, out.detach().cpu().numpy())
     print(f"saved {dst}.npy {tuple(out.shape)}")
     return dst + ".npy"

@@ -1,0 +1,175 @@
+"""Render hand-off: the animated mesh -> shaded image frames, a depth image and a face-id image, on the device (include/fdm_hip.h,
+fdm_render_*; kernels csrc/render_out.hpp; DESIGN.md section 2 item 23 is the definition).  The definition is this project's own -- a
+pinhole camera, exact integer coverage, a maximum of 1 / depth per pixel, a Lambert sum over directional lights: the reference's camera
+numbers and light directions are the defaults here, its metallic-roughness material is not reproduced."""
+import ctypes as C
+import hashlib
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from ._lib import FdmError, check, lib
+from .handoff import HandoffPlan, fps_pair, frames_list, frames_out_max, offsets_batch
+from .mesh import faces_array
+
+# images [B, L_out_max, H, W, 3] uint8, depth [B, L_out_max, H, W] float32 or None (0 where no surface), face_ids [B, L_out_max, H, W] int32
+# or None (-1 where no surface), frames = L_out per clip (rows at or past it are zeros)
+ImageFrames = namedtuple("ImageFrames", "images depth face_ids frames")
+
+MAX_LIGHTS = 8
+REFERENCE_F = 4754.97941935      # render/render.py: the focal length at 800 x 800 is this over 2 (vocaset, MEAD) or over 8 (BIWI)
+LIGHT_INTENSITY = 0.5            # this project's choice: a normal facing the camera under the five default lights gives
+#                                  k = 0.2 + 0.5 (1 + 4 cos(pi / 6)) = 2.43 and a channel of 0.3 k = 0.73, below saturation
+
+
+class Camera:
+    """A pinhole camera: fx, fy, cx, cy in pixels of a width x height image, near / far in scene units, world-to-camera rotation R [3, 3]
+    and translation t [3] (pc = R p + t; the camera looks down its -z axis, x to the right, y up).  The default stands 1 unit in front
+    of the origin, as the reference's does."""
+
+    def __init__(self, fx, fy, cx, cy, width, height, near=0.01, far=3.0, R=None, t=(0.0, 0.0, -1.0)):
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.width, self.height, self.near, self.far = int(width), int(height), float(near), float(far)
+        self.R = np.eye(3, dtype=np.float32) if R is None else np.ascontiguousarray(np.asarray(R, dtype=np.float32).reshape(3, 3))
+        self.t = np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(3))
+
+    @classmethod
+    def preset(cls, name):
+        """The reference's cameras (render/render.py, render_mead.py): 800 x 800, principal point (400, 400), near 0.01, far 3."""
+        div = {"vocaset": 2.0, "biwi": 8.0, "mead": 2.0}.get(str(name).lower())
+        if div is None:
+            raise ValueError(f"camera preset {name!r}: vocaset, biwi or mead")
+        return cls(REFERENCE_F / div, REFERENCE_F / div, 400.0, 400.0, 800, 800)
+
+    def resized(self, width, height):
+        """The same view on a width x height image: the intrinsics scale with the image."""
+        sx, sy = width / self.width, height / self.height
+        return Camera(self.fx * sx, self.fy * sy, self.cx * sx, self.cy * sy, width, height, self.near, self.far, self.R, self.t)
+
+    def with_pose(self, R=None, t=None):
+        return Camera(self.fx, self.fy, self.cx, self.cy, self.width, self.height, self.near, self.far, self.R if R is None else R,
+                      self.t if t is None else t)
+
+    def numbers(self):
+        """camera [6] float32 = {fx, fy, cx, cy, near, far} as fdm_render_create reads it"""
+        return np.array([self.fx, self.fy, self.cx, self.cy, self.near, self.far], dtype=np.float32)
+
+
+def reference_lights():
+    """dict(lights [5, 4], ambient, base): the reference's five directions -- towards the camera, and that direction turned by +-pi/6
+    about x and about y -- as unit vectors towards the light in camera space, each with LIGHT_INTENSITY; ambient 0.2 and base colour
+    0.3 are the reference's."""
+    a = math.pi / 6.0
+    s, c = math.sin(a), math.cos(a)
+    d = [(0.0, 0.0, 1.0), (0.0, -s, c), (0.0, s, c), (-s, 0.0, c), (s, 0.0, c)]
+    return dict(lights=np.array([x + (LIGHT_INTENSITY,) for x in d], dtype=np.float32), ambient=0.2, base=(0.3, 0.3, 0.3))
+
+
+def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0):
+    ref = reference_lights()
+    if isinstance(camera, str):
+        camera = Camera.preset(camera)
+    lt = ref["lights"] if lights is None else np.asarray(lights, dtype=np.float32).reshape(-1, 4)
+    three = lambda x: np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), (3,)))  # noqa: E731
+    return dict(camera=camera, lights=np.ascontiguousarray(lt), ambient=float(ref["ambient"] if ambient is None else ambient),
+                base=three(ref["base"] if base is None else base), background=three(background), chunk_frames=int(chunk_frames))
+
+
+def _view_key(a):
+    d = hashlib.sha1()
+    cam = a["camera"]
+    for x in (cam.numbers(), cam.R, cam.t, a["lights"], a["base"], a["background"]):
+        d.update(x.tobytes())
+    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], d.hexdigest())
+
+
+def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0):
+    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view)."""
+    return (int(V), hashlib.sha1(faces_array(faces).tobytes()).hexdigest()) + _view_key(_arguments(camera, lights, ambient, base, background, chunk_frames))
+
+
+class RenderPlan(HandoffPlan):
+    """Thin binding of fdm_render_create / fdm_render_forward for one topology and one view: faces [F, 3] over V vertices, camera (a
+    Camera or a preset's name), lights [n <= 8, 4] = unit direction towards the light in camera space and intensity (None: the
+    reference's five), ambient, base colour [3], background [3] in [0, 1] (white, as the reference's default), chunk_frames (0: scratch
+    under 256 MB).  The faces are checked and uploaded here; forward() only passes pointers.  A plan holds one scratch: it serves one
+    stream at a time (pipeline.to_images keeps them per (device, stream, topology, view)).  Without a visible device the plan still
+    validates and forward() raises."""
+
+    _destroy = "fdm_render_destroy"
+
+    def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, device="cuda:0"):
+        super().__init__(device)
+        self.faces, self.V = faces_array(faces), int(V)
+        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames)
+        a = self.view
+        cam = a["camera"]
+        self.W, self.H = cam.width, cam.height
+        self._create("fdm_render_create", self.faces.ctypes.data, len(self.faces), self.V, self.W, self.H, cam.numbers().ctypes.data, cam.R.ctypes.data,
+                     cam.t.ctypes.data, a["lights"].ctypes.data if len(a["lights"]) else None, len(a["lights"]), a["ambient"], a["base"].ctypes.data,
+                     a["background"].ctypes.data)
+        if a["chunk_frames"]:
+            self.set_chunk_frames(a["chunk_frames"])
+        self.key = identity(self.faces, self.V, **a)
+
+    def arguments(self):
+        """The arguments that make this plan again (on another device or stream)."""
+        return dict(faces=self.faces, V=self.V, **self.view)
+
+    def set_view(self, camera=None, lights=None, ambient=None):
+        """Another camera pose / intrinsics (same image size), other lights or ambient term, without a new plan (fdm_render_set_view)."""
+        a = self.view
+        cam = a["camera"] if camera is None else camera
+        if (cam.width, cam.height) != (self.W, self.H):
+            raise FdmError(f"set_view keeps the image size {self.W} x {self.H}, got {cam.width} x {cam.height}")
+        lt = a["lights"] if lights is None else np.ascontiguousarray(np.asarray(lights, dtype=np.float32).reshape(-1, 4))
+        amb = a["ambient"] if ambient is None else float(ambient)
+        check(lib().fdm_render_set_view(self.h, cam.numbers().ctypes.data, cam.R.ctypes.data, cam.t.ctypes.data, lt.ctypes.data if len(lt) else None,
+                                        len(lt), amb))
+        self.view = dict(a, camera=cam, lights=lt, ambient=amb)
+        self.key = identity(self.faces, self.V, **self.view)
+
+    def set_chunk_frames(self, n):
+        """Frames per chunk of scratch (0: the default).  The pixels do not depend on it."""
+        check(lib().fdm_render_set(self.h, b"chunk_frames", int(n)))
+        self.view = dict(self.view, chunk_frames=int(n))
+
+    def forward(self, positions, frames=None, template=None, fps=None, normals=None, depth=False, face_ids=False, out=None):
+        """positions [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device -- vertices, or offsets with template [1 or B, 3 V] --, frames:
+        L per clip (None: L_max), fps = (fps_in, fps_out) or None, normals [B, L_out_max, V, 3] fp32 (what to_mesh returns for the same
+        frames; None: computed here by the same kernel) -> ImageFrames.  out: (images, depth, face_ids) tensors to write instead of
+        new ones (None where the call writes none); their second dimension is L_out_max."""
+        dv = self.device
+        x = offsets_batch(positions, self.V, dv)
+        B, L_max = int(x.shape[0]), int(x.shape[1])
+        fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
+        tp, rows = None, 0
+        if template is not None:
+            tp = torch.as_tensor(template, dtype=torch.float32).to(dv).reshape(-1, 3 * self.V).contiguous()
+            rows = int(tp.shape[0])
+        if out is None:
+            Lo = frames_out_max(fr, fi, fo)
+            img = torch.empty(B, Lo, self.H, self.W, 3, dtype=torch.uint8, device=dv)
+            dep = torch.empty(B, Lo, self.H, self.W, dtype=torch.float32, device=dv) if depth else None
+            ids = torch.empty(B, Lo, self.H, self.W, dtype=torch.int32, device=dv) if face_ids else None
+        else:
+            img, dep, ids = out
+            Lo = int(img.shape[1]) if img.dim() == 5 else 0
+            for t, dt, shp in ((img, torch.uint8, (B, Lo, self.H, self.W, 3)), (dep, torch.float32, (B, Lo, self.H, self.W)), (ids, torch.int32, (B, Lo, self.H, self.W))):
+                if t is not None and (t.dtype != dt or t.device != dv or tuple(t.shape) != shp or not t.is_contiguous()):
+                    raise FdmError(f"out must be contiguous {dt} {list(shp)} tensors on {dv}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        nr = None
+        if normals is not None:
+            nr = normals.detach()
+            if nr.dtype != torch.float32 or nr.device != dv or nr.numel() != B * Lo * 3 * self.V or nr.shape[0] != B:
+                raise FdmError(f"normals must be float32 [{B}, {Lo}, {self.V}, 3] on {dv}, got {nr.dtype} {tuple(nr.shape)} on {nr.device}")
+            nr = nr.contiguous()
+        fa, got = (C.c_int * B)(*fr), (C.c_int * B)()
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(dv):
+            check(lib().fdm_render_forward(self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr), img.data_ptr(), ptr(dep), ptr(ids), Lo, got,
+                                           torch.cuda.current_stream(dv).cuda_stream))
+        self._keep = (x, tp, nr)      # read asynchronously on this stream
+        return ImageFrames(img, dep, ids, list(got))

@@ -1124,6 +1124,66 @@ int fdm_wrap_forward(fdm_wrap* w, const float* offsets, const int* frames, int B
                      float* out, void* stream);
 int fdm_wrap_destroy(fdm_wrap* w);
 
+/* ------------------------------------------------------------------------------------------
+ * Render hand-off: shaded image frames of the animated mesh.  The definition is this project's own: a
+ * pinhole camera, exact integer coverage, a per-pixel maximum of 1 / depth, and a Lambert sum over directional lights.  It is not
+ * pyrender's metallic-roughness material; there is no reference renderer to compare images with.  Everything on the device is fp32,
+ * every operation rounded on its own, no contraction; dot and cross as in the wrap hand-off above; square roots are correctly rounded.
+ * Inputs per call: positions [B, L_max, 3 V] fp32 device (what the mesh, wrap and head hand-offs write, or offsets with a template of 1 or
+ *   B rows: p = offset + template, one fp32 add), frames [B] HOST ints (NULL: L_max each), fps_in / fps_out as in fdm_mesh_forward: with
+ *   both > 0 and different the positions are resampled by that call's rule (L_out and the taps of fdm_mesh_frames, l0 p[i0] + l1 p[i1]).
+ *   Vertex normals are those of fdm_mesh_forward on the same output frame (area-weighted, ascending face index) over the object's faces,
+ *   or `normals` [B, L_out_max, V, 3] fp32 device when the caller brings them.
+ * The object (HOST arrays at create, not read after the call): faces [F, 3] with fdm_mesh_create's index checks; W, H in 1 .. 4096;
+ *   camera = {fx, fy, cx, cy, near, far} with fx, fy > 0 and 0 < near < far; world-to-camera R [3, 3] row-major and t [3]; up to 8
+ *   directional lights [n, 4] = {unit direction TOWARDS the light in camera space (| |d|^2 - 1 | <= 1e-4), intensity >= 0}; ambient >= 0;
+ *   base [3] >= 0; background [3] in [0, 1].  fdm_render_set_view replaces camera, R, t, lights and ambient without a new create.
+ * 1 Vertex (per frame and vertex).  pc = R p + t, each component ((r0 p.x + r1 p.y) + r2 p.z) + t; d = -pc.z (the camera looks down -z);
+ *   w = 1 / d; sx = fx (pc.x w) + cx; sy = cy - fy (pc.y w); X = (int)rintf(256 sx), Y = (int)rintf(256 sy): 8 sub-pixel bits.  The vertex
+ *   is BAD when any of p, d, sx, sy is not finite, when d <= near or d >= far, or when |rintf(256 sx)| or |rintf(256 sy)| > 2^20.
+ *   nc = R n in the same order (no t).
+ * 2 Triangle.  One with a bad vertex is dropped: there is NO clipping (a limit: a head in front of the camera never straddles the near
+ *   plane; a triangle that does vanishes whole).  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) in 64-bit ints; A == 0 is dropped; A < 0:
+ *   vertices 1 and 2 change places (both sides are drawn) and A = -A.
+ * 3 Coverage (exact).  Pixel (x, y) has the centre (px, py) = (256 x + 128, 256 y + 128).  For the oriented triangle the edge function
+ *   of a -> b is E = (Xb - Xa)(py - Ya) - (Yb - Ya)(px - Xa) in 64-bit ints; E0 belongs to the edge 1 -> 2, E1 to 2 -> 0, E2 to 0 -> 1
+ *   (E0 + E1 + E2 = A).  The pixel is covered when for every edge E > 0, or E == 0 and the edge is a top or a left one: with
+ *   (dx, dy) = (Xb - Xa, Yb - Ya), x to the right and y down, dy < 0 (left) or dy == 0 and dx > 0 (top).  Exactly one of an edge and its
+ *   reverse qualifies, so two triangles that share an edge cover every pixel of their union once.  Only pixels of the triangle's
+ *   box clamped to the viewport are visited.
+ * 4 Depth.  l_i = (float)E_i / (float)A (64-bit int to float, round to nearest even, one division); iw = (l0 w0 + l1 w1) + l2 w2 (1 / d
+ *   is linear on the screen).  The pixel's fragment is the one with the largest iw; among equal iw the lowest face index: the maximum
+ *   of the 64-bit key (bits(iw) << 32) | (0xFFFFFFFF - face).  An iw that is not finite or not > 0 never enters.  A maximum does not
+ *   depend on the order of the triangles: a clip's pixels do not depend on the batch, L_max, L_out_max or the chunk.
+ * 5 Resolve (per pixel).  No fragment: the background, depth 0, face -1.  Else, with E_i, l_i, iw of the winning face recomputed:
+ *   b_i = (l_i w_i) / iw; n = (b0 nc0 + b1 nc1) + b2 nc2 per component; s = dot(n, n); nh = n / sqrtf(s) when s > 0, else 0; nh = -nh
+ *   when nh.z < 0 (the far side of a surface is lit like the near one); k = ambient + sum over lights l ascending of
+ *   I_l max(0, dot(nh, dir_l)) (max(0, x) = x > 0 ? x : 0); per channel c = base_c k, a NaN c takes the background's channel, c = min(1, c),
+ *   u8 = (int)(255 c + 0.5f); the background's channels go through the same two last steps.
+ *   rgb [B, L_out_max, H, W, 3] uint8; depth [B, L_out_max, H, W] fp32 = 1 / iw (or NULL); face [B, L_out_max, H, W] int32 (or NULL).
+ *   Rows at or past a clip's L_out are zeros in every output; input rows at or past frames[b] are never read.
+ * A call works through its live output frames a chunk at a time on `stream`: per-vertex records and the visibility buffer exist for one
+ * chunk (one scratch per object, grown when a call needs more; the call that grows waits for the device).  fdm_render_set(r,
+ * "chunk_frames", n): n frames per chunk, 0 = the default, the largest chunk whose scratch stays under 256 MB (at least one frame).
+ * Not built: textures, the metallic-roughness material, anti-aliasing, clipping, video encoding.
+ * fdm_render_create validates without a device and fdm_render_forward then ends in FDM_ERR_STATE.  Every check is made before the first
+ * launch: FDM_ERR_ARG (a null r / positions / rgb, tmpl_rows not 0, 1 or B, a null template with tmpl_rows > 0, frame rates not finite
+ * or negative; at create and set_view: a null array, F or V < 1, a face index outside [0, V), W or H outside 1 .. 4096, more than 8
+ * lights, a light direction that is not a unit vector, near >= far, anything not finite; in fdm_render_set an unknown key or n outside
+ * 0 .. 4096), FDM_ERR_SHAPE (B, L_max or L_out_max < 1, frames[b] outside [0, L_max], a clip whose L_out exceeds L_out_max).
+ * frames_out [B] HOST (or NULL) receives L_out per clip.  An object serves one stream at a time.  fdm_version() keeps its value: callers
+ * detect the feature by the symbol.  Call times are unmeasured: profiles/render_out/README.md. */
+typedef struct fdm_render fdm_render;
+int fdm_render_create(const int* faces, int F, int V, int W, int H, const float* camera /*[6]*/, const float* R /*[9]*/, const float* t /*[3]*/,
+                      const float* lights /*[n_lights,4] or NULL*/, int n_lights, float ambient, const float* base /*[3]*/,
+                      const float* background /*[3]*/, fdm_render** out);
+int fdm_render_set_view(fdm_render* r, const float* camera, const float* R, const float* t, const float* lights, int n_lights, float ambient);
+int fdm_render_set(fdm_render* r, const char* key, long long value);
+int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
+                       double fps_out, const float* normals /*or NULL*/, unsigned char* rgb, float* depth /*or NULL*/, int* face /*or NULL*/,
+                       int L_out_max, int* frames_out, void* stream);
+int fdm_render_destroy(fdm_render* r);
+
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
  * (diffusion_BIWI_encoder_decoder.py:565-603: cosine schedule in fp64, fp32 cast); DDIM pairs and per-pair coefficients
  * (:684-708, eta = 0; returns the number of live pairs, the dead (t, -1) pair excluded); get_slopes (models/fdm_vocaset.py:96-106);
