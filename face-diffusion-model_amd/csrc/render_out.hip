@@ -16,6 +16,7 @@
 struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
   int F = 0, V = 0, W = 0, H = 0;
   long long chunk_frames = 0;             // 0: the default (scratch under RENDER_SCRATCH_BYTES)
+  int samples = 1;                        // coverage samples per pixel: 1, 4 or 16
   fdm::RenderView view;
   fdm_mesh* mesh = nullptr;               // the normals of a chunk (fdm_mesh_forward on the chunk's positions)
   int* faces = nullptr;                   // device [F][3]
@@ -23,7 +24,7 @@ struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
   float *P = nullptr, *N = nullptr;       // device scratch of one chunk: [n][3V] each
   int4* xyw = nullptr;                    // [n][V]
   float4* nc = nullptr;                   // [n][V]
-  unsigned long long* vis = nullptr;      // [n][H][W], zero between calls (render_resolve_kernel leaves it so)
+  unsigned long long* vis = nullptr;      // [n][H][W][samples], zero between calls (the resolve kernels leave it so)
   long long rowtab_cap = 0, P_cap = 0, N_cap = 0, xyw_cap = 0, nc_cap = 0, vis_cap = 0;
   std::vector<int2> rows;                 // host: the live rows of the call in flight (the asynchronous upload reads it)
   bool vis_dirty = false;                 // a call ended between raster and resolve: clear before the next use
@@ -34,6 +35,7 @@ using namespace fdm;
 
 constexpr long long RENDER_SCRATCH_BYTES = 256LL << 20;
 constexpr long long RENDER_CHUNK_MAX = 4096;      // rows of one launch (grid y <= 65535)
+constexpr long long RENDER_FRAME_KEYS_MAX = 1LL << 26;      // W H samples of one frame: 512 MB of keys (4096^2 at 4 samples, 2048^2 at 16)
 
 bool finite_all(const float* x, int n) {
   for (int i = 0; i < n; ++i)
@@ -73,7 +75,11 @@ int check_view(const char* who, const float* camera, const float* R, const float
 }
 
 long long frame_bytes(const fdm_render& R) {
-  return (long long)R.V * (12 + 12 + 16 + 16) + (long long)R.W * R.H * 8;
+  return (long long)R.V * (12 + 12 + 16 + 16) + (long long)R.W * R.H * R.samples * 8;
+}
+
+template <int S> void sample_pattern(int* xy) {
+  for (int s = 0; s < S; ++s) render_sample_offset<S>(s, xy[2 * s], xy[2 * s + 1]);
 }
 
 }  // namespace
@@ -125,9 +131,26 @@ int fdm_render_set_view(fdm_render* r, const float* camera, const float* R, cons
 
 int fdm_render_set(fdm_render* r, const char* key, long long value) {
   if (!r || !key) return fail(FDM_ERR_ARG, "render_set: null argument");
-  if (std::strcmp(key, "chunk_frames") != 0) return fail(FDM_ERR_ARG, "render_set: unknown key %s (chunk_frames)", key);
+  if (std::strcmp(key, "samples") == 0) {
+    if (value != 1 && value != 4 && value != 16) return fail(FDM_ERR_ARG, "render_set: samples = %lld (1, 4 or 16)", value);
+    if ((long long)r->W * r->H * value > RENDER_FRAME_KEYS_MAX)
+      return fail(FDM_ERR_ARG, "render_set: samples = %lld on %d x %d pixels is %lld keys per frame (at most 2^26; samples is 1, 4 or 16)", value, r->W,
+                  r->H, (long long)r->W * r->H * value);
+    r->samples = (int)value;
+    return FDM_OK;
+  }
+  if (std::strcmp(key, "chunk_frames") != 0) return fail(FDM_ERR_ARG, "render_set: unknown key %s (chunk_frames, samples)", key);
   if (value < 0 || value > RENDER_CHUNK_MAX) return fail(FDM_ERR_ARG, "render_set: chunk_frames = %lld (0 = the default, at most %lld)", value, RENDER_CHUNK_MAX);
   r->chunk_frames = value;
+  return FDM_OK;
+}
+
+int fdm_render_sample_pattern_host(int samples, int* xy) {
+  if (!xy) return fail(FDM_ERR_ARG, "render_sample_pattern_host: null xy");
+  if (samples == 1) sample_pattern<1>(xy);
+  else if (samples == 4) sample_pattern<4>(xy);
+  else if (samples == 16) sample_pattern<16>(xy);
+  else return fail(FDM_ERR_ARG, "render_sample_pattern_host: samples = %d (1, 4 or 16)", samples);
   return FDM_OK;
 }
 
@@ -161,7 +184,7 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
   FCK(grow(r->mem, &r->xyw, &r->xyw_cap, chunk * r->V));
   FCK(grow(r->mem, &r->nc, &r->nc_cap, chunk * r->V));
   const long long vis_before = r->vis_cap;
-  FCK(grow(r->mem, &r->vis, &r->vis_cap, chunk * WH));
+  FCK(grow(r->mem, &r->vis, &r->vis_cap, chunk * WH * r->samples));
   if (r->vis_cap != vis_before || r->vis_dirty) {
     HIPCK(hipMemsetAsync(r->vis, 0, (size_t)r->vis_cap * sizeof(unsigned long long), s));
     r->vis_dirty = false;
@@ -192,10 +215,22 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
     hipLaunchKernelGGL(render_vertex_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const float*)r->P, normals ? normals : (const float*)r->N,
                        normals ? tab : (const int2*)nullptr, L_out_max, r->V, r->view, r->xyw, r->nc);
     r->vis_dirty = true;
-    hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
-                       r->W, r->H, r->vis);
-    hipLaunchKernelGGL(render_resolve_kernel, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
+    if (r->samples == 1) {
+      hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
+                         r->W, r->H, r->vis);
+      hipLaunchKernelGGL(render_resolve_kernel, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
+    } else if (r->samples == 4) {
+      hipLaunchKernelGGL(render_raster_aa_kernel<4>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
+                         r->V, r->W, r->H, r->vis);
+      hipLaunchKernelGGL(render_resolve_aa_kernel<4>, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
+    } else {
+      hipLaunchKernelGGL(render_raster_aa_kernel<16>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
+                         r->V, r->W, r->H, r->vis);
+      hipLaunchKernelGGL(render_resolve_aa_kernel<16>, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
+    }
     HIPCK(hipGetLastError());
     r->vis_dirty = false;
   }

@@ -14,7 +14,16 @@
 //                          atomic): a maximum, so the buffer does not depend on the order the triangles arrive in.
 //   render_resolve_kernel  one lane per (chunk row, pixel): reads the key and writes 0 back (the buffer is clear for the next chunk),
 //                          recomputes the winning face's fragment, interpolates the normal, shades, writes rgb / depth / face.
-// No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt; times are unmeasured.
+// With S = 4 or 16 samples per pixel (fdm_render_set "samples") the last two are replaced by
+//   render_raster_aa_kernel<S>   the same lane per (chunk row, face) over a visibility buffer [n][H][W][S], the samples of a pixel
+//                          adjacent.  The work items of a box are its (pixel, sample) pairs in that order, so the 64 lanes of the
+//                          wavefront issue their atomicMax on 512 contiguous bytes of a pixel row.  Every box is handed to the
+//                          whole wavefront: there is no per-lane walk here (profiles/render_out/README.md says why).
+//   render_resolve_aa_kernel<S>  one lane per (chunk row, pixel): reads and clears the pixel's 8 S contiguous bytes 16 at a time, shades
+//                          every sample that has a fragment (a triangle's setup and normals are kept while consecutive samples name
+//                          the same face), sums the channels in sample order, scales by 1 / S; depth and face from the largest key.
+// S = 1 launches render_raster_kernel and render_resolve_kernel as they stand.
+// No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +50,15 @@ __device__ __forceinline__ float render_dot(float ax, float ay, float az, float 
   return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
 }
 __device__ __forceinline__ bool render_finite(float x) { return fabsf(x) < __builtin_inff(); }      // false for NaN
+
+// Sample s of a pixel, in units of 1 / 256 pixel from the pixel's corner.  S = 1: the centre.  S = 4: the rotated grid
+// (96, 32), (224, 96), (32, 160), (160, 224).  S = 16: the 4 x 4 grid, s = 4 j + i at (32 + 64 i, 32 + 64 j).  Every offset of
+// S > 1 lies in 32 .. 224 (the raster box relies on it).
+template <int S> __host__ __device__ __forceinline__ void render_sample_offset(int s, int& ox, int& oy) {
+  if (S == 1) { ox = 128; oy = 128; }
+  else if (S == 4) { ox = 32 + 64 * ((0x2031 >> (4 * s)) & 3); oy = 32 + 64 * s; }
+  else { ox = 32 + 64 * (s & 3); oy = 32 + 64 * (s >> 2); }
+}
 
 // rowtab: [n] {clip, output frame} of the chunk's rows.  lens: [B][2] = {L, L_out}.  P: [n][V3].  tmpl_stride: 0 or V3.
 __global__ __launch_bounds__(256) void render_pos_kernel(const float* off, const float* tmpl, int tmpl_stride, const int* lens, const int2* rowtab,
@@ -123,9 +141,8 @@ __device__ __forceinline__ bool render_edge(int Xa, int Ya, int Xb, int Yb, int 
   E = (long long)dx * (py - Ya) - (long long)dy * (px - Xa);
   return E > 0 || (E == 0 && (dy < 0 || (dy == 0 && dx > 0)));
 }
-// covered: E_i, l_i = (float)E_i / (float)A, iw = (l0 w0 + l1 w1) + l2 w2
-__device__ __forceinline__ bool render_fragment(const RenderTri& T, int x, int y, float& l0, float& l1, float& l2, float& iw) {
-  const int px = 256 * x + 128, py = 256 * y + 128;
+// covered at the sample position (px, py): E_i, l_i = (float)E_i / (float)A, iw = (l0 w0 + l1 w1) + l2 w2
+__device__ __forceinline__ bool render_fragment_at(const RenderTri& T, int px, int py, float& l0, float& l1, float& l2, float& iw) {
   long long E0, E1, E2;
   const bool in0 = render_edge(T.X1, T.Y1, T.X2, T.Y2, px, py, E0);
   const bool in1 = render_edge(T.X2, T.Y2, T.X0, T.Y0, px, py, E1);
@@ -135,12 +152,19 @@ __device__ __forceinline__ bool render_fragment(const RenderTri& T, int x, int y
   iw = __fadd_rn(__fadd_rn(__fmul_rn(l0, T.w0), __fmul_rn(l1, T.w1)), __fmul_rn(l2, T.w2));
   return in0 && in1 && in2;
 }
-__device__ __forceinline__ void render_hit(const RenderTri& T, int x, int y, int face, int W, unsigned long long* vis) {
+__device__ __forceinline__ bool render_fragment(const RenderTri& T, int x, int y, float& l0, float& l1, float& l2, float& iw) {
+  return render_fragment_at(T, 256 * x + 128, 256 * y + 128, l0, l1, l2, iw);      // the pixel centre
+}
+// the fragment of `face` at (px, py), if there is one, into the key at `slot`
+__device__ __forceinline__ void render_hit_at(const RenderTri& T, int px, int py, int face, unsigned long long* slot) {
   float l0, l1, l2, iw;
-  if (!render_fragment(T, x, y, l0, l1, l2, iw)) return;
+  if (!render_fragment_at(T, px, py, l0, l1, l2, iw)) return;
   if (!(iw > 0.f) || !render_finite(iw)) return;
   const unsigned long long key = ((unsigned long long)__float_as_uint(iw) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)face);
-  atomicMax(vis + (size_t)y * W + x, key);
+  atomicMax(slot, key);
+}
+__device__ __forceinline__ void render_hit(const RenderTri& T, int x, int y, int face, int W, unsigned long long* vis) {
+  render_hit_at(T, 256 * x + 128, 256 * y + 128, face, vis + (size_t)y * W + x);
 }
 
 // xyw: [n][V]; faces [F][3]; vis: [n][H][W] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
@@ -185,6 +209,31 @@ __global__ __launch_bounds__(RENDER_TB) void render_raster_kernel(const int4* xy
   }
 }
 
+// step 5 for one fragment of the oriented triangle T with the camera-space normals of its vertices 0, 1, 2: the Lambert factor k
+__device__ __forceinline__ float render_shade(const RenderTri& T, const float4& n0, const float4& n1, const float4& n2, float l0, float l1, float l2,
+                                              float iw, const RenderView& vw) {
+  const float b0 = __fdiv_rn(__fmul_rn(l0, T.w0), iw), b1 = __fdiv_rn(__fmul_rn(l1, T.w1), iw), b2 = __fdiv_rn(__fmul_rn(l2, T.w2), iw);
+  float nx = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.x), __fmul_rn(b1, n1.x)), __fmul_rn(b2, n2.x));
+  float ny = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.y), __fmul_rn(b1, n1.y)), __fmul_rn(b2, n2.y));
+  float nz = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.z), __fmul_rn(b1, n1.z)), __fmul_rn(b2, n2.z));
+  const float s = render_dot(nx, ny, nz, nx, ny, nz);
+  if (s > 0.f) {
+    const float r = sqrtf(s);           // the correctly rounded expansion, as in mesh_nrm_kernel
+    nx = __fdiv_rn(nx, r); ny = __fdiv_rn(ny, r); nz = __fdiv_rn(nz, r);
+  } else {
+    nx = ny = nz = 0.f;
+  }
+  if (nz < 0.f) { nx = -nx; ny = -ny; nz = -nz; }
+  float k = vw.ambient;
+#pragma unroll
+  for (int l = 0; l < RENDER_MAX_LIGHTS; ++l) {      // (unrolled: the view stays in scalar registers)
+    if (l >= vw.n_lights) break;
+    const float d = render_dot(nx, ny, nz, vw.dir[l][0], vw.dir[l][1], vw.dir[l][2]);
+    k = __fadd_rn(k, __fmul_rn(vw.intensity[l], d > 0.f ? d : 0.f));
+  }
+  return k;
+}
+
 __device__ __forceinline__ unsigned char render_u8(float c, float bg) {      // c: base_c k, or the background's channel itself
   if (c != c) c = bg;
   c = c < 1.f ? c : 1.f;
@@ -214,25 +263,7 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
     const int y = i / W, x = i - y * W;
     float l0, l1, l2, iw;
     (void)render_fragment(T, x, y, l0, l1, l2, iw);
-    const float b0 = __fdiv_rn(__fmul_rn(l0, T.w0), iw), b1 = __fdiv_rn(__fmul_rn(l1, T.w1), iw), b2 = __fdiv_rn(__fmul_rn(l2, T.w2), iw);
-    float nx = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.x), __fmul_rn(b1, n1.x)), __fmul_rn(b2, n2.x));
-    float ny = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.y), __fmul_rn(b1, n1.y)), __fmul_rn(b2, n2.y));
-    float nz = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.z), __fmul_rn(b1, n1.z)), __fmul_rn(b2, n2.z));
-    const float s = render_dot(nx, ny, nz, nx, ny, nz);
-    if (s > 0.f) {
-      const float r = sqrtf(s);           // the correctly rounded expansion, as in mesh_nrm_kernel
-      nx = __fdiv_rn(nx, r); ny = __fdiv_rn(ny, r); nz = __fdiv_rn(nz, r);
-    } else {
-      nx = ny = nz = 0.f;
-    }
-    if (nz < 0.f) { nx = -nx; ny = -ny; nz = -nz; }
-    float k = vw.ambient;
-#pragma unroll
-    for (int l = 0; l < RENDER_MAX_LIGHTS; ++l) {      // (unrolled: the view stays in scalar registers)
-      if (l >= vw.n_lights) break;
-      const float d = render_dot(nx, ny, nz, vw.dir[l][0], vw.dir[l][1], vw.dir[l][2]);
-      k = __fadd_rn(k, __fmul_rn(vw.intensity[l], d > 0.f ? d : 0.f));
-    }
+    const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
     cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
     dep = __fdiv_rn(1.f, iw);
   }
@@ -240,6 +271,112 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
   px[0] = render_u8(cr, vw.background[0]); px[1] = render_u8(cg, vw.background[1]); px[2] = render_u8(cb, vw.background[2]);
   if (depth) depth[o] = dep;
   if (face) face[o] = id;
+}
+
+// ---- S = 4 or 16 samples per pixel
+// xyw: [n][V]; faces [F][3]; vis: [n][H][W][S] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
+template <int S>
+__global__ __launch_bounds__(RENDER_TB) void render_raster_aa_kernel(const int4* xyw, const int* faces, int F, int V, int W, int H,
+                                                                     unsigned long long* vis) {
+  static_assert(S == 4 || S == 16, "the sample patterns of render_sample_offset");
+  const int row = blockIdx.y, f = blockIdx.x * RENDER_TB + threadIdx.x;
+  const int4* rec = xyw + (size_t)row * V;
+  unsigned long long* img = vis + (size_t)row * W * H * S;
+  RenderTri T = {};
+  int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+  if (f < F) {
+    const int* fv = faces + 3 * (size_t)f;
+    T = render_setup(rec[fv[0]], rec[fv[1]], rec[fv[2]]);
+    if (T.ok) {      // pixels with a sample inside the triangle's box (the offsets lie in 32 .. 224), clamped to the viewport
+      x0 = max((min(T.X0, min(T.X1, T.X2)) + 31) >> 8, 0);
+      x1 = min((max(T.X0, max(T.X1, T.X2)) - 32) >> 8, W - 1);
+      y0 = max((min(T.Y0, min(T.Y1, T.Y2)) + 31) >> 8, 0);
+      y1 = min((max(T.Y0, max(T.Y1, T.Y2)) - 32) >> 8, H - 1);
+    }
+  }
+  const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+  const int nitem = (bw > 0 && bh > 0) ? bw * bh * S : 0;      // <= W H S <= 2^26 (fdm_render_set)
+  // the boxes of this wavefront, one after the other, by all 64 lanes (every lane of the wavefront comes here): item i is sample
+  // i % S of the box's pixel i / S, so the lanes' keys lie next to each other along a pixel row
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(nitem > 0);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    RenderTri Q;
+    Q.X0 = __shfl(T.X0, src); Q.Y0 = __shfl(T.Y0, src); Q.X1 = __shfl(T.X1, src); Q.Y1 = __shfl(T.Y1, src);
+    Q.X2 = __shfl(T.X2, src); Q.Y2 = __shfl(T.Y2, src);
+    Q.w0 = __shfl(T.w0, src); Q.w1 = __shfl(T.w1, src); Q.w2 = __shfl(T.w2, src);
+    Q.A = (long long)(Q.X1 - Q.X0) * (Q.Y2 - Q.Y0) - (long long)(Q.Y1 - Q.Y0) * (Q.X2 - Q.X0);
+    const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), sbw = __shfl(bw, src), sn = __shfl(nitem, src), sf = __shfl(f, src);
+    for (int i = lane; i < sn; i += 64) {
+      const int pix = i / S, s = i - pix * S;
+      const int dy = pix / sbw;
+      const int x = sx0 + (pix - dy * sbw), y = sy0 + dy;
+      int ox, oy;
+      render_sample_offset<S>(s, ox, oy);
+      render_hit_at(Q, 256 * x + ox, 256 * y + oy, sf, img + ((size_t)y * W + x) * S + s);
+    }
+  }
+}
+
+// rgb / depth / face as render_resolve_kernel; vis [n][H][W][S].  grid (blocks of RENDER_TB pixels, chunk rows).
+template <int S>
+__global__ __launch_bounds__(RENDER_TB) void render_resolve_aa_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
+                                                                      const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
+                                                                      unsigned char* rgb, float* depth, int* face) {
+  static_assert(S == 4 || S == 16, "the sample patterns of render_sample_offset");
+  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
+  if (i >= W * H) return;
+  const int2 bt = rowtab[row];
+  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
+  ulonglong2* slot = reinterpret_cast<ulonglong2*>(vis + ((size_t)row * W * H + i) * S);      // 8 S bytes, 16-byte aligned
+  const int y = i / W, x = i - y * W;
+  const size_t r0 = (size_t)row * V;
+  float ar = 0.f, ag = 0.f, ab = 0.f;
+  unsigned long long best = 0ull;
+  unsigned held = 0xFFFFFFFFu;            // the face whose setup T, n0, n1, n2 hold
+  RenderTri T = {};
+  float4 n0 = {}, n1 = {}, n2 = {};
+#pragma unroll 1
+  for (int h = 0; h < S / 2; ++h) {
+    const ulonglong2 two = slot[h];
+    slot[h] = make_ulonglong2(0ull, 0ull);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const unsigned long long key = e ? two.y : two.x;
+      const int s = 2 * h + e;
+      float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2];
+      const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+      if (key && won < (unsigned)F) {     // (a key names a face of the list: the raster kernel wrote it)
+        if (won != held) {
+          const int* fv = faces + 3 * (size_t)won;
+          T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
+          n0 = nc[r0 + fv[0]]; n1 = nc[r0 + fv[T.swapped ? 2 : 1]]; n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
+          held = won;
+        }
+        int ox, oy;
+        render_sample_offset<S>(s, ox, oy);
+        float l0, l1, l2, iw;
+        (void)render_fragment_at(T, 256 * x + ox, 256 * y + oy, l0, l1, l2, iw);
+        const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
+        cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
+        if (cr != cr) cr = vw.background[0];
+        if (cg != cg) cg = vw.background[1];
+        if (cb != cb) cb = vw.background[2];
+        cr = cr < 1.f ? cr : 1.f; cg = cg < 1.f ? cg : 1.f; cb = cb < 1.f ? cb : 1.f;
+        best = key > best ? key : best;
+      }
+      ar = s ? __fadd_rn(ar, cr) : cr; ag = s ? __fadd_rn(ag, cg) : cg; ab = s ? __fadd_rn(ab, cb) : cb;
+    }
+  }
+  const float inv = 1.f / (float)S;       // a power of two: the product is exact
+  unsigned char* px = rgb + 3 * o;
+  px[0] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ar, inv)), 0.5f);
+  px[1] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ag, inv)), 0.5f);
+  px[2] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ab, inv)), 0.5f);
+  if (depth) depth[o] = best ? __fdiv_rn(1.f, __uint_as_float((unsigned)(best >> 32))) : 0.f;
+  if (face) face[o] = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
 }
 
 }  // namespace fdm

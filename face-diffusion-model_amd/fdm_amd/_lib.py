@@ -231,6 +231,7 @@ SYMBOLS = {
     "fdm_render_create": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, vp, C.POINTER(vp)]),
     "fdm_render_set_view": (ci, [vp, vp, vp, vp, vp, ci, cf]),
     "fdm_render_set": (ci, [vp, C.c_char_p, ll]),
+    "fdm_render_sample_pattern_host": (ci, [ci, vp]),
     "fdm_render_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, vp, vp, vp, ci, vp, vp]),
     "fdm_render_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),

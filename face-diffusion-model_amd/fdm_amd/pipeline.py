@@ -263,7 +263,7 @@ def _render_plan(render, faces, V, device):
     """The render hand-off plan of `device`, the current stream, this topology and this view (render.RenderPlan.key).  render: a
     render.RenderPlan (used as it is where it was made for this device and stream, made again from its arguments otherwise; `faces`
     is then not read) or the dict of RenderPlan's arguments after faces and V (camera, lights, ambient, base, background,
-    chunk_frames)."""
+    chunk_frames, samples)."""
     from .render import RenderPlan, identity
     dv, at = _on_stream(device)
     if isinstance(render, RenderPlan):
@@ -293,7 +293,8 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
     """Vertices (or vertex offsets with template=) -> render.ImageFrames: shaded uint8 frames [B, L_out, H, W, 3] of the mesh with the
     triangle list `faces` [F, 3], drawn on the device in ONE call (render.RenderPlan; include/fdm_hip.h, fdm_render_forward; DESIGN.md
     section 2 item 23 states every operation).  render: a render.RenderPlan, or the dict of its arguments after faces and V -- camera (a
-    render.Camera or "vocaset" | "biwi" | "mead"), lights, ambient, base, background, chunk_frames -- which may also carry depth=True
+    render.Camera or "vocaset" | "biwi" | "mead"), lights, ambient, base, background, chunk_frames, samples (1, 4 or 16 coverage samples
+    per pixel: anti-aliased frames) -- which may also carry depth=True
     and face_ids=True for the depth [B, L_out, H, W] and face-id images.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with
     frames = L per clip (None: all L); a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of ImageFrames, each cut to its own
     frames and bit for bit what its own call returns; or a mesh.MeshFrames (planar fp32): its positions, normals and frames are drawn
@@ -1226,11 +1227,14 @@ def add_wrap_arguments(ap):
 
 
 def add_render_arguments(ap):
-    """--render / --render_size / --background_black of the demo command lines (the device render hand-off, to_images)."""
+    """--render / --render_size / --render_samples / --background_black of the demo command lines (the device render hand-off,
+    to_images)."""
     ap.add_argument("--render", action="store_true",
                     help="build-added: also save <stem>_frames.npy, uint8 [1, L_out, N, N, 3]: the frames of <stem>.npy drawn on the device with the "
                          "reference's camera and light directions (needs --faces_file), and print the ffmpeg line that makes an .mp4 of them")
     ap.add_argument("--render_size", type=int, default=800, help="build-added: N, the side of the rendered frames in pixels (with --render)")
+    ap.add_argument("--render_samples", type=int, default=1, choices=(1, 4, 16),
+                    help="build-added: coverage samples per pixel of the rendered frames, 4 or 16 for anti-aliased edges (with --render)")
     ap.add_argument("--background_black", action="store_true", help="a black background instead of white (with --render)")
 
 
@@ -1240,7 +1244,7 @@ def save_frames(a, p, verts, faces, dst):
     name = next((n for n in ("biwi", "mead") if n in p.name.lower()), "vocaset")
     N = int(a.render_size)
     bg = (0.0, 0.0, 0.0) if a.background_black else (1.0, 1.0, 1.0)
-    im = to_images(verts, faces, dict(camera=Camera.preset(name).resized(N, N), background=bg))
+    im = to_images(verts, faces, dict(camera=Camera.preset(name).resized(N, N), background=bg, samples=int(getattr(a, "render_samples", 1))))
     np.save(dst + "_frames", im.images.detach().cpu().numpy())
     print(f"saved {dst}_frames.npy {tuple(im.images.shape)}")
     rate = a.out_fps or a.in_fps or p.fps or 30

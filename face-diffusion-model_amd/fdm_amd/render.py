@@ -67,14 +67,26 @@ def reference_lights():
     return dict(lights=np.array([x + (LIGHT_INTENSITY,) for x in d], dtype=np.float32), ambient=0.2, base=(0.3, 0.3, 0.3))
 
 
-def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0):
+SAMPLE_COUNTS = (1, 4, 16)          # coverage samples per pixel (fdm_render_set "samples")
+
+
+def sample_pattern(n):
+    """The offsets of the n = 1, 4 or 16 coverage samples of a pixel, int32 [n, 2] = (x, y) in 1/256 pixel from the pixel's corner
+    (fdm_render_sample_pattern_host; no device needed)."""
+    xy = np.zeros((max(int(n), 0), 2), dtype=np.int32)
+    check(lib().fdm_render_sample_pattern_host(int(n), xy.ctypes.data))
+    return xy
+
+
+def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1):
     ref = reference_lights()
     if isinstance(camera, str):
         camera = Camera.preset(camera)
     lt = ref["lights"] if lights is None else np.asarray(lights, dtype=np.float32).reshape(-1, 4)
     three = lambda x: np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), (3,)))  # noqa: E731
     return dict(camera=camera, lights=np.ascontiguousarray(lt), ambient=float(ref["ambient"] if ambient is None else ambient),
-                base=three(ref["base"] if base is None else base), background=three(background), chunk_frames=int(chunk_frames))
+                base=three(ref["base"] if base is None else base), background=three(background), chunk_frames=int(chunk_frames),
+                samples=int(samples))
 
 
 def _view_key(a):
@@ -82,28 +94,31 @@ def _view_key(a):
     cam = a["camera"]
     for x in (cam.numbers(), cam.R, cam.t, a["lights"], a["base"], a["background"]):
         d.update(x.tobytes())
-    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], d.hexdigest())
+    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], a["samples"], d.hexdigest())
 
 
-def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0):
-    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view)."""
-    return (int(V), hashlib.sha1(faces_array(faces).tobytes()).hexdigest()) + _view_key(_arguments(camera, lights, ambient, base, background, chunk_frames))
+def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1):
+    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view, the sample count among it)."""
+    return (int(V), hashlib.sha1(faces_array(faces).tobytes()).hexdigest()) + _view_key(_arguments(camera, lights, ambient, base, background, chunk_frames,
+                                                                                                    samples))
 
 
 class RenderPlan(HandoffPlan):
     """Thin binding of fdm_render_create / fdm_render_forward for one topology and one view: faces [F, 3] over V vertices, camera (a
     Camera or a preset's name), lights [n <= 8, 4] = unit direction towards the light in camera space and intensity (None: the
     reference's five), ambient, base colour [3], background [3] in [0, 1] (white, as the reference's default), chunk_frames (0: scratch
-    under 256 MB).  The faces are checked and uploaded here; forward() only passes pointers.  A plan holds one scratch: it serves one
+    under 256 MB), samples (1, 4 or 16 coverage samples per pixel: anti-aliased frames; the scratch holds 8 W H
+    samples bytes per frame).  The faces are checked and uploaded here; forward() only passes pointers.  A plan holds one scratch: it serves one
     stream at a time (pipeline.to_images keeps them per (device, stream, topology, view)).  Without a visible device the plan still
     validates and forward() raises."""
 
     _destroy = "fdm_render_destroy"
 
-    def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, device="cuda:0"):
+    def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1,
+                 device="cuda:0"):
         super().__init__(device)
         self.faces, self.V = faces_array(faces), int(V)
-        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames)
+        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames, samples)
         a = self.view
         cam = a["camera"]
         self.W, self.H = cam.width, cam.height
@@ -112,6 +127,8 @@ class RenderPlan(HandoffPlan):
                      a["background"].ctypes.data)
         if a["chunk_frames"]:
             self.set_chunk_frames(a["chunk_frames"])
+        if a["samples"] != 1:
+            self.set_samples(a["samples"])
         self.key = identity(self.faces, self.V, **a)
 
     def arguments(self):
@@ -135,6 +152,13 @@ class RenderPlan(HandoffPlan):
         """Frames per chunk of scratch (0: the default).  The pixels do not depend on it."""
         check(lib().fdm_render_set(self.h, b"chunk_frames", int(n)))
         self.view = dict(self.view, chunk_frames=int(n))
+
+    def set_samples(self, n):
+        """Coverage samples per pixel: 1, 4 or 16 (fdm_render_set "samples").  The plan's key follows: plans of different sample counts
+        are different plans to pipeline's cache."""
+        check(lib().fdm_render_set(self.h, b"samples", int(n)))
+        self.view = dict(self.view, samples=int(n))
+        self.key = identity(self.faces, self.V, **self.view)
 
     def forward(self, positions, frames=None, template=None, fps=None, normals=None, depth=False, face_ids=False, out=None):
         """positions [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device -- vertices, or offsets with template [1 or B, 3 V] --, frames:

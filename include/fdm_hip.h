@@ -1165,12 +1165,27 @@ int fdm_wrap_destroy(fdm_wrap* w);
  * A call works through its live output frames a chunk at a time on `stream`: per-vertex records and the visibility buffer exist for one
  * chunk (one scratch per object, grown when a call needs more; the call that grows waits for the device).  fdm_render_set(r,
  * "chunk_frames", n): n frames per chunk, 0 = the default, the largest chunk whose scratch stays under 256 MB (at least one frame).
- * Not built: textures, the metallic-roughness material, anti-aliasing, clipping, video encoding.
+ * Anti-aliasing: fdm_render_set(r, "samples", S) with S = 1 (the default: everything above as it stands), 4 or 16 coverage samples per
+ *   pixel; any other S, or W H S > 2^26 keys per frame (4096^2 at 4 samples, 2048^2 at 16: 512 MB), is FDM_ERR_ARG.  The sample offsets
+ *   (ox_s, oy_s) are integers on the same 256-units-per-pixel grid (fdm_render_sample_pattern_host writes them, no device needed):
+ *     S = 1: (128, 128), the pixel centre;  S = 4 (rotated grid), in sample order: (96, 32), (224, 96), (32, 160), (160, 224);
+ *     S = 16 (4 x 4 grid): sample s = 4 j + i at (32 + 64 i, 32 + 64 j).
+ *   Steps 1 and 2 are unchanged.  Steps 3 and 4 hold per (triangle, pixel, sample) with (px, py) = (256 x + ox_s, 256 y + oy_s): the
+ *   same edge functions and top-left rule, the same l_i, iw and key, and every sample keeps the maximum key of its own.  Which pixels a
+ *   triangle is tried on is not part of the definition (a conservative box), nor does it show in the output.
+ *   Resolve, per pixel: for s ascending the three channels c_s -- a sample with a fragment is shaded as in step 5 from its own l_i and
+ *   iw (c = base_c k, a NaN c takes the background's channel, c = min(1, c)), a sample without one takes the background's channel --;
+ *   the channel's sum ((c_0 + c_1) + c_2) + ... in fp32, one rounded multiplication by 1 / S (a power of two: exact), then
+ *   u8 = (int)(255 c + 0.5f).  depth and face at S > 1 are a choice, made so that both images stay exact and independent of order:
+ *   they come from the maximum key over the pixel's samples -- the nearest sampled surface, among equal iw the lowest face index --,
+ *   depth = 1 / iw of that key, face its face; 0 and -1 when no sample has a fragment.  The visibility buffer holds 8 W H S bytes per
+ *   frame of a chunk, and the default chunk counts them.
+ * Not built: textures, the metallic-roughness material, alpha / coverage output for compositing, clipping, YUV output, video encoding.
  * fdm_render_create validates without a device and fdm_render_forward then ends in FDM_ERR_STATE.  Every check is made before the first
  * launch: FDM_ERR_ARG (a null r / positions / rgb, tmpl_rows not 0, 1 or B, a null template with tmpl_rows > 0, frame rates not finite
  * or negative; at create and set_view: a null array, F or V < 1, a face index outside [0, V), W or H outside 1 .. 4096, more than 8
- * lights, a light direction that is not a unit vector, near >= far, anything not finite; in fdm_render_set an unknown key or n outside
- * 0 .. 4096), FDM_ERR_SHAPE (B, L_max or L_out_max < 1, frames[b] outside [0, L_max], a clip whose L_out exceeds L_out_max).
+ * lights, a light direction that is not a unit vector, near >= far, anything not finite; in fdm_render_set an unknown key -- the keys
+ * are chunk_frames and samples --, chunk_frames outside 0 .. 4096 or samples as above), FDM_ERR_SHAPE (B, L_max or L_out_max < 1, frames[b] outside [0, L_max], a clip whose L_out exceeds L_out_max).
  * frames_out [B] HOST (or NULL) receives L_out per clip.  An object serves one stream at a time.  fdm_version() keeps its value: callers
  * detect the feature by the symbol.  Call times are unmeasured: profiles/render_out/README.md. */
 typedef struct fdm_render fdm_render;
@@ -1179,6 +1194,9 @@ int fdm_render_create(const int* faces, int F, int V, int W, int H, const float*
                       const float* background /*[3]*/, fdm_render** out);
 int fdm_render_set_view(fdm_render* r, const float* camera, const float* R, const float* t, const float* lights, int n_lights, float ambient);
 int fdm_render_set(fdm_render* r, const char* key, long long value);
+/* The sample offsets of `samples` = 1, 4 or 16 into xy [samples][2] HOST ints (no device needed); FDM_ERR_ARG for any other count or
+ * a null xy.  Callers detect multi-sample rendering by this symbol. */
+int fdm_render_sample_pattern_host(int samples, int* xy);
 int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
                        double fps_out, const float* normals /*or NULL*/, unsigned char* rgb, float* depth /*or NULL*/, int* face /*or NULL*/,
                        int L_out_max, int* frames_out, void* stream);

@@ -2,8 +2,9 @@
 written once plus one read of the positions.  One child process per case, each under its own `timeout -k 10`; a case that fails ends
 the run (nothing more is started on the device after a fault).  Nothing here is a merge condition; until it has been run the figures
 in profiles/render_out/README.md are listed as unmeasured.
-  python tools/bench_render.py            # all cases
-  python tools/bench_render.py --case 0   # one case, in this process"""
+  python tools/bench_render.py                      # all cases at one sample per pixel
+  python tools/bench_render.py --samples 1 4 16     # every case at each sample count (a child process per case and count)
+  python tools/bench_render.py --case 0 --samples 4 # one case, in this process"""
 import argparse
 import json
 import os
@@ -21,7 +22,7 @@ CASES = [("4 x 498 frames, V = 5023, 800 x 800", 4, 498, 5023, 800, 300), ("1 x 
 HBM_TBPS = 8.0       # the MI355X's stated peak, for the floor only
 
 
-def one(k, reps):
+def one(k, reps, samples=1):
     import numpy as np
     import torch
     import mesh_cases as MC
@@ -34,7 +35,7 @@ def one(k, reps):
     g = torch.Generator().manual_seed(k)
     x = (2e-3 * torch.randn(B, L, 3 * V, generator=g)).to("cuda:0")
     tmpl = torch.from_numpy(P.reshape(1, -1)).to("cuda:0")
-    plan = render.RenderPlan(faces, V, render.Camera.preset("vocaset").resized(N, N), device="cuda:0")
+    plan = render.RenderPlan(faces, V, render.Camera.preset("vocaset").resized(N, N), samples=samples, device="cuda:0")
     out = (torch.empty(B, L, N, N, 3, dtype=torch.uint8, device="cuda:0"), None, None)
     plan.forward(x, None, tmpl, out=out)          # grows the scratch
     torch.cuda.synchronize()
@@ -49,7 +50,7 @@ def one(k, reps):
     bytes_ = out[0].numel() + x.numel() * 4
     floor_ms = bytes_ / (HBM_TBPS * 1e12) * 1e3
     covered = float((out[0][0, 0].float().mean(-1) < 255).float().mean())
-    print(json.dumps(dict(case=name, ms_min=min(ms), ms_median=sorted(ms)[len(ms) // 2], reps=reps, floor_ms=floor_ms,
+    print(json.dumps(dict(case=name, samples=samples, ms_min=min(ms), ms_median=sorted(ms)[len(ms) // 2], reps=reps, floor_ms=floor_ms,
                           floor_share=floor_ms / min(ms), us_per_frame=1e3 * min(ms) / (B * L), covered=covered)))
 
 
@@ -57,14 +58,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", type=int, default=None)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--samples", type=int, nargs="+", default=[1], choices=(1, 4, 16), help="coverage samples per pixel (one child per case and count)")
     a = ap.parse_args()
     if a.case is not None:
-        return one(a.case, a.reps)
+        for n in a.samples:
+            one(a.case, a.reps, n)
+        return 0
     for k, c in enumerate(CASES):
-        r = subprocess.run(["timeout", "-k", "10", str(c[5]), sys.executable, os.path.abspath(__file__), "--case", str(k), "--reps", str(a.reps)])
-        if r.returncode != 0:
-            print(f"case {k} ({c[0]}) ended with status {r.returncode}: stopping here", file=sys.stderr)
-            return r.returncode
+        for n in a.samples:
+            r = subprocess.run(["timeout", "-k", "10", str(c[5]), sys.executable, os.path.abspath(__file__), "--case", str(k), "--reps", str(a.reps),
+                                "--samples", str(n)])
+            if r.returncode != 0:
+                print(f"case {k} ({c[0]}) at {n} samples ended with status {r.returncode}: stopping here", file=sys.stderr)
+                return r.returncode
     return 0
 
 
