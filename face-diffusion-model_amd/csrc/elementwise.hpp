@@ -803,8 +803,10 @@ __global__ __launch_bounds__(256) void vq_stats_partial_rowbook_kernel(const flo
                                                                        double* partial, int* hist) {
   vq_stats_partial_body<true>(z, codebook, book, n_books, idx, B, R, c, K, min_enc, partial, hist);
 }
-// book[row * rep .. row * rep + rep) = argmax(x[row, :]) (the first maximum, as torch.argmax -- except that a NaN never wins a
-// comparison here, where torch.argmax returns the NaN's index; the per-clip argmax_rows_kernel has the same rule): the codebook of every frame of an emotion
+// book[row * rep .. row * rep + rep) = argmax(x[row, :]) (the first maximum, as torch.argmax -- except for NaN, where torch.argmax
+// returns the NaN's index.  Here the scan starts from column 0 and moves on `v > best` alone, so a NaN in a column >= 1 never wins
+// ([1, NaN, 3] -> 2), while a NaN in column 0 is never beaten and stays the best ([NaN, 5, 3] -> 0; all NaN -> 0).  The per-clip
+// argmax_rows_kernel has the same rule): the codebook of every frame of an emotion
 // track, written once per latent vector of the frame (rep = G: the EVQ grouping maps frames to rows as it maps clips to rows)
 __global__ void argmax_rows_rep_kernel(const float* x, int* out, long long rows, int n, int rep) {
   const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -844,6 +846,9 @@ __global__ __launch_bounds__(256) void vq_stats_final_kernel(const double* parti
 // One workgroup per frame: squared vertex error d2 = ((gx-px)^2 + (gy-py)^2) + (gz-pz)^2 (numpy's order over axis 2, so
 // the per-frame maximum is bit-identical to the reference's), over a vertex region (or all vertices when region == NULL).
 // frame_max[f] = max d2;  frame_sum[2f] = sum d2, frame_sum[2f+1] = sum sqrt(d2)  (double accumulators, fixed order).
+// A NaN d2 in the region makes the frame's maximum NaN, as numpy's max does (fmaxf alone would drop it and report a clean
+// finite error for a frame that has none); the sums are NaN then as well, and so are all three outputs of the final kernel.
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
 __global__ __launch_bounds__(256) void vertex_err_kernel(const float* gt, const float* pred, const int* region, int R, int V,
                                                          float* frame_max, double* frame_sum) {
   __shared__ float rmax[4];
@@ -855,20 +860,20 @@ __global__ __launch_bounds__(256) void vertex_err_kernel(const float* gt, const 
     const size_t o = base + (size_t)(region ? region[r] : r) * 3;
     const float dx = __fsub_rn(gt[o], pred[o]), dy = __fsub_rn(gt[o + 1], pred[o + 1]), dz = __fsub_rn(gt[o + 2], pred[o + 2]);
     const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-    mx = fmaxf(mx, d2);
+    mx = max_keep_nan(mx, d2);
     s2 += (double)d2;
     sn += sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = max_keep_nan(mx, __shfl_xor(mx, o, 64));
     s2 += __shfl_xor(s2, o, 64);
     sn += __shfl_xor(sn, o, 64);
   }
   if ((threadIdx.x & 63) == 0) { rmax[threadIdx.x >> 6] = mx; rs[threadIdx.x >> 6] = s2; rn[threadIdx.x >> 6] = sn; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    frame_max[blockIdx.x] = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+    frame_max[blockIdx.x] = max_keep_nan(max_keep_nan(rmax[0], rmax[1]), max_keep_nan(rmax[2], rmax[3]));
     frame_sum[2 * blockIdx.x] = (rs[0] + rs[1]) + (rs[2] + rs[3]);
     frame_sum[2 * blockIdx.x + 1] = (rn[0] + rn[1]) + (rn[2] + rn[3]);
   }

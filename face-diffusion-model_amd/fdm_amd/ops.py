@@ -334,10 +334,11 @@ def time_groupnorm_lens(x, gamma, beta, B, T, C, lens, *, y_f32=None, y_t=None, 
                                            _p(lens), stream()))
 
 
-def mean_diff(a, b, l1=False):
-    """mean((a - b)^2) or mean(|a - b|) as a 1-element device tensor."""
-    partial = torch.empty(1024, device=a.device)
-    out = torch.empty(1, device=a.device)
+def mean_diff(a, b, l1=False, partial=None, out=None):
+    """mean((a - b)^2) or mean(|a - b|) as a 1-element device tensor.  partial (scratch, min(1024, ceil(n / 256)) floats are written)
+    and out (1 float) may be the caller's."""
+    partial = torch.empty(1024, device=a.device) if partial is None else partial
+    out = torch.empty(1, device=a.device) if out is None else out
     check(lib().fdm_op_mean_diff(_p(a), _p(b), _p(partial), _p(out), a.numel(), int(l1), stream()))
     return out
 
@@ -360,6 +361,28 @@ def adain(content, style, out, NC, Lc, Ls, eps=1e-5):
 
 def vq_quant(z, codebook, book, B, R, c, K, zq_bcl, idx):
     check(lib().fdm_op_vq_quant(_p(z), _p(codebook), _p(book), B, R, c, K, _p(zq_bcl), _p(idx), stream()))
+
+
+def vq_stats(z, codebook, book, idx, B, R, c, K, beta, min_encodings, partial, hist, out):
+    """book: int32 [B] or None.  partial: >= min(1024, ceil(B R / 4)) doubles, hist: K int32 (cleared by the call), out: 2 floats
+    (loss, perplexity); min_encodings [B R, K] fp32 or None."""
+    check(lib().fdm_op_vq_stats(_p(z), _p(codebook), _p(book), _p(idx), B, R, c, K, beta, _p(min_encodings), _p(partial), _p(hist), _p(out),
+                                stream()))
+
+
+def argmax_rows(x, book, rows, n, rep, n_books):
+    """book[r * rep .. r * rep + rep) = the first maximum of x[r, :n] (int32)."""
+    check(lib().fdm_op_argmax_rows(_p(x), _p(book), rows, n, rep, n_books, stream()))
+
+
+def vq_quant_rows(z, codebook, book_rows, n_books, B, R, c, K, zq_bcl, idx):
+    """vq_quant with one codebook slice per row: book_rows int32 [B R]."""
+    check(lib().fdm_op_vq_quant_rows(_p(z), _p(codebook), _p(book_rows), n_books, B, R, c, K, _p(zq_bcl), _p(idx), stream()))
+
+
+def vq_stats_rows(z, codebook, book_rows, n_books, idx, B, R, c, K, beta, min_encodings, partial, hist, out):
+    check(lib().fdm_op_vq_stats_rows(_p(z), _p(codebook), _p(book_rows), n_books, _p(idx), B, R, c, K, beta, _p(min_encodings), _p(partial),
+                                     _p(hist), _p(out), stream()))
 
 
 PCM_FORMATS = {torch.int16: _lib.PCM_S16, torch.int32: _lib.PCM_S32, torch.uint8: _lib.PCM_U8, torch.float32: _lib.PCM_F32}

@@ -429,7 +429,9 @@ int fdm_op_mean_diff(const float* a, const float* b, float* partial, float* out,
  * region: R int32 vertex indices (NULL with R == V: all vertices).  Per frame: frame_max[f] = max_r d2 (bit-identical to
  * numpy's float32 value), frame_sum[2f] = sum_r d2, frame_sum[2f+1] = sum_r sqrt(d2) with d2 = |gt - pred|^2;
  * out[0] = mean_f frame_max ("Lip/Face Vertex Error"), out[1] = mean d2 ("Emotion Mean Error"), out[2] = mean |d|
- * ("Mean Vertex Error"; compute_diversity's pairwise distance).  Deterministic (fixed reduction order).                  */
+ * ("Mean Vertex Error"; compute_diversity's pairwise distance).  Deterministic (fixed reduction order).
+ * NaN propagates as in numpy: a NaN coordinate of a region vertex makes that frame's frame_max and sums NaN and with them
+ * all of out[0..2]; other frames' frame_max keep their bits; a NaN at a vertex outside the region is never read.          */
 int fdm_op_vertex_err(const float* gt, const float* pred, const int* region, int R, int F, int V,
                       float* frame_max, double* frame_sum, double* out, void* stream);
 /* out[0] = mean_r std_f(|verts[f, region[r]] - tmpl[region[r]]|^2): the per-sequence motion statistic whose gt - pred
