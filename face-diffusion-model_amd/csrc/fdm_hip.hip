@@ -98,6 +98,7 @@ int fdm_abi_struct_size(const char* name) {
   if (n == "fdm_slot_bank_args") return (int)sizeof(fdm_slot_bank_args);
   if (n == "fdm_pcm") return (int)sizeof(fdm_pcm);
   if (n == "fdm_flame_model") return (int)sizeof(fdm_flame_model);
+  if (n == "fdm_render_planes") return (int)sizeof(fdm_render_planes);
   return fdm::fail(FDM_ERR_ARG, "abi_struct_size: unknown struct '%s'", name);
 }
 

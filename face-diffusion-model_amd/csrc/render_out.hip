@@ -17,6 +17,7 @@ struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
   int F = 0, V = 0, W = 0, H = 0;
   long long chunk_frames = 0;             // 0: the default (scratch under RENDER_SCRATCH_BYTES)
   int samples = 1;                        // coverage samples per pixel: 1, 4 or 16
+  int yuv_matrix = 709, yuv_range = 0, yuv_layout = 0;      // fdm_render_set "yuv_*": 601 | 709, 0 limited | 1 full, 0 I420 | 1 NV12
   fdm::RenderView view;
   fdm_mesh* mesh = nullptr;               // the normals of a chunk (fdm_mesh_forward on the chunk's positions)
   int* faces = nullptr;                   // device [F][3]
@@ -139,7 +140,23 @@ int fdm_render_set(fdm_render* r, const char* key, long long value) {
     r->samples = (int)value;
     return FDM_OK;
   }
-  if (std::strcmp(key, "chunk_frames") != 0) return fail(FDM_ERR_ARG, "render_set: unknown key %s (chunk_frames, samples)", key);
+  if (std::strcmp(key, "yuv_matrix") == 0) {
+    if (value != 601 && value != 709) return fail(FDM_ERR_ARG, "render_set: yuv_matrix = %lld (601 or 709)", value);
+    r->yuv_matrix = (int)value;
+    return FDM_OK;
+  }
+  if (std::strcmp(key, "yuv_range") == 0) {
+    if (value != 0 && value != 1) return fail(FDM_ERR_ARG, "render_set: yuv_range = %lld (0 limited, 1 full)", value);
+    r->yuv_range = (int)value;
+    return FDM_OK;
+  }
+  if (std::strcmp(key, "yuv_layout") == 0) {
+    if (value != 0 && value != 1) return fail(FDM_ERR_ARG, "render_set: yuv_layout = %lld (0 I420, 1 NV12)", value);
+    r->yuv_layout = (int)value;
+    return FDM_OK;
+  }
+  if (std::strcmp(key, "chunk_frames") != 0)
+    return fail(FDM_ERR_ARG, "render_set: unknown key %s (chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout)", key);
   if (value < 0 || value > RENDER_CHUNK_MAX) return fail(FDM_ERR_ARG, "render_set: chunk_frames = %lld (0 = the default, at most %lld)", value, RENDER_CHUNK_MAX);
   r->chunk_frames = value;
   return FDM_OK;
@@ -154,22 +171,62 @@ int fdm_render_sample_pattern_host(int samples, int* xy) {
   return FDM_OK;
 }
 
-int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
-                       double fps_out, const float* normals, unsigned char* rgb, float* depth, int* face, int L_out_max, int* frames_out,
-                       void* stream) {
-  if (!r || !positions || !rgb) return fail(FDM_ERR_ARG, "render_forward: null argument");
-  if (tmpl_rows != 0 && tmpl_rows != 1 && tmpl_rows != B) return fail(FDM_ERR_ARG, "render_forward: tmpl_rows = %d (0, 1 or B = %d)", tmpl_rows, B);
-  if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "render_forward: tmpl_rows = %d with a null template", tmpl_rows);
-  FCK(check_fps("render_forward", fps_in, fps_out));
-  if (B < 1 || L_max < 1 || L_out_max < 1) return fail(FDM_ERR_SHAPE, "render_forward: B = %d, L_max = %d, L_out_max = %d", B, L_max, L_out_max);
+int fdm_render_yuv_coeffs_host(int matrix, int full_range, int* coeffs) {
+  if (!coeffs) return fail(FDM_ERR_ARG, "render_yuv_coeffs_host: null coeffs");
+  if (matrix != 601 && matrix != 709) return fail(FDM_ERR_ARG, "render_yuv_coeffs_host: matrix = %d (601 or 709)", matrix);
+  const double Kr = matrix == 601 ? 0.299 : 0.2126, Kb = matrix == 601 ? 0.114 : 0.0722;
+  const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;
+  auto q = [](double x) { return (int)std::floor(65536.0 * x + 0.5); };
+  const int yr = q(Kr * sy), yb = q(Kb * sy), yg = q(sy) - yr - yb;      // the green terms from the other two: every grey is exact
+  const int ub = q(sc / 2.0), ur = q(-Kr * sc / (2.0 * (1.0 - Kb))), ug = -(ur + ub);
+  const int vr = q(sc / 2.0), vb = q(-Kb * sc / (2.0 * (1.0 - Kr))), vg = -(vr + vb);
+  const int all[10] = {yr, yg, yb, ur, ug, ub, vr, vg, vb, full_range ? 0 : 16};
+  std::memcpy(coeffs, all, sizeof(all));
+  return FDM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <int S> void launch_resolve_planes(bool yuv, dim3 grid, hipStream_t s, const fdm_render* r, const int2* tab, int L_out_max,
+                                            const RenderOut& out, const RenderYuv& yc) {
+  if (yuv)
+    hipLaunchKernelGGL((render_resolve_planes_kernel<S, true>), grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
+  else
+    hipLaunchKernelGGL((render_resolve_planes_kernel<S, false>), grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
+}
+
+// The body of fdm_render_forward (planes = false: the resolve kernels as they stand, out.rgb set, alpha and yuv null) and of
+// fdm_render_forward_planes (planes = true: render_resolve_planes_kernel writes whichever outputs are not null).  r, positions and the
+// outputs have been checked by the caller.
+int render_run(const char* who, fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+               double fps_in, double fps_out, const float* normals, const RenderOut& out, bool planes, int L_out_max, int* frames_out, void* stream) {
+  unsigned char* const rgb = out.rgb;
+  float* const depth = out.depth;
+  int* const face = out.face;
+  if (tmpl_rows != 0 && tmpl_rows != 1 && tmpl_rows != B) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d (0, 1 or B = %d)", who, tmpl_rows, B);
+  if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d with a null template", who, tmpl_rows);
+  FCK(check_fps(who, fps_in, fps_out));
+  if (B < 1 || L_max < 1 || L_out_max < 1) return fail(FDM_ERR_SHAPE, "%s: B = %d, L_max = %d, L_out_max = %d", who, B, L_max, L_out_max);
   std::vector<int> hl;
   const ClipLens c = clip_lens(frames, B, L_max, fps_in, fps_out, L_out_max, hl);
-  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "render_forward: clip %d has %d frames, the batch is %d long", c.clip, c.L, L_max);
-  if (c.bad == ClipLens::OUTPUT) return fail(FDM_ERR_SHAPE, "render_forward: clip %d gives %lld frames, the output is %d long", c.clip, c.Lo, L_out_max);
+  if (c.bad == ClipLens::LENGTH) return fail(FDM_ERR_SHAPE, "%s: clip %d has %d frames, the batch is %d long", who, c.clip, c.L, L_max);
+  if (c.bad == ClipLens::OUTPUT) return fail(FDM_ERR_SHAPE, "%s: clip %d gives %lld frames, the output is %d long", who, c.clip, c.Lo, L_out_max);
   const long long V3 = 3LL * r->V, WH = (long long)r->W * r->H;
   if ((long long)B * L_out_max > 0x7fffffffLL || (V3 + RENDER_POS_TILE - 1) / RENDER_POS_TILE > 65535)
-    return fail(FDM_ERR_SHAPE, "render_forward: %lld output rows of %d vertices exceed one launch", (long long)B * L_out_max, r->V);
-  FCK(handoff_device(*r, "render_forward"));
+    return fail(FDM_ERR_SHAPE, "%s: %lld output rows of %d vertices exceed one launch", who, (long long)B * L_out_max, r->V);
+  RenderYuv yc;
+  std::memset(&yc, 0, sizeof(yc));
+  if (out.yuv) {
+    int k[10];
+    FCK(fdm_render_yuv_coeffs_host(r->yuv_matrix, r->yuv_range, k));
+    yc.yr = k[0]; yc.yg = k[1]; yc.yb = k[2]; yc.ur = k[3]; yc.ug = k[4]; yc.ub = k[5]; yc.vr = k[6]; yc.vg = k[7]; yc.vb = k[8]; yc.y0 = k[9];
+    yc.nv12 = r->yuv_layout;
+  }
+  FCK(handoff_device(*r, who));
   hipStream_t s = (hipStream_t)stream;
   std::vector<int2>& rows = r->rows;      // the live output frames, in (clip, frame) order
   rows.clear();
@@ -195,14 +252,17 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
   for (int b = 0; b < B; ++b) {
     const long long lo = hl[2 * b + 1], n = (L_out_max - lo) * WH, at = ((long long)b * L_out_max + lo) * WH;
     if (!n) continue;
-    HIPCK(hipMemsetAsync(rgb + 3 * at, 0, (size_t)(3 * n), s));
+    if (rgb) HIPCK(hipMemsetAsync(rgb + 3 * at, 0, (size_t)(3 * n), s));
     if (depth) HIPCK(hipMemsetAsync(depth + at, 0, (size_t)n * sizeof(float), s));
     if (face) HIPCK(hipMemsetAsync(face + at, 0, (size_t)n * sizeof(int), s));
+    if (out.alpha) HIPCK(hipMemsetAsync(out.alpha + at, 0, (size_t)n, s));
+    if (out.yuv) HIPCK(hipMemsetAsync(out.yuv + at + at / 2, 0, (size_t)(n + n / 2), s));      // (W H is a multiple of 4 here)
   }
   const int rs = resamples(fps_in, fps_out) ? 1 : 0, tstride = tmpl_rows == B && B > 1 ? (int)V3 : 0;
   const float* tp = tmpl_rows ? tmpl : nullptr;
   const unsigned vblocks = (unsigned)((r->V + RENDER_TB - 1) / RENDER_TB), fblocks = (unsigned)((r->F + RENDER_TB - 1) / RENDER_TB);
   const unsigned pblocks = (unsigned)((WH + RENDER_TB - 1) / RENDER_TB);
+  const unsigned qblocks = (unsigned)((WH / 4 + RENDER_TB - 1) / RENDER_TB);      // 2 x 2 blocks of pixels (with yuv)
   for (long long r0 = 0; r0 < live; r0 += chunk) {
     const int n = (int)std::min(chunk, live - r0);
     const int2* tab = r->rowtab + r0;
@@ -215,7 +275,22 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
     hipLaunchKernelGGL(render_vertex_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const float*)r->P, normals ? normals : (const float*)r->N,
                        normals ? tab : (const int2*)nullptr, L_out_max, r->V, r->view, r->xyw, r->nc);
     r->vis_dirty = true;
-    if (r->samples == 1) {
+    if (planes) {
+      const dim3 grid(out.yuv ? qblocks : pblocks, (unsigned)n);
+      if (r->samples == 1) {
+        hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
+                           r->W, r->H, r->vis);
+        launch_resolve_planes<1>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
+      } else if (r->samples == 4) {
+        hipLaunchKernelGGL(render_raster_aa_kernel<4>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
+                           r->V, r->W, r->H, r->vis);
+        launch_resolve_planes<4>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
+      } else {
+        hipLaunchKernelGGL(render_raster_aa_kernel<16>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
+                           r->V, r->W, r->H, r->vis);
+        launch_resolve_planes<16>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
+      }
+    } else if (r->samples == 1) {
       hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
                          r->W, r->H, r->vis);
       hipLaunchKernelGGL(render_resolve_kernel, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
@@ -236,6 +311,32 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
   }
   if (frames_out) for (int b = 0; b < B; ++b) frames_out[b] = hl[2 * b + 1];
   return FDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
+                       double fps_out, const float* normals, unsigned char* rgb, float* depth, int* face, int L_out_max, int* frames_out,
+                       void* stream) {
+  if (!r || !positions || !rgb) return fail(FDM_ERR_ARG, "render_forward: null argument");
+  const RenderOut out = {rgb, depth, face, nullptr, nullptr};
+  return render_run("render_forward", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, false, L_out_max, frames_out,
+                    stream);
+}
+
+int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+                              double fps_in, double fps_out, const float* normals, const fdm_render_planes* planes, int L_out_max,
+                              int* frames_out, void* stream) {
+  if (!r || !positions || !planes) return fail(FDM_ERR_ARG, "render_forward_planes: null argument");
+  const RenderOut out = {planes->rgb, planes->depth, planes->face, planes->alpha, planes->yuv};
+  if (!out.rgb && !out.depth && !out.face && !out.alpha && !out.yuv) return fail(FDM_ERR_ARG, "render_forward_planes: every output is null");
+  if (out.yuv && ((r->W | r->H) & 1))
+    return fail(FDM_ERR_ARG, "render_forward_planes: yuv 4:2:0 needs an even width and height, the viewport is %d x %d", r->W, r->H);
+  if (out.yuv && ((size_t)out.yuv & 1)) return fail(FDM_ERR_ARG, "render_forward_planes: yuv must be 2-byte aligned");
+  return render_run("render_forward_planes", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, true, L_out_max,
+                    frames_out, stream);
 }
 
 }  // extern "C"

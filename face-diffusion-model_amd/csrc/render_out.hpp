@@ -23,6 +23,12 @@
 //                          every sample that has a fragment (a triangle's setup and normals are kept while consecutive samples name
 //                          the same face), sums the channels in sample order, scales by 1 / S; depth and face from the largest key.
 // S = 1 launches render_raster_kernel and render_resolve_kernel as they stand.
+// The per-pixel work of the two resolve kernels is one device function each (render_resolve_pixel, render_resolve_aa_pixel<S>: a pixel ->
+// three 8-bit channels, the largest key, the count of covered samples).  fdm_render_forward_planes replaces the resolve kernel by
+//   render_resolve_planes_kernel<S, YUV>   the same functions; writes any of rgb / depth / face / alpha (coverage count -> 8 bits) and,
+//                          with YUV, the frame's Y'CbCr 4:2:0 planes (I420 or NV12) from the 8-bit rgb, one lane per 2 x 2 block of
+//                          pixels.  The keys are cleared as they are read, so every plane comes out of this one pass and no rgb image
+//                          is written that the caller did not ask for.
 // No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -240,6 +246,44 @@ __device__ __forceinline__ unsigned char render_u8(float c, float bg) {      // 
   return (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, c), 0.5f);
 }
 
+// What the resolve of one pixel gives: the three 8-bit channels, the largest key over the pixel's samples (0: no fragment) and n, the
+// number of its samples that have a fragment.  depth, face and alpha follow from best and n.
+struct RenderPixel {
+  unsigned char r, g, b;
+  int n;
+  unsigned long long best;
+};
+__device__ __forceinline__ float render_key_depth(unsigned long long best) {
+  return best ? __fdiv_rn(1.f, __uint_as_float((unsigned)(best >> 32))) : 0.f;
+}
+__device__ __forceinline__ int render_key_face(unsigned long long best) {
+  return best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
+}
+
+// Step 5 for the pixel (x, y) of the chunk's row whose vertex records start at r0 = row V: reads the key at `slot` and writes 0 back
+// (the buffer is clear for the next chunk), recomputes the winning face's fragment, interpolates the normal, shades.
+__device__ __forceinline__ RenderPixel render_resolve_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int x, int y,
+                                                            const RenderView& vw, unsigned long long* slot) {
+  const unsigned long long key = *slot;
+  *slot = 0ull;
+  float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2];
+  RenderPixel p;
+  p.n = 0; p.best = 0ull;
+  const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+  if (key && won < (unsigned)F) {         // (a key names a face of the list: the raster kernel wrote it)
+    const int* fv = faces + 3 * (size_t)won;
+    const RenderTri T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
+    const float4 n0 = nc[r0 + fv[0]], n1 = nc[r0 + fv[T.swapped ? 2 : 1]], n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
+    float l0, l1, l2, iw;
+    (void)render_fragment(T, x, y, l0, l1, l2, iw);
+    const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
+    cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
+    p.n = 1; p.best = key;                // (the recomputed iw has the key's bits: the same expressions on the same integers)
+  }
+  p.r = render_u8(cr, vw.background[0]); p.g = render_u8(cg, vw.background[1]); p.b = render_u8(cb, vw.background[2]);
+  return p;
+}
+
 // rgb / depth / face: the call's outputs [B][Lo_max][H][W](3); depth and face may be null.  grid (blocks of RENDER_TB pixels, chunk rows).
 __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
                                                                    const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
@@ -248,29 +292,12 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
   if (i >= W * H) return;
   const int2 bt = rowtab[row];
   const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
-  unsigned long long* slot = vis + (size_t)row * W * H + i;
-  const unsigned long long key = *slot;
-  *slot = 0ull;
-  float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2], dep = 0.f;
-  int id = -1;
-  const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-  if (key && won < (unsigned)F) {         // (a key names a face of the list: the raster kernel wrote it)
-    id = (int)won;
-    const int* fv = faces + 3 * (size_t)id;
-    const size_t r0 = (size_t)row * V;
-    const RenderTri T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
-    const float4 n0 = nc[r0 + fv[0]], n1 = nc[r0 + fv[T.swapped ? 2 : 1]], n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
-    const int y = i / W, x = i - y * W;
-    float l0, l1, l2, iw;
-    (void)render_fragment(T, x, y, l0, l1, l2, iw);
-    const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
-    cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
-    dep = __fdiv_rn(1.f, iw);
-  }
+  const int y = i / W, x = i - y * W;
+  const RenderPixel p = render_resolve_pixel(xyw, nc, faces, F, (size_t)row * V, x, y, vw, vis + (size_t)row * W * H + i);
   unsigned char* px = rgb + 3 * o;
-  px[0] = render_u8(cr, vw.background[0]); px[1] = render_u8(cg, vw.background[1]); px[2] = render_u8(cb, vw.background[2]);
-  if (depth) depth[o] = dep;
-  if (face) face[o] = id;
+  px[0] = p.r; px[1] = p.g; px[2] = p.b;
+  if (depth) depth[o] = render_key_depth(p.best);
+  if (face) face[o] = render_key_face(p.best);
 }
 
 // ---- S = 4 or 16 samples per pixel
@@ -320,21 +347,15 @@ __global__ __launch_bounds__(RENDER_TB) void render_raster_aa_kernel(const int4*
   }
 }
 
-// rgb / depth / face as render_resolve_kernel; vis [n][H][W][S].  grid (blocks of RENDER_TB pixels, chunk rows).
+// The resolve of the pixel (x, y) at S = 4 or 16: reads and clears the pixel's 8 S contiguous bytes at `slot` 16 at a time, shades every
+// sample that has a fragment, sums the channels in sample order, scales by 1 / S.
 template <int S>
-__global__ __launch_bounds__(RENDER_TB) void render_resolve_aa_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
-                                                                      const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
-                                                                      unsigned char* rgb, float* depth, int* face) {
+__device__ __forceinline__ RenderPixel render_resolve_aa_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int x, int y,
+                                                               const RenderView& vw, ulonglong2* slot) {
   static_assert(S == 4 || S == 16, "the sample patterns of render_sample_offset");
-  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
-  if (i >= W * H) return;
-  const int2 bt = rowtab[row];
-  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
-  ulonglong2* slot = reinterpret_cast<ulonglong2*>(vis + ((size_t)row * W * H + i) * S);      // 8 S bytes, 16-byte aligned
-  const int y = i / W, x = i - y * W;
-  const size_t r0 = (size_t)row * V;
   float ar = 0.f, ag = 0.f, ab = 0.f;
-  unsigned long long best = 0ull;
+  RenderPixel p;
+  p.n = 0; p.best = 0ull;
   unsigned held = 0xFFFFFFFFu;            // the face whose setup T, n0, n1, n2 hold
   RenderTri T = {};
   float4 n0 = {}, n1 = {}, n2 = {};
@@ -365,18 +386,110 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_aa_kernel(const int4
         if (cg != cg) cg = vw.background[1];
         if (cb != cb) cb = vw.background[2];
         cr = cr < 1.f ? cr : 1.f; cg = cg < 1.f ? cg : 1.f; cb = cb < 1.f ? cb : 1.f;
-        best = key > best ? key : best;
+        p.best = key > p.best ? key : p.best;
+        ++p.n;
       }
       ar = s ? __fadd_rn(ar, cr) : cr; ag = s ? __fadd_rn(ag, cg) : cg; ab = s ? __fadd_rn(ab, cb) : cb;
     }
   }
   const float inv = 1.f / (float)S;       // a power of two: the product is exact
+  p.r = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ar, inv)), 0.5f);
+  p.g = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ag, inv)), 0.5f);
+  p.b = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ab, inv)), 0.5f);
+  return p;
+}
+
+// rgb / depth / face as render_resolve_kernel; vis [n][H][W][S].  grid (blocks of RENDER_TB pixels, chunk rows).
+template <int S>
+__global__ __launch_bounds__(RENDER_TB) void render_resolve_aa_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
+                                                                      const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
+                                                                      unsigned char* rgb, float* depth, int* face) {
+  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
+  if (i >= W * H) return;
+  const int2 bt = rowtab[row];
+  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
+  ulonglong2* slot = reinterpret_cast<ulonglong2*>(vis + ((size_t)row * W * H + i) * S);      // 8 S bytes, 16-byte aligned
+  const int y = i / W, x = i - y * W;
+  const RenderPixel p = render_resolve_aa_pixel<S>(xyw, nc, faces, F, (size_t)row * V, x, y, vw, slot);
   unsigned char* px = rgb + 3 * o;
-  px[0] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ar, inv)), 0.5f);
-  px[1] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ag, inv)), 0.5f);
-  px[2] = (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, __fmul_rn(ab, inv)), 0.5f);
-  if (depth) depth[o] = best ? __fdiv_rn(1.f, __uint_as_float((unsigned)(best >> 32))) : 0.f;
-  if (face) face[o] = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
+  px[0] = p.r; px[1] = p.g; px[2] = p.b;
+  if (depth) depth[o] = render_key_depth(p.best);
+  if (face) face[o] = render_key_face(p.best);
+}
+
+// ---- the planes form of resolve (fdm_render_forward_planes): any of rgb / depth / face / alpha / yuv from the one pass over vis
+struct RenderOut {                        // kernel argument (by value): the call's outputs, null where it writes none
+  unsigned char* rgb; float* depth; int* face; unsigned char* alpha; unsigned char* yuv;
+};
+struct RenderYuv {                        // kernel argument (by value): fdm_render_yuv_coeffs_host's ten numbers and the layout
+  int yr, yg, yb, ur, ug, ub, vr, vg, vb, y0;
+  int nv12;
+};
+__host__ __device__ __forceinline__ int render_clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// the pixel (x, y) at any S: one of the two functions above on the pixel's keys
+template <int S>
+__device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int W, int x, int y,
+                                                    const RenderView& vw, unsigned long long* img) {
+  unsigned long long* slot = img + ((size_t)y * W + x) * S;
+  if constexpr (S == 1) return render_resolve_pixel(xyw, nc, faces, F, r0, x, y, vw, slot);
+  else return render_resolve_aa_pixel<S>(xyw, nc, faces, F, r0, x, y, vw, reinterpret_cast<ulonglong2*>(slot));
+}
+// rgb / depth / face / alpha of the pixel at o = (output frame) W H + y W + x, where asked for
+__device__ __forceinline__ void render_store_pixel(const RenderOut& out, size_t o, const RenderPixel& p, int S) {
+  if (out.rgb) { unsigned char* px = out.rgb + 3 * o; px[0] = p.r; px[1] = p.g; px[2] = p.b; }
+  if (out.depth) out.depth[o] = render_key_depth(p.best);
+  if (out.face) out.face[o] = render_key_face(p.best);
+  if (out.alpha) out.alpha[o] = (unsigned char)((255 * p.n + S / 2) / S);
+}
+
+// YUV = false: one lane per (chunk row, pixel), as the resolve kernels, plus the alpha store.  grid (blocks of RENDER_TB pixels, rows).
+// YUV = true (W and H even): one lane per (chunk row, 2 x 2 block of pixels).  The lane resolves its four pixels one after the other
+// (not unrolled: the registers of one pixel, three channel sums and one luma byte stay live), stores each row's two luma bytes in one
+// 2-byte store -- the 64 lanes of a wavefront write 128 contiguous bytes of a luma row -- and the block's chroma once (NV12: one
+// 2-byte store).  yuv: [B][Lo_max][3 W H / 2], 2-byte aligned.  grid (blocks of RENDER_TB blocks of pixels, chunk rows).
+template <int S, bool YUV>
+__global__ __launch_bounds__(RENDER_TB) void render_resolve_planes_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W,
+                                                                          int H, const int2* rowtab, int Lo_max, const RenderView vw,
+                                                                          unsigned long long* vis, const RenderOut out, const RenderYuv yc) {
+  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
+  const size_t WH = (size_t)W * H, r0 = (size_t)row * V;
+  unsigned long long* img = vis + (size_t)row * WH * S;
+  if constexpr (!YUV) {
+    if (i >= W * H) return;
+    const int2 bt = rowtab[row];
+    const int y = i / W, x = i - y * W;
+    const RenderPixel p = render_pixel<S>(xyw, nc, faces, F, r0, W, x, y, vw, img);
+    render_store_pixel(out, ((size_t)bt.x * Lo_max + bt.y) * WH + i, p, S);
+  } else {
+    const int W2 = W >> 1;
+    if (i >= W2 * (H >> 1)) return;
+    const int2 bt = rowtab[row];
+    const size_t frame = (size_t)bt.x * Lo_max + bt.y;
+    const int by = i / W2, bx = i - by * W2;
+    unsigned char* Yp = out.yuv + frame * (WH + WH / 2);
+    int Rs = 0, Gs = 0, Bs = 0, left = 0;
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {
+      const int x = 2 * bx + (q & 1), y = 2 * by + (q >> 1);
+      const RenderPixel p = render_pixel<S>(xyw, nc, faces, F, r0, W, x, y, vw, img);
+      render_store_pixel(out, frame * WH + (size_t)y * W + x, p, S);
+      const int R = p.r, G = p.g, B = p.b;
+      Rs += R; Gs += G; Bs += B;
+      const int luma = render_clamp_u8(((yc.yr * R + yc.yg * G + yc.yb * B + 32768) >> 16) + yc.y0);
+      if (q & 1) *reinterpret_cast<uchar2*>(Yp + (size_t)y * W + 2 * bx) = make_uchar2((unsigned char)left, (unsigned char)luma);
+      else left = luma;
+    }
+    const unsigned char U = (unsigned char)render_clamp_u8(((yc.ur * Rs + yc.ug * Gs + yc.ub * Bs + (1 << 17)) >> 18) + 128);
+    const unsigned char Vv = (unsigned char)render_clamp_u8(((yc.vr * Rs + yc.vg * Gs + yc.vb * Bs + (1 << 17)) >> 18) + 128);
+    unsigned char* Cp = Yp + WH;
+    if (yc.nv12) {
+      *reinterpret_cast<uchar2*>(Cp + 2 * (size_t)i) = make_uchar2(U, Vv);
+    } else {
+      Cp[i] = U;
+      Cp[WH / 4 + i] = Vv;
+    }
+  }
 }
 
 }  // namespace fdm

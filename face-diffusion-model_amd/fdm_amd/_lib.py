@@ -93,6 +93,10 @@ class Pcm(C.Structure):
     _fields_ = [("data", vp), ("format", ci), ("channels", ci), ("rate", ci), ("frames", ll)]
 
 
+class RenderPlanes(C.Structure):          # fdm_render_planes: the outputs of fdm_render_forward_planes, null where none is written
+    _fields_ = [("rgb", vp), ("depth", vp), ("face", vp), ("alpha", vp), ("yuv", vp)]
+
+
 class FlameModelDesc(C.Structure):
     _fields_ = [("V", ci), ("J", ci), ("NB", ci), ("expr_at", ci), ("v_template", vp), ("shapedirs", vp), ("posedirs", vp),
                 ("j_regressor", vp), ("parents", vp), ("lbs_weights", vp)]
@@ -105,7 +109,7 @@ WRAP_OFFSETS = 1      # fdm_wrap_forward flags
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
            "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs,
-           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm, "fdm_flame_model": FlameModelDesc}
+           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm, "fdm_flame_model": FlameModelDesc, "fdm_render_planes": RenderPlanes}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -233,6 +237,8 @@ SYMBOLS = {
     "fdm_render_set": (ci, [vp, C.c_char_p, ll]),
     "fdm_render_sample_pattern_host": (ci, [ci, vp]),
     "fdm_render_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, vp, vp, vp, ci, vp, vp]),
+    "fdm_render_forward_planes": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, C.POINTER(RenderPlanes), ci, vp, vp]),
+    "fdm_render_yuv_coeffs_host": (ci, [ci, ci, vp]),
     "fdm_render_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),

@@ -256,14 +256,14 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
     return [y[b:b + 1, :n] for b, n in enumerate(frames)] if many else y
 
 
-_RENDER_OUTPUTS = ("depth", "face_ids")      # keys of a render= dict that choose outputs, not the plan
+_RENDER_OUTPUTS = ("depth", "face_ids", "alpha", "yuv")      # keys of a render= dict that choose outputs, not the plan
 
 
 def _render_plan(render, faces, V, device):
     """The render hand-off plan of `device`, the current stream, this topology and this view (render.RenderPlan.key).  render: a
     render.RenderPlan (used as it is where it was made for this device and stream, made again from its arguments otherwise; `faces`
     is then not read) or the dict of RenderPlan's arguments after faces and V (camera, lights, ambient, base, background,
-    chunk_frames, samples)."""
+    chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout; yuv="i420" | "nv12" among its outputs is the plan's yuv_layout)."""
     from .render import RenderPlan, identity
     dv, at = _on_stream(device)
     if isinstance(render, RenderPlan):
@@ -274,6 +274,8 @@ def _render_plan(render, faces, V, device):
         if faces is None:
             raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn")
         kw = {k: v for k, v in render.items() if k not in _RENDER_OUTPUTS}
+        if isinstance(render.get("yuv"), str):
+            kw["yuv_layout"] = render["yuv"]
         key, make, given = identity(faces, V, **kw), (lambda: RenderPlan(faces, V, device=dv, **kw)), None
     plan = cached_plan(at, "render", key, make, given)
     if plan.key != key:      # its view was changed (RenderPlan.set_view) after it was kept under this key
@@ -285,17 +287,21 @@ def _render_plan(render, faces, V, device):
 def _split_images(im):
     """A batched ImageFrames -> one per clip, each cut to its own frames ([1, L_out, H, W, 3])."""
     cut = lambda t, b, n: None if t is None else t[b:b + 1, :n]  # noqa: E731
-    return [type(im)(cut(im.images, b, n), cut(im.depth, b, n), cut(im.face_ids, b, n), [n]) for b, n in enumerate(im.frames)]
+    return [type(im)(cut(im.images, b, n), cut(im.depth, b, n), cut(im.face_ids, b, n), [n], cut(im.alpha, b, n), cut(im.yuv, b, n))
+            for b, n in enumerate(im.frames)]
 
 
 @torch.no_grad()
-def to_images(offsets, faces, render, template=None, frames=None, fps=None, normals=None, depth=None, face_ids=None, device=None):
+def to_images(offsets, faces, render, template=None, frames=None, fps=None, normals=None, depth=None, face_ids=None, device=None, alpha=None,
+              yuv=None):
     """Vertices (or vertex offsets with template=) -> render.ImageFrames: shaded uint8 frames [B, L_out, H, W, 3] of the mesh with the
     triangle list `faces` [F, 3], drawn on the device in ONE call (render.RenderPlan; include/fdm_hip.h, fdm_render_forward; DESIGN.md
     section 2 item 23 states every operation).  render: a render.RenderPlan, or the dict of its arguments after faces and V -- camera (a
     render.Camera or "vocaset" | "biwi" | "mead"), lights, ambient, base, background, chunk_frames, samples (1, 4 or 16 coverage samples
-    per pixel: anti-aliased frames) -- which may also carry depth=True
-    and face_ids=True for the depth [B, L_out, H, W] and face-id images.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with
+    per pixel: anti-aliased frames), yuv_matrix, yuv_range -- which may also carry depth=True
+    and face_ids=True for the depth [B, L_out, H, W] and face-id images, alpha=True for the coverage plane [B, L_out, H, W] uint8 and
+    yuv="i420" | "nv12" for each frame's Y'CbCr 4:2:0 planes [B, L_out, 3 W H / 2] uint8 (even W and H; with a RenderPlan yuv=True: the
+    layout is the plan's); without the last two the call is the one it was.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with
     frames = L per clip (None: all L); a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of ImageFrames, each cut to its own
     frames and bit for bit what its own call returns; or a mesh.MeshFrames (planar fp32): its positions, normals and frames are drawn
     as they are.  template: [1 or B, 3 V], or for a list one per clip.  fps = (fps_in, fps_out): the positions are resampled by
@@ -304,6 +310,8 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
     opts = render if isinstance(render, dict) else {}
     depth = bool(opts.get("depth", False)) if depth is None else depth
     face_ids = bool(opts.get("face_ids", False)) if face_ids is None else face_ids
+    alpha = bool(opts.get("alpha", False)) if alpha is None else alpha
+    yuv = bool(opts.get("yuv", False)) if yuv is None else bool(yuv)
     if isinstance(offsets, MeshFrames):
         mf = offsets
         if mf.positions.dtype != torch.float32 or mf.positions.shape[-1] != 3:
@@ -313,7 +321,7 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
     if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
         template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
     x, frames, many = _pack_offsets(offsets, frames, device, "to_images")
-    im = _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, depth, face_ids)
+    im = _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, depth, face_ids, alpha=alpha, yuv=yuv)
     return _split_images(im) if many else im
 
 
@@ -564,7 +572,8 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
 
     render (a render.RenderPlan or the dict of its arguments after faces and V: camera, lights, ambient, base, background,
-    chunk_frames; depth=True / face_ids=True for those images too): with faces= the call returns (render.ImageFrames, latent) in place
+    chunk_frames; depth=True / face_ids=True for those images too, alpha=True for the coverage plane, yuv="i420" | "nv12" for the
+    4:2:0 planes with yuv_matrix / yuv_range, as to_images): with faces= the call returns (render.ImageFrames, latent) in place
     of the mesh.MeshFrames -- shaded uint8 frames [B, L_out, H, W, 3] of the mesh `faces`, drawn on the device (to_images) from the
     positions and normals the mesh hand-off would have returned; out_fps= is honoured; after flame= or wrap= the posed or wrapped mesh
     is drawn (faces= is then that mesh's triangle list).  faces= is required; mesh= is not read; with rig= the call returns
@@ -1227,8 +1236,8 @@ def add_wrap_arguments(ap):
 
 
 def add_render_arguments(ap):
-    """--render / --render_size / --render_samples / --background_black of the demo command lines (the device render hand-off,
-    to_images)."""
+    """--render / --render_size / --render_samples / --background_black / --render_alpha / --render_yuv (+ _matrix, _full) of the demo
+    command lines (the device render hand-off, to_images)."""
     ap.add_argument("--render", action="store_true",
                     help="build-added: also save <stem>_frames.npy, uint8 [1, L_out, N, N, 3]: the frames of <stem>.npy drawn on the device with the "
                          "reference's camera and light directions (needs --faces_file), and print the ffmpeg line that makes an .mp4 of them")
@@ -1236,20 +1245,49 @@ def add_render_arguments(ap):
     ap.add_argument("--render_samples", type=int, default=1, choices=(1, 4, 16),
                     help="build-added: coverage samples per pixel of the rendered frames, 4 or 16 for anti-aliased edges (with --render)")
     ap.add_argument("--background_black", action="store_true", help="a black background instead of white (with --render)")
+    ap.add_argument("--render_alpha", action="store_true",
+                    help="build-added: also save <stem>_alpha.npy, uint8 [1, L_out, N, N]: the coverage of every pixel; with --background_black "
+                         "the frames are premultiplied by it (with --render)")
+    ap.add_argument("--render_yuv", choices=("i420", "nv12"), default=None,
+                    help="build-added: also save the frames as Y'CbCr 4:2:0 made on the device, <stem>.y4m (i420) or raw <stem>.nv12, and print "
+                         "the ffmpeg line that encodes them without a colour conversion (with --render; N even)")
+    ap.add_argument("--render_yuv_matrix", type=int, default=709, choices=(601, 709), help="build-added: the matrix of --render_yuv (BT.601 or BT.709)")
+    ap.add_argument("--render_yuv_full", action="store_true", help="build-added: full-range --render_yuv (0 .. 255) instead of limited (16 .. 235)")
 
 
 def save_frames(a, p, verts, faces, dst):
-    """--render: verts [1, L_out, 3 V] -> <dst>_frames.npy and the ffmpeg line (not run: video encoding is not part of this project)."""
-    from .render import Camera
+    """--render: verts [1, L_out, 3 V] -> <dst>_frames.npy and the ffmpeg line (not run: video encoding is not part of this project);
+    --render_alpha: <dst>_alpha.npy; --render_yuv: <dst>.y4m or <dst>.nv12 and their ffmpeg line."""
+    from .render import Camera, write_y4m
     name = next((n for n in ("biwi", "mead") if n in p.name.lower()), "vocaset")
     N = int(a.render_size)
     bg = (0.0, 0.0, 0.0) if a.background_black else (1.0, 1.0, 1.0)
-    im = to_images(verts, faces, dict(camera=Camera.preset(name).resized(N, N), background=bg, samples=int(getattr(a, "render_samples", 1))))
+    view = dict(camera=Camera.preset(name).resized(N, N), background=bg, samples=int(getattr(a, "render_samples", 1)))
+    layout, full = getattr(a, "render_yuv", None), bool(getattr(a, "render_yuv_full", False))
+    if getattr(a, "render_alpha", False):
+        view["alpha"] = True
+    if layout:
+        view.update(yuv=layout, yuv_matrix=int(getattr(a, "render_yuv_matrix", 709)), yuv_range="full" if full else "limited")
+    im = to_images(verts, faces, view)
     np.save(dst + "_frames", im.images.detach().cpu().numpy())
     print(f"saved {dst}_frames.npy {tuple(im.images.shape)}")
     rate = a.out_fps or a.in_fps or p.fps or 30
     print(f"python -c \"import numpy as np, sys; sys.stdout.buffer.write(np.load('{dst}_frames.npy').tobytes())\" | "
           f"ffmpeg -f rawvideo -pix_fmt rgb24 -s {N}x{N} -r {rate:g} -i - -i {a.audio_file} -c:v libx264 -pix_fmt yuv420p -shortest {dst}.mp4")
+    if im.alpha is not None:
+        np.save(dst + "_alpha", im.alpha.detach().cpu().numpy())
+        print(f"saved {dst}_alpha.npy {tuple(im.alpha.shape)}")
+    if layout == "i420":
+        size = write_y4m(dst + ".y4m", im.yuv, im.frames, N, N, rate, full)
+        print(f"saved {dst}.y4m ({size} bytes)")
+        print(f"ffmpeg -i {dst}.y4m -i {a.audio_file} -c:v libx264 -pix_fmt yuv420p -shortest {dst}_yuv.mp4")
+    elif layout == "nv12":
+        with open(dst + ".nv12", "wb") as f:
+            f.write(im.yuv[0, :im.frames[0]].detach().cpu().numpy().tobytes())
+        print(f"saved {dst}.nv12 ({im.frames[0]} frames of {3 * N * N // 2} bytes)")
+        tags = f"-color_range {'pc' if full else 'tv'} -colorspace {'bt709' if view['yuv_matrix'] == 709 else 'smpte170m'}"
+        print(f"ffmpeg -f rawvideo -pix_fmt nv12 -s {N}x{N} -r {rate:g} {tags} -i {dst}.nv12 -i {a.audio_file} -c:v libx264 -pix_fmt yuv420p "
+              f"-shortest {dst}_yuv.mp4")
 
 
 def wrap_arguments(a, faces, template, device):

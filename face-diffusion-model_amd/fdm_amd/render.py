@@ -6,17 +6,20 @@ import ctypes as C
 import hashlib
 import math
 from collections import namedtuple
+from fractions import Fraction
 
 import numpy as np
 import torch
 
-from ._lib import FdmError, check, lib
+from ._lib import FdmError, RenderPlanes, check, lib
 from .handoff import HandoffPlan, fps_pair, frames_list, frames_out_max, offsets_batch
 from .mesh import faces_array
 
 # images [B, L_out_max, H, W, 3] uint8, depth [B, L_out_max, H, W] float32 or None (0 where no surface), face_ids [B, L_out_max, H, W] int32
 # or None (-1 where no surface), frames = L_out per clip (rows at or past it are zeros)
-ImageFrames = namedtuple("ImageFrames", "images depth face_ids frames")
+# alpha [B, L_out_max, H, W] uint8 or None (coverage: 255 n / S rounded, n of the pixel's S samples covered), yuv [B, L_out_max, 3 W H / 2]
+# uint8 or None (each frame's Y'CbCr 4:2:0 planes, I420 or NV12, as ffmpeg's rawvideo reads them)
+ImageFrames = namedtuple("ImageFrames", "images depth face_ids frames alpha yuv", defaults=(None, None))
 
 MAX_LIGHTS = 8
 REFERENCE_F = 4754.97941935      # render/render.py: the focal length at 800 x 800 is this over 2 (vocaset, MEAD) or over 8 (BIWI)
@@ -78,15 +81,55 @@ def sample_pattern(n):
     return xy
 
 
-def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1):
+YUV_RANGES = {"limited": 0, "full": 1}          # fdm_render_set "yuv_range"
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}            # fdm_render_set "yuv_layout"
+
+
+def yuv_coeffs(matrix, full_range):
+    """int32 [10] = {yr, yg, yb, ur, ug, ub, vr, vg, vb, y0}: the 16-bit fixed-point numbers of the RGB -> Y'CbCr conversion for matrix
+    601 or 709, limited or full range (fdm_render_yuv_coeffs_host; no device needed)."""
+    k = np.zeros(10, dtype=np.int32)
+    check(lib().fdm_render_yuv_coeffs_host(int(matrix), int(bool(full_range)), k.ctypes.data))
+    return k
+
+
+def write_y4m(path, yuv, frames, width, height, fps, full_range=False):
+    """One clip's I420 frames as a YUV4MPEG2 file (which ffmpeg, mpv and the encoders' own command lines read): yuv uint8
+    [L_out_max, 3 W H / 2] or [1, L_out_max, 3 W H / 2], a tensor or an array; frames: how many of them are live (an int, or the
+    ImageFrames.frames of one clip); fps: a number or (num, den); full_range: what the plan's yuv_range was.  The header is
+    `YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420jpeg XCOLORRANGE=FULL|LIMITED`, then `FRAME` and the frame's bytes per live frame.
+    NV12 has no Y4M form: save those bytes raw.  Returns the file's size in bytes."""
+    a = yuv.detach().cpu().numpy() if isinstance(yuv, torch.Tensor) else np.asarray(yuv)
+    W, H = int(width), int(height)
+    n = 3 * W * H // 2
+    if a.ndim == 3 and a.shape[0] == 1:
+        a = a[0]
+    L = int(frames[0] if isinstance(frames, (list, tuple)) else frames)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != n or W % 2 or H % 2 or not 0 <= L <= a.shape[0]:
+        raise FdmError(f"write_y4m takes one clip's uint8 [L_out_max >= {L}, {n}] I420 frames of an even {W} x {H}, got {a.dtype} {a.shape}")
+    num, den = (int(fps[0]), int(fps[1])) if isinstance(fps, (list, tuple)) else Fraction(fps).limit_denominator(1001).as_integer_ratio()
+    head = f"YUV4MPEG2 W{W} H{H} F{num}:{den} Ip A1:1 C420jpeg XCOLORRANGE={'FULL' if full_range else 'LIMITED'}\n".encode()
+    with open(path, "wb") as f:
+        f.write(head)
+        for t in range(L):
+            f.write(b"FRAME\n")
+            f.write(np.ascontiguousarray(a[t]).tobytes())
+    return len(head) + L * (6 + n)
+
+
+def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1, yuv_matrix=709,
+               yuv_range="limited", yuv_layout="i420"):
     ref = reference_lights()
     if isinstance(camera, str):
         camera = Camera.preset(camera)
     lt = ref["lights"] if lights is None else np.asarray(lights, dtype=np.float32).reshape(-1, 4)
     three = lambda x: np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), (3,)))  # noqa: E731
+    rng, lay = str(yuv_range).lower(), str(yuv_layout).lower()
+    if int(yuv_matrix) not in (601, 709) or rng not in YUV_RANGES or lay not in YUV_LAYOUTS:
+        raise FdmError(f"yuv_matrix = {yuv_matrix!r} (601 or 709), yuv_range = {yuv_range!r} (limited or full), yuv_layout = {yuv_layout!r} (i420 or nv12)")
     return dict(camera=camera, lights=np.ascontiguousarray(lt), ambient=float(ref["ambient"] if ambient is None else ambient),
                 base=three(ref["base"] if base is None else base), background=three(background), chunk_frames=int(chunk_frames),
-                samples=int(samples))
+                samples=int(samples), yuv_matrix=int(yuv_matrix), yuv_range=rng, yuv_layout=lay)
 
 
 def _view_key(a):
@@ -94,13 +137,14 @@ def _view_key(a):
     cam = a["camera"]
     for x in (cam.numbers(), cam.R, cam.t, a["lights"], a["base"], a["background"]):
         d.update(x.tobytes())
-    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], a["samples"], d.hexdigest())
+    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], a["samples"], a["yuv_matrix"], a["yuv_range"], a["yuv_layout"], d.hexdigest())
 
 
-def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1):
-    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view, the sample count among it)."""
+def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1, yuv_matrix=709,
+             yuv_range="limited", yuv_layout="i420"):
+    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view, the sample count and the yuv settings among it)."""
     return (int(V), hashlib.sha1(faces_array(faces).tobytes()).hexdigest()) + _view_key(_arguments(camera, lights, ambient, base, background, chunk_frames,
-                                                                                                    samples))
+                                                                                                    samples, yuv_matrix, yuv_range, yuv_layout))
 
 
 class RenderPlan(HandoffPlan):
@@ -108,17 +152,18 @@ class RenderPlan(HandoffPlan):
     Camera or a preset's name), lights [n <= 8, 4] = unit direction towards the light in camera space and intensity (None: the
     reference's five), ambient, base colour [3], background [3] in [0, 1] (white, as the reference's default), chunk_frames (0: scratch
     under 256 MB), samples (1, 4 or 16 coverage samples per pixel: anti-aliased frames; the scratch holds 8 W H
-    samples bytes per frame).  The faces are checked and uploaded here; forward() only passes pointers.  A plan holds one scratch: it serves one
+    samples bytes per frame), yuv_matrix (601 or 709), yuv_range ("limited" or "full") and yuv_layout ("i420" or "nv12") of the 4:2:0
+    planes that forward(yuv=True) writes.  The faces are checked and uploaded here; forward() only passes pointers.  A plan holds one scratch: it serves one
     stream at a time (pipeline.to_images keeps them per (device, stream, topology, view)).  Without a visible device the plan still
     validates and forward() raises."""
 
     _destroy = "fdm_render_destroy"
 
     def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1,
-                 device="cuda:0"):
+                 yuv_matrix=709, yuv_range="limited", yuv_layout="i420", device="cuda:0"):
         super().__init__(device)
         self.faces, self.V = faces_array(faces), int(V)
-        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames, samples)
+        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout)
         a = self.view
         cam = a["camera"]
         self.W, self.H = cam.width, cam.height
@@ -129,6 +174,8 @@ class RenderPlan(HandoffPlan):
             self.set_chunk_frames(a["chunk_frames"])
         if a["samples"] != 1:
             self.set_samples(a["samples"])
+        if (a["yuv_matrix"], a["yuv_range"], a["yuv_layout"]) != (709, "limited", "i420"):
+            self.set_yuv(a["yuv_matrix"], a["yuv_range"], a["yuv_layout"])
         self.key = identity(self.faces, self.V, **a)
 
     def arguments(self):
@@ -160,11 +207,31 @@ class RenderPlan(HandoffPlan):
         self.view = dict(self.view, samples=int(n))
         self.key = identity(self.faces, self.V, **self.view)
 
-    def forward(self, positions, frames=None, template=None, fps=None, normals=None, depth=False, face_ids=False, out=None):
+    def set_yuv(self, matrix=None, range=None, layout=None):  # noqa: A002 (the C key is "yuv_range")
+        """The 4:2:0 planes of forward(yuv=True): matrix 601 or 709, range "limited" or "full", layout "i420" or "nv12" (None: as it is;
+        fdm_render_set "yuv_matrix" / "yuv_range" / "yuv_layout").  The plan's key follows, as with set_samples."""
+        a = self.view
+        new = _arguments(a["camera"], yuv_matrix=a["yuv_matrix"] if matrix is None else matrix, yuv_range=a["yuv_range"] if range is None else range,
+                         yuv_layout=a["yuv_layout"] if layout is None else layout)
+        check(lib().fdm_render_set(self.h, b"yuv_matrix", new["yuv_matrix"]))
+        check(lib().fdm_render_set(self.h, b"yuv_range", YUV_RANGES[new["yuv_range"]]))
+        check(lib().fdm_render_set(self.h, b"yuv_layout", YUV_LAYOUTS[new["yuv_layout"]]))
+        self.view = dict(a, yuv_matrix=new["yuv_matrix"], yuv_range=new["yuv_range"], yuv_layout=new["yuv_layout"])
+        self.key = identity(self.faces, self.V, **self.view)
+
+    def forward(self, positions, frames=None, template=None, fps=None, normals=None, depth=False, face_ids=False, out=None, rgb=True,
+                alpha=False, yuv=False):
         """positions [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device -- vertices, or offsets with template [1 or B, 3 V] --, frames:
         L per clip (None: L_max), fps = (fps_in, fps_out) or None, normals [B, L_out_max, V, 3] fp32 (what to_mesh returns for the same
         frames; None: computed here by the same kernel) -> ImageFrames.  out: (images, depth, face_ids) tensors to write instead of
-        new ones (None where the call writes none); their second dimension is L_out_max."""
+        new ones (None where the call writes none); their second dimension is L_out_max.
+        rgb=False, alpha=True or yuv=True choose the planes form (fdm_render_forward_planes): images only with rgb, alpha
+        [B, L_out_max, H, W] uint8 coverage, yuv [B, L_out_max, 3 W H / 2] uint8 in the plan's matrix, range and layout (W and H even).
+        out may also be a dict keyed rgb / depth / face_ids / alpha / yuv: the call then writes exactly its tensors, whatever the flags
+        say.  With the defaults the call is fdm_render_forward as before."""
+        if isinstance(out, dict) or not rgb or alpha or yuv:
+            return self._forward_planes(positions, frames, template, fps, normals, out,
+                                        dict(rgb=rgb, depth=depth, face_ids=face_ids, alpha=alpha, yuv=yuv))
         dv = self.device
         x = offsets_batch(positions, self.V, dv)
         B, L_max = int(x.shape[0]), int(x.shape[1])
@@ -197,3 +264,55 @@ class RenderPlan(HandoffPlan):
                                            torch.cuda.current_stream(dv).cuda_stream))
         self._keep = (x, tp, nr)      # read asynchronously on this stream
         return ImageFrames(img, dep, ids, list(got))
+
+    _PLANES = ("rgb", "depth", "face_ids", "alpha", "yuv")
+
+    def _forward_planes(self, positions, frames, template, fps, normals, out, want):
+        """forward() through fdm_render_forward_planes.  want: which of _PLANES to make, into new tensors or those of the (images, depth,
+        face_ids) tuple `out`; a dict `out` names its own."""
+        dv = self.device
+        x = offsets_batch(positions, self.V, dv)
+        B, L_max = int(x.shape[0]), int(x.shape[1])
+        fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
+        tp, rows = None, 0
+        if template is not None:
+            tp = torch.as_tensor(template, dtype=torch.float32).to(dv).reshape(-1, 3 * self.V).contiguous()
+            rows = int(tp.shape[0])
+        H, W = self.H, self.W
+        spec = dict(rgb=(torch.uint8, (H, W, 3)), depth=(torch.float32, (H, W)), face_ids=(torch.int32, (H, W)), alpha=(torch.uint8, (H, W)),
+                    yuv=(torch.uint8, (3 * W * H // 2,)))
+        if isinstance(out, dict):
+            if set(out) - set(self._PLANES):
+                raise FdmError(f"out has the keys {sorted(out)}: the outputs are {', '.join(self._PLANES)}")
+            given = {k: t for k, t in out.items() if t is not None}
+            names = [k for k in self._PLANES if k in given]
+        else:
+            given = {} if out is None else {k: t for k, t in zip(self._PLANES, out) if t is not None}
+            names = [k for k in self._PLANES if want[k] or k in given]
+        if not names:
+            raise FdmError("the call makes no output: every one of rgb, depth, face_ids, alpha and yuv is off")
+        first = next(iter(given.values()), None)
+        Lo = frames_out_max(fr, fi, fo) if first is None else (int(first.shape[1]) if first.dim() >= 2 else 0)
+        t = {}
+        for k in names:
+            dt, shp = spec[k]
+            shp = (B, Lo) + shp
+            t[k] = given.get(k)
+            if t[k] is None:
+                t[k] = torch.empty(shp, dtype=dt, device=dv)
+            elif t[k].dtype != dt or t[k].device != dv or tuple(t[k].shape) != shp or not t[k].is_contiguous():
+                raise FdmError(f"out[{k!r}] must be a contiguous {dt} {list(shp)} tensor on {dv}, got {t[k].dtype} {tuple(t[k].shape)} on {t[k].device}")
+        nr = None
+        if normals is not None:
+            nr = normals.detach()
+            if nr.dtype != torch.float32 or nr.device != dv or nr.numel() != B * Lo * 3 * self.V or nr.shape[0] != B:
+                raise FdmError(f"normals must be float32 [{B}, {Lo}, {self.V}, 3] on {dv}, got {nr.dtype} {tuple(nr.shape)} on {nr.device}")
+            nr = nr.contiguous()
+        fa, got = (C.c_int * B)(*fr), (C.c_int * B)()
+        ptr = lambda a: None if a is None else a.data_ptr()  # noqa: E731
+        planes = RenderPlanes(ptr(t.get("rgb")), ptr(t.get("depth")), ptr(t.get("face_ids")), ptr(t.get("alpha")), ptr(t.get("yuv")))
+        with torch.cuda.device(dv):
+            check(lib().fdm_render_forward_planes(self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr), C.byref(planes), Lo, got,
+                                                  torch.cuda.current_stream(dv).cuda_stream))
+        self._keep = (x, tp, nr)      # read asynchronously on this stream
+        return ImageFrames(t.get("rgb"), t.get("depth"), t.get("face_ids"), list(got), t.get("alpha"), t.get("yuv"))

@@ -1182,12 +1182,45 @@ int fdm_wrap_destroy(fdm_wrap* w);
  *   they come from the maximum key over the pixel's samples -- the nearest sampled surface, among equal iw the lowest face index --,
  *   depth = 1 / iw of that key, face its face; 0 and -1 when no sample has a fragment.  The visibility buffer holds 8 W H S bytes per
  *   frame of a chunk, and the default chunk counts them.
- * Not built: textures, the metallic-roughness material, alpha / coverage output for compositing, clipping, YUV output, video encoding.
+ * Planes for compositing and video (fdm_render_forward_planes; fdm_render_forward and everything it writes are unchanged).  `out` names
+ *   any of rgb, depth, face (as above), alpha and yuv; a NULL member is not written, and rgb may be NULL too.  Every plane comes out of
+ *   the one resolve pass (the keys are cleared as they are read) and no rgb image is written to memory that the caller did not ask for.
+ *   alpha [B, L_out_max, H, W] uint8: with n the number of the pixel's S samples that have a fragment (the resolve's own test: a key
+ *     that is not 0 and names a face < F), alpha = (255 n + S / 2) / S in integers: 0 or 255 at S = 1; 0, 64, 128, 191, 255 at S = 4.
+ *     Alpha is coverage alone: it does not depend on shading, lights or background.  With background = (0, 0, 0) an uncovered sample adds
+ *     0 to the channel sums, so rgb is then premultiplied by this coverage and rgb + alpha over black is a premultiplied RGBA frame (no
+ *     new rgb mode is needed).  The one caveat: a sample whose shade is NaN takes the background's channel, as in step 5.
+ *   yuv [B, L_out_max, 3 W H / 2] uint8, 2-byte aligned, W and H both even (else FDM_ERR_ARG; alpha has no such limit): Y'CbCr 4:2:0,
+ *     each frame one contiguous block in the byte order of `ffmpeg -f rawvideo -pix_fmt yuv420p` (I420: Y [H][W], U [H/2][W/2],
+ *     V [H/2][W/2]) or `-pix_fmt nv12` (NV12: Y [H][W], then [H/2][W/2][2] interleaved U, V).  The planes are a function of the frame's
+ *     uint8 rgb as defined above (step 5 / the multi-sample resolve, after (int)(255 c + 0.5f)), whether or not rgb is stored.  All
+ *     arithmetic is 32-bit signed integers, >> an arithmetic shift (floor).  With the ten numbers of fdm_render_yuv_coeffs_host (no
+ *     device needed) {yr, yg, yb, ur, ug, ub, vr, vg, vb, y0}:
+ *       per pixel        Y = clamp(((yr R + yg G + yb B + 32768) >> 16) + y0, 0, 255);
+ *       per 2 x 2 block  Rs, Gs, Bs = the sums of its four uint8 values (0 .. 1020: the largest product sum is 6.7e7),
+ *                        U = clamp(((ur Rs + ug Gs + ub Bs + (1 << 17)) >> 18) + 128, 0, 255), V likewise with vr, vg, vb:
+ *       chroma sited at the block's centre (C420jpeg in Y4M terms).  Limited range stays in 16 .. 235 (Y) and 16 .. 240 (U, V) over all
+ *       2^24 colours; full range reaches 256 for pure blue or red before the clamp.
+ *     The numbers: (Kr, Kb) = (0.299, 0.114) for matrix 601, (0.2126, 0.0722) for 709; sy = 219 / 255 and sc = 224 / 255 for limited
+ *       range, both 1 for full range; q(x) = floor(65536 x + 0.5) in fp64; yr = q(Kr sy), yb = q(Kb sy), yg = q(sy) - yr - yb;
+ *       ub = q(sc / 2), ur = q(-Kr sc / (2 (1 - Kb))), ug = -(ur + ub); vr = q(sc / 2), vb = q(-Kb sc / (2 (1 - Kr))), vg = -(vr + vb);
+ *       y0 = 16 limited, 0 full.  The green terms follow from the other two, so white, black and every grey are exact.
+ *         601 limited  16829 33039 6416  -9714 -19070 28784  28784 -24103 -4681  16
+ *         601 full     19595 38470 7471 -11058 -21710 32768  32768 -27439 -5329   0
+ *         709 limited  11966 40254 4064  -6596 -22188 28784  28784 -26145 -2639  16
+ *         709 full     13933 46871 4732  -7509 -25259 32768  32768 -29763 -3005   0
+ *     fdm_render_set keys: "yuv_matrix" 601 or 709 (default 709), "yuv_range" 0 limited or 1 full (default 0), "yuv_layout" 0 I420 or
+ *       1 NV12 (default 0); any other value is FDM_ERR_ARG.
+ *   Rows at or past a clip's L_out are zero bytes in alpha and yuv as in every other output (zeros, not video black).  The call keeps
+ *   fdm_render_forward's checks, chunks, scratch and one-stream rule; a null `out`, or one whose five members are all null, is FDM_ERR_ARG.
+ * Not built: textures, the metallic-roughness material, clipping, 4:2:2 / 4:4:4 or 10-bit output, video encoding.
  * fdm_render_create validates without a device and fdm_render_forward then ends in FDM_ERR_STATE.  Every check is made before the first
  * launch: FDM_ERR_ARG (a null r / positions / rgb, tmpl_rows not 0, 1 or B, a null template with tmpl_rows > 0, frame rates not finite
  * or negative; at create and set_view: a null array, F or V < 1, a face index outside [0, V), W or H outside 1 .. 4096, more than 8
  * lights, a light direction that is not a unit vector, near >= far, anything not finite; in fdm_render_set an unknown key -- the keys
- * are chunk_frames and samples --, chunk_frames outside 0 .. 4096 or samples as above), FDM_ERR_SHAPE (B, L_max or L_out_max < 1, frames[b] outside [0, L_max], a clip whose L_out exceeds L_out_max).
+ * are chunk_frames, samples, yuv_matrix, yuv_range and yuv_layout --, chunk_frames outside 0 .. 4096, samples or a yuv_* value as
+ * above; in the planes form rgb may be null, and a null out, five null members, yuv with an odd W or H or an odd yuv address are
+ * refused), FDM_ERR_SHAPE (B, L_max or L_out_max < 1, frames[b] outside [0, L_max], a clip whose L_out exceeds L_out_max).
  * frames_out [B] HOST (or NULL) receives L_out per clip.  An object serves one stream at a time.  fdm_version() keeps its value: callers
  * detect the feature by the symbol.  Call times are unmeasured: profiles/render_out/README.md. */
 typedef struct fdm_render fdm_render;
@@ -1202,6 +1235,16 @@ int fdm_render_sample_pattern_host(int samples, int* xy);
 int fdm_render_forward(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows, double fps_in,
                        double fps_out, const float* normals /*or NULL*/, unsigned char* rgb, float* depth /*or NULL*/, int* face /*or NULL*/,
                        int L_out_max, int* frames_out, void* stream);
+/* The planes form (the paragraph "Planes for compositing and video" above).  Callers detect it by the symbol. */
+typedef struct fdm_render_planes {      /* any may be NULL, not all */
+  unsigned char* rgb; float* depth; int* face; unsigned char* alpha; unsigned char* yuv;
+} fdm_render_planes;
+int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+                              double fps_in, double fps_out, const float* normals /*or NULL*/, const fdm_render_planes* out, int L_out_max,
+                              int* frames_out, void* stream);
+/* {yr, yg, yb, ur, ug, ub, vr, vg, vb, y0} of matrix = 601 or 709 and full_range = 0 or not into coeffs [10] HOST ints (no device
+ * needed); FDM_ERR_ARG for any other matrix or a null coeffs. */
+int fdm_render_yuv_coeffs_host(int matrix, int full_range, int* coeffs /*[10]*/);
 int fdm_render_destroy(fdm_render* r);
 
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
