@@ -25,7 +25,7 @@ struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
   float *P = nullptr, *N = nullptr;       // device scratch of one chunk: [n][3V] each
   int4* xyw = nullptr;                    // [n][V]
   float4* nc = nullptr;                   // [n][V]
-  unsigned long long* vis = nullptr;      // [n][H][W][samples], zero between calls (the resolve kernels leave it so)
+  unsigned long long* vis = nullptr;      // [n][H][W][samples], zero between calls (the resolve kernel leaves it so)
   long long rowtab_cap = 0, P_cap = 0, N_cap = 0, xyw_cap = 0, nc_cap = 0, vis_cap = 0;
   std::vector<int2> rows;                 // host: the live rows of the call in flight (the asynchronous upload reads it)
   bool vis_dirty = false;                 // a call ended between raster and resolve: clear before the next use
@@ -189,24 +189,22 @@ int fdm_render_yuv_coeffs_host(int matrix, int full_range, int* coeffs) {
 
 namespace {
 
-template <int S> void launch_resolve_planes(bool yuv, dim3 grid, hipStream_t s, const fdm_render* r, const int2* tab, int L_out_max,
-                                            const RenderOut& out, const RenderYuv& yc) {
-  if (yuv)
-    hipLaunchKernelGGL((render_resolve_planes_kernel<S, true>), grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
-  else
-    hipLaunchKernelGGL((render_resolve_planes_kernel<S, false>), grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                       (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
+// raster and resolve of a chunk of n rows at S samples per pixel; with yuv one resolve lane per 2 x 2 block of pixels
+template <int S> void launch_raster_resolve(const fdm_render* r, int n, const int2* tab, int L_out_max, const RenderOut& out, const RenderYuv& yc,
+                                            hipStream_t s) {
+  const auto blocks = [](long long lanes) { return (unsigned)((lanes + RENDER_TB - 1) / RENDER_TB); };
+  const long long WH = (long long)r->W * r->H;
+  hipLaunchKernelGGL(render_raster_kernel<S>, dim3(blocks(r->F), (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
+                     r->V, r->W, r->H, r->vis);
+  const auto resolve = out.yuv ? render_resolve_kernel<S, true> : render_resolve_kernel<S, false>;
+  hipLaunchKernelGGL(resolve, dim3(blocks(out.yuv ? WH / 4 : WH), (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
+                     (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
 }
 
-// The body of fdm_render_forward (planes = false: the resolve kernels as they stand, out.rgb set, alpha and yuv null) and of
-// fdm_render_forward_planes (planes = true: render_resolve_planes_kernel writes whichever outputs are not null).  r, positions and the
-// outputs have been checked by the caller.
+// The body of fdm_render_forward (out.rgb set, alpha and yuv null) and of fdm_render_forward_planes: render_resolve_kernel writes
+// whichever outputs are not null.  r, positions and the outputs have been checked by the caller.
 int render_run(const char* who, fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
-               double fps_in, double fps_out, const float* normals, const RenderOut& out, bool planes, int L_out_max, int* frames_out, void* stream) {
-  unsigned char* const rgb = out.rgb;
-  float* const depth = out.depth;
-  int* const face = out.face;
+               double fps_in, double fps_out, const float* normals, const RenderOut& out, int L_out_max, int* frames_out, void* stream) {
   if (tmpl_rows != 0 && tmpl_rows != 1 && tmpl_rows != B) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d (0, 1 or B = %d)", who, tmpl_rows, B);
   if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d with a null template", who, tmpl_rows);
   FCK(check_fps(who, fps_in, fps_out));
@@ -221,9 +219,7 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
   RenderYuv yc;
   std::memset(&yc, 0, sizeof(yc));
   if (out.yuv) {
-    int k[10];
-    FCK(fdm_render_yuv_coeffs_host(r->yuv_matrix, r->yuv_range, k));
-    yc.yr = k[0]; yc.yg = k[1]; yc.yb = k[2]; yc.ur = k[3]; yc.ug = k[4]; yc.ub = k[5]; yc.vr = k[6]; yc.vg = k[7]; yc.vb = k[8]; yc.y0 = k[9];
+    FCK(fdm_render_yuv_coeffs_host(r->yuv_matrix, r->yuv_range, yc.k));
     yc.nv12 = r->yuv_layout;
   }
   FCK(handoff_device(*r, who));
@@ -252,17 +248,16 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
   for (int b = 0; b < B; ++b) {
     const long long lo = hl[2 * b + 1], n = (L_out_max - lo) * WH, at = ((long long)b * L_out_max + lo) * WH;
     if (!n) continue;
-    if (rgb) HIPCK(hipMemsetAsync(rgb + 3 * at, 0, (size_t)(3 * n), s));
-    if (depth) HIPCK(hipMemsetAsync(depth + at, 0, (size_t)n * sizeof(float), s));
-    if (face) HIPCK(hipMemsetAsync(face + at, 0, (size_t)n * sizeof(int), s));
+    if (out.rgb) HIPCK(hipMemsetAsync(out.rgb + 3 * at, 0, (size_t)(3 * n), s));
+    if (out.depth) HIPCK(hipMemsetAsync(out.depth + at, 0, (size_t)n * sizeof(float), s));
+    if (out.face) HIPCK(hipMemsetAsync(out.face + at, 0, (size_t)n * sizeof(int), s));
     if (out.alpha) HIPCK(hipMemsetAsync(out.alpha + at, 0, (size_t)n, s));
     if (out.yuv) HIPCK(hipMemsetAsync(out.yuv + at + at / 2, 0, (size_t)(n + n / 2), s));      // (W H is a multiple of 4 here)
   }
   const int rs = resamples(fps_in, fps_out) ? 1 : 0, tstride = tmpl_rows == B && B > 1 ? (int)V3 : 0;
   const float* tp = tmpl_rows ? tmpl : nullptr;
-  const unsigned vblocks = (unsigned)((r->V + RENDER_TB - 1) / RENDER_TB), fblocks = (unsigned)((r->F + RENDER_TB - 1) / RENDER_TB);
-  const unsigned pblocks = (unsigned)((WH + RENDER_TB - 1) / RENDER_TB);
-  const unsigned qblocks = (unsigned)((WH / 4 + RENDER_TB - 1) / RENDER_TB);      // 2 x 2 blocks of pixels (with yuv)
+  const unsigned vblocks = (unsigned)((r->V + RENDER_TB - 1) / RENDER_TB);
+  const auto raster_resolve = r->samples == 1 ? launch_raster_resolve<1> : r->samples == 4 ? launch_raster_resolve<4> : launch_raster_resolve<16>;
   for (long long r0 = 0; r0 < live; r0 += chunk) {
     const int n = (int)std::min(chunk, live - r0);
     const int2* tab = r->rowtab + r0;
@@ -275,37 +270,7 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
     hipLaunchKernelGGL(render_vertex_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const float*)r->P, normals ? normals : (const float*)r->N,
                        normals ? tab : (const int2*)nullptr, L_out_max, r->V, r->view, r->xyw, r->nc);
     r->vis_dirty = true;
-    if (planes) {
-      const dim3 grid(out.yuv ? qblocks : pblocks, (unsigned)n);
-      if (r->samples == 1) {
-        hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
-                           r->W, r->H, r->vis);
-        launch_resolve_planes<1>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
-      } else if (r->samples == 4) {
-        hipLaunchKernelGGL(render_raster_aa_kernel<4>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
-                           r->V, r->W, r->H, r->vis);
-        launch_resolve_planes<4>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
-      } else {
-        hipLaunchKernelGGL(render_raster_aa_kernel<16>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
-                           r->V, r->W, r->H, r->vis);
-        launch_resolve_planes<16>(out.yuv != nullptr, grid, s, r, tab, L_out_max, out, yc);
-      }
-    } else if (r->samples == 1) {
-      hipLaunchKernelGGL(render_raster_kernel, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F, r->V,
-                         r->W, r->H, r->vis);
-      hipLaunchKernelGGL(render_resolve_kernel, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
-    } else if (r->samples == 4) {
-      hipLaunchKernelGGL(render_raster_aa_kernel<4>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
-                         r->V, r->W, r->H, r->vis);
-      hipLaunchKernelGGL(render_resolve_aa_kernel<4>, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
-    } else {
-      hipLaunchKernelGGL(render_raster_aa_kernel<16>, dim3(fblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
-                         r->V, r->W, r->H, r->vis);
-      hipLaunchKernelGGL(render_resolve_aa_kernel<16>, dim3(pblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                         (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, rgb, depth, face);
-    }
+    raster_resolve(r, n, tab, L_out_max, out, yc, s);
     HIPCK(hipGetLastError());
     r->vis_dirty = false;
   }
@@ -322,8 +287,7 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
                        void* stream) {
   if (!r || !positions || !rgb) return fail(FDM_ERR_ARG, "render_forward: null argument");
   const RenderOut out = {rgb, depth, face, nullptr, nullptr};
-  return render_run("render_forward", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, false, L_out_max, frames_out,
-                    stream);
+  return render_run("render_forward", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, L_out_max, frames_out, stream);
 }
 
 int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
@@ -335,8 +299,8 @@ int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* 
   if (out.yuv && ((r->W | r->H) & 1))
     return fail(FDM_ERR_ARG, "render_forward_planes: yuv 4:2:0 needs an even width and height, the viewport is %d x %d", r->W, r->H);
   if (out.yuv && ((size_t)out.yuv & 1)) return fail(FDM_ERR_ARG, "render_forward_planes: yuv must be 2-byte aligned");
-  return render_run("render_forward_planes", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, true, L_out_max,
-                    frames_out, stream);
+  return render_run("render_forward_planes", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, L_out_max, frames_out,
+                    stream);
 }
 
 }  // extern "C"

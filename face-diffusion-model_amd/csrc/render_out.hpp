@@ -7,28 +7,24 @@
 //                          (render_out.hip calls the mesh hand-off on these positions) unless the caller brings them.
 //   render_vertex_kernel   one lane per (chunk row, vertex): camera transform, projection, snapping to 8 sub-pixel bits, the `bad` test and
 //                          the camera-space normal; two 16-byte records per vertex.
-//   render_raster_kernel   one lane per (chunk row, face): setup (drop, int64 area, orientation) and the clamped box.  A box of at most
-//                          RENDER_LANE_BOX pixels is walked by its own lane; a larger one is handed to the whole wavefront (the lanes that
-//                          hold one are taken in turn by ballot, the triangle travels by shuffles, the 64 lanes take the box's pixels 64
-//                          apart).  Every covered pixel's key goes into the visibility buffer with a 64-bit atomicMax (a vector global
-//                          atomic): a maximum, so the buffer does not depend on the order the triangles arrive in.
-//   render_resolve_kernel  one lane per (chunk row, pixel): reads the key and writes 0 back (the buffer is clear for the next chunk),
-//                          recomputes the winning face's fragment, interpolates the normal, shades, writes rgb / depth / face.
-// With S = 4 or 16 samples per pixel (fdm_render_set "samples") the last two are replaced by
-//   render_raster_aa_kernel<S>   the same lane per (chunk row, face) over a visibility buffer [n][H][W][S], the samples of a pixel
-//                          adjacent.  The work items of a box are its (pixel, sample) pairs in that order, so the 64 lanes of the
-//                          wavefront issue their atomicMax on 512 contiguous bytes of a pixel row.  Every box is handed to the
-//                          whole wavefront: there is no per-lane walk here (profiles/render_out/README.md says why).
-//   render_resolve_aa_kernel<S>  one lane per (chunk row, pixel): reads and clears the pixel's 8 S contiguous bytes 16 at a time, shades
-//                          every sample that has a fragment (a triangle's setup and normals are kept while consecutive samples name
-//                          the same face), sums the channels in sample order, scales by 1 / S; depth and face from the largest key.
-// S = 1 launches render_raster_kernel and render_resolve_kernel as they stand.
-// The per-pixel work of the two resolve kernels is one device function each (render_resolve_pixel, render_resolve_aa_pixel<S>: a pixel ->
-// three 8-bit channels, the largest key, the count of covered samples).  fdm_render_forward_planes replaces the resolve kernel by
-//   render_resolve_planes_kernel<S, YUV>   the same functions; writes any of rgb / depth / face / alpha (coverage count -> 8 bits) and,
-//                          with YUV, the frame's Y'CbCr 4:2:0 planes (I420 or NV12) from the 8-bit rgb, one lane per 2 x 2 block of
-//                          pixels.  The keys are cleared as they are read, so every plane comes out of this one pass and no rgb image
-//                          is written that the caller did not ask for.
+//   render_raster_kernel<S>   S = 1, 4 or 16 samples per pixel (fdm_render_set "samples").  One lane per (chunk row, face): setup (drop,
+//                          int64 area, orientation) and the clamped box of pixels that have a sample inside the triangle's box.  The
+//                          visibility buffer is [n][H][W][S], the samples of a pixel adjacent.  A box is handed to the whole wavefront:
+//                          the lanes that hold one are taken in turn by ballot, the triangle travels by shuffles, and the 64 lanes take
+//                          the box's (pixel, sample) items 64 apart in that order, so at S > 1 one atomicMax wave-instruction covers 512
+//                          contiguous bytes of a pixel row.  At S = 1 alone a box of at most RENDER_LANE_BOX pixels is walked by its own
+//                          lane instead; at S > 1 there is no per-lane walk (profiles/render_out/README.md says why).  Every covered
+//                          sample's key goes into the buffer with a 64-bit atomicMax (a vector global atomic): a maximum, so the buffer
+//                          does not depend on the order the triangles arrive in.
+//   render_resolve_kernel<S, YUV>   the per-pixel work is one device function, render_pixel<S>: reads the pixel's 8 S contiguous bytes
+//                          of keys (16 at a time at S > 1) and writes 0 back (the buffer is clear for the next chunk), shades every
+//                          sample that has a fragment (a triangle's setup and normals are kept while consecutive samples name the same
+//                          face), sums the channels in sample order, scales by 1 / S -> three 8-bit channels, the largest key, the count
+//                          of covered samples.  The kernel writes whichever of rgb / depth / face / alpha (coverage count -> 8 bits) the
+//                          call asks for, one lane per (chunk row, pixel); with YUV also the frame's Y'CbCr 4:2:0 planes (I420 or NV12)
+//                          from the 8-bit rgb, one lane per 2 x 2 block of pixels.  The keys are cleared as they are read, so every
+//                          plane comes out of this one pass and no rgb image is written that the caller did not ask for.
+//                          fdm_render_forward is the call with alpha and yuv null.
 // No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -158,9 +154,6 @@ __device__ __forceinline__ bool render_fragment_at(const RenderTri& T, int px, i
   iw = __fadd_rn(__fadd_rn(__fmul_rn(l0, T.w0), __fmul_rn(l1, T.w1)), __fmul_rn(l2, T.w2));
   return in0 && in1 && in2;
 }
-__device__ __forceinline__ bool render_fragment(const RenderTri& T, int x, int y, float& l0, float& l1, float& l2, float& iw) {
-  return render_fragment_at(T, 256 * x + 128, 256 * y + 128, l0, l1, l2, iw);      // the pixel centre
-}
 // the fragment of `face` at (px, py), if there is one, into the key at `slot`
 __device__ __forceinline__ void render_hit_at(const RenderTri& T, int px, int py, int face, unsigned long long* slot) {
   float l0, l1, l2, iw;
@@ -169,48 +162,65 @@ __device__ __forceinline__ void render_hit_at(const RenderTri& T, int px, int py
   const unsigned long long key = ((unsigned long long)__float_as_uint(iw) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)face);
   atomicMax(slot, key);
 }
-__device__ __forceinline__ void render_hit(const RenderTri& T, int x, int y, int face, int W, unsigned long long* vis) {
-  render_hit_at(T, 256 * x + 128, 256 * y + 128, face, vis + (size_t)y * W + x);
+// the pixels p0 .. p1 of one axis that have a sample of render_sample_offset<S> inside lo .. hi (snapped), clamped to 0 .. n - 1
+template <int S> __device__ __forceinline__ void render_box(int lo, int hi, int n, int& p0, int& p1) {
+  constexpr int O_LO = S == 1 ? 128 : 32, O_HI = S == 1 ? 128 : 224;      // the least and the largest offset of the pattern
+  p0 = max((lo + 255 - O_HI) >> 8, 0);        // the first p with 256 p + O_HI >= lo
+  p1 = min((hi - O_LO) >> 8, n - 1);          // the last p with 256 p + O_LO <= hi
+}
+// lane src's triangle, for every lane of the wavefront (A from the coordinates; swapped and ok do not travel: a box exists only if ok)
+__device__ __forceinline__ RenderTri render_tri_of_lane(const RenderTri& T, int src) {
+  RenderTri Q = {};
+  Q.X0 = __shfl(T.X0, src); Q.Y0 = __shfl(T.Y0, src); Q.X1 = __shfl(T.X1, src); Q.Y1 = __shfl(T.Y1, src);
+  Q.X2 = __shfl(T.X2, src); Q.Y2 = __shfl(T.Y2, src);
+  Q.w0 = __shfl(T.w0, src); Q.w1 = __shfl(T.w1, src); Q.w2 = __shfl(T.w2, src);
+  Q.A = (long long)(Q.X1 - Q.X0) * (Q.Y2 - Q.Y0) - (long long)(Q.Y1 - Q.Y0) * (Q.X2 - Q.X0);
+  return Q;
 }
 
-// xyw: [n][V]; faces [F][3]; vis: [n][H][W] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
+// xyw: [n][V]; faces [F][3]; vis: [n][H][W][S] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
+template <int S>
 __global__ __launch_bounds__(RENDER_TB) void render_raster_kernel(const int4* xyw, const int* faces, int F, int V, int W, int H,
                                                                   unsigned long long* vis) {
+  static_assert(S == 1 || S == 4 || S == 16, "the sample patterns of render_sample_offset");
   const int row = blockIdx.y, f = blockIdx.x * RENDER_TB + threadIdx.x;
   const int4* rec = xyw + (size_t)row * V;
-  unsigned long long* img = vis + (size_t)row * W * H;
+  unsigned long long* img = vis + (size_t)row * W * H * S;
   RenderTri T = {};
   int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
   if (f < F) {
     const int* fv = faces + 3 * (size_t)f;
     T = render_setup(rec[fv[0]], rec[fv[1]], rec[fv[2]]);
-    if (T.ok) {      // pixels whose centre 256 x + 128 lies inside the triangle's box, clamped to the viewport
-      x0 = max((min(T.X0, min(T.X1, T.X2)) + 127) >> 8, 0);
-      x1 = min((max(T.X0, max(T.X1, T.X2)) - 128) >> 8, W - 1);
-      y0 = max((min(T.Y0, min(T.Y1, T.Y2)) + 127) >> 8, 0);
-      y1 = min((max(T.Y0, max(T.Y1, T.Y2)) - 128) >> 8, H - 1);
+    if (T.ok) {      // pixels with a sample inside the triangle's box, clamped to the viewport
+      render_box<S>(min(T.X0, min(T.X1, T.X2)), max(T.X0, max(T.X1, T.X2)), W, x0, x1);
+      render_box<S>(min(T.Y0, min(T.Y1, T.Y2)), max(T.Y0, max(T.Y1, T.Y2)), H, y0, y1);
     }
   }
   const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-  const int npix = (bw > 0 && bh > 0) ? bw * bh : 0;      // <= W H <= 2^24
-  if (npix > 0 && npix <= RENDER_LANE_BOX)
-    for (int y = y0; y <= y1; ++y)
-      for (int x = x0; x <= x1; ++x) render_hit(T, x, y, f, W, img);
-  // the large boxes of this wavefront, one after the other, by all 64 lanes (every lane of the wavefront comes here)
+  const int nitem = (bw > 0 && bh > 0) ? bw * bh * S : 0;      // <= W H S <= 2^26 (fdm_render_set)
+  bool wide = nitem > 0;                  // at S > 1 every box goes to the wavefront (profiles/render_out/README.md)
+  if constexpr (S == 1) {                 // a small box is walked by its own lane: one atomicMax per trip, not unrolled
+    wide = nitem > RENDER_LANE_BOX;
+    if (nitem > 0 && !wide)
+      for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) render_hit_at(T, 256 * x + 128, 256 * y + 128, f, img + (size_t)y * W + x);
+  }
+  // the wide boxes of this wavefront, one after the other, by all 64 lanes (every lane of the wavefront comes here): item i is sample
+  // i % S of the box's pixel i / S, so the lanes' keys lie next to each other along a pixel row
   const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(npix > RENDER_LANE_BOX);
+  unsigned long long todo = __ballot(wide);
   while (todo) {
     const int src = __ffsll((long long)todo) - 1;
     todo &= todo - 1;
-    RenderTri S;
-    S.X0 = __shfl(T.X0, src); S.Y0 = __shfl(T.Y0, src); S.X1 = __shfl(T.X1, src); S.Y1 = __shfl(T.Y1, src);
-    S.X2 = __shfl(T.X2, src); S.Y2 = __shfl(T.Y2, src);
-    S.w0 = __shfl(T.w0, src); S.w1 = __shfl(T.w1, src); S.w2 = __shfl(T.w2, src);
-    S.A = (long long)(S.X1 - S.X0) * (S.Y2 - S.Y0) - (long long)(S.Y1 - S.Y0) * (S.X2 - S.X0);
-    const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), sbw = __shfl(bw, src), sn = __shfl(npix, src), sf = __shfl(f, src);
+    const RenderTri Q = render_tri_of_lane(T, src);
+    const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), sbw = __shfl(bw, src), sn = __shfl(nitem, src), sf = __shfl(f, src);
     for (int i = lane; i < sn; i += 64) {
-      const int dy = i / sbw;
-      render_hit(S, sx0 + (i - dy * sbw), sy0 + dy, sf, W, img);
+      const int pix = i / S, s = i - pix * S;
+      const int dy = pix / sbw;
+      const int x = sx0 + (pix - dy * sbw), y = sy0 + dy;
+      int ox, oy;
+      render_sample_offset<S>(s, ox, oy);
+      render_hit_at(Q, 256 * x + ox, 256 * y + oy, sf, img + ((size_t)y * W + x) * S + s);
     }
   }
 }
@@ -240,12 +250,6 @@ __device__ __forceinline__ float render_shade(const RenderTri& T, const float4& 
   return k;
 }
 
-__device__ __forceinline__ unsigned char render_u8(float c, float bg) {      // c: base_c k, or the background's channel itself
-  if (c != c) c = bg;
-  c = c < 1.f ? c : 1.f;
-  return (unsigned char)(int)__fadd_rn(__fmul_rn(255.f, c), 0.5f);
-}
-
 // What the resolve of one pixel gives: the three 8-bit channels, the largest key over the pixel's samples (0: no fragment) and n, the
 // number of its samples that have a fragment.  depth, face and alpha follow from best and n.
 struct RenderPixel {
@@ -260,99 +264,16 @@ __device__ __forceinline__ int render_key_face(unsigned long long best) {
   return best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
 }
 
-// Step 5 for the pixel (x, y) of the chunk's row whose vertex records start at r0 = row V: reads the key at `slot` and writes 0 back
-// (the buffer is clear for the next chunk), recomputes the winning face's fragment, interpolates the normal, shades.
-__device__ __forceinline__ RenderPixel render_resolve_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int x, int y,
-                                                            const RenderView& vw, unsigned long long* slot) {
-  const unsigned long long key = *slot;
-  *slot = 0ull;
-  float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2];
-  RenderPixel p;
-  p.n = 0; p.best = 0ull;
-  const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-  if (key && won < (unsigned)F) {         // (a key names a face of the list: the raster kernel wrote it)
-    const int* fv = faces + 3 * (size_t)won;
-    const RenderTri T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
-    const float4 n0 = nc[r0 + fv[0]], n1 = nc[r0 + fv[T.swapped ? 2 : 1]], n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
-    float l0, l1, l2, iw;
-    (void)render_fragment(T, x, y, l0, l1, l2, iw);
-    const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
-    cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
-    p.n = 1; p.best = key;                // (the recomputed iw has the key's bits: the same expressions on the same integers)
-  }
-  p.r = render_u8(cr, vw.background[0]); p.g = render_u8(cg, vw.background[1]); p.b = render_u8(cb, vw.background[2]);
-  return p;
-}
-
-// rgb / depth / face: the call's outputs [B][Lo_max][H][W](3); depth and face may be null.  grid (blocks of RENDER_TB pixels, chunk rows).
-__global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
-                                                                   const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
-                                                                   unsigned char* rgb, float* depth, int* face) {
-  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
-  if (i >= W * H) return;
-  const int2 bt = rowtab[row];
-  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
-  const int y = i / W, x = i - y * W;
-  const RenderPixel p = render_resolve_pixel(xyw, nc, faces, F, (size_t)row * V, x, y, vw, vis + (size_t)row * W * H + i);
-  unsigned char* px = rgb + 3 * o;
-  px[0] = p.r; px[1] = p.g; px[2] = p.b;
-  if (depth) depth[o] = render_key_depth(p.best);
-  if (face) face[o] = render_key_face(p.best);
-}
-
-// ---- S = 4 or 16 samples per pixel
-// xyw: [n][V]; faces [F][3]; vis: [n][H][W][S] keys (0 = no fragment).  grid (blocks of RENDER_TB faces, chunk rows).
+// Step 5 for the pixel (x, y) of the chunk's row whose vertex records start at r0 = row V and whose keys start at img: reads the
+// pixel's 8 S contiguous bytes of keys (S = 1: one 8-byte load; S > 1: 16 bytes at a time) and writes 0 back (the buffer is clear for
+// the next chunk); per sample recomputes the winning face's fragment, interpolates the normal, shades; sums the channels in sample
+// order, scales by 1 / S.  At S = 1 the sum is the one sample's colour and the scale is 1.
 template <int S>
-__global__ __launch_bounds__(RENDER_TB) void render_raster_aa_kernel(const int4* xyw, const int* faces, int F, int V, int W, int H,
-                                                                     unsigned long long* vis) {
-  static_assert(S == 4 || S == 16, "the sample patterns of render_sample_offset");
-  const int row = blockIdx.y, f = blockIdx.x * RENDER_TB + threadIdx.x;
-  const int4* rec = xyw + (size_t)row * V;
-  unsigned long long* img = vis + (size_t)row * W * H * S;
-  RenderTri T = {};
-  int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-  if (f < F) {
-    const int* fv = faces + 3 * (size_t)f;
-    T = render_setup(rec[fv[0]], rec[fv[1]], rec[fv[2]]);
-    if (T.ok) {      // pixels with a sample inside the triangle's box (the offsets lie in 32 .. 224), clamped to the viewport
-      x0 = max((min(T.X0, min(T.X1, T.X2)) + 31) >> 8, 0);
-      x1 = min((max(T.X0, max(T.X1, T.X2)) - 32) >> 8, W - 1);
-      y0 = max((min(T.Y0, min(T.Y1, T.Y2)) + 31) >> 8, 0);
-      y1 = min((max(T.Y0, max(T.Y1, T.Y2)) - 32) >> 8, H - 1);
-    }
-  }
-  const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-  const int nitem = (bw > 0 && bh > 0) ? bw * bh * S : 0;      // <= W H S <= 2^26 (fdm_render_set)
-  // the boxes of this wavefront, one after the other, by all 64 lanes (every lane of the wavefront comes here): item i is sample
-  // i % S of the box's pixel i / S, so the lanes' keys lie next to each other along a pixel row
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(nitem > 0);
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    RenderTri Q;
-    Q.X0 = __shfl(T.X0, src); Q.Y0 = __shfl(T.Y0, src); Q.X1 = __shfl(T.X1, src); Q.Y1 = __shfl(T.Y1, src);
-    Q.X2 = __shfl(T.X2, src); Q.Y2 = __shfl(T.Y2, src);
-    Q.w0 = __shfl(T.w0, src); Q.w1 = __shfl(T.w1, src); Q.w2 = __shfl(T.w2, src);
-    Q.A = (long long)(Q.X1 - Q.X0) * (Q.Y2 - Q.Y0) - (long long)(Q.Y1 - Q.Y0) * (Q.X2 - Q.X0);
-    const int sx0 = __shfl(x0, src), sy0 = __shfl(y0, src), sbw = __shfl(bw, src), sn = __shfl(nitem, src), sf = __shfl(f, src);
-    for (int i = lane; i < sn; i += 64) {
-      const int pix = i / S, s = i - pix * S;
-      const int dy = pix / sbw;
-      const int x = sx0 + (pix - dy * sbw), y = sy0 + dy;
-      int ox, oy;
-      render_sample_offset<S>(s, ox, oy);
-      render_hit_at(Q, 256 * x + ox, 256 * y + oy, sf, img + ((size_t)y * W + x) * S + s);
-    }
-  }
-}
-
-// The resolve of the pixel (x, y) at S = 4 or 16: reads and clears the pixel's 8 S contiguous bytes at `slot` 16 at a time, shades every
-// sample that has a fragment, sums the channels in sample order, scales by 1 / S.
-template <int S>
-__device__ __forceinline__ RenderPixel render_resolve_aa_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int x, int y,
-                                                               const RenderView& vw, ulonglong2* slot) {
-  static_assert(S == 4 || S == 16, "the sample patterns of render_sample_offset");
+__device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int W, int x, int y,
+                                                    const RenderView& vw, unsigned long long* img) {
+  static_assert(S == 1 || S == 4 || S == 16, "the sample patterns of render_sample_offset");
+  constexpr int PER = S == 1 ? 1 : 2;     // keys per load
+  unsigned long long* slot = img + ((size_t)y * W + x) * S;      // 8 S bytes, at S > 1 16-byte aligned
   float ar = 0.f, ag = 0.f, ab = 0.f;
   RenderPixel p;
   p.n = 0; p.best = 0ull;
@@ -360,17 +281,24 @@ __device__ __forceinline__ RenderPixel render_resolve_aa_pixel(const int4* xyw, 
   RenderTri T = {};
   float4 n0 = {}, n1 = {}, n2 = {};
 #pragma unroll 1
-  for (int h = 0; h < S / 2; ++h) {
-    const ulonglong2 two = slot[h];
-    slot[h] = make_ulonglong2(0ull, 0ull);
+  for (int h = 0; h < S / PER; ++h) {
+    ulonglong2 two = make_ulonglong2(0ull, 0ull);
+    if constexpr (S == 1) {
+      two.x = *slot;
+      *slot = 0ull;
+    } else {
+      ulonglong2* pair = reinterpret_cast<ulonglong2*>(slot) + h;
+      two = *pair;
+      *pair = make_ulonglong2(0ull, 0ull);
+    }
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
+    for (int e = 0; e < PER; ++e) {
       const unsigned long long key = e ? two.y : two.x;
-      const int s = 2 * h + e;
+      const int s = PER * h + e;
       float cr = vw.background[0], cg = vw.background[1], cb = vw.background[2];
       const unsigned won = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
       if (key && won < (unsigned)F) {     // (a key names a face of the list: the raster kernel wrote it)
-        if (won != held) {
+        if (S == 1 || won != held) {
           const int* fv = faces + 3 * (size_t)won;
           T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
           n0 = nc[r0 + fv[0]]; n1 = nc[r0 + fv[T.swapped ? 2 : 1]]; n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
@@ -378,7 +306,7 @@ __device__ __forceinline__ RenderPixel render_resolve_aa_pixel(const int4* xyw, 
         }
         int ox, oy;
         render_sample_offset<S>(s, ox, oy);
-        float l0, l1, l2, iw;
+        float l0, l1, l2, iw;             // (the recomputed iw has the key's bits: the same expressions on the same integers)
         (void)render_fragment_at(T, 256 * x + ox, 256 * y + oy, l0, l1, l2, iw);
         const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
         cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
@@ -399,42 +327,15 @@ __device__ __forceinline__ RenderPixel render_resolve_aa_pixel(const int4* xyw, 
   return p;
 }
 
-// rgb / depth / face as render_resolve_kernel; vis [n][H][W][S].  grid (blocks of RENDER_TB pixels, chunk rows).
-template <int S>
-__global__ __launch_bounds__(RENDER_TB) void render_resolve_aa_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
-                                                                      const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
-                                                                      unsigned char* rgb, float* depth, int* face) {
-  const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
-  if (i >= W * H) return;
-  const int2 bt = rowtab[row];
-  const size_t o = ((size_t)bt.x * Lo_max + bt.y) * W * H + i;
-  ulonglong2* slot = reinterpret_cast<ulonglong2*>(vis + ((size_t)row * W * H + i) * S);      // 8 S bytes, 16-byte aligned
-  const int y = i / W, x = i - y * W;
-  const RenderPixel p = render_resolve_aa_pixel<S>(xyw, nc, faces, F, (size_t)row * V, x, y, vw, slot);
-  unsigned char* px = rgb + 3 * o;
-  px[0] = p.r; px[1] = p.g; px[2] = p.b;
-  if (depth) depth[o] = render_key_depth(p.best);
-  if (face) face[o] = render_key_face(p.best);
-}
-
-// ---- the planes form of resolve (fdm_render_forward_planes): any of rgb / depth / face / alpha / yuv from the one pass over vis
 struct RenderOut {                        // kernel argument (by value): the call's outputs, null where it writes none
   unsigned char* rgb; float* depth; int* face; unsigned char* alpha; unsigned char* yuv;
 };
-struct RenderYuv {                        // kernel argument (by value): fdm_render_yuv_coeffs_host's ten numbers and the layout
-  int yr, yg, yb, ur, ug, ub, vr, vg, vb, y0;
+struct RenderYuv {                        // kernel argument (by value)
+  int k[10];                              // fdm_render_yuv_coeffs_host's {yr, yg, yb, ur, ug, ub, vr, vg, vb, y0}
   int nv12;
 };
 __host__ __device__ __forceinline__ int render_clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
-// the pixel (x, y) at any S: one of the two functions above on the pixel's keys
-template <int S>
-__device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int W, int x, int y,
-                                                    const RenderView& vw, unsigned long long* img) {
-  unsigned long long* slot = img + ((size_t)y * W + x) * S;
-  if constexpr (S == 1) return render_resolve_pixel(xyw, nc, faces, F, r0, x, y, vw, slot);
-  else return render_resolve_aa_pixel<S>(xyw, nc, faces, F, r0, x, y, vw, reinterpret_cast<ulonglong2*>(slot));
-}
 // rgb / depth / face / alpha of the pixel at o = (output frame) W H + y W + x, where asked for
 __device__ __forceinline__ void render_store_pixel(const RenderOut& out, size_t o, const RenderPixel& p, int S) {
   if (out.rgb) { unsigned char* px = out.rgb + 3 * o; px[0] = p.r; px[1] = p.g; px[2] = p.b; }
@@ -443,15 +344,16 @@ __device__ __forceinline__ void render_store_pixel(const RenderOut& out, size_t 
   if (out.alpha) out.alpha[o] = (unsigned char)((255 * p.n + S / 2) / S);
 }
 
-// YUV = false: one lane per (chunk row, pixel), as the resolve kernels, plus the alpha store.  grid (blocks of RENDER_TB pixels, rows).
+// out: the call's outputs [B][Lo_max][H][W](3), any of them null.
+// YUV = false: one lane per (chunk row, pixel).  grid (blocks of RENDER_TB pixels, chunk rows).
 // YUV = true (W and H even): one lane per (chunk row, 2 x 2 block of pixels).  The lane resolves its four pixels one after the other
 // (not unrolled: the registers of one pixel, three channel sums and one luma byte stay live), stores each row's two luma bytes in one
 // 2-byte store -- the 64 lanes of a wavefront write 128 contiguous bytes of a luma row -- and the block's chroma once (NV12: one
 // 2-byte store).  yuv: [B][Lo_max][3 W H / 2], 2-byte aligned.  grid (blocks of RENDER_TB blocks of pixels, chunk rows).
 template <int S, bool YUV>
-__global__ __launch_bounds__(RENDER_TB) void render_resolve_planes_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W,
-                                                                          int H, const int2* rowtab, int Lo_max, const RenderView vw,
-                                                                          unsigned long long* vis, const RenderOut out, const RenderYuv yc) {
+__global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
+                                                                   const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
+                                                                   const RenderOut out, const RenderYuv yc) {
   const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
   const size_t WH = (size_t)W * H, r0 = (size_t)row * V;
   unsigned long long* img = vis + (size_t)row * WH * S;
@@ -468,6 +370,7 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_planes_kernel(const 
     const size_t frame = (size_t)bt.x * Lo_max + bt.y;
     const int by = i / W2, bx = i - by * W2;
     unsigned char* Yp = out.yuv + frame * (WH + WH / 2);
+    const int* k = yc.k;
     int Rs = 0, Gs = 0, Bs = 0, left = 0;
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
@@ -476,12 +379,12 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_planes_kernel(const 
       render_store_pixel(out, frame * WH + (size_t)y * W + x, p, S);
       const int R = p.r, G = p.g, B = p.b;
       Rs += R; Gs += G; Bs += B;
-      const int luma = render_clamp_u8(((yc.yr * R + yc.yg * G + yc.yb * B + 32768) >> 16) + yc.y0);
+      const int luma = render_clamp_u8(((k[0] * R + k[1] * G + k[2] * B + 32768) >> 16) + k[9]);
       if (q & 1) *reinterpret_cast<uchar2*>(Yp + (size_t)y * W + 2 * bx) = make_uchar2((unsigned char)left, (unsigned char)luma);
       else left = luma;
     }
-    const unsigned char U = (unsigned char)render_clamp_u8(((yc.ur * Rs + yc.ug * Gs + yc.ub * Bs + (1 << 17)) >> 18) + 128);
-    const unsigned char Vv = (unsigned char)render_clamp_u8(((yc.vr * Rs + yc.vg * Gs + yc.vb * Bs + (1 << 17)) >> 18) + 128);
+    const unsigned char U = (unsigned char)render_clamp_u8(((k[3] * Rs + k[4] * Gs + k[5] * Bs + (1 << 17)) >> 18) + 128);
+    const unsigned char Vv = (unsigned char)render_clamp_u8(((k[6] * Rs + k[7] * Gs + k[8] * Bs + (1 << 17)) >> 18) + 128);
     unsigned char* Cp = Yp + WH;
     if (yc.nv12) {
       *reinterpret_cast<uchar2*>(Cp + 2 * (size_t)i) = make_uchar2(U, Vv);

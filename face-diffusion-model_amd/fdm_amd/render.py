@@ -158,6 +158,7 @@ class RenderPlan(HandoffPlan):
     validates and forward() raises."""
 
     _destroy = "fdm_render_destroy"
+    _PLANES = ("rgb", "depth", "face_ids", "alpha", "yuv")
 
     def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1,
                  yuv_matrix=709, yuv_range="limited", yuv_layout="i420", device="cuda:0"):
@@ -228,48 +229,8 @@ class RenderPlan(HandoffPlan):
         rgb=False, alpha=True or yuv=True choose the planes form (fdm_render_forward_planes): images only with rgb, alpha
         [B, L_out_max, H, W] uint8 coverage, yuv [B, L_out_max, 3 W H / 2] uint8 in the plan's matrix, range and layout (W and H even).
         out may also be a dict keyed rgb / depth / face_ids / alpha / yuv: the call then writes exactly its tensors, whatever the flags
-        say.  With the defaults the call is fdm_render_forward as before."""
-        if isinstance(out, dict) or not rgb or alpha or yuv:
-            return self._forward_planes(positions, frames, template, fps, normals, out,
-                                        dict(rgb=rgb, depth=depth, face_ids=face_ids, alpha=alpha, yuv=yuv))
-        dv = self.device
-        x = offsets_batch(positions, self.V, dv)
-        B, L_max = int(x.shape[0]), int(x.shape[1])
-        fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
-        tp, rows = None, 0
-        if template is not None:
-            tp = torch.as_tensor(template, dtype=torch.float32).to(dv).reshape(-1, 3 * self.V).contiguous()
-            rows = int(tp.shape[0])
-        if out is None:
-            Lo = frames_out_max(fr, fi, fo)
-            img = torch.empty(B, Lo, self.H, self.W, 3, dtype=torch.uint8, device=dv)
-            dep = torch.empty(B, Lo, self.H, self.W, dtype=torch.float32, device=dv) if depth else None
-            ids = torch.empty(B, Lo, self.H, self.W, dtype=torch.int32, device=dv) if face_ids else None
-        else:
-            img, dep, ids = out
-            Lo = int(img.shape[1]) if img.dim() == 5 else 0
-            for t, dt, shp in ((img, torch.uint8, (B, Lo, self.H, self.W, 3)), (dep, torch.float32, (B, Lo, self.H, self.W)), (ids, torch.int32, (B, Lo, self.H, self.W))):
-                if t is not None and (t.dtype != dt or t.device != dv or tuple(t.shape) != shp or not t.is_contiguous()):
-                    raise FdmError(f"out must be contiguous {dt} {list(shp)} tensors on {dv}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        nr = None
-        if normals is not None:
-            nr = normals.detach()
-            if nr.dtype != torch.float32 or nr.device != dv or nr.numel() != B * Lo * 3 * self.V or nr.shape[0] != B:
-                raise FdmError(f"normals must be float32 [{B}, {Lo}, {self.V}, 3] on {dv}, got {nr.dtype} {tuple(nr.shape)} on {nr.device}")
-            nr = nr.contiguous()
-        fa, got = (C.c_int * B)(*fr), (C.c_int * B)()
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(dv):
-            check(lib().fdm_render_forward(self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr), img.data_ptr(), ptr(dep), ptr(ids), Lo, got,
-                                           torch.cuda.current_stream(dv).cuda_stream))
-        self._keep = (x, tp, nr)      # read asynchronously on this stream
-        return ImageFrames(img, dep, ids, list(got))
-
-    _PLANES = ("rgb", "depth", "face_ids", "alpha", "yuv")
-
-    def _forward_planes(self, positions, frames, template, fps, normals, out, want):
-        """forward() through fdm_render_forward_planes.  want: which of _PLANES to make, into new tensors or those of the (images, depth,
-        face_ids) tuple `out`; a dict `out` names its own."""
+        say.  A call that makes rgb and neither alpha nor yuv, without a dict, is fdm_render_forward as before."""
+        want = dict(rgb=rgb, depth=depth, face_ids=face_ids, alpha=alpha, yuv=yuv)
         dv = self.device
         x = offsets_batch(positions, self.V, dv)
         B, L_max = int(x.shape[0]), int(x.shape[1])
@@ -310,9 +271,13 @@ class RenderPlan(HandoffPlan):
             nr = nr.contiguous()
         fa, got = (C.c_int * B)(*fr), (C.c_int * B)()
         ptr = lambda a: None if a is None else a.data_ptr()  # noqa: E731
-        planes = RenderPlanes(ptr(t.get("rgb")), ptr(t.get("depth")), ptr(t.get("face_ids")), ptr(t.get("alpha")), ptr(t.get("yuv")))
+        p = [ptr(t.get(k)) for k in self._PLANES]
+        head = (self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr))
         with torch.cuda.device(dv):
-            check(lib().fdm_render_forward_planes(self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr), C.byref(planes), Lo, got,
-                                                  torch.cuda.current_stream(dv).cuda_stream))
+            tail = (Lo, got, torch.cuda.current_stream(dv).cuda_stream)
+            if not isinstance(out, dict) and "rgb" in t and "alpha" not in t and "yuv" not in t:
+                check(lib().fdm_render_forward(*head, *p[:3], *tail))
+            else:
+                check(lib().fdm_render_forward_planes(*head, C.byref(RenderPlanes(*p)), *tail))
         self._keep = (x, tp, nr)      # read asynchronously on this stream
         return ImageFrames(t.get("rgb"), t.get("depth"), t.get("face_ids"), list(got), t.get("alpha"), t.get("yuv"))

@@ -1,5 +1,5 @@
 """MI355X: the render hand-off at 4 and 16 coverage samples per pixel (fdm_render_set "samples"; csrc/render_out.hpp,
-render_raster_aa_kernel / render_resolve_aa_kernel) -- rgb, depth and face-id images equal to the numpy restatement of
+render_raster_kernel<S> / render_resolve_kernel<S, YUV>) -- rgb, depth and face-id images equal to the numpy restatement of
 tests/render_aa_cases.py on every element (the anti-aliasing paragraph), on the smallest shapes that can go
 wrong: viewports whose W H is no multiple of the block and whose W is odd, sub-pixel slivers, boxes of one pixel and of the whole
 view, a triangle larger than the view, face counts around the block size, chunks, ragged batches, one plan switched between sample

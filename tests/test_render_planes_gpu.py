@@ -1,4 +1,4 @@
-"""MI355X: the planes of the render hand-off (fdm_render_forward_planes; csrc/render_out.hpp, render_resolve_planes_kernel) -- rgb,
+"""MI355X: the planes of the render hand-off (fdm_render_forward_planes; csrc/render_out.hpp, render_resolve_kernel<S, YUV>) -- rgb,
 depth and face equal to fdm_render_forward on the same inputs, alpha equal to the numpy restatement from the per-sample coverage, the
 4:2:0 planes equal byte for byte to the restatement applied to the call's own rgb (tests/render_planes_cases.py; DESIGN.md section 2
 item 24), on the smallest shapes that can go wrong: one chroma sample, a chroma grid that no block of lanes divides, a partial last
@@ -157,7 +157,7 @@ def test_odd_sizes_refuse_yuv_and_still_give_alpha():
     assert np.array_equal(got.alpha.cpu().numpy()[0, 0], want_alpha) and got.yuv is None and got.images is not None and got.depth is None
 
 
-@pytest.mark.parametrize("S", [1, 4])
+@pytest.mark.parametrize("S", SAMPLES)
 def test_every_subset_of_the_outputs(S):
     p, f, vw, _, _ = static_case("icosphere1", (34, 18), S)
     plan = plan_of(f, len(p), vw, samples=S, yuv_layout="nv12", yuv_matrix=601)
@@ -186,7 +186,7 @@ def clips_case(S):
     return x, tmpl, frames, fps, faces, V, vw, alphas
 
 
-@pytest.mark.parametrize("S", [1, 4])
+@pytest.mark.parametrize("S", SAMPLES)
 def test_ragged_clips_padding_and_chunks(S):
     x, tmpl, frames, fps, faces, V, vw, alphas = clips_case(S)
     plan = plan_of(faces, V, vw, samples=S)
