@@ -122,7 +122,7 @@ def _mesh_fps(p, in_fps, out_fps):
     return float(fi), float(out_fps)
 
 
-def _split_mesh(mf):
+def _split_mesh(mf, _=None):
     """A batched MeshFrames -> one per clip, each cut to its own frames ([1, L_out, V, 3 or 6])."""
     return [type(mf)(mf.positions[b:b + 1, :n], None if mf.normals is None else mf.normals[b:b + 1, :n], [n]) for b, n in enumerate(mf.frames)]
 
@@ -146,6 +146,17 @@ def _pack_offsets(offsets, frames, device, who):
     return x.to(dv), frames, many
 
 
+def _per_clip(who, offsets, frames, template, device, forward, split):
+    """What to_mesh, to_rig, to_wrap and to_images share: a list of templates that comes with a ragged list of clips is stacked into
+    rows, the offsets are packed (_pack_offsets, in the name of `who`), forward(x, frames, template) is the ONE device call, and for a
+    list split(result, frames in) cuts the batch's result into one per clip."""
+    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
+        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
+    x, frames, many = _pack_offsets(offsets, frames, device, who)
+    res = forward(x, frames, template)
+    return split(res, frames) if many else res
+
+
 @torch.no_grad()
 def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, interleaved=False, half=False, device=None):
     """Vertex offsets (what the decoder writes; or vertices, with template=None) -> mesh.MeshFrames: positions = offsets + template,
@@ -154,25 +165,24 @@ def to_mesh(offsets, faces, template=None, frames=None, fps=None, normals=True, 
     offsets: a device tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip (None: all L) -> one MeshFrames for the batch; or a
     ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of MeshFrames, each cut to its own frames and bit for bit what its
     own call returns.  template: [1 or B, 3 V], or for a list one per clip.  normals / interleaved / half: the output options."""
-    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
-        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
-    x, frames, many = _pack_offsets(offsets, frames, device, "to_mesh")
-    mf = _mesh_plan(faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, interleaved, half)
-    return _split_mesh(mf) if many else mf
+    return _per_clip("to_mesh", offsets, frames, template, device, lambda x, fr, tp: _mesh_plan(faces, x.shape[-1] // 3, x.device).forward(
+        x, fr, tp, fps, normals, interleaved, half), _split_mesh)
 
 
-def _rig_plan(rig, device):
-    """The rig hand-off plan of `device`, the current stream and this rig (rig.RigPlan.key).  rig: a rig.RigPlan (used as it is where
-    it was made for this device and stream, made again from its arguments otherwise) or the dict of RigPlan's arguments (every call
-    then digests the basis to recognise it: animate_many, animate_long and SlotServer come here once and go on with the plan)."""
-    from .rig import RigPlan, identity
+def _bound_plan(kind, given, device):
+    """The "rig" or "wrap" hand-off plan of `device`, the current stream and this rig or binding (RigPlan.key / WrapPlan.key).  given: a
+    rig.RigPlan / wrap.WrapPlan (used as it is where it was made for this device and stream, made again from its arguments -- a
+    binding it found included -- otherwise) or the dict of its arguments (every call then digests the arrays to recognise them:
+    animate_many, animate_long and SlotServer come here once, in _Outputs, and go on with the plan)."""
+    from . import rig, wrap
+    mod, cls = {"rig": (rig, rig.RigPlan), "wrap": (wrap, wrap.WrapPlan)}[kind]
     dv, at = _on_stream(device)
-    if isinstance(rig, RigPlan):
-        return cached_plan(at, "rig", rig.key, lambda: RigPlan(device=dv, **rig.arguments()), rig)
-    return cached_plan(at, "rig", identity(**rig), lambda: RigPlan(device=dv, **rig))
+    if isinstance(given, cls):
+        return cached_plan(at, kind, given.key, lambda: cls(device=dv, **given.arguments()), given)
+    return cached_plan(at, kind, mod.identity(**given), lambda: cls(device=dv, **given))
 
 
-def _split_rig(rf):
+def _split_rig(rf, _=None):
     """A batched RigFrames -> one per clip, each cut to its own frames ([1, L_out, K])."""
     return [type(rf)(rf.weights[b:b + 1, :n], [n], rf.names) for b, n in enumerate(rf.frames)]
 
@@ -190,11 +200,9 @@ def to_rig(offsets, basis, frames=None, fps=None, weights=None, ridge=0.0, bound
     together under a penalty on the change between neighbouring OUTPUT frames (rig.RigPlan): smooth
     curves that still respect the bounds, on the device.  A clip's result does not depend on the clips batched with it."""
     from .rig import RigPlan
-    x, frames, many = _pack_offsets(offsets, frames, device, "to_rig")
     rig = basis if isinstance(basis, (RigPlan, dict)) else dict(basis=basis, weights=weights, ridge=ridge, bounds=bounds, sweeps=sweeps, names=names,
                                                                 smooth=smooth, smooth_weights=smooth_weights)
-    rf = _rig_plan(rig, x.device).forward(x, frames, fps)
-    return _split_rig(rf) if many else rf
+    return _per_clip("to_rig", offsets, frames, None, device, lambda x, fr, _: _bound_plan("rig", rig, x.device).forward(x, fr, fps), _split_rig)
 
 
 def _flame_plan(model, device, landmarks=None):
@@ -227,18 +235,6 @@ def to_flame(pose, model, expression=None, shape=None, transl=None, extra=None, 
     return _flame_plan(model, device, landmarks).forward(pose, expression, shape, transl, extra, frames)
 
 
-def _wrap_plan(wrap, device):
-    """The wrap hand-off plan of `device`, the current stream and this binding (wrap.WrapPlan.key).  wrap: a wrap.WrapPlan (used as it is
-    where it was made for this device and stream, made again from its arguments -- the binding it found included -- otherwise) or the
-    dict of WrapPlan's arguments (every call then digests the meshes to recognise them: animate_many, animate_long and SlotServer come
-    here once and go on with the plan)."""
-    from .wrap import WrapPlan, identity
-    dv, at = _on_stream(device)
-    if isinstance(wrap, WrapPlan):
-        return cached_plan(at, "wrap", wrap.key, lambda: WrapPlan(device=dv, **wrap.arguments()), wrap)
-    return cached_plan(at, "wrap", identity(**wrap), lambda: WrapPlan(device=dv, **wrap))
-
-
 @torch.no_grad()
 def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device=None):
     """Vertex offsets of the model's topology (or vertices, with template=None) -> the vertices [B, L, 3 Vt] of a mesh of ANOTHER
@@ -249,11 +245,8 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
     the SOURCE, or for a list one per clip.  offsets_out: displacements from the target's rest position instead of positions -- a rig
     on the target's own blendshapes is to_rig(to_wrap(..., offsets_out=True), basis_t).  There is no frame-rate step here: resample
     AFTER, with to_mesh(wrapped, faces_t, None, fps=) or to_rig(..., fps=)."""
-    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
-        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
-    x, frames, many = _pack_offsets(offsets, frames, device, "to_wrap")
-    y = _wrap_plan(wrap, x.device).forward(x, frames, template, offsets_out)
-    return [y[b:b + 1, :n] for b, n in enumerate(frames)] if many else y
+    return _per_clip("to_wrap", offsets, frames, template, device, lambda x, fr, tp: _bound_plan("wrap", wrap, x.device).forward(x, fr, tp, offsets_out),
+                     lambda y, fr: [y[b:b + 1, :n] for b, n in enumerate(fr)])
 
 
 _RENDER_OUTPUTS = ("depth", "face_ids", "alpha", "yuv")      # keys of a render= dict that choose outputs, not the plan
@@ -284,7 +277,7 @@ def _render_plan(render, faces, V, device):
     return plan
 
 
-def _split_images(im):
+def _split_images(im, _=None):
     """A batched ImageFrames -> one per clip, each cut to its own frames ([1, L_out, H, W, 3])."""
     cut = lambda t, b, n: None if t is None else t[b:b + 1, :n]  # noqa: E731
     return [type(im)(cut(im.images, b, n), cut(im.depth, b, n), cut(im.face_ids, b, n), [n], cut(im.alpha, b, n), cut(im.yuv, b, n))
@@ -318,11 +311,8 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
             raise FdmError("to_images draws planar float32 MeshFrames (not interleaved, not half)")
         B, Lo, V = (int(n) for n in mf.positions.shape[:3])
         offsets, frames, normals = mf.positions.reshape(B, Lo, 3 * V), mf.frames, (mf.normals if normals is None else normals)
-    if isinstance(offsets, (list, tuple)) and isinstance(template, (list, tuple)):
-        template = torch.stack([torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in template])
-    x, frames, many = _pack_offsets(offsets, frames, device, "to_images")
-    im = _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(x, frames, template, fps, normals, depth, face_ids, alpha=alpha, yuv=yuv)
-    return _split_images(im) if many else im
+    return _per_clip("to_images", offsets, frames, template, device, lambda x, fr, tp: _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(
+        x, fr, tp, fps, normals, depth, face_ids, alpha=alpha, yuv=yuv), _split_images)
 
 
 def _flame_rows(x, L, R, what):
@@ -491,78 +481,97 @@ def _template_rows(template, width, device, S=1, B=1):
     return tp.repeat_interleave(S, dim=0) if (S > 1 and tp.shape[0] == B and B > 1) else tp
 
 
+def _padded_rows(rows, L):
+    """A per-frame flame= argument given per clip -> one batch [n, >= L, width], zeros past each clip's rows (never read)."""
+    rows = [torch.as_tensor(a, dtype=torch.float32).reshape(-1, torch.as_tensor(a).shape[-1]) for a in rows]
+    pad = torch.zeros(len(rows), max(L, max(int(r.shape[0]) for r in rows)), rows[0].shape[-1])
+    for b, r in enumerate(rows):
+        pad[b, :r.shape[0]] = r
+    return pad
+
+
+class _Outputs:
+    """What a call makes of its decoded offsets, resolved ONCE per animate / animate_many / animate_long call or per SlotServer from the
+    preset, the device and the eight output keywords: the combinations that return nothing are refused, a rig= / wrap= dict is
+    digested and made into its plan (_bound_plan: not per group, not per finished clip), and fps is (fps_in, fps_out) by _mesh_fps's
+    rule where faces= or rig= asks for a hand-off that reads it (fps=: the pair itself, from a caller that holds it).  Calling it is
+    the chain; `together` is the chain for the clips a SlotServer finishes in one step."""
+
+    def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None):
+        if render is not None and faces is None:
+            raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
+        if flame is not None:
+            _flame_check(flame)
+            if rig is not None and faces is None:
+                raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
+        if wrap is not None and rig is not None and faces is None:
+            raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
+        self.device, self.faces, self.mesh, self.flame, self.render = device, faces, dict(mesh or {}), flame, render
+        self.rig = None if rig is None else _bound_plan("rig", rig, device)
+        self.wrap = None if wrap is None else _bound_plan("wrap", wrap, device)
+        self.fps = fps or (_mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None)
+
+    def __call__(self, out, template=None, S=1, B=1, flame=None):
+        """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
+        template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair.
+        flame=: the offsets pose the model's head (_flame_posed) and the posed vertices stand where offsets + template stood (the
+        template argument is not read); rig= still fits the un-posed offsets; rig= without faces= returns no vertices, so flame= is
+        refused with it.  wrap=: the vertices of the bound mesh (to_wrap) stand where offsets + template stood -- after flame= they follow
+        the posed head; with faces= the mesh hand-off runs on them with no template, so `faces` is then the TARGET's triangle list and fps
+        applies there; rig= keeps fitting the model's own offsets (a rig on the target topology is to_rig(to_wrap(..., offsets_out=True),
+        basis_t)), and rig= without faces= is refused with it as with flame=.  render=: the render.ImageFrames of the mesh `faces` (to_images)
+        stand where its mesh.MeshFrames stood -- the template added, fps applied, the posed or wrapped vertices drawn; faces= is required
+        and mesh= is not read.
+        The ragged form: `out` a LIST of decoded clips [1, L_b, V3] with `template` None or one per clip -> a list with one result per
+        clip, from ONE rig, ONE head, ONE wrap and ONE mesh or render call over the unequal lengths, each result bit for bit its own
+        call's.  flame (this group's, in place of the call's): pose / expression / transl [L', n] for all clips or a list with one per clip."""
+        many, flame = isinstance(out, (list, tuple)), self.flame if flame is None else flame
+        fit = None if self.rig is None else to_rig(out, self.rig, fps=self.fps)                  # 1. the fit, on the offsets as decoded
+        if self.faces is None and fit is not None:
+            return fit
+        if flame is not None:                                                                    # 2. the head
+            frames = None
+            if many:     # one padded batch; an argument given per clip is padded with it
+                out, frames, _ = _pack_offsets(out, None, self.device, "to_flame")
+                flame = {k: _padded_rows(v, int(out.shape[1])) if (k in ("pose", "expression", "transl") and isinstance(v, (list, tuple))) else v
+                         for k, v in flame.items()}
+            out, template = _flame_posed(out, flame, self.device, frames, S, B), None
+            if many:
+                out = [out[b:b + 1, :n] for b, n in enumerate(frames)]
+        if template is not None and not many:      # (a list of templates goes on as it is: one per clip)
+            template = _template_rows(template, out.shape[-1], self.device, S, B)
+        if self.wrap is not None:                                                                # 3. the wrap
+            out, template = to_wrap(out, self.wrap, template, device=self.device), None
+        if self.faces is None:                                                                   # 4. the template, the mesh or the images
+            if template is None:
+                return out
+            return [c + _template_rows(t, c.shape[-1], self.device).unsqueeze(1) for c, t in zip(out, template)] if many else out + template.unsqueeze(1)
+        if self.render is None:
+            res = to_mesh(out, self.faces, template, fps=self.fps, **self.mesh)
+        else:
+            res = to_images(out, self.faces, self.render, template, fps=self.fps, device=self.device)
+        if fit is None:                                                                          # 5. with the fit
+            return res
+        return list(zip(res, fit)) if many else (res, fit)
+
+    def together(self, clips, templates):
+        """The chain for clips [1, L_b, V3] that were decoded together, `templates` holding one or None per clip -> one result per clip.
+        They share the ragged form's calls where there is a call to share; with no hand-off asked for, or with a mesh or a wrap that
+        reads templates and a template on some clips only, they go clip by clip."""
+        given, reads_templates = [t is not None for t in templates], self.faces is not None or self.wrap is not None
+        if (not reads_templates and self.rig is None) or (reads_templates and any(given) and not all(given)):
+            return [self(c.contiguous(), t) for c, t in zip(clips, templates)]
+        return self(clips, templates if given[0] else None)
+
+
 def _hand_off(out, template, device, faces=None, mesh=None, rig=None, fps=None, S=1, B=1, flame=None, wrap=None, render=None):
-    """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
-    template added there); with rig= the rig.RigFrames fitted to the offsets, never to the templated vertices; with both the pair.
-    flame=: the offsets pose the model's head (_flame_posed) and the posed vertices stand where offsets + template stood (the
-    template argument is not read); rig= still fits the un-posed offsets; rig= without faces= returns no vertices, so flame= is
-    refused with it.  wrap=: the vertices of the bound mesh (to_wrap) stand where offsets + template stood -- after flame= they follow
-    the posed head; with faces= the mesh hand-off runs on them with no template, so `faces` is then the TARGET's triangle list and fps
-    applies there; rig= keeps fitting the model's own offsets (a rig on the target topology is to_rig(to_wrap(..., offsets_out=True),
-    basis_t)), and rig= without faces= is refused with it as with flame=.  render=: the render.ImageFrames of the mesh `faces` (to_images)
-    stand where its mesh.MeshFrames stood -- the template added, fps applied, the posed or wrapped vertices drawn; faces= is required
-    and mesh= is not read."""
-    if render is not None and faces is None:
-        raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
-    if flame is not None:
-        _flame_check(flame)
-        if rig is not None and faces is None:
-            raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
-    if wrap is not None and rig is not None and faces is None:
-        raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
-    rf = None if rig is None else to_rig(out, rig, fps=fps)
-    if faces is None and rf is not None:
-        return rf
-    if flame is not None:
-        out, template = _flame_posed(out, flame, device, S=S, B=B), None
-    tp = None if template is None else _template_rows(template, out.shape[-1], device, S, B)
-    if wrap is not None:
-        out, tp = to_wrap(out, wrap, tp, device=device), None
-    if faces is None:
-        return out if tp is None else out + tp.unsqueeze(1)
-    mf = to_mesh(out, faces, tp, fps=fps, **(mesh or {})) if render is None else to_images(out, faces, render, tp, fps=fps, device=device)
-    return mf if rf is None else (mf, rf)
+    """The chain (_Outputs) for a batch, from a caller that holds fps = (fps_in, fps_out) or None itself."""
+    return _Outputs(None, device, faces, None, mesh, None, rig, flame, wrap, render, fps)(out, template, S, B)
 
 
 def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fps=None, flame=None, wrap=None, render=None):
-    """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip: ONE mesh call and ONE rig call
-    over the unequal lengths, each result bit for bit its own call's.  flame=: ONE ragged head call first (pose / expression /
-    transl [L', n] for all clips or a list with one per clip); its posed clips stand where offsets + template stood.  wrap=: ONE ragged
-    wrap call after that; the wrapped clips stand where offsets + template stood (as _hand_off).  render=: ONE ragged render call
-    in place of the mesh call (as _hand_off)."""
-    offsets = clips
-    if render is not None and faces is None:
-        raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
-    if wrap is not None and rig is not None and faces is None:
-        raise ValueError("wrap= with rig= and no faces=: the call would return the fit of the model's own offsets alone and never wrap anything")
-    if flame is not None:
-        _flame_check(flame)
-        if rig is not None and faces is None:
-            raise ValueError("flame= with rig= and no faces=: the call would return the fit of the un-posed offsets alone and never pose anything")
-        x, frames, _ = _pack_offsets(clips, None, device, "to_flame")
-        per = dict(flame)
-        for k in ("pose", "expression", "transl"):
-            v = flame.get(k)
-            if isinstance(v, (list, tuple)):      # one per clip: padded with zeros to the batch's length (rows past a clip's frames are never read)
-                rows = [torch.as_tensor(a, dtype=torch.float32).reshape(-1, torch.as_tensor(a).shape[-1]) for a in v]
-                pad = torch.zeros(len(rows), max(int(x.shape[1]), max(int(r.shape[0]) for r in rows)), rows[0].shape[-1])
-                for b, r in enumerate(rows):
-                    pad[b, :r.shape[0]] = r
-                per[k] = pad
-        posed = _flame_posed(x, per, device, frames)
-        clips, templates = [posed[b:b + 1, :n] for b, n in enumerate(frames)], None
-    if wrap is not None:
-        clips, templates = to_wrap(clips, wrap, templates, device=device), None
-    if faces is None and rig is None:
-        return clips if templates is None else [c + _template_rows(t, c.shape[-1], device).unsqueeze(1) for c, t in zip(clips, templates)]
-    if render is not None:
-        res = to_images(clips, faces, render, templates, fps=fps, device=device)
-    else:
-        res = None if faces is None else to_mesh(clips, faces, templates, fps=fps, **(mesh or {}))
-    if rig is not None:
-        fits = to_rig(offsets, rig, fps=fps)
-        res = fits if res is None else list(zip(res, fits))
-    return res
+    """_hand_off for a ragged list of decoded clips [1, L_b, V3] with templates None or one per clip."""
+    return _Outputs(None, device, faces, None, mesh, None, rig, flame, wrap, render, fps)(clips, templates)
 
 
 @torch.no_grad()
@@ -623,6 +632,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     row 0 only: the other conditions differ from their sequential calls by that stream -- equal in distribution (the reference's
     sequential calls draw from one running generator), not bit for bit."""
     model, p, _, _ = _unwrap(diffusion)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     # the default style is a row per clip; a style that was given counts with the rows it has
@@ -653,8 +663,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     key = _sampler_definition(p, ddim_steps, sampler, sampler_steps, eta)
     latent = _sample(diffusion, key, audio, shape, cond, x_T.repeat_interleave(S, dim=0) if S > 1 else x_T, seed, **trk)
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emotion_one_hot, et))
-    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, S, B, flame, wrap, render), latent
+    return outputs(out, template, S, B), latent
 
 
 @torch.no_grad()
@@ -702,8 +711,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     frames) or None per clip, or one track for all.  A group with a track in it is sampled and quantised with tracks throughout (a
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model, p, _, _ = _unwrap(diffusion)
-    rig = None if rig is None else _rig_plan(rig, device)        # a dict is digested and made into a plan once, not per group
-    wrap = None if wrap is None else _wrap_plan(wrap, device)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
     n = len(audios)
     wavs = _waveforms(audios, rate, device)
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
@@ -711,7 +719,6 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     else:
         hubs = [model.audio_encoder(w.reshape(1, -1)).last_hidden_state for w in wavs]             # [1, N_b, fw] each, own length
     Ls = [min(h.shape[1] // p.pair, p.max_len) for h in hubs]
-    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
 
     def row(x, b, width, default):
         """clip b's condition [1, width]: its entry of a list, its row of one [n, width] tensor, or the one row given for all"""
@@ -775,7 +782,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
             # the group's clips, each at its own length, through one mesh and one rig hand-off call
             tps = None if templates is None else [_per(templates, b) for b in grp]
             fl = None if flame is None else {k: ([v[b] for b in grp] if (k in ("pose", "expression", "transl") and isinstance(v, (list, tuple))) else v) for k, v in flame.items()}
-            for b, v in zip(grp, _hand_off_many(offs, tps, device, faces, mesh, rig, fps, fl, wrap, render)):
+            for b, v in zip(grp, outputs(offs, tps, flame=fl)):
                 verts[b] = v
     finally:
         model._hub_key, model._hub = prev
@@ -806,8 +813,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     wraps a ClassifierFreeSampleModel.  sampler / sampler_steps / eta: as animate() (the history of the multistep solver is the
     blended x0 in the long layout)."""
     model, p, cfg, scale = _unwrap(diffusion)
-    rig = None if rig is None else _rig_plan(rig, device)
-    wrap = None if wrap is None else _wrap_plan(wrap, device)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     style = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B, device)
@@ -823,8 +829,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     latent = plan.sample_windows(_start_noise((B, L_total * p.G, p.c), seed), seed=seed, cfg_scale=scale, **_sampler_args(key, diffusion))
     et = None if emotion_track is None else torch.as_tensor(emotion_track)[..., :L_total, :]
     out = autoencoder.decode(_quantise(autoencoder, p, latent, emo, et))
-    fps = _mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None
-    return _hand_off(out, template, device, faces, mesh, rig, fps, flame=flame, wrap=wrap, render=render), latent
+    return outputs(out, template), latent
 
 
 class SlotServer:
@@ -870,17 +875,12 @@ class SlotServer:
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
                  faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None):
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
-        if render is not None and faces is None:
-            raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
-        self.render = render
-        self.wrap = None if wrap is None else _wrap_plan(wrap, device)
-        self.faces, self.mesh = faces, dict(mesh or {})
-        self.rig = None if rig is None else _rig_plan(rig, device)     # a dict is digested and made into a plan once, not per finished clip
-        self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
-        self.batched_decodes = []                   # clips per batched decode, in call order
         self.model, p, self.cfg, self.scale = _unwrap(diffusion)
         self.p = p
-        self.mesh_fps = _mesh_fps(p, in_fps, out_fps) if faces is not None or rig is not None else None
+        self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render)     # once, not per finished clip
+        self.rig = self.outputs.rig
+        self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
+        self.batched_decodes = []                   # clips per batched decode, in call order
         self.n_slots = int(slots)
         self.L = min(int(max_frames), p.max_len) if max_frames else p.max_len
         self.plan = self.model.plan(device)
@@ -1098,15 +1098,10 @@ class SlotServer:
         self._fill()
         return fin
 
-    def _vertices(self, out, template):
-        """What results() yields for one decoded clip: offsets + template, or with faces= its mesh.MeshFrames, with rig= its
-        rig.RigFrames, with both the pair."""
-        return _hand_off(out, template, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap, render=self.render)
-
     def _finish_one(self, slots, lat, r):
         """One finished request: its latent quantised and decoded at its own length, the result kept for results(), its slots idle."""
         out = self.ae.decode(self._quant(lat, r))
-        self._done.append((r["handle"], self._vertices(out, r["template"]), lat))
+        self._done.append((r["handle"], self.outputs(out, r["template"]), lat))
         for s in slots:
             self._slot[s] = None
         return 1
@@ -1143,14 +1138,7 @@ class SlotServer:
             qs = _quantise(self.ae, p, pad, torch.cat([r["emo"] for r in reqs]) if p.n_emo else None)
         outs = self.ae.decode_many(qs, [r["L"] for r in reqs])
         self.batched_decodes.append(len(done))
-        clips, tps = [outs[i:i + 1, :r["L"]] for i, r in enumerate(reqs)], [r["template"] for r in reqs]
-        mixed = any(t is None for t in tps) and any(t is not None for t in tps)
-        if (self.faces is None and self.rig is None and self.wrap is None) or ((self.faces is not None or self.wrap is not None) and mixed):
-            # no hand-off call to share, or a mesh with a template on some requests only: clip by clip
-            res = [self._vertices(c.contiguous(), t) for c, t in zip(clips, tps)]
-        else:       # one mesh call and one rig call over the unequal lengths
-            res = _hand_off_many(clips, None if tps[0] is None else tps, self.device, self.faces, self.mesh, self.rig, self.mesh_fps, wrap=self.wrap,
-                                 render=self.render)
+        res = self.outputs.together([outs[i:i + 1, :r["L"]] for i, r in enumerate(reqs)], [r["template"] for r in reqs])
         for s, r, out, lat in zip(done, reqs, res, lats):
             self._done.append((r["handle"], out, lat))
             self._slot[s] = None

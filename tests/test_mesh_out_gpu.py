@@ -236,6 +236,23 @@ def test_animate_many_and_slot_server_with_faces_equal_to_mesh_of_the_default(ba
         assert torch.equal(meshes[h2].positions, ref.positions) and torch.equal(meshes[h2].normals, ref.normals)
 
 
+def test_slot_server_batched_decode_with_a_template_on_one_request_only():
+    """batch_stages: two requests finish in the same step() and share one decode; one has a template and one has none, so the mesh
+    hand-off takes them clip by clip, and each result is bit for bit its own animate(..., faces=) call's."""
+    diffusion, ae = tiny_models()
+    faces, V, _ = MC.mesh(PIPE_MESH)
+    wavs = [tiny_audio(0.6, 0), tiny_audio(0.4, 1)]
+    tmpls = [MC.template(PIPE_MESH, seed=20), None]
+    srv = pipeline.SlotServer(diffusion, ae, slots=2, max_frames=64, ddim_steps=2, device=DEV, batch_stages=True, faces=faces)
+    hs = srv.submit_many(wavs, tmpls, seeds=1)
+    meshes = {h: v for h, v, _ in srv.drain(2)}
+    assert srv.batched_decodes == [2]
+    for h, wav, tmpl in zip(hs, wavs, tmpls):
+        ref, _ = pipeline.animate(diffusion, ae, wav, tmpl, ddim_steps=2, seed=1, device=DEV, faces=faces)
+        assert isinstance(meshes[h], mesh.MeshFrames) and meshes[h].frames == ref.frames
+        assert torch.equal(meshes[h].positions, ref.positions) and torch.equal(meshes[h].normals, ref.normals)
+
+
 def test_demo_command_line_with_faces_file(tmp_path):
     """demo --faces_file --out_fps 60 --save_normals: <stem>.npy keeps the reference's name and [1, L_out, 3V] shape and holds
     to_mesh(animate(...)) at 60 fps, <stem>_normals.npy its normals (one command-line run: each one builds the models)."""
