@@ -99,6 +99,7 @@ int fdm_abi_struct_size(const char* name) {
   if (n == "fdm_pcm") return (int)sizeof(fdm_pcm);
   if (n == "fdm_flame_model") return (int)sizeof(fdm_flame_model);
   if (n == "fdm_render_planes") return (int)sizeof(fdm_render_planes);
+  if (n == "fdm_render_material") return (int)sizeof(fdm_render_material);
   return fdm::fail(FDM_ERR_ARG, "abi_struct_size: unknown struct '%s'", name);
 }
 

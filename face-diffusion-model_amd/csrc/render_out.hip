@@ -3,7 +3,8 @@
 // and keeps the view on the host (it travels to the kernels as an argument, so fdm_render_set_view touches no device memory); a forward
 // call validates (every check before the first launch), lists the live output frames, grows the scratch to one chunk of them and loops
 // over the chunks on the caller's stream.  The vertex normals are the mesh hand-off's own: an internal fdm_mesh over the same faces runs
-// mesh_nrm_kernel on each chunk's positions, unless the caller brings normals.
+// mesh_nrm_kernel on each chunk's positions, unless the caller brings normals.  A material (fdm_render_set_material, DESIGN item 25) is
+// state of the object: its tables are checked and uploaded at set, and a forward call then launches the MAT instance of the resolve kernel.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,6 +30,15 @@ struct fdm_render : fdm::Handoff {        // lens: {L, L_out} per clip
   long long rowtab_cap = 0, P_cap = 0, N_cap = 0, xyw_cap = 0, nc_cap = 0, vis_cap = 0;
   std::vector<int2> rows;                 // host: the live rows of the call in flight (the asynchronous upload reads it)
   bool vis_dirty = false;                 // a call ended between raster and resolve: clear before the next use
+  // the material (fdm_render_set_material): kind 0 and unlit 0 is none, and the call runs the MAT = false kernels
+  int mat_kind = 0, mat_unlit = 0, n_lut = 0, tex_w = 0, tex_h = 0, tex_filter = 0;
+  float mat_lo = 0.f, mat_span = 1.f;     // kind 2: span = hi - lo, rounded once
+  float* colors = nullptr;                // device [V][3]
+  float4* lut = nullptr;                  // device [n_lut] {r, g, b, 0}
+  float2* uv = nullptr;                   // device [F][3]
+  uchar4* tex = nullptr;                  // device [tex_h][tex_w] {r, g, b, 0}
+  float* u = nullptr;                     // device scratch of one chunk, kind 2: [n][V]
+  long long u_cap = 0;
 };
 
 namespace {
@@ -76,7 +86,7 @@ int check_view(const char* who, const float* camera, const float* R, const float
 }
 
 long long frame_bytes(const fdm_render& R) {
-  return (long long)R.V * (12 + 12 + 16 + 16) + (long long)R.W * R.H * R.samples * 8;
+  return (long long)R.V * (12 + 12 + 16 + 16 + (R.mat_kind == 2 ? 4 : 0)) + (long long)R.W * R.H * R.samples * 8;
 }
 
 template <int S> void sample_pattern(int* xy) {
@@ -196,15 +206,32 @@ template <int S> void launch_raster_resolve(const fdm_render* r, int n, const in
   const long long WH = (long long)r->W * r->H;
   hipLaunchKernelGGL(render_raster_kernel<S>, dim3(blocks(r->F), (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const int*)r->faces, r->F,
                      r->V, r->W, r->H, r->vis);
-  const auto resolve = out.yuv ? render_resolve_kernel<S, true> : render_resolve_kernel<S, false>;
-  hipLaunchKernelGGL(resolve, dim3(blocks(out.yuv ? WH / 4 : WH), (unsigned)n), dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc,
-                     (const int*)r->faces, r->F, r->V, r->W, r->H, tab, L_out_max, r->view, r->vis, out, yc);
+  const dim3 grid(blocks(out.yuv ? WH / 4 : WH), (unsigned)n);
+  if (!r->mat_kind && !r->mat_unlit) {    // no material: the kernels as they were
+    const auto resolve = out.yuv ? render_resolve_kernel<S, true, false> : render_resolve_kernel<S, false, false>;
+    hipLaunchKernelGGL(resolve, grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc, (const int*)r->faces, r->F, r->V, r->W, r->H,
+                       tab, L_out_max, r->view, r->vis, out, yc);
+    return;
+  }
+  RenderMat mt;
+  mt.kind = r->mat_kind; mt.unlit = r->mat_unlit;
+  mt.colors = r->colors; mt.u = r->u; mt.lut = r->lut; mt.n_lut = r->n_lut;
+  mt.uv = r->uv; mt.tex = reinterpret_cast<const unsigned*>(r->tex); mt.tex_w = r->tex_w; mt.tex_h = r->tex_h; mt.filter = r->tex_filter;
+  const auto resolve = out.yuv ? render_resolve_kernel<S, true, true, RenderMat> : render_resolve_kernel<S, false, true, RenderMat>;
+  hipLaunchKernelGGL(resolve, grid, dim3(RENDER_TB), 0, s, (const int4*)r->xyw, (const float4*)r->nc, (const int*)r->faces, r->F, r->V, r->W, r->H, tab,
+                     L_out_max, r->view, r->vis, out, yc, mt);
 }
 
 // The body of fdm_render_forward (out.rgb set, alpha and yuv null) and of fdm_render_forward_planes: render_resolve_kernel writes
-// whichever outputs are not null.  r, positions and the outputs have been checked by the caller.
+// whichever outputs are not null.  r, positions and the outputs have been checked by the caller.  scalars: the field of a scalar-map
+// object [B][L_max][V] (fdm_render_forward_material), null on every other object; takes_scalars: the call has the argument at all.
 int render_run(const char* who, fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
-               double fps_in, double fps_out, const float* normals, const RenderOut& out, int L_out_max, int* frames_out, void* stream) {
+               double fps_in, double fps_out, const float* normals, const RenderOut& out, int L_out_max, int* frames_out, void* stream,
+               const float* scalars = nullptr, bool takes_scalars = false) {
+  if (r->mat_kind == 2 && !takes_scalars)
+    return fail(FDM_ERR_STATE, "%s: the object has a scalar-map material: fdm_render_forward_material brings the scalars", who);
+  if (r->mat_kind == 2 && !scalars) return fail(FDM_ERR_ARG, "%s: null scalars on an object with a scalar-map material", who);
+  if (r->mat_kind != 2 && scalars) return fail(FDM_ERR_ARG, "%s: scalars on an object whose material is of kind %d (a scalar map is kind 2)", who, r->mat_kind);
   if (tmpl_rows != 0 && tmpl_rows != 1 && tmpl_rows != B) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d (0, 1 or B = %d)", who, tmpl_rows, B);
   if (tmpl_rows && !tmpl) return fail(FDM_ERR_ARG, "%s: tmpl_rows = %d with a null template", who, tmpl_rows);
   FCK(check_fps(who, fps_in, fps_out));
@@ -236,6 +263,7 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
   if (!normals) FCK(grow(r->mem, &r->N, &r->N_cap, chunk * V3));
   FCK(grow(r->mem, &r->xyw, &r->xyw_cap, chunk * r->V));
   FCK(grow(r->mem, &r->nc, &r->nc_cap, chunk * r->V));
+  if (r->mat_kind == 2) FCK(grow(r->mem, &r->u, &r->u_cap, chunk * r->V));
   const long long vis_before = r->vis_cap;
   FCK(grow(r->mem, &r->vis, &r->vis_cap, chunk * WH * r->samples));
   if (r->vis_cap != vis_before || r->vis_dirty) {
@@ -269,6 +297,9 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
     }
     hipLaunchKernelGGL(render_vertex_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, (const float*)r->P, normals ? normals : (const float*)r->N,
                        normals ? tab : (const int2*)nullptr, L_out_max, r->V, r->view, r->xyw, r->nc);
+    if (r->mat_kind == 2)
+      hipLaunchKernelGGL(render_scalar_kernel, dim3(vblocks, (unsigned)n), dim3(RENDER_TB), 0, s, scalars, (const int*)r->lens, tab, L_max, r->V, rs,
+                         r->mat_lo, r->mat_span, r->u);
     r->vis_dirty = true;
     raster_resolve(r, n, tab, L_out_max, out, yc, s);
     HIPCK(hipGetLastError());
@@ -276,6 +307,20 @@ int render_run(const char* who, fdm_render* r, const float* positions, const int
   }
   if (frames_out) for (int b = 0; b < B; ++b) frames_out[b] = hl[2 * b + 1];
   return FDM_OK;
+}
+
+// The planes form behind fdm_render_forward_planes and fdm_render_forward_material: the checks of the output set, written once.
+int render_planes_run(const char* who, fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+                      double fps_in, double fps_out, const float* normals, const fdm_render_planes* planes, int L_out_max, int* frames_out,
+                      void* stream, const float* scalars, bool takes_scalars) {
+  if (!r || !positions || !planes) return fail(FDM_ERR_ARG, "%s: null argument", who);
+  const RenderOut out = {planes->rgb, planes->depth, planes->face, planes->alpha, planes->yuv};
+  if (!out.rgb && !out.depth && !out.face && !out.alpha && !out.yuv) return fail(FDM_ERR_ARG, "%s: every output is null", who);
+  if (out.yuv && ((r->W | r->H) & 1))
+    return fail(FDM_ERR_ARG, "%s: yuv 4:2:0 needs an even width and height, the viewport is %d x %d", who, r->W, r->H);
+  if (out.yuv && ((size_t)out.yuv & 1)) return fail(FDM_ERR_ARG, "%s: yuv must be 2-byte aligned", who);
+  return render_run(who, r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, L_out_max, frames_out, stream, scalars,
+                    takes_scalars);
 }
 
 }  // namespace
@@ -293,14 +338,92 @@ int fdm_render_forward(fdm_render* r, const float* positions, const int* frames,
 int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
                               double fps_in, double fps_out, const float* normals, const fdm_render_planes* planes, int L_out_max,
                               int* frames_out, void* stream) {
-  if (!r || !positions || !planes) return fail(FDM_ERR_ARG, "render_forward_planes: null argument");
-  const RenderOut out = {planes->rgb, planes->depth, planes->face, planes->alpha, planes->yuv};
-  if (!out.rgb && !out.depth && !out.face && !out.alpha && !out.yuv) return fail(FDM_ERR_ARG, "render_forward_planes: every output is null");
-  if (out.yuv && ((r->W | r->H) & 1))
-    return fail(FDM_ERR_ARG, "render_forward_planes: yuv 4:2:0 needs an even width and height, the viewport is %d x %d", r->W, r->H);
-  if (out.yuv && ((size_t)out.yuv & 1)) return fail(FDM_ERR_ARG, "render_forward_planes: yuv must be 2-byte aligned");
-  return render_run("render_forward_planes", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, out, L_out_max, frames_out,
-                    stream);
+  return render_planes_run("render_forward_planes", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, planes, L_out_max,
+                           frames_out, stream, nullptr, false);
+}
+
+int fdm_render_forward_material(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+                                double fps_in, double fps_out, const float* normals, const fdm_render_planes* planes, int L_out_max,
+                                int* frames_out, void* stream, const float* scalars) {
+  return render_planes_run("render_forward_material", r, positions, frames, B, L_max, tmpl, tmpl_rows, fps_in, fps_out, normals, planes, L_out_max,
+                           frames_out, stream, scalars, true);
+}
+
+int fdm_render_set_material(fdm_render* r, const fdm_render_material* m) {
+  const char* who = "render_set_material";
+  if (!r) return fail(FDM_ERR_ARG, "%s: null object", who);
+  fdm_render_material none;
+  std::memset(&none, 0, sizeof(none));
+  if (!m) m = &none;
+  if (m->kind < 0 || m->kind > 3) return fail(FDM_ERR_ARG, "%s: kind = %d (0 base, 1 vertex colours, 2 scalar map, 3 texture)", who, m->kind);
+  if (m->unlit != 0 && m->unlit != 1) return fail(FDM_ERR_ARG, "%s: unlit = %d (0 or 1)", who, m->unlit);
+  float span = 1.f;
+  if (m->kind == 1) {
+    if (!m->colors) return fail(FDM_ERR_ARG, "%s: null colors for vertex colours", who);
+    for (long long i = 0; i < 3LL * r->V; ++i)
+      if (!std::isfinite(m->colors[i]) || !(m->colors[i] >= 0.f))
+        return fail(FDM_ERR_ARG, "%s: colors[%lld][%lld] = %g (finite, >= 0)", who, i / 3, i % 3, (double)m->colors[i]);
+  }
+  if (m->kind == 2) {
+    if (!m->lut) return fail(FDM_ERR_ARG, "%s: null lut for a scalar map", who);
+    if (m->n_lut < 2 || m->n_lut > 1024) return fail(FDM_ERR_ARG, "%s: n_lut = %d (2 .. 1024)", who, m->n_lut);
+    for (int i = 0; i < 3 * m->n_lut; ++i)
+      if (!std::isfinite(m->lut[i]) || !(m->lut[i] >= 0.f))
+        return fail(FDM_ERR_ARG, "%s: lut[%d][%d] = %g (finite, >= 0)", who, i / 3, i % 3, (double)m->lut[i]);
+    if (!std::isfinite(m->lo) || !std::isfinite(m->hi) || !(m->lo < m->hi))
+      return fail(FDM_ERR_ARG, "%s: the range lo = %g, hi = %g (finite, lo < hi)", who, (double)m->lo, (double)m->hi);
+    span = m->hi - m->lo;
+    if (!std::isfinite(span)) return fail(FDM_ERR_ARG, "%s: the range lo = %g, hi = %g has no finite fp32 span", who, (double)m->lo, (double)m->hi);
+  }
+  if (m->kind == 3) {
+    if (!m->uv || !m->texture) return fail(FDM_ERR_ARG, "%s: null uv or texture for a texture", who);
+    if (m->tex_w < 1 || m->tex_w > 8192 || m->tex_h < 1 || m->tex_h > 8192)
+      return fail(FDM_ERR_ARG, "%s: a texture of %d x %d (1 .. 8192 each)", who, m->tex_w, m->tex_h);
+    if (m->filter != 0 && m->filter != 1) return fail(FDM_ERR_ARG, "%s: filter = %d (0 nearest, 1 bilinear)", who, m->filter);
+  }
+  if (r->on_device) {                     // the new tables first: a failed upload leaves the object as it was
+    float* colors = nullptr; float4* lut = nullptr; float2* uv = nullptr; uchar4* tex = nullptr;
+    int rc = FDM_OK;
+    if (m->kind == 1) rc = put(r->mem, &colors, m->colors, (size_t)r->V * 3);
+    if (m->kind == 2) {
+      std::vector<float4> t((size_t)m->n_lut);
+      for (int i = 0; i < m->n_lut; ++i) t[i] = make_float4(m->lut[3 * i], m->lut[3 * i + 1], m->lut[3 * i + 2], 0.f);
+      rc = put(r->mem, &lut, t.data(), t.size());
+    }
+    if (m->kind == 3) {
+      const size_t n = (size_t)m->tex_w * m->tex_h;
+      std::vector<uchar4> t(n);           // rgb padded to 4-byte texels
+      for (size_t i = 0; i < n; ++i) t[i] = make_uchar4(m->texture[3 * i], m->texture[3 * i + 1], m->texture[3 * i + 2], 0);
+      rc = put(r->mem, &tex, t.data(), n);
+      if (rc == FDM_OK) rc = put(r->mem, &uv, reinterpret_cast<const float2*>(m->uv), (size_t)r->F * 3);
+    }
+    if (rc != FDM_OK) {
+      for (void* p : {(void*)colors, (void*)lut, (void*)uv, (void*)tex}) if (p) r->mem.free_one(p);
+      return rc;
+    }
+    if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) {      // a call in flight may still read the old tables
+      for (void* p : {(void*)colors, (void*)lut, (void*)uv, (void*)tex}) if (p) r->mem.free_one(p);      // (nothing reads the new ones yet)
+      return fail(FDM_ERR_HIP, "%s: hipDeviceSynchronize: %s", who, hipGetErrorString(e));
+    }
+    for (void* p : {(void*)r->colors, (void*)r->lut, (void*)r->uv, (void*)r->tex}) if (p) r->mem.free_one(p);
+    r->colors = colors; r->lut = lut; r->uv = uv; r->tex = tex;
+  }
+  r->mat_kind = m->kind; r->mat_unlit = m->unlit;
+  r->n_lut = m->kind == 2 ? m->n_lut : 0;
+  r->mat_lo = m->kind == 2 ? m->lo : 0.f; r->mat_span = span;
+  r->tex_w = m->kind == 3 ? m->tex_w : 0; r->tex_h = m->kind == 3 ? m->tex_h : 0; r->tex_filter = m->kind == 3 ? m->filter : 0;
+  return FDM_OK;
+}
+
+int fdm_op_vertex_dist(const float* a, const float* b, float* out, int rows, int V, void* stream) {
+  if (!a || !b || !out) return fail(FDM_ERR_ARG, "vertex_dist: null operand");
+  if (rows < 1 || V < 1) return fail(FDM_ERR_SHAPE, "vertex_dist: rows = %d, V = %d", rows, V);
+  if (!fdm_device_ok()) return fail(FDM_ERR_STATE, "vertex_dist: no gfx950 device visible (there is no CPU fallback)");
+  const long long n = (long long)rows * V;
+  if ((n + 255) / 256 > 0x7fffffffLL) return fail(FDM_ERR_SHAPE, "vertex_dist: %lld vertices exceed one launch", n);
+  hipLaunchKernelGGL(vertex_dist_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
+  HIPCK(hipGetLastError());
+  return FDM_OK;
 }
 
 }  // extern "C"

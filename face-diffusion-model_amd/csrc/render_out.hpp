@@ -25,6 +25,15 @@
 //                          from the 8-bit rgb, one lane per 2 x 2 block of pixels.  The keys are cleared as they are read, so every
 //                          plane comes out of this one pass and no rgb image is written that the caller did not ask for.
 //                          fdm_render_forward is the call with alpha and yuv null.
+//   render_resolve_kernel<S, YUV, MAT>   MAT = false is the kernel above, instruction for instruction (an object with no material).  MAT =
+//                          true (fdm_render_set_material, DESIGN item 25): the colour that stands where `base` stands comes from the
+//                          object's material behind one wavefront-uniform switch (the kind is a kernel argument) -- interpolated vertex
+//                          colours, a colour table looked up at the interpolated scalar, or a texture read nearest or bilinear at the
+//                          interpolated uv of the winning face's corners -- and `unlit` puts k = 1 in place of the Lambert sum.  The
+//                          held face keeps its three corners' attributes next to its setup and normals.
+//   render_scalar_kernel   kind 2 alone, one lane per (chunk row, vertex): the scalar field resampled by render_pos_kernel's
+//                          expressions on the same live-row table, then u = fmin(fmax((s - lo) / span, 0), 1).
+//   vertex_dist_kernel     fdm_op_vertex_dist: the distance of two vertex sets per (row, vertex), for error fields.
 // No cooperative launch, grid barrier or spin-wait.  Resource figures: profiles/render_out/resources.txt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -225,10 +234,11 @@ __global__ __launch_bounds__(RENDER_TB) void render_raster_kernel(const int4* xy
   }
 }
 
-// step 5 for one fragment of the oriented triangle T with the camera-space normals of its vertices 0, 1, 2: the Lambert factor k
+// step 5 for one fragment of the oriented triangle T with the camera-space normals of its vertices 0, 1, 2: the Lambert factor k; the
+// perspective weights b0, b1, b2 are handed out (a material interpolates its attributes with them: computed once)
 __device__ __forceinline__ float render_shade(const RenderTri& T, const float4& n0, const float4& n1, const float4& n2, float l0, float l1, float l2,
-                                              float iw, const RenderView& vw) {
-  const float b0 = __fdiv_rn(__fmul_rn(l0, T.w0), iw), b1 = __fdiv_rn(__fmul_rn(l1, T.w1), iw), b2 = __fdiv_rn(__fmul_rn(l2, T.w2), iw);
+                                              float iw, const RenderView& vw, float& b0, float& b1, float& b2) {
+  b0 = __fdiv_rn(__fmul_rn(l0, T.w0), iw); b1 = __fdiv_rn(__fmul_rn(l1, T.w1), iw); b2 = __fdiv_rn(__fmul_rn(l2, T.w2), iw);
   float nx = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.x), __fmul_rn(b1, n1.x)), __fmul_rn(b2, n2.x));
   float ny = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.y), __fmul_rn(b1, n1.y)), __fmul_rn(b2, n2.y));
   float nz = __fadd_rn(__fadd_rn(__fmul_rn(b0, n0.z), __fmul_rn(b1, n1.z)), __fmul_rn(b2, n2.z));
@@ -250,6 +260,91 @@ __device__ __forceinline__ float render_shade(const RenderTri& T, const float4& 
   return k;
 }
 
+// ---- materials (DESIGN item 25): the colour m that stands where `base` stands in step 5
+struct RenderNoMat {};                    // what render_pixel<S, false> is handed in place of a material: nothing
+__device__ __forceinline__ RenderNoMat render_first_or_none() { return RenderNoMat(); }
+template <typename T> __device__ __forceinline__ const T& render_first_or_none(const T& t) { return t; }
+struct RenderMat {                        // kernel argument (by value) of the MAT = true instances; the same in every lane
+  int kind, unlit;                        // 0 base, 1 vertex colours, 2 scalar map, 3 texture
+  const float* colors;                    // kind 1: [V][3]
+  const float* u;                         // kind 2: [n][V] of the chunk, in [0, 1] (render_scalar_kernel)
+  const float4* lut;                      // kind 2: [n_lut] {r, g, b, 0}
+  int n_lut;
+  const float2* uv;                       // kind 3: [F][3] per face corner
+  const unsigned* tex;                    // kind 3: [tex_h][tex_w] texels r | g << 8 | b << 16 (the bytes r, g, b, 0), row 0 at the top
+  int tex_w, tex_h, filter;               // 0 nearest, 1 bilinear
+};
+// The attributes of the held face's oriented corners i = 0, 1, 2 are nine floats a0 .. a8: kind 1 a(3 i + c), kind 2 a(i), kind 3 a(2 i),
+// a(2 i + 1).  Nine variables of their own, not an array or a struct: the compiler merges the kinds' stores into one store at a
+// run-time offset, and an aggregate then lives in scratch memory.
+#define RENDER_ATTR_REFS float &a0, float &a1, float &a2, float &a3, float &a4, float &a5, float &a6, float &a7, float &a8
+#define RENDER_ATTR_VALS float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, float a8
+#define RENDER_ATTR_ARGS a0, a1, a2, a3, a4, a5, a6, a7, a8
+
+__device__ __forceinline__ float render_interp(float b0, float b1, float b2, float a0, float a1, float a2) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(b0, a0), __fmul_rn(b1, a1)), __fmul_rn(b2, a2));
+}
+__device__ __forceinline__ float render_lerp(float a, float b, float f) { return __fadd_rn(a, __fmul_rn(f, __fsub_rn(b, a))); }
+// fmaxf / fminf return the operand that is not NaN: a NaN x gives lo
+__device__ __forceinline__ float render_clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ void render_texel(const RenderMat& mt, int col, int row, float& r, float& g, float& b) {
+  const unsigned t = mt.tex[(size_t)row * mt.tex_w + col];      // one 4-byte load
+  r = __fdiv_rn((float)(t & 255u), 255.f); g = __fdiv_rn((float)((t >> 8) & 255u), 255.f); b = __fdiv_rn((float)((t >> 16) & 255u), 255.f);
+}
+// the attributes of face `won` whose oriented corners are the vertices v0, v1, v2 (corners 1 and 2 swapped where the setup swapped them)
+__device__ __forceinline__ void render_attr_load(const RenderMat& mt, unsigned won, bool swapped, size_t r0, int v0, int v1, int v2, RENDER_ATTR_REFS) {
+  if (mt.kind == 1) {
+    const float *c0 = mt.colors + 3 * (size_t)v0, *c1 = mt.colors + 3 * (size_t)v1, *c2 = mt.colors + 3 * (size_t)v2;
+    a0 = c0[0]; a1 = c0[1]; a2 = c0[2]; a3 = c1[0]; a4 = c1[1]; a5 = c1[2]; a6 = c2[0]; a7 = c2[1]; a8 = c2[2];
+  } else if (mt.kind == 2) {
+    a0 = mt.u[r0 + v0]; a1 = mt.u[r0 + v1]; a2 = mt.u[r0 + v2];
+  } else if (mt.kind == 3) {
+    const float2* q = mt.uv + 3 * (size_t)won;
+    const float2 q0 = q[0], q1 = q[swapped ? 2 : 1], q2 = q[swapped ? 1 : 2];
+    a0 = q0.x; a1 = q0.y; a2 = q1.x; a3 = q1.y; a4 = q2.x; a5 = q2.y;
+  }
+}
+// m of one fragment with the perspective weights b0, b1, b2 (the switch is uniform over the wavefront: the kind is a kernel argument)
+__device__ __forceinline__ void render_material(const RenderMat& mt, RENDER_ATTR_VALS, float b0, float b1, float b2, const RenderView& vw, float& mr,
+                                                float& mg, float& mb) {
+  mr = vw.base[0]; mg = vw.base[1]; mb = vw.base[2];
+  if (mt.kind == 1) {
+    mr = render_interp(b0, b1, b2, a0, a3, a6);
+    mg = render_interp(b0, b1, b2, a1, a4, a7);
+    mb = render_interp(b0, b1, b2, a2, a5, a8);
+  } else if (mt.kind == 2) {
+    const float u = render_clampf(render_interp(b0, b1, b2, a0, a1, a2), 0.f, 1.f);
+    const float x = __fmul_rn(u, (float)(mt.n_lut - 1));      // in [0, n_lut - 1]
+    const int i = min((int)x, mt.n_lut - 2);
+    const float f = __fsub_rn(x, (float)i);
+    const float4 p = mt.lut[i], q = mt.lut[i + 1];
+    mr = render_lerp(p.x, q.x, f); mg = render_lerp(p.y, q.y, f); mb = render_lerp(p.z, q.z, f);
+  } else if (mt.kind == 3) {
+    const float tu = render_interp(b0, b1, b2, a0, a2, a4), tv = render_interp(b0, b1, b2, a1, a3, a5);
+    const float fw = (float)mt.tex_w, fh = (float)mt.tex_h, cw = (float)(mt.tex_w - 1), ch = (float)(mt.tex_h - 1);
+    if (mt.filter == 0) {                 // the clamps are made in float: no index leaves the texture, whatever the bits of uv
+      const int col = (int)render_clampf(floorf(__fmul_rn(tu, fw)), 0.f, cw);
+      const int row = (int)render_clampf(floorf(__fmul_rn(__fsub_rn(1.f, tv), fh)), 0.f, ch);
+      render_texel(mt, col, row, mr, mg, mb);
+    } else {
+      const float x = __fsub_rn(__fmul_rn(tu, fw), 0.5f), y = __fsub_rn(__fmul_rn(__fsub_rn(1.f, tv), fh), 0.5f);
+      const float x0 = floorf(x), y0 = floorf(y);
+      const float fx = __fsub_rn(x, x0), fy = __fsub_rn(y, y0);      // NaN for a NaN or infinite coordinate: the sample takes the background
+      const int c0 = (int)render_clampf(x0, 0.f, cw), c1 = (int)render_clampf(__fadd_rn(x0, 1.f), 0.f, cw);
+      const int r0 = (int)render_clampf(y0, 0.f, ch), r1 = (int)render_clampf(__fadd_rn(y0, 1.f), 0.f, ch);
+      float ar, ag, ab, br, bg, bb;
+      render_texel(mt, c0, r0, ar, ag, ab);
+      render_texel(mt, c1, r0, br, bg, bb);
+      const float tr = render_lerp(ar, br, fx), tg = render_lerp(ag, bg, fx), tb = render_lerp(ab, bb, fx);
+      render_texel(mt, c0, r1, ar, ag, ab);
+      render_texel(mt, c1, r1, br, bg, bb);
+      mr = render_lerp(tr, render_lerp(ar, br, fx), fy);
+      mg = render_lerp(tg, render_lerp(ag, bg, fx), fy);
+      mb = render_lerp(tb, render_lerp(ab, bb, fx), fy);
+    }
+  }
+}
+
 // What the resolve of one pixel gives: the three 8-bit channels, the largest key over the pixel's samples (0: no fragment) and n, the
 // number of its samples that have a fragment.  depth, face and alpha follow from best and n.
 struct RenderPixel {
@@ -267,10 +362,11 @@ __device__ __forceinline__ int render_key_face(unsigned long long best) {
 // Step 5 for the pixel (x, y) of the chunk's row whose vertex records start at r0 = row V and whose keys start at img: reads the
 // pixel's 8 S contiguous bytes of keys (S = 1: one 8-byte load; S > 1: 16 bytes at a time) and writes 0 back (the buffer is clear for
 // the next chunk); per sample recomputes the winning face's fragment, interpolates the normal, shades; sums the channels in sample
-// order, scales by 1 / S.  At S = 1 the sum is the one sample's colour and the scale is 1.
-template <int S>
+// order, scales by 1 / S.  At S = 1 the sum is the one sample's colour and the scale is 1.  MAT: the colour comes from the material mt
+// (a RenderMat) in place of vw.base; with MAT = false mt is not read.
+template <int S, bool MAT, typename M>
 __device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float4* nc, const int* faces, int F, size_t r0, int W, int x, int y,
-                                                    const RenderView& vw, unsigned long long* img) {
+                                                    const RenderView& vw, const M& mt, unsigned long long* img) {
   static_assert(S == 1 || S == 4 || S == 16, "the sample patterns of render_sample_offset");
   constexpr int PER = S == 1 ? 1 : 2;     // keys per load
   unsigned long long* slot = img + ((size_t)y * W + x) * S;      // 8 S bytes, at S > 1 16-byte aligned
@@ -280,6 +376,7 @@ __device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float
   unsigned held = 0xFFFFFFFFu;            // the face whose setup T, n0, n1, n2 hold
   RenderTri T = {};
   float4 n0 = {}, n1 = {}, n2 = {};
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f;      // (MAT alone)
 #pragma unroll 1
   for (int h = 0; h < S / PER; ++h) {
     ulonglong2 two = make_ulonglong2(0ull, 0ull);
@@ -302,14 +399,24 @@ __device__ __forceinline__ RenderPixel render_pixel(const int4* xyw, const float
           const int* fv = faces + 3 * (size_t)won;
           T = render_setup(xyw[r0 + fv[0]], xyw[r0 + fv[1]], xyw[r0 + fv[2]]);
           n0 = nc[r0 + fv[0]]; n1 = nc[r0 + fv[T.swapped ? 2 : 1]]; n2 = nc[r0 + fv[T.swapped ? 1 : 2]];
+          if constexpr (MAT) render_attr_load(mt, won, T.swapped, r0, fv[0], fv[T.swapped ? 2 : 1], fv[T.swapped ? 1 : 2], RENDER_ATTR_ARGS);
           held = won;
         }
         int ox, oy;
         render_sample_offset<S>(s, ox, oy);
         float l0, l1, l2, iw;             // (the recomputed iw has the key's bits: the same expressions on the same integers)
         (void)render_fragment_at(T, 256 * x + ox, 256 * y + oy, l0, l1, l2, iw);
-        const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw);
-        cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
+        float b0, b1, b2;
+        if constexpr (!MAT) {
+          const float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw, b0, b1, b2);
+          cr = __fmul_rn(vw.base[0], k); cg = __fmul_rn(vw.base[1], k); cb = __fmul_rn(vw.base[2], k);
+        } else {
+          float k = render_shade(T, n0, n1, n2, l0, l1, l2, iw, vw, b0, b1, b2);
+          if (mt.unlit) k = 1.f;
+          float mr, mg, mb;
+          render_material(mt, RENDER_ATTR_ARGS, b0, b1, b2, vw, mr, mg, mb);
+          cr = __fmul_rn(mr, k); cg = __fmul_rn(mg, k); cb = __fmul_rn(mb, k);
+        }
         if (cr != cr) cr = vw.background[0];
         if (cg != cg) cg = vw.background[1];
         if (cb != cb) cb = vw.background[2];
@@ -350,10 +457,14 @@ __device__ __forceinline__ void render_store_pixel(const RenderOut& out, size_t 
 // (not unrolled: the registers of one pixel, three channel sums and one luma byte stay live), stores each row's two luma bytes in one
 // 2-byte store -- the 64 lanes of a wavefront write 128 contiguous bytes of a luma row -- and the block's chroma once (NV12: one
 // 2-byte store).  yuv: [B][Lo_max][3 W H / 2], 2-byte aligned.  grid (blocks of RENDER_TB blocks of pixels, chunk rows).
-template <int S, bool YUV>
+// MAT = false: no further argument (the kernel's signature and code are what they were), the object has no material; MAT = true: one
+// more argument, the object's RenderMat (kinds 0 to 3 and unlit).
+template <int S, bool YUV, bool MAT, typename... M>
 __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* xyw, const float4* nc, const int* faces, int F, int V, int W, int H,
                                                                    const int2* rowtab, int Lo_max, const RenderView vw, unsigned long long* vis,
-                                                                   const RenderOut out, const RenderYuv yc) {
+                                                                   const RenderOut out, const RenderYuv yc, const M... mat) {
+  static_assert(sizeof...(M) == (MAT ? 1 : 0), "one RenderMat with MAT, nothing without");
+  const auto& mt = render_first_or_none(mat...);
   const int row = blockIdx.y, i = blockIdx.x * RENDER_TB + threadIdx.x;
   const size_t WH = (size_t)W * H, r0 = (size_t)row * V;
   unsigned long long* img = vis + (size_t)row * WH * S;
@@ -361,7 +472,7 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
     if (i >= W * H) return;
     const int2 bt = rowtab[row];
     const int y = i / W, x = i - y * W;
-    const RenderPixel p = render_pixel<S>(xyw, nc, faces, F, r0, W, x, y, vw, img);
+    const RenderPixel p = render_pixel<S, MAT>(xyw, nc, faces, F, r0, W, x, y, vw, mt, img);
     render_store_pixel(out, ((size_t)bt.x * Lo_max + bt.y) * WH + i, p, S);
   } else {
     const int W2 = W >> 1;
@@ -375,7 +486,7 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
       const int x = 2 * bx + (q & 1), y = 2 * by + (q >> 1);
-      const RenderPixel p = render_pixel<S>(xyw, nc, faces, F, r0, W, x, y, vw, img);
+      const RenderPixel p = render_pixel<S, MAT>(xyw, nc, faces, F, r0, W, x, y, vw, mt, img);
       render_store_pixel(out, frame * WH + (size_t)y * W + x, p, S);
       const int R = p.r, G = p.g, B = p.b;
       Rs += R; Gs += G; Bs += B;
@@ -393,6 +504,33 @@ __global__ __launch_bounds__(RENDER_TB) void render_resolve_kernel(const int4* x
       Cp[WH / 4 + i] = Vv;
     }
   }
+}
+
+// Kind 2, per (chunk row, vertex): the scalar field on the input frames -> u of the row's output frame.  sc: [B][L_max][V]; rowtab,
+// lens, resample as render_pos_kernel (its expressions, no template; rows at or past frames[b] are never read); u: [n][V].
+// grid (blocks of RENDER_TB vertices, chunk rows).
+__global__ __launch_bounds__(RENDER_TB) void render_scalar_kernel(const float* sc, const int* lens, const int2* rowtab, int L_max, int V, int resample,
+                                                                  float lo, float span, float* u) {
+  const int row = blockIdx.y, v = blockIdx.x * RENDER_TB + threadIdx.x;
+  if (v >= V) return;
+  const int2 bt = rowtab[row];
+  const int b = bt.x, t = bt.y;
+  int i0 = t, i1 = t;
+  float l0 = 1.f, l1 = 0.f;
+  if (resample) interp_taps(lens[2 * b], lens[2 * b + 1], t, i0, i1, l0, l1);
+  const float s0 = sc[((size_t)b * L_max + i0) * V + v];
+  float s = s0;
+  if (resample) s = __fadd_rn(__fmul_rn(l0, s0), __fmul_rn(l1, sc[((size_t)b * L_max + i1) * V + v]));
+  u[(size_t)row * V + v] = render_clampf(__fdiv_rn(__fsub_rn(s, lo), span), 0.f, 1.f);
+}
+
+// fdm_op_vertex_dist: out[r][v] = sqrtf((dx dx + dy dy) + dz dz) of a - b over [rows][3 V].  n = rows V lanes.
+__global__ __launch_bounds__(256) void vertex_dist_kernel(const float* a, const float* b, float* out, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float *p = a + 3 * i, *q = b + 3 * i;
+  const float dx = __fsub_rn(p[0], q[0]), dy = __fsub_rn(p[1], q[1]), dz = __fsub_rn(p[2], q[2]);
+  out[i] = sqrtf(render_dot(dx, dy, dz, dx, dy, dz));      // the correctly rounded expansion, as in mesh_nrm_kernel
 }
 
 }  // namespace fdm

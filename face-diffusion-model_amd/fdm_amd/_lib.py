@@ -97,6 +97,11 @@ class RenderPlanes(C.Structure):          # fdm_render_planes: the outputs of fd
     _fields_ = [("rgb", vp), ("depth", vp), ("face", vp), ("alpha", vp), ("yuv", vp)]
 
 
+class RenderMaterial(C.Structure):        # fdm_render_material: what fdm_render_set_material reads (HOST arrays, not kept)
+    _fields_ = [("kind", ci), ("unlit", ci), ("colors", vp), ("lut", vp), ("n_lut", ci), ("lo", cf), ("hi", cf), ("uv", vp), ("texture", vp),
+                ("tex_w", ci), ("tex_h", ci), ("filter", ci)]
+
+
 class FlameModelDesc(C.Structure):
     _fields_ = [("V", ci), ("J", ci), ("NB", ci), ("expr_at", ci), ("v_template", vp), ("shapedirs", vp), ("posedirs", vp),
                 ("j_regressor", vp), ("parents", vp), ("lbs_weights", vp)]
@@ -109,7 +114,8 @@ WRAP_OFFSETS = 1      # fdm_wrap_forward flags
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
            "fdm_model_desc": ModelDesc, "fdm_sample_args": SampleArgs, "fdm_vq_desc": VqDesc, "fdm_slot_group_args": SlotGroupArgs,
-           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm, "fdm_flame_model": FlameModelDesc, "fdm_render_planes": RenderPlanes}
+           "fdm_slot_bank_args": SlotBankArgs, "fdm_pcm": Pcm, "fdm_flame_model": FlameModelDesc, "fdm_render_planes": RenderPlanes,
+           "fdm_render_material": RenderMaterial}
 
 # every symbol include/fdm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -239,6 +245,9 @@ SYMBOLS = {
     "fdm_render_forward": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, vp, vp, vp, ci, vp, vp]),
     "fdm_render_forward_planes": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, C.POINTER(RenderPlanes), ci, vp, vp]),
     "fdm_render_yuv_coeffs_host": (ci, [ci, ci, vp]),
+    "fdm_render_set_material": (ci, [vp, C.POINTER(RenderMaterial)]),
+    "fdm_render_forward_material": (ci, [vp, vp, vp, ci, ci, vp, ci, C.c_double, C.c_double, vp, C.POINTER(RenderPlanes), ci, vp, vp, vp]),
+    "fdm_op_vertex_dist": (ci, [vp, vp, vp, ci, ci, vp]),
     "fdm_render_destroy": (ci, [vp]),
     "fdm_vq_create": (ci, [C.POINTER(VqDesc), ci, C.POINTER(vp)]),
     "fdm_vq_set_weights": (ci, [vp, C.c_char_p, vp, ll, vp]),

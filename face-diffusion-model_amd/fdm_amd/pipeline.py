@@ -249,14 +249,15 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
                      lambda y, fr: [y[b:b + 1, :n] for b, n in enumerate(fr)])
 
 
-_RENDER_OUTPUTS = ("depth", "face_ids", "alpha", "yuv")      # keys of a render= dict that choose outputs, not the plan
+# keys of a render= dict that choose outputs or bring a call's scalar field, not the plan
+_RENDER_OUTPUTS = ("depth", "face_ids", "alpha", "yuv", "scalars", "error_to")
 
 
 def _render_plan(render, faces, V, device):
     """The render hand-off plan of `device`, the current stream, this topology and this view (render.RenderPlan.key).  render: a
     render.RenderPlan (used as it is where it was made for this device and stream, made again from its arguments otherwise; `faces`
     is then not read) or the dict of RenderPlan's arguments after faces and V (camera, lights, ambient, base, background,
-    chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout; yuv="i420" | "nv12" among its outputs is the plan's yuv_layout)."""
+    chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout, material; yuv="i420" | "nv12" among its outputs is the plan's yuv_layout)."""
     from .render import RenderPlan, identity
     dv, at = _on_stream(device)
     if isinstance(render, RenderPlan):
@@ -285,8 +286,26 @@ def _split_images(im, _=None):
 
 
 @torch.no_grad()
+def _packed_scalars(scalars, x, frames):
+    """The scalar field of a call as one batch [B, L_max, V] next to the packed positions x: a list with one [L_b, V] per clip is
+    zero-padded as _pack_offsets pads the clips; a tensor goes as it is."""
+    if not isinstance(scalars, (list, tuple)):
+        return scalars
+    V = int(x.shape[-1]) // 3
+    if len(scalars) != int(x.shape[0]):
+        raise ValueError(f"{len(scalars)} scalar fields for {int(x.shape[0])} clips")
+    pad = torch.zeros(int(x.shape[0]), int(x.shape[1]), V, device=x.device)
+    for b, c in enumerate(scalars):
+        c = torch.as_tensor(c, dtype=torch.float32).reshape(-1, V)
+        if int(c.shape[0]) != int(frames[b]):
+            raise ValueError(f"the scalar field of clip {b} has {int(c.shape[0])} frames, the clip {int(frames[b])}")
+        pad[b, :c.shape[0]] = c
+    return pad
+
+
+@torch.no_grad()
 def to_images(offsets, faces, render, template=None, frames=None, fps=None, normals=None, depth=None, face_ids=None, device=None, alpha=None,
-              yuv=None):
+              yuv=None, scalars=None):
     """Vertices (or vertex offsets with template=) -> render.ImageFrames: shaded uint8 frames [B, L_out, H, W, 3] of the mesh with the
     triangle list `faces` [F, 3], drawn on the device in ONE call (render.RenderPlan; include/fdm_hip.h, fdm_render_forward; DESIGN.md
     section 2 item 23 states every operation).  render: a render.RenderPlan, or the dict of its arguments after faces and V -- camera (a
@@ -298,13 +317,16 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
     frames = L per clip (None: all L); a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V] clips -> a list of ImageFrames, each cut to its own
     frames and bit for bit what its own call returns; or a mesh.MeshFrames (planar fp32): its positions, normals and frames are drawn
     as they are.  template: [1 or B, 3 V], or for a list one per clip.  fps = (fps_in, fps_out): the positions are resampled by
-    to_mesh's rule first.  normals [B, L_out, V, 3]: the caller's instead of the ones computed here (to_mesh's)."""
+    to_mesh's rule first.  normals [B, L_out, V, 3]: the caller's instead of the ones computed here (to_mesh's).  material= in the dict
+    (a render.Material: vertex colours, a scalar map or a texture) colours the surface; a scalar map reads
+    scalars [B, L, V] on the INPUT frames (for a list of clips a list of [L_b, V]), given here or in the dict."""
     from .mesh import MeshFrames
     opts = render if isinstance(render, dict) else {}
     depth = bool(opts.get("depth", False)) if depth is None else depth
     face_ids = bool(opts.get("face_ids", False)) if face_ids is None else face_ids
     alpha = bool(opts.get("alpha", False)) if alpha is None else alpha
     yuv = bool(opts.get("yuv", False)) if yuv is None else bool(yuv)
+    scalars = opts.get("scalars") if scalars is None else scalars
     if isinstance(offsets, MeshFrames):
         mf = offsets
         if mf.positions.dtype != torch.float32 or mf.positions.shape[-1] != 3:
@@ -312,7 +334,46 @@ def to_images(offsets, faces, render, template=None, frames=None, fps=None, norm
         B, Lo, V = (int(n) for n in mf.positions.shape[:3])
         offsets, frames, normals = mf.positions.reshape(B, Lo, 3 * V), mf.frames, (mf.normals if normals is None else normals)
     return _per_clip("to_images", offsets, frames, template, device, lambda x, fr, tp: _render_plan(render, faces, x.shape[-1] // 3, x.device).forward(
-        x, fr, tp, fps, normals, depth, face_ids, alpha=alpha, yuv=yuv), _split_images)
+        x, fr, tp, fps, normals, depth, face_ids, alpha=alpha, yuv=yuv, scalars=_packed_scalars(scalars, x, fr)), _split_images)
+
+
+def _render_material(render):
+    """The render.Material of a render= argument (a dict or a render.RenderPlan), or None."""
+    return render.get("material") if isinstance(render, dict) else getattr(render, "view", {}).get("material")
+
+
+def _gt_rows(c, gt):
+    """error_to for the clips c [B, L, 3 V] that are about to be drawn: [L', 3 V], [L', V, 3], [B, L', 3 V] or [B, L', V, 3] with L' >= L ->
+    [B, L, 3 V] on c's device, cropped to the clip.  A wrong vertex count or too few frames is a ValueError."""
+    B, L, V3 = (int(n) for n in c.shape)
+    g = torch.as_tensor(gt, dtype=torch.float32)
+    if g.dim() >= 3 and g.shape[-1] == 3 and int(g.shape[-2]) * 3 == V3:
+        g = g.reshape(tuple(g.shape[:-2]) + (V3,))
+    if g.dim() == 2:
+        g = g.unsqueeze(0)
+    if g.dim() != 3 or int(g.shape[-1]) != V3 or int(g.shape[0]) not in (1, B):
+        raise ValueError(f"error_to has the shape {tuple(torch.as_tensor(gt).shape)}: the drawn mesh has {V3 // 3} vertices ({V3} numbers a frame), "
+                         f"the call {B} clips")
+    if int(g.shape[1]) < L:
+        raise ValueError(f"error_to has {int(g.shape[1])} frames, the clip {L}")
+    return g[:, :L].expand(B, L, V3).to(c.device).contiguous()
+
+
+def _error_field(out, template, gt, device):
+    """render=dict(error_to=gt): the scalars of the call, |drawn vertex - gt| per input frame and vertex (render.vertex_error), for a
+    batch [B, L, 3 V] or a list of clips with one gt per clip.  The vertex count was checked when the call began (_Outputs); the
+    lengths are checked here, for every clip before the first launch of the hand-off -- the model has run by then: a clip's length
+    is known only from its encoded audio."""
+    from .render import vertex_error
+    drawn = lambda c, t: c.contiguous() if t is None else c + _template_rows(t, c.shape[-1], device).unsqueeze(1)  # noqa: E731
+    if not isinstance(out, (list, tuple)):
+        return vertex_error(drawn(out, template), _gt_rows(out, gt))
+    if not isinstance(gt, (list, tuple)) or len(gt) != len(out):
+        raise ValueError(f"error_to for {len(out)} clips is a list with one ground truth per clip")
+    clips = [c.reshape(1, -1, c.shape[-1]) for c in out]
+    gts = [_gt_rows(c, g) for c, g in zip(clips, gt)]
+    tps = template if isinstance(template, (list, tuple)) else [template] * len(out)
+    return [vertex_error(drawn(c, t), g)[0] for c, t, g in zip(clips, tps, gts)]
 
 
 def _flame_rows(x, L, R, what):
@@ -500,6 +561,12 @@ class _Outputs:
     def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None):
         if render is not None and faces is None:
             raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
+        if isinstance(render, dict) and (render.get("error_to") is not None or render.get("scalars") is not None):
+            mat = _render_material(render)
+            if render.get("error_to") is not None and render.get("scalars") is not None:
+                raise ValueError("render= takes scalars= or error_to=, not both")
+            if mat is None or mat.kind != 2:
+                raise ValueError("render=dict(scalars= | error_to=) needs material=render.Material.scalar_map(...)")
         if flame is not None:
             _flame_check(flame)
             if rig is not None and faces is None:
@@ -510,6 +577,15 @@ class _Outputs:
         self.rig = None if rig is None else _bound_plan("rig", rig, device)
         self.wrap = None if wrap is None else _bound_plan("wrap", wrap, device)
         self.fps = fps or (_mesh_fps(p, in_fps, out_fps) if (faces is not None or rig is not None) else None)
+        if isinstance(render, dict) and render.get("error_to") is not None:
+            # the vertex count of what will be drawn is known here, before anything runs: the wrap's target, else the model's own (a
+            # posed head keeps it).  A clip's length is known only once its audio has been encoded: _gt_rows checks it at the hand-off.
+            V = self.wrap.Vt if self.wrap is not None else (p.V3 // 3 if p is not None else None)
+            gts = render["error_to"] if isinstance(render["error_to"], (list, tuple)) else [render["error_to"]]
+            for g in gts:
+                shp = tuple(torch.as_tensor(g).shape)
+                if V is not None and not (len(shp) >= 2 and (shp[-1] == 3 * V or (len(shp) >= 3 and shp[-1] == 3 and shp[-2] == V))):
+                    raise ValueError(f"error_to has the shape {shp}: the drawn mesh has {V} vertices ([L', {3 * V}] or [L', {V}, 3])")
 
     def __call__(self, out, template=None, S=1, B=1, flame=None):
         """What a call returns for a batch of decoded offsets [B*S, L, V3]: offsets + template; with faces= the mesh.MeshFrames (the
@@ -549,7 +625,10 @@ class _Outputs:
         if self.render is None:
             res = to_mesh(out, self.faces, template, fps=self.fps, **self.mesh)
         else:
-            res = to_images(out, self.faces, self.render, template, fps=self.fps, device=self.device)
+            render = self.render
+            if isinstance(render, dict) and render.get("error_to") is not None:      # the error field of what is about to be drawn
+                render = dict(render, scalars=_error_field(out, template, render["error_to"], self.device))
+            res = to_images(out, self.faces, render, template, fps=self.fps, device=self.device)
         if fit is None:                                                                          # 5. with the fit
             return res
         return list(zip(res, fit)) if many else (res, fit)
@@ -582,7 +661,10 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 
     render (a render.RenderPlan or the dict of its arguments after faces and V: camera, lights, ambient, base, background,
     chunk_frames; depth=True / face_ids=True for those images too, alpha=True for the coverage plane, yuv="i420" | "nv12" for the
-    4:2:0 planes with yuv_matrix / yuv_range, as to_images): with faces= the call returns (render.ImageFrames, latent) in place
+    4:2:0 planes with yuv_matrix / yuv_range, as to_images; material= a render.Material, and with a scalar map scalars= [B, L, V] or
+    error_to= ground-truth vertices [L' >= L, 3 V] of the drawn mesh: the field is then render.vertex_error of what is about to be
+    drawn, for a per-vertex error heat map; a wrong vertex count is a ValueError before anything runs, too few frames one before
+    the hand-off's first launch, once the clip's length is known from its audio): with faces= the call returns (render.ImageFrames, latent) in place
     of the mesh.MeshFrames -- shaded uint8 frames [B, L_out, H, W, 3] of the mesh `faces`, drawn on the device (to_images) from the
     positions and normals the mesh hand-off would have returned; out_fps= is honoured; after flame= or wrap= the posed or wrapped mesh
     is drawn (faces= is then that mesh's triangle list).  faces= is required; mesh= is not read; with rig= the call returns
@@ -869,7 +951,8 @@ class SlotServer:
 
     wrap: as animate(): every finished clip's vertices are those of the bound mesh ([1, L, 3 Vt], or what faces= makes of them).
 
-    render: as animate(): results() yields a render.ImageFrames in place of the mesh.MeshFrames (faces= is required)."""
+    render: as animate(): results() yields a render.ImageFrames in place of the mesh.MeshFrames (faces= is required).  Its material= may be
+    vertex colours or a texture; a scalar map is refused (ValueError): per-request scalar fields are not built."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
@@ -877,6 +960,9 @@ class SlotServer:
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.model, p, self.cfg, self.scale = _unwrap(diffusion)
         self.p = p
+        mat = _render_material(render) if render is not None else None
+        if mat is not None and mat.kind == 2:
+            raise ValueError("SlotServer draws materials of vertex colours and textures; a scalar map needs a field per request, which is not built")
         self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render)     # once, not per finished clip
         self.rig = self.outputs.rig
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
@@ -1241,6 +1327,38 @@ def add_render_arguments(ap):
                          "the ffmpeg line that encodes them without a colour conversion (with --render; N even)")
     ap.add_argument("--render_yuv_matrix", type=int, default=709, choices=(601, 709), help="build-added: the matrix of --render_yuv (BT.601 or BT.709)")
     ap.add_argument("--render_yuv_full", action="store_true", help="build-added: full-range --render_yuv (0 .. 255) instead of limited (16 .. 235)")
+    ap.add_argument("--render_colors", default=None, help="build-added: c.npy, float [V, 3] >= 0: vertex colours in place of the grey base (with --render)")
+    ap.add_argument("--render_texture", default=None,
+                    help="build-added: tex.npy, uint8 [Ht, Wt, 3] with row 0 at the top (no image formats are decoded), drawn with --render_uv")
+    ap.add_argument("--render_uv", default=None, help="build-added: uv.npz with the keys vt [T, 2] and ft [F, 3] (FLAME's) or uv [F, 3, 2] (with --render_texture)")
+    ap.add_argument("--render_error_to", default=None,
+                    help="build-added: gt.npy, ground-truth vertices [L' >= L, 3 V]: the frames show the per-vertex distance to them as a heat map (with --render)")
+    ap.add_argument("--render_error_max", type=float, default=0.01, help="build-added: the distance that takes the last colour of the table (with --render_error_to)")
+    ap.add_argument("--render_colormap", default="heat", choices=("heat", "jet", "grey"), help="build-added: the table of --render_error_to")
+    ap.add_argument("--render_unlit", action="store_true", help="build-added: the material's colour as it is, without the lights (with --render)")
+
+
+def material_arguments(a):
+    """dict(material=, error_to=) of the --render_colors / --render_texture + --render_uv / --render_error_to flags (at most one of the
+    three), empty without them; --render_unlit alone is the base colour unlit."""
+    from .render import Material, uv_corners
+    unlit = bool(getattr(a, "render_unlit", False))
+    colors, tex, uvf, gt = (getattr(a, k, None) for k in ("render_colors", "render_texture", "render_uv", "render_error_to"))
+    if sum(x is not None for x in (colors, tex, gt)) > 1:
+        raise ValueError("--render_colors, --render_texture and --render_error_to are three materials: one at a time")
+    if (tex is None) != (uvf is None):
+        raise ValueError("--render_texture and --render_uv go together")
+    if colors is not None:
+        return dict(material=Material.vertex_colors(np.load(colors), unlit=unlit))
+    if tex is not None:
+        z = np.load(uvf)
+        uv = z["uv"] if "uv" in z.files else uv_corners(z["vt"], z["ft"])
+        return dict(material=Material.texture(np.load(tex), uv, unlit=unlit))
+    if gt is not None:
+        g = np.load(gt).astype(np.float32)
+        return dict(material=Material.scalar_map(getattr(a, "render_colormap", "heat"), 0.0, float(getattr(a, "render_error_max", 0.01)), unlit=unlit),
+                    error_to=g.reshape(g.shape[-3] if g.ndim >= 3 and g.shape[-1] == 3 else g.shape[-2], -1))
+    return dict(material=Material.base(unlit=True)) if unlit else {}
 
 
 def save_frames(a, p, verts, faces, dst):
@@ -1256,6 +1374,11 @@ def save_frames(a, p, verts, faces, dst):
         view["alpha"] = True
     if layout:
         view.update(yuv=layout, yuv_matrix=int(getattr(a, "render_yuv_matrix", 709)), yuv_range="full" if full else "limited")
+    mat = material_arguments(a)
+    if "error_to" in mat:      # the error field of the saved vertices
+        v = verts if verts.dim() == 3 else verts.unsqueeze(0)
+        mat = dict(material=mat["material"], scalars=_error_field(v, None, mat["error_to"], v.device))
+    view.update(mat)
     im = to_images(verts, faces, view)
     np.save(dst + "_frames", im.images.detach().cpu().numpy())
     print(f"saved {dst}_frames.npy {tuple(im.images.shape)}")

@@ -11,7 +11,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from ._lib import FdmError, RenderPlanes, check, lib
+from ._lib import FdmError, RenderMaterial, RenderPlanes, check, lib
 from .handoff import HandoffPlan, fps_pair, frames_list, frames_out_max, offsets_batch
 from .mesh import faces_array
 
@@ -117,8 +117,135 @@ def write_y4m(path, yuv, frames, width, height, fps, full_range=False):
     return len(head) + L * (6 + n)
 
 
+# ---- materials (include/fdm_hip.h, fdm_render_set_material)
+FILTERS = {"nearest": 0, "bilinear": 1}
+# this project's own control points (position in [0, 1], (r, g, b)); "monotone": no channel ever falls along the table
+COLORMAPS = {
+    "grey": (((0.0, (0.0, 0.0, 0.0)), (1.0, (1.0, 1.0, 1.0))), True),
+    "heat": (((0.0, (0.0, 0.0, 0.0)), (0.375, (1.0, 0.0, 0.0)), (0.75, (1.0, 1.0, 0.0)), (1.0, (1.0, 1.0, 1.0))), True),
+    "jet": (((0.0, (0.0, 0.0, 0.5)), (0.125, (0.0, 0.0, 1.0)), (0.375, (0.0, 1.0, 1.0)), (0.625, (1.0, 1.0, 0.0)), (0.875, (1.0, 0.0, 0.0)),
+             (1.0, (0.5, 0.0, 0.0))), False),
+}
+
+
+def colormap(name, n=256):
+    """float32 [n, 3], 2 <= n <= 1024: the table `name` ("heat", "jet" or "grey") from COLORMAPS' control points, piecewise linear in
+    fp64 at i / (n - 1), rounded to fp32.  The end points are the first and the last control point exactly."""
+    if name not in COLORMAPS:
+        raise ValueError(f"colormap {name!r}: {', '.join(sorted(COLORMAPS))}")
+    if not 2 <= int(n) <= 1024:
+        raise ValueError(f"colormap: n = {n} (2 .. 1024)")
+    pts = COLORMAPS[name][0]
+    at = np.array([p[0] for p in pts], dtype=np.float64)
+    t = np.arange(int(n), dtype=np.float64) / float(int(n) - 1)
+    return np.stack([np.interp(t, at, np.array([p[1][c] for p in pts], dtype=np.float64)) for c in range(3)], axis=1).astype(np.float32)
+
+
+def uv_corners(vt, ft):
+    """A UV set with a face list of its own (FLAME's vt [T, 2] and ft [F, 3]) -> float32 [F, 3, 2], one (u, v) per face corner: what
+    Material.texture takes.  A vertex on a seam has one vt per side, so nothing is split."""
+    vt, ft = np.asarray(vt, dtype=np.float32), np.asarray(ft)
+    if vt.ndim != 2 or vt.shape[1] != 2 or ft.ndim != 2 or ft.shape[1] != 3 or not np.issubdtype(ft.dtype, np.integer):
+        raise ValueError(f"uv_corners takes vt [T, 2] and integer ft [F, 3], got {vt.shape} and {ft.dtype} {ft.shape}")
+    if len(ft) and (ft.min() < 0 or ft.max() >= len(vt)):
+        raise ValueError(f"uv_corners: ft names entries {int(ft.min())} .. {int(ft.max())} of {len(vt)}")
+    return np.ascontiguousarray(vt[ft])
+
+
+class Material:
+    """What stands where the base colour stands in the shade (fdm_render_set_material): state of a RenderPlan.  Made by
+    Material.vertex_colors(c [V, 3] >= 0), Material.scalar_map(a table [N, 3] or a colormap's name, lo, hi) -- the call then brings
+    scalars [B, L, V], mapped lo -> the table's first row, hi -> its last, NaN -> its first -- or Material.texture(image [Ht, Wt, 3]
+    uint8 with row 0 at the top, uv [F, 3, 2] per face corner (uv_corners), filter "bilinear" or "nearest"; no mip levels: a minified
+    texture aliases, samples=16 is the remedy), each with unlit=True for k = 1 in place of the Lambert sum; Material.base(unlit=) is
+    the base colour.  What is wrong with the arrays themselves is a ValueError here, before any plan.  `token` names the material to the
+    plan caches; the arrays are copied and kept read-only, so it cannot go stale."""
+
+    def __init__(self, kind, unlit=False, colors=None, lut=None, lo=0.0, hi=1.0, uv=None, image=None, filter="bilinear"):  # noqa: A002
+        self.kind, self.unlit = int(kind), bool(unlit)
+        self.colors = self.lut = self.uv = self.image = None
+        self.lo, self.hi, self.filter = np.float32(lo), np.float32(hi), str(filter).lower()
+        bad = lambda a: not np.isfinite(a).all() or (a < 0).any()  # noqa: E731
+        if self.kind == 1:
+            self.colors = np.array(colors, dtype=np.float32, order="C")
+            if self.colors.ndim != 2 or self.colors.shape[1] != 3 or bad(self.colors):
+                raise ValueError(f"vertex colours are [V, 3], finite and >= 0, got {self.colors.shape}")
+        elif self.kind == 2:
+            self.lut = colormap(lut) if isinstance(lut, str) else np.array(lut, dtype=np.float32, order="C")
+            if self.lut.ndim != 2 or self.lut.shape[1] != 3 or not 2 <= len(self.lut) <= 1024 or bad(self.lut):
+                raise ValueError(f"a colour table is [N, 3] with 2 <= N <= 1024, finite and >= 0, got {self.lut.shape}")
+            with np.errstate(all="ignore"):
+                span = self.hi - self.lo
+            if not (np.isfinite(self.lo) and np.isfinite(self.hi) and self.lo < self.hi and np.isfinite(span)):
+                raise ValueError(f"a scalar map's range is finite with lo < hi, got lo = {lo}, hi = {hi}")
+        elif self.kind == 3:
+            img = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or not (1 <= img.shape[0] <= 8192 and 1 <= img.shape[1] <= 8192):
+                raise ValueError(f"a texture is uint8 [Ht, Wt, 3] with 1 <= Wt, Ht <= 8192, got {img.dtype} {img.shape}")
+            self.image, self.uv = np.array(img, order="C"), np.array(uv, dtype=np.float32, order="C")
+            if self.uv.ndim != 3 or self.uv.shape[1:] != (3, 2):
+                raise ValueError(f"uv is [F, 3, 2], one pair per face corner (uv_corners makes it from vt and ft), got {self.uv.shape}")
+            if self.filter not in FILTERS:
+                raise ValueError(f"filter = {filter!r}: nearest or bilinear")
+        elif self.kind != 0:
+            raise ValueError(f"material kind {kind}: 0 base, 1 vertex colours, 2 scalar map, 3 texture")
+        d = hashlib.sha1()
+        for a in (self.colors, self.lut, self.uv, self.image):      # the material's own copies, read-only: the token stays true
+            if a is not None:
+                a.flags.writeable = False
+                d.update(repr(a.shape).encode() + a.tobytes())
+        self.token = (self.kind, self.unlit, float(self.lo), float(self.hi), self.filter if self.kind == 3 else "", d.hexdigest())
+
+    @classmethod
+    def base(cls, unlit=False):
+        return cls(0, unlit)
+
+    @classmethod
+    def vertex_colors(cls, c, unlit=False):
+        return cls(1, unlit, colors=c)
+
+    @classmethod
+    def scalar_map(cls, lut_or_name, lo, hi, unlit=False):
+        return cls(2, unlit, lut=lut_or_name, lo=lo, hi=hi)
+
+    @classmethod
+    def texture(cls, image, uv, filter="bilinear", unlit=False):  # noqa: A002
+        return cls(3, unlit, uv=uv, image=image, filter=filter)
+
+    def descriptor(self, V, F):
+        """The fdm_render_material of this material for a mesh of V vertices and F faces (it points into this object's arrays)."""
+        if self.kind == 1 and len(self.colors) != V:
+            raise ValueError(f"the material has {len(self.colors)} vertex colours, the mesh {V} vertices")
+        if self.kind == 3 and len(self.uv) != F:
+            raise ValueError(f"the material has uv for {len(self.uv)} faces, the mesh {F} faces")
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        h, w = self.image.shape[:2] if self.kind == 3 else (0, 0)
+        return RenderMaterial(self.kind, int(self.unlit), ptr(self.colors), ptr(self.lut), 0 if self.lut is None else len(self.lut), float(self.lo),
+                              float(self.hi), ptr(self.uv), ptr(self.image), int(w), int(h), FILTERS.get(self.filter, 0))
+
+
+def vertex_error(pred, gt):
+    """Per-vertex distance |pred - gt| on the device (fdm_op_vertex_dist): pred and gt float32 device tensors of one shape, [..., 3 V] (at
+    most three dimensions) or [B, L, V, 3] -> [..., V] float32: the scalars of an error heat map (Material.scalar_map)."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(gt, torch.Tensor)) or not pred.is_cuda or pred.dtype != torch.float32:
+        raise FdmError("vertex_error runs on float32 device tensors (no CPU fallback)")
+    if gt.shape != pred.shape or gt.dtype != pred.dtype or gt.device != pred.device:
+        raise ValueError(f"vertex_error: pred is {pred.dtype} {tuple(pred.shape)} on {pred.device}, gt {gt.dtype} {tuple(gt.shape)} on {gt.device}")
+    if pred.dim() < 1 or pred.dim() > 4 or (pred.dim() == 4 and pred.shape[-1] != 3) or (pred.dim() < 4 and pred.shape[-1] % 3) or not pred.numel():
+        raise ValueError(f"vertex_error takes [..., 3 V] or [B, L, V, 3], got {tuple(pred.shape)}")
+    lead = tuple(pred.shape[:-2]) + (int(pred.shape[-2]),) if pred.dim() == 4 else tuple(pred.shape[:-1]) + (int(pred.shape[-1]) // 3,)
+    a, b = pred.detach().contiguous(), gt.detach().contiguous()
+    V = lead[-1]
+    out = torch.empty(lead, dtype=torch.float32, device=pred.device)
+    with torch.cuda.device(pred.device):
+        check(lib().fdm_op_vertex_dist(a.data_ptr(), b.data_ptr(), out.data_ptr(), out.numel() // V, V, torch.cuda.current_stream(pred.device).cuda_stream))
+    return out
+
+
 def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1, yuv_matrix=709,
-               yuv_range="limited", yuv_layout="i420"):
+               yuv_range="limited", yuv_layout="i420", material=None):
+    if material is not None and not isinstance(material, Material):
+        raise ValueError(f"material= takes a render.Material, got {type(material).__name__}")
     ref = reference_lights()
     if isinstance(camera, str):
         camera = Camera.preset(camera)
@@ -129,7 +256,7 @@ def _arguments(camera, lights=None, ambient=None, base=None, background=(1.0, 1.
         raise FdmError(f"yuv_matrix = {yuv_matrix!r} (601 or 709), yuv_range = {yuv_range!r} (limited or full), yuv_layout = {yuv_layout!r} (i420 or nv12)")
     return dict(camera=camera, lights=np.ascontiguousarray(lt), ambient=float(ref["ambient"] if ambient is None else ambient),
                 base=three(ref["base"] if base is None else base), background=three(background), chunk_frames=int(chunk_frames),
-                samples=int(samples), yuv_matrix=int(yuv_matrix), yuv_range=rng, yuv_layout=lay)
+                samples=int(samples), yuv_matrix=int(yuv_matrix), yuv_range=rng, yuv_layout=lay, material=material)
 
 
 def _view_key(a):
@@ -137,14 +264,16 @@ def _view_key(a):
     cam = a["camera"]
     for x in (cam.numbers(), cam.R, cam.t, a["lights"], a["base"], a["background"]):
         d.update(x.tobytes())
-    return (cam.width, cam.height, a["ambient"], a["chunk_frames"], a["samples"], a["yuv_matrix"], a["yuv_range"], a["yuv_layout"], d.hexdigest())
+    key = (cam.width, cam.height, a["ambient"], a["chunk_frames"], a["samples"], a["yuv_matrix"], a["yuv_range"], a["yuv_layout"], d.hexdigest())
+    return key if a.get("material") is None else key + (a["material"].token,)      # (no material: the key it always was)
 
 
 def identity(faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1, yuv_matrix=709,
-             yuv_range="limited", yuv_layout="i420"):
-    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view, the sample count and the yuv settings among it)."""
+             yuv_range="limited", yuv_layout="i420", material=None):
+    """RenderPlan(...).key without making the plan: (V, digest of the faces, the view, the sample count and the yuv settings among it,
+    and with a material its token)."""
     return (int(V), hashlib.sha1(faces_array(faces).tobytes()).hexdigest()) + _view_key(_arguments(camera, lights, ambient, base, background, chunk_frames,
-                                                                                                    samples, yuv_matrix, yuv_range, yuv_layout))
+                                                                                                    samples, yuv_matrix, yuv_range, yuv_layout, material))
 
 
 class RenderPlan(HandoffPlan):
@@ -161,10 +290,12 @@ class RenderPlan(HandoffPlan):
     _PLANES = ("rgb", "depth", "face_ids", "alpha", "yuv")
 
     def __init__(self, faces, V, camera, lights=None, ambient=None, base=None, background=(1.0, 1.0, 1.0), chunk_frames=0, samples=1,
-                 yuv_matrix=709, yuv_range="limited", yuv_layout="i420", device="cuda:0"):
+                 yuv_matrix=709, yuv_range="limited", yuv_layout="i420", material=None, device="cuda:0"):
         super().__init__(device)
         self.faces, self.V = faces_array(faces), int(V)
-        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout)
+        self.view = _arguments(camera, lights, ambient, base, background, chunk_frames, samples, yuv_matrix, yuv_range, yuv_layout, material)
+        if material is not None:
+            material.descriptor(self.V, len(self.faces))      # (a material that does not fit the mesh: before the object is made)
         a = self.view
         cam = a["camera"]
         self.W, self.H = cam.width, cam.height
@@ -177,6 +308,8 @@ class RenderPlan(HandoffPlan):
             self.set_samples(a["samples"])
         if (a["yuv_matrix"], a["yuv_range"], a["yuv_layout"]) != (709, "limited", "i420"):
             self.set_yuv(a["yuv_matrix"], a["yuv_range"], a["yuv_layout"])
+        if material is not None:
+            self.set_material(material)
         self.key = identity(self.faces, self.V, **a)
 
     def arguments(self):
@@ -208,6 +341,16 @@ class RenderPlan(HandoffPlan):
         self.view = dict(self.view, samples=int(n))
         self.key = identity(self.faces, self.V, **self.view)
 
+    def set_material(self, material):
+        """The plan's material (a Material, or None: the base colour again; fdm_render_set_material).  The plan's key follows, as with
+        set_samples.  A scalar map makes forward() take scalars=."""
+        if material is not None and not isinstance(material, Material):
+            raise ValueError(f"set_material takes a render.Material or None, got {type(material).__name__}")
+        desc = None if material is None else material.descriptor(self.V, len(self.faces))
+        check(lib().fdm_render_set_material(self.h, None if desc is None else C.byref(desc)))
+        self.view = dict(self.view, material=material)
+        self.key = identity(self.faces, self.V, **self.view)
+
     def set_yuv(self, matrix=None, range=None, layout=None):  # noqa: A002 (the C key is "yuv_range")
         """The 4:2:0 planes of forward(yuv=True): matrix 601 or 709, range "limited" or "full", layout "i420" or "nv12" (None: as it is;
         fdm_render_set "yuv_matrix" / "yuv_range" / "yuv_layout").  The plan's key follows, as with set_samples."""
@@ -221,7 +364,7 @@ class RenderPlan(HandoffPlan):
         self.key = identity(self.faces, self.V, **self.view)
 
     def forward(self, positions, frames=None, template=None, fps=None, normals=None, depth=False, face_ids=False, out=None, rgb=True,
-                alpha=False, yuv=False):
+                alpha=False, yuv=False, scalars=None):
         """positions [B, L_max, 3 V] (or [L, 3 V]) fp32 on the plan's device -- vertices, or offsets with template [1 or B, 3 V] --, frames:
         L per clip (None: L_max), fps = (fps_in, fps_out) or None, normals [B, L_out_max, V, 3] fp32 (what to_mesh returns for the same
         frames; None: computed here by the same kernel) -> ImageFrames.  out: (images, depth, face_ids) tensors to write instead of
@@ -229,11 +372,22 @@ class RenderPlan(HandoffPlan):
         rgb=False, alpha=True or yuv=True choose the planes form (fdm_render_forward_planes): images only with rgb, alpha
         [B, L_out_max, H, W] uint8 coverage, yuv [B, L_out_max, 3 W H / 2] uint8 in the plan's matrix, range and layout (W and H even).
         out may also be a dict keyed rgb / depth / face_ids / alpha / yuv: the call then writes exactly its tensors, whatever the flags
-        say.  A call that makes rgb and neither alpha nor yuv, without a dict, is fdm_render_forward as before."""
+        say.  A call that makes rgb and neither alpha nor yuv, without a dict, is fdm_render_forward as before.
+        scalars [B, L_max, V] fp32 (or [L, V]): the field a scalar-map material draws, on the INPUT frames (resampled with the positions);
+        required with such a material, refused without one (ValueError)."""
         want = dict(rgb=rgb, depth=depth, face_ids=face_ids, alpha=alpha, yuv=yuv)
         dv = self.device
         x = offsets_batch(positions, self.V, dv)
         B, L_max = int(x.shape[0]), int(x.shape[1])
+        mat, sc = self.view.get("material"), None
+        if (mat is not None and mat.kind == 2) != (scalars is not None):
+            raise ValueError("scalars= goes with a scalar-map material (Material.scalar_map) and with no other: the plan has " +
+                             ("none" if mat is None else f"kind {mat.kind}") + (" and the call no scalars" if scalars is None else ""))
+        if scalars is not None:
+            sc = torch.as_tensor(scalars, dtype=torch.float32).to(dv)
+            if sc.numel() != B * L_max * self.V:
+                raise ValueError(f"scalars must be [{B}, {L_max}, {self.V}] (one per input frame and vertex), got {tuple(sc.shape)}")
+            sc = sc.reshape(B, L_max, self.V).contiguous()
         fr, (fi, fo) = frames_list(frames, B, L_max), fps_pair(fps)
         tp, rows = None, 0
         if template is not None:
@@ -275,9 +429,11 @@ class RenderPlan(HandoffPlan):
         head = (self.h, x.data_ptr(), fa, B, L_max, ptr(tp), rows, fi, fo, ptr(nr))
         with torch.cuda.device(dv):
             tail = (Lo, got, torch.cuda.current_stream(dv).cuda_stream)
-            if not isinstance(out, dict) and "rgb" in t and "alpha" not in t and "yuv" not in t:
+            if sc is not None:
+                check(lib().fdm_render_forward_material(*head, C.byref(RenderPlanes(*p)), *tail, sc.data_ptr()))
+            elif not isinstance(out, dict) and "rgb" in t and "alpha" not in t and "yuv" not in t:
                 check(lib().fdm_render_forward(*head, *p[:3], *tail))
             else:
                 check(lib().fdm_render_forward_planes(*head, C.byref(RenderPlanes(*p)), *tail))
-        self._keep = (x, tp, nr)      # read asynchronously on this stream
+        self._keep = (x, tp, nr, sc)      # read asynchronously on this stream
         return ImageFrames(t.get("rgb"), t.get("depth"), t.get("face_ids"), list(got), t.get("alpha"), t.get("yuv"))

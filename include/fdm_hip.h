@@ -1213,7 +1213,45 @@ int fdm_wrap_destroy(fdm_wrap* w);
  *       1 NV12 (default 0); any other value is FDM_ERR_ARG.
  *   Rows at or past a clip's L_out are zero bytes in alpha and yuv as in every other output (zeros, not video black).  The call keeps
  *   fdm_render_forward's checks, chunks, scratch and one-stream rule; a null `out`, or one whose five members are all null, is FDM_ERR_ARG.
- * Not built: textures, the metallic-roughness material, clipping, 4:2:2 / 4:4:4 or 10-bit output, video encoding.
+ * Materials (fdm_render_set_material).  A material is state of the object; it decides the colour m that stands
+ *   where `base` stands in step 5: c = m_c k.  Coverage, depth, keys, ties, the sample patterns, the NaN-takes-background rule, min(1, c),
+ *   the sample sum, the rounding to uint8, alpha, the yuv planes, depth, face, chunks and the clearing of the visibility buffer are as
+ *   above; an object with no material set runs the code it ran before and gives the same bytes.  b_i = (l_i w_i) / iw are step 5's
+ *   weights; "interpolated" means (b0 a0 + b1 a1) + b2 a2, each operation rounded, with the corners in the ORIENTED triangle's order:
+ *   where A < 0 swapped vertices 1 and 2, the attributes of corners 1 and 2 swap with them, as the normals do.
+ *   kind 0, base: m = base.
+ *   kind 1, vertex colours: colors [V, 3] fp32, finite and >= 0, fixed per object; m_c is the interpolated colour.
+ *   kind 2, scalar map: lut [n_lut, 3] fp32, 2 <= n_lut <= 1024, finite and >= 0; lo < hi, both finite, span = hi - lo rounded once to
+ *     fp32 on the host (finite); per call scalars [B, L_max, V] fp32 device on the INPUT frames, resampled to the output frames as the
+ *     positions are (l0 s[i0] + l1 s[i1] with fdm_mesh_frames' taps, no template; rows at or past frames[b] are never read).  Per vertex
+ *     of an output frame u_v = fmin(fmax((s_v - lo) / span, 0), 1), fmax and fmin returning the operand that is not NaN, so a NaN scalar
+ *     gives u = 0.  Per fragment: u interpolated, clamped to [0, 1] again the same way; x = u (float)(n_lut - 1); i = min((int)x, n_lut - 2);
+ *     f = x - (float)i; m_c = lut[i][c] + f (lut[i + 1][c] - lut[i][c]).  The scalar is interpolated and then mapped, not the colours,
+ *     so isolines are straight across a triangle.
+ *   kind 3, texture: uv [F, 3, 2] fp32, one (u, v) pair per face corner (seams need no vertex splitting), any bits allowed; texture
+ *     [tex_h, tex_w, 3] uint8, 1 <= tex_w, tex_h <= 8192, row 0 at the top; filter 0 nearest or 1 bilinear.  tu, tv are interpolated.  A
+ *     texel channel is (float)u8 / 255.f (a rounded division).  Bilinear: x = tu (float)tex_w - 0.5f, y = (1 - tv) (float)tex_h - 0.5f (v
+ *     points up, as in FLAME and OpenGL UV sets); x0 = floorf(x), fx = x - x0; the columns are (int)fmin(fmax(x0, 0), tex_w - 1) and the
+ *     same of x0 + 1 (clamp to edge), the rows likewise from y0 = floorf(y), fy = y - y0; top = t00 + fx (t01 - t00), bot = t10 + fx
+ *     (t11 - t10), m = top + fy (bot - top).  Nearest: column (int)fmin(fmax(floorf(tu tex_w), 0), tex_w - 1), row likewise from
+ *     (1 - tv) tex_h.  The clamps are made in float before any conversion: no index leaves the texture for any bits of uv, NaN and
+ *     infinities included.  Bilinear: a NaN or infinite coordinate makes fx or fy NaN, hence m NaN, hence the sample takes the
+ *     background by step 5's rule.  Nearest has no fx: a NaN coordinate reads column or row 0, an infinite one the edge it points to.  There are no mip levels (a limit): a
+ *     minified texture aliases, and samples = 16 is the remedy.
+ *   unlit = 1, for any kind: k = 1.0f in place of the Lambert sum (heat maps are usually wanted flat).
+ *   fdm_render_set_material(r, m) reads m's HOST arrays during the call and keeps none; NULL or kind 0 with unlit 0: back to base.
+ *   FDM_ERR_ARG (the object is left as it was): a null r, an unknown kind or filter, unlit not 0 or 1, a null array that the kind needs,
+ *   n_lut or a texture size out of range, lo >= hi, lo, hi, span, a colour or a table entry not finite, a negative colour or table entry.
+ *   Without a device the set validates and a later forward ends in FDM_ERR_STATE.  The call waits for the device before it frees the
+ *   tables it replaces.  fdm_render_forward and fdm_render_forward_planes draw objects of kinds 0, 1 and 3 (the material is object
+ *   state); on a kind-2 object they return FDM_ERR_STATE.  fdm_render_forward_material is fdm_render_forward_planes with one more
+ *   argument, scalars: FDM_ERR_ARG when it is null on a kind-2 object or not null on an object of another kind; u per (chunk row,
+ *   vertex) is 4 V more bytes of scratch per frame, counted in the default chunk.
+ * fdm_op_vertex_dist(a, b, out, rows, V, stream): out[r, v] = sqrtf((dx dx + dy dy) + dz dz) of a - b over [rows, 3 V] fp32 device, each
+ *   operation rounded, the square root correctly rounded: a per-vertex error field for a scalar map, made on the device.  FDM_ERR_ARG: a
+ *   null operand; FDM_ERR_SHAPE: rows or V < 1; FDM_ERR_STATE: no device.
+ * Not built: the metallic-roughness material, clipping, mip levels, normal maps, per-frame vertex colours, 4:2:2 / 4:4:4 or 10-bit
+ *   output, video encoding.
  * fdm_render_create validates without a device and fdm_render_forward then ends in FDM_ERR_STATE.  Every check is made before the first
  * launch: FDM_ERR_ARG (a null r / positions / rgb, tmpl_rows not 0, 1 or B, a null template with tmpl_rows > 0, frame rates not finite
  * or negative; at create and set_view: a null array, F or V < 1, a face index outside [0, V), W or H outside 1 .. 4096, more than 8
@@ -1245,6 +1283,21 @@ int fdm_render_forward_planes(fdm_render* r, const float* positions, const int* 
 /* {yr, yg, yb, ur, ug, ub, vr, vg, vb, y0} of matrix = 601 or 709 and full_range = 0 or not into coeffs [10] HOST ints (no device
  * needed); FDM_ERR_ARG for any other matrix or a null coeffs. */
 int fdm_render_yuv_coeffs_host(int matrix, int full_range, int* coeffs /*[10]*/);
+/* Materials (the paragraph "Materials" above).  Callers detect them by the symbol. */
+typedef struct fdm_render_material {
+  int kind;                                   /* 0 base, 1 vertex colours, 2 scalar map, 3 texture */
+  int unlit;
+  const float* colors;                        /* HOST [V, 3], kind 1 */
+  const float* lut; int n_lut; float lo, hi;  /* HOST [n_lut, 3], kind 2 */
+  const float* uv;                            /* HOST [F, 3, 2], kind 3 */
+  const unsigned char* texture;               /* HOST [tex_h, tex_w, 3], kind 3 */
+  int tex_w, tex_h, filter;                   /* filter: 0 nearest, 1 bilinear */
+} fdm_render_material;
+int fdm_render_set_material(fdm_render* r, const fdm_render_material* m /* NULL or kind 0: back to base */);
+int fdm_render_forward_material(fdm_render* r, const float* positions, const int* frames, int B, int L_max, const float* tmpl, int tmpl_rows,
+                                double fps_in, double fps_out, const float* normals /*or NULL*/, const fdm_render_planes* out, int L_out_max,
+                                int* frames_out, void* stream, const float* scalars /* DEVICE [B, L_max, V] or NULL */);
+int fdm_op_vertex_dist(const float* a, const float* b, float* out, int rows, int V, void* stream);
 int fdm_render_destroy(fdm_render* r);
 
 /* Host-side tables (no device needed): the 12 GaussianDiffusion buffers in registration order, T floats each
