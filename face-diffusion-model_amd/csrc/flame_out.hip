@@ -8,17 +8,8 @@
 #include <cmath>
 #include <vector>
 
+#include "flame_obj.hpp"
 #include "flame_out.hpp"
-#include "host.hpp"
-
-struct fdm_flame : fdm::Handoff {         // lens: frames per clip
-  int V = 0, J = 0, NB = 0, expr_at = 0, NL = 0, chunks = 0;
-  std::vector<int> parents;
-  float *D = nullptr, *T = nullptr, *JT = nullptr, *JD = nullptr, *wts = nullptr, *lb = nullptr;   // device: the model
-  int *par = nullptr, *lv = nullptr;
-  float *xf = nullptr, *pf = nullptr, *cf = nullptr, *vid = nullptr;       // scratch of the call in flight
-  long long xf_cap = 0, pf_cap = 0, cf_cap = 0, vid_cap = 0;
-};
 
 namespace {
 using namespace fdm;
@@ -82,6 +73,21 @@ void tables(const fdm_flame_model* m, float* D, long long ld, float* JT, float* 
 }
 
 }  // namespace
+
+namespace fdm {
+void flame_launch_pose(fdm_flame* F, const float* shape, int shape_rows, int NS, const float* expr, int NE, const float* pose, int L_max, long long rows,
+                       hipStream_t s) {
+  const long long tiles = (rows + ROW_TILE - 1) / ROW_TILE;
+  hipLaunchKernelGGL(flame_pose_kernel, dim3((unsigned)((tiles * ROW_TILE + 63) / 64)), dim3(64), 0, s, shape, shape_rows, NS, expr, NE, pose,
+                     (const int*)F->lens, L_max, (int)rows, F->J, F->expr_at, (const float*)F->JT, (const float*)F->JD, (const int*)F->par, F->xf, F->pf,
+                     F->cf);
+}
+void flame_launch_shape(fdm_flame* F, const float* shape, int NS, int shape_rows, hipStream_t s) {
+  const int ld = F->chunks * ROW_CHUNK;
+  hipLaunchKernelGGL(flame_shape_kernel, dim3((unsigned)((ld / 4 + 255) / 256), (unsigned)shape_rows), dim3(256), 0, s, (const float*)F->T,
+                     (const float*)F->D, ld, shape, NS, F->vid);
+}
+}  // namespace fdm
 
 extern "C" {
 
@@ -153,11 +159,8 @@ int fdm_flame_forward(fdm_flame* F, const float* shape, int NS, int shape_rows, 
   FCK(grow(F->mem, &F->cf, &F->cf_cap, tiles * NT * ROW_TILE));
   FCK(grow(F->mem, &F->vid, &F->vid_cap, (long long)shape_rows * ld));
   FCK(handoff_lens(*F, hl, s));
-  hipLaunchKernelGGL(flame_pose_kernel, dim3((unsigned)((tiles * ROW_TILE + 63) / 64)), dim3(64), 0, s, shape, shape_rows, NS, expr, NE, pose,
-                     (const int*)F->lens, L_max, (int)rows, J, F->expr_at, (const float*)F->JT, (const float*)F->JD, (const int*)F->par, F->xf, F->pf,
-                     F->cf);
-  hipLaunchKernelGGL(flame_shape_kernel, dim3((unsigned)((ld / 4 + 255) / 256), (unsigned)shape_rows), dim3(256), 0, s, (const float*)F->T,
-                     (const float*)F->D, ld, shape, NS, F->vid);
+  flame_launch_pose(F, shape, shape_rows, NS, expr, NE, pose, L_max, rows, s);
+  flame_launch_shape(F, shape, NS, shape_rows, s);
   FlameSkinArgs a;
   a.vid = F->vid; a.shape_rows = shape_rows; a.D = F->D; a.ld = ld;
   a.row_expr = F->expr_at; a.NE = NE; a.row_pose = F->NB; a.P = P;

@@ -25,19 +25,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fdm_hip.h"
+#include "flame_math.hpp"
 #include "handoff.hpp"
 
 namespace fdm {
 
 // (flame_skin_kernel's geometry is handoff.hpp's: ROW_CHUNK elements of 3V = 256 whole vertices and ROW_TILE rows per workgroup)
-constexpr int FLAME_JMAX = 8;
 constexpr int FLAME_NBMAX = 512;
 constexpr int FLAME_NLMAX = 256;
-
-// ((a0 b0 + a1 b1) + a2 b2), every operation rounded
-__device__ __forceinline__ float flame_dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
-  return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
-}
 
 // shape [shape_rows][NS], expr [rows][NE], pose [rows][3 J]; lens [B]; JT [3 J], JD [NB][3 J], parents [J].
 // xf [tiles * ROW_TILE][J][12] (row-major 3 x 4 per joint), pf [rows][9 (J - 1)], cf [tiles][NE + 9 (J - 1)][ROW_TILE].  Dead rows: zeros.
@@ -60,42 +55,14 @@ __global__ __launch_bounds__(64) void flame_pose_kernel(const float* shape, int 
     if (row < rows) for (int i = 0; i < P; ++i) pf[(size_t)row * P + i] = 0.f;
     return;
   }
-  // joints: JT + sum_k shape_k JD_k + sum_k expr_k JD_(expr_at + k), k ascending, product and sum rounded
   float jf[3 * FLAME_JMAX];
-#pragma unroll
-  for (int i = 0; i < 3 * FLAME_JMAX; ++i) jf[i] = i < J3 ? JT[i] : 0.f;
-  const float* sh = shape + (size_t)(shape_rows == 1 ? 0 : b) * NS;
-  for (int k = 0; k < NS; ++k) {
-    const float c = sh[k];
-    const float* d = JD + (size_t)k * J3;
-#pragma unroll
-    for (int i = 0; i < 3 * FLAME_JMAX; ++i) if (i < J3) jf[i] = __fadd_rn(jf[i], __fmul_rn(c, d[i]));
-  }
-  const float* ex = expr + (size_t)row * NE;
-  for (int k = 0; k < NE; ++k) {
-    const float c = ex[k];
-    oc[(size_t)k * ROW_TILE] = c;
-    const float* d = JD + (size_t)(expr_at + k) * J3;
-#pragma unroll
-    for (int i = 0; i < 3 * FLAME_JMAX; ++i) if (i < J3) jf[i] = __fadd_rn(jf[i], __fmul_rn(c, d[i]));
-  }
+  flame_joints(jf, JT, JD, J3, shape + (size_t)(shape_rows == 1 ? 0 : b) * NS, NS, expr + (size_t)row * NE, NE, expr_at, oc);
 #pragma unroll
   for (int i = 0; i < 3 * FLAME_JMAX; ++i) if (i < J3) sJ[i][tid] = jf[i];
   const float* pr = pose + (size_t)row * J3;
   for (int j = 0; j < J; ++j) {
-    // Rodrigues: angle = |r + 1e-8|, axis = r / angle, R = I + sin K + (1 - cos) K K
-    const float rx = pr[3 * j], ry = pr[3 * j + 1], rz = pr[3 * j + 2];
-    const float ex_ = __fadd_rn(rx, 1e-8f), ey_ = __fadd_rn(ry, 1e-8f), ez_ = __fadd_rn(rz, 1e-8f);
-    const float angle = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(ex_, ex_), __fmul_rn(ey_, ey_)), __fmul_rn(ez_, ez_)));
-    const float x = __fdiv_rn(rx, angle), y = __fdiv_rn(ry, angle), z = __fdiv_rn(rz, angle);
-    const float s = sinf(angle), omc = __fsub_rn(1.f, cosf(angle));
-    const float xx = __fmul_rn(x, x), yy = __fmul_rn(y, y), zz = __fmul_rn(z, z);
-    const float xy = __fmul_rn(x, y), xz = __fmul_rn(x, z), yz = __fmul_rn(y, z);
-    const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
-    const float KK[9] = {-__fadd_rn(yy, zz), xy, xz, xy, -__fadd_rn(xx, zz), yz, xz, yz, -__fadd_rn(xx, yy)};
     float R[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) R[e] = __fadd_rn(__fadd_rn(e % 4 == 0 ? 1.f : 0.f, __fmul_rn(s, K[e])), __fmul_rn(omc, KK[e]));
+    flame_rodrigues(pr[3 * j], pr[3 * j + 1], pr[3 * j + 2], R);
     if (j >= 1) {
 #pragma unroll
       for (int e = 0; e < 9; ++e) {

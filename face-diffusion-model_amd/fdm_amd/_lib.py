@@ -233,6 +233,11 @@ SYMBOLS = {
     "fdm_flame_create": (ci, [C.POINTER(FlameModelDesc), vp, vp, ci, C.POINTER(vp)]),
     "fdm_flame_forward": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
     "fdm_flame_destroy": (ci, [vp]),
+    "fdm_flame_fit_create": (ci, [vp, vp, ci, ci, ci, vp, C.POINTER(vp)]),
+    "fdm_flame_fit_set": (ci, [vp, C.c_char_p, C.c_double]),
+    "fdm_flame_fit_forward": (ci, [vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "fdm_flame_fit_step": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "fdm_flame_fit_destroy": (ci, [vp]),
     "fdm_wrap_coords_host": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp]),
     "fdm_wrap_create": (ci, [vp, vp, ci, ci, vp, ci, vp, vp, C.POINTER(vp)]),
     "fdm_wrap_binding": (ci, [vp, vp, vp, vp]),

@@ -10,10 +10,17 @@ import numpy as np
 import torch
 
 from ._lib import FdmError, FlameModelDesc, check, lib
-from .handoff import HandoffPlan, frames_list
+from .handoff import HandoffPlan, cached_plan, frames_list
 
 # vertices [B, L_max, V, 3] fp32 (rows at or past frames[b] are zeros), landmarks [B, L_max, NL, 3] or None, frames per clip
 FlameFrames = namedtuple("FlameFrames", "vertices landmarks frames")
+
+# expression [B, L_max, n_expr], pose [B, L_max, 3 J] (fixed joints carry pose0), transl [B, L_max, 3] (zeros unless fitted), rms [B, L_max],
+# status [B, L_max] int32 (0, or 1 + the Cholesky column at which the row's step failed), frames per clip, vertices [B, L_max, V, 3] or None
+FlameFit = namedtuple("FlameFit", "expression pose transl rms status frames vertices")
+JOINT_NAMES = ("global", "neck", "jaw", "eye_l", "eye_r")      # the 5-joint FLAME chain
+FIT_PMAX = 128
+FIT_DEFAULTS = dict(iters=20, lam=1e-6, ridge_expr=0.0, ridge_pose=0.0, pivot_tol=2.0 ** -18)      # settings, not measurements
 
 KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights")
 FLAME_POSE = 15           # global, neck, jaw, left eye, right eye
@@ -234,6 +241,147 @@ class FlamePlan(HandoffPlan):
         self._keep = (pose, ex, sh, tr, xt)          # read asynchronously on this stream
         ff = FlameFrames(verts, lm, fr)
         return (ff, xf, pf) if xforms else ff
+
+    def fit_plan(self, n_expr=50, joints=("jaw",), transl=False, weights=None):
+        """The FlameFitPlan for one free set and weight vector, cached through handoff.cached_plan per (device, stream, MODEL digest, free
+        set, weights) -- by the model, not by this head object.  A second FlamePlan of the same model on the same device and stream
+        therefore gets the fit object bound to the FIRST head's native handle: the tables are the same, so the results are, but the
+        first head's device memory stays pinned for the life of the process and the two heads share one scratch (one stream at a time
+        for all of them)."""
+        jt = fit_joints(joints, self.J)
+        wk = None if weights is None else hashlib.sha1(np.ascontiguousarray(torch.as_tensor(weights).detach().cpu().numpy(), dtype=np.float32).tobytes()).hexdigest()
+        # one fit object per (device, stream, model digest, free set): it holds this head (which must outlive it), the head holds nothing back
+        return cached_plan((str(self.device), self.stream), "flame_fit", (self.key, int(n_expr), jt, bool(transl), wk),
+                           lambda: FlameFitPlan(self, n_expr, jt, transl, weights))
+
+    def _fit_inputs(self, target, shape, pose0, frames):
+        dv = self.device
+        y = torch.as_tensor(target).detach()
+        if y.dim() >= 2 and y.shape[-1] == 3 and y.shape[-2] == self.V:
+            y = y.reshape(*y.shape[:-2], -1)
+        y = self._dev(y, "target", 3 * self.V)
+        B, L = int(y.shape[0]), int(y.shape[1])
+        sh, NS, srows = None, 0, 1
+        if shape is not None:
+            sh = torch.as_tensor(shape).detach().to(dv, torch.float32)
+            sh = (sh.reshape(1, -1) if sh.dim() == 1 else sh).contiguous()
+            NS, srows = int(sh.shape[1]), int(sh.shape[0])
+        p0 = None if pose0 is None else self._dev(pose0, "pose0", 3 * self.J, B, L)
+        return y, B, L, sh, NS, srows, p0, frames_list(frames, B, L)
+
+    def fit(self, target, n_expr=50, joints=("jaw",), transl=False, shape=None, pose0=None, weights=None, iters=None, lam=None, ridge_expr=None,
+            ridge_pose=None, frames=None, return_vertices=False, pivot_tol=None):
+        """The reverse of forward() (fdm_flame_fit_forward): target [B, L_max, V, 3] or [B, L_max, 3 V] (or one
+        clip without the batch) absolute vertex positions -> FlameFit.  n_expr: the first n expression coefficients; joints: the free
+        joints by index or by name (JOINT_NAMES, 5-joint models); transl: fit a translation; shape as in forward (fixed); pose0
+        [B, L_max, 3 J]: the start, and the rotation of the joints that stay fixed; weights [V] >= 0; iters, lam, ridge_expr, ridge_pose:
+        pivot_tol (a row fails at a pivot not above pivot_tol x its damped diagonal; 0: the plain test pivot > 0): FIT_DEFAULTS (settings,
+        not measurements)."""
+        fp = self.fit_plan(n_expr, joints, transl, weights)
+        fp.set(iters=iters, lam=lam, ridge_expr=ridge_expr, ridge_pose=ridge_pose, pivot_tol=pivot_tol)
+        y, B, L, sh, NS, srows, p0, fr = self._fit_inputs(target, shape, pose0, frames)
+        dv = self.device
+        new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dv)  # noqa: E731
+        ex, ps, tr, rms, st = new(B, L, fp.n_expr), new(B, L, 3 * self.J), new(B, L, 3), new(B, L), new(B, L, dt=torch.int32)
+        verts = new(B, L, self.V, 3) if return_vertices else None
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        fa = (C.c_int * B)(*fr)
+        with torch.cuda.device(dv):
+            check(lib().fdm_flame_fit_forward(fp.h, y.data_ptr(), p(sh), NS, srows, p(p0), fa, B, L, ex.data_ptr(), ps.data_ptr(), tr.data_ptr(),
+                                              rms.data_ptr(), p(verts), st.data_ptr(), torch.cuda.current_stream(dv).cuda_stream))
+        self._keep = (y, sh, p0)                     # read asynchronously on this stream
+        return FlameFit(ex, ps, tr, rms, st, fr, verts)
+
+    def fit_step(self, target, expression, pose, transl=None, n_expr=50, joints=("jaw",), fit_transl=False, shape=None, pose0=None, weights=None,
+                 lam=None, ridge_expr=None, ridge_pose=None, frames=None):
+        """ONE Gauss-Newton step from given parameters (fdm_flame_fit_step; for tests and tools) -> dict(H [B, L, (P + 1)(P + 2) / 2],
+        delta [B, L, P], dX, dE, xforms, status)."""
+        fp = self.fit_plan(n_expr, joints, fit_transl, weights)
+        fp.set(lam=lam, ridge_expr=ridge_expr, ridge_pose=ridge_pose)
+        y, B, L, sh, NS, srows, p0, fr = self._fit_inputs(target, shape, pose0, frames)
+        dv, J, P = self.device, self.J, fp.P
+        ps = self._dev(pose, "pose", 3 * J, B, L)
+        ex = self._dev(expression, "expression", fp.n_expr, B, L) if fp.n_expr else None
+        tr = self._dev(transl, "transl", 3, B, L) if fp.transl else None
+        new = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dv)  # noqa: E731
+        out = dict(H=new(B, L, (P + 1) * (P + 2) // 2), delta=new(B, L, P), dX=new(B, L, 3 * len(fp.joints), J, 12), dE=new(B, L, fp.n_expr, J, 3),
+                   xforms=new(B, L, J, 12), status=new(B, L, dt=torch.int32))
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        fa = (C.c_int * B)(*fr)
+        with torch.cuda.device(dv):
+            check(lib().fdm_flame_fit_step(fp.h, y.data_ptr(), p(sh), NS, srows, p(p0), p(ex), ps.data_ptr(), p(tr), fa, B, L, out["H"].data_ptr(),
+                                           out["delta"].data_ptr(), out["dX"].data_ptr(), out["dE"].data_ptr(), out["xforms"].data_ptr(),
+                                           out["status"].data_ptr(), torch.cuda.current_stream(dv).cuda_stream))
+        self._keep = (y, sh, p0, ps, ex, tr)
+        return out
+
+
+def fit_joints(joints, J):
+    """joints: names of JOINT_NAMES (5-joint models) or indices -> ascending tuple of joint indices, refused when out of range or twice"""
+    if joints is None:
+        joints = ()
+    if isinstance(joints, (str, int)):
+        joints = (joints,)
+    out = []
+    for j in joints:
+        if isinstance(j, str):
+            if J != len(JOINT_NAMES) or j not in JOINT_NAMES:
+                raise FdmError(f"joint name {j!r}: names {JOINT_NAMES} are those of a 5-joint model, this one has {J} joints")
+            j = JOINT_NAMES.index(j)
+        j = int(j)
+        if j < 0 or j >= J:
+            raise FdmError(f"joint index {j} out of range 0..{J - 1}")
+        if j in out:
+            raise FdmError(f"joint {j} is given twice")
+        out.append(j)
+    return tuple(sorted(out))
+
+
+class FlameFitPlan(HandoffPlan):
+    """fdm_flame_fit_create on a FlamePlan's head for one free set (n_expr, joints, transl, weights).  It uses the head's tables and
+    scratch: one stream at a time for the pair.  It keeps the head alive; FlamePlan.fit_plan caches these through handoff.cached_plan."""
+
+    _destroy = "fdm_flame_fit_destroy"
+
+    def __init__(self, head, n_expr, joints, transl, weights):
+        super().__init__(head.device)
+        self.head = head
+        self.n_expr, self.joints, self.transl = int(n_expr), fit_joints(joints, head.J), bool(transl)
+        self.P = self.n_expr + 3 * len(self.joints) + 3 * int(self.transl)
+        NE = head.NB - head.model.expr_at
+        if self.n_expr < 0 or self.n_expr > NE:
+            raise FdmError(f"n_expr = {self.n_expr}: the model has NE = {NE} expression coefficients")
+        if self.P < 1 or self.P > FIT_PMAX:
+            raise FdmError(f"P = {self.P} free parameters (1..{FIT_PMAX})")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(torch.as_tensor(weights).detach().cpu().numpy(), dtype=np.float32).reshape(-1)
+            if w.shape[0] != head.V:
+                raise FdmError(f"weights must be [{head.V}], got {w.shape[0]}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0) or not np.any(w > 0):
+                raise FdmError("weights must be finite, not negative and not all zero")
+        self.weights = w
+        fj = (C.c_int * max(1, len(self.joints)))(*self.joints)
+        self._create("fdm_flame_fit_create", head.h, fj, len(self.joints), self.n_expr, int(self.transl), None if w is None else w.ctypes.data)
+        self._set = {}
+
+    def set(self, **kw):
+        """iters, lam, ridge_expr, ridge_pose, pivot_tol (None: the default)"""
+        for k, v in kw.items():
+            v = FIT_DEFAULTS[k] if v is None else v
+            if k == "iters":
+                if int(v) != v or int(v) < 1:
+                    raise FdmError(f"iters = {v} (a whole number >= 1)")
+            elif not (float(v) >= 0.0) or float(v) == float("inf"):
+                raise FdmError(f"{k} = {v} (finite and not negative)")
+            if self._set.get(k) != v:
+                check(lib().fdm_flame_fit_set(self.h, {"lam": b"lambda"}.get(k, k.encode()), float(v)))
+                self._set[k] = v
+
+    def columns(self):
+        """what column q of theta is: ('expr', k) | ('pose', 3 j + c) | ('transl', c)"""
+        return ([("expr", k) for k in range(self.n_expr)] + [("pose", 3 * j + c) for j in self.joints for c in range(3)] +
+                [("transl", c) for c in range(3 * int(self.transl))])
 
 
 def full_pose(pose6, J=5):

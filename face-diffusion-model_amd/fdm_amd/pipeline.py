@@ -235,6 +235,57 @@ def to_flame(pose, model, expression=None, shape=None, transl=None, extra=None, 
     return _flame_plan(model, device, landmarks).forward(pose, expression, shape, transl, extra, frames)
 
 
+FLAME_FIT_KEYS = ("model", "n_expr", "joints", "transl", "shape", "pose0", "weights", "iters", "lam", "ridge_expr", "ridge_pose", "pivot_tol", "return_vertices")
+
+
+def _flame_fit_check(flame_fit):
+    """flame_fit= of animate*: a dict with model and no key but FLAME_FIT_KEYS"""
+    if not isinstance(flame_fit, dict) or "model" not in flame_fit or set(flame_fit) - set(FLAME_FIT_KEYS):
+        raise ValueError(f"flame_fit= takes a dict with model and optionally {FLAME_FIT_KEYS[1:]}; got {sorted(flame_fit) if isinstance(flame_fit, dict) else type(flame_fit).__name__}")
+
+
+def _split_fit(ft, _=None):
+    """A batched FlameFit -> one per clip, each cut to its own frames"""
+    cut = lambda x, b, n: None if x is None else x[b:b + 1, :n]  # noqa: E731
+    return [type(ft)(cut(ft.expression, b, n), cut(ft.pose, b, n), cut(ft.transl, b, n), cut(ft.rms, b, n), cut(ft.status, b, n), [n], cut(ft.vertices, b, n))
+            for b, n in enumerate(ft.frames)]
+
+
+def _resample_rows(x, frames, fps):
+    """x [B, L, C] with frames per clip -> (y [B, Lo_max, C], frames out) by the mesh hand-off's frame rule (interp_taps: ops.linear_interp)"""
+    from . import ops
+    from .handoff import fps_pair, frames_out
+    fi, fo = fps_pair(fps)
+    fr = [int(x.shape[1])] * int(x.shape[0]) if frames is None else [int(f) for f in frames]
+    if not (fi > 0 and fo > 0 and fi != fo):
+        return x, frames
+    lo = [frames_out(f, fi, fo) for f in fr]
+    y = torch.zeros(x.shape[0], max(lo + [1]), x.shape[2], device=x.device)
+    for b, (n, m) in enumerate(zip(fr, lo)):
+        if n:
+            src, dst = x[b:b + 1, :n].contiguous(), torch.empty(1, m, x.shape[2], device=x.device)
+            ops.linear_interp(src, dst, 1, n, m, int(x.shape[2]))
+            y[b, :m] = dst[0]
+    return y, lo
+
+
+@torch.no_grad()
+def to_flame_params(offsets, model, template=None, frames=None, fps=None, device=None, **fit):
+    """Vertex offsets (or vertices, with template=None) -> flame.FlameFit: per frame the expression coefficients, joint rotations and
+    optional translation of the head `model` that reproduce offsets + template (flame.FlamePlan.fit; include/fdm_hip.h,
+    fdm_flame_fit_forward).  model: a flame.FlameModel, a flame.FlamePlan or a model file.  offsets: a device
+    tensor [B, L, 3 V] (or [L, 3 V]) with frames = L per clip -> one FlameFit; or a ragged LIST of clips -> a list, each cut to its own
+    frames and bit for bit what its own call returns.  template [1 or B, 3 V] (a list: one per clip).  fps = (in, out): the targets are
+    resampled by the mesh hand-off's frame rule before the fit.  **fit: n_expr, joints, transl, shape, pose0, weights, iters, lam,
+    ridge_expr, ridge_pose, return_vertices of FlamePlan.fit."""
+    def forward(x, fr, tp):
+        if tp is not None:
+            x = x + _template_rows(tp, x.shape[-1], x.device, 1, int(x.shape[0])).unsqueeze(1)
+        x, fr = _resample_rows(x.contiguous(), fr, fps)
+        return _flame_plan(model, x.device).fit(x, frames=fr, **fit)
+    return _per_clip("to_flame_params", offsets, frames, template, device, forward, _split_fit)
+
+
 @torch.no_grad()
 def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device=None):
     """Vertex offsets of the model's topology (or vertices, with template=None) -> the vertices [B, L, 3 Vt] of a mesh of ANOTHER
@@ -558,7 +609,14 @@ class _Outputs:
     rule where faces= or rig= asks for a hand-off that reads it (fps=: the pair itself, from a caller that holds it).  Calling it is
     the chain; `together` is the chain for the clips a SlotServer finishes in one step."""
 
-    def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None):
+    def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None, flame_fit=None):
+        if flame_fit is not None:
+            _flame_fit_check(flame_fit)
+            if flame is not None:
+                raise ValueError("flame_fit= with flame=: one poses the head and the other un-poses it; pass one of them")
+            if wrap is not None:
+                raise ValueError("flame_fit= with wrap=: the fit is of the model's own topology; fit first (to_flame_params), wrap the posed head after")
+        self.flame_fit = flame_fit
         if render is not None and faces is None:
             raise ValueError("render= needs faces=: the triangle list of the mesh that is drawn (after wrap=, the target's)")
         if isinstance(render, dict) and (render.get("error_to") is not None or render.get("scalars") is not None):
@@ -601,6 +659,8 @@ class _Outputs:
         The ragged form: `out` a LIST of decoded clips [1, L_b, V3] with `template` None or one per clip -> a list with one result per
         clip, from ONE rig, ONE head, ONE wrap and ONE mesh or render call over the unequal lengths, each result bit for bit its own
         call's.  flame (this group's, in place of the call's): pose / expression / transl [L', n] for all clips or a list with one per clip."""
+        if self.flame_fit is not None:                                                           # 0. the head's parameters stand where the vertices stood
+            return self._with_flame_fit(out, template, S, B)
         many, flame = isinstance(out, (list, tuple)), self.flame if flame is None else flame
         fit = None if self.rig is None else to_rig(out, self.rig, fps=self.fps)                  # 1. the fit, on the offsets as decoded
         if self.faces is None and fit is not None:
@@ -633,11 +693,34 @@ class _Outputs:
             return res
         return list(zip(res, fit)) if many else (res, fit)
 
+    def _with_flame_fit(self, out, template, S, B):
+        """flame_fit=: the flame.FlameFit of offsets + template (to_flame_params, at the model's own frame rate) stands where the vertices
+        stood; with faces= or rig= the rest of the chain runs as without the argument and the call returns (that result..., FlameFit)."""
+        many = isinstance(out, (list, tuple))
+        kw = {k: v for k, v in self.flame_fit.items() if k != "model"}
+        tp = template
+        if tp is not None and not many:
+            tp = _template_rows(tp, out.shape[-1], self.device, S, B)
+        ff = to_flame_params(out, self.flame_fit["model"], tp, device=self.device, **kw)
+        if self.faces is None and self.rig is None:
+            return ff
+        saved, self.flame_fit = self.flame_fit, None
+        try:
+            rest = self(out, template, S, B)
+        finally:
+            self.flame_fit = saved
+        pair = self.faces is not None and self.rig is not None      # (the rest is then (mesh or images, rig fit); results are namedtuples themselves)
+        if many:
+            return [(tuple(r) + (f,)) if pair else (r, f) for r, f in zip(rest, ff)]
+        return (tuple(rest) + (ff,)) if pair else (rest, ff)
+
     def together(self, clips, templates):
         """The chain for clips [1, L_b, V3] that were decoded together, `templates` holding one or None per clip -> one result per clip.
         They share the ragged form's calls where there is a call to share; with no hand-off asked for, or with a mesh or a wrap that
         reads templates and a template on some clips only, they go clip by clip."""
         given, reads_templates = [t is not None for t in templates], self.faces is not None or self.wrap is not None
+        if self.flame_fit is not None:
+            reads_templates = True
         if (not reads_templates and self.rig is None) or (reads_templates and any(given) and not all(given)):
             return [self(c.contiguous(), t) for c, t in zip(clips, templates)]
         return self(clips, templates if given[0] else None)
@@ -656,7 +739,7 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
 
     render (a render.RenderPlan or the dict of its arguments after faces and V: camera, lights, ambient, base, background,
@@ -714,7 +797,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     row 0 only: the other conditions differ from their sequential calls by that stream -- equal in distribution (the reference's
     sequential calls draw from one running generator), not bit for bit."""
     model, p, _, _ = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     # the default style is a row per clip; a style that was given counts with the rows it has
@@ -752,7 +835,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
                  style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None,
-                 wrap=None, render=None):
+                 wrap=None, render=None, flame_fit=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
 
     render: as animate(); each group's clips are drawn in ONE ragged render call and the first returned list holds a
@@ -793,7 +876,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     frames) or None per clip, or one track for all.  A group with a track in it is sampled and quantised with tracks throughout (a
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model, p, _, _ = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
     n = len(audios)
     wavs = _waveforms(audios, rate, device)
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
@@ -874,7 +957,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
     render: as animate(): the whole recording is drawn (a chunk of frames at a time inside the call).
     wrap: as animate(): the bound mesh follows the whole recording.
@@ -895,7 +978,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     wraps a ClassifierFreeSampleModel.  sampler / sampler_steps / eta: as animate() (the history of the multistep solver is the
     blended x0 in the long layout)."""
     model, p, cfg, scale = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     style = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B, device)
@@ -956,14 +1039,14 @@ class SlotServer:
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
-                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None):
+                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None, flame_fit=None):
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.model, p, self.cfg, self.scale = _unwrap(diffusion)
         self.p = p
         mat = _render_material(render) if render is not None else None
         if mat is not None and mat.kind == 2:
             raise ValueError("SlotServer draws materials of vertex colours and textures; a scalar map needs a field per request, which is not built")
-        self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render)     # once, not per finished clip
+        self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render, flame_fit=flame_fit)     # once, not per finished clip
         self.rig = self.outputs.rig
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
         self.batched_decodes = []                   # clips per batched decode, in call order
@@ -1437,6 +1520,40 @@ def add_flame_arguments(ap):
     ap.add_argument("--template_params", type=str, default=None, help="build-added: .npy of [1, NE + 6] FLAME parameters (expression, then global and jaw pose) for the template (with --flame_model)")
 
 
+def add_flame_fit_arguments(ap, has_flame_model):
+    """--flame_fit / --fit_joints / --fit_expr / --fit_iters of the demo command lines (to_flame_params of the saved frames); --flame_model
+    too where the preset's command line has none of its own."""
+    if not has_flame_model:
+        ap.add_argument("--flame_model", type=str, default=None, help="build-added: FLAME-type model file (.npz or a pickled dict of plain arrays: flame.FlameModel.load) for --flame_fit")
+        ap.add_argument("--flame_expr_at", type=int, default=None, help="build-added: index of the first expression coefficient (FLAME: 300; default the file's expr_at, else NB)")
+    ap.add_argument("--flame_fit", action="store_true",
+                    help="build-added: fit the head of --flame_model to every saved frame on the device and write <stem>_flame.npz (expression [1, L, n], "
+                         "pose [1, L, 3 J], transl [1, L, 3], rms [1, L]) beside <stem>.npy")
+    ap.add_argument("--fit_joints", type=str, default="jaw", help="build-added: free joints of --flame_fit, names (global neck jaw eye_l eye_r) or indices, comma-separated; 'none': expression only")
+    ap.add_argument("--fit_expr", type=int, default=50, help="build-added: expression coefficients fitted by --flame_fit")
+    ap.add_argument("--fit_iters", type=int, default=None, help="build-added: Gauss-Newton steps of --flame_fit (default: flame.FIT_DEFAULTS, a setting)")
+
+
+def flame_fit_arguments(a):
+    """flame_fit= of to_flame_params from the parsed flags, or None without --flame_fit."""
+    if not getattr(a, "flame_fit", False):
+        return None
+    if not a.flame_model:
+        raise ValueError("--flame_fit needs --flame_model")
+    from .flame import FlameModel
+    names = [] if a.fit_joints.strip().lower() in ("", "none") else [j.strip() for j in a.fit_joints.split(",")]
+    return dict(model=FlameModel.load(a.flame_model, expr_at=a.flame_expr_at), n_expr=a.fit_expr, joints=tuple(int(j) if j.lstrip("-").isdigit() else j for j in names),
+                iters=a.fit_iters)
+
+
+def save_flame_fit(fit_args, out, dst):
+    """<dst>_flame.npz: the FlameFit of the saved frames `out` [1, L, 3 V] (absolute vertices)"""
+    kw = {k: v for k, v in fit_args.items() if k != "model"}
+    ff = to_flame_params(out, fit_args["model"], **kw)
+    np.savez(dst + "_flame.npz", expression=ff.expression.cpu().numpy(), pose=ff.pose.cpu().numpy(), transl=ff.transl.cpu().numpy(), rms=ff.rms.cpu().numpy())
+    print(f"saved {dst}_flame.npz expression {tuple(ff.expression.shape)} pose {tuple(ff.pose.shape)} (rms max {float(ff.rms.max()):.3g}, {int((ff.status != 0).sum())} failed frames)")
+
+
 def flame_template(model, params=None, device="cuda:0", n_expr=50):
     """The MEAD template of samples/sample_diffusion_mead.py:76 from parameters: params [..., NE + 6] (expression, then global and jaw
     pose; None: zeros, the neutral face) -> [1, 3 V] on the device (flame.torch2mesh: zero shape, 4 decimals).  model: a
@@ -1500,7 +1617,9 @@ def demo_main(preset, argv=None):
     add_render_arguments(ap)
     if p.n_emo:        # MEAD: the template comes from FLAME parameters
         add_flame_arguments(ap)
+    add_flame_fit_arguments(ap, bool(p.n_emo))
     a = ap.parse_args(argv)
+    ffa = flame_fit_arguments(a)
     if a.render and not a.faces_file:
         raise ValueError("--render draws the model's triangles: it needs --faces_file")
     rig = rig_arguments(a)
@@ -1513,7 +1632,8 @@ def demo_main(preset, argv=None):
     template = None
     if os.path.exists(a.template_file) and a.template_file.endswith(".npy"):
         template = np.load(a.template_file).reshape(1, -1)
-    ft = flame_arguments(a, a.device)        # --flame_model: the template from parameters, in place of --template_file
+    # --flame_model on the MEAD command line: the template from parameters, in place of --template_file (elsewhere it serves --flame_fit alone)
+    ft = flame_arguments(a, a.device) if p.n_emo else None
     if ft is not None:
         template = ft
     wp, faces_t = wrap_arguments(a, np.load(a.faces_file) if a.faces_file else None, template, a.device)
@@ -1558,6 +1678,8 @@ def demo_main(preset, argv=None):
         print(f"saved {dst}_wrap.npy {tuple(wv.shape)}")
     if a.render:            # the saved frames drawn on the device: one image per frame of <stem>.npy
         save_frames(a, p, out, np.load(a.faces_file), dst)
+    if ffa is not None:     # the head's parameters of the saved frames: one fit per frame of <stem>.npy
+        save_flame_fit(ffa, out, dst)
     np.save(dst, out.detach().cpu().numpy())
     print(f"saved {dst}.npy {tuple(out.shape)}")
     return dst + ".npy"

@@ -1046,7 +1046,7 @@ int fdm_rig_set_temporal(fdm_rig* r, double smooth, const float* sweights);
  * the object's scratch first, which waits for the device.  An object holds ONE scratch: it serves one stream at a time.  Every check is
  * made before the first launch: FDM_ERR_ARG (null f / pose / verts, null shape with NS > 0 or expr with NE > 0, NS outside [0, expr_at],
  * NE outside [0, NB - expr_at], shape_rows not 1 or B, lmk without an embedding), FDM_ERR_SHAPE (B or L_max < 1, frames[b] outside
- * [0, L_max]).  Not built: the dynamic contour landmarks, fitting pose from vertices, fp16 output.  Call times: profiles/flame_out/README.md. */
+ * [0, L_max]).  Not built: the dynamic contour landmarks, fp16 output (fitting pose from vertices: fdm_flame_fit_* below).  Call times: profiles/flame_out/README.md. */
 typedef struct fdm_flame_model {
   int V, J, NB, expr_at;
   const float* v_template; const float* shapedirs; const float* posedirs; const float* j_regressor;
@@ -1059,6 +1059,65 @@ int fdm_flame_forward(fdm_flame* f, const float* shape, int NS, int shape_rows, 
                       const float* extra, const int* frames, int B, int L_max, float* verts, float* lmk, float* xforms, float* posefeat,
                       void* stream);
 int fdm_flame_destroy(fdm_flame* f);
+
+/* ------------------------------------------------------------------------------------------
+ * Parametric head, the reverse direction: vertices in, expression and pose parameters out.  Frames are
+ * independent.  Per live frame with target y [3 V] (absolute positions), fixed shape (per clip, or none) and the forward map F above,
+ * `iters` damped Gauss-Newton steps on
+ *     1/2 sum_v m_v |F(shape, expr, pose)_v + t - y_v|^2 + 1/2 ridge_expr |expr|^2 + 1/2 ridge_pose |pose_free - pose0_free|^2
+ * over theta = (the first n_expr expression coefficients; the axis-angle of the joints free_joints[0..n_free), in that order; the
+ * translation t when transl = 1), P = n_expr + 3 n_free + 3 transl in [1, 128], from theta = (0, pose0, 0).  Joints not in the free set
+ * keep pose0's rotation (zeros without pose0).  m = vertex_weights [V] (HOST, at create; NULL: ones).  There is no line search and no
+ * data-dependent branch: 2 + 5 iters launches, then the forward's own launches and one more for rms / verts.
+ * A step at theta (all fp32, fixed order, no atomics; tests/flame_fit_cases.py restates every line in numpy):
+ *   pose      the forward's pose stage at theta (its kernel): the transforms A_j, the pose feature, the blend coefficients.
+ *   deriv     per row, every operation rounded, 3-term sums as (a0 b0 + a1 b1) + a2 b2.  With r a free joint's axis-angle,
+ *             t2 = (r.x r.x + r.y r.y) + r.z r.z, K = hat(r), KK = r r^T - t2 I, S_c = e_c r^T + r e_c^T - 2 r_c I:
+ *               t2 >= 1e-2: th = sqrt(t2), a = sinf(th) / th, b = (1 - cosf(th)) / t2, a1 = (cosf(th) - a) / t2, b1 = (a - 2 b) / t2;
+ *               t2 <  1e-2 (the small-angle branch): a = 1 + t2 (-1/6 + t2 / 120), b = 1/2 + t2 (-1/24 + t2 / 720),
+ *                           a1 = -1/3 + t2 (1/30 - t2 / 840), b1 = -1/12 + t2 (1/180 - t2 / 6720);
+ *               dR_c = ((a hat(e_c) + b S_c) + (a1 r_c) K) + (b1 r_c) KK   (the closed-form derivative of I + a K + b K K).
+ *             Pose column (joint f, component c), joints ascending: dG_0 = [dR_c if f = 0, else 0 | 0]; for j >= 1, p = parents[j],
+ *             d = Jf_j - Jf_p: dG_j.R = G_p.R dR_c if j = f, else dG_p.R R_j; dG_j.t = dG_p.R d + dG_p.t; dA_j = [dG_j.R | dG_j.t - dG_j.R Jf_j].
+ *             Expression column k, e = JD[expr_at + k]: h_0 = e_0, h_j = G_p.R (e_j - e_p) + h_p, dE_j = h_j - G_j.R e_j.
+ *   columns   per vertex with T (the forward's blended transform), v (the forward's blended vertex before skinning), w its weights:
+ *             expression k: fma(T_c2, d.z, fma(T_c1, d.y, T_c0 d.x)) + E_c with d = D[expr_at + k] at the vertex and
+ *               E_c = w_0 dE_0c, then fma(w_j, dE_jc, E_c), j ascending -- exact for fixed rotations;
+ *             pose q: U = w_0 dA_0, fma(w_j, dA_j, U); fma(U_c2, v.z, fma(U_c1, v.y, U_c0 v.x)) + U_c3 -- the derivative of the skinning;
+ *               the derivative of the pose correctives is LEFT OUT (the Gauss-Newton approximation; a zero residual is still a fixed point);
+ *             translation: the identity.  Residual r_c = (forward_c [+ t_c]) - y_c, the forward's own operation sequence.
+ *   normal    with Z = [J | r] (P + 1 columns), per chunk of 256 vertices the upper triangle of Z^T M Z: s = fma(m Z_ia, Z_ib, s) over the
+ *             chunk's elements i = 3 v + c ascending from s = 0 (m Z_ia a rounded product); then the chunks' sums added in ascending chunk
+ *             order (rounded adds).  H = the P x P block, g = the last column.
+ *   solve     A = H + diag(rho_q + lambda) (rho + lambda rounded, then one rounded add), b_q = -(g_q + rho_q (theta_q - theta0_q)); rho is
+ *             ridge_expr on expression columns, ridge_pose on pose columns, 0 on the translation.  Right-looking Cholesky, columns
+ *             ascending: the row FAILS at column j when its pivot is not > pivot_tol x the damped diagonal A_jj before elimination (this also
+ *             catches NaN; pivot_tol = 0 is the plain test pivot > 0); l_jj = sqrt(pivot), l_ij = A_ij / l_jj, A_ik = fma(-l_ij, l_kj, A_ik) for j < k <= i.  y_j = b_j / l_jj,
+ *             b_i = fma(-l_ij, y_j, b_i), j ascending; x_j = y_j / l_jj, y_i = fma(-l_ji, x_j, y_i), j descending; theta_q += x_q.
+ *             A failed row sets status[row] = j + 1 and keeps its theta; it is evaluated again at the next step and fails again.
+ * Outputs (device): expr [B, L_max, n_expr], pose [B, L_max, 3 J] (all joints: fixed ones carry pose0), transl [B, L_max, 3] (zeros when
+ * the translation is not free), rms [B, L_max] = sqrt(S / sum m) with S the chunks' sums (ascending) of a 256-slot halving tree over
+ * m ((dx dx + dy dy) + dz dz) of d = verts - y, verts [B, L_max, V, 3] = fdm_flame_forward of the returned parameters (that call), status
+ * [B, L_max] ints.  Every output but expr and pose may be NULL (expr too when n_expr = 0).  Rows at or past frames[b] are zeros; target and pose0 rows there are
+ * never read (they may be NaN).
+ * fdm_flame_fit_create (HOST arrays, not kept; the head must outlive the fit and the two share one stream at a time: the fit uses the
+ * head's tables and scratch): FDM_ERR_ARG for P outside [1, 128], n_expr > NE = NB - expr_at, a joint index out of range or given twice,
+ * vertex weights negative, not finite or all zero.  fdm_flame_fit_set: "iters" (default 20, >= 1), "lambda" (1e-6), "ridge_expr" (0),
+ * "ridge_pose" (0), each finite and not negative, "pivot_tol" (2^-18, in [0, 1]): settings, not measurements.  fdm_flame_fit_forward: checks as fdm_flame_forward; no
+ * allocation after the first call at a given (B, L_max).  fdm_flame_fit_step: ONE step from the GIVEN parameters (copied; the caller's are
+ * left alone), for tests and tools: H [B, L_max, (P + 1)(P + 2) / 2] (the reduced upper triangle, row-major packed; dead rows zeros), delta
+ * [B, L_max, P], dX [B, L_max, 3 n_free, J, 12], dE [B, L_max, n_expr, J, 3], xforms [B, L_max, J, 12] (each may be NULL), status.
+ * Not built: fitting shape, robust losses, temporal smoothing of the parameters, the derivative of the pose correctives, the dynamic
+ * contour.  Call times are unmeasured: profiles/flame_fit/README.md. */
+typedef struct fdm_flame_fit fdm_flame_fit;
+int fdm_flame_fit_create(fdm_flame* f, const int* free_joints, int n_free, int n_expr, int transl, const float* vertex_weights, fdm_flame_fit** out);
+int fdm_flame_fit_set(fdm_flame_fit* fit, const char* key, double value);
+int fdm_flame_fit_forward(fdm_flame_fit* fit, const float* target, const float* shape, int NS, int shape_rows, const float* pose0, const int* frames,
+                          int B, int L_max, float* expr, float* pose, float* transl, float* rms, float* verts, int* status, void* stream);
+int fdm_flame_fit_step(fdm_flame_fit* fit, const float* target, const float* shape, int NS, int shape_rows, const float* pose0, const float* expr,
+                       const float* pose, const float* transl, const int* frames, int B, int L_max, float* H, float* delta, float* dX, float* dE,
+                       float* xforms, int* status, void* stream);
+int fdm_flame_fit_destroy(fdm_flame_fit* fit);
 
 /* ------------------------------------------------------------------------------------------
  * Wrap hand-off: the animated face drives a mesh of ANOTHER topology (a character head with its own vertex count and UV seams, another
