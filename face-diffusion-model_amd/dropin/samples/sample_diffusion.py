@@ -128,6 +128,7 @@ def main(dataset=None, argv=None):
                     help="build-added: the synthetic clips arrive as raw 48 kHz stereo int16 PCM and go through the device front end "
                          "(pipeline.prepare_audio: conversion, downmix, resampling, normalisation, 1 s of zeros); no file is read")
     pipeline.add_flame_arguments(ap)
+    pipeline.add_time_filter_arguments(ap)
     named = dataset is not None
     if named:
         pipeline.add_track_arguments(ap, presets.get(dataset))
@@ -146,6 +147,10 @@ def main(dataset=None, argv=None):
     if trk and a.all_styles:
         ap.error("--style_track / --emotion_track take one condition per clip: not with --all_styles")
     fast.update(trk)
+    # build-added: --time_filter: the decoded offsets of every clip smoothed along time on the device before they are saved
+    tf = pipeline.time_filter_arguments(a, p)
+    if tf is not None:
+        fast.update(time_filter=tf)
     steps = a.ddim_steps if a.ddim_steps is not None else (SHIPPED_DDIM_STEPS[dataset] or 100)
     all_styles = a.all_styles or (named and dataset == "vocaset" and not trk)      # samples/sample_diffusion_vocaset.py:71 loops every one-hot
     # one clip, one condition per sampling call (the reference's bs = 1 loop): the step program's single-clip setting

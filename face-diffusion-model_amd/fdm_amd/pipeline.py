@@ -300,6 +300,57 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
                      lambda y, fr: [y[b:b + 1, :n] for b, n in enumerate(fr)])
 
 
+TIME_FILTER_KEYS = ("taps", "kind", "sigma", "seconds", "order", "radius", "edge", "strength")
+
+
+def _time_filter_arguments(time_filter, fps=None):
+    """time_filter= of animate* and to_filtered: a tfilter.TimeFilterPlan as it is, or the dict of its arguments after V (no key but
+    TIME_FILTER_KEYS) with seconds= in place of sigma= converted by the model's frame rate `fps`.  A ValueError for anything else."""
+    from .tfilter import TimeFilterPlan
+    if isinstance(time_filter, TimeFilterPlan):
+        return time_filter
+    if not isinstance(time_filter, dict) or set(time_filter) - set(TIME_FILTER_KEYS):
+        raise ValueError(f"time_filter= takes a tfilter.TimeFilterPlan or a dict with {TIME_FILTER_KEYS}; got "
+                         f"{sorted(time_filter) if isinstance(time_filter, dict) else type(time_filter).__name__}")
+    kw = dict(time_filter)
+    if kw.get("seconds") is not None:
+        if kw.get("sigma") is not None:
+            raise ValueError("time_filter= takes sigma= (frames) or seconds=, not both")
+        if not fps:
+            raise ValueError("time_filter=dict(seconds=) needs the model's frame rate: the preset states none, pass in_fps=")
+        kw["sigma"] = float(kw["seconds"]) * float(fps)
+    kw.pop("seconds", None)
+    return kw
+
+
+def _time_filter_plan(time_filter, V, device, fps=None):
+    """The time filter plan of `device`, the current stream and this filter (tfilter.TimeFilterPlan.key): a plan is used as it is where
+    it was made for this device and stream and made again from its arguments otherwise; a dict is digested to recognise it."""
+    from .tfilter import TimeFilterPlan, identity
+    dv, at = _on_stream(device)
+    given = _time_filter_arguments(time_filter, fps)
+    if isinstance(given, TimeFilterPlan):
+        if given.V != int(V):
+            raise FdmError(f"the time filter plan is for {given.V} vertices, the frames have {int(V)}")
+        return cached_plan(at, "tfilter", given.key, lambda: TimeFilterPlan(device=dv, **given.arguments()), given)
+    return cached_plan(at, "tfilter", identity(int(V), **given), lambda: TimeFilterPlan(int(V), device=dv, **given))
+
+
+@torch.no_grad()
+def to_filtered(offsets, time_filter, frames=None, fps=None, device=None):
+    """Vertex offsets (what the decoder writes) -> the same offsets smoothed along time by a zero-phase FIR filter, each clip at its own
+    length, in ONE device call (tfilter.TimeFilterPlan; include/fdm_hip.h, fdm_tfilter_forward; DESIGN.md section 2 item 27 states
+    every operation).  time_filter: a tfilter.TimeFilterPlan, or the dict of its arguments after V (taps= | kind="gaussian" with
+    sigma= frames or seconds= | kind="savgol" with radius= and order=; edge= "mirror" | "nearest"; strength= [V] in [0, 1], 0 keeps a
+    vertex's input bits); seconds= is converted with fps, the MODEL's frame rate.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V])
+    with frames = L per clip (None: all L; rows past a clip's frames come out as zeros); or a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V]
+    clips -> a list of [1, L_b, 3 V], one padded call, each clip bit for bit what its own call returns.  What a filter does to
+    perceptual quality or lip-sync metrics is unmeasured."""
+    return _per_clip("to_filtered", offsets, frames, None, device,
+                     lambda x, fr, _: _time_filter_plan(time_filter, x.shape[-1] // 3, x.device, fps).forward(x, fr),
+                     lambda y, fr: [y[b:b + 1, :n] for b, n in enumerate(fr)])
+
+
 # keys of a render= dict that choose outputs or bring a call's scalar field, not the plan
 _RENDER_OUTPUTS = ("depth", "face_ids", "alpha", "yuv", "scalars", "error_to")
 
@@ -607,9 +658,14 @@ class _Outputs:
     preset, the device and the eight output keywords: the combinations that return nothing are refused, a rig= / wrap= dict is
     digested and made into its plan (_bound_plan: not per group, not per finished clip), and fps is (fps_in, fps_out) by _mesh_fps's
     rule where faces= or rig= asks for a hand-off that reads it (fps=: the pair itself, from a caller that holds it).  Calling it is
-    the chain; `together` is the chain for the clips a SlotServer finishes in one step."""
+    the chain; `together` is the chain for the clips a SlotServer finishes in one step.  time_filter= (the last keyword) is stage 0:
+    the decoded offsets are filtered along time (to_filtered) before anything below reads them."""
 
-    def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None, flame_fit=None):
+    def __init__(self, p, device, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, fps=None, flame_fit=None,
+                 time_filter=None):
+        # the filter's arguments are checked here, before anything runs (seconds= by the model's frame rate); its plan is made at the
+        # first call, when the vertex count is known from the decoded frames
+        self.time_filter = None if time_filter is None else _time_filter_arguments(time_filter, in_fps or (p.fps if p is not None else None) or (fps[0] if fps else None))
         if flame_fit is not None:
             _flame_fit_check(flame_fit)
             if flame is not None:
@@ -659,7 +715,16 @@ class _Outputs:
         The ragged form: `out` a LIST of decoded clips [1, L_b, V3] with `template` None or one per clip -> a list with one result per
         clip, from ONE rig, ONE head, ONE wrap and ONE mesh or render call over the unequal lengths, each result bit for bit its own
         call's.  flame (this group's, in place of the call's): pose / expression / transl [L', n] for all clips or a list with one per clip."""
-        if self.flame_fit is not None:                                                           # 0. the head's parameters stand where the vertices stood
+        if self.time_filter is not None:                                                         # 0. the time filter: every output below reads the filtered offsets
+            first = out[0] if isinstance(out, (list, tuple)) else out
+            if first.is_cuda:        # the plan, once: later calls do not digest the dict again (a host tensor is refused below)
+                self.time_filter = _time_filter_plan(self.time_filter, first.shape[-1] // 3, first.device)
+            out = to_filtered(out, self.time_filter)
+        return self._chain(out, template, S, B, flame)
+
+    def _chain(self, out, template=None, S=1, B=1, flame=None):
+        """The chain of __call__ after the time filter."""
+        if self.flame_fit is not None:                                                           # the head's parameters stand where the vertices stood
             return self._with_flame_fit(out, template, S, B)
         many, flame = isinstance(out, (list, tuple)), self.flame if flame is None else flame
         fit = None if self.rig is None else to_rig(out, self.rig, fps=self.fps)                  # 1. the fit, on the offsets as decoded
@@ -706,7 +771,7 @@ class _Outputs:
             return ff
         saved, self.flame_fit = self.flame_fit, None
         try:
-            rest = self(out, template, S, B)
+            rest = self._chain(out, template, S, B)
         finally:
             self.flame_fit = saved
         pair = self.faces is not None and self.rig is not None      # (the rest is then (mesh or images, rig fit); results are namedtuples themselves)
@@ -739,8 +804,15 @@ def _hand_off_many(clips, templates, device, faces=None, mesh=None, rig=None, fp
 @torch.no_grad()
 def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, steps=None,
             ddim_steps=None, seed=0, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None):
+            rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None,
+            time_filter=None):
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
+
+    time_filter (a tfilter.TimeFilterPlan or the dict of its arguments after V: taps= | kind="gaussian" with sigma= frames or seconds= |
+    kind="savgol" with radius= and order=; edge=, strength= [V]): the decoded offsets are smoothed along time on the device (to_filtered)
+    BEFORE anything else reads them, at the model's own frame rate: the returned vertices, the mesh, wrap, render, rig and head
+    outputs all follow the filtered offsets; the returned latent is untouched.  What a filter does to perceptual quality or
+    lip-sync metrics is unmeasured.  None: every path as before, launch for launch.
 
     render (a render.RenderPlan or the dict of its arguments after faces and V: camera, lights, ambient, base, background,
     chunk_frames; depth=True / face_ids=True for those images too, alpha=True for the coverage plane, yuv="i420" | "nv12" for the
@@ -797,7 +869,7 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     row 0 only: the other conditions differ from their sequential calls by that stream -- equal in distribution (the reference's
     sequential calls draw from one running generator), not bit for bit."""
     model, p, _, _ = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit, time_filter=time_filter)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     # the default style is a row per clip; a style that was given counts with the rows it has
@@ -835,8 +907,10 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
 def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=None, emotion_one_hots=None, ddim_steps=None,
                  seed=0, device="cuda:0", max_batch=8, bucket=16, sampler=None, sampler_steps=20, eta=0.0, batch_stages=False,
                  style_track=None, emotion_track=None, rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None,
-                 wrap=None, render=None, flame_fit=None):
+                 wrap=None, render=None, flame_fit=None, time_filter=None):
     """A test set's clips (different durations) through ONE sampling call per group of `max_batch` clips.
+
+    time_filter: as animate(); each group's decoded clips are filtered in ONE ragged call, each at its own length.
 
     render: as animate(); each group's clips are drawn in ONE ragged render call and the first returned list holds a
     render.ImageFrames per clip.
@@ -876,7 +950,7 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
     frames) or None per clip, or one track for all.  A group with a track in it is sampled and quantised with tracks throughout (a
     clip without one rides its one-hot on every frame: the same bits); every result equals animate() on that clip."""
     model, p, _, _ = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit, time_filter=time_filter)
     n = len(audios)
     wavs = _waveforms(audios, rate, device)
     if batch_stages:      # one encoder call over all clips of the call, each at its own length inside the padded batch
@@ -957,8 +1031,10 @@ def animate_many(diffusion, autoencoder, audios, templates=None, id_one_hots=Non
 @torch.no_grad()
 def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, emotion_one_hot=None, ddim_steps=None, seed=0,
                  window=None, overlap=60, device="cuda:0", sampler=None, sampler_steps=20, eta=0.0, style_track=None, emotion_track=None,
-                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None):
+                 rate=None, faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, flame=None, wrap=None, render=None, flame_fit=None,
+                 time_filter=None):
     """rate: `audio` is ONE raw PCM clip at that sample rate, taken through the device front end first (as animate()).
+    time_filter: as animate(): the whole decoded recording is filtered once.
     render: as animate(): the whole recording is drawn (a chunk of frames at a time inside the call).
     wrap: as animate(): the bound mesh follows the whole recording.
     flame: as animate(): the whole recording's offsets pose the model's head (pose [L', 3 J] with L' >= L_total).
@@ -978,7 +1054,7 @@ def animate_long(diffusion, autoencoder, audio, template=None, id_one_hot=None, 
     wraps a ClassifierFreeSampleModel.  sampler / sampler_steps / eta: as animate() (the history of the multistep solver is the
     blended x0 in the long layout)."""
     model, p, cfg, scale = _unwrap(diffusion)
-    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit)
+    outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, flame, wrap, render, flame_fit=flame_fit, time_filter=time_filter)
     audio = _waveform(audio, rate, device)
     B = audio.shape[0]
     style = _condition(id_one_hot, p.n_style, _STYLE_DEFAULT, B, device)
@@ -1035,18 +1111,21 @@ class SlotServer:
     wrap: as animate(): every finished clip's vertices are those of the bound mesh ([1, L, 3 Vt], or what faces= makes of them).
 
     render: as animate(): results() yields a render.ImageFrames in place of the mesh.MeshFrames (faces= is required).  Its material= may be
-    vertex colours or a texture; a scalar map is refused (ValueError): per-request scalar fields are not built."""
+    vertex colours or a texture; a scalar map is refused (ValueError): per-request scalar fields are not built.
+
+    time_filter: as animate(): every finished clip's decoded offsets are filtered first.  The server's one filter applies to all its
+    requests (a filter per request is not built)."""
 
     def __init__(self, diffusion, autoencoder, slots=8, max_frames=None, ddim_steps=None, sampler=None, sampler_steps=20, eta=0.0,
                  device="cuda:0", batch_stages=False, long_frames=0, long_groups=4, overlap=60, samplers=0, bank_steps=0,
-                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None, flame_fit=None):
+                 faces=None, out_fps=None, mesh=None, in_fps=None, rig=None, wrap=None, render=None, flame_fit=None, time_filter=None):
         self.diffusion, self.ae, self.device = diffusion, autoencoder, device
         self.model, p, self.cfg, self.scale = _unwrap(diffusion)
         self.p = p
         mat = _render_material(render) if render is not None else None
         if mat is not None and mat.kind == 2:
             raise ValueError("SlotServer draws materials of vertex colours and textures; a scalar map needs a field per request, which is not built")
-        self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render, flame_fit=flame_fit)     # once, not per finished clip
+        self.outputs = _Outputs(p, device, faces, out_fps, mesh, in_fps, rig, None, wrap, render, flame_fit=flame_fit, time_filter=time_filter)     # once, not per finished clip
         self.rig = self.outputs.rig
         self.batch_stages = bool(batch_stages)      # step(): one decode for all clips that finish together (as animate_many)
         self.batched_decodes = []                   # clips per batched decode, in call order
@@ -1352,6 +1431,49 @@ def track_arguments(a, p, L):
     return out
 
 
+def add_time_filter_arguments(ap):
+    """--time_filter / --time_filter_seconds / --time_filter_edge / --time_filter_keep / --time_filter_keep_strength of the demo and
+    sampler command lines (the device time filter, to_filtered)."""
+    ap.add_argument("--time_filter", type=str, default=None,
+                    help="build-added: smooth the decoded offsets along time on the device before anything reads them: gaussian:SIGMA (frames) | "
+                         "savgol:RADIUS:ORDER.  Off by default; its effect on quality or lip-sync metrics is unmeasured")
+    ap.add_argument("--time_filter_seconds", type=float, default=None, help="build-added: a Gaussian time filter of that many seconds (by the model's frame rate)")
+    ap.add_argument("--time_filter_edge", type=str, default=None, choices=("mirror", "nearest"), help="build-added: the edge rule of the time filter (default mirror)")
+    ap.add_argument("--time_filter_keep", type=str, default=None,
+                    help="build-added: idx.npy, vertex indices that take the filter at --time_filter_keep_strength only (the lips keep their closures); 1 elsewhere")
+    ap.add_argument("--time_filter_keep_strength", type=float, default=0.0, help="build-added: the strength in [0, 1] on the vertices of --time_filter_keep (0: untouched)")
+
+
+def time_filter_arguments(a, p):
+    """time_filter= of animate() from the parsed flags (the dict of tfilter.TimeFilterPlan's arguments), or None without a filter."""
+    spec, seconds = getattr(a, "time_filter", None), getattr(a, "time_filter_seconds", None)
+    edge, keep = getattr(a, "time_filter_edge", None), getattr(a, "time_filter_keep", None)
+    if spec is None and seconds is None:
+        if edge is not None or keep is not None:
+            raise ValueError("--time_filter_edge / --time_filter_keep need --time_filter or --time_filter_seconds")
+        return None
+    if spec is not None and seconds is not None:
+        raise ValueError("--time_filter and --time_filter_seconds are two filters: give one of them")
+    if seconds is not None:
+        kw = dict(kind="gaussian", seconds=float(seconds))
+    else:
+        parts = spec.split(":")
+        try:
+            if parts[0] == "gaussian" and len(parts) == 2:
+                kw = dict(kind="gaussian", sigma=float(parts[1]))
+            elif parts[0] == "savgol" and len(parts) == 3:
+                kw = dict(kind="savgol", radius=int(parts[1]), order=int(parts[2]))
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"--time_filter {spec!r}: gaussian:SIGMA or savgol:RADIUS:ORDER") from None
+    kw["edge"] = edge or "mirror"
+    if keep is not None:
+        from .tfilter import strength_from_region
+        kw["strength"] = strength_from_region(p.V3 // 3, np.load(keep), float(getattr(a, "time_filter_keep_strength", 0.0)))
+    return kw
+
+
 def add_rig_arguments(ap):
     """--rig_file / --rig_ridge / --rig_sweeps / --rig_smooth of the demo command lines (the device rig hand-off, to_rig)."""
     ap.add_argument("--rig_file", type=str, default=None,
@@ -1618,8 +1740,10 @@ def demo_main(preset, argv=None):
     if p.n_emo:        # MEAD: the template comes from FLAME parameters
         add_flame_arguments(ap)
     add_flame_fit_arguments(ap, bool(p.n_emo))
+    add_time_filter_arguments(ap)
     a = ap.parse_args(argv)
     ffa = flame_fit_arguments(a)
+    tfa = time_filter_arguments(a, p)
     if a.render and not a.faces_file:
         raise ValueError("--render draws the model's triangles: it needs --faces_file")
     rig = rig_arguments(a)
@@ -1643,6 +1767,10 @@ def demo_main(preset, argv=None):
     fast = dict(sampler=a.sampler, sampler_steps=a.sampler_steps, eta=a.eta)
     # tracks cover every latent frame the audio can give (16 kHz, 320 samples per encoder frame); the calls take the frames they need
     fast.update(track_arguments(a, p, max(len(wav) // 320 // p.pair + 2, p.max_len)))
+    if tfa is not None:      # everything saved below follows the filtered offsets (seconds= by --in_fps or the preset's frame rate)
+        fast.update(time_filter=tfa)
+        if not a.faces_file:
+            fast.update(in_fps=a.in_fps)
     if a.faces_file:
         fast.update(faces=np.load(a.faces_file), out_fps=a.out_fps, in_fps=a.in_fps, mesh=dict(normals=a.save_normals), rig=rig)
     if rig is not None and not a.faces_file:        # the offsets come back bare: the rig is fitted to them, the template added after

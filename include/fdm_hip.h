@@ -1186,6 +1186,47 @@ int fdm_wrap_forward(fdm_wrap* w, const float* offsets, const int* frames, int B
 int fdm_wrap_destroy(fdm_wrap* w);
 
 /* ------------------------------------------------------------------------------------------
+ * Time filter hand-off: a zero-phase FIR filter of the decoded offsets along time, per clip at its own
+ * length, BEFORE any other hand-off reads them -- the VQ decoder writes every frame from its own code vector, so its output carries
+ * frame-to-frame jitter, and the mesh, wrap, render, rig and head hand-offs all read the same [B, L_max, 3 V] offsets.  What a given
+ * filter does to perceptual quality or to lip-sync metrics is UNMEASURED (there are no trained checkpoints here); it is off unless asked for.
+ * Inputs: x [B, L_max, N] fp32 device, N = 3 V; lens [B] HOST ints, 1 <= L_b <= L_max (NULL: L_max each); half-taps h[0..R] fp32,
+ *   0 <= R <= 32, the full kernel symmetric, h[-k] = h[k]; an edge rule; optionally a strength s [V] fp32, each in [0, 1].
+ * Edge index e(i) of a clip of L frames.  FDM_TFILTER_MIRROR: L == 1: 0; otherwise p = 2 (L - 1), m = ((i mod p) + p) mod p,
+ *   e = m < L ? m : p - m -- the end sample is not repeated, and the rule holds for any R against any L, clips shorter than the radius
+ *   included.  FDM_TFILTER_NEAREST: e = min(max(i, 0), L - 1).
+ * Filtered value of element (t, n) of a live frame, fp32, every operation rounded on its own (no contraction):
+ *     acc = h[0] x[t][n];  for k = 1 .. R:  acc = acc + h[k] (x[e(t - k)][n] + x[e(t + k)][n]);  f = acc
+ *   The pair is summed first: filtering a time-reversed clip gives the time-reversed result bit for bit.
+ * Output: without a strength y = f.  With the strength s_v of column n's vertex: y = x (a copy, -0.0 included) where s_v == 0; otherwise
+ *   d = f - x, y = x + s_v d, three rounded operations (s_v = 1 is NOT the call without a strength, bit for bit).
+ * Rows at or past L_b are written as zeros; input rows at or past L_b are never read (they may be NaN).  y may not overlap x (refused).
+ *   A clip's bits do not depend on the batch, on L_max or on a tile size: every element is the fixed chain above.  No atomics.
+ * Taps are built on the host in fp64 and handed over as fp32 (the caller rounds; any taps of its own are as good):
+ *   fdm_tfilter_taps_host, kind FDM_TFILTER_GAUSSIAN: w_k = exp(-k^2 / (2 sigma^2)) with sigma = param (finite, > 0), normalised so
+ *   that h0 + 2 sum h_k = 1; kind FDM_TFILTER_SAVGOL: the Savitzky-Golay smoothing taps of window 2 R + 1 and polynomial order param
+ *   in {2, 3, 4, 5}, the centre row of the least-squares fit (orders 2 and 3 share a row, as do 4 and 5; an order >= 2 R + 1 is
+ *   refused).  taps holds R + 1 doubles.  Rounded to fp32 their sum is 1 only to rounding: a constant comes back to within the
+ *   rounding bound of the chain above, not bit for bit, unless the taps are dyadic.
+ * fdm_tfilter_create validates without a device (forward then ends in FDM_ERR_STATE) and uploads taps [R + 1] and strength [V] (HOST
+ *   arrays, not read after the call); every launch of the object goes to `stream`: an object serves one stream at a time.  FDM_ERR_ARG:
+ *   V < 1, R outside [0, 32], a NaN or infinite tap, a strength outside [0, 1] or NaN, an unknown edge rule, a null pointer.
+ * fdm_tfilter_forward: ONE launch, never synchronises except to grow the lengths scratch.  Every check is made before it: FDM_ERR_ARG
+ *   (a null pointer, y overlapping x), FDM_ERR_SHAPE (B < 1, L_max < 1, a length outside [1, L_max]).  fdm_version() keeps its value:
+ *   callers detect the feature by the symbol.
+ * Not built: causal or adaptive filters (One-Euro) for streaming, asymmetric taps or velocity outputs, fp16 in or out, filtering
+ *   after the frame-rate step.  Call times: profiles/time_filter/README.md. */
+#define FDM_TFILTER_GAUSSIAN 0
+#define FDM_TFILTER_SAVGOL 1
+#define FDM_TFILTER_MIRROR 0
+#define FDM_TFILTER_NEAREST 1
+typedef struct fdm_tfilter fdm_tfilter;
+int fdm_tfilter_taps_host(int kind, int radius, double param, double* taps /*[radius + 1]*/);
+int fdm_tfilter_create(int V, int radius, const float* taps, const float* strength /*[V] or NULL*/, int edge, void* stream, fdm_tfilter** out);
+int fdm_tfilter_forward(fdm_tfilter* f, const float* x, const int* lens /*HOST [B] or NULL*/, int B, int L_max, float* y);
+int fdm_tfilter_destroy(fdm_tfilter* f);
+
+/* ------------------------------------------------------------------------------------------
  * Render hand-off: shaded image frames of the animated mesh.  The definition is this project's own: a
  * pinhole camera, exact integer coverage, a per-pixel maximum of 1 / depth, and a Lambert sum over directional lights.  It is not
  * pyrender's metallic-roughness material; there is no reference renderer to compare images with.  Everything on the device is fp32,
