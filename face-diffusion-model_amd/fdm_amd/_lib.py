@@ -112,6 +112,9 @@ MESH_INTERLEAVED, MESH_F16, MESH_NORMALS = 1, 2, 4      # fdm_mesh_forward flags
 WRAP_OFFSETS = 1      # fdm_wrap_forward flags
 TFILTER_GAUSSIAN, TFILTER_SAVGOL = 0, 1      # fdm_tfilter_taps_host kinds
 TFILTER_MIRROR, TFILTER_NEAREST = 0, 1       # fdm_tfilter_create edge rules
+TFILTER_EMA, TFILTER_ONE_EURO = 0, 1         # fdm_tfilter_create_recur kinds
+TFILTER_CAUSAL, TFILTER_ZERO_PHASE = 0, 1    # fdm_tfilter_create_recur directions
+TFILTER_NCOEFF = 8                           # floats of fdm_tfilter_recur_coeffs_host
 
 # public structs of include/fdm_hip.h -> their mirrors (sizes checked against the loaded library in lib())
 STRUCTS = {"fdm_sched_args": SchedArgs, "fdm_gemm_args": GemmArgs, "fdm_attn_args": AttnArgs, "fdm_ln_args": LnArgs,
@@ -249,6 +252,10 @@ SYMBOLS = {
     "fdm_tfilter_create": (ci, [ci, ci, vp, vp, ci, vp, C.POINTER(vp)]),
     "fdm_tfilter_forward": (ci, [vp, vp, vp, ci, ci, vp]),
     "fdm_tfilter_destroy": (ci, [vp]),
+    "fdm_tfilter_recur_coeffs_host": (ci, [ci, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "fdm_tfilter_create_recur": (ci, [ci, ci, vp, vp, ci, vp, C.POINTER(vp)]),
+    "fdm_tfilter_forward_state": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    "fdm_tfilter_set_prefetch": (ci, [vp, ci]),
     "fdm_render_create": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, vp, C.POINTER(vp)]),
     "fdm_render_set_view": (ci, [vp, vp, vp, vp, vp, ci, cf]),
     "fdm_render_set": (ci, [vp, C.c_char_p, ll]),

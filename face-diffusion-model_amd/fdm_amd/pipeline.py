@@ -301,18 +301,29 @@ def to_wrap(offsets, wrap, template=None, frames=None, offsets_out=False, device
 
 
 TIME_FILTER_KEYS = ("taps", "kind", "sigma", "seconds", "order", "radius", "edge", "strength")
+TIME_RECUR_KEYS = ("kind", "fps", "cutoff", "min_cutoff", "beta", "d_cutoff", "direction", "strength")      # kind="ema" | "one_euro"
 
 
 def _time_filter_arguments(time_filter, fps=None):
     """time_filter= of animate* and to_filtered: a tfilter.TimeFilterPlan as it is, or the dict of its arguments after V (no key but
-    TIME_FILTER_KEYS) with seconds= in place of sigma= converted by the model's frame rate `fps`.  A ValueError for anything else."""
-    from .tfilter import TimeFilterPlan
+    TIME_FILTER_KEYS) with seconds= in place of sigma= converted by the model's frame rate `fps`; for kind="ema" | "one_euro" no key but
+    TIME_RECUR_KEYS, fps= defaulting to the model's frame rate and direction= to "zero_phase".  A ValueError for anything else."""
+    from .tfilter import RECUR_KINDS, TimeFilterPlan
     if isinstance(time_filter, TimeFilterPlan):
         return time_filter
-    if not isinstance(time_filter, dict) or set(time_filter) - set(TIME_FILTER_KEYS):
-        raise ValueError(f"time_filter= takes a tfilter.TimeFilterPlan or a dict with {TIME_FILTER_KEYS}; got "
+    recur = isinstance(time_filter, dict) and time_filter.get("kind") in RECUR_KINDS
+    keys = TIME_RECUR_KEYS if recur else TIME_FILTER_KEYS
+    if not isinstance(time_filter, dict) or set(time_filter) - set(keys):
+        raise ValueError(f"time_filter= takes a tfilter.TimeFilterPlan or a dict with {keys}; got "
                          f"{sorted(time_filter) if isinstance(time_filter, dict) else type(time_filter).__name__}")
     kw = dict(time_filter)
+    if recur:
+        if kw.get("fps") is None:
+            if not fps:
+                raise ValueError(f"time_filter=dict(kind={kw['kind']!r}) needs the model's frame rate: the preset states none, pass in_fps=")
+            kw["fps"] = float(fps)
+        kw["direction"] = kw.get("direction") or "zero_phase"
+        return kw
     if kw.get("seconds") is not None:
         if kw.get("sigma") is not None:
             raise ValueError("time_filter= takes sigma= (frames) or seconds=, not both")
@@ -338,11 +349,13 @@ def _time_filter_plan(time_filter, V, device, fps=None):
 
 @torch.no_grad()
 def to_filtered(offsets, time_filter, frames=None, fps=None, device=None):
-    """Vertex offsets (what the decoder writes) -> the same offsets smoothed along time by a zero-phase FIR filter, each clip at its own
-    length, in ONE device call (tfilter.TimeFilterPlan; include/fdm_hip.h, fdm_tfilter_forward; DESIGN.md section 2 item 27 states
-    every operation).  time_filter: a tfilter.TimeFilterPlan, or the dict of its arguments after V (taps= | kind="gaussian" with
-    sigma= frames or seconds= | kind="savgol" with radius= and order=; edge= "mirror" | "nearest"; strength= [V] in [0, 1], 0 keeps a
-    vertex's input bits); seconds= is converted with fps, the MODEL's frame rate.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V])
+    """Vertex offsets (what the decoder writes) -> the same offsets smoothed along time by a zero-phase FIR filter or by a recurrence,
+    each clip at its own length, in ONE device call (tfilter.TimeFilterPlan; include/fdm_hip.h, fdm_tfilter_forward; DESIGN.md section
+    2 items 27 and 28 state every operation).  time_filter: a tfilter.TimeFilterPlan, or the dict of its arguments after V (taps= |
+    kind="gaussian" with sigma= frames or seconds= | kind="savgol" with radius= and order=; edge= "mirror" | "nearest"; or
+    kind="one_euro" with min_cutoff= Hz, beta= (it depends on the mesh's scale) and d_cutoff= Hz | kind="ema" with cutoff= Hz, either
+    with direction= "zero_phase" (the default: whole clips are filtered offline) | "causal"; strength= [V] in [0, 1], 0 keeps a
+    vertex's input bits); seconds= is converted with fps, the MODEL's frame rate, which is also the recurrences' fps= unless given.  offsets: a device tensor [B, L, 3 V] (or [L, 3 V])
     with frames = L per clip (None: all L; rows past a clip's frames come out as zeros); or a ragged LIST of [1, L_b, 3 V] / [L_b, 3 V]
     clips -> a list of [1, L_b, 3 V], one padded call, each clip bit for bit what its own call returns.  What a filter does to
     perceptual quality or lip-sync metrics is unmeasured."""
@@ -809,7 +822,8 @@ def animate(diffusion, autoencoder, audio, template=None, id_one_hot=None, emoti
     """audio [B, n] (processor-normalised) -> vertices [B, L, V3].  DDPM full chain by default, DDIM if ddim_steps.
 
     time_filter (a tfilter.TimeFilterPlan or the dict of its arguments after V: taps= | kind="gaussian" with sigma= frames or seconds= |
-    kind="savgol" with radius= and order=; edge=, strength= [V]): the decoded offsets are smoothed along time on the device (to_filtered)
+    kind="savgol" with radius= and order=; edge=, strength= [V]; or kind="one_euro" with min_cutoff=, beta=, d_cutoff= | kind="ema" with
+    cutoff=, in Hz, fps= defaulting to the model's frame rate and direction= to "zero_phase"): the decoded offsets are smoothed along time on the device (to_filtered)
     BEFORE anything else reads them, at the model's own frame rate: the returned vertices, the mesh, wrap, render, rig and head
     outputs all follow the filtered offsets; the returned latent is untouched.  What a filter does to perceptual quality or
     lip-sync metrics is unmeasured.  None: every path as before, launch for launch.
@@ -1432,11 +1446,14 @@ def track_arguments(a, p, L):
 
 
 def add_time_filter_arguments(ap):
-    """--time_filter / --time_filter_seconds / --time_filter_edge / --time_filter_keep / --time_filter_keep_strength of the demo and
-    sampler command lines (the device time filter, to_filtered)."""
+    """--time_filter / --time_filter_seconds / --time_filter_edge / --time_filter_direction / --time_filter_keep /
+    --time_filter_keep_strength of the demo and sampler command lines (the device time filter, to_filtered)."""
     ap.add_argument("--time_filter", type=str, default=None,
                     help="build-added: smooth the decoded offsets along time on the device before anything reads them: gaussian:SIGMA (frames) | "
-                         "savgol:RADIUS:ORDER.  Off by default; its effect on quality or lip-sync metrics is unmeasured")
+                         "savgol:RADIUS:ORDER | one_euro:MIN_CUTOFF:BETA[:D_CUTOFF] | ema:CUTOFF (cutoffs in Hz; BETA in Hz per (mesh unit per second): "
+                         "it depends on the mesh's scale).  Off by default; its effect on quality or lip-sync metrics is unmeasured")
+    ap.add_argument("--time_filter_direction", type=str, default=None, choices=("zero_phase", "causal"),
+                    help="build-added: one_euro / ema only: zero_phase (default: forward, then backward over the result) | causal (it lags)")
     ap.add_argument("--time_filter_seconds", type=float, default=None, help="build-added: a Gaussian time filter of that many seconds (by the model's frame rate)")
     ap.add_argument("--time_filter_edge", type=str, default=None, choices=("mirror", "nearest"), help="build-added: the edge rule of the time filter (default mirror)")
     ap.add_argument("--time_filter_keep", type=str, default=None,
@@ -1448,9 +1465,10 @@ def time_filter_arguments(a, p):
     """time_filter= of animate() from the parsed flags (the dict of tfilter.TimeFilterPlan's arguments), or None without a filter."""
     spec, seconds = getattr(a, "time_filter", None), getattr(a, "time_filter_seconds", None)
     edge, keep = getattr(a, "time_filter_edge", None), getattr(a, "time_filter_keep", None)
+    direction = getattr(a, "time_filter_direction", None)
     if spec is None and seconds is None:
-        if edge is not None or keep is not None:
-            raise ValueError("--time_filter_edge / --time_filter_keep need --time_filter or --time_filter_seconds")
+        if edge is not None or keep is not None or direction is not None:
+            raise ValueError("--time_filter_edge / --time_filter_direction / --time_filter_keep need --time_filter or --time_filter_seconds")
         return None
     if spec is not None and seconds is not None:
         raise ValueError("--time_filter and --time_filter_seconds are two filters: give one of them")
@@ -1463,11 +1481,24 @@ def time_filter_arguments(a, p):
                 kw = dict(kind="gaussian", sigma=float(parts[1]))
             elif parts[0] == "savgol" and len(parts) == 3:
                 kw = dict(kind="savgol", radius=int(parts[1]), order=int(parts[2]))
+            elif parts[0] == "one_euro" and len(parts) in (3, 4):
+                kw = dict(kind="one_euro", min_cutoff=float(parts[1]), beta=float(parts[2]))
+                if len(parts) == 4:
+                    kw["d_cutoff"] = float(parts[3])
+            elif parts[0] == "ema" and len(parts) == 2:
+                kw = dict(kind="ema", cutoff=float(parts[1]))
             else:
                 raise ValueError
         except ValueError:
-            raise ValueError(f"--time_filter {spec!r}: gaussian:SIGMA or savgol:RADIUS:ORDER") from None
-    kw["edge"] = edge or "mirror"
+            raise ValueError(f"--time_filter {spec!r}: gaussian:SIGMA, savgol:RADIUS:ORDER, one_euro:MIN_CUTOFF:BETA[:D_CUTOFF] or ema:CUTOFF") from None
+    if kw["kind"] in ("one_euro", "ema"):
+        if edge is not None:
+            raise ValueError("--time_filter_edge belongs to gaussian and savgol: a recurrence has no edge rule")
+        kw["direction"] = direction or "zero_phase"
+    else:
+        if direction is not None:
+            raise ValueError("--time_filter_direction belongs to one_euro and ema: an FIR filter is zero-phase")
+        kw["edge"] = edge or "mirror"
     if keep is not None:
         from .tfilter import strength_from_region
         kw["strength"] = strength_from_region(p.V3 // 3, np.load(keep), float(getattr(a, "time_filter_keep_strength", 0.0)))

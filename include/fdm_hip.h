@@ -1214,17 +1214,55 @@ int fdm_wrap_destroy(fdm_wrap* w);
  * fdm_tfilter_forward: ONE launch, never synchronises except to grow the lengths scratch.  Every check is made before it: FDM_ERR_ARG
  *   (a null pointer, y overlapping x), FDM_ERR_SHAPE (B < 1, L_max < 1, a length outside [1, L_max]).  fdm_version() keeps its value:
  *   callers detect the feature by the symbol.
- * Not built: causal or adaptive filters (One-Euro) for streaming, asymmetric taps or velocity outputs, fp16 in or out, filtering
- *   after the frame-rate step.  Call times: profiles/time_filter/README.md. */
+ * Not built: asymmetric taps or velocity outputs, fp16 in or out, filtering after the frame-rate step, a filter per request.  Call
+ *   times: profiles/time_filter/README.md.
+ *
+ * The recurrences: a one-pole low-pass (FDM_TFILTER_EMA) and the One Euro filter (FDM_TFILTER_ONE_EURO;
+ * Casiez, Roussel, Vogel, CHI 2012: a one-pole low-pass whose cutoff rises with the smoothed speed of the vertex, so a slow vertex is
+ * smoothed hard and a fast one passes almost untouched), causal with a state carried from call to call, or zero-phase.  Same x, lens,
+ * strength rule, zero rows and no-overlap rule as above; every operation is one fp32 operation rounded on its own.
+ * Constants, fdm_tfilter_recur_coeffs_host (device-free) -> coeffs [FDM_TFILTER_NCOEFF] = {k, c0, be, cd, fr, ad, a0, 0}:
+ *   k = (float)(fps / (2 pi)) with the division in fp64; c0 = (float)cutoff (ema) or (float)min_cutoff; be = (float)beta;
+ *   cd = (float)d_cutoff; fr = (float)fps; ad = cd / (cd + k) and a0 = c0 / (c0 + k) in fp32.  For FDM_TFILTER_EMA beta and d_cutoff
+ *   are not read and be = cd = ad = 0.  Cutoffs are in Hz, > 0; fps > 0; beta >= 0, in Hz per (mesh unit per second): a sensible value
+ *   depends on the mesh's scale.  What any setting does to perceptual quality or lip-sync metrics is UNMEASURED.
+ * ema, per column:  y_0 = x_0;  y_t = y_{t-1} + a0 (x_t - y_{t-1}).
+ * one_euro, per vertex (its three columns):  y_0 = x_0, dh_0 = 0;  for t >= 1, per column:  dx = (x_t - x_{t-1}) fr,
+ *   dh_t = dh_{t-1} + ad (dx - dh_{t-1});  per vertex:  s = sqrt((dh.x dh.x + dh.y dh.y) + dh.z dh.z), fc = c0 + be s, a = fc / (fc + k);
+ *   per column:  y_t = y_{t-1} + a (x_t - y_{t-1}).  x_{t-1} is the raw input, as in the paper.  A constant comes back bit for bit.
+ * FDM_TFILTER_CAUSAL: f = y (it lags).  FDM_TFILTER_ZERO_PHASE: the causal filter, then the same causal filter over the result walked
+ *   from frame L - 1 down to 0, starting afresh, each clip at its own L: flip(causal(flip(causal(x)))).
+ * Strength: s_v == 0 copies the input bits, otherwise out = x + s_v (f - x) against the ORIGINAL x (under zero-phase once, after the
+ *   second walk); the recurrence itself always runs on the unblended f.
+ * fdm_tfilter_create_recur returns an fdm_tfilter: fdm_tfilter_forward (one launch, 1 <= L_b <= L_max) and fdm_tfilter_destroy serve
+ *   both families.  FDM_ERR_ARG: an unknown kind or direction, a coefficient that is not finite, k, c0 or fr <= 0, be < 0, for one_euro
+ *   cd or ad <= 0, a strength outside [0, 1], a null pointer.
+ * fdm_tfilter_forward_state (causal only; FDM_ERR_ARG on an FIR object or on zero-phase): per clip seen [B] DEVICE ints (frames consumed
+ *   so far, 0 = fresh) and st [B][3][N] DEVICE fp32 (y_prev, x_prev, dh; ema reads and writes row 0 alone).  0 <= L_b <= L_max.  A clip with
+ *   seen > 0 continues exactly as if the frames had been contiguous: the chunks of a recording give the bits of the whole recording.  The
+ *   state is written back and L_b added to seen (a second small launch); a clip with L_b == 0 is untouched, its state included.
+ *   Nothing is read back.  Zero both arrays to start afresh.
+ * fdm_tfilter_set_prefetch: how many frames the walk loads ahead (1, 4, 8 or 16; 16 unless set).  A tuning knob: no bit depends on it. */
 #define FDM_TFILTER_GAUSSIAN 0
 #define FDM_TFILTER_SAVGOL 1
 #define FDM_TFILTER_MIRROR 0
 #define FDM_TFILTER_NEAREST 1
+#define FDM_TFILTER_EMA 0
+#define FDM_TFILTER_ONE_EURO 1
+#define FDM_TFILTER_CAUSAL 0
+#define FDM_TFILTER_ZERO_PHASE 1
+#define FDM_TFILTER_NCOEFF 8
 typedef struct fdm_tfilter fdm_tfilter;
 int fdm_tfilter_taps_host(int kind, int radius, double param, double* taps /*[radius + 1]*/);
 int fdm_tfilter_create(int V, int radius, const float* taps, const float* strength /*[V] or NULL*/, int edge, void* stream, fdm_tfilter** out);
 int fdm_tfilter_forward(fdm_tfilter* f, const float* x, const int* lens /*HOST [B] or NULL*/, int B, int L_max, float* y);
 int fdm_tfilter_destroy(fdm_tfilter* f);
+int fdm_tfilter_recur_coeffs_host(int kind, double fps, double cutoff_or_min_cutoff, double beta, double d_cutoff, float* coeffs /*[FDM_TFILTER_NCOEFF]*/);
+int fdm_tfilter_create_recur(int V, int kind, const float* coeffs /*[FDM_TFILTER_NCOEFF]*/, const float* strength /*[V] or NULL*/, int direction,
+                             void* stream, fdm_tfilter** out);
+int fdm_tfilter_forward_state(fdm_tfilter* f, const float* x, const int* lens /*HOST [B] or NULL*/, int B, int L_max, float* st /*DEVICE [B][3][3V]*/,
+                              int* seen /*DEVICE [B]*/, float* y);
+int fdm_tfilter_set_prefetch(fdm_tfilter* f, int depth);
 
 /* ------------------------------------------------------------------------------------------
  * Render hand-off: shaded image frames of the animated mesh.  The definition is this project's own: a
