@@ -59,6 +59,13 @@ template <typename E> __device__ __forceinline__ void mma16(f32x4& acc, const u3
 //             residual plane in fp16's normal range; the two small products are summed in their own accumulator)
 // E = element type in memory, NP = planes, KV = operand kind of the packed K / V outputs of a QKV projection in that mode
 // (f16x3 feeds the split attention kernel plane pairs).
+// The fp32 -> kind conversion (store_opnd1 / store_opnd4 below; the same bits from both), word for word what
+// tests/test_opnd_convert_gpu.py holds the device to:
+//   bf16    round to nearest even; fp32 subnormals become bf16 subnormals; inf stays inf, overflow rounds to inf; a NaN stays a NaN
+//   fp16    c = clamp_f16(x), then round to nearest even with gradual underflow (zeros keep x's sign).  +-inf store +-65504; a
+//           quiet NaN stores -65504 and a signalling NaN +65504 (see clamp_f16): never a NaN, never an inf
+//   f16x3_t hi = fp16(c), lo = fp16((c - float(hi)) * 2048): both fp32 operations are exact, lo carries the one rounding, so
+//           |x - (hi + lo / 2048)| <= 2^-22 |x| + 2^-36; lo is +0 wherever c is an fp16 number (-0 and the clamped values included)
 // ---------------------------------------------------------------------------------------------------
 struct f16x3_t {};
 // one-plane 16-bit kinds (bf16, and fp16 = the split kind's hi plane alone): the throughput modes -- hardware exp / log forms in
@@ -96,7 +103,9 @@ template <typename V8> __device__ __forceinline__ void st8(void* p, const V8& v)
 #endif
 }
 // fp16 overflows at 65504: operand copies are clamped (one v_med3_f32; activations / weights on this path are O(1..100), the clamp keeps a stray
-// value -- or a NaN, which med3 maps to the lower bound -- finite)
+// value -- or a NaN -- finite).  For a NaN med3 returns min(min(x, lo), hi), and in IEEE mode min drops a quiet NaN but quiets and
+// returns a signalling one: a quiet NaN comes out as the lower bound, a signalling NaN as the UPPER bound (measured on the MI355X,
+// tests/test_opnd_convert_gpu.py).  Device arithmetic only ever produces quiet NaNs; a signalling one can arrive in host data.
 __device__ __forceinline__ float clamp_f16(float x) { return __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
 // Store 4 consecutive fp32 values v as operand kind T at dst (split kinds: hi plane at dst, lo plane at dst + lo_off).
 template <typename T> __device__ __forceinline__ void store_opnd4(void* dst, long long lo_off, const f32x4& v) {

@@ -361,7 +361,15 @@ int fdm_op_layernorm(const fdm_ln_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Small elementwise / layout operators.                                                      */
-/* dst_t[i] = (dtype) src_f32[i]; split dtypes: hi plane at dst, lo plane at dst + n elements */
+/* dst_t[i] = (dtype) src_f32[i]; split dtypes: hi plane at dst, lo plane at dst + n elements.  dst needs its element type's
+ * alignment only.  The rule per kind (the operand copies out_t / y_t / x_out_t of the other operators follow it too):
+ *   FDM_F32    the 32 bits are copied.
+ *   FDM_BF16   round to nearest even; fp32 subnormals become bf16 subnormals; inf stays inf and a finite value at or above
+ *              2^128 - 2^119 rounds to inf; a NaN stores a NaN (payload unspecified).
+ *   FDM_F16    clamp to [-65504, 65504] first (+-inf store +-65504, -0 stays -0), then round to nearest even with gradual underflow.
+ *              No NaN and no inf is ever stored: a quiet NaN stores -65504, a signalling NaN +65504.
+ *   FDM_F16X3  hi = fp16(c), c the clamped value as for FDM_F16; lo = fp16((c - hi) * 2048), the subtraction and the scaling exact in
+ *              fp32: |x - (hi + lo / 2048)| <= 2^-22 |x| + 2^-36 for |x| <= 65504.  lo = +0 where c is an fp16 number. */
 int fdm_op_cast(const float* src, void* dst, long long n, int dtype, void* stream);
 /* out[r, :] = act(in[r, :] + vec[:]) -- e.g. tau table = Mish(W_t^T + b_t), models/fdm_vocaset.py:71-72 */
 int fdm_op_bias_act(const float* in, const float* vec, float* out, long long rows, int d, int act, void* stream);
